@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- BLS12-381 pairings/sec through the HIP multi-pairing engine.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5|h2c]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5|h2c] [--full] [--dump-outputs DIR]
+
+A plain c2 / c3 run sets up, warms up, times the K steps and prints the line; --full adds the result checks and every
+other figure (multiply-add probe, clock samples, single-call latencies, c3's 8-GPU projection, CPU baselines, and after
+c2 the secondary configs).  --dump-outputs DIR writes the results of the last timed step (DIR/pairings.npy: B x 12 x 48
+bytes as float32, one Fq12 per verification); the inputs are PRF-seeded, the same in every run with the same arguments.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the script starts itself under
 `python -m torch.distributed.run` as a CHILD process (before anything touches a GPU) and
@@ -27,7 +32,7 @@ A "step" is one pass of the hot path over one batch already resident in HBM.
       ranks (strong scaling): per-rank sum, all-gather of one 100-byte record per rank, `world` additions.
   h2c hash 16 384 message hashes to G2.
 
-Every configuration checks its results (reference golden vectors where they exist, bilinearity /
+Every configuration (c2 / c3 with --full) checks its results (reference golden vectors where they exist, bilinearity /
 linearity identities evaluated by the engine itself otherwise) and aborts on a mismatch.
 Prints ONE JSON line on rank 0.
 """
@@ -60,6 +65,7 @@ PEAK_HBM_GBS = 8000.0
 LS_LINES = 68
 LS_LINE_BYTES_PER_PAIRING = LS_LINES * 336
 PEAK_MAD28_T = 34.1       # measured v_mad_i64_i32 rate, profiles/r03_fp28_microbench.txt
+DUMP_LIMIT_BYTES = 64 << 20
 N_ORDER = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
 
 
@@ -364,7 +370,8 @@ class ClockWatch:
 
 
 def timed_steps(env, args, step, engs, streams):
-    """W warm-up steps, [the multiply-add probe,] barrier, K timed steps, barrier: (seconds max over ranks, per-step ms, kernel times)"""
+    """W warm-up steps, [--full: the multiply-add probe,] barrier, K timed steps, barrier: (seconds max over ranks, per-step ms,
+    kernel times)"""
     torch = env.torch
     S = len(streams)
     torch.cuda.synchronize()
@@ -373,13 +380,14 @@ def timed_steps(env, args, step, engs, streams):
     torch.cuda.synchronize()
     # the roof in THIS process on THIS box: ~30 ms of v_mad_i64_i32 on every SIMD right before the timed steps (the chip is warm
     # and at its power-limited clock after the warm-up steps)
-    env.peak_now = engs[0].mad_probe(30.0) if not getattr(args, "no_peak_probe", False) else None
+    env.peak_now = engs[0].mad_probe(30.0) if args.full and not args.no_peak_probe else None
     env.barrier()
     for e in engs:
         e.timing_enable(True)         # HIP events around every kernel, on the stream it runs on
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
-    watch = ClockWatch(torch, env.local_dev)
-    watch.start()
+    watch = ClockWatch(torch, env.local_dev) if args.full else None
+    if watch:
+        watch.start()
     engs[0].mark(1)                   # (the device is idle here: everything dispatched until the closing mark is the timed region)
     t0 = time.perf_counter()
     for i in range(args.steps):
@@ -389,7 +397,7 @@ def timed_steps(env, args, step, engs, streams):
     env.barrier()
     dt = env.max_over_ranks(time.perf_counter() - t0)
     engs[0].mark(2)
-    env.clock = watch.stop()
+    env.clock = watch.stop() if watch else None
     step_ms = sorted(a.elapsed_time(b) for a, b in ev)
     ktimes = [t for e in engs for t in e.timing_read()]
     for e in engs:
@@ -418,6 +426,22 @@ def latency_probe(env, eng, t1, t2, n, stream, reps=4):
         stream.synchronize()
         ms.append(a.elapsed_time(b))
     return min(ms)
+
+
+def dump_outputs(d, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: each tensor as d/<name>.npy in float32 (its byte values are exact there).  One beyond its share of
+    `limit` keeps a fixed, seeded sample of its rows (first axis), their indices in d/<name>_rows.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    share = limit // len(arrays)
+    for name, t in arrays.items():
+        a = t.cpu().numpy().astype(np.float32)
+        if a.nbytes > share:
+            row = a.nbytes // a.shape[0]
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], share // (row + 8), replace=False))
+            np.save(os.path.join(d, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def run_pairing(env, args):
@@ -487,10 +511,15 @@ def run_pairing(env, args):
             shard[k].final_batch_dev(gath[k], world, B, outs[k], st)
 
     dt, step_ms, ktimes = timed_steps(env, args, step, engs, streams)
+    if args.dump_outputs and rank == 0:
+        # what the caller of the step receives: B Fq12 values of 12 coefficients, 48 big-endian bytes each (every rank holds them)
+        dump_outputs(args.dump_outputs, {"pairings": outs[(args.steps - 1) % S].view(B, 12, 48)})
     ws_after_steps = {"all_contexts": sum(e.workspace_bytes()["total"] for e in engs), "contexts": len(engs), "one_context": eng.workspace_bytes()}
-    results = [bytes(o.cpu().numpy()) for o in outs[:min(S, args.steps)]]
-    assert all(r == results[0] for r in results), "streams disagree"
-    per = [results[0][576 * v:576 * (v + 1)] for v in range(B)]
+    full = args.full
+    if full:
+        results = [bytes(o.cpu().numpy()) for o in outs[:min(S, args.steps)]]
+        assert all(r == results[0] for r in results), "streams disagree"
+        per = [results[0][576 * v:576 * (v + 1)] for v in range(B)]
     miller_ms = [ms for k, ms in ktimes if k == 0]
     reduce_ms = [ms for k, ms in ktimes if k == 1]
     fexp_ms = [ms for k, ms in ktimes if k == 2]
@@ -507,15 +536,15 @@ def run_pairing(env, args):
     else:
         launches = len(miller_ms)
         miller_avg = sum(miller_ms) / len(miller_ms)
-    # every rank's sums of a_i b_i per verification and its kernel time go to rank 0
-    sums = [sum(x * y for x, y in zip(a[v * n:(v + 1) * n], b[v * n:(v + 1) * n])) % N_ORDER for v in range(B)]
+    # every rank's sums of a_i b_i per verification (--full: for the check) and its kernel time go to rank 0
+    sums = [sum(x * y for x, y in zip(a[v * n:(v + 1) * n], b[v * n:(v + 1) * n])) % N_ORDER for v in range(B)] if full else None
     info = env.gather_objects({"rank": rank, "sums": sums, "k_miller_ms_avg": miller_avg, "pairs": n * B,
                                "device": torch.cuda.get_device_name(dev)})
     # latency views of the literal configs on this GPU alone: one 1025-pair verification, one 8192-pair shard
     # ONE step alone on an idle GPU with the kernel timers on: the durations of the few-wavefront kernels (products of
     # partials, Horner, final exponentiations) as they are, not stretched by the next step's chip-filling point chains
     solo = {}
-    if rank == 0 and env.dist is None:
+    if full and rank == 0 and env.dist is None:
         torch.cuda.synchronize()
         eng.timing_enable(True)
         step(0)
@@ -527,7 +556,7 @@ def run_pairing(env, args):
             solo[names.get(kind, str(kind))] = solo.get(names.get(kind, str(kind)), 0.0) + ms
     eng.set_mp_threshold(4096)
     lat = {}
-    if rank == 0 and not args.no_latency:
+    if full and rank == 0 and not args.no_latency:
         # the throughput-against-batch curve of ONE call (the headline needs 524 800 pairs in flight per step): the literal
         # configs among them -- 1025 pairs = configs[1], 8192 = the per-GPU shard of configs[2], 65 536 = configs[2] on one GPU
         for m in (1, 2, 5, 64, 512, 1025, 2048, 4096, 8192, 16384, 65536, 262144, 1048576):
@@ -543,7 +572,7 @@ def run_pairing(env, args):
     # of 8 gathered partials (blsgpu_final_exp_product_batch_dev) -- so that the first measured SCALE line can be read
     # against a stated expectation; the all-gather of 8 x 576 bytes is a latency (assumed 0.05 ms, not measured here)
     projection = None
-    if c3 and rank == 0 and world == 1 and not args.no_latency:
+    if full and c3 and rank == 0 and world == 1 and not args.no_latency:
         shard_pairs, ranks8 = args.pairs_total // 8, 8
         x1, x2 = env.up(g1[:96 * shard_pairs]), env.up(g2[:192 * shard_pairs])
         p8 = torch.zeros(ranks8 * 144, dtype=torch.int32, device=dev)
@@ -571,30 +600,32 @@ def run_pairing(env, args):
     if rank == 0:
         total_pairs = sum(i["pairs"] for i in info) * args.steps
         value = total_pairs / dt
-        tot = [sum(i["sums"][v] for i in info) % N_ORDER for v in range(B)]
-        want = bilinear_expectation(eng, gen1, gen2, tot)
-        check = "bilinear-ok" if per == want else "MISMATCH"
-        if not c3 and n == 1025 and check != "MISMATCH" and world == 1:
-            # verification 0 = the batch whose result the reference produced
-            check = "golden+bilinear-ok" if per[0].hex() == gj["seeded"]["1025"]["out"] else "MISMATCH"
-        elif not c3 and check != "MISMATCH":
-            # verification 0 is the multi-pairing of the PRF pairs 0 .. world * n - 1 (rank r holds the slice
-            # [r n, (r + 1) n)): for 8192 / 65 536 pairs in all the reference produced its value
-            ref = os.path.join(gold, "pairing_seeded_%d.json" % (n * world))
-            if os.path.exists(ref):
-                with open(ref) as f:
-                    check = "reference-digest+bilinear-ok" if per[0].hex() == json.load(f)["out"] else "MISMATCH"
-        if c3 and check != "MISMATCH":
-            # the ONE multi-pairing of c3 is the reference's own for 8192 / 65 536 pairs (fixtures generated by
-            # importing the reference, tests/golden/make_golden.py seeded8192 / seeded65536): whatever the sharding
-            ref = os.path.join(gold, "pairing_seeded_%d.json" % args.pairs_total)
-            if os.path.exists(ref):
-                with open(ref) as f:
-                    check = "reference-digest+bilinear-ok" if per[0].hex() == json.load(f)["out"] else "MISMATCH"
-        if len(set(per)) != B:
-            check = "MISMATCH"                       # different batches must give different results
-        if check == "MISMATCH":
-            raise SystemExit("result mismatch -- bench invalid")
+        check = "not checked (bench.py --full checks the results)"
+        if full:
+            tot = [sum(i["sums"][v] for i in info) % N_ORDER for v in range(B)]
+            want = bilinear_expectation(eng, gen1, gen2, tot)
+            check = "bilinear-ok" if per == want else "MISMATCH"
+            if not c3 and n == 1025 and check != "MISMATCH" and world == 1:
+                # verification 0 = the batch whose result the reference produced
+                check = "golden+bilinear-ok" if per[0].hex() == gj["seeded"]["1025"]["out"] else "MISMATCH"
+            elif not c3 and check != "MISMATCH":
+                # verification 0 is the multi-pairing of the PRF pairs 0 .. world * n - 1 (rank r holds the slice
+                # [r n, (r + 1) n)): for 8192 / 65 536 pairs in all the reference produced its value
+                ref = os.path.join(gold, "pairing_seeded_%d.json" % (n * world))
+                if os.path.exists(ref):
+                    with open(ref) as f:
+                        check = "reference-digest+bilinear-ok" if per[0].hex() == json.load(f)["out"] else "MISMATCH"
+            if c3 and check != "MISMATCH":
+                # the ONE multi-pairing of c3 is the reference's own for 8192 / 65 536 pairs (fixtures generated by
+                # importing the reference, tests/golden/make_golden.py seeded8192 / seeded65536): whatever the sharding
+                ref = os.path.join(gold, "pairing_seeded_%d.json" % args.pairs_total)
+                if os.path.exists(ref):
+                    with open(ref) as f:
+                        check = "reference-digest+bilinear-ok" if per[0].hex() == json.load(f)["out"] else "MISMATCH"
+            if len(set(per)) != B:
+                check = "MISMATCH"                       # different batches must give different results
+            if check == "MISMATCH":
+                raise SystemExit("result mismatch -- bench invalid")
         # dominant kernel = the Miller kernel (all the per-pairing work): algorithmic MACs of one launch
         # over its average duration in the timed region (launches do not overlap each other, see step())
         ach = MAC_PER_PAIRING * n * B / (miller_avg * 1e-3) / 1e12
@@ -680,12 +711,12 @@ def run_pairing(env, args):
                                         "per pair and step (this design squares once per GROUP in the Horner kernel) and 300 MAC32 per Fq "
                                         "product (28-bit limbs execute 392); the two nearly cancel: executed_mad28_per_pairing / "
                                         "stage_frac_by_executed_work state what the two kernels really issue")
-        if not args.no_cpu_baseline and world == 1:
+        if full and not args.no_cpu_baseline and world == 1:
             cb = cpu_baseline(g1[:96 * min(n, 1025)], g2[:192 * min(n, 1025)], min(n, 1025), per[0] if n == 1025 else None)
             if not cb["matches_gpu"]:
                 raise SystemExit("CPU oracle and GPU disagree -- bench invalid")
             line["cpu_baseline"] = cb
-        if not c3 and world == 1 and not args.no_secondary:
+        if full and not c3 and world == 1 and not args.no_secondary:
             line["secondary"] = secondary(env, args, eng, gen1, gen2)
         return line
     return None
@@ -1228,7 +1259,7 @@ def dry_run(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=48)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 48 for c2 / c3, 3 for c4 / c5 / h2c)")
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--config", default="c2", choices=["c2", "c3", "c4", "c5", "h2c"])
     ap.add_argument("--pairs", type=int, default=PAIRS_PER_GPU, help="c2: pairs per GPU per verification")
@@ -1252,14 +1283,23 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="c2: skip the c3 / c4 / c5 / h2c runs after the timed region")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch path only (no GPU): form the process group, all-gather one 576-byte partial per rank over gloo, report")
+    ap.add_argument("--full", action="store_true",
+                    help="c2 / c3: besides the timed steps, the result checks, the multiply-add probe and clock samples, the single-call "
+                         "latencies, c3's 8-GPU projection, the CPU baselines and the secondary configs (the --no-* options thin this out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="c2 / c3: write the results of the last timed step as DIR/<name>.npy (float32)")
     args = ap.parse_args()
     args.streams_given = any(a == "--streams" or a.startswith("--streams=") for a in sys.argv[1:])
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
     if args.dry_run:
         return dry_run(args)
-    if args.config in ("c4", "c5", "h2c") and args.steps == 48:
-        args.steps = 3
+    if args.steps is None:
+        args.steps = 3 if args.config in ("c4", "c5", "h2c") else 48
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.dump_outputs and args.config not in ("c2", "c3"):
+        raise SystemExit("--dump-outputs: c2 / c3 only")
     env = Env(args)
     if env.world != args.gpus:
         raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, env.world))

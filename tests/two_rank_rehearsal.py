@@ -7,7 +7,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--no-latency", "--no-cpu-baseline", "--no-secondary"]
+COMMON = ["--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--full", "--no-latency", "--no-cpu-baseline", "--no-secondary"]
 RUNS = {
     # BASELINE configs[2]'s shape at 8192 pairs: ONE multi-pairing sharded two ways (4096 pairs per rank), one partial per
     # rank through the all-gather, the final exponentiation on both ranks; check = the reference's digest

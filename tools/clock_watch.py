@@ -1,5 +1,5 @@
 """Engine clock and package power of the GPU while a command runs (samples of rocm-smi every ~0.25 s):
-usage: python3 tools/clock_watch.py -- python3 bench.py --no-cpu-baseline --no-secondary --no-latency
+usage: python3 tools/clock_watch.py -- python3 bench.py --full --no-cpu-baseline --no-secondary --no-latency
 Prints the command's stdout, then one JSON line with the samples' min / median / max."""
 import json, re, statistics, subprocess, sys, threading, time
 cmd = sys.argv[sys.argv.index("--") + 1:]

@@ -8,25 +8,25 @@ O=gpurun_out/$R
 mkdir -p $O
 PART=${PART:-AB}
 if [[ $PART == *A* ]]; then
-timeout -k 10 300 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 300 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 echo "bench done"
-timeout -k 10 200 python bench.py --gpus 2 --backend gloo --steps 8 --warmup 2 > $O/bench_2rank_gloo_rehearsal.json 2> $O/bench_2rank.err
-timeout -k 10 200 python bench.py --force-process-group --no-cpu-baseline --no-latency > $O/bench_rccl_1rank_rehearsal.json 2> $O/bench_rccl_1rank.err
-timeout -k 10 200 python bench.py --config c3 --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_c3.json 2> $O/bench_c3.err
-timeout -k 10 200 python bench.py --config c3 --gpus 2 --backend gloo --steps 8 --warmup 2 > $O/bench_c3_2rank_gloo.json 2> $O/bench_c3_2rank.err
+timeout -k 10 200 python bench.py --full --gpus 2 --backend gloo --steps 8 --warmup 2 > $O/bench_2rank_gloo_rehearsal.json 2> $O/bench_2rank.err
+timeout -k 10 200 python bench.py --full --force-process-group --no-cpu-baseline --no-latency > $O/bench_rccl_1rank_rehearsal.json 2> $O/bench_rccl_1rank.err
+timeout -k 10 200 python bench.py --full --config c3 --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_c3.json 2> $O/bench_c3.err
+timeout -k 10 200 python bench.py --full --config c3 --gpus 2 --backend gloo --steps 8 --warmup 2 > $O/bench_c3_2rank_gloo.json 2> $O/bench_c3_2rank.err
 for c in c4 c5 h2c; do timeout -k 10 300 python bench.py --config $c > $O/bench_$c.json 2> $O/bench_$c.err; done
 echo "config lines done"
 # the timed region ALONE under the kernel trace (no latency probes, no secondary configs): per-kernel averages of this CSV are the bench's
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/kt -o kt --output-format csv -- python3 bench.py --steps 16 --warmup 4 --no-cpu-baseline --no-latency --no-secondary > $O/kt_bench.json 2> $O/kt.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/kt -o kt --output-format csv -- python3 bench.py --full --steps 16 --warmup 4 --no-cpu-baseline --no-latency --no-secondary > $O/kt_bench.json 2> $O/kt.err
 for c in c4 c5 h2c; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/kt_$c -o kt --output-format csv -- python3 bench.py --config $c --steps 2 > $O/kt_$c.json 2> $O/kt_$c.err
 done
 echo "kernel traces done"
 fi
 if [[ $PART == *B* ]]; then
-timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc_fetch -o f --output-format csv -- python3 bench.py --steps 4 --warmup 1 --streams 1 --no-cpu-baseline --no-latency --no-secondary > $O/pmc_fetch.json 2> $O/pmc_fetch.err
-timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc_write -o w --output-format csv -- python3 bench.py --steps 4 --warmup 1 --streams 1 --no-cpu-baseline --no-latency --no-secondary > $O/pmc_write.json 2> $O/pmc_write.err
-timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_LDS -d $O/pmc_sq -o s --output-format csv -- python3 bench.py --steps 4 --warmup 1 --streams 1 --no-cpu-baseline --no-latency --no-secondary > $O/pmc_sq.json 2> $O/pmc_sq.err
+timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc_fetch -o f --output-format csv -- python3 bench.py --full --steps 4 --warmup 1 --streams 1 --no-cpu-baseline --no-latency --no-secondary > $O/pmc_fetch.json 2> $O/pmc_fetch.err
+timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc_write -o w --output-format csv -- python3 bench.py --full --steps 4 --warmup 1 --streams 1 --no-cpu-baseline --no-latency --no-secondary > $O/pmc_write.json 2> $O/pmc_write.err
+timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_LDS -d $O/pmc_sq -o s --output-format csv -- python3 bench.py --full --steps 4 --warmup 1 --streams 1 --no-cpu-baseline --no-latency --no-secondary > $O/pmc_sq.json 2> $O/pmc_sq.err
 for c in c4 c5 h2c; do
   timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_LDS -d $O/pmc_$c -o p --output-format csv -- python3 bench.py --config $c --steps 1 > $O/pmc_$c.json 2> $O/pmc_$c.err || echo "pmc $c failed"
 done
