@@ -69,11 +69,13 @@ int blsgpu_ctx_reserve(blsgpu_ctx *ctx, size_t max_pairs);
 /* Bytes of device memory the context's grow-only workspace holds right now, by purpose (the high-water mark of the
  * calls made so far; the line-stream stage keeps 68 x 336 bytes of line records per pair of its largest call, the
  * counterpart of the n-arrays of mpz_t the reference mallocs per call, fields_t_c.pyx:2348-2388).  out[BLSGPU_WS_TOTAL]
- * is the sum.  No device call is made. */
+ * is the sum (which also counts the fixed-base G1 table and the HD derivation slice, blsgpu_g1_mul_gen /
+ * blsgpu_hd_children; they have no field of their own).  No device call is made. */
 enum { BLSGPU_WS_PARTIALS = 0, BLSGPU_WS_STAGING, BLSGPU_WS_LINES, BLSGPU_WS_LINE_PRODUCTS, BLSGPU_WS_FLAGS_AND_LISTS,
        BLSGPU_WS_GROUP_SUMS, BLSGPU_WS_SLOTS, BLSGPU_WS_TOTAL, BLSGPU_WS_FIELDS };
 int blsgpu_ctx_workspace_bytes(blsgpu_ctx *ctx, size_t out[BLSGPU_WS_FIELDS]);
-/* Wait for the context's enqueued work and free the buffers that larger ones replaced. */
+/* Wait for the context's enqueued work and free the buffers that larger ones replaced.  The fixed-base G1 table of
+ * blsgpu_g1_mul_gen stays (0.9 MB, built once): blsgpu_ctx_destroy frees it. */
 int blsgpu_ctx_trim(blsgpu_ctx *ctx);
 /* Batches of at least `pairs` pairs run the throughput-oriented Miller kernel
  * (several pairs per wavefront sharing one accumulator); smaller batches the
@@ -275,6 +277,44 @@ int blsgpu_g1_decompress(blsgpu_ctx *ctx, const uint8_t *in, size_t n, uint8_t *
 int blsgpu_g2_decompress(blsgpu_ctx *ctx, const uint8_t *in, size_t n, uint8_t *out, uint8_t *ok);
 int blsgpu_g1_decompress_dev(blsgpu_ctx *ctx, const void *d_in, size_t n, void *d_out, void *d_ok, void *stream);
 int blsgpu_g2_decompress_dev(blsgpu_ctx *ctx, const void *d_in, size_t n, void *d_out, void *d_ok, void *stream);
+
+/* Fixed-base multiplication by the generator:  out_i = (s_i mod n) G1 (+ A_i)  for n scalars at once -- the
+ * PrivateKey.get_public_key of the reference (keys.py:104-105, G1 * sk with the generator of ec.py:394-396) and, with A,
+ * the public derivation step sk_left.get_public_key().value + self.public_key.value (keys.py:292-293).  A scalar is 32 bytes
+ * big-endian, any value below 2^256 (reduced mod the group order on the device: the same point); its product is a sum of
+ * 32 entries of a table of d 2^(8w) G1 (8-bit windows, 0.9 MB) that the context builds on first use and keeps until
+ * blsgpu_ctx_destroy -- no doubling, one inversion per scalar (csrc/blsgpu_g1fix.hip).  The table is indexed by the
+ * scalar's digits: NOT constant-time (nor is the variable-base path of blsgpu_g1_msm).
+ * add: NULL (n_add = 0), one point added to every product (n_add = 1) or one per scalar (n_add = n); 96 bytes affine,
+ * (0, 0) = infinity.  out_aff: n x 96 bytes affine ((0, 0) for infinity); out_ser: n x 48 bytes, PublicKey.serialize()
+ * (ec.py:94-111: x big-endian with 0x80 when y > q // 2; 48 zero bytes for infinity); either may be NULL, not both.
+ * n == 0 writes nothing. */
+int blsgpu_g1_mul_gen(blsgpu_ctx *ctx, const uint8_t *scalars, size_t n, const uint8_t *add, size_t n_add, uint8_t *out_aff,
+                      uint8_t *out_ser);
+int blsgpu_g1_mul_gen_dev(blsgpu_ctx *ctx, const void *d_scalars, size_t n, const void *d_add, size_t n_add, void *d_out_aff,
+                          void *d_out_ser, void *stream);
+
+/* HD child derivation of n siblings of one parent (keys.py:167-316 of the reference): for every index i,
+ * i_left = hmac256(ser || be32(i) || 0, chain_code), i_right = hmac256(ser || be32(i) || 1, chain_code) (util.hmac256;
+ * ser = PublicKey.serialize() of parent_pk_aff, or for an index >= 2^31 in private mode the 32 bytes of parent_sk); the
+ * child's chain code is i_right, and
+ *   public mode (parent_sk NULL; ExtendedPublicKey.public_child, keys.py:276-296): child key (i_left mod n) G1 + parent key;
+ *   private mode (ExtendedPrivateKey.private_child, keys.py:191-215): child sk = (i_left + parent_sk) mod n into out_sk,
+ *   child key sk G1.
+ * Both HMACs run on the device (midstates of the key blocks computed once per call), the keys on blsgpu_g1_mul_gen's table.
+ * parent_pk_aff: 96 bytes affine (in private mode the parent sk's public key); parent_sk: 32 bytes big-endian or NULL.
+ * out_chain: n x 32 bytes; out_sk: n x 32 bytes (private mode; ignored in public mode); out_pk_aff (n x 96 bytes) and
+ * out_pk_ser (n x 48 bytes) as in blsgpu_g1_mul_gen, either may be NULL.  In public mode an index >= 2^31 fails the whole
+ * call with -EINVAL ("Cannot derive hardened children from public key") before anything is written.  Not constant-time. */
+int blsgpu_hd_children(blsgpu_ctx *ctx, const uint8_t chain_code[32], const uint8_t parent_pk_aff[BLSGPU_G1_BYTES],
+                       const uint8_t *parent_sk, const uint32_t *indices, size_t n, uint8_t *out_chain, uint8_t *out_sk,
+                       uint8_t *out_pk_aff, uint8_t *out_pk_ser);
+/* The same with the indices and outputs in device memory, enqueued on `stream`; chain_code, parent_pk_aff and parent_sk
+ * are host buffers.  Public mode first scans the indices on the device and synchronises the stream once to read the
+ * result of that check. */
+int blsgpu_hd_children_dev(blsgpu_ctx *ctx, const uint8_t chain_code[32], const uint8_t parent_pk_aff[BLSGPU_G1_BYTES],
+                           const uint8_t *parent_sk, const void *d_indices, size_t n, void *d_out_chain, void *d_out_sk,
+                           void *d_out_pk_aff, void *d_out_pk_ser, void *stream);
 
 /* Measurement aid (bench.py): when enabled, HIP events are recorded on the
  * launch stream around every kernel this context launches (up to 1024 launches

@@ -25,6 +25,7 @@ SYMBOLS = (
     "blsgpu_miller_loop_batch", "blsgpu_miller_loop_batch_dev", "blsgpu_line_eval_batch", "blsgpu_ctx_trim",
     "blsgpu_fq12_op_batch", "blsgpu_fq12_pow_batch", "blsgpu_ctx_set_mp3_threshold", "blsgpu_ctx_set_ls_threshold", "blsgpu_ctx_set_ls_teams", "blsgpu_ctx_set_bulk_event", "blsgpu_ctx_set_fexp_team_threshold", "blsgpu_ctx_set_fexp_trace", "blsgpu_ctx_set_fexpw_stamps", "blsgpu_debug_read_lines",
     "blsgpu_ctx_workspace_bytes", "blsgpu_verify_pipeline", "blsgpu_verify_pipeline_dev",
+    "blsgpu_g1_mul_gen", "blsgpu_g1_mul_gen_dev", "blsgpu_hd_children", "blsgpu_hd_children_dev",
 )
 
 _lib = None
@@ -105,6 +106,10 @@ def load_library(path=None):
         L.blsgpu_hash_to_g2_dev.argtypes = [vp, vp, sz, vp, vp]
         L.blsgpu_map_to_g2.argtypes = [vp, cp, sz, cp]
         L.blsgpu_map_to_g2_dev.argtypes = [vp, vp, sz, vp, vp]
+        L.blsgpu_g1_mul_gen.argtypes = [vp, cp, sz, cp, sz, vp, vp]
+        L.blsgpu_g1_mul_gen_dev.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp]
+        L.blsgpu_hd_children.argtypes = [vp, cp, cp, cp, vp, sz, vp, vp, vp, vp]
+        L.blsgpu_hd_children_dev.argtypes = [vp, cp, cp, cp, vp, sz, vp, vp, vp, vp, vp]
         L.blsgpu_timing_enable.argtypes = [vp, ctypes.c_int]
         L.blsgpu_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int), sz,
                                          ctypes.POINTER(sz)]
@@ -332,6 +337,52 @@ class Engine:
 
     def g2_msm(self, pts, scalars, k, groups=1):
         return self._msm(self.lib.blsgpu_g2_msm, 192, pts, scalars, k, groups)
+
+    def g1_mul_gen(self, scalars, add=None, n_add=0, aff=True, ser=True):
+        """(s_i mod n) G1 (+ A) for n scalars (n x 32 bytes big-endian, or ints below 2^256) on the fixed-base table;
+        add: None, one point (n_add = 1) or n points (n_add = n), 96 bytes affine each.
+        -> (n x 96 affine bytes or None, n x 48 serialised bytes or None)"""
+        sb = scalars if isinstance(scalars, (bytes, bytearray)) else b"".join(int(s).to_bytes(32, "big") for s in scalars)
+        if len(sb) % 32:
+            raise ValueError("need n x 32 scalar bytes")
+        n = len(sb) // 32
+        if n_add not in (0, 1, n) or len(add or b"") != 96 * n_add:
+            raise ValueError("add must hold 0, 1 or n points of 96 bytes")
+        if not (aff or ser):
+            raise ValueError("ask for at least one output")
+        oa = ctypes.create_string_buffer(max(1, 96 * n)) if aff else None
+        os_ = ctypes.create_string_buffer(max(1, 48 * n)) if ser else None
+        self._check(self.lib.blsgpu_g1_mul_gen(self.h, bytes(sb), n, bytes(add) if n_add else None, n_add, oa, os_), "blsgpu_g1_mul_gen")
+        return (oa.raw[:96 * n] if aff else None), (os_.raw[:48 * n] if ser else None)
+
+    def hd_children(self, chain_code, parent_pk_aff, parent_sk, indices, aff=True, ser=True):
+        """HD children of one parent (blsgpu_hd_children): parent_sk None = public derivation.
+        -> (n x 32 chain codes, n x 32 child keys or None, n x 96 affine keys or None, n x 48 serialised keys or None)"""
+        if len(chain_code) != 32 or len(parent_pk_aff) != 96 or (parent_sk is not None and len(parent_sk) != 32):
+            raise ValueError("chain code 32, parent key 96 (and private key 32) bytes")
+        n = len(indices)
+        if any(i < 0 or i >= 1 << 32 for i in indices):
+            raise OverflowError("child indices are 32-bit")           # (a c_uint32 array would wrap them silently)
+        idx = (ctypes.c_uint32 * max(1, n))(*indices)
+        chain = ctypes.create_string_buffer(max(1, 32 * n))
+        sk = ctypes.create_string_buffer(max(1, 32 * n)) if parent_sk is not None else None
+        oa = ctypes.create_string_buffer(max(1, 96 * n)) if aff else None
+        os_ = ctypes.create_string_buffer(max(1, 48 * n)) if ser else None
+        self._check(self.lib.blsgpu_hd_children(self.h, bytes(chain_code), bytes(parent_pk_aff),
+                                                None if parent_sk is None else bytes(parent_sk), idx, n, chain, sk, oa, os_),
+                    "blsgpu_hd_children")
+        return (chain.raw[:32 * n], sk.raw[:32 * n] if sk is not None else None, oa.raw[:96 * n] if aff else None,
+                os_.raw[:48 * n] if ser else None)
+
+    def g1_mul_gen_dev(self, d_scalars, n, d_out_aff, d_out_ser, stream=0, d_add=None, n_add=0):
+        self._check(self.lib.blsgpu_g1_mul_gen_dev(self.h, d_scalars, n, d_add, n_add, d_out_aff, d_out_ser, stream),
+                    "blsgpu_g1_mul_gen_dev")
+
+    def hd_children_dev(self, chain_code, parent_pk_aff, parent_sk, d_indices, n, d_out_chain, d_out_sk, d_out_pk_aff,
+                        d_out_pk_ser, stream=0):
+        self._check(self.lib.blsgpu_hd_children_dev(self.h, bytes(chain_code), bytes(parent_pk_aff),
+                                                    None if parent_sk is None else bytes(parent_sk), d_indices, n, d_out_chain,
+                                                    d_out_sk, d_out_pk_aff, d_out_pk_ser, stream), "blsgpu_hd_children_dev")
 
     def timing_enable(self, on=True):
         self._check(self.lib.blsgpu_timing_enable(self.h, int(on)), "blsgpu_timing_enable")

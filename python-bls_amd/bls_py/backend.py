@@ -46,6 +46,14 @@ class HipProvider:
     def g2_decompress(self, data: bytes):
         return self._eng.g2_decompress(data)
 
+    def g1_mul_gen(self, scalars: bytes, add=None, n_add: int = 0):
+        """(s_i mod n) G1 (+ A) -> (n x 96 affine bytes, n x 48 serialised bytes)"""
+        return self._eng.g1_mul_gen(scalars, add, n_add)
+
+    def hd_children(self, chain_code: bytes, parent_pk_aff: bytes, parent_sk, indices):
+        """-> (n x 32 chain codes, n x 32 child keys or None (public), n x 96 affine keys, n x 48 serialised keys)"""
+        return self._eng.hd_children(chain_code, parent_pk_aff, parent_sk, indices)
+
     # ---- the whole of BLS.verify's device work without a host round trip between its steps (bls.py:153-201) ----
     def verify_pipeline(self, neg_g1: bytes, sig: bytes, hashes: bytes, n: int, keys_affine=None, key_pts=None, key_scalars=None, k=0) -> bytes:
         """e(-G1, sig) * prod_i e(P_i, H(m_i)) for n message hashes (32 bytes each): blsgpu_verify_pipeline -- ONE upload,
@@ -60,7 +68,9 @@ def use(provider):
     miller_loop_batch(g1, g2, n, inf=None), line_eval_batch(r, q|None, p, n),
     g1_msm / g2_msm(pts, scalars|None, k, groups) -> (bytes, [is_inf]),
     map_to_g2(t: n x 192 bytes) -> n x 192 bytes,
-    g1_decompress / g2_decompress(bytes) -> (affine bytes, [accepted])."""
+    g1_decompress / g2_decompress(bytes) -> (affine bytes, [accepted]),
+    g1_mul_gen(scalars, add|None, n_add) -> (affine bytes, serialised bytes),
+    hd_children(chain_code, parent_pk_aff, parent_sk|None, indices) -> (chain codes, child keys|None, affine, serialised)."""
     global _provider
     _provider = provider
 

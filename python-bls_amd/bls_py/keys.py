@@ -1,5 +1,7 @@
-"""Key types (keys.py:17-164 of the reference): PublicKey = G1 point with a
-48-byte compressed form, PrivateKey = scalar mod n."""
+"""Key types (keys.py:17-316 of the reference): PublicKey = G1 point with a
+48-byte compressed form, PrivateKey = scalar mod n, and the HD keys
+ExtendedPrivateKey / ExtendedPublicKey, whose children are derived on the GPU
+many siblings at a time (blsgpu_hd_children)."""
 from copy import deepcopy
 from random import SystemRandom
 
@@ -110,6 +112,17 @@ class PrivateKey:
             self.__dict__["_pk_point"] = pt
         return PublicKey.from_g1(pt)
 
+    @staticmethod
+    def get_public_key_batch(private_keys):
+        """[sk.get_public_key() for sk in private_keys] in one GPU call on the fixed-base table (blsgpu_g1_mul_gen);
+        the keys come back with their serialisation."""
+        from . import backend
+        sks = list(private_keys)
+        if not sks:
+            return []
+        aff, ser = backend.get().g1_mul_gen(b"".join(sk.value.to_bytes(32, "big") for sk in sks), None, 0)
+        return [_pk_from_device(aff[96 * i:96 * (i + 1)], ser[48 * i:48 * (i + 1)]) for i in range(len(sks))]
+
     def __setattr__(self, name, v):
         if name == "value":
             self.__dict__.pop("_pk_point", None)
@@ -183,3 +196,169 @@ class PrivateKey:
 
     def __repr__(self):
         return "PrivateKey(%s)" % hex(self.value)
+
+
+def _pk_from_device(aff, ser):
+    """PublicKey of the device's affine bytes, its 48-byte serialisation kept (no square root on the host)"""
+    pk = PublicKey(JacobianPoint._from(H.F1, H.aff_to_jac(H.F1, H.g1_from_abi(aff)), default_ec))
+    pk._ser = bytes(ser)
+    return pk
+
+
+def _pk_affine(pk):
+    return H.g1_affine_bytes(H.jac_to_affine(H.F1, pk.value._jac()))
+
+
+def _child_indices(indices):
+    """the indices as ints; OverflowError outside 32 bits, as i.to_bytes(4, "big") of the reference raises"""
+    out = [int(i) for i in indices]
+    for i in out:
+        if i < 0 or i >= 1 << 32:
+            i.to_bytes(4, "big")
+    return out
+
+
+class ExtendedPrivateKey:
+    """HD private key (keys.py:167-255 of the reference).  private_child_batch / public_child_batch derive many
+    siblings in one GPU call: both HMACs and the key multiplications of every child on the device."""
+    version = 1
+    EXTENDED_PRIVATE_KEY_SIZE = 77
+
+    def __init__(self, version, depth, parent_fingerprint, child_number, chain_code, private_key):
+        self.version = version
+        self.depth = depth
+        self.parent_fingerprint = parent_fingerprint
+        self.child_number = child_number
+        self.chain_code = chain_code
+        self.private_key = private_key
+
+    @staticmethod
+    def from_seed(seed):
+        i_left = hmac256(seed + bytes([0]), b"BLS HD seed")
+        i_right = hmac256(seed + bytes([1]), b"BLS HD seed")
+        sk_int = int.from_bytes(i_left, "big") % GROUP_ORDER
+        sk = PrivateKey.from_bytes(sk_int.to_bytes(PrivateKey.PRIVATE_KEY_SIZE, "big"))
+        return ExtendedPrivateKey(ExtendedPrivateKey.version, 0, 0, 0, i_right, sk)
+
+    def private_child(self, i):
+        return self.private_child_batch([i])[0]
+
+    def private_child_batch(self, indices):
+        """[self.private_child(i) for i in indices] in one GPU call (blsgpu_hd_children, private mode); hardened and
+        non-hardened indices may be mixed."""
+        from . import backend
+        if self.depth >= 255:
+            raise Exception("Cannot go further than 255 levels")
+        idx = _child_indices(indices)
+        if not idx:
+            return []
+        pk = self.private_key.get_public_key()
+        chain, sks, aff, ser = backend.get().hd_children(self.chain_code, _pk_affine(pk), self.private_key.serialize(), idx)
+        fp = pk.get_fingerprint()
+        out = []
+        for j, i in enumerate(idx):
+            sk = PrivateKey.from_bytes(sks[32 * j:32 * (j + 1)])
+            child_pk = _pk_from_device(aff[96 * j:96 * (j + 1)], ser[48 * j:48 * (j + 1)])
+            sk.__dict__["_pk_point"] = child_pk.value          # the cache get_public_key fills (same point)
+            child = ExtendedPrivateKey(ExtendedPrivateKey.version, self.depth + 1, fp, i, chain[32 * j:32 * (j + 1)], sk)
+            child.__dict__["_pk"] = child_pk
+            out.append(child)
+        return out
+
+    def public_child(self, i):
+        return self.private_child(i).get_extended_public_key()
+
+    def public_child_batch(self, indices):
+        """[self.public_child(i) for i in indices] in one GPU call"""
+        return [c.get_extended_public_key() for c in self.private_child_batch(indices)]
+
+    def _public_key(self):
+        pk = self.__dict__.get("_pk")
+        if pk is None or pk.value is not self.private_key.__dict__.get("_pk_point"):
+            return self.private_key.get_public_key()
+        out = PublicKey(pk.value)
+        out._ser = pk._ser
+        return out
+
+    def get_extended_public_key(self):
+        # the reference serialises and parses back (keys.py:222-229): the same fields, without the square root of from_bytes
+        return ExtendedPublicKey(int.from_bytes(self.version.to_bytes(4, "big"), "big"), self.depth, self.parent_fingerprint,
+                                 self.child_number, self.chain_code, self._public_key())
+
+    def get_private_key(self):
+        return self.private_key
+
+    def get_public_key(self):
+        return self.private_key.get_public_key()
+
+    def size(self):
+        return self.EXTENDED_PRIVATE_KEY_SIZE
+
+    def serialize(self):
+        return (self.version.to_bytes(4, "big") + bytes([self.depth]) + self.parent_fingerprint.to_bytes(4, "big") +
+                self.child_number.to_bytes(4, "big") + self.chain_code + self.private_key.serialize())
+
+    def __eq__(self, other):
+        return self.serialize() == other.serialize()
+
+    def __hash__(self):
+        return int.from_bytes(self.serialize(), "big")
+
+
+class ExtendedPublicKey:
+    """HD public key (keys.py:258-316 of the reference); public_child_batch derives many siblings in one GPU call."""
+    EXTENDED_PUBLIC_KEY_SIZE = 93
+
+    def __init__(self, version, depth, parent_fingerprint, child_number, chain_code, public_key):
+        self.version = version
+        self.depth = depth
+        self.parent_fingerprint = parent_fingerprint
+        self.child_number = child_number
+        self.chain_code = chain_code
+        self.public_key = public_key
+
+    @staticmethod
+    def from_bytes(serialized):
+        version = int.from_bytes(serialized[:4], "big")
+        depth = int.from_bytes(serialized[4:5], "big")
+        parent_fingerprint = int.from_bytes(serialized[5:9], "big")
+        child_number = int.from_bytes(serialized[9:13], "big")
+        chain_code = serialized[13:45]
+        public_key = PublicKey.from_bytes(serialized[45:])
+        return ExtendedPublicKey(version, depth, parent_fingerprint, child_number, chain_code, public_key)
+
+    def public_child(self, i):
+        return self.public_child_batch([i])[0]
+
+    def public_child_batch(self, indices):
+        """[self.public_child(i) for i in indices] in one GPU call (blsgpu_hd_children, public mode)."""
+        from . import backend
+        if self.depth >= 255:
+            raise Exception("Cannot go further than 255 levels")
+        idx = [int(i) for i in indices]
+        if any(i >= 1 << 31 for i in idx):
+            raise Exception("Cannot derive hardened children from public key")
+        idx = _child_indices(idx)
+        if not idx:
+            return []
+        chain, _, aff, ser = backend.get().hd_children(self.chain_code, _pk_affine(self.public_key), None, idx)
+        fp = self.public_key.get_fingerprint()
+        return [ExtendedPublicKey(self.version, self.depth + 1, fp, i, chain[32 * j:32 * (j + 1)],
+                                  _pk_from_device(aff[96 * j:96 * (j + 1)], ser[48 * j:48 * (j + 1)]))
+                for j, i in enumerate(idx)]
+
+    def get_public_key(self):
+        return self.public_key
+
+    def size(self):
+        return self.EXTENDED_PUBLIC_KEY_SIZE
+
+    def serialize(self):
+        return (self.version.to_bytes(4, "big") + bytes([self.depth]) + self.parent_fingerprint.to_bytes(4, "big") +
+                self.child_number.to_bytes(4, "big") + self.chain_code + self.public_key.serialize())
+
+    def __eq__(self, other):
+        return self.serialize() == other.serialize()
+
+    def __hash__(self):
+        return int.from_bytes(self.serialize(), "big")

@@ -22,6 +22,7 @@
 #include "blsgpu_lsw.hip"
 #include "blsgpu_g1w.hip"
 #include "blsgpu_msm.hip"
+#include "blsgpu_g1fix.hip"
 #include "blsgpu_h2c.hip"
 #include "blsgpu_h2cw.hip"
 #include "blsgpu_probe.hip"
@@ -118,6 +119,9 @@ struct blsgpu_ctx {
     void* d_fexpw_stamps = nullptr;    // tools/fexpw_stamps.py: cycle counter of result 0 around every operation of the script (k_fexp_wide)
     void* d_fexp_ws = nullptr;         // their slots
     size_t fexp_ws_cap = 0;
+    uint32_t* d_fix_table = nullptr;   // the fixed-base G1 table (blsgpu_g1fix.hip), built on first use; freed by blsgpu_ctx_destroy only
+    void* d_fix_ws = nullptr;          // blsgpu_hd_children*: the parent key, a flag word and one slice of HMAC outputs
+    size_t fix_ws_cap = 0;
     hipEvent_t bulk_event = nullptr;   // caller's event, recorded after the last chip-filling kernel of a Miller stage
     size_t msm_part_cap = 0;           // in u32
     // optional per-kernel timing (blsgpu_timing_enable): HIP events recorded on
@@ -628,6 +632,132 @@ int msm_host(blsgpu_ctx* c, const uint8_t* pts, const uint8_t* scalars, size_t k
     if (out_inf) HIP_TRY(hipMemcpy(out_inf, dinf, groups, hipMemcpyDeviceToHost));
     return 0;
 }
+
+// ------------------------------------------------------------ fixed-base G1, HD derivation (blsgpu_g1fix.hip) --
+constexpr size_t FIX_SLICE = (size_t)1 << 22;          // items per launch of the _dev forms
+constexpr size_t FIX_HOST_SLICE = (size_t)1 << 18;     // items per staged slice of the host-buffer forms (<= 76 MB of staging)
+
+// the table of d 2^(8w) G1, built on `st` the first time a context needs it
+int fix_table(blsgpu_ctx* c, hipStream_t st) {
+    if (c->d_fix_table) return 0;
+    using namespace blsgpu::g1fix;
+    const Gen g = {{0xdb22c6bbu, 0xfb3af00au, 0xf97a1aefu, 0x6c55e83fu, 0x171bac58u, 0xa14e3a3fu, 0x9774b905u, 0xc3688c4fu, 0x4fa9ac0fu,
+                    0x2695638cu, 0x3197d794u, 0x17f1d3a7u},
+                   {0x46c5e7e1u, 0x0caa2329u, 0xa2888ae4u, 0xd03cc744u, 0x2c04b3edu, 0x00db18cbu, 0xd5d00af6u, 0xfcf5e095u, 0x741d8ae4u,
+                    0xa09e30edu, 0xe3aaa0f1u, 0x08b3f481u}};      // G1, ec.py:394-396 (little-endian words)
+    void* p = nullptr;
+    HIP_TRY(hipMalloc(&p, TABLE_BYTES));
+    hipLaunchKernelGGL(k_fix_table, dim3((ENTRIES + 63) / 64), dim3(64), 0, st, g, (uint32_t*)p);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        return fail(-EIO, std::string("k_fix_table: ") + hipGetErrorString(e));
+    }
+    c->d_fix_table = (uint32_t*)p;
+    return 0;
+}
+
+int check_n_add(size_t n, size_t n_add, const void* add) {
+    if (n_add != 0 && n_add != 1 && n_add != n) return fail(-EINVAL, "n_add must be 0, 1 or n");
+    if (n_add && !add) return fail(-EINVAL, "NULL add buffer");
+    return 0;
+}
+
+// enqueues out_i = s_i G1 (+ A) on `st` (caller: StreamGuard, table built)
+int fix_mul_launch(blsgpu_ctx* c, const void* d_scalars, size_t n, const void* d_add, size_t n_add, void* d_out_aff, void* d_out_ser,
+                   hipStream_t st) {
+    const bool per = n_add == n && n_add > 1;
+    for (size_t lo = 0; lo < n; lo += FIX_SLICE) {
+        const size_t m = n - lo < FIX_SLICE ? n - lo : FIX_SLICE;
+        hipLaunchKernelGGL(blsgpu::g1fix::k_fix_mul, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint32_t*)c->d_fix_table,
+                           (const uint32_t*)d_scalars + lo * 8, (uint32_t)m,
+                           n_add ? (const uint32_t*)d_add + (per ? lo * 24 : 0) : nullptr, per ? 1u : 0u,
+                           d_out_aff ? (uint32_t*)d_out_aff + lo * 24 : nullptr, d_out_ser ? (uint32_t*)d_out_ser + lo * 12 : nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+int g1_mul_gen_dev(blsgpu_ctx* c, const void* d_scalars, size_t n, const void* d_add, size_t n_add, void* d_out_aff, void* d_out_ser,
+                   hipStream_t st) {
+    if (n == 0) return 0;
+    if (!d_scalars) return fail(-EINVAL, "NULL scalar buffer");
+    if (int rc = check_n_add(n, n_add, d_add)) return rc;
+    StreamGuard sg(c, st);
+    if (int rc = fix_table(c, st)) return rc;
+    return fix_mul_launch(c, d_scalars, n, d_add, n_add, d_out_aff, d_out_ser, st);
+}
+
+// 48 big-endian bytes of q // 2 (blsgpu::g1fix::HALF_Q_WORDS)
+bool y_gt_half_q(const uint8_t y[48]) {
+    for (int b = 0; b < 48; b++) {
+        const uint8_t h = (uint8_t)(blsgpu::g1fix::HALF_Q_WORDS[11 - b / 4] >> (24 - 8 * (b % 4)));
+        if (y[b] != h) return y[b] > h;
+    }
+    return false;
+}
+uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
+
+// the per-call constants of a parent: HMAC midstates of the chain code, PublicKey.serialize() of the parent key
+// (ec.py:94-111; (0, 0) -> 48 zero bytes), and for private derivation its key's bytes and value mod n
+blsgpu::g1fix::HdParent hd_parent(const uint8_t chain_code[32], const uint8_t parent_pk_aff[96], const uint8_t* parent_sk) {
+    blsgpu::g1fix::HdParent P;
+    memset(&P, 0, sizeof(P));
+    hdk::hmac_key(chain_code, 32, P.key);
+    for (int j = 0; j < 12; j++) P.pk_ser[j] = be32(parent_pk_aff + 4 * j);
+    if (y_gt_half_q(parent_pk_aff + 48)) P.pk_ser[0] |= 0x80000000u;
+    if (parent_sk) {
+        for (int j = 0; j < 8; j++) { P.sk_ser[j] = be32(parent_sk + 4 * j); P.sk[7 - j] = P.sk_ser[j]; }
+        hdk::reduce_n(P.sk);
+        P.priv = 1;
+    }
+    return P;
+}
+
+// n children of one parent on `st`; public mode (parent_sk NULL) with `check`: a device scan of the indices and one
+// synchronising read of its flag first, -EINVAL before anything is written if one is hardened
+int hd_children_dev(blsgpu_ctx* c, const uint8_t chain_code[32], const uint8_t parent_pk_aff[96], const uint8_t* parent_sk, const void* d_idx,
+                    size_t n, void* d_chain, void* d_sk, void* d_pk_aff, void* d_pk_ser, bool check, hipStream_t st) {
+    if (n == 0) return 0;
+    if (!chain_code || !parent_pk_aff || !d_idx || !d_chain) return fail(-EINVAL, "NULL argument");
+    if (parent_sk && !d_sk) return fail(-EINVAL, "private derivation needs out_sk");
+    if (n > 0xFFFFFFFFull) return fail(-EINVAL, "batch too large");
+    const blsgpu::g1fix::HdParent P = hd_parent(chain_code, parent_pk_aff, parent_sk);
+    StreamGuard sg(c, st);
+    const bool pub = parent_sk == nullptr;
+    const size_t slice = pub ? (n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE) : 0;
+    if (int rc = grow_buffer(c, &c->d_fix_ws, &c->fix_ws_cap, 256 + slice * 32)) return rc;
+    char* ws = (char*)c->d_fix_ws;                                  // [0, 96) parent key, [128, 132) flag, [256, ..) i_left
+    if (pub && check) {
+        HIP_TRY(hipMemsetAsync(ws + 128, 0, 4, st));
+        hipLaunchKernelGGL(blsgpu::g1fix::k_hd_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_idx, (uint32_t)n,
+                           (uint32_t*)(ws + 128));
+        HIP_TRY(hipGetLastError());
+        uint32_t flag = 0;
+        HIP_TRY(hipMemcpyAsync(&flag, ws + 128, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (flag) return fail(-EINVAL, "Cannot derive hardened children from public key");
+    }
+    const bool pk_out = d_pk_aff || d_pk_ser;
+    if (pk_out) {
+        if (int rc = fix_table(c, st)) return rc;
+    }
+    if (pub) HIP_TRY(hipMemcpyAsync(ws, parent_pk_aff, 96, hipMemcpyHostToDevice, st));
+    const size_t step = pub ? slice : FIX_SLICE;
+    for (size_t lo = 0; lo < n; lo += step) {
+        const size_t m = n - lo < step ? n - lo : step;
+        uint32_t* scal = pub ? (uint32_t*)(ws + 256) : (uint32_t*)d_sk + lo * 8;
+        hipLaunchKernelGGL(blsgpu::g1fix::k_hd_hmac, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, P, (const uint32_t*)d_idx + lo,
+                           (uint32_t)m, (uint32_t*)d_chain + lo * 8, scal);
+        HIP_TRY(hipGetLastError());
+        if (pk_out) {
+            if (int rc = fix_mul_launch(c, scal, m, pub ? ws : nullptr, pub ? 1 : 0, d_pk_aff ? (char*)d_pk_aff + lo * 96 : nullptr,
+                                        d_pk_ser ? (char*)d_pk_ser + lo * 48 : nullptr, st))
+                return rc;
+        }
+    }
+    return 0;
+}
 }  // namespace
 
 
@@ -800,6 +930,8 @@ BLSGPU_EXPORT void blsgpu_ctx_destroy(blsgpu_ctx* c) {
     if (c->d_exflags) (void)hipFree(c->d_exflags);
     if (c->d_fexp_ws) (void)hipFree(c->d_fexp_ws);
     if (c->d_h2c_ws) (void)hipFree(c->d_h2c_ws);
+    if (c->d_fix_table) (void)hipFree(c->d_fix_table);
+    if (c->d_fix_ws) (void)hipFree(c->d_fix_ws);
     for (void* q : c->retired) (void)hipFree(q);
     if (c->last_event) (void)hipEventDestroy(c->last_event);
     if (c->ev0) {
@@ -983,6 +1115,8 @@ BLSGPU_EXPORT int blsgpu_ctx_workspace_bytes(blsgpu_ctx* c, size_t out[BLSGPU_WS
     out[BLSGPU_WS_SLOTS] = c->fexp_ws_cap + c->h2c_ws_cap;
     size_t total = 0;
     for (int i = 0; i < BLSGPU_WS_TOTAL; i++) total += out[i];
+    // the fixed-base table and the HD derivation slice have no field of their own: they count in the total only
+    total += (c->d_fix_table ? blsgpu::g1fix::TABLE_BYTES : 0) + c->fix_ws_cap;
     out[BLSGPU_WS_TOTAL] = total;
     return 0;
 }
@@ -1856,6 +1990,75 @@ BLSGPU_EXPORT int blsgpu_g2_decompress_dev(blsgpu_ctx* c, const void* d_in, size
     if (!c || (n && (!d_in || !d_out || !d_ok))) return fail(-EINVAL, "NULL argument");
     HIP_TRY(hipSetDevice(c->device));
     return decompress_dev<2>(c, d_in, n, d_out, d_ok, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------ fixed-base G1, HD derivation --
+BLSGPU_EXPORT int blsgpu_g1_mul_gen(blsgpu_ctx* c, const uint8_t* scalars, size_t n, const uint8_t* add, size_t n_add, uint8_t* out_aff,
+                                    uint8_t* out_ser) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (n == 0) return 0;
+    if (!scalars || (!out_aff && !out_ser)) return fail(-EINVAL, "NULL argument");
+    if (int rc = check_n_add(n, n_add, add)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE, per = n_add == n && n_add > 1;
+    const size_t o_add = S * 32, o_aff = o_add + (per ? S : 1) * 96, o_ser = o_aff + (out_aff ? S * 96 : 0);
+    if (int rc = grow_buffer(c, &c->d_io, &c->io_cap, o_ser + (out_ser ? S * 48 : 0) + 64)) return rc;
+    char* d = (char*)c->d_io;
+    if (n_add == 1) HIP_TRY(hipMemcpyAsync(d + o_add, add, 96, hipMemcpyHostToDevice, 0));
+    for (size_t lo = 0; lo < n; lo += S) {
+        const size_t m = n - lo < S ? n - lo : S;
+        HIP_TRY(hipMemcpyAsync(d, scalars + lo * 32, m * 32, hipMemcpyHostToDevice, 0));
+        if (per) HIP_TRY(hipMemcpyAsync(d + o_add, add + lo * 96, m * 96, hipMemcpyHostToDevice, 0));
+        if (int rc = g1_mul_gen_dev(c, d, m, n_add ? d + o_add : nullptr, per ? m : n_add, out_aff ? d + o_aff : nullptr,
+                                    out_ser ? d + o_ser : nullptr, nullptr))
+            return rc;
+        if (out_aff) HIP_TRY(hipMemcpy(out_aff + lo * 96, d + o_aff, m * 96, hipMemcpyDeviceToHost));
+        if (out_ser) HIP_TRY(hipMemcpy(out_ser + lo * 48, d + o_ser, m * 48, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+BLSGPU_EXPORT int blsgpu_g1_mul_gen_dev(blsgpu_ctx* c, const void* d_scalars, size_t n, const void* d_add, size_t n_add, void* d_out_aff,
+                                        void* d_out_ser, void* stream) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    return g1_mul_gen_dev(c, d_scalars, n, d_add, n_add, d_out_aff, d_out_ser, (hipStream_t)stream);
+}
+
+BLSGPU_EXPORT int blsgpu_hd_children(blsgpu_ctx* c, const uint8_t chain_code[32], const uint8_t parent_pk_aff[96], const uint8_t* parent_sk,
+                                     const uint32_t* indices, size_t n, uint8_t* out_chain, uint8_t* out_sk, uint8_t* out_pk_aff,
+                                     uint8_t* out_pk_ser) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (n == 0) return 0;
+    if (!chain_code || !parent_pk_aff || !indices || !out_chain) return fail(-EINVAL, "NULL argument");
+    if (parent_sk && !out_sk) return fail(-EINVAL, "private derivation needs out_sk");
+    if (!parent_sk)
+        for (size_t i = 0; i < n; i++)
+            if (indices[i] >> 31) return fail(-EINVAL, "Cannot derive hardened children from public key");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE;
+    const size_t o_chain = S * 4, o_sk = o_chain + S * 32, o_aff = o_sk + (parent_sk ? S * 32 : 0), o_ser = o_aff + (out_pk_aff ? S * 96 : 0);
+    if (int rc = grow_buffer(c, &c->d_io, &c->io_cap, o_ser + (out_pk_ser ? S * 48 : 0) + 64)) return rc;
+    char* d = (char*)c->d_io;
+    for (size_t lo = 0; lo < n; lo += S) {
+        const size_t m = n - lo < S ? n - lo : S;
+        HIP_TRY(hipMemcpyAsync(d, indices + lo, m * 4, hipMemcpyHostToDevice, 0));
+        if (int rc = hd_children_dev(c, chain_code, parent_pk_aff, parent_sk, d, m, d + o_chain, parent_sk ? d + o_sk : nullptr,
+                                     out_pk_aff ? d + o_aff : nullptr, out_pk_ser ? d + o_ser : nullptr, false, nullptr))
+            return rc;
+        HIP_TRY(hipMemcpy(out_chain + lo * 32, d + o_chain, m * 32, hipMemcpyDeviceToHost));
+        if (parent_sk) HIP_TRY(hipMemcpy(out_sk + lo * 32, d + o_sk, m * 32, hipMemcpyDeviceToHost));
+        if (out_pk_aff) HIP_TRY(hipMemcpy(out_pk_aff + lo * 96, d + o_aff, m * 96, hipMemcpyDeviceToHost));
+        if (out_pk_ser) HIP_TRY(hipMemcpy(out_pk_ser + lo * 48, d + o_ser, m * 48, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+BLSGPU_EXPORT int blsgpu_hd_children_dev(blsgpu_ctx* c, const uint8_t chain_code[32], const uint8_t parent_pk_aff[96], const uint8_t* parent_sk,
+                                         const void* d_indices, size_t n, void* d_out_chain, void* d_out_sk, void* d_out_pk_aff,
+                                         void* d_out_pk_ser, void* stream) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    return hd_children_dev(c, chain_code, parent_pk_aff, parent_sk, d_indices, n, d_out_chain, d_out_sk, d_out_pk_aff, d_out_pk_ser, true,
+                           (hipStream_t)stream);
 }
 
 #ifdef BLSGPU_STAMPS

@@ -1,0 +1,170 @@
+// blsgpu_g1fix.hip -- fixed-base G1 multiplication  out_i = s_i G1 (+ A_i)  and batched HD child derivation
+// (included by blsgpu_api.hip).
+//
+// Every s G1 of the other entries is a variable-base multiplication (k_smul: a table of the point's own multiples per
+// lane, 252 doublings, 64 complete additions).  The generator is fixed, so its multiples are computed ONCE per context:
+// unsigned 8-bit windows, entry (w, d) = d 2^(8w) G1 for w < 32, 1 <= d <= 255, affine (x, y) in the L28 form of fp28.h --
+// 32 x 255 x 112 bytes = 0.9 MB, inside one XCD's 4 MB L2.  A scalar is then s = sum_w d_w 2^(8w) and s G1 = sum_w
+// T[w][d_w]: 32 complete mixed additions (r28::pmadd, none for a zero digit), no doubling, then one inversion for the
+// affine result.  One scalar per lane; the lanes of a wavefront gather from the same window's 28 KB at each step.
+// The table is indexed by secret digits: not constant-time (neither is k_smul).
+#pragma once
+
+#include "hd_derive.h"
+
+namespace blsgpu {
+namespace g1fix {
+
+constexpr uint32_t WINDOWS = 32, DIGITS = 255;
+constexpr uint32_t ENTRY_DW = 2 * r28::NL;                                   // affine (x, y), L28
+constexpr uint32_t ENTRIES = WINDOWS * DIGITS;
+constexpr size_t TABLE_BYTES = (size_t)ENTRIES * ENTRY_DW * 4;
+constexpr uint32_t HALF_Q_WORDS[12] = {0xffffd555u, 0xdcff7fffu, 0x58a9ffffu, 0x0f55ffffu, 0x7b587b12u, 0xb3986950u,
+                                       0x79c2895fu, 0xb23ba5c2u, 0x21a5d66bu, 0x258dd3dbu, 0x1cbff34du, 0x0d0088f5u};   // q // 2
+
+struct Gen { uint32_t x[12], y[12]; };                                        // an affine point, little-endian words
+
+// (X : Y : Z) -> canonical x, y (little-endian words; (0, 0) for Z = 0 since fq_inv(0) = 0), one inversion
+__device__ __forceinline__ void to_affine_raw(const r28::ptT<r28::fe>& a, uint32_t x[12], uint32_t y[12]) {
+    uint32_t zv[12], ziv[12];
+    r28::to_vm(zv, a.Z);
+    bls::fq_inv(ziv, zv);
+    const r28::fe zi = r28::from_vm(ziv);
+    r28::to_raw(x, r28::mul(a.X, zi));
+    r28::to_raw(y, r28::mul(a.Y, zi));
+}
+
+// The table: entry e = w * 255 + d - 1 holds d 2^(8w) G1 -- one entry per lane, double-and-add over the 8 bits of d, then 8w
+// doublings, then the affine form.  Once per context (a few hundred microseconds).
+__global__ void __launch_bounds__(64) k_fix_table(Gen g, uint32_t* __restrict__ table)
+#if BLSGPU_EMIT(BLSGPU_TU_FIX)
+{
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= ENTRIES) return;
+    const uint32_t w = e / DIGITS, d = e % DIGITS + 1u;
+    const r28::fe gx = r28::from_raw(g.x), gy = r28::from_raw(g.y);
+    r28::ptT<r28::fe> acc = r28::pt_inf<r28::fe>();
+#pragma unroll 1
+    for (int b = 7; b >= 0; b--) {
+        acc = r28::pdbl(acc);
+        if ((d >> b) & 1u) r28::pmadd(acc, gx, gy);
+    }
+#pragma unroll 1
+    for (uint32_t t = 0; t < 8u * w; t++) acc = r28::pdbl(acc);
+    uint32_t x[12], y[12];
+    to_affine_raw(acc, x, y);
+    r28::st(r28::from_raw(x), table + (size_t)e * ENTRY_DW);
+    r28::st(r28::from_raw(y), table + (size_t)e * ENTRY_DW + r28::NL);
+}
+#else
+;
+#endif
+
+// out_i = (s_i mod n) G1 + A_i.  scalars: n x 32 bytes big-endian; add: NULL, one point (add_per = 0) or n points (add_per = 1),
+// 96 bytes affine big-endian, (0, 0) = infinity; out_aff (n x 96 bytes, (0, 0) for infinity) and out_ser (n x 48 bytes, the
+// reference's compression ec.py:94-111: x with 0x80 when y > q // 2, 48 zero bytes for infinity) may each be NULL.
+// s mod n gives the same point as s (G1 has order n); the complete additions need no special case for A = +-s G1.
+__global__ void __launch_bounds__(256) k_fix_mul(const uint32_t* __restrict__ table, const uint32_t* __restrict__ scalars, uint32_t n,
+                                                 const uint32_t* __restrict__ add, uint32_t add_per, uint32_t* __restrict__ out_aff,
+                                                 uint32_t* __restrict__ out_ser)
+#if BLSGPU_EMIT(BLSGPU_TU_FIX)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t s[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) s[j] = bswap32(scalars[(size_t)i * 8 + 7 - j]);
+    hdk::reduce_n(s);
+    r28::ptT<r28::fe> acc = r28::pt_inf<r28::fe>();
+    if (add) {
+        const uint32_t* a = add + (size_t)(add_per ? i : 0u) * 24;
+        uint32_t x[12], y[12], any = 0;
+#pragma unroll
+        for (int w = 0; w < 12; w++) { x[11 - w] = bswap32(a[w]); y[11 - w] = bswap32(a[12 + w]); any |= x[11 - w] | y[11 - w]; }
+        if (any) r28::pmadd(acc, r28::from_raw(x), r28::from_raw(y));
+    }
+#pragma unroll 1
+    for (uint32_t w = 0; w < WINDOWS; w++) {
+        const uint32_t d = (s[w >> 2] >> ((w & 3u) * 8u)) & 255u;
+        if (d) {
+            const uint32_t* p = table + (size_t)(w * DIGITS + d - 1u) * ENTRY_DW;
+            r28::pmadd(acc, r28::ld(p), r28::ld(p + r28::NL));
+        }
+    }
+    uint32_t x[12], y[12];
+    to_affine_raw(acc, x, y);
+    if (out_aff) {
+#pragma unroll
+        for (int w = 0; w < 12; w++) { out_aff[(size_t)i * 24 + w] = bswap32(x[11 - w]); out_aff[(size_t)i * 24 + 12 + w] = bswap32(y[11 - w]); }
+    }
+    if (out_ser) {
+        bool gt = false, decided = false;                   // y > q // 2, most significant word first
+#pragma unroll
+        for (int w = 11; w >= 0; w--) {
+            if (!decided && y[w] != HALF_Q_WORDS[w]) { gt = y[w] > HALF_Q_WORDS[w]; decided = true; }
+        }
+        x[11] |= gt ? 0x80000000u : 0u;                     // (infinity: y = 0, so x stays 0)
+#pragma unroll
+        for (int w = 0; w < 12; w++) out_ser[(size_t)i * 12 + w] = bswap32(x[11 - w]);
+    }
+}
+#else
+;
+#endif
+
+// One call's parent: the HMAC key midstates of the chain code, the parent's serialised keys as big-endian words and, for
+// private derivation, its key mod n (little-endian words).
+struct HdParent {
+    hdk::HmacKey key;
+    uint32_t pk_ser[12];        // PublicKey.serialize() of the parent (the message of an index < 2^31)
+    uint32_t sk_ser[8];         // PrivateKey.serialize() (the message of a hardened index; private mode)
+    uint32_t sk[8];             // parent key mod n (private mode)
+    uint32_t priv;              // 1: private derivation
+};
+
+// Child i of the parent, one per lane (keys.py:191-215 / 276-296 of the reference): i_left, i_right = the two HMACs;
+// chain[i] = i_right; scal[i] = i_left (public mode: the fixed-base kernel reduces it and adds the parent key) or the child
+// key (i_left + sk) mod n (private mode).  chain / scal: n x 32 bytes.
+__global__ void __launch_bounds__(256) k_hd_hmac(HdParent P, const uint32_t* __restrict__ idx, uint32_t n, uint32_t* __restrict__ chain,
+                                                 uint32_t* __restrict__ scal)
+#if BLSGPU_EMIT(BLSGPU_TU_FIX)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t index = idx[i];
+    const bool hardened = (index >> 31) != 0u;              // only in private mode (the host refuses them in public mode)
+    uint32_t il[8], ir[8];
+    if (P.priv && hardened) hdk::child_hmacs(P.key, P.sk_ser, 8, index, il, ir);
+    else hdk::child_hmacs(P.key, P.pk_ser, 12, index, il, ir);
+#pragma unroll
+    for (int j = 0; j < 8; j++) chain[(size_t)i * 8 + j] = bswap32(ir[j]);
+    if (P.priv) {
+        uint32_t a[8], r[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) a[j] = il[7 - j];
+        hdk::reduce_n(a);
+        hdk::add_mod_n(r, a, P.sk);
+#pragma unroll
+        for (int j = 0; j < 8; j++) scal[(size_t)i * 8 + j] = bswap32(r[7 - j]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; j++) scal[(size_t)i * 8 + j] = bswap32(il[j]);
+    }
+}
+#else
+;
+#endif
+
+// flag[0] |= 1 if any of the n indices is >= 2^31 (the _dev form of public derivation checks before it writes)
+__global__ void __launch_bounds__(256) k_hd_check(const uint32_t* __restrict__ idx, uint32_t n, uint32_t* __restrict__ flag)
+#if BLSGPU_EMIT(BLSGPU_TU_FIX)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && (idx[i] >> 31)) atomicOr(flag, 1u);
+}
+#else
+;
+#endif
+
+}  // namespace g1fix
+}  // namespace blsgpu
