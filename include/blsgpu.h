@@ -70,7 +70,8 @@ int blsgpu_ctx_reserve(blsgpu_ctx *ctx, size_t max_pairs);
  * calls made so far; the line-stream stage keeps 68 x 336 bytes of line records per pair of its largest call, the
  * counterpart of the n-arrays of mpz_t the reference mallocs per call, fields_t_c.pyx:2348-2388).  out[BLSGPU_WS_TOTAL]
  * is the sum (which also counts the fixed-base G1 table and the HD derivation slice, blsgpu_g1_mul_gen /
- * blsgpu_hd_children; they have no field of their own).  No device call is made. */
+ * blsgpu_hd_children, and the commitments of blsgpu_g1_poly_check; they have no field of their own).  No device call is
+ * made. */
 enum { BLSGPU_WS_PARTIALS = 0, BLSGPU_WS_STAGING, BLSGPU_WS_LINES, BLSGPU_WS_LINE_PRODUCTS, BLSGPU_WS_FLAGS_AND_LISTS,
        BLSGPU_WS_GROUP_SUMS, BLSGPU_WS_SLOTS, BLSGPU_WS_TOTAL, BLSGPU_WS_FIELDS };
 int blsgpu_ctx_workspace_bytes(blsgpu_ctx *ctx, size_t out[BLSGPU_WS_FIELDS]);
@@ -315,6 +316,24 @@ int blsgpu_hd_children(blsgpu_ctx *ctx, const uint8_t chain_code[32], const uint
 int blsgpu_hd_children_dev(blsgpu_ctx *ctx, const uint8_t chain_code[32], const uint8_t parent_pk_aff[BLSGPU_G1_BYTES],
                            const uint8_t *parent_sk, const void *d_indices, size_t n, void *d_out_chain, void *d_out_sk,
                            void *d_out_pk_aff, void *d_out_pk_ser, void *stream);
+
+/* Feldman share check (Threshold.verify_secret_fragment, threshold.py:104-125 of the reference) for n fragments at once.
+ * commit: n_polys x t affine G1 points (96 B, (0,0) = infinity; caller guarantees on-curve);
+ * poly: n uint32 polynomial indices; x, s: n x 32 B big-endian (any value < 2^256, reduced mod n on the device).
+ * status[i] = 1 if (s_i mod n)G1 == sum_k x_i^k C[poly_i][k], 0 if not, 2 if poly_i has a commitment C_k (k >= 1)
+ * outside the order-n subgroup (not decided on the device).  out_aff (NULL or n x 96 B): the Horner value.
+ * s/status may be NULL together (evaluation only); out_aff and status not both NULL. t == 0 or a poly index >= n_polys:
+ * -EINVAL before anything is written. n == 0 writes nothing.
+ * The commitments are prepared once per call (csrc/blsgpu_g1poly.hip): L28 form, and a check [n] C_k == O per commitment;
+ * then one fragment per lane: Horner in the exponent over the bits of x_i mod n, (s_i mod n) G1 on blsgpu_g1_mul_gen's
+ * table, a projective comparison.  Sort the fragments by polynomial: a wavefront then reads one polynomial.  The loops
+ * follow the bits of the (public) x_i and the table gathers the digits of s_i: NOT constant-time. */
+int blsgpu_g1_poly_check(blsgpu_ctx *ctx, const uint8_t *commit, size_t n_polys, size_t t, const uint32_t *poly,
+                         const uint8_t *x, const uint8_t *s, size_t n, uint8_t *status, uint8_t *out_aff);
+/* The same with every buffer in device memory, enqueued on `stream`.  The indices are first scanned on the device and the
+ * stream is synchronised once to read the result of that check. */
+int blsgpu_g1_poly_check_dev(blsgpu_ctx *ctx, const void *d_commit, size_t n_polys, size_t t, const void *d_poly,
+                             const void *d_x, const void *d_s, size_t n, void *d_status, void *d_out_aff, void *stream);
 
 /* Measurement aid (bench.py): when enabled, HIP events are recorded on the
  * launch stream around every kernel this context launches (up to 1024 launches

@@ -26,6 +26,7 @@ SYMBOLS = (
     "blsgpu_fq12_op_batch", "blsgpu_fq12_pow_batch", "blsgpu_ctx_set_mp3_threshold", "blsgpu_ctx_set_ls_threshold", "blsgpu_ctx_set_ls_teams", "blsgpu_ctx_set_bulk_event", "blsgpu_ctx_set_fexp_team_threshold", "blsgpu_ctx_set_fexp_trace", "blsgpu_ctx_set_fexpw_stamps", "blsgpu_debug_read_lines",
     "blsgpu_ctx_workspace_bytes", "blsgpu_verify_pipeline", "blsgpu_verify_pipeline_dev",
     "blsgpu_g1_mul_gen", "blsgpu_g1_mul_gen_dev", "blsgpu_hd_children", "blsgpu_hd_children_dev",
+    "blsgpu_g1_poly_check", "blsgpu_g1_poly_check_dev",
 )
 
 _lib = None
@@ -110,6 +111,8 @@ def load_library(path=None):
         L.blsgpu_g1_mul_gen_dev.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp]
         L.blsgpu_hd_children.argtypes = [vp, cp, cp, cp, vp, sz, vp, vp, vp, vp]
         L.blsgpu_hd_children_dev.argtypes = [vp, cp, cp, cp, vp, sz, vp, vp, vp, vp, vp]
+        L.blsgpu_g1_poly_check.argtypes = [vp, cp, sz, sz, vp, cp, cp, sz, vp, vp]
+        L.blsgpu_g1_poly_check_dev.argtypes = [vp, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp]
         L.blsgpu_timing_enable.argtypes = [vp, ctypes.c_int]
         L.blsgpu_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int), sz,
                                          ctypes.POINTER(sz)]
@@ -383,6 +386,32 @@ class Engine:
         self._check(self.lib.blsgpu_hd_children_dev(self.h, bytes(chain_code), bytes(parent_pk_aff),
                                                     None if parent_sk is None else bytes(parent_sk), d_indices, n, d_out_chain,
                                                     d_out_sk, d_out_pk_aff, d_out_pk_ser, stream), "blsgpu_hd_children_dev")
+
+    def g1_poly_check(self, commit, n_polys, t, poly, x, s=None, aff=False):
+        """Feldman share checks (blsgpu_g1_poly_check): commit n_polys x t x 96 affine bytes, poly n indices, x / s n x 32
+        bytes big-endian (or ints below 2^256); s None = evaluation only.
+        -> (n status bytes (1 equal, 0 not, 2 undecided) or None, n x 96 affine Horner values or None)"""
+        def as_bytes(v):
+            return v if isinstance(v, (bytes, bytearray)) else b"".join(int(a).to_bytes(32, "big") for a in v)
+        xb = as_bytes(x)
+        n = len(poly)
+        sb = as_bytes(s) if s is not None else None
+        if len(xb) != 32 * n or (sb is not None and len(sb) != 32 * n) or len(commit) != 96 * n_polys * t:
+            raise ValueError("need n x 32 bytes of x (and s) and n_polys x t x 96 bytes of commitments")
+        if sb is None and not aff:
+            raise ValueError("ask for at least one output")
+        if any(p < 0 or p >= 1 << 32 for p in poly):
+            raise OverflowError("polynomial indices are 32-bit")
+        idx = (ctypes.c_uint32 * max(1, n))(*poly)
+        st = ctypes.create_string_buffer(max(1, n)) if sb is not None else None
+        oa = ctypes.create_string_buffer(max(1, 96 * n)) if aff else None
+        self._check(self.lib.blsgpu_g1_poly_check(self.h, bytes(commit), n_polys, t, idx, bytes(xb), None if sb is None else bytes(sb), n,
+                                                  st, oa), "blsgpu_g1_poly_check")
+        return (st.raw[:n] if st is not None else None), (oa.raw[:96 * n] if aff else None)
+
+    def g1_poly_check_dev(self, d_commit, n_polys, t, d_poly, d_x, d_s, n, d_status, d_out_aff, stream=0):
+        self._check(self.lib.blsgpu_g1_poly_check_dev(self.h, d_commit, n_polys, t, d_poly, d_x, d_s, n, d_status, d_out_aff, stream),
+                    "blsgpu_g1_poly_check_dev")
 
     def timing_enable(self, on=True):
         self._check(self.lib.blsgpu_timing_enable(self.h, int(on)), "blsgpu_timing_enable")

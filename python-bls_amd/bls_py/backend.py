@@ -54,6 +54,11 @@ class HipProvider:
         """-> (n x 32 chain codes, n x 32 child keys or None (public), n x 96 affine keys, n x 48 serialised keys)"""
         return self._eng.hd_children(chain_code, parent_pk_aff, parent_sk, indices)
 
+    def g1_poly_check(self, commit: bytes, n_polys: int, t: int, poly, x: bytes, s=None, aff: bool = False):
+        """Feldman share checks: -> (n status bytes: 1 (s_i mod n) G1 == sum_k x_i^k C[poly_i][k], 0 not, 2 poly_i has a
+        C_k (k >= 1) outside the order-n subgroup; or None for s None) and the n x 96 affine Horner values (aff) or None"""
+        return self._eng.g1_poly_check(commit, n_polys, t, poly, x, s, aff)
+
     # ---- the whole of BLS.verify's device work without a host round trip between its steps (bls.py:153-201) ----
     def verify_pipeline(self, neg_g1: bytes, sig: bytes, hashes: bytes, n: int, keys_affine=None, key_pts=None, key_scalars=None, k=0) -> bytes:
         """e(-G1, sig) * prod_i e(P_i, H(m_i)) for n message hashes (32 bytes each): blsgpu_verify_pipeline -- ONE upload,
@@ -70,7 +75,8 @@ def use(provider):
     map_to_g2(t: n x 192 bytes) -> n x 192 bytes,
     g1_decompress / g2_decompress(bytes) -> (affine bytes, [accepted]),
     g1_mul_gen(scalars, add|None, n_add) -> (affine bytes, serialised bytes),
-    hd_children(chain_code, parent_pk_aff, parent_sk|None, indices) -> (chain codes, child keys|None, affine, serialised)."""
+    hd_children(chain_code, parent_pk_aff, parent_sk|None, indices) -> (chain codes, child keys|None, affine, serialised),
+    g1_poly_check(commit, n_polys, t, poly, x, s|None, aff) -> (status bytes|None, affine Horner values|None)."""
     global _provider
     _provider = provider
 

@@ -103,6 +103,31 @@ class PrivateKey:
         fragments = [sum(c * pow(x, i, GROUP_ORDER) for i, c in enumerate(poly)) for x in range(1, N + 1)]
         return PrivateKey(poly[0]), commitments, fragments
 
+    @staticmethod
+    def new_threshold_batch(T, N, count):
+        """[PrivateKey.new_threshold(T, N) for _ in range(count)]: the coefficients drawn from RNG in the same order, the
+        count x T commitments g1*c in one GPU call on the fixed-base table (blsgpu_g1_mul_gen), the fragments P(1..N)
+        by Horner mod n on the host (as Fq(n, .) values)."""
+        from . import backend
+        from .ec import AffinePoint
+        assert 1 <= T <= N
+        polys = [[RNG.randint(1, GROUP_ORDER - 1) for _ in range(T)] for _ in range(count)]
+        if not polys:
+            return []
+        aff, _ = backend.get().g1_mul_gen(b"".join(c.to_bytes(32, "big") for poly in polys for c in poly))
+        out = []
+        for d, poly in enumerate(polys):
+            commitments = [AffinePoint._from(H.F1, H.g1_from_abi(aff[96 * (d * T + k):96 * (d * T + k + 1)]), default_ec)
+                           for k in range(T)]
+            fragments = []
+            for x in range(1, N + 1):
+                acc = 0
+                for c in reversed(poly):
+                    acc = (acc * x + c) % GROUP_ORDER
+                fragments.append(Fq(GROUP_ORDER, acc))
+            out.append((PrivateKey(poly[0]), commitments, fragments))
+        return out
+
     def get_public_key(self):
         # sk G1 is one engine call (a scalar multiplication: ~2 ms with its round trip); the point is kept, a NEW PublicKey
         # object comes back every time as in keys.py:104-105 (callers that change `value` would lose the cache: __setattr__ below)

@@ -1,6 +1,6 @@
 """k-of-n threshold helpers (threshold.py:56-136 of the reference)."""
-from .bls12381 import n as GROUP_ORDER
-from .ec import JacobianPoint, default_ec, generator_Fq
+from .bls12381 import n as GROUP_ORDER, q as FIELD_Q
+from .ec import AffinePoint, JacobianPoint, default_ec, generator_Fq
 from .fields import Fq
 from . import hostmath as H
 from .signature import Signature
@@ -40,8 +40,84 @@ class Threshold:
         return lhs == rhs
 
     @staticmethod
+    def verify_secret_fragment_batch(T, secret_fragments, players, commitments, ec=default_ec):
+        """[verify_secret_fragment(T, s, p, C) for s, p, C in zip(secret_fragments, players, commitments)] with the
+        checks of on-curve G1 commitments on the GPU (blsgpu_g1_poly_check): the commitment lists are deduplicated into
+        polynomials, every fragment is one lane of a Horner evaluation in the exponent.  The assertions of the single
+        call run for every element first.  Lists holding anything but on-curve G1 AffinePoints, fragments that are
+        neither an Fq mod n nor an int in [1, n) and players that are not ints take the host loop; a polynomial with a
+        commitment C_k (k >= 1) outside the order-n subgroup (where Horner's x^k and the reference's x^k mod n differ)
+        is decided exactly by one grouped multi-scalar sum with the scalars x^k mod n."""
+        secret_fragments, players, commitments = list(secret_fragments), list(players), list(commitments)
+        if not (len(secret_fragments) == len(players) == len(commitments)):
+            raise ValueError("need one player and one commitment list per fragment")
+        for s, p, C in zip(secret_fragments, players, commitments):
+            assert len(C) == T
+            assert s != 0
+            assert p != 0
+        n = ec.n
+        host_only = T < 1 or ec is not default_ec          # (the device knows the one curve, and t >= 1)
+        results = [None] * len(players)
+        polys, by_id, by_content = [], {}, {}      # device polynomials: commitment lists deduplicated
+        dev = []                                   # (fragment, polynomial)
+        for i, (s, p, C) in enumerate(zip(secret_fragments, players, commitments)):
+            j = by_id.get(id(C))
+            if j is None:
+                key = _g1_content(C)
+                j = -1 if key is None else by_content.get(key)
+                if j is None:
+                    j = by_content[key] = len(polys)
+                    polys.append(C)
+                by_id[id(C)] = j
+            if (j < 0 or host_only or type(p) is not int
+                    or not ((type(s) is Fq and s.Q == n) or (type(s) is int and 0 < s < n))):
+                results[i] = Threshold.verify_secret_fragment(T, s, p, C, ec)
+            else:
+                dev.append((i, j))
+        if not dev:
+            return results
+        from . import backend
+        dev.sort(key=lambda e: e[1])               # a wavefront reads one polynomial
+        commit = b"".join(H.g1_affine_bytes(pt._aff()) for C in polys for pt in C)
+        xb = b"".join((players[i] % n).to_bytes(32, "big") for i, _ in dev)
+        sb = b"".join(int(secret_fragments[i]).to_bytes(32, "big") for i, _ in dev)
+        status, _ = backend.get().g1_poly_check(commit, len(polys), T, [j for _, j in dev], xb, sb)
+        undecided = []
+        for (i, j), st in zip(dev, status):
+            if st == 2:
+                undecided.append((i, j))
+            else:
+                results[i] = st == 1
+        if undecided:
+            # sum_k (x^k mod n) C_k exactly as the reference forms it (C_0 with 1), against (s mod n) G1
+            from .bls import _g1_sums
+            sums = _g1_sums([[pt.to_jacobian() for pt in polys[j]] for _, j in undecided],
+                            [[pow(players[i], k, n) for k in range(T)] for i, _ in undecided])
+            lhs, _ = backend.get().g1_mul_gen(b"".join(int(secret_fragments[i]).to_bytes(32, "big") for i, _ in undecided))
+            for e, ((i, _), J) in enumerate(zip(undecided, sums)):
+                rhs = bytes(96) if J.infinity else H.g1_affine_bytes(J.to_affine()._aff())
+                results[i] = lhs[96 * e:96 * (e + 1)] == rhs
+        return results
+
+    @staticmethod
     def aggregate_unit_sigs(signatures, players, T, ec=default_ec):
         """sum_i lambda_i * sig_i  (a |players|-point G2 multi-scalar multiplication)."""
         from .bls import _g2_sum
         lam = Threshold.lagrange_coeffs_at_zero(players, ec)
         return Signature.from_g2(_g2_sum([sig.value for sig in signatures], [int(l) for l in lam]))
+
+
+def _g1_content(C):
+    """the content key of a commitment list whose every element is an on-curve G1 AffinePoint (the device's input), or
+    None (the host loop takes it)"""
+    key = []
+    for pt in C:
+        if type(pt) is not AffinePoint or pt.FE is not Fq or pt.x.Q != FIELD_Q or pt.y.Q != FIELD_Q:
+            return None
+        if pt.infinity:
+            key.append(None)
+        elif pt.is_on_curve():
+            key.append((pt.x.Z, pt.y.Z))
+        else:
+            return None
+    return tuple(key)

@@ -23,6 +23,7 @@
 #include "blsgpu_g1w.hip"
 #include "blsgpu_msm.hip"
 #include "blsgpu_g1fix.hip"
+#include "blsgpu_g1poly.hip"
 #include "blsgpu_h2c.hip"
 #include "blsgpu_h2cw.hip"
 #include "blsgpu_probe.hip"
@@ -122,6 +123,8 @@ struct blsgpu_ctx {
     uint32_t* d_fix_table = nullptr;   // the fixed-base G1 table (blsgpu_g1fix.hip), built on first use; freed by blsgpu_ctx_destroy only
     void* d_fix_ws = nullptr;          // blsgpu_hd_children*: the parent key, a flag word and one slice of HMAC outputs
     size_t fix_ws_cap = 0;
+    void* d_poly_ws = nullptr;         // blsgpu_g1_poly_check*: a flag word, the subgroup flags and the commitments in L28 form
+    size_t poly_ws_cap = 0;
     hipEvent_t bulk_event = nullptr;   // caller's event, recorded after the last chip-filling kernel of a Miller stage
     size_t msm_part_cap = 0;           // in u32
     // optional per-kernel timing (blsgpu_timing_enable): HIP events recorded on
@@ -758,6 +761,84 @@ int hd_children_dev(blsgpu_ctx* c, const uint8_t chain_code[32], const uint8_t p
     }
     return 0;
 }
+// ------------------------------------------------------------ Feldman share checks (blsgpu_g1poly.hip) --
+// the arguments every form checks before anything is written (after t == 0 and n == 0)
+int poly_args(size_t n_polys, size_t t, const void* commit, const void* poly, const void* x, const void* s, const void* status,
+              const void* out_aff) {
+    if (!commit || !poly || !x) return fail(-EINVAL, "NULL argument");
+    if (!s != !status) return fail(-EINVAL, "s and status must be NULL together");
+    if (!status && !out_aff) return fail(-EINVAL, "ask for status or out_aff");
+    if (n_polys == 0) return fail(-EINVAL, "polynomial index out of range");
+    if (n_polys > 0x7FFFFFFFull / t) return fail(-EINVAL, "too many commitments");
+    return 0;
+}
+
+// workspace: [0, 4) index-check flag, [256, o_l28) subgroup flags (one word per polynomial), [o_l28, ..) the L28 commitments
+size_t poly_ws_l28(size_t n_polys) { return 256 + (n_polys * 4 + 255) / 256 * 256; }
+int poly_ws(blsgpu_ctx* c, size_t n_polys, size_t t) {
+    return grow_buffer(c, &c->d_poly_ws, &c->poly_ws_cap, poly_ws_l28(n_polys) + n_polys * t * blsgpu::g1poly::ENTRY_DW * 4);
+}
+
+// the commitments of the call, once: L28 entries, then the subgroup flags (caller: StreamGuard, poly_ws)
+int poly_prep(blsgpu_ctx* c, const void* d_commit, size_t n_polys, size_t t, bool table, hipStream_t st) {
+    using namespace blsgpu::g1poly;
+    if (table) {
+        if (int rc = fix_table(c, st)) return rc;
+    }
+    char* ws = (char*)c->d_poly_ws;
+    const size_t m = n_polys * t;
+    uint32_t* l28 = (uint32_t*)(ws + poly_ws_l28(n_polys));
+    HIP_TRY(hipMemsetAsync(ws + 256, 0, n_polys * 4, st));
+    hipLaunchKernelGGL(k_poly_prep, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_commit, (uint32_t)m, l28);
+    HIP_TRY(hipGetLastError());
+    if (t > 1) {
+        const size_t mk = n_polys * (t - 1);
+        hipLaunchKernelGGL(k_poly_subgroup, dim3((unsigned)((mk + 255) / 256)), dim3(256), 0, st, (const uint32_t*)l28, (uint32_t)n_polys,
+                           (uint32_t)t, (uint32_t*)(ws + 256));
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+// n fragments against the prepared commitments, FIX_SLICE per launch (caller: StreamGuard, poly_prep)
+int poly_eval_launch(blsgpu_ctx* c, size_t n_polys, size_t t, const void* d_poly, const void* d_x, const void* d_s, size_t n, void* d_status,
+                     void* d_out_aff, hipStream_t st) {
+    char* ws = (char*)c->d_poly_ws;
+    for (size_t lo = 0; lo < n; lo += FIX_SLICE) {
+        const size_t m = n - lo < FIX_SLICE ? n - lo : FIX_SLICE;
+        hipLaunchKernelGGL(blsgpu::g1poly::k_poly_eval, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
+                           (const uint32_t*)c->d_fix_table, (const uint32_t*)(ws + poly_ws_l28(n_polys)), (const uint32_t*)(ws + 256),
+                           (uint32_t)n_polys, (uint32_t)t, (const uint32_t*)d_poly + lo, (const uint32_t*)d_x + lo * 8,
+                           d_s ? (const uint32_t*)d_s + lo * 8 : nullptr, (uint32_t)m, d_status ? (uint8_t*)d_status + lo : nullptr,
+                           d_out_aff ? (uint32_t*)d_out_aff + lo * 24 : nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+// the _dev form: a device scan of the indices and one synchronising read of its flag first (-EINVAL before anything is written)
+int poly_check_dev(blsgpu_ctx* c, const void* d_commit, size_t n_polys, size_t t, const void* d_poly, const void* d_x, const void* d_s,
+                   size_t n, void* d_status, void* d_out_aff, hipStream_t st) {
+    if (t == 0) return fail(-EINVAL, "t must be at least 1");
+    if (n == 0) return 0;
+    if (int rc = poly_args(n_polys, t, d_commit, d_poly, d_x, d_s, d_status, d_out_aff)) return rc;
+    StreamGuard sg(c, st);
+    if (int rc = poly_ws(c, n_polys, t)) return rc;
+    uint32_t* flag = (uint32_t*)c->d_poly_ws;
+    HIP_TRY(hipMemsetAsync(flag, 0, 4, st));
+    for (size_t lo = 0; lo < n; lo += FIX_SLICE) {
+        const size_t m = n - lo < FIX_SLICE ? n - lo : FIX_SLICE;
+        hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_poly + lo,
+                           (uint32_t)m, (uint32_t)n_polys, flag);
+        HIP_TRY(hipGetLastError());
+    }
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (bad) return fail(-EINVAL, "polynomial index out of range");
+    if (int rc = poly_prep(c, d_commit, n_polys, t, d_status != nullptr, st)) return rc;
+    return poly_eval_launch(c, n_polys, t, d_poly, d_x, d_s, n, d_status, d_out_aff, st);
+}
 }  // namespace
 
 
@@ -932,6 +1013,7 @@ BLSGPU_EXPORT void blsgpu_ctx_destroy(blsgpu_ctx* c) {
     if (c->d_h2c_ws) (void)hipFree(c->d_h2c_ws);
     if (c->d_fix_table) (void)hipFree(c->d_fix_table);
     if (c->d_fix_ws) (void)hipFree(c->d_fix_ws);
+    if (c->d_poly_ws) (void)hipFree(c->d_poly_ws);
     for (void* q : c->retired) (void)hipFree(q);
     if (c->last_event) (void)hipEventDestroy(c->last_event);
     if (c->ev0) {
@@ -1115,8 +1197,9 @@ BLSGPU_EXPORT int blsgpu_ctx_workspace_bytes(blsgpu_ctx* c, size_t out[BLSGPU_WS
     out[BLSGPU_WS_SLOTS] = c->fexp_ws_cap + c->h2c_ws_cap;
     size_t total = 0;
     for (int i = 0; i < BLSGPU_WS_TOTAL; i++) total += out[i];
-    // the fixed-base table and the HD derivation slice have no field of their own: they count in the total only
-    total += (c->d_fix_table ? blsgpu::g1fix::TABLE_BYTES : 0) + c->fix_ws_cap;
+    // the fixed-base table, the HD derivation slice and the share-check commitments have no field of their own: they
+    // count in the total only
+    total += (c->d_fix_table ? blsgpu::g1fix::TABLE_BYTES : 0) + c->fix_ws_cap + c->poly_ws_cap;
     out[BLSGPU_WS_TOTAL] = total;
     return 0;
 }
@@ -2059,6 +2142,50 @@ BLSGPU_EXPORT int blsgpu_hd_children_dev(blsgpu_ctx* c, const uint8_t chain_code
     HIP_TRY(hipSetDevice(c->device));
     return hd_children_dev(c, chain_code, parent_pk_aff, parent_sk, d_indices, n, d_out_chain, d_out_sk, d_out_pk_aff, d_out_pk_ser, true,
                            (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------ Feldman share checks --
+BLSGPU_EXPORT int blsgpu_g1_poly_check(blsgpu_ctx* c, const uint8_t* commit, size_t n_polys, size_t t, const uint32_t* poly, const uint8_t* x,
+                                       const uint8_t* s, size_t n, uint8_t* status, uint8_t* out_aff) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (t == 0) return fail(-EINVAL, "t must be at least 1");
+    if (n == 0) return 0;
+    if (int rc = poly_args(n_polys, t, commit, poly, x, s, status, out_aff)) return rc;
+    for (size_t i = 0; i < n; i++)
+        if (poly[i] >= n_polys) return fail(-EINVAL, "polynomial index out of range");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE;
+    const size_t o_poly = (n_polys * t * 96 + 255) / 256 * 256, o_x = o_poly + S * 4, o_s = o_x + S * 32, o_st = o_s + (s ? S * 32 : 0);
+    const size_t o_aff = o_st + (status ? (S + 255) / 256 * 256 : 0);
+    if (int rc = grow_buffer(c, &c->d_io, &c->io_cap, o_aff + (out_aff ? S * 96 : 0) + 64)) return rc;
+    char* d = (char*)c->d_io;
+    HIP_TRY(hipMemcpyAsync(d, commit, n_polys * t * 96, hipMemcpyHostToDevice, 0));
+    {
+        StreamGuard sg(c, nullptr);
+        if (int rc = poly_ws(c, n_polys, t)) return rc;
+        if (int rc = poly_prep(c, d, n_polys, t, status != nullptr, nullptr)) return rc;
+    }
+    for (size_t lo = 0; lo < n; lo += S) {
+        const size_t m = n - lo < S ? n - lo : S;
+        HIP_TRY(hipMemcpyAsync(d + o_poly, poly + lo, m * 4, hipMemcpyHostToDevice, 0));
+        HIP_TRY(hipMemcpyAsync(d + o_x, x + lo * 32, m * 32, hipMemcpyHostToDevice, 0));
+        if (s) HIP_TRY(hipMemcpyAsync(d + o_s, s + lo * 32, m * 32, hipMemcpyHostToDevice, 0));
+        {
+            StreamGuard sg(c, nullptr);
+            if (int rc = poly_eval_launch(c, n_polys, t, d + o_poly, d + o_x, s ? d + o_s : nullptr, m, status ? d + o_st : nullptr,
+                                          out_aff ? d + o_aff : nullptr, nullptr))
+                return rc;
+        }
+        if (status) HIP_TRY(hipMemcpy(status + lo, d + o_st, m, hipMemcpyDeviceToHost));
+        if (out_aff) HIP_TRY(hipMemcpy(out_aff + lo * 96, d + o_aff, m * 96, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+BLSGPU_EXPORT int blsgpu_g1_poly_check_dev(blsgpu_ctx* c, const void* d_commit, size_t n_polys, size_t t, const void* d_poly, const void* d_x,
+                                           const void* d_s, size_t n, void* d_status, void* d_out_aff, void* stream) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    return poly_check_dev(c, d_commit, n_polys, t, d_poly, d_x, d_s, n, d_status, d_out_aff, (hipStream_t)stream);
 }
 
 #ifdef BLSGPU_STAMPS

@@ -34,6 +34,19 @@ __device__ __forceinline__ void to_affine_raw(const r28::ptT<r28::fe>& a, uint32
     r28::to_raw(y, r28::mul(a.Y, zi));
 }
 
+// acc += s G1 for s < 2^256 given as 8 little-endian words (reduce mod n first for s mod n): one complete mixed addition
+// per non-zero 8-bit digit, gathered from the table (k_fix_mul, and the left-hand side of k_poly_eval in blsgpu_g1poly.hip)
+__device__ __forceinline__ void fix_sum(const uint32_t* __restrict__ table, const uint32_t s[8], r28::ptT<r28::fe>& acc) {
+#pragma unroll 1
+    for (uint32_t w = 0; w < WINDOWS; w++) {
+        const uint32_t d = (s[w >> 2] >> ((w & 3u) * 8u)) & 255u;
+        if (d) {
+            const uint32_t* p = table + (size_t)(w * DIGITS + d - 1u) * ENTRY_DW;
+            r28::pmadd(acc, r28::ld(p), r28::ld(p + r28::NL));
+        }
+    }
+}
+
 // The table: entry e = w * 255 + d - 1 holds d 2^(8w) G1 -- one entry per lane, double-and-add over the 8 bits of d, then 8w
 // doublings, then the affine form.  Once per context (a few hundred microseconds).
 __global__ void __launch_bounds__(64) k_fix_table(Gen g, uint32_t* __restrict__ table)
@@ -83,14 +96,7 @@ __global__ void __launch_bounds__(256) k_fix_mul(const uint32_t* __restrict__ ta
         for (int w = 0; w < 12; w++) { x[11 - w] = bswap32(a[w]); y[11 - w] = bswap32(a[12 + w]); any |= x[11 - w] | y[11 - w]; }
         if (any) r28::pmadd(acc, r28::from_raw(x), r28::from_raw(y));
     }
-#pragma unroll 1
-    for (uint32_t w = 0; w < WINDOWS; w++) {
-        const uint32_t d = (s[w >> 2] >> ((w & 3u) * 8u)) & 255u;
-        if (d) {
-            const uint32_t* p = table + (size_t)(w * DIGITS + d - 1u) * ENTRY_DW;
-            r28::pmadd(acc, r28::ld(p), r28::ld(p + r28::NL));
-        }
-    }
+    fix_sum(table, s, acc);
     uint32_t x[12], y[12];
     to_affine_raw(acc, x, y);
     if (out_aff) {
