@@ -1400,11 +1400,11 @@ static int launch_miller_ls(blsgpu_ctx* c, const void* d_g1, const void* d_g2, c
                                (const uint32_t*)d_g2, (uint32_t)n, (int32_t*)c->d_lines, (uint8_t*)c->d_bad, dg);
         } else if (n <= c->ls_quad_max) {                // few pairs: four lanes each, the tangent step's levels shared by the two pairs
             const WaveShape ws = wave_shape(c, (4 * n + 63) / 64);
-            hipLaunchKernelGGL(ml::k_ml_lines4, dim3(ws.blocks), dim3(ws.threads), 0, st, (const uint32_t*)d_g1,
+            hipLaunchKernelGGL(ml::k_ml_lines4, dim3(ws.blocks), dim3(ws.threads), ws.threads * ml::sp::SLAB_BYTES_PER_LANE, st, (const uint32_t*)d_g1,
                                (const uint32_t*)d_g2, (uint32_t)n, (int32_t*)c->d_lines, (uint8_t*)c->d_bad, dg);
         } else {
             const WaveShape ws = wave_shape(c, (2 * n + 63) / 64);
-            hipLaunchKernelGGL(ml::k_ml_lines2, dim3(ws.blocks), dim3(ws.threads), 0, st, (const uint32_t*)d_g1,
+            hipLaunchKernelGGL(ml::k_ml_lines2, dim3(ws.blocks), dim3(ws.threads), ws.threads * ml::sp::SLAB_BYTES_PER_LANE, st, (const uint32_t*)d_g1,
                                (const uint32_t*)d_g2, (uint32_t)n, (int32_t*)c->d_lines, (uint8_t*)c->d_bad, dg);
         }
     }

@@ -202,7 +202,34 @@ template <int M> __device__ __forceinline__ void store_part(int32_t* __restrict_
     for (int j = 0; j < NL; j++) o[j] = x.v[j];
 }
 
-__device__ __forceinline__ void tangent_step(h& X, h& Y, h& Z, const fe& px3n, const fe& py, int32_t* __restrict__ rec) {
+// The chain's per-pair constants in LDS (round 6): -3 px, py and the lane's parts of Q's coordinates, read at the point of
+// use.  Held in registers they were the first values the allocator spilled -- 48 VGPRs at two wavefronts per SIMD --, and
+// each scratch reload waited on vmcnt(0), which on gfx9 also counts the line-record stores just issued; an LDS read waits
+// on lgkmcnt only.  The lane's column of its wavefront's slab: slot k limb j at p[(k NL + j) 64], 4 NL dwords per lane.
+typedef __attribute__((address_space(3))) int32_t lds_i32;
+constexpr int SLAB_SLOTS = 4;                           // -3 px, py, Q.x part, Q.y part
+constexpr int SLAB_BYTES_PER_LANE = SLAB_SLOTS * NL * 4;
+struct Slab {
+    lds_i32* p;
+    template <class T> __device__ __forceinline__ void put(int k, const T& x) const {
+#pragma unroll
+        for (int j = 0; j < NL; j++) p[(k * NL + j) * 64] = x.v[j];
+    }
+    template <class T> __device__ __forceinline__ T get(int k) const {
+        lds_i32* q = p;
+        asm volatile("" : "+v"(q));                     // opaque per use: the reads stay here, not hoisted out of the loops
+        T r;
+#pragma unroll
+        for (int j = 0; j < NL; j++) r.v[j] = q[(k * NL + j) * 64];
+        return r;
+    }
+    __device__ __forceinline__ fe px3n() const { return get<fe>(0); }
+    __device__ __forceinline__ fe py() const { return get<fe>(1); }
+    __device__ __forceinline__ h xq() const { return get<h>(2); }
+    __device__ __forceinline__ h yq() const { return get<h>(3); }
+};
+
+__device__ __forceinline__ void tangent_step(h& X, h& Y, h& Z, const Slab& k, int32_t* __restrict__ rec) {
     // (the statements are asm volatile underneath, so this order IS the execution order: every value is consumed as
     // early as the data flow allows, which keeps the step inside 256 registers)
     // Round 4: the two mixed products as squares -- 2YZ = (Y + Z)^2 - Y^2 - Z^2 and 2XY = (X + Y)^2 - X^2 - Y^2 with the
@@ -210,11 +237,11 @@ __device__ __forceinline__ void tangent_step(h& X, h& Y, h& Z, const fe& px3n, c
     // of two (588); the sums are normalised first (a square of 2^29-limbs would not fit the columns).  Same field
     // elements, same line records.
     const h XX = sqr(X);
-    store_part(rec, 1, mulf(XX, px3n));                               // X^2 (-3 px)
+    store_part(rec, 1, mulf(XX, k.px3n()));                           // X^2 (-3 px)
     const h C = sqr(Z);
     const h B = sqr(Y);
     const S<3> H = sub(sub(sqr(norm(add(Y, Z))), B), C);              // 2YZ
-    store_part(rec, 2, mulf(H, py));                                  // 2YZ py
+    store_part(rec, 2, mulf(H, k.py()));                              // 2YZ py
     const h z8 = mulc_norm<4>(H);                                     // 8YZ
     const h E = b3(C);
     const S<3> A2 = sub(sub(sqr(norm(add(X, Y))), XX), B);            // 2XY
@@ -225,20 +252,19 @@ __device__ __forceinline__ void tangent_step(h& X, h& Y, h& Z, const fe& px3n, c
     Y = sqr_m12sqr(G, E);                                             // G^2 - 12 E^2: one sum of two products (round 4: two squares, 2 x 392 + the scaling)
     Z = mul(left(B), right(z8));
 }
-__device__ __forceinline__ void chord_step(h& X, h& Y, h& Z, const h& xq, const h& yq, const fe& px3n, const fe& py3,
-                                           int32_t* __restrict__ rec) {
+__device__ __forceinline__ void chord_step(h& X, h& Y, h& Z, const Slab& k, int32_t* __restrict__ rec) {
     const Rop<1> rz = right(Z);
-    const h th = norm(sub(Y, mul(left(yq), rz))), la = norm(sub(X, mul(left(xq), rz)));
+    const h th = norm(sub(Y, mul(left(k.yq()), rz))), la = norm(sub(X, mul(left(k.xq()), rz)));
     const Lop<1> lth = left(th), lla = left(la);
     const h C = sqr(th), D = sqr(la);
     const Rop<1> rd = right(D);
     const h E = mul(lla, rd), Fz = mul(left(Z), right(C)), Gg = mul(left(X), rd);
     const h H = norm(sub(add(E, Fz), add(Gg, Gg)));
     const h GH = norm(sub(Gg, H));
-    const h xq3 = mulc_norm<3>(xq), nyq3 = mulc_norm<3>(neg(yq));
+    const h xq3 = mulc_norm<3>(k.xq()), nyq3 = mulc_norm<3>(neg(k.yq()));
     store_part(rec, 0, dot2(lth, right(xq3), lla, right(nyq3)));
-    store_part(rec, 1, mulf(th, px3n));
-    store_part(rec, 2, mulf(la, py3));
+    store_part(rec, 1, mulf(th, k.px3n()));
+    store_part(rec, 2, mulf(la, r28::mulc_norm<3>(k.py())));
     const h nE = norm(neg(E));
     const h Y3 = dot2(lth, right(GH), left(nE), right(Y));
     X = mul(lla, right(H));
@@ -275,7 +301,7 @@ template <int W, int M> __device__ __forceinline__ S<W> widen(const S<M>& x) {  
 // The tangent step of sp::tangent_step dealt out over the two pairs: level 1 the five squares (X^2, Y^2, (X + Y)^2 | Z^2,
 // (Y + Z)^2), level 2 {2XY (B - F), G^2, X^2 (-3 px) | B 8YZ, E^2, 2YZ py}: 3 squares + product + square + product by an Fq
 // value deep (2548 multiply-adds per lane) instead of 4718.  Pair 0 stores the line's coefficients 0 and 1, pair 1 the third.
-__device__ __forceinline__ void tangent_step(h& X, h& Y, h& Z, const fe& px3n, const fe& py, int32_t* __restrict__ rec) {
+__device__ __forceinline__ void tangent_step(h& X, h& Y, h& Z, const Slab& k, int32_t* __restrict__ rec) {
     const h sa = sqr(pick(X, Z)), sb = sqr(pick(Y, norm(add(Y, Z)))), sc = sqr(norm(add(X, Y)));
     const h oa = oth(sa), ob = oth(sb);
     const h XX = pick(sa, oa), C = pick(oa, sa), B = pick(sb, ob), T1 = pick(ob, sb);
@@ -287,9 +313,7 @@ __device__ __forceinline__ void tangent_step(h& X, h& Y, h& Z, const fe& px3n, c
     if (!hi()) store_part(rec, 0, sub(B, E));
     const S<3> F3 = mulc<3>(E);
     const h BmF = norm(sub(B, F3)), G = norm(add(B, F3));
-    fe kf;
-#pragma unroll
-    for (int j = 0; j < NL; j++) kf.v[j] = hi() ? py.v[j] : px3n.v[j];
+    const fe kf = k.get<fe>(hi() ? 1 : 0);                            // py | -3 px
     const h lc = mulf(pick(widen<3>(XX), H), kf);                      // X^2 (-3 px) | 2YZ py
     {
         int32_t* o = rec + ((hi() ? 2 : 1) * 2 + (odd() ? 1 : 0)) * NL;
@@ -305,29 +329,43 @@ __device__ __forceinline__ void tangent_step(h& X, h& Y, h& Z, const fe& px3n, c
 }
 }  // namespace sq
 
-// Two lanes per pair (lane 2p: real parts, lane 2p + 1: imaginary parts).  Same lines, flags and work list as k_ml_lines.
-#ifndef BLSGPU_ML_LINES2_WAVES
-#define BLSGPU_ML_LINES2_WAVES 2
-#endif
-__global__ void __launch_bounds__(256, BLSGPU_ML_LINES2_WAVES) k_ml_lines2(const uint32_t* __restrict__ g1, const uint32_t* __restrict__ g2, uint32_t n,
-                                                                           int32_t* __restrict__ lines, uint8_t* __restrict__ bad, DegenList dg)
-#if BLSGPU_EMIT(BLSGPU_TU_ML)
-{
+// The runs of tangent steps between the chord steps of ML_NX, 6 bits each: bits 62 | 61 60 | 59 - 57 | 56 - 48 | 47 - 16 | 15 - 0.
+constexpr uint64_t ml_runs() {
+    uint64_t r = 0;
+    int s = 0, k = 0;
+    for (int bit = 62; bit >= 0; bit--) {
+        k++;
+        if ((ML_NX >> bit) & 1ull) { r |= (uint64_t)k << (6 * s++); k = 0; }
+    }
+    return r | (uint64_t)k << (6 * s);
+}
+constexpr uint64_t ML_RUNS = ml_runs();
+static_assert(ML_RUNS == (1ull | 2ull << 6 | 3ull << 12 | 9ull << 18 | 32ull << 24 | 16ull << 30), "tangent runs of |x|");
+
+// The point chain of k_ml_lines2 (QUAD = false: two lanes per pair) and k_ml_lines4 (QUAD = true: four).  The tangent runs
+// are a loop of their own and the five chord steps sit between them (round 6): the allocator sees the tangent step alone.
+// Launched with SLAB_BYTES_PER_LANE of dynamic LDS per thread (the constants of the steps, sp::Slab).
+template <bool QUAD>
+__device__ __forceinline__ void lines_chain(const uint32_t* __restrict__ g1, const uint32_t* __restrict__ g2, uint32_t n,
+                                            int32_t* __restrict__ lines, uint8_t* __restrict__ bad, DegenList dg) {
+    extern __shared__ int32_t ml_slab[];
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t pr = t >> 1;
+    const uint32_t pr = t >> (QUAD ? 2 : 1);
     const uint32_t p = pr < n ? pr : n - 1u;                      // the last wavefront's spare lanes repeat the last pair
     const uint32_t part = t & 1u;
     const uint32_t* s1 = g1 + (size_t)p * 24;
     const uint32_t* s2 = g2 + (size_t)p * 48 + part * 12;
-    fe px3n, pyv;
+    const sp::Slab sl{(sp::lds_i32*)ml_slab + (threadIdx.x >> 6) * (sp::SLAB_SLOTS * NL * 64) + (threadIdx.x & 63u)};
     sp::h X, Y, Z;
     bool ok = !q_flagged(dg, p);
     {
         const fe px = load_coord(s1), py = load_coord(s1 + 12);
-        px3n = r28::mulc_norm<3>(r28::neg(px));
-        pyv = py;
+        sl.put(0, r28::mulc_norm<3>(r28::neg(px)));
+        sl.put(1, py);
         X = sp::load_part(s2);
         Y = sp::load_part(s2 + 24);
+        sl.put(2, X);
+        sl.put(3, Y);
         const int32_t one[NL] = BLS28_ONE;
 #pragma unroll
         for (int j = 0; j < NL; j++) Z.v[j] = part ? 0 : one[j];
@@ -340,27 +378,43 @@ __global__ void __launch_bounds__(256, BLSGPU_ML_LINES2_WAVES) k_ml_lines2(const
         const auto d = sp::sub(sp::sub(yy, xxx), four);              // S<6>
         ok = ok && sp::is_zero2(sp::mulf(d, r28::fe_one()));
     }
-    int32_t* rec = lines + (size_t)p * LINE_DW;
+    // line L's records start at row = lines + L n LINE_DW, the same for the whole wavefront (SGPRs); the pair's record is a
+    // 32-bit offset from there (n LINE_DW dwords fit: the 68 rows of a call are far below 2^32 bytes each)
+    int32_t* row = lines;
+    const uint32_t roff = p * (uint32_t)LINE_DW;
     const size_t lstride = (size_t)n * LINE_DW;
 #pragma unroll 1
-    for (int bit = 62; bit >= 0; bit--) {
-        sp::tangent_step(X, Y, Z, px3n, pyv, rec);
-        rec += lstride;
-        if ((ML_NX >> bit) & 1ull) {
-            const sp::h xq = sp::load_part(s2), yq = sp::load_part(s2 + 24);
-            const fe py3 = r28::mulc_norm<3>(load_coord(s1 + 12));
-            sp::chord_step(X, Y, Z, xq, yq, px3n, py3, rec);
-            rec += lstride;
+    for (int s = 0;; s++) {
+        const int run = (int)((ML_RUNS >> (6 * s)) & 63u);
+#pragma unroll 1
+        for (int i = 0; i < run; i++) {
+            if (QUAD) sq::tangent_step(X, Y, Z, sl, row + roff);
+            else sp::tangent_step(X, Y, Z, sl, row + roff);
+            row += lstride;
         }
+        if (s == 5) break;
+        sp::chord_step(X, Y, Z, sl, row + roff);                 // (k_ml_lines4: both pairs run it whole and store the same record)
+        row += lstride;
     }
     ok = ok && !sp::is_zero2(Z);
-    if (part == 0 && pr < n) {
+    if ((t & (QUAD ? 3u : 1u)) == 0u && pr < n) {
         bad[p] = ok ? 0 : 1;
         if (!ok) {
             const uint32_t at = atomicAdd(dg.count, 1u);
             dg.blocks[at] = p;
         }
     }
+}
+
+// Two lanes per pair (lane 2p: real parts, lane 2p + 1: imaginary parts).  Same lines, flags and work list as k_ml_lines.
+#ifndef BLSGPU_ML_LINES2_WAVES
+#define BLSGPU_ML_LINES2_WAVES 2
+#endif
+__global__ void __launch_bounds__(256, BLSGPU_ML_LINES2_WAVES) k_ml_lines2(const uint32_t* __restrict__ g1, const uint32_t* __restrict__ g2, uint32_t n,
+                                                                           int32_t* __restrict__ lines, uint8_t* __restrict__ bad, DegenList dg)
+#if BLSGPU_EMIT(BLSGPU_TU_ML)
+{
+    lines_chain<false>(g1, g2, n, lines, bad, dg);
 }
 #else
 ;
@@ -373,54 +427,7 @@ __global__ void __launch_bounds__(256, BLSGPU_ML_LINES2_WAVES) k_ml_lines4(const
                                                                            int32_t* __restrict__ lines, uint8_t* __restrict__ bad, DegenList dg)
 #if BLSGPU_EMIT(BLSGPU_TU_ML)
 {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t pr = t >> 2;
-    const uint32_t p = pr < n ? pr : n - 1u;                      // the last wavefront's spare lanes repeat the last pair
-    const uint32_t part = t & 1u;
-    const uint32_t* s1 = g1 + (size_t)p * 24;
-    const uint32_t* s2 = g2 + (size_t)p * 48 + part * 12;
-    fe px3n, pyv;
-    sp::h X, Y, Z;
-    bool ok = !q_flagged(dg, p);
-    {
-        const fe px = load_coord(s1), py = load_coord(s1 + 12);
-        px3n = r28::mulc_norm<3>(r28::neg(px));
-        pyv = py;
-        X = sp::load_part(s2);
-        Y = sp::load_part(s2 + 24);
-        const int32_t one[NL] = BLS28_ONE;
-#pragma unroll
-        for (int j = 0; j < NL; j++) Z.v[j] = part ? 0 : one[j];
-        // Q on the twist: y^2 - x^3 - 4 (1 + u) = 0
-        const sp::h yy = sp::sqr(Y), xx = sp::sqr(X);
-        const sp::h xxx = sp::mul(sp::left(xx), sp::right(X));
-        sp::S<4> four;
-#pragma unroll
-        for (int j = 0; j < NL; j++) four.v[j] = 4 * one[j];
-        const auto d = sp::sub(sp::sub(yy, xxx), four);              // S<6>
-        ok = ok && sp::is_zero2(sp::mulf(d, r28::fe_one()));
-    }
-    int32_t* rec = lines + (size_t)p * LINE_DW;
-    const size_t lstride = (size_t)n * LINE_DW;
-#pragma unroll 1
-    for (int bit = 62; bit >= 0; bit--) {
-        sq::tangent_step(X, Y, Z, px3n, pyv, rec);
-        rec += lstride;
-        if ((ML_NX >> bit) & 1ull) {
-            const sp::h xq = sp::load_part(s2), yq = sp::load_part(s2 + 24);
-            const fe py3 = r28::mulc_norm<3>(load_coord(s1 + 12));
-            sp::chord_step(X, Y, Z, xq, yq, px3n, py3, rec);      // (five of 68 steps: both pairs run it whole and store the same record)
-            rec += lstride;
-        }
-    }
-    ok = ok && !sp::is_zero2(Z);
-    if ((t & 3u) == 0u && pr < n) {
-        bad[p] = ok ? 0 : 1;
-        if (!ok) {
-            const uint32_t at = atomicAdd(dg.count, 1u);
-            dg.blocks[at] = p;
-        }
-    }
+    lines_chain<true>(g1, g2, n, lines, bad, dg);
 }
 #else
 ;
