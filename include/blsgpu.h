@@ -335,6 +335,19 @@ int blsgpu_g1_poly_check(blsgpu_ctx *ctx, const uint8_t *commit, size_t n_polys,
 int blsgpu_g1_poly_check_dev(blsgpu_ctx *ctx, const void *d_commit, size_t n_polys, size_t t, const void *d_poly,
                              const void *d_x, const void *d_s, size_t n, void *d_status, void *d_out_aff, void *stream);
 
+/* Subgroup membership for n affine points at once: pts is n x 96 B (G1: x || y) or n x 192 B (G2: x.c0 x.c1 y.c0 y.c1),
+ * big-endian, all zero = infinity.  status[i] = 1 if point i is on the curve and in the order-n subgroup (infinity
+ * included), 2 if it is on the curve but outside the subgroup, 0 if it is off the curve.  n == 0 writes nothing and
+ * returns 0; NULL pts or status with n > 0: -EINVAL before anything is written.
+ * One point per lane (csrc/blsgpu_subgroup.hip): G1 tests phi(P) == -[u^2] P (127 doublings, 16 additions), G2 tests
+ * psi(Q) == [u] Q (63 doublings, 5 additions on the twist); projective comparison, no inversion.  The work follows the
+ * public bits of u only. */
+int blsgpu_g1_subgroup_check(blsgpu_ctx *ctx, const uint8_t *pts, size_t n, uint8_t *status);
+int blsgpu_g2_subgroup_check(blsgpu_ctx *ctx, const uint8_t *pts, size_t n, uint8_t *status);
+/* The same with both buffers in device memory, enqueued on `stream` (no synchronisation). */
+int blsgpu_g1_subgroup_check_dev(blsgpu_ctx *ctx, const void *d_pts, size_t n, void *d_status, void *stream);
+int blsgpu_g2_subgroup_check_dev(blsgpu_ctx *ctx, const void *d_pts, size_t n, void *d_status, void *stream);
+
 /* Measurement aid (bench.py): when enabled, HIP events are recorded on the
  * launch stream around every kernel this context launches (up to 1024 launches
  * between reads).  blsgpu_timing_read waits for them and returns, per launch,

@@ -27,6 +27,7 @@ SYMBOLS = (
     "blsgpu_ctx_workspace_bytes", "blsgpu_verify_pipeline", "blsgpu_verify_pipeline_dev",
     "blsgpu_g1_mul_gen", "blsgpu_g1_mul_gen_dev", "blsgpu_hd_children", "blsgpu_hd_children_dev",
     "blsgpu_g1_poly_check", "blsgpu_g1_poly_check_dev",
+    "blsgpu_g1_subgroup_check", "blsgpu_g1_subgroup_check_dev", "blsgpu_g2_subgroup_check", "blsgpu_g2_subgroup_check_dev",
 )
 
 _lib = None
@@ -113,6 +114,9 @@ def load_library(path=None):
         L.blsgpu_hd_children_dev.argtypes = [vp, cp, cp, cp, vp, sz, vp, vp, vp, vp, vp]
         L.blsgpu_g1_poly_check.argtypes = [vp, cp, sz, sz, vp, cp, cp, sz, vp, vp]
         L.blsgpu_g1_poly_check_dev.argtypes = [vp, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp]
+        for g in ("g1", "g2"):
+            getattr(L, "blsgpu_%s_subgroup_check" % g).argtypes = [vp, cp, sz, vp]
+            getattr(L, "blsgpu_%s_subgroup_check_dev" % g).argtypes = [vp, vp, sz, vp, vp]
         L.blsgpu_timing_enable.argtypes = [vp, ctypes.c_int]
         L.blsgpu_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int), sz,
                                          ctypes.POINTER(sz)]
@@ -412,6 +416,29 @@ class Engine:
     def g1_poly_check_dev(self, d_commit, n_polys, t, d_poly, d_x, d_s, n, d_status, d_out_aff, stream=0):
         self._check(self.lib.blsgpu_g1_poly_check_dev(self.h, d_commit, n_polys, t, d_poly, d_x, d_s, n, d_status, d_out_aff, stream),
                     "blsgpu_g1_poly_check_dev")
+
+    def _subgroup(self, g, psz, pts):
+        if len(pts) % psz:
+            raise ValueError("need n x %d bytes" % psz)
+        n = len(pts) // psz
+        st = ctypes.create_string_buffer(max(1, n))
+        name = "blsgpu_%s_subgroup_check" % g
+        self._check(getattr(self.lib, name)(self.h, bytes(pts), n, st), name)
+        return st.raw[:n]
+
+    def g1_subgroup(self, pts):
+        """n x 96 affine bytes ((0, 0) = infinity) -> n status bytes: 1 in G1, 2 on the curve outside it, 0 off the curve"""
+        return self._subgroup("g1", 96, pts)
+
+    def g2_subgroup(self, pts):
+        """n x 192 affine bytes (all zero = infinity) -> n status bytes: 1 in G2, 2 on the twist outside it, 0 off it"""
+        return self._subgroup("g2", 192, pts)
+
+    def g1_subgroup_dev(self, d_pts, n, d_status, stream=0):
+        self._check(self.lib.blsgpu_g1_subgroup_check_dev(self.h, d_pts, n, d_status, stream), "blsgpu_g1_subgroup_check_dev")
+
+    def g2_subgroup_dev(self, d_pts, n, d_status, stream=0):
+        self._check(self.lib.blsgpu_g2_subgroup_check_dev(self.h, d_pts, n, d_status, stream), "blsgpu_g2_subgroup_check_dev")
 
     def timing_enable(self, on=True):
         self._check(self.lib.blsgpu_timing_enable(self.h, int(on)), "blsgpu_timing_enable")

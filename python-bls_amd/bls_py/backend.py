@@ -59,6 +59,14 @@ class HipProvider:
         C_k (k >= 1) outside the order-n subgroup; or None for s None) and the n x 96 affine Horner values (aff) or None"""
         return self._eng.g1_poly_check(commit, n_polys, t, poly, x, s, aff)
 
+    def g1_subgroup(self, pts: bytes) -> bytes:
+        """n x 96 affine bytes -> n status bytes: 1 in G1 (infinity included), 2 on the curve outside G1, 0 off the curve"""
+        return self._eng.g1_subgroup(pts)
+
+    def g2_subgroup(self, pts: bytes) -> bytes:
+        """n x 192 affine bytes -> n status bytes: 1 in G2 (infinity included), 2 on the twist outside G2, 0 off the twist"""
+        return self._eng.g2_subgroup(pts)
+
     # ---- the whole of BLS.verify's device work without a host round trip between its steps (bls.py:153-201) ----
     def verify_pipeline(self, neg_g1: bytes, sig: bytes, hashes: bytes, n: int, keys_affine=None, key_pts=None, key_scalars=None, k=0) -> bytes:
         """e(-G1, sig) * prod_i e(P_i, H(m_i)) for n message hashes (32 bytes each): blsgpu_verify_pipeline -- ONE upload,
@@ -76,7 +84,8 @@ def use(provider):
     g1_decompress / g2_decompress(bytes) -> (affine bytes, [accepted]),
     g1_mul_gen(scalars, add|None, n_add) -> (affine bytes, serialised bytes),
     hd_children(chain_code, parent_pk_aff, parent_sk|None, indices) -> (chain codes, child keys|None, affine, serialised),
-    g1_poly_check(commit, n_polys, t, poly, x, s|None, aff) -> (status bytes|None, affine Horner values|None)."""
+    g1_poly_check(commit, n_polys, t, poly, x, s|None, aff) -> (status bytes|None, affine Horner values|None),
+    g1_subgroup / g2_subgroup(affine bytes) -> status bytes (1 in the subgroup, 2 on the curve outside it, 0 off it)."""
     global _provider
     _provider = provider
 

@@ -4,6 +4,8 @@
 Qs = [signature] + H(m) exactly as bls.py:153-201 does and hands them to the
 multi-pairing engine.  The group sums (signature aggregation, per-message key
 folding, aggregate public keys) are GPU multi-scalar sums as well."""
+import secrets
+
 from . import hostmath as H
 from .aggregation_info import AggregationInfo
 from .bls12381 import n as GROUP_ORDER
@@ -51,6 +53,27 @@ def _jac_g1_bytes(J):
     if J.z.Z == 1:
         return int(J.x.Z).to_bytes(48, "big") + int(J.y.Z).to_bytes(48, "big")
     return H.g1_affine_bytes(J.to_affine()._aff())
+
+
+def _g1_group_sums(prov, groups):
+    """[(affine bytes, is_infinity) of sum_j s_j P_j] for groups of (P bytes, scalar) pairs: one g1_msm per power-of-two
+    group length (padded with infinity), so that one long group does not pad every other to its length"""
+    out = [None] * len(groups)
+    by_len = {}
+    for j, g in enumerate(groups):
+        by_len.setdefault(1 << (len(g) - 1).bit_length(), []).append(j)
+    for k, js in by_len.items():
+        pts, sc = bytearray(), []
+        for j in js:
+            for b, s in groups[j]:
+                pts += b
+                sc.append(s)
+            pts += bytes(96) * (k - len(groups[j]))
+            sc += [0] * (k - len(groups[j]))
+        res, inf = prov.g1_msm(bytes(pts), sc, k, len(js))
+        for q, j in enumerate(js):
+            out[j] = (res[96 * q:96 * (q + 1)], inf[q])
+    return out
 
 
 class BLS:
@@ -183,6 +206,115 @@ class BLS:
             out = prov.pairing_multi_batch(b"".join(x[1] for x in items), b"".join(x[2] for x in items), size, len(items))
             for j, (i, _, _) in enumerate(items):
                 results[i] = out[576 * j:576 * (j + 1)] == ONE
+        return results
+
+    @staticmethod
+    def verify_batch_randomized(signatures, rng=None):
+        """verify_batch(signatures) by a random linear combination: ONE multi-pairing of (distinct messages + 1) pairs
+        decides every eligible signature, e(-G1, sum r_i sig_i) * prod_m e(sum_i r_i P_im, H(m)) == 1, with r_i drawn
+        uniformly from [1, 2^64) (rng.getrandbits(64), in the order of the list; default secrets.SystemRandom()).
+        Eligible: a signature point in G2 and not infinity, every key in G1, 32-byte message hashes, every per-message
+        key sum P_im and every H(m) not infinity.  The others, and all eligible ones if the product
+        is not 1, are decided by verify_batch in the same call.  The answers equal verify_batch's except that an invalid
+        eligible signature is reported True with probability at most 1 / (2^64 - 1)."""
+        prov = backend.get()
+        rng = rng or secrets.SystemRandom()
+        results = [None] * len(signatures)
+        plans = []                                        # (index, message hashes, key groups (PublicKey), exponent groups)
+        for i, sig in enumerate(signatures):
+            info = sig.aggregation_info
+            by_message = {}
+            for mh, pk in zip(info.message_hashes, info.public_keys):
+                by_message.setdefault(mh, []).append(pk)
+            kg, eg = [], []
+            try:
+                for mh, keys in by_message.items():
+                    uniq = list(set(keys))
+                    eg.append([info.tree[(mh, pk)] for pk in uniq])
+                    kg.append(uniq)
+            except KeyError:
+                results[i] = False                        # bls.py:189-190
+                continue
+            plans.append((i, list(by_message), kg, eg))
+        elig = [p for p in plans if not signatures[p[0]].value.infinity and all(len(mh) == 32 for mh in p[1])]
+
+        # subgroup membership: the distinct keys, the signature points (one device call each)
+        sig_bytes = [H.g2_affine_bytes(signatures[p[0]].value.to_affine()._aff()) for p in elig]
+        if elig:
+            st = prov.g2_subgroup(b"".join(sig_bytes))
+            keep = [st[j] == 1 and any(sig_bytes[j]) for j in range(len(elig))]
+            elig, sig_bytes = [p for p, k in zip(elig, keep) if k], [b for b, k in zip(sig_bytes, keep) if k]
+        key_bytes = {}
+        for p in elig:
+            for g in p[2]:
+                for pk in g:
+                    if pk not in key_bytes:
+                        key_bytes[pk] = _jac_g1_bytes(pk.value)
+        if key_bytes:
+            st = prov.g1_subgroup(b"".join(key_bytes.values()))
+            key_ok = {pk: st[j] == 1 and (pk.value.infinity or any(b)) for j, (pk, b) in enumerate(key_bytes.items())}
+            keep = [all(key_ok[pk] for g in p[2] for pk in g) for p in elig]
+            elig, sig_bytes = [p for p, k in zip(elig, keep) if k], [b for b, k in zip(sig_bytes, keep) if k]
+
+        # P_im: one key -> e pk, infinity iff e = 0 mod n or pk = O (pk in G1); several -> one grouped G1 sum
+        multi = [[(key_bytes[pk], int(e) % GROUP_ORDER) for pk, e in zip(g, eg)]
+                 for p in elig for g, eg in zip(p[2], p[3]) if len(g) > 1]
+        sums = iter(_g1_group_sums(prov, multi))
+        terms, keep = [], []                              # per signature: [(message hash, P bytes, scalar factor)]
+        for p in elig:
+            t, ok = [], True
+            for mh, g, eg in zip(p[1], p[2], p[3]):
+                if len(g) > 1:
+                    b, inf = next(sums)
+                    t.append((mh, b, 1))
+                else:
+                    e = int(eg[0]) % GROUP_ORDER
+                    inf = e == 0 or g[0].value.infinity
+                    t.append((mh, key_bytes[g[0]], e))
+                ok = ok and not inf
+            terms.append(t)
+            keep.append(ok)
+        elig, sig_bytes, terms = ([x for x, k in zip(v, keep) if k] for v in (elig, sig_bytes, terms))
+
+        # H(m) of every distinct message (one call); a message that hashes to infinity leaves the combined check
+        msgs = list(dict.fromkeys(mh for p in elig for mh in p[1]))
+        if msgs:
+            hm = prov.hash_to_g2(b"".join(msgs))
+            hm = {mh: hm[192 * j:192 * (j + 1)] for j, mh in enumerate(msgs)}
+            keep = [all(any(hm[mh]) for mh in p[1]) for p in elig]
+            elig, sig_bytes, terms = ([x for x, k in zip(v, keep) if k] for v in (elig, sig_bytes, terms))
+
+        ok = True
+        if elig:
+            r = []
+            for _ in elig:
+                x = 0
+                while x == 0:
+                    x = rng.getrandbits(64)
+                r.append(x)
+            S, s_inf = prov.g2_msm(b"".join(sig_bytes), r, len(elig), 1)
+            by_msg = {}
+            for ri, t in zip(r, terms):
+                for mh, b, e in t:
+                    by_msg.setdefault(mh, []).append((b, ri * e % GROUP_ORDER))
+            order = list(by_msg)
+            Pm = _g1_group_sums(prov, [by_msg[mh] for mh in order])
+            if BLS._NEG_G1 is None:
+                BLS._NEG_G1 = H.g1_affine_bytes((generator_Fq() * (GROUP_ORDER - 1))._aff())
+            g1, g2 = ([], []) if s_inf[0] else ([BLS._NEG_G1], [S])
+            for mh, (b, inf) in zip(order, Pm):
+                if not inf:                               # a combined sum at infinity pairs to 1: left out, not fed as (0, 0)
+                    g1.append(b)
+                    g2.append(hm[mh])
+            if g1:
+                ok = prov.pairing_multi(b"".join(g1), b"".join(g2), len(g1)) == Fq12.one(default_ec.q).serialize()
+        done = {p[0] for p in elig} if ok else set()
+        for i in done:
+            results[i] = True
+        rest = [p[0] for p in plans if p[0] not in done]
+        if rest:
+            for i, v in zip(rest, BLS.verify_batch([signatures[i] for i in rest])):
+                results[i] = v
         return results
 
     @staticmethod

@@ -17,6 +17,21 @@ from .util import hash256, hmac256
 RNG = SystemRandom()
 
 
+def _in_subgroup_batch(points, to_bytes, op):
+    """[(P * n).infinity for P in points] (JacobianPoints; op: the provider's g1_subgroup or g2_subgroup): the device's status byte where it is 1 or 2 (on the curve,
+    where [n] P is exact group arithmetic); the host's [n] P for a point off the curve and for one whose affine form is the
+    all-zero encoding of infinity without being infinity"""
+    from . import backend
+    if not points:
+        return []
+    affs = [P.to_affine()._aff() for P in points]
+    enc = [to_bytes(A) for A in affs]
+    status = getattr(backend.get(), op)(b"".join(enc))
+    zero = bytes(len(enc[0]))
+    return [st == 1 if st and not (A is not None and e == zero) else (P * GROUP_ORDER).infinity
+            for P, A, e, st in zip(points, affs, enc, status)]
+
+
 class PublicKey:
     PUBLIC_KEY_SIZE = 48
 
@@ -50,6 +65,12 @@ class PublicKey:
     def from_g1(g1_el):
         assert type(g1_el) is JacobianPoint
         return PublicKey(g1_el)
+
+    @staticmethod
+    def in_subgroup_batch(keys):
+        """[(pk.value * n).infinity for pk in keys]: order-n subgroup membership of every key in one GPU call
+        (blsgpu_g1_subgroup_check).  Keys off the curve (status 0) are decided by the host multiplication itself."""
+        return _in_subgroup_batch([pk.value for pk in keys], H.g1_affine_bytes, "g1_subgroup")
 
     def serialize(self):
         if self._ser is None:

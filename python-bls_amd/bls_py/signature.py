@@ -39,6 +39,13 @@ class Signature:
     def from_g2(g2_el, aggregation_info=None):
         return Signature(g2_el, aggregation_info)
 
+    @staticmethod
+    def in_subgroup_batch(signatures):
+        """[(sig.value * n).infinity for sig in signatures]: order-n subgroup membership of every signature point in one
+        GPU call (blsgpu_g2_subgroup_check); points off the twist are decided by the host multiplication itself."""
+        from .keys import _in_subgroup_batch
+        return _in_subgroup_batch([sig.value for sig in signatures], H.g2_affine_bytes, "g2_subgroup")
+
     def set_aggregation_info(self, aggregation_info):
         self.aggregation_info = aggregation_info
 

@@ -24,6 +24,7 @@
 #include "blsgpu_msm.hip"
 #include "blsgpu_g1fix.hip"
 #include "blsgpu_g1poly.hip"
+#include "blsgpu_subgroup.hip"
 #include "blsgpu_h2c.hip"
 #include "blsgpu_h2cw.hip"
 #include "blsgpu_probe.hip"
@@ -838,6 +839,43 @@ int poly_check_dev(blsgpu_ctx* c, const void* d_commit, size_t n_polys, size_t t
     if (bad) return fail(-EINVAL, "polynomial index out of range");
     if (int rc = poly_prep(c, d_commit, n_polys, t, d_status != nullptr, st)) return rc;
     return poly_eval_launch(c, n_polys, t, d_poly, d_x, d_s, n, d_status, d_out_aff, st);
+}
+// ------------------------------------------------------------ subgroup membership (blsgpu_subgroup.hip) --
+// n affine points of G1 (g = 1, 96 B each) or G2 (g = 2, 192 B each) -> n status bytes, FIX_SLICE per launch
+int subgroup_dev(blsgpu_ctx* c, int g, const void* d_pts, size_t n, void* d_status, hipStream_t st) {
+    if (n == 0) return 0;
+    if (!d_pts || !d_status) return fail(-EINVAL, "NULL argument");
+    StreamGuard sg(c, st);
+    const size_t dw = g == 1 ? 24 : 48;
+    for (size_t lo = 0; lo < n; lo += FIX_SLICE) {
+        const size_t m = n - lo < FIX_SLICE ? n - lo : FIX_SLICE;
+        const dim3 grid((unsigned)((m + 255) / 256));
+        const uint32_t* p = (const uint32_t*)d_pts + lo * dw;
+        uint8_t* s = (uint8_t*)d_status + lo;
+        if (g == 1)
+            hipLaunchKernelGGL(blsgpu::subgroup::k_g1_subgroup, grid, dim3(256), 0, st, p, (uint32_t)m, s);
+        else
+            hipLaunchKernelGGL(blsgpu::subgroup::k_g2_subgroup, grid, dim3(256), 0, st, c->tabs, p, (uint32_t)m, s);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+// the host-buffer form: FIX_HOST_SLICE points per staged slice
+int subgroup_host(blsgpu_ctx* c, int g, const uint8_t* pts, size_t n, uint8_t* status) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (n == 0) return 0;
+    if (!pts || !status) return fail(-EINVAL, "NULL argument");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bytes = g == 1 ? 96 : 192, S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE, o_st = S * bytes;
+    if (int rc = grow_buffer(c, &c->d_io, &c->io_cap, o_st + S + 64)) return rc;
+    char* d = (char*)c->d_io;
+    for (size_t lo = 0; lo < n; lo += S) {
+        const size_t m = n - lo < S ? n - lo : S;
+        HIP_TRY(hipMemcpyAsync(d, pts + lo * bytes, m * bytes, hipMemcpyHostToDevice, 0));
+        if (int rc = subgroup_dev(c, g, d, m, d + o_st, nullptr)) return rc;
+        HIP_TRY(hipMemcpy(status + lo, d + o_st, m, hipMemcpyDeviceToHost));
+    }
+    return 0;
 }
 }  // namespace
 
@@ -2186,6 +2224,26 @@ BLSGPU_EXPORT int blsgpu_g1_poly_check_dev(blsgpu_ctx* c, const void* d_commit, 
     if (!c) return fail(-EINVAL, "ctx is NULL");
     HIP_TRY(hipSetDevice(c->device));
     return poly_check_dev(c, d_commit, n_polys, t, d_poly, d_x, d_s, n, d_status, d_out_aff, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------ subgroup membership --
+BLSGPU_EXPORT int blsgpu_g1_subgroup_check(blsgpu_ctx* c, const uint8_t* pts, size_t n, uint8_t* status) {
+    return subgroup_host(c, 1, pts, n, status);
+}
+BLSGPU_EXPORT int blsgpu_g2_subgroup_check(blsgpu_ctx* c, const uint8_t* pts, size_t n, uint8_t* status) {
+    return subgroup_host(c, 2, pts, n, status);
+}
+BLSGPU_EXPORT int blsgpu_g1_subgroup_check_dev(blsgpu_ctx* c, const void* d_pts, size_t n, void* d_status, void* stream) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return subgroup_dev(c, 1, d_pts, n, d_status, (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_g2_subgroup_check_dev(blsgpu_ctx* c, const void* d_pts, size_t n, void* d_status, void* stream) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return subgroup_dev(c, 2, d_pts, n, d_status, (hipStream_t)stream);
 }
 
 #ifdef BLSGPU_STAMPS
