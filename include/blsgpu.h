@@ -70,8 +70,9 @@ int blsgpu_ctx_reserve(blsgpu_ctx *ctx, size_t max_pairs);
  * calls made so far; the line-stream stage keeps 68 x 336 bytes of line records per pair of its largest call, the
  * counterpart of the n-arrays of mpz_t the reference mallocs per call, fields_t_c.pyx:2348-2388).  out[BLSGPU_WS_TOTAL]
  * is the sum (which also counts the fixed-base G1 table and the HD derivation slice, blsgpu_g1_mul_gen /
- * blsgpu_hd_children, and the commitments of blsgpu_g1_poly_check; they have no field of their own).  No device call is
- * made. */
+ * blsgpu_hd_children, and the commitments of blsgpu_g1_poly_check; they have no field of their own).
+ * BLSGPU_WS_FLAGS_AND_LISTS counts the flag copy of blsgpu_miller_loop_batch's fast form as well (2 bytes per pair of a
+ * slice).  No device call is made. */
 enum { BLSGPU_WS_PARTIALS = 0, BLSGPU_WS_STAGING, BLSGPU_WS_LINES, BLSGPU_WS_LINE_PRODUCTS, BLSGPU_WS_FLAGS_AND_LISTS,
        BLSGPU_WS_GROUP_SUMS, BLSGPU_WS_SLOTS, BLSGPU_WS_TOTAL, BLSGPU_WS_FIELDS };
 int blsgpu_ctx_workspace_bytes(blsgpu_ctx *ctx, size_t out[BLSGPU_WS_FIELDS]);
@@ -82,6 +83,7 @@ int blsgpu_ctx_trim(blsgpu_ctx *ctx);
  * (several pairs per wavefront sharing one accumulator); smaller batches the
  * latency-oriented one (one pair per wavefront).  Default 4096; 0 = always the
  * throughput kernel.  Results are identical either way. */
+int blsgpu_ctx_set_mp_threshold(blsgpu_ctx *ctx, size_t pairs);
 /* Measurement aid (bench.py): the chip's 32 x 32 + 64-bit multiply-add rate (v_mad_i64_i32) measured NOW by a probe kernel of
  * about `target_ms` milliseconds on `stream`; *tmacs = 10^12 multiply-adds per second.  The roofline of this path is that
  * instruction's issue rate (integer VALU, not HBM or MFMA), and the clock the package's power limit leaves differs
@@ -91,11 +93,11 @@ int blsgpu_timing_mad_probe(blsgpu_ctx *ctx, double target_ms, double *tmacs, vo
  * with two of them; tools/collect_profiles.py cuts the per-dispatch counters of a rocprofv3 --pmc run to the dispatches between
  * the marks (the HBM traffic per step of roofline.traffic). */
 int blsgpu_timing_mark(blsgpu_ctx *ctx, unsigned tag, void *stream);
-int blsgpu_ctx_set_mp_threshold(blsgpu_ctx *ctx, size_t pairs);
 /* Calls of at most `pairs` pairs (below the line-stream threshold) run the WIDE Miller loop (csrc/blsgpu_mlw.hip): one pair
  * per workgroup of two wavefronts with a field product per lane -- the loop of fq_miller_loop (fields_t.py:1091-1111) at
  * the depth of one wavefront's instruction stream, the latency form for BLS.verify of a few signatures
- * (bls.py:197-201).  Default 1536 (measured crossover against the wavefront-VM kernel, tools/miller_wide_probe.py); 0 = never (the wavefront-VM kernels).  Results are identical either way. */
+ * (bls.py:197-201).  Default 1536 (measured crossover against the wavefront-VM kernel, tools/miller_wide_probe.py); 0 = never (the wavefront-VM kernels).  Results are identical either way.
+ * Any value is valid: the loop leaves one partial per pair, and the workspace of a call follows the kernel it takes. */
 int blsgpu_ctx_set_miller_wide_max(blsgpu_ctx *ctx, size_t pairs);
 /* The throughput kernel runs three pairs per wavefront from `pairs` pairs per call on and two pairs per
  * wavefront below (a call of a few thousand pairs fills the chip with teams of two and each finishes sooner).

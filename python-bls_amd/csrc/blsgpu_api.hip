@@ -30,21 +30,9 @@
 #include "blsgpu_probe.hip"
 
 #if BLSGPU_EMIT(BLSGPU_TU_HOST)
+#include "blsgpu_ctx.h"
+
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess)                                                                 \
-            return fail(-EIO, std::string(#expr) + ": " + hipGetErrorString(_e));             \
-    } while (0)
-
 constexpr int MILLER_WAVES = 4;        // teams (pairings) per workgroup in k_miller
 constexpr int REDUCE_WAVES = 8;        // teams per workgroup in k_reduce
 constexpr size_t BATCH_TREE_MIN_GROUP = 24;   // batches of groups at least this long use the per-group product tree
@@ -53,123 +41,10 @@ constexpr size_t LS_MAX_PAIRS = (size_t)1 << 20;       // pairs per line-stream 
 
 }  // namespace
 
-struct blsgpu_ctx {
-    int device = 0;
-    blsgpu::VmTables tabs{};
-    void* d_tables = nullptr;          // one allocation holding every table
-    uint32_t* d_part[2] = {nullptr, nullptr};
-    size_t part_cap = 0;               // capacity of each partial buffer, in partials
-    void* d_io = nullptr;              // staging for the host-buffer entry points
-    size_t io_cap = 0;
-    uint32_t* d_out = nullptr;         // 576-byte result staging
-    uint32_t* d_degen = nullptr;       // [0] count, [1 ..] block indices of degenerate pairs (k_miller_slow's work list)
-    size_t degen_cap = 0;
-    size_t miller_wide3_max = 256;     // ... with the accumulator split over two wavefronts (three per pair) up to this many pairs: three SIMDs per pair are free
-    size_t miller_wide_max = 1536;     // calls of at most this many pairs run the wide Miller loop (blsgpu_mlw.hip: one pair per two-wavefront workgroup, a product per lane); 0: never
-    size_t mp_threshold = 4096;        // pairs from which k_miller_mp is used
-    size_t mp3_threshold = (size_t)-1; // ... with three pairs per wavefront from here on, two below; -1: the measured schedule
-    size_t pip_threshold = 4096;       // points from which a single sum uses the bucket method
-    size_t pip_group_threshold = 48;   // points per sum from which a batch of sums does
-    size_t pow2_max = 32768;           // fixed-exponent powers (hash to G2, decompression): up to this many values per launch two wavefronts per 64 values (k_pow2: 0.32 ms against 0.47); 0: never
-    bool msm_wide_tail = true;         // the sorted-bucket G1 sum: window sums and the Horner over the windows on the wide machine (k_msm_horner_wide: 0.9 ms against the wavefront VM's 1.45); false: k_srt_windows + k_msm_pip_horner<1>
-    size_t h2c_wide_max = 2048;        // up to this many messages the cofactor clearing runs one message per WAVEFRONT with a product per lane (blsgpu_h2cw.hip: the latency form); 0: never
-    size_t h2c_reg_threshold = 8192;   // messages from which cofactor clearing runs in registers (one message per lane PAIR; measured: DESIGN.md 2c)
-    size_t h2c_lane_threshold = 2048;  // messages from which the three encoding stages run one encoding per lane (k_h2c_sw0/1/2)
-    bool h2c_jacobi = true;            // ... with the quadratic characters decided by a Jacobi-symbol routine: two powers per encoding, not five
-    size_t h2c_jacobi_threshold = 16384;   // ... from this many messages (below, five parallel powers finish sooner than three serial symbol loops)
-    size_t h2c_quad_max = 16384;       // ... on lane QUADS up to this many messages (k_h2c_clear_quads: half the depth while the chip is not full)
-    bool test_ls_nomem = false;        // test hook (BLSGPU_TEST_LS_NOMEM=1): the line-stream workspace "cannot be allocated"
-    void* d_h2c_ws = nullptr;          // the lane-private point slots of k_h2c_clear_pairs
-    size_t h2c_ws_cap = 0;
-    size_t msm_sort_threshold = 1;      // points from which one G1 sum with scalars uses sorted buckets (k_srt_*): since the tail runs on the wide machine (round 5) they win at every size -- 1 point 1.24 ms against 1.63, 8192 points 1.45 against 2.59 (profiles/r05_c5_window_bits.txt)
-    size_t msm_sort2_threshold = 1;     // the same for ONE G2 sum with scalars (round 5: BLS.aggregate_sigs(secure) as a multi-scalar sum)
-    size_t msm_plain_threshold = 2;     // points from which ONE plain sum (no scalars) runs on the register kernels (k_sum_chunks + folds; round 5) instead of the wavefront VM's k_msm
-    size_t smul_min_groups = 4096;      // sums per call from which a batch of SMALL sums with scalars (scalar multiplications: groups x 1 point) runs one group per lane / lane pair (k_smul, round 5) instead of the wavefront VM's k_msm
-    size_t smul_max_k = 8;              // ... for sums of up to this many points
-    static uint32_t msm_sort2_bits(size_t n) { return n >= 16384 ? 13 : (n >= 512 ? 11 : 9); }   // window bits of the G2 path by size (tools/g2_single_sum_probe.py, profiles/r05_g2_single_sum.txt)
-    size_t horner_np_threshold = 1024; // G2 sums per call from which the window Horner runs several sums per team
-    size_t horner_quads_threshold = 2; // G2 sums per call (lane-pair bucket kernel) from which the window Horner runs one sum per lane quad
-    size_t wg256_max_waves = 4096;     // register kernels: launches of up to this many wavefronts go out as 256-thread workgroups (blsgpu_tu.h)
-    size_t msm_lane_threshold = 65536; // points from which the bucket sums run one (group, chunk, window) per lane
-    bool msm_lane_pairs = true;        // G2: every (group, chunk, window) on a lane PAIR (k_msm_lane2x) instead of one lane
-    uint32_t* d_buckets = nullptr;     // their buckets (HBM)
-    size_t bucket_cap = 0;
-    uint32_t* d_msm_part = nullptr;    // MSM partials
-    // line-stream multi-pairing (blsgpu_ml.hip): used from ls_threshold pairs per call when every group has at least
-    // ls_min_group pairs
-    size_t ls_threshold = 2304;        // measured crossover (tools/ls_wide_sweep.py, round 5 with the point chains sixteen lanes per pair): 2048 pairs 1.70 (VM) vs 1.70 ms, 3072 pairs 1.93 vs 1.79; 5120 in round 4, 16 384 in round 3
-    size_t ls_min_group = 64;
-    size_t ls_teams = 163840;          // accumulators k_ml_accum aims at (10 per wavefront: 8 wavefronts per place at two per SIMD)
-    void* d_lines = nullptr;           // 68 x pairs line records
-    size_t lines_cap = 0;              // bytes
-    void* d_lsp[2] = {nullptr, nullptr};   // dense partial products (ping-pong over the merge levels)
-    size_t lsp_cap[2] = {0, 0};        // bytes
-    void* d_bad = nullptr;             // one byte per pair: left to the slow program
-    void* d_exflags = nullptr;         // blsgpu_miller_loop_batch's fast form: the caller's flags with "py = 0" marked (2 bytes per pair)
-    size_t exflags_cap = 0;
-    size_t bad_cap = 0;
-    bool vm_exact_lanes = true;        // degenerate blocks of the VM kernels through the lane kernels (k_ml_lines_exact / k_ml_small) instead of k_miller_slow
-    bool miller_exact_lanes = true;    // blsgpu_miller_loop_batch (one exact Fq12 per pair) on the lane kernels (k_ml_lines_exact + k_ml_small, round 5) instead of the VM's k_miller_exact
-    bool miller_exact_fast = true;     // ... from the FAST lines: the line-stream kernels + one Fq2 factor per pair (k_ml_exact_fixup) instead of the reference's 73 affine slopes per pair; false: k_ml_lines_exact for every pair
-    size_t ls_merge_wide_max = 16384;  // merge levels with at most this many outputs run one wavefront per output
-    size_t ls_wide_max = 5120;         // calls of at most this many pairs run the point chains sixteen lanes per pair with the values in LDS (k_ml_lines_wide, blsgpu_lsw.hip); 0: never
-    size_t ls_quad_max = 20480;        // calls of at most this many pairs run the point chains on lane QUADS (k_ml_lines4: 0.6 of the depth while lane pairs leave SIMDs empty)
-    size_t fexp_team_threshold = 5120; // results per call from which the final exponentiations run six lanes each (blsgpu_fexp.hip); below: one result per wavefront (measured crossover, tools/fexp_latency.py)
-    bool fexp_wide = true;             // fewer results than that: one result per wavefront, a product per lane (blsgpu_fexpw.hip); false: the VM program
-    size_t fexp_wide_max_partials = 8; // ... which also multiplies up to this many partials per result itself (a dense product is ~2.5 us)
-    void* d_fexp_dbg = nullptr;        // tools/fexp_trace.py: the accumulator of result 0 after every operation of the script (k_fexp_team)
-    void* d_fexpw_stamps = nullptr;    // tools/fexpw_stamps.py: cycle counter of result 0 around every operation of the script (k_fexp_wide)
-    void* d_fexp_ws = nullptr;         // their slots
-    size_t fexp_ws_cap = 0;
-    uint32_t* d_fix_table = nullptr;   // the fixed-base G1 table (blsgpu_g1fix.hip), built on first use; freed by blsgpu_ctx_destroy only
-    void* d_fix_ws = nullptr;          // blsgpu_hd_children*: the parent key, a flag word and one slice of HMAC outputs
-    size_t fix_ws_cap = 0;
-    void* d_poly_ws = nullptr;         // blsgpu_g1_poly_check*: a flag word, the subgroup flags and the commitments in L28 form
-    size_t poly_ws_cap = 0;
-    hipEvent_t bulk_event = nullptr;   // caller's event, recorded after the last chip-filling kernel of a Miller stage
-    size_t msm_part_cap = 0;           // in u32
-    // optional per-kernel timing (blsgpu_timing_enable): HIP events recorded on
-    // the launch stream around every kernel, ring of TIMING_SLOTS launches
-    bool timing = false;
-    static constexpr int TIMING_SLOTS = 1024;
-    hipEvent_t* ev0 = nullptr;
-    hipEvent_t* ev1 = nullptr;
-    int* ev_kind = nullptr;            // 0 k_miller, 1 k_reduce, 2 k_reduce with final exponentiation
-    size_t ev_count = 0;
-    // Workspace buffers only ever GROW: the buffer a larger one replaces is kept until the
-    // context is destroyed (or trimmed by blsgpu_ctx_reserve on an idle context), so work
-    // already enqueued on it stays valid and no hipFree -- a device-wide synchronisation --
-    // happens inside a pipeline.
-    std::vector<void*> retired;
-    // The workspace is shared by everything a context launches: a call on another stream than
-    // the previous one first waits for that one's work (StreamGuard).
-    hipStream_t last_stream = nullptr;
-    hipEvent_t last_event = nullptr;
-    bool used = false;
-};
-
-namespace {
-struct KernelTimer {
-    blsgpu_ctx* c; hipStream_t st; int slot;
-    KernelTimer(blsgpu_ctx* c_, hipStream_t st_, int kind) : c(c_), st(st_), slot(-1) {
-        if (c->timing && c->ev_count < (size_t)blsgpu_ctx::TIMING_SLOTS) {
-            slot = (int)c->ev_count++;
-            c->ev_kind[slot] = kind;
-            (void)hipEventRecord(c->ev0[slot], st);
-        }
-    }
-    ~KernelTimer() { if (slot >= 0) (void)hipEventRecord(c->ev1[slot], st); }
-};
-}  // namespace
-
 // Batches of at least mp_threshold pairs use the multi-pair program (k_miller_mp:
 // fewer instructions per pairing, longer per-batch latency); smaller ones the
 // one-pair-per-wavefront program (k_miller).  Default 4096; per context via
 // blsgpu_ctx_set_mp_threshold, or BLSGPU_MP_THRESHOLD in the environment.
-static size_t default_mp_threshold() {
-    const char* e = getenv("BLSGPU_MP_THRESHOLD");
-    return e ? (size_t)strtoull(e, nullptr, 10) : (size_t)4096;
-}
 static bool use_mp(const blsgpu_ctx* c, size_t n) { return n >= c->mp_threshold; }
 // Two or three pairs per wavefront?  Three costs fewest instructions per pairing (large batches), two fills the
 // chip sooner: 4096 teams are one "round" of the chip, so teams of two win while the batch is a little under a
@@ -180,64 +55,15 @@ static bool use_mp2(const blsgpu_ctx* c, size_t n) {
     if (c->mp3_threshold != (size_t)-1) return n < c->mp3_threshold;
     return n <= 8704 || (n > 9728 && n <= 11264) || (n > 14336 && n <= 18432);
 }
-// Grid and workgroup size for `waves` independent wavefronts of a register kernel (blsgpu_tu.h: wave_index()): four
-// wavefronts per workgroup -- one per SIMD of a CU -- while the launch does not fill the chip several times over.
-struct WaveShape { unsigned blocks, threads; };
-static WaveShape wave_shape(const blsgpu_ctx* c, size_t waves) {
-    const unsigned per = (waves <= c->wg256_max_waves) ? 4u : 1u;
-    return {(unsigned)((waves + per - 1) / per), per * 64u};
+// Partials a call of `pairs` pairs takes on the wavefront-VM kernels: one per Miller block -- at most a team of two pairs
+// (k_miller_mp<2>) -- plus the levels of the reduce chain.
+static size_t pairs_partials(size_t pairs) { return (pairs + 1) / 2 + (pairs + MILLER_WAVES - 1) / MILLER_WAVES + 1; }
+// Room for `partials` partials in each partial buffer, and one work-list entry per Miller block at most (+ the counter).
+static int ensure_partials(blsgpu_ctx* c, size_t partials) {
+    for (BufId b : {B_PART0, B_PART1})
+        if (int rc = c->grow(b, partials * BLSGPU_FQ12_BYTES)) return rc;
+    return c->grow(B_DEGEN, (c->part_cap() + 2) * sizeof(uint32_t));
 }
-// grow-only (see blsgpu_ctx::retired): *p gets at least `bytes`; contents are scratch, not copied
-static int grow_buffer(blsgpu_ctx* c, void** p, size_t* cap_bytes, size_t bytes) {
-    if (bytes <= *cap_bytes) return 0;
-    size_t want = bytes + bytes / 4;                     // headroom: fewer regrowths
-    void* n = nullptr;
-    if (hipMalloc(&n, want) != hipSuccess) {
-        (void)hipGetLastError();                         // the failed attempt must not show up in a later launch check
-        want = bytes;
-        HIP_TRY(hipMalloc(&n, want));
-    }
-    if (*p) c->retired.push_back(*p);
-    *p = n;
-    *cap_bytes = want;
-    return 0;
-}
-template <class T>
-static int grow_elems(blsgpu_ctx* c, T** p, size_t* cap_elems, size_t elems) {
-    if (elems <= *cap_elems) return 0;
-    size_t bytes = *cap_elems * sizeof(T);
-    int rc = grow_buffer(c, (void**)p, &bytes, elems * sizeof(T));
-    if (rc) return rc;
-    *cap_elems = bytes / sizeof(T);
-    return 0;
-}
-static int ensure_workspace(blsgpu_ctx* c, size_t max_pairs) {
-    // one partial per Miller block: at most a team of two pairs (k_miller_mp<2>), plus the levels of the reduce chain
-    size_t need = (max_pairs + 1) / 2 + (max_pairs + MILLER_WAVES - 1) / MILLER_WAVES + 1;
-    if (need > c->part_cap) {
-        size_t cap0 = c->part_cap * 144, cap1 = c->part_cap * 144;     // in u32
-        int rc = grow_elems(c, &c->d_part[0], &cap0, need * 144);
-        if (!rc) rc = grow_elems(c, &c->d_part[1], &cap1, need * 144);
-        if (rc) return rc;
-        c->part_cap = (cap0 < cap1 ? cap0 : cap1) / 144;
-    }
-    // one work-list entry per Miller block at most (+ the counter)
-    return grow_elems(c, &c->d_degen, &c->degen_cap, c->part_cap + 2);
-}
-namespace {
-// Serialises the use of the context's workspace across streams (blsgpu_ctx::last_stream).
-struct StreamGuard {
-    blsgpu_ctx* c; hipStream_t st;
-    StreamGuard(blsgpu_ctx* c_, hipStream_t st_) : c(c_), st(st_) {
-        if (c->used && c->last_stream != st && c->last_event) (void)hipStreamWaitEvent(st, c->last_event, 0);
-    }
-    ~StreamGuard() {
-        if (c->last_event) (void)hipEventRecord(c->last_event, st);
-        c->last_stream = st;
-        c->used = true;
-    }
-};
-}  // namespace
 
 // fixed-exponent powers on a stage image (blsgpu_h2c.hip)
 static int launch_pow(blsgpu_ctx* c, uint32_t* img, uint32_t img_slots, uint32_t base_off, uint32_t acc_off, size_t teams, uint32_t cnt,
@@ -263,8 +89,8 @@ int decompress_dev(blsgpu_ctx* c, const void* d_in, size_t n, void* d_out, void*
     if (n > 0x0FFFFFF0ull) return fail(-EINVAL, "batch too large");
     const size_t teams = (n + C::NE - 1) / C::NE;
     size_t need = teams * C::IMG * 12;
-    if (int rc_ = grow_elems(c, &c->d_msm_part, &c->msm_part_cap, need)) return rc_;
-    uint32_t* img = c->d_msm_part;
+    if (int rc_ = c->grow(B_MSM_PART, need * 4)) return rc_;
+    uint32_t* img = c->at<uint32_t>(B_MSM_PART);
     const size_t lds = (size_t)C::SLOTS * 48;
     constexpr uint32_t BASE = C::BASE - C::STATE0, ACC = C::ACC - C::STATE0;
     hipLaunchKernelGGL((blsgpu::k_decompress<DEG, 0>), dim3((unsigned)teams), dim3(64), lds, st, c->tabs, (const uint32_t*)d_in,
@@ -289,17 +115,12 @@ int decompress_host(blsgpu_ctx* c, const uint8_t* in, size_t n, uint8_t* out, ui
     if (!c || (n && (!in || !out || !ok))) return fail(-EINVAL, "NULL argument");
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
-    size_t need = n * (48 * DEG + 96 * DEG + 1) + 64;
-    if (int rc_ = grow_buffer(c, &c->d_io, &c->io_cap, need)) return rc_;
-    char* din = (char*)c->d_io;
-    char* dout = din + n * 48 * DEG;
-    char* dok = dout + n * 96 * DEG;
-    HIP_TRY(hipMemcpy(din, in, n * 48 * DEG, hipMemcpyHostToDevice));
-    int rc = decompress_dev<DEG>(c, din, n, dout, dok, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out, dout, n * 96 * DEG, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(ok, dok, n, hipMemcpyDeviceToHost));
-    return 0;
+    Staging s(c);
+    const int din = s.in(in, n * 48 * DEG), dout = s.out(out, n * 96 * DEG), dok = s.out(ok, n);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    if (int rc = decompress_dev<DEG>(c, s.at(din), n, s.at(dout), s.at(dok), nullptr)) return rc;
+    return s.down();
 }
 }  // namespace
 
@@ -317,9 +138,9 @@ static int msm_sorted(blsgpu_ctx* c, const void* d_pts, const void* d_scalars, s
     // more than three pieces costs a whole wavefront in k_srt_fix_long.  With signed digits (2^(cb-1) keys per window) 13 bits are
     // the best width at every size the sorted path serves (tools/c5_probe.py under BLSGPU_MSM_SORT_BITS, profiles/r05_c5_window_bits.txt:
     // 2^20 points 5.71 / 5.42 / 5.46 ms for 12 / 13 / 14 bits, 16 384 points 1.88 / 1.52 / 1.68).
-    uint32_t cb = DEG == 1 ? (n < 512 ? 7u : 13u) : c->msm_sort2_bits(n);   // (a few points: 37 windows of 64 keys, 1.06 ms for one point against 1.24)
-    if (const char* e = getenv(DEG == 1 ? "BLSGPU_MSM_SORT_BITS" : "BLSGPU_MSM_SORT2_BITS")) cb = (uint32_t)strtoul(e, nullptr, 10);
-    if (cb < 5 || cb > blsgpu::SRT_MAXBITS) return fail(-EINVAL, "BLSGPU_MSM_SORT_BITS out of range");
+    const size_t pinned = DEG == 1 ? c->sort_bits : c->sort2_bits;
+    if (pinned && (pinned < 5 || pinned > blsgpu::SRT_MAXBITS)) return fail(-EINVAL, "BLSGPU_MSM_SORT_BITS out of range");
+    const uint32_t cb = pinned ? (uint32_t)pinned : DEG == 1 ? (n < 512 ? 7u : 13u) : c->msm_sort2_bits(n);   // (a few points: 37 windows of 64 keys, 1.06 ms for one point against 1.24)
     // signed digits (blsgpu_msm.hip): 2^(cb-1) keys per window; 258 <= cb x windows keeps the recoded scalar inside the windows
     const uint32_t kb = cb - 1, nwin = (258 + cb - 1) / cb;
     const size_t nkeys = (size_t)nwin << kb;
@@ -335,8 +156,8 @@ static int msm_sorted(blsgpu_ctx* c, const void* d_pts, const void* d_scalars, s
                  o_max = take(4), o_idx = take((size_t)nwin * n), o_bsum = take(nkeys * PJ), o_hp = take(units * PJ), o_hk = take(units),
                  o_b0 = take(nsum * nch * PJ), o_b1 = take(nsum * ((nch + 7) / 8) * PJ + PJ), o_win = take((size_t)nwin * PJ), o_live = take((n + 3) / 4),
                  o_wtot = take(2 * (size_t)nwin), o_long = take(nkeys + 4);
-    if (int rc_ = grow_elems(c, &c->d_buckets, &c->bucket_cap, off)) return rc_;
-    uint32_t* W = c->d_buckets;
+    if (int rc_ = c->grow(B_BUCKETS, off * 4)) return rc_;
+    uint32_t* W = c->at<uint32_t>(B_BUCKETS);
     HIP_TRY(hipMemsetAsync(W + o_cnt, 0, nkeys * 4, st));
     HIP_TRY(hipMemsetAsync(W + o_long, 0, 16, st));          // counter of the long runs (the key list follows it)
     uint8_t* live = (uint8_t*)(W + o_live);
@@ -425,8 +246,8 @@ static int msm_plain(blsgpu_ctx* c, const void* d_pts, size_t n, void* d_out, vo
     auto take = [&](size_t words) { size_t o = off; off += (words + 3) & ~(size_t)3; return o; };
     const size_t PJ = G::PJ;
     const size_t o_prep = take(n * blsgpu::L28_AFF * DEG), o_live = take((n + 3) / 4), o_b0 = take(U * PJ), o_b1 = take(((U + 7) / 8) * PJ + PJ);
-    if (int rc_ = grow_elems(c, &c->d_buckets, &c->bucket_cap, off)) return rc_;
-    uint32_t* W = c->d_buckets;
+    if (int rc_ = c->grow(B_BUCKETS, off * 4)) return rc_;
+    uint32_t* W = c->at<uint32_t>(B_BUCKETS);
     uint8_t* live = (uint8_t*)(W + o_live);
     hipLaunchKernelGGL(blsgpu::k_lane_prep<DEG>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_pts, (uint32_t)n, W + o_prep, live);
     const auto blocks = [&](size_t nunits) { return dim3((unsigned)((nunits * G::LP + 63) / 64)); };
@@ -465,11 +286,11 @@ static int msm_small_groups(blsgpu_ctx* c, const void* d_pts, const void* d_scal
     size_t off = 0;
     auto take = [&](size_t words) { size_t o = off; off += (words + 3) & ~(size_t)3; return o; };
     const size_t o_prep = take(n0 * blsgpu::L28_AFF * DEG), o_live = take((n0 + 3) / 4), o_tab = take(units0 * k * blsgpu::SMUL_T * G::PJ);
-    if (grow_elems(c, &c->d_buckets, &c->bucket_cap, off)) {
+    if (c->grow(B_BUCKETS, off * 4)) {
         (void)hipGetLastError();
         return 1;                                              // no room: the caller's other kernels
     }
-    uint32_t* W = c->d_buckets;
+    uint32_t* W = c->at<uint32_t>(B_BUCKETS);
     uint8_t* live = (uint8_t*)(W + o_live);
     for (size_t lo = 0; lo < groups; lo += slice) {
         const size_t m = groups - lo < slice ? groups - lo : slice, n = k * m, units = (m + upw - 1) / upw * upw;
@@ -509,8 +330,7 @@ int msm_dev(blsgpu_ctx* c, const void* d_pts, const void* d_scalars, size_t k, s
         size_t n = k * groups;
         // enough points for one (group, chunk, window) per lane to fill the chip?  (3 waves per SIMD = 3072 chunks)
         const bool lane_path = n >= c->msm_lane_threshold;
-        size_t want = lane_path ? 3072 : 256;
-        if (const char* e = getenv("BLSGPU_PIP_CHUNKS")) want = (size_t)strtoull(e, nullptr, 10);
+        const size_t want = c->pip_chunks ? c->pip_chunks : (lane_path ? 3072 : 256);
         size_t chunk = (groups > 1) ? k : (k + want - 1) / want;
         if (!lane_path && chunk < 64 * (size_t)C::NP && groups == 1) chunk = 64 * (size_t)C::NP;
         if (!lane_path) chunk = ((chunk + C::NP - 1) / C::NP) * C::NP;
@@ -521,8 +341,9 @@ int msm_dev(blsgpu_ctx* c, const void* d_pts, const void* d_scalars, size_t k, s
         // projective triples (36 DEG) or the lane path's affine L28 points (28 DEG) + live flags
         constexpr size_t PJ28 = blsgpu::L28_PJ * DEG;
         size_t need = (chunks + 1) * groups * blsgpu::PIP_W * PJ28 + n * 36 * DEG + (n + 3) / 4 + 4;
-        if (int rc_ = grow_elems(c, &c->d_msm_part, &c->msm_part_cap, need)) return rc_;
-        uint32_t* d_win = c->d_msm_part + chunks * groups * blsgpu::PIP_W * PJ28;
+        if (int rc_ = c->grow(B_MSM_PART, need * 4)) return rc_;
+        uint32_t* const d_part = c->at<uint32_t>(B_MSM_PART);
+        uint32_t* d_win = d_part + chunks * groups * blsgpu::PIP_W * PJ28;
         uint32_t* d_prep = d_win + groups * blsgpu::PIP_W * PJ28;
         if (lane_path) {
             // one (group, chunk, window) per lane, buckets in HBM
@@ -532,31 +353,32 @@ int msm_dev(blsgpu_ctx* c, const void* d_pts, const void* d_scalars, size_t k, s
             HIP_TRY(hipGetLastError());
             const size_t lanes = groups * chunks * blsgpu::PIP_W;
             const size_t bneed = lanes * (blsgpu::PIP_NB - 1) * PJ28 + fold_n * groups * blsgpu::PIP_W * 36 * DEG;
-            if (int rc_ = grow_elems(c, &c->d_buckets, &c->bucket_cap, bneed)) return rc_;
+            if (int rc_ = c->grow(B_BUCKETS, bneed * 4)) return rc_;
+            uint32_t* const d_buckets = c->at<uint32_t>(B_BUCKETS);
             // a batch of G2 sums (one chunk each): the window sums stay in the L28 form and the Horner runs one sum per lane quad
             const bool horner_quads = DEG == 2 && c->msm_lane_pairs && chunks == 1 && groups >= c->horner_quads_threshold;
             if (DEG == 2 && c->msm_lane_pairs)
                 hipLaunchKernelGGL(blsgpu::k_msm_lane2x, dim3((unsigned)((2 * lanes + 63) / 64)), dim3(64), 0, st, d_prep, d_live,
-                                   (const uint32_t*)d_scalars, (uint32_t)k, (uint32_t)chunk, (uint32_t)chunks, (uint32_t)lanes, c->d_buckets,
-                                   c->d_msm_part, (fold_n || horner_quads) ? 0u : 1u);
+                                   (const uint32_t*)d_scalars, (uint32_t)k, (uint32_t)chunk, (uint32_t)chunks, (uint32_t)lanes, d_buckets,
+                                   d_part, (fold_n || horner_quads) ? 0u : 1u);
             else
                 hipLaunchKernelGGL(blsgpu::k_msm_lane<DEG>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, d_prep, d_live,
-                                   (const uint32_t*)d_scalars, (uint32_t)k, (uint32_t)chunk, (uint32_t)chunks, (uint32_t)lanes, c->d_buckets,
-                                   c->d_msm_part, fold_n ? 0u : 1u);
+                                   (const uint32_t*)d_scalars, (uint32_t)k, (uint32_t)chunk, (uint32_t)chunks, (uint32_t)lanes, d_buckets,
+                                   d_part, fold_n ? 0u : 1u);
             HIP_TRY(hipGetLastError());
             if (horner_quads) {
                 const WaveShape ws = wave_shape(c, (4 * groups + 63) / 64);
-                hipLaunchKernelGGL(blsgpu::k_msm_horner_quads, dim3(ws.blocks), dim3(ws.threads), 0, st, c->d_msm_part,
+                hipLaunchKernelGGL(blsgpu::k_msm_horner_quads, dim3(ws.blocks), dim3(ws.threads), 0, st, d_part,
                                    (uint32_t)blsgpu::PIP_W, (uint32_t)blsgpu::PIP_C, (uint32_t)groups, (uint32_t*)d_out, (uint8_t*)d_out_inf);
                 HIP_TRY(hipGetLastError());
                 return 0;
             }
-            const uint32_t* winsrc = c->d_msm_part;
+            const uint32_t* winsrc = d_part;
             size_t wchunks = chunks;
             if (fold_n) {                                    // many chunks: fold runs of 64 partials per lane first
-                uint32_t* d_fold = c->d_buckets + lanes * (blsgpu::PIP_NB - 1) * PJ28;
+                uint32_t* d_fold = d_buckets + lanes * (blsgpu::PIP_NB - 1) * PJ28;
                 const size_t ftotal = groups * blsgpu::PIP_W * fold_n;
-                hipLaunchKernelGGL(blsgpu::k_msm_lane_fold<DEG>, dim3((unsigned)((ftotal + 63) / 64)), dim3(64), 0, st, c->d_msm_part,
+                hipLaunchKernelGGL(blsgpu::k_msm_lane_fold<DEG>, dim3((unsigned)((ftotal + 63) / 64)), dim3(64), 0, st, d_part,
                                    (uint32_t)chunks, 64u, (uint32_t)fold_n, (uint32_t)ftotal, d_fold, 1u);
                 HIP_TRY(hipGetLastError());
                 winsrc = d_fold;
@@ -571,10 +393,10 @@ int msm_dev(blsgpu_ctx* c, const void* d_pts, const void* d_scalars, size_t k, s
                                st, c->tabs, (const uint32_t*)d_pts, (uint32_t)n, d_prep);
             HIP_TRY(hipGetLastError());
             hipLaunchKernelGGL(blsgpu::k_msm_pip<DEG>, dim3((unsigned)chunks, blsgpu::PIP_W, (unsigned)groups), dim3(64), (size_t)P::SLOTS * 48,
-                               st, c->tabs, d_prep, (const uint32_t*)d_scalars, (uint32_t)k, (uint32_t)chunk, c->d_msm_part);
+                               st, c->tabs, d_prep, (const uint32_t*)d_scalars, (uint32_t)k, (uint32_t)chunk, d_part);
             HIP_TRY(hipGetLastError());
             hipLaunchKernelGGL(blsgpu::k_msm_pip_windows<DEG>, dim3(blsgpu::PIP_W, (unsigned)groups), dim3(64), (size_t)blsgpu::TEAM_BYTES, st,
-                               c->tabs, c->d_msm_part, (uint32_t)chunks, d_win);
+                               c->tabs, d_part, (uint32_t)chunks, d_win);
             HIP_TRY(hipGetLastError());
         }
         if (DEG == 2 && groups >= c->horner_np_threshold) {  // a batch of G2 sums: BLSVM_HMSM2_NP sums per team
@@ -601,15 +423,15 @@ int msm_dev(blsgpu_ctx* c, const void* d_pts, const void* d_scalars, size_t k, s
     size_t bpg = (k + chunk - 1) / chunk;
     size_t blocks = bpg * groups;
     size_t need = blocks * 36 * DEG;
-    if (int rc_ = grow_elems(c, &c->d_msm_part, &c->msm_part_cap, need)) return rc_;
+    if (int rc_ = c->grow(B_MSM_PART, need * 4)) return rc_;
     size_t lds = (size_t)MSM_WAVES * blsgpu::TEAM_BYTES;
     hipLaunchKernelGGL(blsgpu::k_msm<DEG>, dim3((unsigned)blocks), dim3(MSM_WAVES * 64), lds, st, c->tabs,
                        (const uint32_t*)d_pts, (const uint32_t*)d_scalars, (uint32_t)k, (uint32_t)chunk, (uint32_t)bpg,
-                       c->d_msm_part);
+                       c->at<uint32_t>(B_MSM_PART));
     HIP_TRY(hipGetLastError());
     size_t fblocks = (groups + MSM_WAVES - 1) / MSM_WAVES;
     hipLaunchKernelGGL(blsgpu::k_msm_finish<DEG>, dim3((unsigned)fblocks), dim3(MSM_WAVES * 64), lds, st, c->tabs,
-                       c->d_msm_part, (uint32_t)bpg, (uint32_t)groups, (uint32_t*)d_out, (uint8_t*)d_out_inf);
+                       c->at<uint32_t>(B_MSM_PART), (uint32_t)bpg, (uint32_t)groups, (uint32_t*)d_out, (uint8_t*)d_out_inf);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -621,20 +443,12 @@ int msm_host(blsgpu_ctx* c, const uint8_t* pts, const uint8_t* scalars, size_t k
     size_t n = k * groups;
     if (n && !pts) return fail(-EINVAL, "NULL point buffer");
     HIP_TRY(hipSetDevice(c->device));
-    size_t pb = n * 96 * DEG, sb = scalars ? n * 32 : 0, ob = groups * 96 * DEG;
-    size_t need = pb + sb + ob + groups + 64;
-    if (int rc_ = grow_buffer(c, &c->d_io, &c->io_cap, need)) return rc_;
-    char* dp = (char*)c->d_io;
-    char* ds = dp + pb;
-    char* dout = ds + ((sb + 15) & ~size_t(15));
-    char* dinf = dout + ob;
-    if (pb) HIP_TRY(hipMemcpyAsync(dp, pts, pb, hipMemcpyHostToDevice, 0));
-    if (sb) HIP_TRY(hipMemcpyAsync(ds, scalars, sb, hipMemcpyHostToDevice, 0));
-    int rc = msm_dev<DEG>(c, dp, scalars ? ds : nullptr, k, groups, dout, dinf, 0);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out, dout, ob, hipMemcpyDeviceToHost));
-    if (out_inf) HIP_TRY(hipMemcpy(out_inf, dinf, groups, hipMemcpyDeviceToHost));
-    return 0;
+    Staging s(c);
+    const int dp = s.in(pts, n * 96 * DEG), ds = s.in(scalars, n * 32), dout = s.out(out, groups * 96 * DEG), dinf = s.out_kept(out_inf, groups);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    if (int rc = msm_dev<DEG>(c, s.at(dp), s.opt(ds), k, groups, s.at(dout), s.at(dinf), 0)) return rc;
+    return s.down();
 }
 
 // ------------------------------------------------------------ fixed-base G1, HD derivation (blsgpu_g1fix.hip) --
@@ -730,8 +544,8 @@ int hd_children_dev(blsgpu_ctx* c, const uint8_t chain_code[32], const uint8_t p
     StreamGuard sg(c, st);
     const bool pub = parent_sk == nullptr;
     const size_t slice = pub ? (n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE) : 0;
-    if (int rc = grow_buffer(c, &c->d_fix_ws, &c->fix_ws_cap, 256 + slice * 32)) return rc;
-    char* ws = (char*)c->d_fix_ws;                                  // [0, 96) parent key, [128, 132) flag, [256, ..) i_left
+    if (int rc = c->grow(B_FIX_WS, 256 + slice * 32)) return rc;
+    char* ws = c->at<char>(B_FIX_WS);                                  // [0, 96) parent key, [128, 132) flag, [256, ..) i_left
     if (pub && check) {
         HIP_TRY(hipMemsetAsync(ws + 128, 0, 4, st));
         hipLaunchKernelGGL(blsgpu::g1fix::k_hd_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_idx, (uint32_t)n,
@@ -777,7 +591,7 @@ int poly_args(size_t n_polys, size_t t, const void* commit, const void* poly, co
 // workspace: [0, 4) index-check flag, [256, o_l28) subgroup flags (one word per polynomial), [o_l28, ..) the L28 commitments
 size_t poly_ws_l28(size_t n_polys) { return 256 + (n_polys * 4 + 255) / 256 * 256; }
 int poly_ws(blsgpu_ctx* c, size_t n_polys, size_t t) {
-    return grow_buffer(c, &c->d_poly_ws, &c->poly_ws_cap, poly_ws_l28(n_polys) + n_polys * t * blsgpu::g1poly::ENTRY_DW * 4);
+    return c->grow(B_POLY_WS, poly_ws_l28(n_polys) + n_polys * t * blsgpu::g1poly::ENTRY_DW * 4);
 }
 
 // the commitments of the call, once: L28 entries, then the subgroup flags (caller: StreamGuard, poly_ws)
@@ -786,7 +600,7 @@ int poly_prep(blsgpu_ctx* c, const void* d_commit, size_t n_polys, size_t t, boo
     if (table) {
         if (int rc = fix_table(c, st)) return rc;
     }
-    char* ws = (char*)c->d_poly_ws;
+    char* ws = c->at<char>(B_POLY_WS);
     const size_t m = n_polys * t;
     uint32_t* l28 = (uint32_t*)(ws + poly_ws_l28(n_polys));
     HIP_TRY(hipMemsetAsync(ws + 256, 0, n_polys * 4, st));
@@ -804,7 +618,7 @@ int poly_prep(blsgpu_ctx* c, const void* d_commit, size_t n_polys, size_t t, boo
 // n fragments against the prepared commitments, FIX_SLICE per launch (caller: StreamGuard, poly_prep)
 int poly_eval_launch(blsgpu_ctx* c, size_t n_polys, size_t t, const void* d_poly, const void* d_x, const void* d_s, size_t n, void* d_status,
                      void* d_out_aff, hipStream_t st) {
-    char* ws = (char*)c->d_poly_ws;
+    char* ws = c->at<char>(B_POLY_WS);
     for (size_t lo = 0; lo < n; lo += FIX_SLICE) {
         const size_t m = n - lo < FIX_SLICE ? n - lo : FIX_SLICE;
         hipLaunchKernelGGL(blsgpu::g1poly::k_poly_eval, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
@@ -825,7 +639,7 @@ int poly_check_dev(blsgpu_ctx* c, const void* d_commit, size_t n_polys, size_t t
     if (int rc = poly_args(n_polys, t, d_commit, d_poly, d_x, d_s, d_status, d_out_aff)) return rc;
     StreamGuard sg(c, st);
     if (int rc = poly_ws(c, n_polys, t)) return rc;
-    uint32_t* flag = (uint32_t*)c->d_poly_ws;
+    uint32_t* flag = c->at<uint32_t>(B_POLY_WS);
     HIP_TRY(hipMemsetAsync(flag, 0, 4, st));
     for (size_t lo = 0; lo < n; lo += FIX_SLICE) {
         const size_t m = n - lo < FIX_SLICE ? n - lo : FIX_SLICE;
@@ -866,16 +680,15 @@ int subgroup_host(blsgpu_ctx* c, int g, const uint8_t* pts, size_t n, uint8_t* s
     if (n == 0) return 0;
     if (!pts || !status) return fail(-EINVAL, "NULL argument");
     HIP_TRY(hipSetDevice(c->device));
-    const size_t bytes = g == 1 ? 96 : 192, S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE, o_st = S * bytes;
-    if (int rc = grow_buffer(c, &c->d_io, &c->io_cap, o_st + S + 64)) return rc;
-    char* d = (char*)c->d_io;
-    for (size_t lo = 0; lo < n; lo += S) {
-        const size_t m = n - lo < S ? n - lo : S;
-        HIP_TRY(hipMemcpyAsync(d, pts + lo * bytes, m * bytes, hipMemcpyHostToDevice, 0));
-        if (int rc = subgroup_dev(c, g, d, m, d + o_st, nullptr)) return rc;
-        HIP_TRY(hipMemcpy(status + lo, d + o_st, m, hipMemcpyDeviceToHost));
-    }
-    return 0;
+    const size_t S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE;
+    Staging s(c);
+    const int dp = s.in(pts, S, g == 1 ? 96 : 192), dst = s.out(status, S, 1);
+    if (int rc = s.alloc()) return rc;
+    return for_slices(n, S, [&](size_t lo, size_t m) {
+        if (int rc = s.up(lo, m)) return rc;
+        if (int rc = subgroup_dev(c, g, s.at(dp), m, s.at(dst), nullptr)) return rc;
+        return s.down(lo, m);
+    });
 }
 }  // namespace
 
@@ -899,43 +712,7 @@ BLSGPU_EXPORT int blsgpu_ctx_create(int device, blsgpu_ctx** out) {
     HIP_TRY(hipSetDevice(device));
     blsgpu_ctx* c = new blsgpu_ctx();
     c->device = device;
-    c->mp_threshold = default_mp_threshold();
-    if (const char* e = getenv("BLSGPU_MILLER_WIDE3_MAX")) c->miller_wide3_max = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_MILLER_WIDE_MAX")) c->miller_wide_max = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_MP3_THRESHOLD")) c->mp3_threshold = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_LS_THRESHOLD")) c->ls_threshold = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_LS_MIN_GROUP")) c->ls_min_group = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_LS_TEAMS")) c->ls_teams = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_FEXP_TEAM_THRESHOLD")) c->fexp_team_threshold = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_FEXP_WIDE")) c->fexp_wide = atoi(e) != 0;
-    if (const char* e = getenv("BLSGPU_FEXP_WIDE_MAX_PARTIALS")) c->fexp_wide_max_partials = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_VM_EXACT_LANES")) c->vm_exact_lanes = atoi(e) != 0;
-    if (const char* e = getenv("BLSGPU_LS_MERGE_WIDE_MAX")) c->ls_merge_wide_max = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_LS_WIDE_MAX")) c->ls_wide_max = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_LS_QUAD_MAX")) c->ls_quad_max = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_PIP_THRESHOLD")) c->pip_threshold = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_PIP_GROUP_THRESHOLD")) c->pip_group_threshold = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_POW2_MAX")) c->pow2_max = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_MSM_WIDE_TAIL")) c->msm_wide_tail = atoi(e) != 0;
-    if (const char* e = getenv("BLSGPU_H2C_WIDE_MAX")) c->h2c_wide_max = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_H2C_REG_THRESHOLD")) c->h2c_reg_threshold = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_H2C_QUAD_MAX")) c->h2c_quad_max = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_TEST_LS_NOMEM")) c->test_ls_nomem = atoi(e) != 0;
-    if (const char* e = getenv("BLSGPU_H2C_JACOBI")) c->h2c_jacobi = atoi(e) != 0;
-    if (const char* e = getenv("BLSGPU_H2C_JACOBI_THRESHOLD")) c->h2c_jacobi_threshold = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_H2C_LANE_THRESHOLD")) c->h2c_lane_threshold = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_MSM_SORT_THRESHOLD")) c->msm_sort_threshold = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_MSM_SORT2_THRESHOLD")) c->msm_sort2_threshold = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_MILLER_EXACT_LANES")) c->miller_exact_lanes = atoi(e) != 0;
-    if (const char* e = getenv("BLSGPU_MILLER_EXACT_FAST")) c->miller_exact_fast = atoi(e) != 0;
-    if (const char* e = getenv("BLSGPU_MSM_PLAIN_THRESHOLD")) c->msm_plain_threshold = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_SMUL_MIN_GROUPS")) c->smul_min_groups = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_SMUL_MAX_K")) c->smul_max_k = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_HORNER_NP_THRESHOLD")) c->horner_np_threshold = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_HORNER_QUADS_THRESHOLD")) c->horner_quads_threshold = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_WG256_MAX_WAVES")) c->wg256_max_waves = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_MSM_LANE_THRESHOLD")) c->msm_lane_threshold = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("BLSGPU_MSM_LANE_PAIRS")) c->msm_lane_pairs = atoi(e) != 0;
+    read_knobs(c);
     // pack all tables into one device allocation (16-byte aligned pieces)
     auto al = [](size_t x) { return (x + 15) & ~size_t(15); };
     size_t o_m = 0;
@@ -1021,7 +798,7 @@ BLSGPU_EXPORT int blsgpu_ctx_create(int device, blsgpu_ctx** out) {
     (void)hipFuncSetAttribute((const void*)blsgpu::k_msm<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * blsgpu::TEAM_BYTES);
     (void)hipFuncSetAttribute((const void*)blsgpu::k_msm_finish<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * blsgpu::TEAM_BYTES);
     (void)hipFuncSetAttribute((const void*)blsgpu::k_msm_finish<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * blsgpu::TEAM_BYTES);
-    int rc = ensure_workspace(c, 4096);
+    int rc = ensure_partials(c, pairs_partials(4096));
     if (!rc && hipEventCreateWithFlags(&c->last_event, hipEventDisableTiming) != hipSuccess) rc = fail(-EIO, "hipEventCreate failed");
     if (rc) {
         blsgpu_ctx_destroy(c);
@@ -1035,23 +812,10 @@ BLSGPU_EXPORT void blsgpu_ctx_destroy(blsgpu_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->d_tables) (void)hipFree(c->d_tables);
-    for (int i = 0; i < 2; i++)
-        if (c->d_part[i]) (void)hipFree(c->d_part[i]);
-    if (c->d_io) (void)hipFree(c->d_io);
     if (c->d_out) (void)hipFree(c->d_out);
-    if (c->d_msm_part) (void)hipFree(c->d_msm_part);
-    if (c->d_buckets) (void)hipFree(c->d_buckets);
-    if (c->d_degen) (void)hipFree(c->d_degen);
-    if (c->d_lines) (void)hipFree(c->d_lines);
-    for (int i = 0; i < 2; i++)
-        if (c->d_lsp[i]) (void)hipFree(c->d_lsp[i]);
-    if (c->d_bad) (void)hipFree(c->d_bad);
-    if (c->d_exflags) (void)hipFree(c->d_exflags);
-    if (c->d_fexp_ws) (void)hipFree(c->d_fexp_ws);
-    if (c->d_h2c_ws) (void)hipFree(c->d_h2c_ws);
     if (c->d_fix_table) (void)hipFree(c->d_fix_table);
-    if (c->d_fix_ws) (void)hipFree(c->d_fix_ws);
-    if (c->d_poly_ws) (void)hipFree(c->d_poly_ws);
+    for (const Buf& b : c->buf)
+        if (b.p) (void)hipFree(b.p);
     for (void* q : c->retired) (void)hipFree(q);
     if (c->last_event) (void)hipEventDestroy(c->last_event);
     if (c->ev0) {
@@ -1096,7 +860,7 @@ BLSGPU_EXPORT int blsgpu_timing_mad_probe(blsgpu_ctx* c, double target_ms, doubl
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     constexpr unsigned BLOCKS = 2048, THREADS = 256;
-    if (int rc = grow_buffer(c, &c->d_io, &c->io_cap, (size_t)BLOCKS * THREADS * 4)) return rc;
+    if (int rc = c->grow(B_IO, (size_t)BLOCKS * THREADS * 4)) return rc;
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0));
     HIP_TRY(hipEventCreate(&e1));
@@ -1104,7 +868,7 @@ BLSGPU_EXPORT int blsgpu_timing_mad_probe(blsgpu_ctx* c, double target_ms, doubl
     uint32_t iters = 20000;                                   // ~2.4 ms at 34 T/s: calibrates the second launch
     for (int pass = 0; pass < 2; pass++) {
         HIP_TRY(hipEventRecord(e0, st));
-        hipLaunchKernelGGL(blsgpu::probe::k_mad_probe, dim3(BLOCKS), dim3(THREADS), 0, st, (uint32_t*)c->d_io, iters, (uint32_t)pass);
+        hipLaunchKernelGGL(blsgpu::probe::k_mad_probe, dim3(BLOCKS), dim3(THREADS), 0, st, c->at<uint32_t>(B_IO), iters, (uint32_t)pass);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(e1, st));
         HIP_TRY(hipEventSynchronize(e1));
@@ -1159,10 +923,10 @@ BLSGPU_EXPORT int blsgpu_ctx_set_fexp_team_threshold(blsgpu_ctx* c, size_t resul
 // Diagnostic (tools/exact_trace.py): copies the first `bytes` bytes of the line records of the last line-stream call.
 BLSGPU_EXPORT int blsgpu_debug_read_lines(blsgpu_ctx* c, void* host_buf, size_t bytes) {
     if (!c || !host_buf) return fail(-EINVAL, "NULL argument");
-    if (bytes > c->lines_cap) return fail(-EINVAL, "more than the buffer holds");
+    if (bytes > c->buf[B_LINES].cap) return fail(-EINVAL, "more than the buffer holds");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(host_buf, c->d_lines, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_buf, c->buf[B_LINES].p, bytes, hipMemcpyDeviceToHost));
     return 0;
 }
 // Diagnostic (tools/fexp_trace.py): device buffer of BLS28_FEXP_NOPS x 576 bytes that receives the accumulator of
@@ -1205,17 +969,17 @@ BLSGPU_EXPORT int blsgpu_ctx_set_mp3_threshold(blsgpu_ctx* c, size_t pairs) {
 BLSGPU_EXPORT int blsgpu_ctx_reserve(blsgpu_ctx* c, size_t max_pairs) {
     if (!c) return fail(-EINVAL, "ctx is NULL");
     HIP_TRY(hipSetDevice(c->device));
-    if (int rc = ensure_workspace(c, max_pairs)) return rc;
+    if (int rc = ensure_partials(c, pairs_partials(max_pairs))) return rc;
     if (max_pairs >= c->ls_threshold) {
         // the line-stream stage's buffers as well (a call of that size takes them): line records of one slice, the
         // flags and the work list, and dense partial products for the usual chunking (ls_teams accumulators plus 68 per
         // group of at least ls_min_group pairs); a call that needs more grows them itself
         const size_t n = max_pairs < LS_MAX_PAIRS ? max_pairs : LS_MAX_PAIRS;
         const size_t teams = c->ls_teams + blsgpu::ml::LINES * (n / (c->ls_min_group ? c->ls_min_group : 1) + 1);
-        if (grow_buffer(c, &c->d_lines, &c->lines_cap, n * blsgpu::ml::LINES * blsgpu::ml::LINE_DW * 4) ||
-            grow_buffer(c, &c->d_bad, &c->bad_cap, n) || grow_elems(c, &c->d_degen, &c->degen_cap, n + 2) ||
-            grow_buffer(c, &c->d_lsp[0], &c->lsp_cap[0], teams * blsgpu::ml::DENSE_DW * 4) ||
-            grow_buffer(c, &c->d_lsp[1], &c->lsp_cap[1], (teams / 8 + blsgpu::ml::LINES) * blsgpu::ml::DENSE_DW * 4)) {
+        if (c->grow(B_LINES, n * blsgpu::ml::LINES * blsgpu::ml::LINE_DW * 4) ||
+            c->grow(B_BAD, n) || c->grow(B_DEGEN, (n + 2) * 4) ||
+            c->grow(B_LSP0, teams * blsgpu::ml::DENSE_DW * 4) ||
+            c->grow(B_LSP1, (teams / 8 + blsgpu::ml::LINES) * blsgpu::ml::DENSE_DW * 4)) {
             (void)hipGetLastError();
             return fail(-ENOMEM, "no memory for the line-stream workspace (calls of that size will use the wavefront-VM kernels)");
         }
@@ -1226,18 +990,13 @@ BLSGPU_EXPORT int blsgpu_ctx_reserve(blsgpu_ctx* c, size_t max_pairs) {
 // Bytes of HBM the context holds, by purpose (grow-only buffers: the high-water mark of the calls made so far).
 BLSGPU_EXPORT int blsgpu_ctx_workspace_bytes(blsgpu_ctx* c, size_t out[BLSGPU_WS_FIELDS]) {
     if (!c || !out) return fail(-EINVAL, "NULL argument");
-    out[BLSGPU_WS_PARTIALS] = 2 * c->part_cap * 576;
-    out[BLSGPU_WS_STAGING] = c->io_cap;
-    out[BLSGPU_WS_LINES] = c->lines_cap;
-    out[BLSGPU_WS_LINE_PRODUCTS] = c->lsp_cap[0] + c->lsp_cap[1];
-    out[BLSGPU_WS_FLAGS_AND_LISTS] = c->bad_cap + c->degen_cap * 4;
-    out[BLSGPU_WS_GROUP_SUMS] = c->msm_part_cap * 4 + c->bucket_cap * 4;
-    out[BLSGPU_WS_SLOTS] = c->fexp_ws_cap + c->h2c_ws_cap;
-    size_t total = 0;
-    for (int i = 0; i < BLSGPU_WS_TOTAL; i++) total += out[i];
-    // the fixed-base table, the HD derivation slice and the share-check commitments have no field of their own: they
-    // count in the total only
-    total += (c->d_fix_table ? blsgpu::g1fix::TABLE_BYTES : 0) + c->fix_ws_cap + c->poly_ws_cap;
+    for (int i = 0; i < BLSGPU_WS_FIELDS; i++) out[i] = 0;
+    size_t total = c->d_fix_table ? blsgpu::g1fix::TABLE_BYTES : 0;
+    for (int b = 0; b < B_COUNT; b++) {
+        const size_t bytes = c->buf[b].cap / BUF_INFO[b].unit * BUF_INFO[b].unit;
+        if (BUF_INFO[b].ws_field != BLSGPU_WS_TOTAL) out[BUF_INFO[b].ws_field] += bytes;
+        total += bytes;
+    }
     out[BLSGPU_WS_TOTAL] = total;
     return 0;
 }
@@ -1260,10 +1019,10 @@ static int launch_fexp_team(blsgpu_ctx* c, const uint32_t* d_in, size_t m, size_
     using namespace blsgpu;
     const WaveShape ws = wave_shape(c, (groups + ml::TEAMS - 1) / ml::TEAMS);
     const size_t waves = (size_t)ws.blocks * (ws.threads / 64);                 // every launched wavefront owns rows of the workspace
-    if (int rc = grow_buffer(c, &c->d_fexp_ws, &c->fexp_ws_cap, waves * (ml::TEAMS + 1) * BLS28_FEXP_NSLOTS * ml::DENSE_DW * 4)) return rc;
+    if (int rc = c->grow(B_FEXP_WS, waves * (ml::TEAMS + 1) * BLS28_FEXP_NSLOTS * ml::DENSE_DW * 4)) return rc;
     KernelTimer kt(c, st, 2);
     hipLaunchKernelGGL(fx::k_fexp_team, dim3(ws.blocks), dim3(ws.threads), 0, st, d_in, (uint32_t)m, (uint32_t)istride, (uint32_t)gstride,
-                       (uint32_t)groups, (int32_t*)c->d_fexp_ws, (uint32_t*)d_out_bytes, (uint32_t*)c->d_fexp_dbg);
+                       (uint32_t)groups, c->at<int32_t>(B_FEXP_WS), (uint32_t*)d_out_bytes, (uint32_t*)c->d_fexp_dbg);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1295,7 +1054,7 @@ static int launch_fexp_reg(blsgpu_ctx* c, const uint32_t* d_in, size_t m, size_t
 static int reduce_chain(blsgpu_ctx* c, const uint32_t* d_in, size_t m, size_t groups, size_t istride, size_t gstride,
                         bool do_final, uint32_t* d_out_partial, void* d_out_bytes, hipStream_t st) {
     const uint32_t* src = d_in;
-    int pp = (d_in == c->d_part[0]) ? 1 : 0;
+    int pp = (d_in == c->part(0)) ? 1 : 0;
     size_t lds = (size_t)REDUCE_WAVES * blsgpu::TEAM_BYTES;
     if (groups > 65535) return fail(-EINVAL, "too many groups");
     while (true) {
@@ -1306,9 +1065,9 @@ static int reduce_chain(blsgpu_ctx* c, const uint32_t* d_in, size_t m, size_t gr
         bool last = blocks == 1;
         // the level that leaves one partial per group hands it to the register forms (one more launch, but the VM's
         // final exponentiation inside k_reduce is 1.25 ms of one wavefront)
-        const bool hand_over = last && do_final && use_fexp_reg(c, 1, groups) && groups <= c->part_cap;
-        uint32_t* dst = (last && !hand_over) ? d_out_partial : c->d_part[pp];
-        if (!last && blocks * groups > c->part_cap) return fail(-ENOMEM, "workspace too small; call blsgpu_ctx_reserve");
+        const bool hand_over = last && do_final && use_fexp_reg(c, 1, groups) && groups <= c->part_cap();
+        uint32_t* dst = (last && !hand_over) ? d_out_partial : c->part(pp);
+        if (!last && blocks * groups > c->part_cap()) return fail(-ENOMEM, "workspace too small; call blsgpu_ctx_reserve");
         {
             KernelTimer kt(c, st, (last && do_final && !hand_over) ? 2 : 1);
             hipLaunchKernelGGL(blsgpu::k_reduce, dim3((unsigned)blocks, (unsigned)groups), dim3(REDUCE_WAVES * 64), lds, st, c->tabs,
@@ -1331,22 +1090,33 @@ static int reduce_chain(blsgpu_ctx* c, const uint32_t* d_in, size_t m, size_t gr
 // Then k_miller_slow: it rewrites the partials of the blocks that met a degenerate pair with the
 // reference-faithful program (normally none: every wavefront leaves at once).
 constexpr unsigned SLOW_GRID = 3072;           // three wavefronts per SIMD (166 VGPRs, 10 KB of LDS each)
+// Which Miller kernel runs `groups` runs of gsz pairs, hence how many partials come out per group (bpg).
 // team: 0 = choose by batch size; 2 / 3 = k_miller_mp with that many pairs per wavefront (groups of two or three pairs: one team
 // per group, the group's product comes out of the Miller kernel)
-static int launch_miller(blsgpu_ctx* c, const void* d_g1, const void* d_g2, const void* d_inf, size_t gsz, size_t groups, bool one_per_block,
-                         uint32_t* d_partials, hipStream_t st, size_t* bpg_out, int team = 0) {
+struct MillerPlan { bool wide, mp, mp2; size_t per_block, bpg; };
+static MillerPlan miller_plan(const blsgpu_ctx* c, size_t gsz, size_t groups, bool one_per_block, int team = 0) {
+    MillerPlan p;
     // a few pairs: one pair per two-wavefront workgroup with a product per lane (blsgpu_mlw.hip), every pair its own partial
     // (where the one-pair-per-wavefront k_miller ran: calls below the throughput kernels' threshold)
-    const bool wide = !team && gsz * groups <= c->miller_wide_max && !use_mp(c, gsz * groups);
-    const bool mp = team ? true : (!wide && !one_per_block && use_mp(c, gsz * groups));
-    const bool mp2 = team ? team == 2 : (mp && use_mp2(c, gsz * groups));   // a few thousand pairs: teams of two fill the chip
-    const size_t per_block = (one_per_block || wide) ? 1 : (mp ? (mp2 ? (size_t)2 : (size_t)BLSVM_MP_G) : (size_t)MILLER_WAVES);
-    size_t bpg = (gsz + per_block - 1) / per_block;
+    p.wide = !team && gsz * groups <= c->miller_wide_max && !use_mp(c, gsz * groups);
+    p.mp = team ? true : (!p.wide && !one_per_block && use_mp(c, gsz * groups));
+    p.mp2 = team ? team == 2 : (p.mp && use_mp2(c, gsz * groups));   // a few thousand pairs: teams of two fill the chip
+    p.per_block = (one_per_block || p.wide) ? 1 : (p.mp ? (p.mp2 ? (size_t)2 : (size_t)BLSVM_MP_G) : (size_t)MILLER_WAVES);
+    p.bpg = (gsz + p.per_block - 1) / p.per_block;
+    return p;
+}
+// The caller has sized the workspace for miller_plan(...).bpg x groups partials (ensure_partials) BEFORE it took d_partials:
+// nothing grows here -- a grown buffer would leave that pointer on a retired one -- and a launch that does not fit fails.
+static int launch_miller(blsgpu_ctx* c, const void* d_g1, const void* d_g2, const void* d_inf, size_t gsz, size_t groups, bool one_per_block,
+                         uint32_t* d_partials, hipStream_t st, size_t* bpg_out, int team = 0) {
+    const auto [wide, mp, mp2, per_block, bpg] = miller_plan(c, gsz, groups, one_per_block, team);
     *bpg_out = bpg;
     if (bpg * groups > 0x7FFFFFFFull) return fail(-EINVAL, "batch too large");
-    if (bpg * groups + 2 > c->degen_cap) return fail(-ENOMEM, "work list too small");
-    blsgpu::DegenList dg{c->d_degen, c->d_degen + 1, (const uint8_t*)d_inf};
-    HIP_TRY(hipMemsetAsync(c->d_degen, 0, sizeof(uint32_t), st));
+    if ((d_partials == c->part(0) || d_partials == c->part(1)) && bpg * groups > c->part_cap())
+        return fail(-ENOMEM, "partial buffer too small for the Miller kernel's blocks");
+    if (bpg * groups + 2 > c->degen_cap()) return fail(-ENOMEM, "work list too small");
+    blsgpu::DegenList dg{c->at<uint32_t>(B_DEGEN), c->at<uint32_t>(B_DEGEN) + 1, (const uint8_t*)d_inf};
+    HIP_TRY(hipMemsetAsync(c->at<uint32_t>(B_DEGEN), 0, sizeof(uint32_t), st));
     if (wide) {
         KernelTimer kt(c, st, 0);
         if (gsz * groups <= c->miller_wide3_max)
@@ -1377,12 +1147,12 @@ static int launch_miller(blsgpu_ctx* c, const void* d_g1, const void* d_g2, cons
     // takes 6 ms per PAIR.  Both kernels leave at once when the list is empty.
     const size_t nv = bpg * groups * per_block;            // virtual pairs: every block could be listed
     if (c->vm_exact_lanes && nv <= ((size_t)1 << 16) &&
-        !grow_buffer(c, &c->d_lines, &c->lines_cap, nv * blsgpu::ml::LINES * blsgpu::ml::LINE_DW * 4) && !grow_buffer(c, &c->d_bad, &c->bad_cap, nv)) {
+        !c->grow(B_LINES, nv * blsgpu::ml::LINES * blsgpu::ml::LINE_DW * 4) && !c->grow(B_BAD, nv)) {
         KernelTimer kt(c, st, 3);
         hipLaunchKernelGGL(blsgpu::ml::k_ml_lines_exact, dim3(1024), dim3(64), 0, st, (const uint32_t*)d_g1, (const uint32_t*)d_g2, (uint32_t)nv,
-                           (int32_t*)c->d_lines, (uint8_t*)c->d_bad, dg, (uint32_t)gsz, (uint32_t)bpg, (uint32_t)per_block);
+                           c->at<int32_t>(B_LINES), c->at<uint8_t>(B_BAD), dg, (uint32_t)gsz, (uint32_t)bpg, (uint32_t)per_block);
         hipLaunchKernelGGL(blsgpu::ml::k_ml_small, dim3((unsigned)((bpg * groups + blsgpu::ml::TEAMS - 1) / blsgpu::ml::TEAMS)), dim3(64), 0, st,
-                           (const int32_t*)c->d_lines, (const uint8_t*)c->d_bad, (uint32_t)nv, (uint32_t)per_block, (uint32_t)(bpg * groups),
+                           c->at<int32_t>(B_LINES), c->at<uint8_t>(B_BAD), (uint32_t)nv, (uint32_t)per_block, (uint32_t)(bpg * groups),
                            d_partials, 144u, (const uint32_t*)dg.count, (const uint32_t*)dg.blocks);
     } else {
         (void)hipGetLastError();
@@ -1400,8 +1170,10 @@ static bool use_ls(const blsgpu_ctx* c, size_t gsz, size_t groups) {
 }
 // d_fused_out (optional): the caller wants nothing but the final exponentiation of each group's product -- the kernel
 // that ends the stage (k_ml_horner_fexp) then goes on to it in place: no partial, no further launch; *fused tells.
+// one_per_group: one accumulator per group whatever ls_min_group says (blsgpu_miller_loop_batch_dev: a group is a pair).
 static int launch_miller_ls(blsgpu_ctx* c, const void* d_g1, const void* d_g2, const void* d_inf, size_t gsz, size_t groups,
-                            uint32_t* d_partials, hipStream_t st, void* d_fused_out = nullptr, bool* fused = nullptr) {
+                            uint32_t* d_partials, hipStream_t st, void* d_fused_out = nullptr, bool* fused = nullptr,
+                            bool one_per_group = false) {
     using namespace blsgpu;
     const size_t n = gsz * groups;
     // chunks: equal runs of a group's pairs, one accumulator each per line index, sized so that about ls_teams
@@ -1419,31 +1191,31 @@ static int launch_miller_ls(blsgpu_ctx* c, const void* d_g1, const void* d_g2, c
     const size_t chunk = (gsz + cpg - 1) / cpg;
     cpg = (gsz + chunk - 1) / chunk;
     constexpr size_t FAN = 8;
-    const bool small = gsz < c->ls_min_group;              // one accumulator per group runs the whole loop (k_ml_small)
+    const bool small = one_per_group || gsz < c->ls_min_group;   // one accumulator per group runs the whole loop (k_ml_small)
     if (c->test_ls_nomem ||                                // tests/test_gpu_alternate_forms.py: the fallback below, without exhausting a GPU
-        grow_buffer(c, &c->d_lines, &c->lines_cap, n * ml::LINES * ml::LINE_DW * 4) ||
-        (!small && grow_buffer(c, &c->d_lsp[0], &c->lsp_cap[0], groups * cpg * ml::LINES * ml::DENSE_DW * 4)) ||
-        (!small && grow_buffer(c, &c->d_lsp[1], &c->lsp_cap[1], groups * ((cpg + FAN - 1) / FAN) * ml::LINES * ml::DENSE_DW * 4)) ||
-        grow_buffer(c, &c->d_bad, &c->bad_cap, n) ||
-        grow_elems(c, &c->d_degen, &c->degen_cap, n + 2)) {
+        c->grow(B_LINES, n * ml::LINES * ml::LINE_DW * 4) ||
+        (!small && c->grow(B_LSP0, groups * cpg * ml::LINES * ml::DENSE_DW * 4)) ||
+        (!small && c->grow(B_LSP1, groups * ((cpg + FAN - 1) / FAN) * ml::LINES * ml::DENSE_DW * 4)) ||
+        c->grow(B_BAD, n) ||
+        c->grow(B_DEGEN, (n + 2) * 4)) {
         (void)hipGetLastError();
         return -ENOMEM;                                    // the caller falls back to the wavefront-VM kernels
     }
-    DegenList dg{c->d_degen, c->d_degen + 1, (const uint8_t*)d_inf};
-    HIP_TRY(hipMemsetAsync(c->d_degen, 0, sizeof(uint32_t), st));
+    DegenList dg{c->at<uint32_t>(B_DEGEN), c->at<uint32_t>(B_DEGEN) + 1, (const uint8_t*)d_inf};
+    HIP_TRY(hipMemsetAsync(c->at<uint32_t>(B_DEGEN), 0, sizeof(uint32_t), st));
     {
         KernelTimer kt(c, st, 4);
         if (n <= c->ls_wide_max) {                       // a few thousand pairs: sixteen lanes each, the values in LDS, a product per lane
             hipLaunchKernelGGL(lsw::k_ml_lines_wide, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, st, (const uint32_t*)d_g1,
-                               (const uint32_t*)d_g2, (uint32_t)n, (int32_t*)c->d_lines, (uint8_t*)c->d_bad, dg);
+                               (const uint32_t*)d_g2, (uint32_t)n, c->at<int32_t>(B_LINES), c->at<uint8_t>(B_BAD), dg);
         } else if (n <= c->ls_quad_max) {                // few pairs: four lanes each, the tangent step's levels shared by the two pairs
             const WaveShape ws = wave_shape(c, (4 * n + 63) / 64);
             hipLaunchKernelGGL(ml::k_ml_lines4, dim3(ws.blocks), dim3(ws.threads), ws.threads * ml::sp::SLAB_BYTES_PER_LANE, st, (const uint32_t*)d_g1,
-                               (const uint32_t*)d_g2, (uint32_t)n, (int32_t*)c->d_lines, (uint8_t*)c->d_bad, dg);
+                               (const uint32_t*)d_g2, (uint32_t)n, c->at<int32_t>(B_LINES), c->at<uint8_t>(B_BAD), dg);
         } else {
             const WaveShape ws = wave_shape(c, (2 * n + 63) / 64);
             hipLaunchKernelGGL(ml::k_ml_lines2, dim3(ws.blocks), dim3(ws.threads), ws.threads * ml::sp::SLAB_BYTES_PER_LANE, st, (const uint32_t*)d_g1,
-                               (const uint32_t*)d_g2, (uint32_t)n, (int32_t*)c->d_lines, (uint8_t*)c->d_bad, dg);
+                               (const uint32_t*)d_g2, (uint32_t)n, c->at<int32_t>(B_LINES), c->at<uint8_t>(B_BAD), dg);
         }
     }
     HIP_TRY(hipGetLastError());
@@ -1451,15 +1223,15 @@ static int launch_miller_ls(blsgpu_ctx* c, const void* d_g1, const void* d_g2, c
         // when the list is empty)
         KernelTimer kt(c, st, 3);
         hipLaunchKernelGGL(ml::k_ml_lines_exact, dim3(2048), dim3(64), 0, st, (const uint32_t*)d_g1, (const uint32_t*)d_g2, (uint32_t)n,
-                           (int32_t*)c->d_lines, (uint8_t*)c->d_bad, dg, 0u, 0u, 0u);
+                           c->at<int32_t>(B_LINES), c->at<uint8_t>(B_BAD), dg, 0u, 0u, 0u);
     }
     HIP_TRY(hipGetLastError());
     if (small) {
         {
             KernelTimer kt(c, st, 5);
             const WaveShape ws = wave_shape(c, (groups + ml::TEAMS - 1) / ml::TEAMS);
-            hipLaunchKernelGGL(ml::k_ml_small, dim3(ws.blocks), dim3(ws.threads), 0, st, (const int32_t*)c->d_lines,
-                               (const uint8_t*)c->d_bad, (uint32_t)n, (uint32_t)gsz, (uint32_t)groups, d_partials, 144u,
+            hipLaunchKernelGGL(ml::k_ml_small, dim3(ws.blocks), dim3(ws.threads), 0, st, c->at<int32_t>(B_LINES),
+                               c->at<uint8_t>(B_BAD), (uint32_t)n, (uint32_t)gsz, (uint32_t)groups, d_partials, 144u,
                                (const uint32_t*)nullptr, (const uint32_t*)nullptr);
         }
         HIP_TRY(hipGetLastError());
@@ -1470,9 +1242,9 @@ static int launch_miller_ls(blsgpu_ctx* c, const void* d_g1, const void* d_g2, c
     {
         KernelTimer kt(c, st, 5);
         const WaveShape ws = wave_shape(c, (teams + ml::TEAMS - 1) / ml::TEAMS);
-        hipLaunchKernelGGL(ml::k_ml_accum, dim3(ws.blocks), dim3(ws.threads), 0, st, (const int32_t*)c->d_lines,
-                           (const uint8_t*)c->d_bad, (uint32_t)n, (uint32_t)gsz, (uint32_t)chunk, (uint32_t)cpg, (uint32_t)teams,
-                           (int32_t*)c->d_lsp[0]);
+        hipLaunchKernelGGL(ml::k_ml_accum, dim3(ws.blocks), dim3(ws.threads), 0, st, c->at<int32_t>(B_LINES),
+                           c->at<uint8_t>(B_BAD), (uint32_t)n, (uint32_t)gsz, (uint32_t)chunk, (uint32_t)cpg, (uint32_t)teams,
+                           c->lsp(0));
     }
     HIP_TRY(hipGetLastError());
     int cur = 0;
@@ -1481,13 +1253,13 @@ static int launch_miller_ls(blsgpu_ctx* c, const void* d_g1, const void* d_g2, c
         teams = groups * cpo * ml::LINES;
         KernelTimer kt(c, st, 6);
         if (teams <= c->ls_merge_wide_max)                                 // few outputs: one wavefront each, a product per lane
-            hipLaunchKernelGGL(fxw::k_ml_merge_wide, dim3((unsigned)teams), dim3(64), 0, st, (const int32_t*)c->d_lsp[cur], (uint32_t)cpg,
-                               (uint32_t)FAN, (uint32_t)cpo, (int32_t*)c->d_lsp[cur ^ 1]);
+            hipLaunchKernelGGL(fxw::k_ml_merge_wide, dim3((unsigned)teams), dim3(64), 0, st, c->lsp(cur), (uint32_t)cpg,
+                               (uint32_t)FAN, (uint32_t)cpo, c->lsp(cur ^ 1));
         else {
             const WaveShape ws = wave_shape(c, (teams + ml::TEAMS - 1) / ml::TEAMS);
             hipLaunchKernelGGL(ml::k_ml_merge, dim3(ws.blocks), dim3(ws.threads), 0, st,
-                               (const int32_t*)c->d_lsp[cur], (uint32_t)cpg, (uint32_t)FAN, (uint32_t)cpo, (uint32_t)teams,
-                               (int32_t*)c->d_lsp[cur ^ 1]);
+                               c->lsp(cur), (uint32_t)cpg, (uint32_t)FAN, (uint32_t)cpo, (uint32_t)teams,
+                               c->lsp(cur ^ 1));
         }
         HIP_TRY(hipGetLastError());
         cpg = cpo;
@@ -1497,7 +1269,7 @@ static int launch_miller_ls(blsgpu_ctx* c, const void* d_g1, const void* d_g2, c
     {
         const bool fuse = d_fused_out != nullptr && use_fexp_wide(c, 1, groups);
         KernelTimer kt(c, st, fuse ? 2 : 7);
-        hipLaunchKernelGGL(fxw::k_ml_horner_fexp, dim3((unsigned)groups), dim3(64), 0, st, (const int32_t*)c->d_lsp[cur], d_partials, 144u,
+        hipLaunchKernelGGL(fxw::k_ml_horner_fexp, dim3((unsigned)groups), dim3(64), 0, st, c->lsp(cur), d_partials, 144u,
                            (uint32_t*)(fuse ? d_fused_out : nullptr));
         if (fused) *fused = fuse;
     }
@@ -1520,11 +1292,10 @@ static int grouped_pairing(blsgpu_ctx* c, const void* d_g1, const void* d_g2, co
         }
         return 0;
     }
-    size_t need_pairs = (gsz + 3) * groups;            // every group rounds its team count up
-    if ((need_pairs + 1) / 2 + (need_pairs + MILLER_WAVES - 1) / MILLER_WAVES + 1 > c->part_cap) {
-        int rc = ensure_workspace(c, need_pairs);
-        if (rc) return rc;
-    }
+    // every group rounds its team count up; the wide Miller loop leaves one partial per pair
+    size_t partials = pairs_partials((gsz + 3) * groups);
+    const size_t vm_blocks = miller_plan(c, gsz, groups, false).bpg * groups;
+    if (int rc = ensure_partials(c, partials > vm_blocks ? partials : vm_blocks)) return rc;
     size_t bpg = 0;
     bool ls_done = false;
     if (gsz > 0 && use_ls(c, gsz, groups)) {
@@ -1535,7 +1306,7 @@ static int grouped_pairing(blsgpu_ctx* c, const void* d_g1, const void* d_g2, co
             bool fused = false;
             // one partial per group comes out of the stage: straight into the caller's buffer when that is all it wants
             // (the sharded entries), no copying pass of k_reduce behind it
-            uint32_t* target = (d_out_partial && !d_out_bytes) ? d_out_partial : c->d_part[0];
+            uint32_t* target = (d_out_partial && !d_out_bytes) ? d_out_partial : c->part(0);
             rc = launch_miller_ls(c, d_g1, d_g2, d_inf, gsz, groups, target, st, d_out_bytes, &fused);
             if (rc == 0 && (fused || target == d_out_partial)) return 0;   // (fused: the stage's last kernel ran the final exponentiations too)
             bpg = 1;
@@ -1544,7 +1315,7 @@ static int grouped_pairing(blsgpu_ctx* c, const void* d_g1, const void* d_g2, co
             for (size_t g0 = 0; g0 < groups && !rc; g0 += per) {
                 const size_t gn = groups - g0 < per ? groups - g0 : per;
                 rc = launch_miller_ls(c, (const char*)d_g1 + g0 * gsz * BLSGPU_G1_BYTES, (const char*)d_g2 + g0 * gsz * BLSGPU_G2_BYTES,
-                                      d_inf ? (const char*)d_inf + g0 * gsz * 2 : nullptr, gsz, gn, c->d_part[0] + g0 * 144, st);
+                                      d_inf ? (const char*)d_inf + g0 * gsz * 2 : nullptr, gsz, gn, c->part(0) + g0 * 144, st);
             }
             bpg = 1;
         } else if (groups == 1) {
@@ -1552,7 +1323,7 @@ static int grouped_pairing(blsgpu_ctx* c, const void* d_g1, const void* d_g2, co
             for (size_t p0 = 0; p0 < gsz && !rc; p0 += LS_MAX_PAIRS, k++) {
                 const size_t pn = gsz - p0 < LS_MAX_PAIRS ? gsz - p0 : LS_MAX_PAIRS;
                 rc = launch_miller_ls(c, (const char*)d_g1 + p0 * BLSGPU_G1_BYTES, (const char*)d_g2 + p0 * BLSGPU_G2_BYTES,
-                                      d_inf ? (const char*)d_inf + p0 * 2 : nullptr, pn, 1, c->d_part[0] + k * 144, st);
+                                      d_inf ? (const char*)d_inf + p0 * 2 : nullptr, pn, 1, c->part(0) + k * 144, st);
             }
             bpg = k;
         } else {
@@ -1563,10 +1334,10 @@ static int grouped_pairing(blsgpu_ctx* c, const void* d_g1, const void* d_g2, co
     }
     if (ls_done) {
     } else if (gsz > 0) {
-        int rc = launch_miller(c, d_g1, d_g2, d_inf, gsz, groups, false, c->d_part[0], st, &bpg);
+        int rc = launch_miller(c, d_g1, d_g2, d_inf, gsz, groups, false, c->part(0), st, &bpg);
         if (rc) return rc;
     }
-    return reduce_chain(c, c->d_part[0], bpg, groups, 1, bpg, d_out_bytes != nullptr, d_out_partial, d_out_bytes, st);
+    return reduce_chain(c, c->part(0), bpg, groups, 1, bpg, d_out_bytes != nullptr, d_out_partial, d_out_bytes, st);
 }
 
 BLSGPU_EXPORT int blsgpu_miller_product_dev(blsgpu_ctx* c, const void* d_g1, const void* d_g2, const void* d_inf, size_t n,
@@ -1598,10 +1369,8 @@ BLSGPU_EXPORT int blsgpu_final_exp_product_batch_dev(blsgpu_ctx* c, const void* 
     if (m > 0 && !d_partials) return fail(-EINVAL, "NULL partials");
     HIP_TRY(hipSetDevice(c->device));
     StreamGuard sg(c, (hipStream_t)stream);
-    if (((m + REDUCE_PER_BLOCK - 1) / REDUCE_PER_BLOCK) * groups + 1 > c->part_cap) {
-        int rc = ensure_workspace(c, m * groups * MILLER_WAVES);
-        if (rc) return rc;
-    }
+    // the first level of the reduce chain leaves a partial per 64 of a group's
+    if (int rc = ensure_partials(c, ((m + REDUCE_PER_BLOCK - 1) / REDUCE_PER_BLOCK) * groups + 1)) return rc;
     return reduce_chain(c, (const uint32_t*)d_partials, m, groups, groups, 1, true, nullptr, d_out, (hipStream_t)stream);
 }
 
@@ -1620,18 +1389,11 @@ BLSGPU_EXPORT int blsgpu_pairing_multi(blsgpu_ctx* c, const uint8_t* g1, const u
     if (!c || !out) return fail(-EINVAL, "NULL argument");
     if (n > 0 && (!g1 || !g2)) return fail(-EINVAL, "NULL point buffer");
     HIP_TRY(hipSetDevice(c->device));
-    size_t need = n * (BLSGPU_G1_BYTES + BLSGPU_G2_BYTES + 2);
-    if (int rc_ = grow_buffer(c, &c->d_io, &c->io_cap, need)) return rc_;
-    char* d1 = (char*)c->d_io;
-    char* d2 = d1 + n * BLSGPU_G1_BYTES;
-    char* di = d2 + n * BLSGPU_G2_BYTES;
-    if (n) {
-        HIP_TRY(hipMemcpyAsync(d1, g1, n * BLSGPU_G1_BYTES, hipMemcpyHostToDevice, 0));
-        HIP_TRY(hipMemcpyAsync(d2, g2, n * BLSGPU_G2_BYTES, hipMemcpyHostToDevice, 0));
-        if (inf) HIP_TRY(hipMemcpyAsync(di, inf, n * 2, hipMemcpyHostToDevice, 0));
-    }
-    int rc = blsgpu_pairing_multi_dev(c, d1, d2, inf ? di : nullptr, n, c->d_out, nullptr);
-    if (rc) return rc;
+    Staging s(c);
+    const int d1 = s.in(g1, n * BLSGPU_G1_BYTES), d2 = s.in(g2, n * BLSGPU_G2_BYTES), di = s.in(inf, n * 2);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    if (int rc = blsgpu_pairing_multi_dev(c, s.at(d1), s.at(d2), s.opt(di), n, c->d_out, nullptr)) return rc;
     HIP_TRY(hipMemcpy(out, c->d_out, BLSGPU_FQ12_BYTES, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -1654,7 +1416,7 @@ BLSGPU_EXPORT int blsgpu_miller_loop_batch_dev(blsgpu_ctx* c, const void* d_g1, 
         const hipStream_t st = (hipStream_t)stream;
         const size_t slice = 262144;
         const size_t m0 = n < slice ? n : slice;
-        if (c->miller_exact_fast && grow_buffer(c, &c->d_exflags, &c->exflags_cap, 2 * m0) == 0 && ensure_workspace(c, 2 * m0) == 0) {
+        if (c->miller_exact_fast && c->grow(B_EXFLAGS, 2 * m0) == 0 && ensure_partials(c, m0 + (m0 + 1) / 2 + 1) == 0) {
             // the ordinary line-stream kernels with one accumulator per pair, then one Fq2 factor per pair turns the fast value into the
             // reference's (k_ml_exact_fixup: 73 dependent inversions per pair become one); a pair the fast formulas are not valid for
             // -- or whose py is 0, which the factor divides by -- takes the reference's own lines inside the same launches
@@ -1664,29 +1426,29 @@ BLSGPU_EXPORT int blsgpu_miller_loop_batch_dev(blsgpu_ctx* c, const void* d_g1, 
                 const uint32_t* p1 = (const uint32_t*)d_g1 + lo * 24;
                 const uint32_t* p2 = (const uint32_t*)d_g2 + lo * 48;
                 hipLaunchKernelGGL(ml::k_ml_exact_flags, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, p1, d_inf ? (const uint8_t*)d_inf + 2 * lo : nullptr,
-                                   (uint32_t)m, (uint8_t*)c->d_exflags);
-                const int rc_ = launch_miller_ls(c, p1, p2, c->d_exflags, 1, m, c->d_part[0], st);
+                                   (uint32_t)m, c->at<uint8_t>(B_EXFLAGS));
+                const int rc_ = launch_miller_ls(c, p1, p2, c->at<uint8_t>(B_EXFLAGS), 1, m, c->part(0), st, nullptr, nullptr, true);
                 if (rc_ == -ENOMEM && lo == 0) { ok = false; break; }          // no room for the line records: the forms below
                 if (rc_) return rc_;
-                hipLaunchKernelGGL(ml::k_ml_exact_fixup, dim3((unsigned)((2 * m + 255) / 256)), dim3(256), 0, st, p1, (const int32_t*)c->d_lines,
-                                   (const uint8_t*)c->d_bad, c->d_part[0], (uint32_t)m, (uint32_t*)d_out + lo * 144);
+                hipLaunchKernelGGL(ml::k_ml_exact_fixup, dim3((unsigned)((2 * m + 255) / 256)), dim3(256), 0, st, p1, c->at<int32_t>(B_LINES),
+                                   c->at<uint8_t>(B_BAD), c->part(0), (uint32_t)m, (uint32_t*)d_out + lo * 144);
                 HIP_TRY(hipGetLastError());
             }
             if (ok) return 0;
         }
-        if (grow_buffer(c, &c->d_lines, &c->lines_cap, m0 * ml::LINES * ml::LINE_DW * 4) == 0 && grow_buffer(c, &c->d_bad, &c->bad_cap, m0) == 0 &&
-            grow_elems(c, &c->d_degen, &c->degen_cap, m0 + 2) == 0 && ensure_workspace(c, 2 * m0) == 0) {
+        if (c->grow(B_LINES, m0 * ml::LINES * ml::LINE_DW * 4) == 0 && c->grow(B_BAD, m0) == 0 &&
+            c->grow(B_DEGEN, (m0 + 2) * 4) == 0 && ensure_partials(c, m0 + (m0 + 1) / 2 + 1) == 0) {
             for (size_t lo = 0; lo < n; lo += slice) {
                 const size_t m = n - lo < slice ? n - lo : slice;
                 const uint32_t* p1 = (const uint32_t*)d_g1 + lo * 24;
                 const uint32_t* p2 = (const uint32_t*)d_g2 + lo * 48;
-                DegenList dg{c->d_degen, c->d_degen + 1, d_inf ? (const uint8_t*)d_inf + 2 * lo : nullptr};
-                hipLaunchKernelGGL(ml::k_ml_list_all, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (uint32_t)m, c->d_degen, c->d_degen + 1);
-                hipLaunchKernelGGL(ml::k_ml_lines_exact, dim3(2048), dim3(64), 0, st, p1, p2, (uint32_t)m, (int32_t*)c->d_lines, (uint8_t*)c->d_bad, dg, 0u, 0u, 0u);
+                DegenList dg{c->at<uint32_t>(B_DEGEN), c->at<uint32_t>(B_DEGEN) + 1, d_inf ? (const uint8_t*)d_inf + 2 * lo : nullptr};
+                hipLaunchKernelGGL(ml::k_ml_list_all, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (uint32_t)m, c->at<uint32_t>(B_DEGEN), c->at<uint32_t>(B_DEGEN) + 1);
+                hipLaunchKernelGGL(ml::k_ml_lines_exact, dim3(2048), dim3(64), 0, st, p1, p2, (uint32_t)m, c->at<int32_t>(B_LINES), c->at<uint8_t>(B_BAD), dg, 0u, 0u, 0u);
                 const WaveShape ws = wave_shape(c, (m + ml::TEAMS - 1) / ml::TEAMS);
-                hipLaunchKernelGGL(ml::k_ml_small, dim3(ws.blocks), dim3(ws.threads), 0, st, (const int32_t*)c->d_lines, (const uint8_t*)c->d_bad, (uint32_t)m, 1u,
-                                   (uint32_t)m, c->d_part[0], 144u, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
-                hipLaunchKernelGGL(ml::k_ml_partials_to_bytes, dim3((unsigned)((m * 12 + 255) / 256)), dim3(256), 0, st, c->d_part[0], (uint32_t)(m * 12),
+                hipLaunchKernelGGL(ml::k_ml_small, dim3(ws.blocks), dim3(ws.threads), 0, st, c->at<int32_t>(B_LINES), c->at<uint8_t>(B_BAD), (uint32_t)m, 1u,
+                                   (uint32_t)m, c->part(0), 144u, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
+                hipLaunchKernelGGL(ml::k_ml_partials_to_bytes, dim3((unsigned)((m * 12 + 255) / 256)), dim3(256), 0, st, c->part(0), (uint32_t)(m * 12),
                                    (uint32_t*)d_out + lo * 144);
                 HIP_TRY(hipGetLastError());
             }
@@ -1705,19 +1467,12 @@ BLSGPU_EXPORT int blsgpu_miller_loop_batch(blsgpu_ctx* c, const uint8_t* g1, con
     if (!c || (n && (!g1 || !g2 || !out))) return fail(-EINVAL, "NULL argument");
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
-    size_t need = n * (BLSGPU_G1_BYTES + BLSGPU_G2_BYTES + BLSGPU_FQ12_BYTES + 2) + 64;
-    if (int rc_ = grow_buffer(c, &c->d_io, &c->io_cap, need)) return rc_;
-    char* dout = (char*)c->d_io;
-    char* d1 = dout + n * BLSGPU_FQ12_BYTES;
-    char* d2 = d1 + n * BLSGPU_G1_BYTES;
-    char* di = d2 + n * BLSGPU_G2_BYTES;
-    HIP_TRY(hipMemcpyAsync(d1, g1, n * BLSGPU_G1_BYTES, hipMemcpyHostToDevice, 0));
-    HIP_TRY(hipMemcpyAsync(d2, g2, n * BLSGPU_G2_BYTES, hipMemcpyHostToDevice, 0));
-    if (inf) HIP_TRY(hipMemcpyAsync(di, inf, n * 2, hipMemcpyHostToDevice, 0));
-    int rc = blsgpu_miller_loop_batch_dev(c, d1, d2, inf ? di : nullptr, n, dout, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out, dout, n * BLSGPU_FQ12_BYTES, hipMemcpyDeviceToHost));
-    return 0;
+    Staging s(c);
+    const int d1 = s.in(g1, n * BLSGPU_G1_BYTES), d2 = s.in(g2, n * BLSGPU_G2_BYTES), di = s.in(inf, n * 2), dout = s.out(out, n * BLSGPU_FQ12_BYTES);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    if (int rc = blsgpu_miller_loop_batch_dev(c, s.at(d1), s.at(d2), s.opt(di), n, s.at(dout), nullptr)) return rc;
+    return s.down();
 }
 
 // fq2_double_line_eval (q == NULL) / fq2_add_line_eval on n (R, [Q,] P) triples
@@ -1726,22 +1481,16 @@ BLSGPU_EXPORT int blsgpu_line_eval_batch(blsgpu_ctx* c, const uint8_t* r, const 
     if (n == 0) return 0;
     if (n > 0x00FFFFF0ull) return fail(-EINVAL, "n too large");
     HIP_TRY(hipSetDevice(c->device));
-    size_t need = n * (2 * BLSGPU_G2_BYTES + BLSGPU_G1_BYTES + BLSGPU_FQ12_BYTES) + 64;
-    if (int rc_ = grow_buffer(c, &c->d_io, &c->io_cap, need)) return rc_;
+    Staging s(c);
+    const int dr = s.in(r, n * BLSGPU_G2_BYTES), dq = s.in(q, n * BLSGPU_G2_BYTES), dp = s.in(p, n * BLSGPU_G1_BYTES), dout = s.out(out, n * BLSGPU_FQ12_BYTES);
+    if (int rc = s.alloc()) return rc;
     StreamGuard sg(c, nullptr);
-    char* dout = (char*)c->d_io;
-    char* dr = dout + n * BLSGPU_FQ12_BYTES;
-    char* dq = dr + n * BLSGPU_G2_BYTES;
-    char* dp = dq + n * BLSGPU_G2_BYTES;
-    HIP_TRY(hipMemcpyAsync(dr, r, n * BLSGPU_G2_BYTES, hipMemcpyHostToDevice, 0));
-    if (q) HIP_TRY(hipMemcpyAsync(dq, q, n * BLSGPU_G2_BYTES, hipMemcpyHostToDevice, 0));
-    HIP_TRY(hipMemcpyAsync(dp, p, n * BLSGPU_G1_BYTES, hipMemcpyHostToDevice, 0));
+    if (int rc = s.up()) return rc;
     const unsigned grid = (unsigned)(n < 16384 ? n : 16384);
-    hipLaunchKernelGGL(blsgpu::k_line_eval, dim3(grid), dim3(64), (size_t)blsgpu::SLOW_TEAM_BYTES, 0, c->tabs, (const uint32_t*)dr,
-                       q ? (const uint32_t*)dq : (const uint32_t*)nullptr, (const uint32_t*)dp, (uint32_t)n, (uint32_t*)dout);
+    hipLaunchKernelGGL(blsgpu::k_line_eval, dim3(grid), dim3(64), (size_t)blsgpu::SLOW_TEAM_BYTES, 0, c->tabs, (const uint32_t*)s.at(dr),
+                       (const uint32_t*)s.opt(dq), (const uint32_t*)s.at(dp), (uint32_t)n, (uint32_t*)s.at(dout));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, dout, n * BLSGPU_FQ12_BYTES, hipMemcpyDeviceToHost));
-    return 0;
+    return s.down();
 }
 
 // Fq12 field operations on n elements (op: 0 add, 1 sub, 2 mul, 3 neg, 4 invert), or a^e for one exponent
@@ -1751,22 +1500,17 @@ int fq12_op_host(blsgpu_ctx* c, uint32_t op, const uint8_t* a, const uint8_t* b,
     if (n == 0) return 0;
     if (n > 0x00FFFFF0ull || nbits > 0x10000) return fail(-EINVAL, "too large");
     HIP_TRY(hipSetDevice(c->device));
-    size_t need = n * BLSGPU_FQ12_BYTES * 3 + nbits + 64;
-    if (int rc_ = grow_buffer(c, &c->d_io, &c->io_cap, need)) return rc_;
+    Staging s(c);
+    const int da = s.in(a, n * BLSGPU_FQ12_BYTES), db = s.in(op <= 2 ? b : nullptr, n * BLSGPU_FQ12_BYTES), de = s.in(nbits ? ebits : nullptr, nbits),
+              dout = s.out(out, n * BLSGPU_FQ12_BYTES);
+    if (int rc = s.alloc()) return rc;
     StreamGuard sg(c, nullptr);
-    char* dout = (char*)c->d_io;
-    char* da = dout + n * BLSGPU_FQ12_BYTES;
-    char* db = da + n * BLSGPU_FQ12_BYTES;
-    char* de = db + n * BLSGPU_FQ12_BYTES;
-    HIP_TRY(hipMemcpyAsync(da, a, n * BLSGPU_FQ12_BYTES, hipMemcpyHostToDevice, 0));
-    if (op <= 2) HIP_TRY(hipMemcpyAsync(db, b, n * BLSGPU_FQ12_BYTES, hipMemcpyHostToDevice, 0));
-    if (nbits) HIP_TRY(hipMemcpyAsync(de, ebits, nbits, hipMemcpyHostToDevice, 0));
+    if (int rc = s.up()) return rc;
     const unsigned grid = (unsigned)(n < 16384 ? n : 16384);
-    hipLaunchKernelGGL(blsgpu::k_fq12_op, dim3(grid), dim3(64), (size_t)blsgpu::SLOW_TEAM_BYTES, 0, c->tabs, op, (const uint32_t*)da,
-                       (const uint32_t*)db, (const uint8_t*)de, (uint32_t)nbits, (uint32_t)n, (uint32_t*)dout);
+    hipLaunchKernelGGL(blsgpu::k_fq12_op, dim3(grid), dim3(64), (size_t)blsgpu::SLOW_TEAM_BYTES, 0, c->tabs, op, (const uint32_t*)s.at(da),
+                       (const uint32_t*)s.at(db), (const uint8_t*)s.at(de), (uint32_t)nbits, (uint32_t)n, (uint32_t*)s.at(dout));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, dout, n * BLSGPU_FQ12_BYTES, hipMemcpyDeviceToHost));
-    return 0;
+    return s.down();
 }
 }  // namespace
 BLSGPU_EXPORT int blsgpu_fq12_op_batch(blsgpu_ctx* c, int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out) {
@@ -1792,28 +1536,25 @@ BLSGPU_EXPORT int blsgpu_final_exp_batch(blsgpu_ctx* c, const uint8_t* in, size_
     if (!c || (m && (!in || !out))) return fail(-EINVAL, "NULL argument");
     if (m == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
-    size_t need = m * 576 * 2 + 64;
-    if (int rc_ = grow_buffer(c, &c->d_io, &c->io_cap, need)) return rc_;
-    int rc = ensure_workspace(c, m * MILLER_WAVES);
-    if (rc) return rc;
+    Staging s(c);
+    const int din = s.in(in, m * 576), dout = s.out(out, m * 576);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = ensure_partials(c, 3 * m + 1)) return rc;    // (one per element is written)
     StreamGuard sg(c, nullptr);
-    char* din = (char*)c->d_io;
-    char* dout = din + m * 576;
-    HIP_TRY(hipMemcpy(din, in, m * 576, hipMemcpyHostToDevice));
+    if (int rc = s.up()) return rc;
     size_t lds = (size_t)REDUCE_WAVES * blsgpu::TEAM_BYTES;
     unsigned blocks = (unsigned)((m + REDUCE_WAVES - 1) / REDUCE_WAVES);
     hipLaunchKernelGGL(blsgpu::k_bytes_to_partials, dim3(blocks), dim3(REDUCE_WAVES * 64), lds, 0, c->tabs,
-                       (const uint32_t*)din, (uint32_t)m, c->d_part[1]);
+                       (const uint32_t*)s.at(din), (uint32_t)m, c->part(1));
     HIP_TRY(hipGetLastError());
     if (use_fexp_reg(c, 1, m)) {
-        if (int rc2 = launch_fexp_reg(c, c->d_part[1], 1, 1, 1, m, dout, 0)) return rc2;
+        if (int rc2 = launch_fexp_reg(c, c->part(1), 1, 1, 1, m, s.at(dout), 0)) return rc2;
     } else {
-        hipLaunchKernelGGL(blsgpu::k_final_groups, dim3(blocks), dim3(REDUCE_WAVES * 64), lds, 0, c->tabs, c->d_part[1],
-                           1u, (uint32_t)m, (uint32_t*)dout);
+        hipLaunchKernelGGL(blsgpu::k_final_groups, dim3(blocks), dim3(REDUCE_WAVES * 64), lds, 0, c->tabs, c->part(1),
+                           1u, (uint32_t)m, (uint32_t*)s.at(dout));
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipMemcpy(out, dout, m * 576, hipMemcpyDeviceToHost));
-    return 0;
+    return s.down();
 }
 
 BLSGPU_EXPORT int blsgpu_final_exp(blsgpu_ctx* c, const uint8_t in[576], uint8_t out[576]) {
@@ -1834,17 +1575,18 @@ BLSGPU_EXPORT int blsgpu_pairing_multi_batch_dev(blsgpu_ctx* c, const void* d_g1
     hipStream_t st = (hipStream_t)stream;
     StreamGuard sg(c, st);
     if (gsz >= BATCH_TREE_MIN_GROUP) return grouped_pairing(c, d_g1, d_g2, d_inf, gsz, groups, nullptr, d_out, st);
-    int rc = ensure_workspace(c, (n + 1) * MILLER_WAVES);      // one partial per PAIR here
+    // every launch below leaves at most one partial per PAIR (miller_plan: bpg x groups <= n whichever kernel runs)
+    int rc = ensure_partials(c, 3 * (n + 1) + 1);
     if (rc) return rc;
     if (gsz >= 1 && use_ls(c, gsz, groups) && n <= LS_MAX_PAIRS) {
         // a large batch of small groups: point chains on lane pairs, then one accumulator per group (blsgpu_ml.hip)
-        rc = launch_miller_ls(c, d_g1, d_g2, d_inf, gsz, groups, c->d_part[0], st);
+        rc = launch_miller_ls(c, d_g1, d_g2, d_inf, gsz, groups, c->part(0), st);
         if (rc == 0) {
-            if (use_fexp_reg(c, 1, groups)) return launch_fexp_reg(c, c->d_part[0], 1, 1, 1, groups, d_out, st);
+            if (use_fexp_reg(c, 1, groups)) return launch_fexp_reg(c, c->part(0), 1, 1, 1, groups, d_out, st);
             size_t lds = (size_t)REDUCE_WAVES * blsgpu::TEAM_BYTES;
             unsigned blocks = (unsigned)((groups + REDUCE_WAVES - 1) / REDUCE_WAVES);
             KernelTimer kt(c, st, 2);
-            hipLaunchKernelGGL(blsgpu::k_final_groups, dim3(blocks), dim3(REDUCE_WAVES * 64), lds, st, c->tabs, c->d_part[0], 1u,
+            hipLaunchKernelGGL(blsgpu::k_final_groups, dim3(blocks), dim3(REDUCE_WAVES * 64), lds, st, c->tabs, c->part(0), 1u,
                                (uint32_t)groups, (uint32_t*)d_out);
             HIP_TRY(hipGetLastError());
             return 0;
@@ -1856,17 +1598,17 @@ BLSGPU_EXPORT int blsgpu_pairing_multi_batch_dev(blsgpu_ctx* c, const void* d_g1
     const bool team_groups = (gsz == 2 || gsz == (size_t)BLSVM_MP_G) && use_mp(c, n) && groups <= 0x7FFFFFFFull;
     if (n) {
         size_t bpg = 0;
-        rc = team_groups ? launch_miller(c, d_g1, d_g2, d_inf, gsz, groups, false, c->d_part[0], st, &bpg, (int)gsz)
-                         : launch_miller(c, d_g1, d_g2, d_inf, n, 1, true, c->d_part[0], st, &bpg);
+        rc = team_groups ? launch_miller(c, d_g1, d_g2, d_inf, gsz, groups, false, c->part(0), st, &bpg, (int)gsz)
+                         : launch_miller(c, d_g1, d_g2, d_inf, n, 1, true, c->part(0), st, &bpg);
         if (rc) return rc;
     }
     if (use_fexp_reg(c, team_groups ? 1 : gsz, groups))
-        return launch_fexp_reg(c, c->d_part[0], team_groups ? 1 : gsz, 1, team_groups ? 1 : gsz, groups, d_out, st);
+        return launch_fexp_reg(c, c->part(0), team_groups ? 1 : gsz, 1, team_groups ? 1 : gsz, groups, d_out, st);
     size_t lds = (size_t)REDUCE_WAVES * blsgpu::TEAM_BYTES;
     unsigned blocks = (unsigned)((groups + REDUCE_WAVES - 1) / REDUCE_WAVES);
     {
         KernelTimer kt(c, st, 2);
-        hipLaunchKernelGGL(blsgpu::k_final_groups, dim3(blocks), dim3(REDUCE_WAVES * 64), lds, st, c->tabs, c->d_part[0],
+        hipLaunchKernelGGL(blsgpu::k_final_groups, dim3(blocks), dim3(REDUCE_WAVES * 64), lds, st, c->tabs, c->part(0),
                            (uint32_t)(team_groups ? 1 : gsz), (uint32_t)groups, (uint32_t*)d_out);
     }
     HIP_TRY(hipGetLastError());
@@ -1880,21 +1622,12 @@ BLSGPU_EXPORT int blsgpu_pairing_multi_batch(blsgpu_ctx* c, const uint8_t* g1, c
     size_t n = gsz * groups;
     if (n && (!g1 || !g2)) return fail(-EINVAL, "NULL point buffer");
     HIP_TRY(hipSetDevice(c->device));
-    size_t need = n * (BLSGPU_G1_BYTES + BLSGPU_G2_BYTES + 2) + groups * 576 + 64;
-    if (int rc_ = grow_buffer(c, &c->d_io, &c->io_cap, need)) return rc_;
-    char* d1 = (char*)c->d_io;
-    char* d2 = d1 + n * BLSGPU_G1_BYTES;
-    char* dout = d2 + n * BLSGPU_G2_BYTES;
-    char* di = dout + groups * 576;
-    if (n) {
-        HIP_TRY(hipMemcpyAsync(d1, g1, n * BLSGPU_G1_BYTES, hipMemcpyHostToDevice, 0));
-        HIP_TRY(hipMemcpyAsync(d2, g2, n * BLSGPU_G2_BYTES, hipMemcpyHostToDevice, 0));
-        if (inf) HIP_TRY(hipMemcpyAsync(di, inf, n * 2, hipMemcpyHostToDevice, 0));
-    }
-    int rc = blsgpu_pairing_multi_batch_dev(c, d1, d2, inf ? di : nullptr, gsz, groups, dout, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out, dout, groups * 576, hipMemcpyDeviceToHost));
-    return 0;
+    Staging s(c);
+    const int d1 = s.in(g1, n * BLSGPU_G1_BYTES), d2 = s.in(g2, n * BLSGPU_G2_BYTES), di = s.in(inf, n * 2), dout = s.out(out, groups * 576);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    if (int rc = blsgpu_pairing_multi_batch_dev(c, s.at(d1), s.at(d2), s.opt(di), gsz, groups, s.at(dout), nullptr)) return rc;
+    return s.down();
 }
 
 BLSGPU_EXPORT int blsgpu_g1_msm(blsgpu_ctx* c, const uint8_t* pts, const uint8_t* scalars, size_t k, size_t groups,
@@ -1928,8 +1661,8 @@ static int map_to_g2_impl(blsgpu_ctx* c, const void* d_in, size_t n, void* d_out
     StreamGuard sg(c, st);
     const size_t teams = (2 * n + BLSVM_H1_NE - 1) / BLSVM_H1_NE;
     size_t need = teams * blsgpu::H1_IMG * 12 + (from_hashes ? n * 64 : 0);     // stage image (+ digests), u32
-    if (int rc_ = grow_elems(c, &c->d_msm_part, &c->msm_part_cap, need)) return rc_;
-    uint32_t* img = c->d_msm_part;
+    if (int rc_ = c->grow(B_MSM_PART, need * 4)) return rc_;
+    uint32_t* img = c->at<uint32_t>(B_MSM_PART);
     const size_t lds = (size_t)blsgpu::H1_TEAM_DW * 4;
     constexpr uint32_t BASE = BLSVM_H1_BASE - BLSVM_H1_STATE0, ACC = BLSVM_H1_ACC - BLSVM_H1_STATE0;
     const bool lanes = n >= c->h2c_lane_threshold;         // the three encoding stages one encoding per lane (k_h2c_sw*)
@@ -1986,14 +1719,14 @@ static int map_to_g2_impl(blsgpu_ctx* c, const void* d_in, size_t n, void* d_out
                            (uint32_t*)d_out);
     } else if (n <= c->h2c_quad_max) {   // a batch that leaves SIMDs empty on lane pairs: one message per lane QUAD
         const WaveShape ws = wave_shape(c, (4 * n + 63) / 64);                   // every launched lane owns rows of the workspace
-        if (int rc2 = grow_buffer(c, &c->d_h2c_ws, &c->h2c_ws_cap, (size_t)ws.blocks * ws.threads * BLS28_H2C_NSLOTS * 3 * blsgpu::r28::NL * 4)) return rc2;
+        if (int rc2 = c->grow(B_H2C_WS, (size_t)ws.blocks * ws.threads * BLS28_H2C_NSLOTS * 3 * blsgpu::r28::NL * 4)) return rc2;
         hipLaunchKernelGGL(blsgpu::k_h2c_clear_quads, dim3(ws.blocks), dim3(ws.threads), 0, st, c->tabs, img, (uint32_t)n,
-                           (uint32_t*)c->d_h2c_ws, (uint32_t*)d_out);
+                           c->at<uint32_t>(B_H2C_WS), (uint32_t*)d_out);
     } else {                               // one message per lane pair, the point operations as a script
         const WaveShape ws = wave_shape(c, (2 * n + 63) / 64);
-        if (int rc2 = grow_buffer(c, &c->d_h2c_ws, &c->h2c_ws_cap, (size_t)ws.blocks * ws.threads * BLS28_H2C_NSLOTS * 3 * blsgpu::r28::NL * 4)) return rc2;
+        if (int rc2 = c->grow(B_H2C_WS, (size_t)ws.blocks * ws.threads * BLS28_H2C_NSLOTS * 3 * blsgpu::r28::NL * 4)) return rc2;
         hipLaunchKernelGGL(blsgpu::k_h2c_clear_pairs, dim3(ws.blocks), dim3(ws.threads), 0, st, c->tabs, img, (uint32_t)n,
-                           (uint32_t*)c->d_h2c_ws, (uint32_t*)d_out);
+                           c->at<uint32_t>(B_H2C_WS), (uint32_t*)d_out);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -2038,61 +1771,46 @@ BLSGPU_EXPORT int blsgpu_verify_pipeline(blsgpu_ctx* c, const uint8_t neg_g1[96]
     if (n > 0x03FFFFF0ull) return fail(-EINVAL, "batch too large");
     HIP_TRY(hipSetDevice(c->device));
     const bool sums = n && !keys_affine;
-    const size_t o_g1 = 0, o_g2 = (n + 1) * BLSGPU_G1_BYTES, o_h = o_g2 + (n + 1) * BLSGPU_G2_BYTES, o_kp = o_h + ((n * 32 + 63) & ~(size_t)63);
-    const size_t o_ks = o_kp + (sums ? n * k * BLSGPU_G1_BYTES : 0), o_out = o_ks + (sums ? n * k * 32 : 0);
+    // the two point arrays: slot 0 comes from the host; the rest is keys_affine, or written on the device
+    Staging s(c);
+    const int d1 = s.scratch((n + 1) * BLSGPU_G1_BYTES), d2 = s.scratch((n + 1) * BLSGPU_G2_BYTES), dh = s.in(msg_hashes, n * 32),
+              dkp = s.in(sums ? key_pts : nullptr, n * k * BLSGPU_G1_BYTES), dks = s.in(sums ? key_scalars : nullptr, n * k * 32), dout = s.out(out, 576);
+    if (int rc = s.alloc()) return rc;
     // the VM kernels round their team counts up: reserve as a call of n + 1 pairs does
-    if (int rc = grow_buffer(c, &c->d_io, &c->io_cap, o_out + 576 + 64)) return rc;
-    if (int rc = ensure_workspace(c, (n + 4) * MILLER_WAVES)) return rc;
-    char* d = (char*)c->d_io;
+    if (int rc = ensure_partials(c, 3 * (n + 4) + 1)) return rc;
     {
         StreamGuard sg(c, nullptr);
-        HIP_TRY(hipMemcpyAsync(d + o_g1, neg_g1, BLSGPU_G1_BYTES, hipMemcpyHostToDevice, nullptr));
-        HIP_TRY(hipMemcpyAsync(d + o_g2, sig, BLSGPU_G2_BYTES, hipMemcpyHostToDevice, nullptr));
-        if (n) {
-            HIP_TRY(hipMemcpyAsync(d + o_h, msg_hashes, n * 32, hipMemcpyHostToDevice, nullptr));
-            if (sums) {
-                HIP_TRY(hipMemcpyAsync(d + o_kp, key_pts, n * k * BLSGPU_G1_BYTES, hipMemcpyHostToDevice, nullptr));
-                HIP_TRY(hipMemcpyAsync(d + o_ks, key_scalars, n * k * 32, hipMemcpyHostToDevice, nullptr));
-            } else {
-                HIP_TRY(hipMemcpyAsync(d + o_g1 + BLSGPU_G1_BYTES, keys_affine, n * BLSGPU_G1_BYTES, hipMemcpyHostToDevice, nullptr));
-            }
-        }
+        HIP_TRY(hipMemcpyAsync(s.at(d1), neg_g1, BLSGPU_G1_BYTES, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(s.at(d2), sig, BLSGPU_G2_BYTES, hipMemcpyHostToDevice, nullptr));
+        if (int rc = s.up()) return rc;
+        if (n && !sums) HIP_TRY(hipMemcpyAsync(s.at(d1) + BLSGPU_G1_BYTES, keys_affine, n * BLSGPU_G1_BYTES, hipMemcpyHostToDevice, nullptr));
     }
-    if (int rc = blsgpu_verify_pipeline_dev(c, d + o_g1, d + o_g2, d + o_h, n, sums ? d + o_kp : nullptr, sums ? d + o_ks : nullptr,
-                                            sums ? k : 0, d + o_out, nullptr))
-        return rc;
-    HIP_TRY(hipMemcpy(out, d + o_out, 576, hipMemcpyDeviceToHost));
-    return 0;
+    if (int rc = blsgpu_verify_pipeline_dev(c, s.at(d1), s.at(d2), s.at(dh), n, s.opt(dkp), s.opt(dks), sums ? k : 0, s.at(dout), nullptr)) return rc;
+    return s.down();
 }
 
 BLSGPU_EXPORT int blsgpu_hash_to_g2(blsgpu_ctx* c, const uint8_t* msg_hashes, size_t n, uint8_t* out) {
     if (!c || (n && (!msg_hashes || !out))) return fail(-EINVAL, "NULL argument");
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
-    size_t need = n * (32 + 192) + 64;
-    if (int rc_ = grow_buffer(c, &c->d_io, &c->io_cap, need)) return rc_;
-    char* din = (char*)c->d_io;
-    char* dout = din + ((n * 32 + 63) & ~(size_t)63);
-    HIP_TRY(hipMemcpy(din, msg_hashes, n * 32, hipMemcpyHostToDevice));
-    int rc = map_to_g2_impl(c, din, n, dout, nullptr, true);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out, dout, n * 192, hipMemcpyDeviceToHost));
-    return 0;
+    Staging s(c);
+    const int din = s.in(msg_hashes, n * 32), dout = s.out(out, n * 192);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    if (int rc = map_to_g2_impl(c, s.at(din), n, s.at(dout), nullptr, true)) return rc;
+    return s.down();
 }
 
 BLSGPU_EXPORT int blsgpu_map_to_g2(blsgpu_ctx* c, const uint8_t* t, size_t n, uint8_t* out) {
     if (!c || (n && (!t || !out))) return fail(-EINVAL, "NULL argument");
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
-    size_t need = n * 192 * 2 + 64;
-    if (int rc_ = grow_buffer(c, &c->d_io, &c->io_cap, need)) return rc_;
-    char* din = (char*)c->d_io;
-    char* dout = din + n * 192;
-    HIP_TRY(hipMemcpy(din, t, n * 192, hipMemcpyHostToDevice));
-    int rc = blsgpu_map_to_g2_dev(c, din, n, dout, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out, dout, n * 192, hipMemcpyDeviceToHost));
-    return 0;
+    Staging s(c);
+    const int din = s.in(t, n * 192), dout = s.out(out, n * 192);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    if (int rc = blsgpu_map_to_g2_dev(c, s.at(din), n, s.at(dout), nullptr)) return rc;
+    return s.down();
 }
 
 // ------------------------------------------------------------ decompression --
@@ -2121,22 +1839,18 @@ BLSGPU_EXPORT int blsgpu_g1_mul_gen(blsgpu_ctx* c, const uint8_t* scalars, size_
     if (!scalars || (!out_aff && !out_ser)) return fail(-EINVAL, "NULL argument");
     if (int rc = check_n_add(n, n_add, add)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE, per = n_add == n && n_add > 1;
-    const size_t o_add = S * 32, o_aff = o_add + (per ? S : 1) * 96, o_ser = o_aff + (out_aff ? S * 96 : 0);
-    if (int rc = grow_buffer(c, &c->d_io, &c->io_cap, o_ser + (out_ser ? S * 48 : 0) + 64)) return rc;
-    char* d = (char*)c->d_io;
-    if (n_add == 1) HIP_TRY(hipMemcpyAsync(d + o_add, add, 96, hipMemcpyHostToDevice, 0));
-    for (size_t lo = 0; lo < n; lo += S) {
-        const size_t m = n - lo < S ? n - lo : S;
-        HIP_TRY(hipMemcpyAsync(d, scalars + lo * 32, m * 32, hipMemcpyHostToDevice, 0));
-        if (per) HIP_TRY(hipMemcpyAsync(d + o_add, add + lo * 96, m * 96, hipMemcpyHostToDevice, 0));
-        if (int rc = g1_mul_gen_dev(c, d, m, n_add ? d + o_add : nullptr, per ? m : n_add, out_aff ? d + o_aff : nullptr,
-                                    out_ser ? d + o_ser : nullptr, nullptr))
-            return rc;
-        if (out_aff) HIP_TRY(hipMemcpy(out_aff + lo * 96, d + o_aff, m * 96, hipMemcpyDeviceToHost));
-        if (out_ser) HIP_TRY(hipMemcpy(out_ser + lo * 48, d + o_ser, m * 48, hipMemcpyDeviceToHost));
-    }
-    return 0;
+    const size_t S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE;
+    const bool per = n_add == n && n_add > 1;
+    Staging s(c);
+    const int dsc = s.in(scalars, S, 32), dadd = per ? s.in(add, S, 96) : s.in(n_add ? add : nullptr, 96), daff = s.out(out_aff, S, 96),
+              dser = s.out(out_ser, S, 48);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    return for_slices(n, S, [&](size_t lo, size_t m) {
+        if (int rc = s.up(lo, m)) return rc;
+        if (int rc = g1_mul_gen_dev(c, s.at(dsc), m, s.opt(dadd), per ? m : n_add, s.opt(daff), s.opt(dser), nullptr)) return rc;
+        return s.down(lo, m);
+    });
 }
 BLSGPU_EXPORT int blsgpu_g1_mul_gen_dev(blsgpu_ctx* c, const void* d_scalars, size_t n, const void* d_add, size_t n_add, void* d_out_aff,
                                         void* d_out_ser, void* stream) {
@@ -2157,21 +1871,16 @@ BLSGPU_EXPORT int blsgpu_hd_children(blsgpu_ctx* c, const uint8_t chain_code[32]
             if (indices[i] >> 31) return fail(-EINVAL, "Cannot derive hardened children from public key");
     HIP_TRY(hipSetDevice(c->device));
     const size_t S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE;
-    const size_t o_chain = S * 4, o_sk = o_chain + S * 32, o_aff = o_sk + (parent_sk ? S * 32 : 0), o_ser = o_aff + (out_pk_aff ? S * 96 : 0);
-    if (int rc = grow_buffer(c, &c->d_io, &c->io_cap, o_ser + (out_pk_ser ? S * 48 : 0) + 64)) return rc;
-    char* d = (char*)c->d_io;
-    for (size_t lo = 0; lo < n; lo += S) {
-        const size_t m = n - lo < S ? n - lo : S;
-        HIP_TRY(hipMemcpyAsync(d, indices + lo, m * 4, hipMemcpyHostToDevice, 0));
-        if (int rc = hd_children_dev(c, chain_code, parent_pk_aff, parent_sk, d, m, d + o_chain, parent_sk ? d + o_sk : nullptr,
-                                     out_pk_aff ? d + o_aff : nullptr, out_pk_ser ? d + o_ser : nullptr, false, nullptr))
-            return rc;
-        HIP_TRY(hipMemcpy(out_chain + lo * 32, d + o_chain, m * 32, hipMemcpyDeviceToHost));
-        if (parent_sk) HIP_TRY(hipMemcpy(out_sk + lo * 32, d + o_sk, m * 32, hipMemcpyDeviceToHost));
-        if (out_pk_aff) HIP_TRY(hipMemcpy(out_pk_aff + lo * 96, d + o_aff, m * 96, hipMemcpyDeviceToHost));
-        if (out_pk_ser) HIP_TRY(hipMemcpy(out_pk_ser + lo * 48, d + o_ser, m * 48, hipMemcpyDeviceToHost));
-    }
-    return 0;
+    Staging s(c);
+    const int didx = s.in(indices, S, 4), dchain = s.out(out_chain, S, 32), dsk = s.out(parent_sk ? out_sk : nullptr, S, 32),
+              daff = s.out(out_pk_aff, S, 96), dser = s.out(out_pk_ser, S, 48);
+    if (int rc = s.alloc()) return rc;
+    return for_slices(n, S, [&](size_t lo, size_t m) {
+        if (int rc = s.up(lo, m)) return rc;
+        if (int rc = hd_children_dev(c, chain_code, parent_pk_aff, parent_sk, s.at(didx), m, s.at(dchain), s.opt(dsk), s.opt(daff), s.opt(dser),
+                                     false, nullptr)) return rc;
+        return s.down(lo, m);
+    });
 }
 BLSGPU_EXPORT int blsgpu_hd_children_dev(blsgpu_ctx* c, const uint8_t chain_code[32], const uint8_t parent_pk_aff[96], const uint8_t* parent_sk,
                                          const void* d_indices, size_t n, void* d_out_chain, void* d_out_sk, void* d_out_pk_aff,
@@ -2193,31 +1902,24 @@ BLSGPU_EXPORT int blsgpu_g1_poly_check(blsgpu_ctx* c, const uint8_t* commit, siz
         if (poly[i] >= n_polys) return fail(-EINVAL, "polynomial index out of range");
     HIP_TRY(hipSetDevice(c->device));
     const size_t S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE;
-    const size_t o_poly = (n_polys * t * 96 + 255) / 256 * 256, o_x = o_poly + S * 4, o_s = o_x + S * 32, o_st = o_s + (s ? S * 32 : 0);
-    const size_t o_aff = o_st + (status ? (S + 255) / 256 * 256 : 0);
-    if (int rc = grow_buffer(c, &c->d_io, &c->io_cap, o_aff + (out_aff ? S * 96 : 0) + 64)) return rc;
-    char* d = (char*)c->d_io;
-    HIP_TRY(hipMemcpyAsync(d, commit, n_polys * t * 96, hipMemcpyHostToDevice, 0));
+    Staging st(c);
+    const int dcommit = st.in(commit, n_polys * t * 96), dpoly = st.in(poly, S, 4), dx = st.in(x, S, 32), ds = st.in(s, S, 32),
+              dstatus = st.out(status, S, 1), daff = st.out(out_aff, S, 96);
+    if (int rc = st.alloc()) return rc;
+    if (int rc = st.up()) return rc;
     {
         StreamGuard sg(c, nullptr);
         if (int rc = poly_ws(c, n_polys, t)) return rc;
-        if (int rc = poly_prep(c, d, n_polys, t, status != nullptr, nullptr)) return rc;
+        if (int rc = poly_prep(c, st.at(dcommit), n_polys, t, status != nullptr, nullptr)) return rc;
     }
-    for (size_t lo = 0; lo < n; lo += S) {
-        const size_t m = n - lo < S ? n - lo : S;
-        HIP_TRY(hipMemcpyAsync(d + o_poly, poly + lo, m * 4, hipMemcpyHostToDevice, 0));
-        HIP_TRY(hipMemcpyAsync(d + o_x, x + lo * 32, m * 32, hipMemcpyHostToDevice, 0));
-        if (s) HIP_TRY(hipMemcpyAsync(d + o_s, s + lo * 32, m * 32, hipMemcpyHostToDevice, 0));
+    return for_slices(n, S, [&](size_t lo, size_t m) {
+        if (int rc = st.up(lo, m)) return rc;
         {
             StreamGuard sg(c, nullptr);
-            if (int rc = poly_eval_launch(c, n_polys, t, d + o_poly, d + o_x, s ? d + o_s : nullptr, m, status ? d + o_st : nullptr,
-                                          out_aff ? d + o_aff : nullptr, nullptr))
-                return rc;
+            if (int rc = poly_eval_launch(c, n_polys, t, st.at(dpoly), st.at(dx), st.opt(ds), m, st.opt(dstatus), st.opt(daff), nullptr)) return rc;
         }
-        if (status) HIP_TRY(hipMemcpy(status + lo, d + o_st, m, hipMemcpyDeviceToHost));
-        if (out_aff) HIP_TRY(hipMemcpy(out_aff + lo * 96, d + o_aff, m * 96, hipMemcpyDeviceToHost));
-    }
-    return 0;
+        return st.down(lo, m);
+    });
 }
 BLSGPU_EXPORT int blsgpu_g1_poly_check_dev(blsgpu_ctx* c, const void* d_commit, size_t n_polys, size_t t, const void* d_poly, const void* d_x,
                                            const void* d_s, size_t n, void* d_status, void* d_out_aff, void* stream) {

@@ -1,0 +1,297 @@
+// blsgpu_ctx.h -- the context behind the C ABI of include/blsgpu.h: every workspace buffer and every tuning knob of the
+// library, and the helpers the host side (blsgpu_api.hip) shares -- error reporting, kernel timing, stream ordering, launch
+// shapes and the staging of the host-buffer entry points.  Included by blsgpu_api.hip in the host translation unit only.
+#pragma once
+
+namespace {
+
+thread_local std::string g_err;
+
+int fail(int code, const std::string& msg) {
+    g_err = msg;
+    return code;
+}
+#define HIP_TRY(expr)                                                                         \
+    do {                                                                                      \
+        hipError_t _e = (expr);                                                               \
+        if (_e != hipSuccess)                                                                 \
+            return fail(-EIO, std::string(#expr) + ": " + hipGetErrorString(_e));             \
+    } while (0)
+
+// A workspace buffer: device memory that only ever GROWS.  The buffer a larger one replaces goes to `retired` and is kept
+// until the context is destroyed (or trimmed by blsgpu_ctx_trim on an idle context), so work already enqueued on it stays
+// valid and no hipFree -- a device-wide synchronisation -- happens inside a pipeline.
+struct Buf {
+    void* p = nullptr;
+    size_t cap = 0;                                          // bytes
+    template <class T> T* as() const { return (T*)p; }
+    // at least `bytes`; contents are scratch, not copied
+    int grow(std::vector<void*>& retired, size_t bytes) {
+        if (bytes <= cap) return 0;
+        size_t want = bytes + bytes / 4;                     // headroom: fewer regrowths
+        void* n = nullptr;
+        if (hipMalloc(&n, want) != hipSuccess) {
+            (void)hipGetLastError();                         // the failed attempt must not show up in a later launch check
+            want = bytes;
+            HIP_TRY(hipMalloc(&n, want));
+        }
+        if (p) retired.push_back(p);
+        p = n;
+        cap = want;
+        return 0;
+    }
+};
+
+// The buffers of a context (blsgpu_ctx::buf) and the field of blsgpu_ctx_workspace_bytes each one counts under.
+enum BufId {
+    B_PART0, B_PART1,    // partials: 144 x u32 (BLSGPU_FQ12_BYTES) each, ping-pong over the levels of the reduce chain
+    B_IO,                // staging for the host-buffer entry points (Staging)
+    B_LINES,             // 68 x pairs line records
+    B_LSP0, B_LSP1,      // dense partial products (ping-pong over the merge levels)
+    B_BAD,               // one byte per pair: left to the slow program
+    B_DEGEN,             // u32 [0] count, [1 ..] block indices of degenerate pairs (k_miller_slow's work list)
+    B_EXFLAGS,           // blsgpu_miller_loop_batch's fast form: the caller's flags with "py = 0" marked (2 bytes per pair)
+    B_MSM_PART,          // MSM partials; the stage images of decompression and hash to G2
+    B_BUCKETS,           // the bucket sums' buckets (HBM); the workspace of the sorted, plain and small-group sums
+    B_FEXP_WS,           // the slots of k_fexp_team
+    B_H2C_WS,            // the lane-private point slots of k_h2c_clear_pairs
+    B_FIX_WS,            // blsgpu_hd_children*: the parent key, a flag word and one slice of HMAC outputs
+    B_POLY_WS,           // blsgpu_g1_poly_check*: a flag word, the subgroup flags and the commitments in L28 form
+    B_COUNT
+};
+// (unit: what the buffer is counted in -- whole partials, whole u32 entries, bytes)
+struct BufInfo { int ws_field; size_t unit; };
+constexpr BufInfo BUF_INFO[B_COUNT] = {
+    {BLSGPU_WS_PARTIALS, BLSGPU_FQ12_BYTES}, {BLSGPU_WS_PARTIALS, BLSGPU_FQ12_BYTES}, {BLSGPU_WS_STAGING, 1}, {BLSGPU_WS_LINES, 1},
+    {BLSGPU_WS_LINE_PRODUCTS, 1}, {BLSGPU_WS_LINE_PRODUCTS, 1}, {BLSGPU_WS_FLAGS_AND_LISTS, 1}, {BLSGPU_WS_FLAGS_AND_LISTS, 4},
+    {BLSGPU_WS_FLAGS_AND_LISTS, 1}, {BLSGPU_WS_GROUP_SUMS, 4}, {BLSGPU_WS_GROUP_SUMS, 4}, {BLSGPU_WS_SLOTS, 1}, {BLSGPU_WS_SLOTS, 1},
+    {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}};             // no field of their own: they count in the total only
+
+}  // namespace
+
+struct blsgpu_ctx {
+    int device = 0;
+    blsgpu::VmTables tabs{};
+    void* d_tables = nullptr;          // one allocation holding every table
+    uint32_t* d_out = nullptr;         // 576-byte result staging
+    uint32_t* d_fix_table = nullptr;   // the fixed-base G1 table (blsgpu_g1fix.hip), built on first use; freed by blsgpu_ctx_destroy only
+    Buf buf[B_COUNT];
+    std::vector<void*> retired;        // Buf::grow
+    int grow(BufId id, size_t bytes) { return buf[id].grow(retired, bytes); }
+    template <class T> T* at(BufId id) const { return buf[id].as<T>(); }
+    uint32_t* part(int i) const { return buf[B_PART0 + i].as<uint32_t>(); }
+    int32_t* lsp(int i) const { return buf[B_LSP0 + i].as<int32_t>(); }
+    // capacity of each partial buffer, in partials, and of the work list, in entries
+    size_t part_cap() const { return (buf[B_PART0].cap < buf[B_PART1].cap ? buf[B_PART0].cap : buf[B_PART1].cap) / BLSGPU_FQ12_BYTES; }
+    size_t degen_cap() const { return buf[B_DEGEN].cap / sizeof(uint32_t); }
+
+    // ---- tuning knobs: the defaults are the measured ones; KNOBS below names the environment variable of each, read once
+    // by blsgpu_ctx_create
+    size_t miller_wide3_max = 256;     // ... with the accumulator split over two wavefronts (three per pair) up to this many pairs: three SIMDs per pair are free
+    size_t miller_wide_max = 1536;     // calls of at most this many pairs run the wide Miller loop (blsgpu_mlw.hip: one pair per two-wavefront workgroup, a product per lane); 0: never
+    size_t mp_threshold = 4096;        // pairs from which k_miller_mp is used
+    size_t mp3_threshold = (size_t)-1; // ... with three pairs per wavefront from here on, two below; -1: the measured schedule
+    size_t pip_threshold = 4096;       // points from which a single sum uses the bucket method
+    size_t pip_group_threshold = 48;   // points per sum from which a batch of sums does
+    size_t pow2_max = 32768;           // fixed-exponent powers (hash to G2, decompression): up to this many values per launch two wavefronts per 64 values (k_pow2: 0.32 ms against 0.47); 0: never
+    bool msm_wide_tail = true;         // the sorted-bucket G1 sum: window sums and the Horner over the windows on the wide machine (k_msm_horner_wide: 0.9 ms against the wavefront VM's 1.45); false: k_srt_windows + k_msm_pip_horner<1>
+    size_t h2c_wide_max = 2048;        // up to this many messages the cofactor clearing runs one message per WAVEFRONT with a product per lane (blsgpu_h2cw.hip: the latency form); 0: never
+    size_t h2c_reg_threshold = 8192;   // messages from which cofactor clearing runs in registers (one message per lane PAIR; measured: DESIGN.md 2c)
+    size_t h2c_lane_threshold = 2048;  // messages from which the three encoding stages run one encoding per lane (k_h2c_sw0/1/2)
+    bool h2c_jacobi = true;            // ... with the quadratic characters decided by a Jacobi-symbol routine: two powers per encoding, not five
+    size_t h2c_jacobi_threshold = 16384;   // ... from this many messages (below, five parallel powers finish sooner than three serial symbol loops)
+    size_t h2c_quad_max = 16384;       // ... on lane QUADS up to this many messages (k_h2c_clear_quads: half the depth while the chip is not full)
+    bool test_ls_nomem = false;        // test hook (BLSGPU_TEST_LS_NOMEM=1): the line-stream workspace "cannot be allocated"
+    size_t msm_sort_threshold = 1;      // points from which one G1 sum with scalars uses sorted buckets (k_srt_*): since the tail runs on the wide machine (round 5) they win at every size -- 1 point 1.24 ms against 1.63, 8192 points 1.45 against 2.59 (profiles/r05_c5_window_bits.txt)
+    size_t msm_sort2_threshold = 1;     // the same for ONE G2 sum with scalars (round 5: BLS.aggregate_sigs(secure) as a multi-scalar sum)
+    size_t msm_plain_threshold = 2;     // points from which ONE plain sum (no scalars) runs on the register kernels (k_sum_chunks + folds; round 5) instead of the wavefront VM's k_msm
+    size_t smul_min_groups = 4096;      // sums per call from which a batch of SMALL sums with scalars (scalar multiplications: groups x 1 point) runs one group per lane / lane pair (k_smul, round 5) instead of the wavefront VM's k_msm
+    size_t smul_max_k = 8;              // ... for sums of up to this many points
+    static uint32_t msm_sort2_bits(size_t n) { return n >= 16384 ? 13 : (n >= 512 ? 11 : 9); }   // window bits of the G2 path by size (tools/g2_single_sum_probe.py, profiles/r05_g2_single_sum.txt)
+    size_t horner_np_threshold = 1024; // G2 sums per call from which the window Horner runs several sums per team
+    size_t horner_quads_threshold = 2; // G2 sums per call (lane-pair bucket kernel) from which the window Horner runs one sum per lane quad
+    size_t wg256_max_waves = 4096;     // register kernels: launches of up to this many wavefronts go out as 256-thread workgroups (blsgpu_tu.h)
+    size_t msm_lane_threshold = 65536; // points from which the bucket sums run one (group, chunk, window) per lane
+    bool msm_lane_pairs = true;        // G2: every (group, chunk, window) on a lane PAIR (k_msm_lane2x) instead of one lane
+    size_t sort_bits = 0;              // window bits of the sorted-bucket G1 sum (BLSGPU_MSM_SORT_BITS); 0: the measured schedule (msm_sorted)
+    size_t sort2_bits = 0;             // ... of the G2 sum (BLSGPU_MSM_SORT2_BITS); 0: msm_sort2_bits(n)
+    size_t pip_chunks = 0;             // chunks one large bucket-method sum is cut into (BLSGPU_PIP_CHUNKS); 0: 256, or 3072 on the lane path
+    // line-stream multi-pairing (blsgpu_ml.hip): used from ls_threshold pairs per call when every group has at least
+    // ls_min_group pairs
+    size_t ls_threshold = 2304;        // measured crossover (tools/ls_wide_sweep.py, round 5 with the point chains sixteen lanes per pair): 2048 pairs 1.70 (VM) vs 1.70 ms, 3072 pairs 1.93 vs 1.79; 5120 in round 4, 16 384 in round 3
+    size_t ls_min_group = 64;
+    size_t ls_teams = 163840;          // accumulators k_ml_accum aims at (10 per wavefront: 8 wavefronts per place at two per SIMD)
+    bool vm_exact_lanes = true;        // degenerate blocks of the VM kernels through the lane kernels (k_ml_lines_exact / k_ml_small) instead of k_miller_slow
+    bool miller_exact_lanes = true;    // blsgpu_miller_loop_batch (one exact Fq12 per pair) on the lane kernels (k_ml_lines_exact + k_ml_small, round 5) instead of the VM's k_miller_exact
+    bool miller_exact_fast = true;     // ... from the FAST lines: the line-stream kernels + one Fq2 factor per pair (k_ml_exact_fixup) instead of the reference's 73 affine slopes per pair; false: k_ml_lines_exact for every pair
+    size_t ls_merge_wide_max = 16384;  // merge levels with at most this many outputs run one wavefront per output
+    size_t ls_wide_max = 5120;         // calls of at most this many pairs run the point chains sixteen lanes per pair with the values in LDS (k_ml_lines_wide, blsgpu_lsw.hip); 0: never
+    size_t ls_quad_max = 20480;        // calls of at most this many pairs run the point chains on lane QUADS (k_ml_lines4: 0.6 of the depth while lane pairs leave SIMDs empty)
+    size_t fexp_team_threshold = 5120; // results per call from which the final exponentiations run six lanes each (blsgpu_fexp.hip); below: one result per wavefront (measured crossover, tools/fexp_latency.py)
+    bool fexp_wide = true;             // fewer results than that: one result per wavefront, a product per lane (blsgpu_fexpw.hip); false: the VM program
+    size_t fexp_wide_max_partials = 8; // ... which also multiplies up to this many partials per result itself (a dense product is ~2.5 us)
+
+    void* d_fexp_dbg = nullptr;        // tools/fexp_trace.py: the accumulator of result 0 after every operation of the script (k_fexp_team)
+    void* d_fexpw_stamps = nullptr;    // tools/fexpw_stamps.py: cycle counter of result 0 around every operation of the script (k_fexp_wide)
+    hipEvent_t bulk_event = nullptr;   // caller's event, recorded after the last chip-filling kernel of a Miller stage
+    // optional per-kernel timing (blsgpu_timing_enable): HIP events recorded on
+    // the launch stream around every kernel, ring of TIMING_SLOTS launches
+    bool timing = false;
+    static constexpr int TIMING_SLOTS = 1024;
+    hipEvent_t* ev0 = nullptr;
+    hipEvent_t* ev1 = nullptr;
+    int* ev_kind = nullptr;            // 0 k_miller, 1 k_reduce, 2 k_reduce with final exponentiation
+    size_t ev_count = 0;
+    // The workspace is shared by everything a context launches: a call on another stream than
+    // the previous one first waits for that one's work (StreamGuard).
+    hipStream_t last_stream = nullptr;
+    hipEvent_t last_event = nullptr;
+    bool used = false;
+};
+
+namespace {
+
+// Every knob once: blsgpu_ctx_create sets the field from the variable when it is set -- sizes by strtoull (base 10),
+// switches by atoi != 0.
+struct Knob {
+    const char* env;
+    size_t blsgpu_ctx::* size;
+    bool blsgpu_ctx::* flag;
+    constexpr Knob(const char* e, size_t blsgpu_ctx::* s) : env(e), size(s), flag(nullptr) {}
+    constexpr Knob(const char* e, bool blsgpu_ctx::* f) : env(e), size(nullptr), flag(f) {}
+};
+const Knob KNOBS[] = {
+    {"BLSGPU_MP_THRESHOLD", &blsgpu_ctx::mp_threshold},
+    {"BLSGPU_MILLER_WIDE3_MAX", &blsgpu_ctx::miller_wide3_max},
+    {"BLSGPU_MILLER_WIDE_MAX", &blsgpu_ctx::miller_wide_max},
+    {"BLSGPU_MP3_THRESHOLD", &blsgpu_ctx::mp3_threshold},
+    {"BLSGPU_LS_THRESHOLD", &blsgpu_ctx::ls_threshold},
+    {"BLSGPU_LS_MIN_GROUP", &blsgpu_ctx::ls_min_group},
+    {"BLSGPU_LS_TEAMS", &blsgpu_ctx::ls_teams},
+    {"BLSGPU_FEXP_TEAM_THRESHOLD", &blsgpu_ctx::fexp_team_threshold},
+    {"BLSGPU_FEXP_WIDE", &blsgpu_ctx::fexp_wide},
+    {"BLSGPU_FEXP_WIDE_MAX_PARTIALS", &blsgpu_ctx::fexp_wide_max_partials},
+    {"BLSGPU_VM_EXACT_LANES", &blsgpu_ctx::vm_exact_lanes},
+    {"BLSGPU_LS_MERGE_WIDE_MAX", &blsgpu_ctx::ls_merge_wide_max},
+    {"BLSGPU_LS_WIDE_MAX", &blsgpu_ctx::ls_wide_max},
+    {"BLSGPU_LS_QUAD_MAX", &blsgpu_ctx::ls_quad_max},
+    {"BLSGPU_PIP_THRESHOLD", &blsgpu_ctx::pip_threshold},
+    {"BLSGPU_PIP_GROUP_THRESHOLD", &blsgpu_ctx::pip_group_threshold},
+    {"BLSGPU_PIP_CHUNKS", &blsgpu_ctx::pip_chunks},
+    {"BLSGPU_POW2_MAX", &blsgpu_ctx::pow2_max},
+    {"BLSGPU_MSM_WIDE_TAIL", &blsgpu_ctx::msm_wide_tail},
+    {"BLSGPU_H2C_WIDE_MAX", &blsgpu_ctx::h2c_wide_max},
+    {"BLSGPU_H2C_REG_THRESHOLD", &blsgpu_ctx::h2c_reg_threshold},
+    {"BLSGPU_H2C_QUAD_MAX", &blsgpu_ctx::h2c_quad_max},
+    {"BLSGPU_TEST_LS_NOMEM", &blsgpu_ctx::test_ls_nomem},
+    {"BLSGPU_H2C_JACOBI", &blsgpu_ctx::h2c_jacobi},
+    {"BLSGPU_H2C_JACOBI_THRESHOLD", &blsgpu_ctx::h2c_jacobi_threshold},
+    {"BLSGPU_H2C_LANE_THRESHOLD", &blsgpu_ctx::h2c_lane_threshold},
+    {"BLSGPU_MSM_SORT_THRESHOLD", &blsgpu_ctx::msm_sort_threshold},
+    {"BLSGPU_MSM_SORT2_THRESHOLD", &blsgpu_ctx::msm_sort2_threshold},
+    {"BLSGPU_MSM_SORT_BITS", &blsgpu_ctx::sort_bits},
+    {"BLSGPU_MSM_SORT2_BITS", &blsgpu_ctx::sort2_bits},
+    {"BLSGPU_MILLER_EXACT_LANES", &blsgpu_ctx::miller_exact_lanes},
+    {"BLSGPU_MILLER_EXACT_FAST", &blsgpu_ctx::miller_exact_fast},
+    {"BLSGPU_MSM_PLAIN_THRESHOLD", &blsgpu_ctx::msm_plain_threshold},
+    {"BLSGPU_SMUL_MIN_GROUPS", &blsgpu_ctx::smul_min_groups},
+    {"BLSGPU_SMUL_MAX_K", &blsgpu_ctx::smul_max_k},
+    {"BLSGPU_HORNER_NP_THRESHOLD", &blsgpu_ctx::horner_np_threshold},
+    {"BLSGPU_HORNER_QUADS_THRESHOLD", &blsgpu_ctx::horner_quads_threshold},
+    {"BLSGPU_WG256_MAX_WAVES", &blsgpu_ctx::wg256_max_waves},
+    {"BLSGPU_MSM_LANE_THRESHOLD", &blsgpu_ctx::msm_lane_threshold},
+    {"BLSGPU_MSM_LANE_PAIRS", &blsgpu_ctx::msm_lane_pairs},
+};
+void read_knobs(blsgpu_ctx* c) {
+    for (const Knob& k : KNOBS)
+        if (const char* e = getenv(k.env)) {
+            if (k.size) c->*k.size = (size_t)strtoull(e, nullptr, 10);
+            else c->*k.flag = atoi(e) != 0;
+        }
+}
+
+struct KernelTimer {
+    blsgpu_ctx* c; hipStream_t st; int slot;
+    KernelTimer(blsgpu_ctx* c_, hipStream_t st_, int kind) : c(c_), st(st_), slot(-1) {
+        if (c->timing && c->ev_count < (size_t)blsgpu_ctx::TIMING_SLOTS) {
+            slot = (int)c->ev_count++;
+            c->ev_kind[slot] = kind;
+            (void)hipEventRecord(c->ev0[slot], st);
+        }
+    }
+    ~KernelTimer() { if (slot >= 0) (void)hipEventRecord(c->ev1[slot], st); }
+};
+
+// Serialises the use of the context's workspace across streams (blsgpu_ctx::last_stream).
+struct StreamGuard {
+    blsgpu_ctx* c; hipStream_t st;
+    StreamGuard(blsgpu_ctx* c_, hipStream_t st_) : c(c_), st(st_) {
+        if (c->used && c->last_stream != st && c->last_event) (void)hipStreamWaitEvent(st, c->last_event, 0);
+    }
+    ~StreamGuard() {
+        if (c->last_event) (void)hipEventRecord(c->last_event, st);
+        c->last_stream = st;
+        c->used = true;
+    }
+};
+
+// Grid and workgroup size for `waves` independent wavefronts of a register kernel (blsgpu_tu.h: wave_index()): four
+// wavefronts per workgroup -- one per SIMD of a CU -- while the launch does not fill the chip several times over.
+struct WaveShape { unsigned blocks, threads; };
+WaveShape wave_shape(const blsgpu_ctx* c, size_t waves) {
+    const unsigned per = (waves <= c->wg256_max_waves) ? 4u : 1u;
+    return {(unsigned)((waves + per - 1) / per), per * 64u};
+}
+
+// The layout of B_IO for one host-buffer call: the entry point declares its regions once, in the order their copies are
+// issued; every region starts on a 256-byte boundary.  A WHOLE region is copied by up() / down(); a region of ITEMS holds
+// one slice and is copied by up(lo, m) / down(lo, m), items [lo, lo + m) of the host array.  Uploads are asynchronous on
+// the null stream, downloads synchronous: the host-buffer forms return with their results.
+struct Staging {
+    struct Region { size_t off, bytes, item; const char* src; char* dst; bool absent; };
+    blsgpu_ctx* c;
+    Region r[8];
+    int n = 0;
+    size_t total = 0;
+    explicit Staging(blsgpu_ctx* c_) : c(c_) {}
+    int add(bool absent, size_t bytes, size_t item, const void* src, void* dst) {
+        r[n] = {total, absent ? 0 : bytes, item, (const char*)src, (char*)dst, absent};
+        total += (r[n].bytes + 255) & ~(size_t)255;
+        return n++;
+    }
+    // an input that is not given (NULL) takes no room and is not copied: opt() of it is NULL
+    int in(const void* src, size_t bytes) { return add(!src, bytes, 0, src, nullptr); }
+    int in(const void* src, size_t items, size_t item) { return add(!src, items * item, item, src, nullptr); }
+    // likewise an output that is not asked for -- unless the device form writes it regardless (out_kept)
+    int out(void* dst, size_t bytes) { return add(!dst, bytes, 0, nullptr, dst); }
+    int out_kept(void* dst, size_t bytes) { return add(false, bytes, 0, nullptr, dst); }
+    int out(void* dst, size_t items, size_t item) { return add(!dst, items * item, item, nullptr, dst); }
+    int scratch(size_t bytes) { return add(false, bytes, 0, nullptr, nullptr); }
+    int alloc() { return c->grow(B_IO, total); }
+    char* at(int i) const { return c->at<char>(B_IO) + r[i].off; }
+    char* opt(int i) const { return r[i].absent ? nullptr : at(i); }
+    int up(size_t lo = 0, size_t m = 0) const {
+        for (int i = 0; i < n; i++) {
+            const size_t bytes = m ? m * r[i].item : (r[i].item ? 0 : r[i].bytes);
+            if (r[i].src && bytes) HIP_TRY(hipMemcpyAsync(at(i), r[i].src + lo * r[i].item, bytes, hipMemcpyHostToDevice, 0));
+        }
+        return 0;
+    }
+    int down(size_t lo = 0, size_t m = 0) const {
+        for (int i = 0; i < n; i++) {
+            const size_t bytes = m ? m * r[i].item : (r[i].item ? 0 : r[i].bytes);
+            if (r[i].dst && bytes) HIP_TRY(hipMemcpy(r[i].dst + lo * r[i].item, at(i), bytes, hipMemcpyDeviceToHost));
+        }
+        return 0;
+    }
+};
+
+// body(lo, m) over [0, n) in runs of at most `step` items
+template <class F>
+int for_slices(size_t n, size_t step, F body) {
+    for (size_t lo = 0; lo < n; lo += step)
+        if (int rc = body(lo, n - lo < step ? n - lo : step)) return rc;
+    return 0;
+}
+
+}  // namespace
