@@ -70,7 +70,8 @@ int blsgpu_ctx_reserve(blsgpu_ctx *ctx, size_t max_pairs);
  * calls made so far; the line-stream stage keeps 68 x 336 bytes of line records per pair of its largest call, the
  * counterpart of the n-arrays of mpz_t the reference mallocs per call, fields_t_c.pyx:2348-2388).  out[BLSGPU_WS_TOTAL]
  * is the sum (which also counts the fixed-base G1 table and the HD derivation slice, blsgpu_g1_mul_gen /
- * blsgpu_hd_children, and the commitments of blsgpu_g1_poly_check; they have no field of their own).
+ * blsgpu_hd_children, the commitments of blsgpu_g1_poly_check and the Lagrange coefficients of blsgpu_threshold_combine /
+ * blsgpu_fr_interpolate_at_zero; they have no field of their own).
  * BLSGPU_WS_FLAGS_AND_LISTS counts the flag copy of blsgpu_miller_loop_batch's fast form as well (2 bytes per pair of a
  * slice).  No device call is made. */
 enum { BLSGPU_WS_PARTIALS = 0, BLSGPU_WS_STAGING, BLSGPU_WS_LINES, BLSGPU_WS_LINE_PRODUCTS, BLSGPU_WS_FLAGS_AND_LISTS,
@@ -349,6 +350,41 @@ int blsgpu_g2_subgroup_check(blsgpu_ctx *ctx, const uint8_t *pts, size_t n, uint
 /* The same with both buffers in device memory, enqueued on `stream` (no synchronisation). */
 int blsgpu_g1_subgroup_check_dev(blsgpu_ctx *ctx, const void *d_pts, size_t n, void *d_status, void *stream);
 int blsgpu_g2_subgroup_check_dev(blsgpu_ctx *ctx, const void *d_pts, size_t n, void *d_status, void *stream);
+
+/* Threshold recovery for `groups` signer sets of k players at once (csrc/blsgpu_lagrange.hip on the scalar-field
+ * arithmetic of csrc/fr_scalar.h): one k per call, 1 <= k <= BLSGPU_LAGRANGE_MAX_K -- a group is one workgroup, one
+ * evaluation point per lane, so a larger k is refused with -EINVAL and left to the caller's host loop.
+ * x: groups x k evaluation points, 32 bytes big-endian each.
+ * Lagrange coefficients at zero (Threshold.lagrange_coeffs_at_zero, threshold.py:56-88 of the reference: the second
+ * barycentric form, w_j = prod_{i != j} (x_j - x_i), shift_j = w_j^-1 (-x_j)^-1, L_j = shift_j / sum_i shift_i):
+ * out_coeffs: groups x k x 32 bytes big-endian, the canonical integers below n the reference computes -- the layout the
+ * multi-scalar sums take as `scalars`.  status[g] = 1 if group g's coefficients were written; 0 if some x_j is 0 or not
+ * below n, or two of them are equal (where the reference asserts, threshold.py:66): its coefficients are all zero.
+ * groups == 0 writes nothing and returns 0; k == 0, k above the limit or a NULL buffer with groups > 0: -EINVAL before
+ * anything is written.  The points are public: the work does not depend on them except through the status. */
+#define BLSGPU_LAGRANGE_MAX_K 1024
+int blsgpu_lagrange_at_zero(blsgpu_ctx *ctx, const uint8_t *x, size_t k, size_t groups, uint8_t *out_coeffs,
+                            uint8_t *status);
+/* The same with every buffer in device memory, enqueued on `stream` (no synchronisation). */
+int blsgpu_lagrange_at_zero_dev(blsgpu_ctx *ctx, const void *d_x, size_t k, size_t groups, void *d_out_coeffs,
+                                void *d_status, void *stream);
+/* Threshold.interpolate_at_zero (threshold.py:91-101): out[g] = sum_j L_j y_j mod n, 32 bytes big-endian per group, with
+ * the coefficients of group g computed as above into the context's workspace; y: groups x k x 32 bytes big-endian, any
+ * value below 2^256 (reduced mod n on the device).  A group with status 0 yields 0.  The y_j are secrets (shares): the
+ * reductions branch on their values, NOT constant-time. */
+int blsgpu_fr_interpolate_at_zero(blsgpu_ctx *ctx, const uint8_t *x, const uint8_t *y, size_t k, size_t groups,
+                                  uint8_t *out, uint8_t *status);
+int blsgpu_fr_interpolate_at_zero_dev(blsgpu_ctx *ctx, const void *d_x, const void *d_y, size_t k, size_t groups,
+                                      void *d_out, void *d_status, void *stream);
+/* Threshold.aggregate_unit_sigs (threshold.py:127-136) per group: out[g] = sum_j L_j sigs[g*k+j], the coefficients
+ * computed into the workspace and handed to the G2 multi-scalar sum on the device -- the internal path of the G2 sum with
+ * device scalars, no host round trip.  sigs_affine: groups x k x 192 bytes as the G2 sums take them; out: groups x 192
+ * bytes; out_inf (may be NULL): 1 for the point at infinity.  A group with status 0 yields the all-zero point with
+ * out_inf = 1. */
+int blsgpu_threshold_combine(blsgpu_ctx *ctx, const uint8_t *sigs_affine, const uint8_t *x, size_t k, size_t groups,
+                             uint8_t *out, uint8_t *out_inf, uint8_t *status);
+int blsgpu_threshold_combine_dev(blsgpu_ctx *ctx, const void *d_sigs_affine, const void *d_x, size_t k, size_t groups,
+                                 void *d_out, void *d_out_inf, void *d_status, void *stream);
 
 /* Measurement aid (bench.py): when enabled, HIP events are recorded on the
  * launch stream around every kernel this context launches (up to 1024 launches

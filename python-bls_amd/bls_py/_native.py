@@ -28,7 +28,11 @@ SYMBOLS = (
     "blsgpu_g1_mul_gen", "blsgpu_g1_mul_gen_dev", "blsgpu_hd_children", "blsgpu_hd_children_dev",
     "blsgpu_g1_poly_check", "blsgpu_g1_poly_check_dev",
     "blsgpu_g1_subgroup_check", "blsgpu_g1_subgroup_check_dev", "blsgpu_g2_subgroup_check", "blsgpu_g2_subgroup_check_dev",
+    "blsgpu_lagrange_at_zero", "blsgpu_lagrange_at_zero_dev", "blsgpu_fr_interpolate_at_zero", "blsgpu_fr_interpolate_at_zero_dev",
+    "blsgpu_threshold_combine", "blsgpu_threshold_combine_dev",
 )
+
+LAGRANGE_MAX_K = 1024          # BLSGPU_LAGRANGE_MAX_K of include/blsgpu.h: players per group the device takes
 
 _lib = None
 _lock = threading.Lock()
@@ -117,6 +121,12 @@ def load_library(path=None):
         for g in ("g1", "g2"):
             getattr(L, "blsgpu_%s_subgroup_check" % g).argtypes = [vp, cp, sz, vp]
             getattr(L, "blsgpu_%s_subgroup_check_dev" % g).argtypes = [vp, vp, sz, vp, vp]
+        L.blsgpu_lagrange_at_zero.argtypes = [vp, cp, sz, sz, vp, vp]
+        L.blsgpu_lagrange_at_zero_dev.argtypes = [vp, vp, sz, sz, vp, vp, vp]
+        L.blsgpu_fr_interpolate_at_zero.argtypes = [vp, cp, cp, sz, sz, vp, vp]
+        L.blsgpu_fr_interpolate_at_zero_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
+        L.blsgpu_threshold_combine.argtypes = [vp, cp, cp, sz, sz, vp, vp, vp]
+        L.blsgpu_threshold_combine_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
         L.blsgpu_timing_enable.argtypes = [vp, ctypes.c_int]
         L.blsgpu_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int), sz,
                                          ctypes.POINTER(sz)]
@@ -439,6 +449,58 @@ class Engine:
 
     def g2_subgroup_dev(self, d_pts, n, d_status, stream=0):
         self._check(self.lib.blsgpu_g2_subgroup_check_dev(self.h, d_pts, n, d_status, stream), "blsgpu_g2_subgroup_check_dev")
+
+    @staticmethod
+    def _scalars(v, n, what):
+        """n x 32 bytes big-endian from bytes or from ints below 2^256"""
+        b = bytes(v) if isinstance(v, (bytes, bytearray)) else b"".join(int(a).to_bytes(32, "big") for a in v)
+        if len(b) != 32 * n:
+            raise ValueError("%s must hold k * groups values of 32 bytes" % what)
+        return b
+
+    def lagrange_at_zero(self, x, k, groups=1):
+        """Lagrange coefficients at zero of `groups` groups of k evaluation points (blsgpu_lagrange_at_zero): x
+        groups x k x 32 bytes big-endian (or ints below 2^256), 1 <= k <= LAGRANGE_MAX_K.
+        -> (groups x k x 32 coefficient bytes, groups status bytes: 1 written, 0 where the reference asserts -- zeros)"""
+        n = k * groups
+        co = ctypes.create_string_buffer(max(1, 32 * n))
+        st = ctypes.create_string_buffer(max(1, groups))
+        self._check(self.lib.blsgpu_lagrange_at_zero(self.h, self._scalars(x, n, "x"), k, groups, co, st), "blsgpu_lagrange_at_zero")
+        return co.raw[:32 * n], st.raw[:groups]
+
+    def fr_interpolate_at_zero(self, x, y, k, groups=1):
+        """sum_j L_j y_j mod n per group (blsgpu_fr_interpolate_at_zero): x, y groups x k x 32 bytes big-endian (or ints
+        below 2^256).  -> (groups x 32 bytes, groups status bytes)"""
+        n = k * groups
+        out = ctypes.create_string_buffer(max(1, 32 * groups))
+        st = ctypes.create_string_buffer(max(1, groups))
+        self._check(self.lib.blsgpu_fr_interpolate_at_zero(self.h, self._scalars(x, n, "x"), self._scalars(y, n, "y"), k, groups, out, st),
+                    "blsgpu_fr_interpolate_at_zero")
+        return out.raw[:32 * groups], st.raw[:groups]
+
+    def threshold_combine(self, sigs, x, k, groups=1):
+        """sum_j L_j sig_j per group (blsgpu_threshold_combine): sigs groups x k x 192 affine bytes, x as above.
+        -> (groups x 192 affine bytes, [is_infinity], groups status bytes)"""
+        n = k * groups
+        if len(sigs) != 192 * n:
+            raise ValueError("signature buffer length does not match k * groups")
+        out = ctypes.create_string_buffer(max(1, 192 * groups))
+        inf = ctypes.create_string_buffer(max(1, groups))
+        st = ctypes.create_string_buffer(max(1, groups))
+        self._check(self.lib.blsgpu_threshold_combine(self.h, bytes(sigs), self._scalars(x, n, "x"), k, groups, out, inf, st),
+                    "blsgpu_threshold_combine")
+        return out.raw[:192 * groups], [bool(b) for b in inf.raw[:groups]], st.raw[:groups]
+
+    def lagrange_at_zero_dev(self, d_x, k, groups, d_out_coeffs, d_status, stream=0):
+        self._check(self.lib.blsgpu_lagrange_at_zero_dev(self.h, d_x, k, groups, d_out_coeffs, d_status, stream), "blsgpu_lagrange_at_zero_dev")
+
+    def fr_interpolate_at_zero_dev(self, d_x, d_y, k, groups, d_out, d_status, stream=0):
+        self._check(self.lib.blsgpu_fr_interpolate_at_zero_dev(self.h, d_x, d_y, k, groups, d_out, d_status, stream),
+                    "blsgpu_fr_interpolate_at_zero_dev")
+
+    def threshold_combine_dev(self, d_sigs, d_x, k, groups, d_out, d_out_inf, d_status, stream=0):
+        self._check(self.lib.blsgpu_threshold_combine_dev(self.h, d_sigs, d_x, k, groups, d_out, d_out_inf, d_status, stream),
+                    "blsgpu_threshold_combine_dev")
 
     def timing_enable(self, on=True):
         self._check(self.lib.blsgpu_timing_enable(self.h, int(on)), "blsgpu_timing_enable")

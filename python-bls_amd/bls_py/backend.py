@@ -67,6 +67,24 @@ class HipProvider:
         """n x 192 affine bytes -> n status bytes: 1 in G2 (infinity included), 2 on the twist outside G2, 0 off the twist"""
         return self._eng.g2_subgroup(pts)
 
+    # ---- threshold recovery for many signer sets at once (threshold.py:56-136): k <= LAGRANGE_MAX_K players per group ----
+    @property
+    def LAGRANGE_MAX_K(self):
+        from . import _native
+        return _native.LAGRANGE_MAX_K
+
+    def lagrange_at_zero(self, x, k: int, groups: int = 1):
+        """-> (groups x k x 32 coefficient bytes, groups status bytes: 1 written, 0 where the reference asserts)"""
+        return self._eng.lagrange_at_zero(x, k, groups)
+
+    def fr_interpolate_at_zero(self, x, y, k: int, groups: int = 1):
+        """-> (groups x 32 bytes: sum_j L_j y_j mod n, groups status bytes)"""
+        return self._eng.fr_interpolate_at_zero(x, y, k, groups)
+
+    def threshold_combine(self, sigs: bytes, x, k: int, groups: int = 1):
+        """-> (groups x 192 affine bytes: sum_j L_j sig_j, [is_infinity], groups status bytes)"""
+        return self._eng.threshold_combine(sigs, x, k, groups)
+
     # ---- the whole of BLS.verify's device work without a host round trip between its steps (bls.py:153-201) ----
     def verify_pipeline(self, neg_g1: bytes, sig: bytes, hashes: bytes, n: int, keys_affine=None, key_pts=None, key_scalars=None, k=0) -> bytes:
         """e(-G1, sig) * prod_i e(P_i, H(m_i)) for n message hashes (32 bytes each): blsgpu_verify_pipeline -- ONE upload,
@@ -85,7 +103,10 @@ def use(provider):
     g1_mul_gen(scalars, add|None, n_add) -> (affine bytes, serialised bytes),
     hd_children(chain_code, parent_pk_aff, parent_sk|None, indices) -> (chain codes, child keys|None, affine, serialised),
     g1_poly_check(commit, n_polys, t, poly, x, s|None, aff) -> (status bytes|None, affine Horner values|None),
-    g1_subgroup / g2_subgroup(affine bytes) -> status bytes (1 in the subgroup, 2 on the curve outside it, 0 off it)."""
+    g1_subgroup / g2_subgroup(affine bytes) -> status bytes (1 in the subgroup, 2 on the curve outside it, 0 off it).
+    Optional (a provider without them sends the Threshold.*_batch methods to the host loop): LAGRANGE_MAX_K,
+    lagrange_at_zero(x, k, groups) -> (coefficient bytes, status bytes), fr_interpolate_at_zero(x, y, k, groups) ->
+    (32 bytes per group, status bytes), threshold_combine(sigs, x, k, groups) -> (affine bytes, [is_inf], status bytes)."""
     global _provider
     _provider = provider
 

@@ -225,6 +225,29 @@ class PrivateKey:
         lam = Threshold.lagrange_coeffs_at_zero(players)[players.index(player)]
         return Signature.from_g2(self.value * (r * lam))
 
+    @staticmethod
+    def sign_threshold_batch(private_keys, m, players):
+        """[sk.sign_threshold(m, p, players) for sk, p in zip(private_keys, players)]: the unit signatures of one session,
+        the share of players[i] being private_keys[i].  One Lagrange evaluation for the session
+        (Threshold.lagrange_coeffs_at_zero_batch: on the GPU), one hash to G2 and one grouped G2 sum of
+        (lambda_i sk_i mod n) H(m) -- where every signer's own sign_threshold pays a full host Lagrange evaluation."""
+        from . import backend
+        from .ec import hash_to_points_prehashed_Fq2
+        from .threshold import Threshold
+        from .util import hash256
+        sks, players = list(private_keys), list(players)
+        if len(sks) != len(players):
+            raise ValueError("one private key per player")
+        if not sks:
+            return []
+        lam = Threshold.lagrange_coeffs_at_zero_batch([players])[0]
+        r = H.g2_affine_bytes(hash_to_points_prehashed_Fq2([hash256(m)])[0]._aff())
+        scalars = [int(l) * sk.value % GROUP_ORDER for l, sk in zip(lam, sks)]
+        out, inf = backend.get().g2_msm(r * len(sks), scalars, 1, len(sks))
+        return [Signature.from_g2(JacobianPoint._from(
+            H.F2, None if inf[i] else H.aff_to_jac(H.F2, H.g2_from_abi(out[192 * i:192 * (i + 1)])), default_ec_twist))
+            for i in range(len(sks))]
+
     def serialize(self):
         return self.value.to_bytes(self.PRIVATE_KEY_SIZE, "big")
 

@@ -106,6 +106,98 @@ class Threshold:
         lam = Threshold.lagrange_coeffs_at_zero(players, ec)
         return Signature.from_g2(_g2_sum([sig.value for sig in signatures], [int(l) for l in lam]))
 
+    # ---- many signer sets at once: the coefficients on the GPU (blsgpu_lagrange_at_zero and its two consumers) ----
+    @staticmethod
+    def _device_buckets(Xs, ec, entry, also=None):
+        """The routing the three *_batch methods share.  The assertion of lagrange_coeffs_at_zero runs for every group
+        first, as a loop of single calls would raise it.  -> (provider, {k: [group indices]}): the groups the device takes,
+        one call per distinct k.  Every other group -- a player that is not an int or is negative (the assertion lets
+        negatives through), k = 0, k above the device limit, another curve, a provider without `entry`, or `also(i)`
+        false -- is left to the caller's host loop."""
+        n = ec.n
+        for X in Xs:
+            assert len(set(X)) == len(X) and all(0 != x < n for x in X)
+        if ec is not default_ec:
+            return None, {}
+        fit = [i for i, X in enumerate(Xs) if X and all(type(x) is int and x > 0 for x in X) and (also is None or also(i))]
+        if not fit:
+            return None, {}
+        from . import backend
+        prov = backend.get()
+        if not hasattr(prov, entry):
+            return None, {}
+        kmax = prov.LAGRANGE_MAX_K
+        buckets = {}
+        for i in fit:
+            if len(Xs[i]) <= kmax:
+                buckets.setdefault(len(Xs[i]), []).append(i)
+        return prov, buckets
+
+    @staticmethod
+    def lagrange_coeffs_at_zero_batch(Xs, ec=default_ec):
+        """[lagrange_coeffs_at_zero(X, ec) for X in Xs] with the coefficients of every group of positive int players
+        computed on the GPU, one call per distinct group length (routing: _device_buckets)."""
+        Xs = [list(X) for X in Xs]
+        prov, buckets = Threshold._device_buckets(Xs, ec, "lagrange_at_zero")
+        out = [None] * len(Xs)
+        for k, idx in buckets.items():
+            xb = b"".join(x.to_bytes(32, "big") for i in idx for x in Xs[i])
+            co, status = prov.lagrange_at_zero(xb, k, len(idx))
+            for q, i in enumerate(idx):
+                if status[q] == 1:
+                    out[i] = [Fq(ec.n, int.from_bytes(co[32 * (q * k + j):32 * (q * k + j + 1)], "big")) for j in range(k)]
+        return [Threshold.lagrange_coeffs_at_zero(X, ec) if r is None else r for X, r in zip(Xs, out)]
+
+    @staticmethod
+    def interpolate_at_zero_batch(Xs, Ys, ec=default_ec):
+        """[interpolate_at_zero(X, Y, ec) for X, Y in zip(Xs, Ys)]: coefficients and the sums sum_j L_j y_j on the GPU
+        (blsgpu_fr_interpolate_at_zero) for groups whose Y holds one Fq mod n or int per player."""
+        Xs, Ys = [list(X) for X in Xs], [list(Y) for Y in Ys]
+        m = min(len(Xs), len(Ys))
+        Xs, Ys = Xs[:m], Ys[:m]
+        n = ec.n
+
+        def values(i):
+            return len(Ys[i]) == len(Xs[i]) and all((type(y) is Fq and y.Q == n) or type(y) is int for y in Ys[i])
+        prov, buckets = Threshold._device_buckets(Xs, ec, "fr_interpolate_at_zero", values)
+        out = [None] * m
+        for k, idx in buckets.items():
+            xb = b"".join(x.to_bytes(32, "big") for i in idx for x in Xs[i])
+            yb = b"".join((int(y) % n).to_bytes(32, "big") for i in idx for y in Ys[i])
+            res, status = prov.fr_interpolate_at_zero(xb, yb, k, len(idx))
+            for q, i in enumerate(idx):
+                if status[q] == 1:
+                    out[i] = Fq(n, int.from_bytes(res[32 * q:32 * (q + 1)], "big"))
+        return [Threshold.interpolate_at_zero(X, Y, ec) if r is None else r for X, Y, r in zip(Xs, Ys, out)]
+
+    @staticmethod
+    def aggregate_unit_sigs_batch(signature_groups, player_groups, T, ec=default_ec):
+        """[aggregate_unit_sigs(s, p, T, ec) for s, p in zip(signature_groups, player_groups)] in one device call per
+        distinct group length (blsgpu_threshold_combine): the coefficients never leave the GPU.  A signature group
+        whose length differs from its player group's takes the host loop, as the groups of _device_buckets do.
+        T is unused, as in the reference."""
+        sigs, Xs = [list(s) for s in signature_groups], [list(p) for p in player_groups]
+        m = min(len(sigs), len(Xs))
+        sigs, Xs = sigs[:m], Xs[:m]
+        prov, buckets = Threshold._device_buckets(Xs, ec, "threshold_combine", lambda i: len(sigs[i]) == len(Xs[i]))
+        out = [None] * m
+        seen = {}                                   # a signature object listed in many groups is converted once
+
+        def affine(sig):
+            b = seen.get(id(sig))
+            if b is None:
+                b = seen[id(sig)] = H.g2_affine_bytes(sig.value.to_affine()._aff())
+            return b
+        for k, idx in buckets.items():
+            pts = b"".join(affine(sig) for i in idx for sig in sigs[i])
+            xb = b"".join(x.to_bytes(32, "big") for i in idx for x in Xs[i])
+            res, inf, status = prov.threshold_combine(pts, xb, k, len(idx))
+            for q, i in enumerate(idx):
+                if status[q] == 1:
+                    out[i] = Signature.from_g2(JacobianPoint._from(
+                        H.F2, None if inf[q] else H.aff_to_jac(H.F2, H.g2_from_abi(res[192 * q:192 * (q + 1)]))))
+        return [Threshold.aggregate_unit_sigs(s, X, T, ec) if r is None else r for s, X, r in zip(sigs, Xs, out)]
+
 
 def _g1_content(C):
     """the content key of a commitment list whose every element is an on-curve G1 AffinePoint (the device's input), or

@@ -25,6 +25,7 @@
 #include "blsgpu_g1fix.hip"
 #include "blsgpu_g1poly.hip"
 #include "blsgpu_subgroup.hip"
+#include "blsgpu_lagrange.hip"
 #include "blsgpu_h2c.hip"
 #include "blsgpu_h2cw.hip"
 #include "blsgpu_probe.hip"
@@ -689,6 +690,45 @@ int subgroup_host(blsgpu_ctx* c, int g, const uint8_t* pts, size_t n, uint8_t* s
         if (int rc = subgroup_dev(c, g, s.at(dp), m, s.at(dst), nullptr)) return rc;
         return s.down(lo, m);
     });
+}
+// ------------------------------------------------------------ Lagrange coefficients (blsgpu_lagrange.hip) --
+// the argument checks the three entry-point pairs share (before anything is written); 1: nothing to do
+int lagrange_args(const blsgpu_ctx* c, size_t k, size_t groups, bool null_buffer) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (k == 0 || k > blsgpu::lagr::MAX_K) return fail(-EINVAL, "k must be 1 .. BLSGPU_LAGRANGE_MAX_K");
+    if (groups == 0) return 1;
+    if (null_buffer) return fail(-EINVAL, "NULL argument");
+    if (groups > 0x7FFFFFFFull || k * groups > 0xFFFFFFF0ull) return fail(-EINVAL, "batch too large");
+    return 0;
+}
+// coefficients and status of `groups` groups of k points (checked by lagrange_args), all on the device
+int lagrange_launch(blsgpu_ctx* c, const void* d_x, size_t k, size_t groups, void* d_coeffs, void* d_status, hipStream_t st) {
+    const blsgpu::lagr::Shape sh = blsgpu::lagr::shape((uint32_t)k);
+    hipLaunchKernelGGL(blsgpu::lagr::k_lagrange, dim3((unsigned)((groups + sh.gpb - 1) / sh.gpb)), dim3(sh.threads), sh.lds, st,
+                       (const uint8_t*)d_x, (uint32_t)k, (uint32_t)groups, sh.gpb, (uint8_t*)d_coeffs, (uint8_t*)d_status);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+int fr_interpolate_dev(blsgpu_ctx* c, const void* d_x, const void* d_y, size_t k, size_t groups, void* d_out, void* d_status, hipStream_t st) {
+    StreamGuard sg(c, st);
+    if (int rc = c->grow(B_LAGR_WS, groups * k * 32)) return rc;
+    if (int rc = lagrange_launch(c, d_x, k, groups, c->at<void>(B_LAGR_WS), d_status, st)) return rc;
+    const blsgpu::lagr::Shape sh = blsgpu::lagr::shape((uint32_t)k);
+    hipLaunchKernelGGL(blsgpu::lagr::k_fr_dot, dim3((unsigned)((groups + sh.gpb - 1) / sh.gpb)), dim3(sh.threads), sh.lds, st,
+                       c->at<uint8_t>(B_LAGR_WS), (const uint8_t*)d_y, (uint32_t)k, (uint32_t)groups, sh.gpb, (uint8_t*)d_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+// the coefficients into the workspace, then the G2 sums of blsgpu_g2_msm_dev with them as its device scalars (a group
+// with status 0 has all-zero scalars: infinity)
+int threshold_combine_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_x, size_t k, size_t groups, void* d_out, void* d_out_inf,
+                          void* d_status, hipStream_t st) {
+    {
+        StreamGuard sg(c, st);
+        if (int rc = c->grow(B_LAGR_WS, groups * k * 32)) return rc;
+        if (int rc = lagrange_launch(c, d_x, k, groups, c->at<void>(B_LAGR_WS), d_status, st)) return rc;
+    }
+    return msm_dev<2>(c, d_sigs, c->at<void>(B_LAGR_WS), k, groups, d_out, d_out_inf, st);
 }
 }  // namespace
 
@@ -1946,6 +1986,60 @@ BLSGPU_EXPORT int blsgpu_g2_subgroup_check_dev(blsgpu_ctx* c, const void* d_pts,
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
     return subgroup_dev(c, 2, d_pts, n, d_status, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------ threshold recovery --
+BLSGPU_EXPORT int blsgpu_lagrange_at_zero_dev(blsgpu_ctx* c, const void* d_x, size_t k, size_t groups, void* d_out_coeffs, void* d_status,
+                                              void* stream) {
+    if (int rc = lagrange_args(c, k, groups, !d_x || !d_out_coeffs || !d_status)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    StreamGuard sg(c, (hipStream_t)stream);
+    return lagrange_launch(c, d_x, k, groups, d_out_coeffs, d_status, (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_lagrange_at_zero(blsgpu_ctx* c, const uint8_t* x, size_t k, size_t groups, uint8_t* out_coeffs, uint8_t* status) {
+    if (int rc = lagrange_args(c, k, groups, !x || !out_coeffs || !status)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    Staging s(c);
+    const int dx = s.in(x, groups * k * 32), dco = s.out(out_coeffs, groups * k * 32), dst = s.out(status, groups);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    if (int rc = blsgpu_lagrange_at_zero_dev(c, s.at(dx), k, groups, s.at(dco), s.at(dst), nullptr)) return rc;
+    return s.down();
+}
+BLSGPU_EXPORT int blsgpu_fr_interpolate_at_zero_dev(blsgpu_ctx* c, const void* d_x, const void* d_y, size_t k, size_t groups, void* d_out,
+                                                    void* d_status, void* stream) {
+    if (int rc = lagrange_args(c, k, groups, !d_x || !d_y || !d_out || !d_status)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return fr_interpolate_dev(c, d_x, d_y, k, groups, d_out, d_status, (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_fr_interpolate_at_zero(blsgpu_ctx* c, const uint8_t* x, const uint8_t* y, size_t k, size_t groups, uint8_t* out,
+                                                uint8_t* status) {
+    if (int rc = lagrange_args(c, k, groups, !x || !y || !out || !status)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    Staging s(c);
+    const int dx = s.in(x, groups * k * 32), dy = s.in(y, groups * k * 32), dout = s.out(out, groups * 32), dst = s.out(status, groups);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    if (int rc = fr_interpolate_dev(c, s.at(dx), s.at(dy), k, groups, s.at(dout), s.at(dst), nullptr)) return rc;
+    return s.down();
+}
+BLSGPU_EXPORT int blsgpu_threshold_combine_dev(blsgpu_ctx* c, const void* d_sigs_affine, const void* d_x, size_t k, size_t groups, void* d_out,
+                                               void* d_out_inf, void* d_status, void* stream) {
+    if (int rc = lagrange_args(c, k, groups, !d_sigs_affine || !d_x || !d_out || !d_status)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return threshold_combine_dev(c, d_sigs_affine, d_x, k, groups, d_out, d_out_inf, d_status, (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_threshold_combine(blsgpu_ctx* c, const uint8_t* sigs_affine, const uint8_t* x, size_t k, size_t groups, uint8_t* out,
+                                           uint8_t* out_inf, uint8_t* status) {
+    if (int rc = lagrange_args(c, k, groups, !sigs_affine || !x || !out || !status)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    Staging s(c);
+    const int dsig = s.in(sigs_affine, groups * k * BLSGPU_G2_BYTES), dx = s.in(x, groups * k * 32), dout = s.out(out, groups * BLSGPU_G2_BYTES),
+              dinf = s.out(out_inf, groups), dst = s.out(status, groups);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    if (int rc = threshold_combine_dev(c, s.at(dsig), s.at(dx), k, groups, s.at(dout), s.opt(dinf), s.at(dst), nullptr)) return rc;
+    return s.down();
 }
 
 #ifdef BLSGPU_STAMPS
