@@ -70,8 +70,8 @@ int blsgpu_ctx_reserve(blsgpu_ctx *ctx, size_t max_pairs);
  * calls made so far; the line-stream stage keeps 68 x 336 bytes of line records per pair of its largest call, the
  * counterpart of the n-arrays of mpz_t the reference mallocs per call, fields_t_c.pyx:2348-2388).  out[BLSGPU_WS_TOTAL]
  * is the sum (which also counts the fixed-base G1 table and the HD derivation slice, blsgpu_g1_mul_gen /
- * blsgpu_hd_children, the commitments of blsgpu_g1_poly_check and the Lagrange coefficients of blsgpu_threshold_combine /
- * blsgpu_fr_interpolate_at_zero; they have no field of their own).
+ * blsgpu_hd_children, the per-path state of blsgpu_hd_paths, the commitments of blsgpu_g1_poly_check and the Lagrange
+ * coefficients of blsgpu_threshold_combine / blsgpu_fr_interpolate_at_zero; they have no field of their own).
  * BLSGPU_WS_FLAGS_AND_LISTS counts the flag copy of blsgpu_miller_loop_batch's fast form as well (2 bytes per pair of a
  * slice).  No device call is made. */
 enum { BLSGPU_WS_PARTIALS = 0, BLSGPU_WS_STAGING, BLSGPU_WS_LINES, BLSGPU_WS_LINE_PRODUCTS, BLSGPU_WS_FLAGS_AND_LISTS,
@@ -319,6 +319,34 @@ int blsgpu_hd_children(blsgpu_ctx *ctx, const uint8_t chain_code[32], const uint
 int blsgpu_hd_children_dev(blsgpu_ctx *ctx, const uint8_t chain_code[32], const uint8_t parent_pk_aff[BLSGPU_G1_BYTES],
                            const uint8_t *parent_sk, const void *d_indices, size_t n, void *d_out_chain, void *d_out_sk,
                            void *d_out_pk_aff, void *d_out_pk_ser, void *stream);
+
+/* HD derivation of n PATHS at once, every path from a parent of its own: path p starts at record parent_of[p] of
+ * `parents` and folds the reference's step -- ExtendedPrivateKey.private_child (keys.py:191-215; priv != 0) or
+ * ExtendedPublicKey.public_child (keys.py:276-296; priv == 0) -- over indices[p * depth .. (p + 1) * depth).  Every level
+ * runs on the device with the path's current chain code as HMAC key (its two key-block midstates per path and level,
+ * util.hmac256, util.py:19-33), the current serialised public key (or, for an index >= 2^31 in private mode, the current
+ * private key) as message and blsgpu_g1_mul_gen's table for the key; nothing returns to the host between levels.  The
+ * outputs are those of `depth` chained blsgpu_hd_children calls, byte for byte.
+ * parents: n_parents records of BLSGPU_HD_PARENT_BYTES: chain code (32), public key affine (96; in private mode the
+ * private key's public key), private key (32, big-endian; ignored when priv == 0).  parent_of: n uint32, or NULL: every
+ * path starts at record 0.  indices: n x depth uint32, path-major; depth: 1 .. 255, the same for every path of a call.
+ * Outputs, of the LEAF of each path: out_chain n x 32; out_sk n x 32 (required when priv, ignored otherwise); out_pk_aff
+ * n x 96 and out_pk_ser n x 48 as in blsgpu_hd_children (either may be NULL, not both); out_parent_fp (may be NULL) n x 4:
+ * the first four bytes of sha256(PublicKey.serialize()) of the key one level above the leaf -- the parent_fingerprint the
+ * reference stores in the child (PublicKey.get_fingerprint, keys.py:47-49); for depth == 1 that of the input parent.
+ * -EINVAL before anything is written: depth == 0 or > 255, n_parents == 0 with n > 0, a NULL required buffer, a parent_of
+ * entry >= n_parents, and in public mode an index >= 2^31 at any level ("Cannot derive hardened children from public
+ * key").  n == 0 writes nothing.  Not constant-time. */
+#define BLSGPU_HD_PARENT_BYTES 160
+int blsgpu_hd_paths(blsgpu_ctx *ctx, const uint8_t *parents, size_t n_parents, int priv, const uint32_t *parent_of,
+                    const uint32_t *indices, size_t depth, size_t n, uint8_t *out_chain, uint8_t *out_sk, uint8_t *out_pk_aff,
+                    uint8_t *out_pk_ser, uint8_t *out_parent_fp);
+/* The same with every buffer in device memory, enqueued on `stream`.  With parent_of, and in public mode, the call first
+ * scans parent_of and the indices on the device and synchronises the stream once to read the result of that check; the
+ * levels then run without another synchronisation. */
+int blsgpu_hd_paths_dev(blsgpu_ctx *ctx, const void *d_parents, size_t n_parents, int priv, const void *d_parent_of,
+                        const void *d_indices, size_t depth, size_t n, void *d_out_chain, void *d_out_sk, void *d_out_pk_aff,
+                        void *d_out_pk_ser, void *d_out_parent_fp, void *stream);
 
 /* Feldman share check (Threshold.verify_secret_fragment, threshold.py:104-125 of the reference) for n fragments at once.
  * commit: n_polys x t affine G1 points (96 B, (0,0) = infinity; caller guarantees on-curve);

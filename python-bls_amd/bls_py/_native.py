@@ -3,6 +3,7 @@
 This is the product's only compute back-end for the pairing path.  There is no
 CPU fallback: when the library or a GPU is missing, `engine()` raises.
 """
+import array
 import ctypes
 import os
 import sys
@@ -26,12 +27,14 @@ SYMBOLS = (
     "blsgpu_fq12_op_batch", "blsgpu_fq12_pow_batch", "blsgpu_ctx_set_mp3_threshold", "blsgpu_ctx_set_ls_threshold", "blsgpu_ctx_set_ls_teams", "blsgpu_ctx_set_bulk_event", "blsgpu_ctx_set_fexp_team_threshold", "blsgpu_ctx_set_fexp_trace", "blsgpu_ctx_set_fexpw_stamps", "blsgpu_debug_read_lines",
     "blsgpu_ctx_workspace_bytes", "blsgpu_verify_pipeline", "blsgpu_verify_pipeline_dev",
     "blsgpu_g1_mul_gen", "blsgpu_g1_mul_gen_dev", "blsgpu_hd_children", "blsgpu_hd_children_dev",
+    "blsgpu_hd_paths", "blsgpu_hd_paths_dev",
     "blsgpu_g1_poly_check", "blsgpu_g1_poly_check_dev",
     "blsgpu_g1_subgroup_check", "blsgpu_g1_subgroup_check_dev", "blsgpu_g2_subgroup_check", "blsgpu_g2_subgroup_check_dev",
     "blsgpu_lagrange_at_zero", "blsgpu_lagrange_at_zero_dev", "blsgpu_fr_interpolate_at_zero", "blsgpu_fr_interpolate_at_zero_dev",
     "blsgpu_threshold_combine", "blsgpu_threshold_combine_dev",
 )
 
+HD_PARENT_BYTES = 160          # BLSGPU_HD_PARENT_BYTES: chain code (32), public key affine (96), private key (32)
 LAGRANGE_MAX_K = 1024          # BLSGPU_LAGRANGE_MAX_K of include/blsgpu.h: players per group the device takes
 
 _lib = None
@@ -116,6 +119,8 @@ def load_library(path=None):
         L.blsgpu_g1_mul_gen_dev.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp]
         L.blsgpu_hd_children.argtypes = [vp, cp, cp, cp, vp, sz, vp, vp, vp, vp]
         L.blsgpu_hd_children_dev.argtypes = [vp, cp, cp, cp, vp, sz, vp, vp, vp, vp, vp]
+        L.blsgpu_hd_paths.argtypes = [vp, cp, sz, ctypes.c_int, vp, vp, sz, sz, vp, vp, vp, vp, vp]
+        L.blsgpu_hd_paths_dev.argtypes = [vp, vp, sz, ctypes.c_int, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp]
         L.blsgpu_g1_poly_check.argtypes = [vp, cp, sz, sz, vp, cp, cp, sz, vp, vp]
         L.blsgpu_g1_poly_check_dev.argtypes = [vp, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp]
         for g in ("g1", "g2"):
@@ -400,6 +405,43 @@ class Engine:
         self._check(self.lib.blsgpu_hd_children_dev(self.h, bytes(chain_code), bytes(parent_pk_aff),
                                                     None if parent_sk is None else bytes(parent_sk), d_indices, n, d_out_chain,
                                                     d_out_sk, d_out_pk_aff, d_out_pk_ser, stream), "blsgpu_hd_children_dev")
+
+    def hd_paths(self, parents, priv, parent_of, paths, aff=True, ser=True, fp=True):
+        """HD paths of one depth, a parent per path (blsgpu_hd_paths).  parents: n_parents x 160 bytes (chain code, affine
+        public key, private key or 32 zero bytes); priv: private derivation; parent_of: n indices into parents, or None
+        (every path starts at parent 0); paths: n sequences of `depth` child indices each.
+        -> (n x 32 chain codes, n x 32 keys or None (public), n x 96 affine keys or None, n x 48 serialised keys or None,
+        n x 4 parent fingerprints or None), all of the paths' leaves"""
+        if len(parents) % HD_PARENT_BYTES:
+            raise ValueError("parent records are %d bytes" % HD_PARENT_BYTES)
+        n = len(paths)
+        depth = len(paths[0]) if n else 1
+        if any(len(p) != depth for p in paths):
+            raise ValueError("the paths of one call have one depth")
+        if parent_of is not None and len(parent_of) != n:
+            raise ValueError("one parent index per path")
+        # (array("I") raises OverflowError outside 32 bits, where a c_uint32 array would wrap silently)
+        flat = array.array("I", [i for p in paths for i in p] or [0])
+        idx = (ctypes.c_uint32 * len(flat)).from_buffer(flat)
+        pof = None
+        if parent_of is not None:
+            pof_arr = array.array("I", list(parent_of) or [0])
+            pof = (ctypes.c_uint32 * len(pof_arr)).from_buffer(pof_arr)
+        chain = ctypes.create_string_buffer(max(1, 32 * n))
+        sk = ctypes.create_string_buffer(max(1, 32 * n)) if priv else None
+        oa = ctypes.create_string_buffer(max(1, 96 * n)) if aff else None
+        os_ = ctypes.create_string_buffer(max(1, 48 * n)) if ser else None
+        of = ctypes.create_string_buffer(max(1, 4 * n)) if fp else None
+        self._check(self.lib.blsgpu_hd_paths(self.h, bytes(parents), len(parents) // HD_PARENT_BYTES, 1 if priv else 0, pof, idx, depth, n,
+                                             chain, sk, oa, os_, of), "blsgpu_hd_paths")
+        return (chain.raw[:32 * n], sk.raw[:32 * n] if priv else None, oa.raw[:96 * n] if aff else None,
+                os_.raw[:48 * n] if ser else None, of.raw[:4 * n] if fp else None)
+
+    def hd_paths_dev(self, d_parents, n_parents, priv, d_parent_of, d_indices, depth, n, d_out_chain, d_out_sk, d_out_pk_aff,
+                     d_out_pk_ser, d_out_parent_fp, stream=0):
+        self._check(self.lib.blsgpu_hd_paths_dev(self.h, d_parents, n_parents, 1 if priv else 0, d_parent_of, d_indices, depth, n,
+                                                 d_out_chain, d_out_sk, d_out_pk_aff, d_out_pk_ser, d_out_parent_fp, stream),
+                    "blsgpu_hd_paths_dev")
 
     def g1_poly_check(self, commit, n_polys, t, poly, x, s=None, aff=False):
         """Feldman share checks (blsgpu_g1_poly_check): commit n_polys x t x 96 affine bytes, poly n indices, x / s n x 32

@@ -54,6 +54,12 @@ class HipProvider:
         """-> (n x 32 chain codes, n x 32 child keys or None (public), n x 96 affine keys, n x 48 serialised keys)"""
         return self._eng.hd_children(chain_code, parent_pk_aff, parent_sk, indices)
 
+    def hd_paths(self, parents: bytes, priv: bool, parent_of, paths):
+        """paths of ONE depth, path j from record parent_of[j] (None: record 0) of parents (160 bytes each: chain code,
+        affine key, private key) -> (n x 32 chain codes, n x 32 keys or None (public), n x 96 affine keys, n x 48 serialised
+        keys, n x 4 parent fingerprints) of the leaves"""
+        return self._eng.hd_paths(parents, priv, parent_of, paths)
+
     def g1_poly_check(self, commit: bytes, n_polys: int, t: int, poly, x: bytes, s=None, aff: bool = False):
         """Feldman share checks: -> (n status bytes: 1 (s_i mod n) G1 == sum_k x_i^k C[poly_i][k], 0 not, 2 poly_i has a
         C_k (k >= 1) outside the order-n subgroup; or None for s None) and the n x 96 affine Horner values (aff) or None"""
@@ -104,6 +110,8 @@ def use(provider):
     hd_children(chain_code, parent_pk_aff, parent_sk|None, indices) -> (chain codes, child keys|None, affine, serialised),
     g1_poly_check(commit, n_polys, t, poly, x, s|None, aff) -> (status bytes|None, affine Horner values|None),
     g1_subgroup / g2_subgroup(affine bytes) -> status bytes (1 in the subgroup, 2 on the curve outside it, 0 off it).
+    Optional (a provider without it sends the HD *_path_batch / *_paths_from methods to chained hd_children calls):
+    hd_paths(parents, priv, parent_of|None, paths of one depth) -> (chain codes, keys|None, affine, serialised, fingerprints).
     Optional (a provider without them sends the Threshold.*_batch methods to the host loop): LAGRANGE_MAX_K,
     lagrange_at_zero(x, k, groups) -> (coefficient bytes, status bytes), fr_interpolate_at_zero(x, y, k, groups) ->
     (32 bytes per group, status bytes), threshold_combine(sigs, x, k, groups) -> (affine bytes, [is_inf], status bytes)."""

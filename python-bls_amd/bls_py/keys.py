@@ -1,7 +1,8 @@
 """Key types (keys.py:17-316 of the reference): PublicKey = G1 point with a
 48-byte compressed form, PrivateKey = scalar mod n, and the HD keys
 ExtendedPrivateKey / ExtendedPublicKey, whose children are derived on the GPU
-many siblings at a time (blsgpu_hd_children)."""
+many siblings at a time (blsgpu_hd_children) and whose descendants many whole
+paths at a time, each from a parent of its own (blsgpu_hd_paths)."""
 from copy import deepcopy
 from random import SystemRandom
 
@@ -287,6 +288,56 @@ def _child_indices(indices):
     return out
 
 
+def _derive_paths(parents, parent_of, paths, priv):
+    """The leaves of paths[j] from parents[parent_of[j]] (extended keys; private derivation: ExtendedPrivateKeys) as
+    (parent, path, chain code, key bytes|None, affine, serialised, parent fingerprint) per path, in input order; None for
+    an empty path.  The reference's exceptions are raised before any device work; paths are bucketed by length, one
+    blsgpu_hd_paths call per distinct length.  A provider without hd_paths gets None back: the caller chains single steps."""
+    from . import backend
+    parents = list(parents)
+    paths = [[int(i) for i in p] for p in paths]
+    flat = [i for p in paths for i in p]
+    if not priv and flat and max(flat) >= 1 << 31:
+        raise Exception("Cannot derive hardened children from public key")
+    if flat and (min(flat) < 0 or max(flat) >= 1 << 32):
+        _child_indices(flat)
+    parent_of = [0] * len(paths) if parent_of is None else [int(a) for a in parent_of]
+    if len(parent_of) != len(paths):
+        raise ValueError("one parent index per path")
+    if parent_of and (min(parent_of) < 0 or max(parent_of) >= len(parents)):
+        raise IndexError("parent index out of range")
+    room = [255 - k.depth for k in parents]
+    if any(len(p) > room[a] for a, p in zip(parent_of, paths)):
+        raise Exception("Cannot go further than 255 levels")
+    prov = backend.get()
+    if not hasattr(prov, "hd_paths"):
+        return None
+    out = [None] * len(paths)
+    lengths = sorted({len(p) for p in paths} - {0})
+    if not lengths:
+        return out
+    if priv:
+        cold = [k.private_key for k in parents if k.private_key.__dict__.get("_pk_point") is None]
+        for sk, pk in zip(cold, PrivateKey.get_public_key_batch(cold)):
+            sk.__dict__["_pk_point"] = pk.value
+        records = b"".join(k.chain_code + _pk_affine(k._public_key()) + k.private_key.serialize() for k in parents)
+    else:
+        records = b"".join(k.chain_code + _pk_affine(k.public_key) + bytes(32) for k in parents)
+    for length in lengths:
+        pos = range(len(paths)) if len(lengths) == 1 and all(paths) else [j for j, p in enumerate(paths) if len(p) == length]
+        chain, sks, aff, ser, fps = prov.hd_paths(records, priv, [parent_of[j] for j in pos], [paths[j] for j in pos])
+        for t, j in enumerate(pos):
+            out[j] = (parents[parent_of[j]], paths[j], chain[32 * t:32 * t + 32], sks[32 * t:32 * t + 32] if priv else None,
+                      aff[96 * t:96 * t + 96], ser[48 * t:48 * t + 48], int.from_bytes(fps[4 * t:4 * t + 4], "big"))
+    return out
+
+
+def _fold(key, path, step):
+    for i in path:
+        key = getattr(key, step)(i)
+    return key
+
+
 class ExtendedPrivateKey:
     """HD private key (keys.py:167-255 of the reference).  private_child_batch / public_child_batch derive many
     siblings in one GPU call: both HMACs and the key multiplications of every child on the device."""
@@ -340,6 +391,45 @@ class ExtendedPrivateKey:
     def public_child_batch(self, indices):
         """[self.public_child(i) for i in indices] in one GPU call"""
         return [c.get_extended_public_key() for c in self.private_child_batch(indices)]
+
+    def private_path_batch(self, paths):
+        """[the fold of private_child over p for p in paths]: whole paths, every level on the GPU, in one call per
+        distinct path length (blsgpu_hd_paths, private mode).  Hardened and non-hardened indices may be mixed; an empty
+        path gives a key equal to self."""
+        paths = list(paths)
+        return ExtendedPrivateKey.private_paths_from([self], [0] * len(paths), paths)
+
+    def public_path_batch(self, paths):
+        """[k.get_extended_public_key() for k in self.private_path_batch(paths)]"""
+        return [c.get_extended_public_key() for c in self.private_path_batch(paths)]
+
+    @staticmethod
+    def private_paths_from(parents, parent_of, paths):
+        """[the fold of private_child over paths[j] from parents[parent_of[j]]]: the paths of many parents in one GPU call
+        per distinct path length (blsgpu_hd_paths) -- the m/a/i grid is parent_of = [a ...], paths = [[i] ...]."""
+        parents, paths = list(parents), [list(p) for p in paths]
+        got = _derive_paths(parents, parent_of, paths, True)
+        if parent_of is None:
+            parent_of = [0] * len(paths)
+        if got is None:
+            return [_fold(parents[a], p, "private_child") if p else ExtendedPrivateKey._copy(parents[a]) for a, p in zip(parent_of, paths)]
+        out = []
+        for a, rec in zip(parent_of, got):
+            if rec is None:
+                out.append(ExtendedPrivateKey._copy(parents[a]))
+                continue
+            parent, path, chain, skb, aff, ser, fp = rec
+            sk = PrivateKey.from_bytes(skb)
+            child_pk = _pk_from_device(aff, ser)
+            sk.__dict__["_pk_point"] = child_pk.value          # the cache get_public_key fills (same point)
+            child = ExtendedPrivateKey(ExtendedPrivateKey.version, parent.depth + len(path), fp, path[-1], chain, sk)
+            child.__dict__["_pk"] = child_pk
+            out.append(child)
+        return out
+
+    @staticmethod
+    def _copy(k):
+        return ExtendedPrivateKey(k.version, k.depth, k.parent_fingerprint, k.child_number, k.chain_code, k.private_key)
 
     def _public_key(self):
         pk = self.__dict__.get("_pk")
@@ -415,6 +505,35 @@ class ExtendedPublicKey:
         return [ExtendedPublicKey(self.version, self.depth + 1, fp, i, chain[32 * j:32 * (j + 1)],
                                   _pk_from_device(aff[96 * j:96 * (j + 1)], ser[48 * j:48 * (j + 1)]))
                 for j, i in enumerate(idx)]
+
+    def public_path_batch(self, paths):
+        """[the fold of public_child over p for p in paths]: whole paths, every level on the GPU, in one call per
+        distinct path length (blsgpu_hd_paths, public mode); an empty path gives a key equal to self."""
+        paths = list(paths)
+        return ExtendedPublicKey.public_paths_from([self], [0] * len(paths), paths)
+
+    @staticmethod
+    def public_paths_from(parents, parent_of, paths):
+        """[the fold of public_child over paths[j] from parents[parent_of[j]]]: the paths of many parents in one GPU call
+        per distinct path length (blsgpu_hd_paths) -- the m/a/i grid is parent_of = [a ...], paths = [[i] ...]."""
+        parents, paths = list(parents), [list(p) for p in paths]
+        got = _derive_paths(parents, parent_of, paths, False)
+        if parent_of is None:
+            parent_of = [0] * len(paths)
+        if got is None:
+            return [_fold(parents[a], p, "public_child") if p else ExtendedPublicKey._copy(parents[a]) for a, p in zip(parent_of, paths)]
+        out = []
+        for a, rec in zip(parent_of, got):
+            if rec is None:
+                out.append(ExtendedPublicKey._copy(parents[a]))
+                continue
+            parent, path, chain, _, aff, ser, fp = rec
+            out.append(ExtendedPublicKey(parent.version, parent.depth + len(path), fp, path[-1], chain, _pk_from_device(aff, ser)))
+        return out
+
+    @staticmethod
+    def _copy(k):
+        return ExtendedPublicKey(k.version, k.depth, k.parent_fingerprint, k.child_number, k.chain_code, k.public_key)
 
     def get_public_key(self):
         return self.public_key

@@ -577,6 +577,69 @@ int hd_children_dev(blsgpu_ctx* c, const uint8_t chain_code[32], const uint8_t p
     }
     return 0;
 }
+// blsgpu_hd_paths*: the arguments every form checks before anything is written (after n == 0)
+int hd_paths_args(const void* parents, size_t n_parents, int priv, const void* indices, size_t depth, size_t n, const void* chain,
+                  const void* sk, const void* aff, const void* ser) {
+    if (depth == 0 || depth > 255) return fail(-EINVAL, "depth must be 1 .. 255");
+    if (n_parents == 0) return fail(-EINVAL, "no parent records");
+    if (!parents || !indices || !chain) return fail(-EINVAL, "NULL argument");
+    if (priv && !sk) return fail(-EINVAL, "private derivation needs out_sk");
+    if (!aff && !ser) return fail(-EINVAL, "ask for out_pk_aff or out_pk_ser");
+    if (n > 0xFFFFFFFFull || n_parents > 0xFFFFFFFFull) return fail(-EINVAL, "batch too large");
+    return 0;
+}
+
+// n paths of `depth` levels on `st`, every buffer in device memory: per slice and level k_hd_path_hmac, then k_fix_mul, over
+// state in B_HDP_WS -- [0, 4) the flag of the scan, [256, ..) per path 32 bytes chain code, 32 bytes key (private) or i_left
+// (public), 96 bytes affine key, and in public mode 96 more (k_fix_mul reads the parent key while it writes the child's).
+// `check`: the device scan of parent_of and (public mode) the indices and one synchronising read of its flag first.
+int hd_paths_dev(blsgpu_ctx* c, const void* d_parents, size_t n_parents, int priv, const void* d_parent_of, const void* d_idx, size_t depth,
+                 size_t n, void* d_chain, void* d_sk, void* d_pk_aff, void* d_pk_ser, void* d_fp, bool check, hipStream_t st) {
+    using namespace blsgpu::g1fix;
+    if (n == 0) return 0;
+    if (int rc = hd_paths_args(d_parents, n_parents, priv, d_idx, depth, n, d_chain, d_sk, d_pk_aff, d_pk_ser)) return rc;
+    StreamGuard sg(c, st);
+    const size_t S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE;
+    if (int rc = c->grow(B_HDP_WS, 256 + S * (priv ? 160 : 256))) return rc;
+    char* ws = c->at<char>(B_HDP_WS);
+    if (check && (d_parent_of || !priv)) {
+        HIP_TRY(hipMemsetAsync(ws, 0, 4, st));
+        hipLaunchKernelGGL(k_hd_path_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_parent_of, (uint32_t)n_parents,
+                           (const uint32_t*)d_idx, (uint32_t)depth, priv ? 0u : 1u, (uint32_t)n, (uint32_t*)ws);
+        HIP_TRY(hipGetLastError());
+        uint32_t flag = 0;
+        HIP_TRY(hipMemcpyAsync(&flag, ws, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (flag & 2u) return fail(-EINVAL, "parent index out of range");
+        if (flag & 1u) return fail(-EINVAL, "Cannot derive hardened children from public key");
+    }
+    if (int rc = fix_table(c, st)) return rc;
+    uint32_t* ws_chain = (uint32_t*)(ws + 256);
+    uint32_t* ws_scal = ws_chain + S * 8;
+    uint32_t* ws_aff[2] = {ws_scal + S * 8, ws_scal + S * 8 + S * 24};
+    const uint32_t* par = (const uint32_t*)d_parents;
+    return for_slices(n, S, [&](size_t lo, size_t m) {
+        int cur = 0;                                                       // ws_aff[cur]: the keys the next level derives from
+        for (size_t l = 0; l < depth; l++) {
+            const bool first = l == 0, last = l + 1 == depth;
+            uint32_t* chain_out = last ? (uint32_t*)d_chain + lo * 8 : ws_chain;
+            uint32_t* scal_out = last && priv ? (uint32_t*)d_sk + lo * 8 : ws_scal;
+            hipLaunchKernelGGL(k_hd_path_hmac, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, first ? par : ws_chain,
+                               first ? par + 32 : ws_scal, first ? par + 8 : ws_aff[cur], first ? 40u : 0u,
+                               d_parent_of ? (const uint32_t*)d_parent_of + lo : nullptr, first ? 1u : 0u,
+                               (const uint32_t*)d_idx + lo * depth + l, (uint32_t)depth, (uint32_t)m, priv ? 1u : 0u, chain_out, scal_out,
+                               first && !priv ? ws_aff[0] : nullptr, last && d_fp ? (uint32_t*)d_fp + lo : nullptr);
+            HIP_TRY(hipGetLastError());
+            const int next = priv ? 0 : cur ^ 1;
+            if (int rc = fix_mul_launch(c, scal_out, m, priv ? nullptr : ws_aff[cur], priv ? 0 : m,
+                                        last ? (d_pk_aff ? (char*)d_pk_aff + lo * 96 : nullptr) : (char*)ws_aff[next],
+                                        last && d_pk_ser ? (char*)d_pk_ser + lo * 48 : nullptr, st))
+                return rc;
+            cur = next;
+        }
+        return 0;
+    });
+}
 // ------------------------------------------------------------ Feldman share checks (blsgpu_g1poly.hip) --
 // the arguments every form checks before anything is written (after t == 0 and n == 0)
 int poly_args(size_t n_polys, size_t t, const void* commit, const void* poly, const void* x, const void* s, const void* status,
@@ -1929,6 +1992,44 @@ BLSGPU_EXPORT int blsgpu_hd_children_dev(blsgpu_ctx* c, const uint8_t chain_code
     HIP_TRY(hipSetDevice(c->device));
     return hd_children_dev(c, chain_code, parent_pk_aff, parent_sk, d_indices, n, d_out_chain, d_out_sk, d_out_pk_aff, d_out_pk_ser, true,
                            (hipStream_t)stream);
+}
+
+BLSGPU_EXPORT int blsgpu_hd_paths(blsgpu_ctx* c, const uint8_t* parents, size_t n_parents, int priv, const uint32_t* parent_of,
+                                  const uint32_t* indices, size_t depth, size_t n, uint8_t* out_chain, uint8_t* out_sk, uint8_t* out_pk_aff,
+                                  uint8_t* out_pk_ser, uint8_t* out_parent_fp) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (depth == 0 || depth > 255) return fail(-EINVAL, "depth must be 1 .. 255");
+    if (n == 0) return 0;
+    if (int rc = hd_paths_args(parents, n_parents, priv, indices, depth, n, out_chain, out_sk, out_pk_aff, out_pk_ser)) return rc;
+    if (parent_of)
+        for (size_t i = 0; i < n; i++)
+            if (parent_of[i] >= n_parents) return fail(-EINVAL, "parent index out of range");
+    if (!priv)
+        for (size_t i = 0; i < n * depth; i++)
+            if (indices[i] >> 31) return fail(-EINVAL, "Cannot derive hardened children from public key");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE;
+    Staging s(c);
+    const int dpar = s.in(parents, n_parents * BLSGPU_HD_PARENT_BYTES), dof = s.in(parent_of, S, 4), didx = s.in(indices, S, depth * 4),
+              dchain = s.out(out_chain, S, 32), dsk = s.out(priv ? out_sk : nullptr, S, 32), daff = s.out(out_pk_aff, S, 96),
+              dser = s.out(out_pk_ser, S, 48), dfp = s.out(out_parent_fp, S, 4);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    return for_slices(n, S, [&](size_t lo, size_t m) {
+        if (int rc = s.up(lo, m)) return rc;
+        if (int rc = hd_paths_dev(c, s.at(dpar), n_parents, priv, s.opt(dof), s.at(didx), depth, m, s.at(dchain), s.opt(dsk), s.opt(daff),
+                                  s.opt(dser), s.opt(dfp), false, nullptr)) return rc;
+        return s.down(lo, m);
+    });
+}
+BLSGPU_EXPORT int blsgpu_hd_paths_dev(blsgpu_ctx* c, const void* d_parents, size_t n_parents, int priv, const void* d_parent_of,
+                                      const void* d_indices, size_t depth, size_t n, void* d_out_chain, void* d_out_sk, void* d_out_pk_aff,
+                                      void* d_out_pk_ser, void* d_out_parent_fp, void* stream) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (depth == 0 || depth > 255) return fail(-EINVAL, "depth must be 1 .. 255");
+    HIP_TRY(hipSetDevice(c->device));
+    return hd_paths_dev(c, d_parents, n_parents, priv, d_parent_of, d_indices, depth, n, d_out_chain, d_out_sk, d_out_pk_aff, d_out_pk_ser,
+                        d_out_parent_fp, true, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------ Feldman share checks --

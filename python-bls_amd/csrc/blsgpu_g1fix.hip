@@ -1,5 +1,5 @@
-// blsgpu_g1fix.hip -- fixed-base G1 multiplication  out_i = s_i G1 (+ A_i)  and batched HD child derivation
-// (included by blsgpu_api.hip).
+// blsgpu_g1fix.hip -- fixed-base G1 multiplication  out_i = s_i G1 (+ A_i), batched HD child derivation and batched HD
+// PATH derivation with a parent per lane (included by blsgpu_api.hip).
 //
 // Every s G1 of the other entries is a variable-base multiplication (k_smul: a table of the point's own multiples per
 // lane, 252 doublings, 64 complete additions).  The generator is fixed, so its multiples are computed ONCE per context:
@@ -8,6 +8,11 @@
 // T[w][d_w]: 32 complete mixed additions (r28::pmadd, none for a zero digit), no doubling, then one inversion for the
 // affine result.  One scalar per lane; the lanes of a wavefront gather from the same window's 28 KB at each step.
 // The table is indexed by secret digits: not constant-time (neither is k_smul).
+//
+// HD paths (blsgpu_hd_paths): one path per lane, one level per pair of launches -- k_hd_path_hmac (the lane's own chain
+// code as HMAC key: two midstate compressions and four HMAC compressions per level) and k_fix_mul on the scalars it
+// leaves -- over state that stays in device memory between the levels.  Like k_hd_hmac and k_fix_mul it is NOT
+// constant-time: the table gathers follow the digits of secret keys, and lanes branch on hardened indices.
 #pragma once
 
 #include "hd_derive.h"
@@ -45,6 +50,17 @@ __device__ __forceinline__ void fix_sum(const uint32_t* __restrict__ table, cons
             r28::pmadd(acc, r28::ld(p), r28::ld(p + r28::NL));
         }
     }
+}
+
+// PublicKey.serialize() of a canonical affine point (ec.py:94-111 of the reference), in place on x: 0x80 in the top byte
+// when y > q // 2 (most significant word first).  Infinity is (0, 0): y = 0, so x stays 0.
+__device__ __forceinline__ void ser_flag(uint32_t x[12], const uint32_t y[12]) {
+    bool gt = false, decided = false;
+#pragma unroll
+    for (int w = 11; w >= 0; w--) {
+        if (!decided && y[w] != HALF_Q_WORDS[w]) { gt = y[w] > HALF_Q_WORDS[w]; decided = true; }
+    }
+    x[11] |= gt ? 0x80000000u : 0u;
 }
 
 // The table: entry e = w * 255 + d - 1 holds d 2^(8w) G1 -- one entry per lane, double-and-add over the 8 bits of d, then 8w
@@ -104,12 +120,7 @@ __global__ void __launch_bounds__(256) k_fix_mul(const uint32_t* __restrict__ ta
         for (int w = 0; w < 12; w++) { out_aff[(size_t)i * 24 + w] = bswap32(x[11 - w]); out_aff[(size_t)i * 24 + 12 + w] = bswap32(y[11 - w]); }
     }
     if (out_ser) {
-        bool gt = false, decided = false;                   // y > q // 2, most significant word first
-#pragma unroll
-        for (int w = 11; w >= 0; w--) {
-            if (!decided && y[w] != HALF_Q_WORDS[w]) { gt = y[w] > HALF_Q_WORDS[w]; decided = true; }
-        }
-        x[11] |= gt ? 0x80000000u : 0u;                     // (infinity: y = 0, so x stays 0)
+        ser_flag(x, y);
 #pragma unroll
         for (int w = 0; w < 12; w++) out_ser[(size_t)i * 12 + w] = bswap32(x[11 - w]);
     }
@@ -167,6 +178,95 @@ __global__ void __launch_bounds__(256) k_hd_check(const uint32_t* __restrict__ i
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && (idx[i] >> 31)) atomicOr(flag, 1u);
+}
+#else
+;
+#endif
+
+// One level of n paths, one path per lane (keys.py:191-215 / 276-296 of the reference with the lane's OWN parent).  The
+// lane's parent is record `src` of (chain_in, aff_in, sk_in): 32 bytes chain code, 96 bytes affine public key, 32 bytes
+// private key (private mode), every array with a stride of rec_dw words -- 40 for the caller's parent records (first
+// level: src = parent_of[p], or 0 without parent_of), or rec_dw = 0 for the state of the level before (strides 8 / 24 / 8,
+// src = p).  The chain code is the HMAC key, so its two midstates are computed here, per lane and per level
+// (hdk::hmac_key_words); the message is the parent key's serialisation (ser_flag, as k_fix_mul writes it) or, for a
+// hardened index in private mode, the private key's bytes.  chain_out[p] = i_right; scal_out[p] = (i_left + sk) mod n
+// (private) or i_left (public: k_fix_mul reduces it and adds the parent key).  chain_out / scal_out may be the state
+// arrays this lane read (no other lane touches them).  aff_copy (or NULL): the parent key's 96 bytes per lane, the `add`
+// of the first public level's k_fix_mul.  fp_out (or NULL): PublicKey.get_fingerprint of the parent key, 4 bytes
+// big-endian -- the last level's parent_fingerprint.
+__global__ void __launch_bounds__(256) k_hd_path_hmac(const uint32_t* chain_in, const uint32_t* sk_in, const uint32_t* __restrict__ aff_in,
+                                                      uint32_t rec_dw, const uint32_t* __restrict__ parent_of, uint32_t first,
+                                                      const uint32_t* __restrict__ idx, uint32_t idx_stride, uint32_t n, uint32_t priv,
+                                                      uint32_t* chain_out, uint32_t* scal_out, uint32_t* __restrict__ aff_copy,
+                                                      uint32_t* __restrict__ fp_out)
+#if BLSGPU_EMIT(BLSGPU_TU_FIX)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const size_t src = first ? (parent_of ? parent_of[p] : 0u) : p;
+    const uint32_t* a = aff_in + src * (rec_dw ? rec_dw : 24u);
+    const uint32_t* c = chain_in + src * (rec_dw ? rec_dw : 8u);
+    const uint32_t index = idx[(size_t)p * idx_stride];
+    const bool hardened = (index >> 31) != 0u;              // only in private mode (refused in public mode before any launch)
+    uint32_t x[12], y[12], ser[12], chain[8], sk_ser[8];
+#pragma unroll
+    for (int w = 0; w < 12; w++) {
+        const uint32_t xw = a[w], yw = a[12 + w];
+        if (aff_copy) { aff_copy[(size_t)p * 24 + w] = xw; aff_copy[(size_t)p * 24 + 12 + w] = yw; }
+        x[11 - w] = bswap32(xw);
+        y[11 - w] = bswap32(yw);
+    }
+    ser_flag(x, y);
+#pragma unroll
+    for (int w = 0; w < 12; w++) ser[w] = x[11 - w];
+#pragma unroll
+    for (int j = 0; j < 8; j++) chain[j] = bswap32(c[j]);
+    if (priv) {
+        const uint32_t* s = sk_in + src * (rec_dw ? rec_dw : 8u);
+#pragma unroll
+        for (int j = 0; j < 8; j++) sk_ser[j] = bswap32(s[j]);
+    }
+    if (fp_out) fp_out[p] = bswap32(hdk::fingerprint(ser));
+    hdk::HmacKey key;
+    hdk::hmac_key_words(chain, key);
+    uint32_t il[8], ir[8];
+    if (priv && hardened) hdk::child_hmacs(key, sk_ser, 8, index, il, ir);
+    else hdk::child_hmacs(key, ser, 12, index, il, ir);
+#pragma unroll
+    for (int j = 0; j < 8; j++) chain_out[(size_t)p * 8 + j] = bswap32(ir[j]);
+    if (priv) {
+        uint32_t l[8], k[8], r[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) { l[j] = il[7 - j]; k[j] = sk_ser[7 - j]; }
+        hdk::reduce_n(l);
+        hdk::reduce_n(k);
+        hdk::add_mod_n(r, l, k);
+#pragma unroll
+        for (int j = 0; j < 8; j++) scal_out[(size_t)p * 8 + j] = bswap32(r[7 - j]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; j++) scal_out[(size_t)p * 8 + j] = bswap32(il[j]);
+    }
+}
+#else
+;
+#endif
+
+// The validity scan of blsgpu_hd_paths_dev, one path per lane: flag[0] |= 2 if parent_of[p] >= n_parents, |= 1 if (pub)
+// any of the path's `depth` indices is >= 2^31
+__global__ void __launch_bounds__(256) k_hd_path_check(const uint32_t* __restrict__ parent_of, uint32_t n_parents,
+                                                       const uint32_t* __restrict__ idx, uint32_t depth, uint32_t pub, uint32_t n,
+                                                       uint32_t* __restrict__ flag)
+#if BLSGPU_EMIT(BLSGPU_TU_FIX)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    if (parent_of && parent_of[p] >= n_parents) atomicOr(flag, 2u);
+    if (pub) {
+        uint32_t any = 0;
+        for (uint32_t l = 0; l < depth; l++) any |= idx[(size_t)p * depth + l];
+        if (any >> 31) atomicOr(flag, 1u);
+    }
 }
 #else
 ;

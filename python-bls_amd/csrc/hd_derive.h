@@ -1,14 +1,16 @@
 // hd_derive.h -- the byte-level steps of HD child derivation (ExtendedPrivateKey.private_child /
 // ExtendedPublicKey.public_child, keys.py:191-215 and 276-296 of the reference): HMAC-SHA256 with the chain code as key
 // (util.hmac256, util.py:19-33) and 256-bit scalars mod the group order n.  The same source compiles for the host
-// (HD_FN = static inline) so tests/test_hd_host.py checks it against Python's hmac, and for gfx950 (blsgpu_g1fix.hip:
+// (HD_FN = static inline) so tests/test_hd_host.py and tests/test_hd_paths_host.py check it against Python's hmac, and for gfx950 (blsgpu_g1fix.hip:
 // one child per lane).
 //
 // A child's HMAC message is ser || be32(i) || b, b in {0, 1}: 48 + 4 + 1 = 53 bytes (parent public key, index < 2^31)
 // or 32 + 4 + 1 = 37 bytes (parent private key, hardened index).  The key (32 bytes) XOR ipad / opad is one block each,
 // whose compressions -- the MIDSTATES -- are the same for every child of a parent: hmac_key computes them once per call.
 // After them a message of at most 55 bytes is one padded block, and the outer hash of the 32-byte inner digest one more:
-// two compressions per HMAC, four per child.
+// two compressions per HMAC, four per child.  A PATH (blsgpu_hd_paths: one path per lane, a parent of its own) changes its
+// chain code level by level, so there the midstates are per lane and per level -- hmac_key_words, six compressions per
+// level -- and the parent fingerprint of the leaf is one more (fingerprint).
 #pragma once
 #include <stdint.h>
 
@@ -107,6 +109,41 @@ HD_FN void child_hmacs(const HmacKey& k, const uint32_t* ser, int sw, uint32_t i
     hmac_block(k, block, i_left);
     block[sw + 1] = 0x01800000u;                                // b = 1
     hmac_block(k, block, i_right);
+}
+
+// ---- paths: the parent changes level by level, so the key midstates are per lane and per level ------------------------
+// hmac_key for a chain code held as 8 big-endian words (the i_right of the level before): two compressions.
+HD_FN void hmac_key_words(const uint32_t chain[8], HmacKey& k) {
+    const uint32_t iv[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+    uint32_t wi[16], wo[16];
+    for (int j = 0; j < 16; j++) {
+        const uint32_t v = j < 8 ? chain[j] : 0u;
+        wi[j] = v ^ 0x36363636u;
+        wo[j] = v ^ 0x5c5c5c5cu;
+    }
+    for (int j = 0; j < 8; j++) { k.ipad[j] = iv[j]; k.opad[j] = iv[j]; }
+    sha256_compress(k.ipad, wi);
+    sha256_compress(k.opad, wo);
+}
+
+// One level of a path (keys.py:202-204 / 284-286 of the reference) under the chain code `chain`: its two midstates, then
+// the two HMACs of child_hmacs -- six compressions.
+HD_FN void path_step(const uint32_t chain[8], const uint32_t* ser, int sw, uint32_t index, uint32_t i_left[8], uint32_t i_right[8]) {
+    HmacKey k;
+    hmac_key_words(chain, k);
+    child_hmacs(k, ser, sw, index, i_left, i_right);
+}
+
+// PublicKey.get_fingerprint (keys.py:47-49 of the reference): the first four bytes of sha256(ser) for the 48 bytes of
+// PublicKey.serialize() as 12 big-endian words -- one padded block, one compression from the IV.
+HD_FN uint32_t fingerprint(const uint32_t ser[12]) {
+    uint32_t st[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+    uint32_t w[16];
+    for (int j = 0; j < 16; j++) w[j] = j < 12 ? ser[j] : 0u;
+    w[12] = 0x80000000u;
+    w[15] = 48 * 8;
+    sha256_compress(st, w);
+    return st[0];
 }
 
 // ---- scalars mod n (the order of G1): 8 little-endian words -----------------------------------------------------------
