@@ -20,7 +20,6 @@
 #include "blsgpu_fexpw.hip"
 #include "blsgpu_mlw.hip"
 #include "blsgpu_lsw.hip"
-#include "blsgpu_g1w.hip"
 #include "blsgpu_msm.hip"
 #include "blsgpu_g1fix.hip"
 #include "blsgpu_g1poly.hip"
@@ -28,6 +27,7 @@
 #include "blsgpu_lagrange.hip"
 #include "blsgpu_h2c.hip"
 #include "blsgpu_h2cw.hip"
+#include "blsgpu_msmw.hip"
 #include "blsgpu_probe.hip"
 
 #if BLSGPU_EMIT(BLSGPU_TU_HOST)
@@ -129,6 +129,13 @@ int decompress_host(blsgpu_ctx* c, const uint8_t* in, size_t n, uint8_t* out, ui
 namespace {
 constexpr int MSM_WAVES = 4;
 
+// The wide machine's Horner (blsgpu_msmw.hip): list g of `lists` -> sum_i 2^(cbits i) in[g][i], one wavefront per list; AFFINE = 0
+// leaves projective sums for the next step, AFFINE = 1 writes the caller's affine point and its infinity flag.
+template <int DEG, int AFFINE>
+static void horner_wide(hipStream_t st, size_t lists, const uint32_t* in, uint32_t npts, uint32_t cbits, uint32_t* out, uint8_t* out_inf) {
+    hipLaunchKernelGGL((blsgpu::msmw::k_msm_horner_wide<DEG, AFFINE>), dim3((unsigned)lists), dim3(64), 0, st, in, npts, cbits, out, out_inf);
+}
+
 // One sum with scalars by sorted buckets (blsgpu_msm.hip, k_srt_*; G1 a unit per lane, G2 per lane pair): enqueues on `st` and
 // returns, like every _dev path (no synchronisation, usable under stream capture).  Returns 1 only when the key list would not fit
 // 32 bits; the caller then takes the fixed-window path.
@@ -194,11 +201,6 @@ static int msm_sorted(blsgpu_ctx* c, const void* d_pts, const void* d_scalars, s
     hipLaunchKernelGGL(blsgpu::k_srt_bits<DEG>, blocks(btotal), dim3(64), 0, st, W + o_bsum, nwin, cb, (uint32_t)btotal, W + o_b0);
     HIP_TRY(hipGetLastError());
     uint32_t *src = W + o_b0, *dst = W + o_b1;
-    // the tail on the wide machine: result = sum_i 2^(c i) P_i over a list, one wavefront per list (blsgpu_g1w.hip, blsgpu_h2cw.hip)
-    const auto horner = [&](size_t lists, const uint32_t* in, uint32_t npts, uint32_t cbits, uint32_t* out) {
-        if (DEG == 1) hipLaunchKernelGGL(blsgpu::g1w::k_msm_horner_wide<0>, dim3((unsigned)lists), dim3(64), 0, st, in, npts, cbits, out, (uint8_t*)nullptr);
-        else hipLaunchKernelGGL(blsgpu::h2cw::k_msm_horner_wide2<0>, dim3((unsigned)lists), dim3(64), 0, st, in, npts, cbits, out, (uint8_t*)nullptr);
-    };
     if (nch == 1 && !wide) {                                  // (5-bit windows: nothing to fold, but the VM's tail reads its own form)
         hipLaunchKernelGGL(blsgpu::k_msm_lane_fold<1>, dim3((unsigned)((nsum + 63) / 64)), dim3(64), 0, st, src, 1u, 1u, 1u, (uint32_t)nsum, dst, 1u);
         src = dst;
@@ -207,7 +209,7 @@ static int msm_sorted(blsgpu_ctx* c, const void* d_pts, const void* d_scalars, s
         const size_t nfold = (cur + 7) / 8, ftotal = nsum * nfold;
         if (wide && ftotal <= 4096 && (cur <= 8 || cur % 8 == 0))
             // few runs left: one wavefront per run, an addition two steps of the wide machine (a lane's own addition is ~6000 instructions)
-            horner(ftotal, src, (uint32_t)(cur < 8 ? cur : 8), 0u, dst);
+            horner_wide<DEG, 0>(st, ftotal, src, (uint32_t)(cur < 8 ? cur : 8), 0u, dst, nullptr);
         else if (wide)
             hipLaunchKernelGGL(blsgpu::k_srt_fold<DEG>, blocks(ftotal), dim3(64), 0, st, src, (uint32_t)cur, 8u, (uint32_t)nfold, (uint32_t)ftotal, dst);
         else
@@ -219,9 +221,8 @@ static int msm_sorted(blsgpu_ctx* c, const void* d_pts, const void* d_scalars, s
     }
     if (wide) {
         // W_w = sum_b 2^b S_(w,b), one wavefront per window; then sum_w 2^(cb w) W_w on one wavefront
-        horner(nwin, src, cb, 1u, W + o_win);
-        if (DEG == 1) hipLaunchKernelGGL(blsgpu::g1w::k_msm_horner_wide<1>, dim3(1), dim3(64), 0, st, W + o_win, nwin, cb, (uint32_t*)d_out, (uint8_t*)d_out_inf);
-        else hipLaunchKernelGGL(blsgpu::h2cw::k_msm_horner_wide2<1>, dim3(1), dim3(64), 0, st, W + o_win, nwin, cb, (uint32_t*)d_out, (uint8_t*)d_out_inf);
+        horner_wide<DEG, 0>(st, nwin, src, cb, 1u, W + o_win, nullptr);
+        horner_wide<DEG, 1>(st, 1, W + o_win, nwin, cb, (uint32_t*)d_out, (uint8_t*)d_out_inf);
     } else {
         hipLaunchKernelGGL(blsgpu::k_srt_windows, dim3(nwin), dim3(64), (size_t)blsgpu::TEAM_BYTES, st, c->tabs, src, cb, W + o_win);
         hipLaunchKernelGGL(blsgpu::k_msm_pip_horner<1>, dim3(1), dim3(64), (size_t)blsgpu::TEAM_BYTES, st, c->tabs, W + o_win, nwin, cb,
@@ -258,18 +259,15 @@ static int msm_plain(blsgpu_ctx* c, const void* d_pts, size_t n, void* d_out, vo
     size_t cur = U;
     while (cur > 8) {
         const size_t nfold = (cur + 7) / 8;
-        if (nfold <= 4096 && cur % 8 == 0) {
-            if (DEG == 1) hipLaunchKernelGGL(blsgpu::g1w::k_msm_horner_wide<0>, dim3((unsigned)nfold), dim3(64), 0, st, src, 8u, 0u, dst, (uint8_t*)nullptr);
-            else hipLaunchKernelGGL(blsgpu::h2cw::k_msm_horner_wide2<0>, dim3((unsigned)nfold), dim3(64), 0, st, src, 8u, 0u, dst, (uint8_t*)nullptr);
-        } else {
+        if (nfold <= 4096 && cur % 8 == 0)
+            horner_wide<DEG, 0>(st, nfold, src, 8u, 0u, dst, nullptr);
+        else
             hipLaunchKernelGGL(blsgpu::k_srt_fold<DEG>, blocks(nfold), dim3(64), 0, st, src, (uint32_t)cur, 8u, (uint32_t)nfold, (uint32_t)nfold, dst);
-        }
         HIP_TRY(hipGetLastError());
         uint32_t* t = src; src = dst; dst = t;
         cur = nfold;
     }
-    if (DEG == 1) hipLaunchKernelGGL(blsgpu::g1w::k_msm_horner_wide<1>, dim3(1), dim3(64), 0, st, src, (uint32_t)cur, 0u, (uint32_t*)d_out, (uint8_t*)d_out_inf);
-    else hipLaunchKernelGGL(blsgpu::h2cw::k_msm_horner_wide2<1>, dim3(1), dim3(64), 0, st, src, (uint32_t)cur, 0u, (uint32_t*)d_out, (uint8_t*)d_out_inf);
+    horner_wide<DEG, 1>(st, 1, src, (uint32_t)cur, 0u, (uint32_t*)d_out, (uint8_t*)d_out_inf);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -32,12 +32,22 @@ using r28::NL;
 constexpr int VF_DW = MLW_PAGES * MLW_PAGE_BYTES / 4;
 
 struct Rec { uint32_t w[5]; };
-__device__ __forceinline__ Rec load_rec(uint32_t kind, uint32_t lane) {
+// a lane's record of a step kind, from the table of any program of the machine (a kind past the table -- MLW_NOP -- reads kind 0:
+// loaded, not used; the clamp folds away where the kind is a constant)
+template <int KINDS>
+__device__ __forceinline__ Rec load_rec(const uint32_t (&tab)[KINDS][5][64], uint32_t kind, uint32_t lane) {
     Rec r;
-    const uint32_t k = kind < (uint32_t)MLW_KINDS ? kind : 0u;          // (MLW_NOP: loaded, not used)
+    const uint32_t k = kind < (uint32_t)KINDS ? kind : 0u;
 #pragma unroll
-    for (int i = 0; i < 5; i++) r.w[i] = MLW_REC[k][i][lane];
+    for (int i = 0; i < 5; i++) r.w[i] = tab[k][i][lane];
     return r;
+}
+// the multiple of a value that lane `lane` of a quad stores: 1, -1, 2, -2
+__device__ __forceinline__ int32_t quad_variant(uint32_t lane) {
+    const uint32_t vr = lane & 3u;
+    int32_t v = vr == 2u ? 2 : -2;                 // (one select per case: no branch)
+    v = vr == 1u ? -1 : v;
+    return vr == 0u ? 1 : v;
 }
 // V[a] + V[b], limb by limb (byte addresses of limb 0; limb j at + 256 j)
 __device__ __forceinline__ void rd2(int32_t* __restrict__ out, const char* vf, uint32_t ab) {
@@ -97,13 +107,15 @@ __device__ __forceinline__ void wstep(char* vf, const Rec& r) {
     srn(V, t, (int32_t)r.w[4] >> 16);
     st14(vf, r.w[4] & 0xFFFFu, V);
 }
-// a stored value is 0 mod q: its digits are those of 0 or of q
-__device__ __forceinline__ bool stored_zero(const char* vf, uint32_t a) {
+// a stored value as a field element
+__device__ __forceinline__ fe ld_fe(const char* vf, uint32_t a) {
     fe x;
 #pragma unroll
     for (int j = 0; j < NL; j++) x.v[j] = *reinterpret_cast<const int32_t*>(vf + a + 256 * j);
-    return r28::is_zero(x);
+    return x;
 }
+// a stored value is 0 mod q: its digits are those of 0 or of q
+__device__ __forceinline__ bool stored_zero(const char* vf, uint32_t a) { return r28::is_zero(ld_fe(vf, a)); }
 
 // Block b = pair b of the call (group b / gsz): its Miller value (up to the factors the final exponentiation removes) as
 // ONE partial in the wavefront VM's form: partials[b * 144 ...] (12 x 12 words x 2^384, the reference's flat order).
@@ -137,7 +149,7 @@ __global__ void __launch_bounds__(W == 2 ? 256 : 192) k_miller_wide(const uint32
     if (wave == CHAIN) {
         // the inputs in their four multiples: quad i of this wavefront stores value i of the list below
         const uint32_t qd = lane >> 2, vr = lane & 3u;
-        const int32_t variant = vr == 0u ? 1 : (vr == 1u ? -1 : (vr == 2u ? 2 : -2));
+        const int32_t variant = quad_variant(lane);
         const uint32_t* s1 = g1 + (size_t)pair * 24;
         const uint32_t* s2 = g2 + (size_t)pair * 48;
         // value i: source words, scale, destination
@@ -165,7 +177,7 @@ __global__ void __launch_bounds__(W == 2 ? 256 : 192) k_miller_wide(const uint32
     const uint32_t* prog = W == 2 ? (wave ? MLW_PROG_CHAIN : MLW_PROG_ACC) : (wave == 0u ? MLW3_PROG_A : (wave == 1u ? MLW3_PROG_B : MLW3_PROG_C));
     uint32_t pc = 0;
     uint32_t k1 = prog[0], k2 = prog[1];
-    Rec r1 = load_rec(k1 & 0x3Fu, lane);
+    Rec r1 = load_rec(MLW_REC, k1 & 0x3Fu, lane);
 #pragma unroll 1
     for (uint32_t ph = 0; ph < (uint32_t)(W == 2 ? MLW_PHASES : MLW3_PHASES); ph++) {
 #pragma unroll 1
@@ -175,7 +187,7 @@ __global__ void __launch_bounds__(W == 2 ? 256 : 192) k_miller_wide(const uint32
             k1 = k2;
             k2 = prog[pc + 2];
             pc++;
-            r1 = load_rec(k1 & 0x3Fu, lane);
+            r1 = load_rec(MLW_REC, k1 & 0x3Fu, lane);
             if ((k & 0x3Fu) != (uint32_t)MLW_NOP) {
                 const uint32_t shape = (k >> 8) & 3u;
                 if (W == 3 && shape == 3u) wstep<1, false, true>(vf, r);
@@ -199,9 +211,7 @@ __global__ void __launch_bounds__(W == 2 ? 256 : 192) k_miller_wide(const uint32
         if (quad < 12u && (lane & 3u) == 0u) {
             const uint32_t k = quad >> 1, part = quad & 1u;
             const uint32_t flat = (k & 1u) ? 3u + (k >> 1) : (k >> 1);             // w-powers 0,2,4,1,3,5 in the flat order
-            fe a;
-#pragma unroll
-            for (int j = 0; j < NL; j++) a.v[j] = *reinterpret_cast<const int32_t*>(vf + (W == 2 ? MLW_AT_F00 : MLW3_AT_F_FINAL) + 4u * lane + 256 * j);
+            const fe a = ld_fe(vf, (W == 2 ? MLW_AT_F00 : MLW3_AT_F_FINAL) + 4u * lane);
             uint32_t w[12];
             r28::to_vm(w, a);
             uint32_t* o = partials + (size_t)pair * 144 + flat * 24u + part * 12u;

@@ -1003,7 +1003,7 @@ __global__ void __launch_bounds__(64) k_msm_lane_fold(const uint32_t* __restrict
 // chain over 8191 buckets), W_w = sum_b 2^b S_b (k_srt_windows) -- then Horner over the windows.
 // Same value as the reference's double-and-add summed over the points (fields_t.py:705-740); parity is on the
 // affine result.  Points at infinity ((0,0)) and zero digits are left out of the list.  Points and sums are in the
-// L28 form of fp28.h (k_srt_prep); the tail is blsgpu_g1w.hip's (or, BLSGPU_MSM_WIDE_TAIL=0, the VM's: the last fold hands it its own form).
+// L28 form of fp28.h (k_srt_prep); the tail is blsgpu_msmw.hip's (or, BLSGPU_MSM_WIDE_TAIL=0, the VM's: the last fold hands it its own form).
 constexpr uint32_t SRT_LANES = 2048u * 64u;                   // two wavefronts per SIMD
 
 // SIGNED digits (round 5): s = sum_w d_w 2^(cb w) with d_w in [-2^(cb-1), 2^(cb-1)) -- the digits of s + C, C = sum_w 2^(cb-1) 2^(cb w),

@@ -1,5 +1,5 @@
-"""Lane-level model and table builder of the WIDE tail of the sorted-bucket G1 sum (round 5; csrc/blsgpu_g1w.hip
-k_msm_horner_wide): result = sum_i 2^(c i) P_i over a short list of projective G1 points by Horner from the top -- the window
+"""Lane-level model and table builder of the WIDE tail of the sorted-bucket G1 sum (round 5; csrc/blsgpu_msmw.hip
+k_msm_horner_wide<1, .>): result = sum_i 2^(c i) P_i over a short list of projective G1 points by Horner from the top -- the window
 sums W_w = sum_b 2^b S_(w,b) (c = 1, one wavefront per window) and the sum over the windows sum_w 2^(13 w) W_w (c = 13, one
 wavefront) of BLS.aggregate_pub_keys(secure) at scale (bls.py:203-223; the reference's double-and-add summed over the points,
 fields_t.py:705-740).  247 doublings and 19 additions of ONE point are a dependent chain: nothing to batch.  The wavefront VM ran it

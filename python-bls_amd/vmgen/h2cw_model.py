@@ -189,7 +189,7 @@ def clear(S0, S1, psix, psiy):
 
 
 def horner(points, cbits):
-    """the window Horner of a G2 sum on the same tables (csrc/blsgpu_h2cw.hip k_msm_horner_wide2: the accumulator and slot point 0,
+    """the window Horner of a G2 sum on the same tables (csrc/blsgpu_msmw.hip k_msm_horner_wide<2, .>: the accumulator and slot point 0,
     kinds DBL1 / DBL2 / ADD1_0p / ADD2): points = homogeneous ((x0, x1), (y0, y1), (z0, z1)), index 0 the lowest; returns
     sum_i 2^(cbits i) points[i] (homogeneous) and the largest |stored value| / q"""
     m = Machine(N, KINDS)

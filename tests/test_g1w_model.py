@@ -1,5 +1,5 @@
 """CPU: the lane tables of the wide tail of the sorted-bucket G1 sum (vmgen/g1w_model.py -- what csrc/g1w_tables_gfx950.h holds and
-csrc/blsgpu_g1w.hip k_msm_horner_wide executes) run digit by digit, the multiplier's 64-bit column bounds and the stored-value
+csrc/blsgpu_msmw.hip k_msm_horner_wide<1, .> executes) run digit by digit, the multiplier's 64-bit column bounds and the stored-value
 range asserted, against the host's integer curve arithmetic (bls_py/hostmath.py): sum_i 2^(c i) P_i as the reference's
 double-and-add would give it (fields_t.py:705-740), including the inputs the complete formulas are there for -- points at
 infinity anywhere in the list, an addend equal to the running sum (a doubling inside the addition), an addend opposite to it."""

@@ -370,7 +370,7 @@ def test_batch_horner_on_lane_quads_workgroup_shapes(lane_engine, seeded_pairs):
 @pytest.fixture(scope="module", params=["tail_on_the_wide_machine", "tail_on_the_wavefront_vm"])
 def sorted_engine(request):
     """An engine whose single G1 sums with scalars use the sorted buckets (k_srt_*) from 1 point on -- once with the default tail
-    (window sums and the Horner over the windows on k_msm_horner_wide) and once with the wavefront VM's (k_srt_windows +
+    (window sums and the Horner over the windows on k_msm_horner_wide<1, .>) and once with the wavefront VM's (k_srt_windows +
     k_msm_pip_horner<1>, BLSGPU_MSM_WIDE_TAIL=0)."""
     if request.param == "tail_on_the_wavefront_vm":
         return _engine_with_values({"BLSGPU_MSM_SORT_THRESHOLD": "1", "BLSGPU_MSM_WIDE_TAIL": "0"})
@@ -532,7 +532,7 @@ def test_c5_full_size_distinct_points(engine, golden):
 @pytest.fixture(scope="module", params=["default_window_bits", "5_bit_windows", "11_bit_windows", "13_bit_windows"])
 def sorted_g2_engine(request):
     """The default selection sends every single G2 sum with scalars to the sorted buckets (k_srt_*<2> on lane pairs, the tail on
-    k_msm_horner_wide2); the window width follows the size by default, the other rows pin it (every fold shape of the tail)."""
+    k_msm_horner_wide<2, .>); the window width follows the size by default, the other rows pin it (every fold shape of the tail)."""
     if request.param == "default_window_bits":
         return _engine_with_values({})
     return _engine_with_values({"BLSGPU_MSM_SORT2_BITS": request.param.split("_")[0]})

@@ -59,7 +59,7 @@ def test_infinity_and_opposite_encodings():
 
 
 def test_window_horner_of_a_g2_sum_on_the_same_tables():
-    """csrc/blsgpu_h2cw.hip k_msm_horner_wide2 (the tail of the sorted-bucket G2 sum: bls.py:225-261 as one multi-scalar sum):
+    """csrc/blsgpu_msmw.hip k_msm_horner_wide<2, .> (the tail of the sorted-bucket G2 sum: bls.py:225-261 as one multi-scalar sum):
     sum_i 2^(c i) P_i with infinity in the list, an addend equal to the running sum and one opposite to it"""
     import random
     rng = random.Random(5)
