@@ -71,7 +71,8 @@ int blsgpu_ctx_reserve(blsgpu_ctx *ctx, size_t max_pairs);
  * counterpart of the n-arrays of mpz_t the reference mallocs per call, fields_t_c.pyx:2348-2388).  out[BLSGPU_WS_TOTAL]
  * is the sum (which also counts the fixed-base G1 table and the HD derivation slice, blsgpu_g1_mul_gen /
  * blsgpu_hd_children, the per-path state of blsgpu_hd_paths, the commitments of blsgpu_g1_poly_check and the Lagrange
- * coefficients of blsgpu_threshold_combine / blsgpu_fr_interpolate_at_zero; they have no field of their own).
+ * coefficients of blsgpu_threshold_combine / blsgpu_fr_interpolate_at_zero, and the point tables of blsgpu_g2_mul_secret /
+ * blsgpu_sign; they have no field of their own).
  * BLSGPU_WS_FLAGS_AND_LISTS counts the flag copy of blsgpu_miller_loop_batch's fast form as well (2 bytes per pair of a
  * slice).  No device call is made. */
 enum { BLSGPU_WS_PARTIALS = 0, BLSGPU_WS_STAGING, BLSGPU_WS_LINES, BLSGPU_WS_LINE_PRODUCTS, BLSGPU_WS_FLAGS_AND_LISTS,
@@ -414,12 +415,48 @@ int blsgpu_threshold_combine(blsgpu_ctx *ctx, const uint8_t *sigs_affine, const 
 int blsgpu_threshold_combine_dev(blsgpu_ctx *ctx, const void *d_sigs_affine, const void *d_x, size_t k, size_t groups,
                                  void *d_out, void *d_out_inf, void *d_status, void *stream);
 
+/* G2 scalar multiplication for SECRET scalars:  out_i = s_i P_(n_pts == 1 ? 0 : i)  with a schedule independent of s
+ * (csrc/blsgpu_g2smul.hip k_g2_smul; vmgen/g2smul_model.py is its specification).  s_i is the literal 256-bit integer of
+ * 32 big-endian bytes, NOT reduced mod the group order -- exactly the `scalars` of blsgpu_g2_msm, whose results this call
+ * reproduces byte for byte.
+ * The claim is exactly this: the sequence of instructions and of memory addresses does not depend on the scalars.  One
+ * scalar per lane pair; signed 4-bit digits of s + C over 65 windows (plain carries); a table 1P .. 8P per scalar in the
+ * workspace (built once when n_pts == 1 and read by every pair); per window four complete doublings and one complete
+ * addition of an entry that is picked by reading all eight and keeping one by compare-and-select, its sign by a select
+ * between y and -y, a zero digit by the constant (0 : 1 : 0) -- nothing is skipped; an input (0, 0) enters as (0 : 1 : 0)
+ * by select; the affine conversion is the fixed-length branch-free safegcd inversion (37 x 30 division steps).
+ * NOT claimed: data-dependent timing inside the hardware (how long an instruction or a memory access takes for given
+ * values), and anything about the points -- in blsgpu_sign the message-dependent H(m), which is public.
+ * pts: n_pts x 192 bytes affine (x.c0 x.c1 y.c0 y.c1, (0, 0) = infinity; on the twist, the subgroup is not required).
+ * out_aff: n x 192 bytes ((0, 0) for infinity); out_ser: n x 96 bytes, Signature.serialize() (ec.py:94-111: x.c0 || x.c1
+ * with 0x80 on the first byte when the imaginary part of y exceeds q // 2; 96 zero bytes for infinity) -- the compression
+ * runs in the kernel; out_inf (may be NULL): n flags, 1 for infinity.  out_aff and out_ser may each be NULL, not both.
+ * n_pts must be 1 or n: anything else, a NULL input or both outputs NULL is -EINVAL before anything is written.  n == 0
+ * writes nothing and returns 0.  Calls are processed in slices of 65 536 scalars, which bounds the table workspace at
+ * 168 MiB (counted in BLSGPU_WS_TOTAL). */
+int blsgpu_g2_mul_secret(blsgpu_ctx *ctx, const uint8_t *pts, size_t n_pts, const uint8_t *scalars, size_t n,
+                         uint8_t *out_aff, uint8_t *out_ser, uint8_t *out_inf);
+/* The same with every buffer in device memory, enqueued on `stream` (no synchronisation). */
+int blsgpu_g2_mul_secret_dev(blsgpu_ctx *ctx, const void *d_pts, size_t n_pts, const void *d_scalars, size_t n,
+                             void *d_out_aff, void *d_out_ser, void *d_out_inf, void *stream);
+/* Signing, the device work of PrivateKey.sign_prehashed (keys.py:128-132 of the reference):
+ * sig_i = sk_i H(h_(n_msg == 1 ? 0 : i)).  sks: n x 32 bytes big-endian; msg_hashes: n_msg x 32 bytes.  The call enqueues
+ * blsgpu_hash_to_g2_dev into the workspace and then k_g2_smul on those points: nothing returns to the host in between, and
+ * the private keys meet only the scalar-independent schedule described above (same claim, same limits; H(m) is public).
+ * n_msg == 1: every key signs the same message (a committee, a threshold session) -- one hash, one shared table.
+ * out_aff / out_ser as in blsgpu_g2_mul_secret; n_msg must be 1 or n (-EINVAL before anything is written otherwise). */
+int blsgpu_sign(blsgpu_ctx *ctx, const uint8_t *sks, const uint8_t *msg_hashes, size_t n_msg, size_t n, uint8_t *out_aff,
+                uint8_t *out_ser);
+int blsgpu_sign_dev(blsgpu_ctx *ctx, const void *d_sks, const void *d_msg_hashes, size_t n_msg, size_t n, void *d_out_aff,
+                    void *d_out_ser, void *stream);
+
 /* Measurement aid (bench.py): when enabled, HIP events are recorded on the
  * launch stream around every kernel this context launches (up to 1024 launches
  * between reads).  blsgpu_timing_read waits for them and returns, per launch,
  * the duration in ms and the kernel kind: 0 = k_miller (Miller loops + workgroup
  * product), 1 = k_reduce (partial products), 2 = k_reduce with the final
- * exponentiation, 3 = k_miller_slow (degenerate pairs; empty work list normally).
+ * exponentiation, 3 = k_miller_slow (degenerate pairs; empty work list normally); the line-stream stages use 4 .. 7, and
+ * 8 = k_g2_smul with its table kernel (one record per blsgpu_g2_mul_secret / per slice of blsgpu_sign).
  * Reading resets the ring. */
 int blsgpu_timing_enable(blsgpu_ctx *ctx, int enable);
 int blsgpu_timing_read(blsgpu_ctx *ctx, float *ms, int *kind, size_t cap, size_t *count);

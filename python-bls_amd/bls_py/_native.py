@@ -32,6 +32,7 @@ SYMBOLS = (
     "blsgpu_g1_subgroup_check", "blsgpu_g1_subgroup_check_dev", "blsgpu_g2_subgroup_check", "blsgpu_g2_subgroup_check_dev",
     "blsgpu_lagrange_at_zero", "blsgpu_lagrange_at_zero_dev", "blsgpu_fr_interpolate_at_zero", "blsgpu_fr_interpolate_at_zero_dev",
     "blsgpu_threshold_combine", "blsgpu_threshold_combine_dev",
+    "blsgpu_g2_mul_secret", "blsgpu_g2_mul_secret_dev", "blsgpu_sign", "blsgpu_sign_dev",
 )
 
 HD_PARENT_BYTES = 160          # BLSGPU_HD_PARENT_BYTES: chain code (32), public key affine (96), private key (32)
@@ -132,6 +133,10 @@ def load_library(path=None):
         L.blsgpu_fr_interpolate_at_zero_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
         L.blsgpu_threshold_combine.argtypes = [vp, cp, cp, sz, sz, vp, vp, vp]
         L.blsgpu_threshold_combine_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
+        L.blsgpu_g2_mul_secret.argtypes = [vp, cp, sz, cp, sz, vp, vp, vp]
+        L.blsgpu_g2_mul_secret_dev.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp, vp]
+        L.blsgpu_sign.argtypes = [vp, cp, cp, sz, sz, vp, vp]
+        L.blsgpu_sign_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
         L.blsgpu_timing_enable.argtypes = [vp, ctypes.c_int]
         L.blsgpu_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int), sz,
                                          ctypes.POINTER(sz)]
@@ -543,6 +548,44 @@ class Engine:
     def threshold_combine_dev(self, d_sigs, d_x, k, groups, d_out, d_out_inf, d_status, stream=0):
         self._check(self.lib.blsgpu_threshold_combine_dev(self.h, d_sigs, d_x, k, groups, d_out, d_out_inf, d_status, stream),
                     "blsgpu_threshold_combine_dev")
+
+    def g2_mul_secret(self, pts, scalars, aff=True, ser=True):
+        """s_i P_i (or s_i P for ONE point of 192 bytes) for n scalars (n x 32 bytes big-endian, or ints below 2^256, taken as
+        they are) on the scalar-independent schedule of blsgpu_g2_mul_secret.
+        -> (n x 192 affine bytes or None, n x 96 serialised bytes or None, [is_infinity])"""
+        sb = scalars if isinstance(scalars, (bytes, bytearray)) else b"".join(int(s).to_bytes(32, "big") for s in scalars)
+        if len(sb) % 32 or len(pts) % 192:
+            raise ValueError("need n x 32 scalar bytes and points of 192 bytes")
+        n, n_pts = len(sb) // 32, len(pts) // 192
+        if not (aff or ser):
+            raise ValueError("ask for at least one output")
+        oa = ctypes.create_string_buffer(max(1, 192 * n)) if aff else None
+        os_ = ctypes.create_string_buffer(max(1, 96 * n)) if ser else None
+        inf = ctypes.create_string_buffer(max(1, n))
+        self._check(self.lib.blsgpu_g2_mul_secret(self.h, bytes(pts), n_pts, bytes(sb), n, oa, os_, inf), "blsgpu_g2_mul_secret")
+        return (oa.raw[:192 * n] if aff else None), (os_.raw[:96 * n] if ser else None), [bool(b) for b in inf.raw[:n]]
+
+    def sign(self, sks, msg_hashes, aff=True, ser=True):
+        """sk_i H(h_i) (or sk_i H(h) for ONE hash of 32 bytes) for n private keys (n x 32 bytes big-endian, or ints): the hash
+        to G2 and the scalar-independent multiplication in one call (blsgpu_sign).
+        -> (n x 192 affine bytes or None, n x 96 bytes of Signature.serialize() or None)"""
+        sb = sks if isinstance(sks, (bytes, bytearray)) else b"".join(int(s).to_bytes(32, "big") for s in sks)
+        if len(sb) % 32 or len(msg_hashes) % 32:
+            raise ValueError("need n x 32 key bytes and hashes of 32 bytes")
+        n, n_msg = len(sb) // 32, len(msg_hashes) // 32
+        if not (aff or ser):
+            raise ValueError("ask for at least one output")
+        oa = ctypes.create_string_buffer(max(1, 192 * n)) if aff else None
+        os_ = ctypes.create_string_buffer(max(1, 96 * n)) if ser else None
+        self._check(self.lib.blsgpu_sign(self.h, bytes(sb), bytes(msg_hashes), n_msg, n, oa, os_), "blsgpu_sign")
+        return (oa.raw[:192 * n] if aff else None), (os_.raw[:96 * n] if ser else None)
+
+    def g2_mul_secret_dev(self, d_pts, n_pts, d_scalars, n, d_out_aff, d_out_ser, d_out_inf=None, stream=0):
+        self._check(self.lib.blsgpu_g2_mul_secret_dev(self.h, d_pts, n_pts, d_scalars, n, d_out_aff, d_out_ser, d_out_inf, stream),
+                    "blsgpu_g2_mul_secret_dev")
+
+    def sign_dev(self, d_sks, d_msg_hashes, n_msg, n, d_out_aff, d_out_ser, stream=0):
+        self._check(self.lib.blsgpu_sign_dev(self.h, d_sks, d_msg_hashes, n_msg, n, d_out_aff, d_out_ser, stream), "blsgpu_sign_dev")
 
     def timing_enable(self, on=True):
         self._check(self.lib.blsgpu_timing_enable(self.h, int(on)), "blsgpu_timing_enable")

@@ -91,6 +91,16 @@ class HipProvider:
         """-> (groups x 192 affine bytes: sum_j L_j sig_j, [is_infinity], groups status bytes)"""
         return self._eng.threshold_combine(sigs, x, k, groups)
 
+    def g2_mul_secret(self, pts: bytes, scalars, aff: bool = True, ser: bool = True):
+        """s_i P_i (one point of 192 bytes: s_i P) on the scalar-independent schedule
+        -> (n x 192 affine bytes, n x 96 serialised bytes, [is_infinity])"""
+        return self._eng.g2_mul_secret(pts, scalars, aff, ser)
+
+    def sign(self, sks, msg_hashes: bytes, aff: bool = True, ser: bool = True):
+        """sk_i H(h_i) (one hash of 32 bytes: sk_i H(h)): hash to G2 and the scalar-independent multiplication in one call
+        -> (n x 192 affine bytes, n x 96 bytes of Signature.serialize())"""
+        return self._eng.sign(sks, msg_hashes, aff, ser)
+
     # ---- the whole of BLS.verify's device work without a host round trip between its steps (bls.py:153-201) ----
     def verify_pipeline(self, neg_g1: bytes, sig: bytes, hashes: bytes, n: int, keys_affine=None, key_pts=None, key_scalars=None, k=0) -> bytes:
         """e(-G1, sig) * prod_i e(P_i, H(m_i)) for n message hashes (32 bytes each): blsgpu_verify_pipeline -- ONE upload,

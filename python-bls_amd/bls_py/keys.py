@@ -219,6 +219,58 @@ class PrivateKey:
     def sign_prehashed(self, h):
         return PrivateKey._sign_hashes([self], [h])[0]
 
+    @staticmethod
+    def _sign_device(private_keys, hashes, aff, ser):
+        """blsgpu_sign for the keys and their 32-byte hashes (a list with one entry per key, or ONE bytes object: every key
+        signs it) -> (keys, hashes per key, affine bytes or None, serialised bytes or None)"""
+        from . import backend
+        sks = list(private_keys)
+        if isinstance(hashes, (bytes, bytearray)):
+            per_key, flat = [bytes(hashes)] * len(sks), bytes(hashes)
+        else:
+            per_key = [bytes(h) for h in hashes]
+            if len(per_key) != len(sks):
+                raise ValueError("one message per key")
+            flat = b"".join(per_key)
+        if any(len(h) != 32 for h in per_key) or (sks and len(flat) not in (32, 32 * len(sks))):
+            raise ValueError("message hashes are 32 bytes")
+        if not sks:
+            return sks, per_key, b"", b""
+        out_aff, out_ser = backend.get().sign(b"".join(sk.serialize() for sk in sks), flat, aff, ser)
+        return sks, per_key, out_aff, out_ser
+
+    @staticmethod
+    def sign_prehashed_serialized_batch(private_keys, hashes):
+        """[sk.sign_prehashed(h).serialize() for sk, h in zip(private_keys, hashes)] as 96-byte strings, in one GPU call
+        (blsgpu_sign): hash to G2, the multiplication by the key on a schedule that does not depend on the key, and the
+        compression all run on the device; no point object is built.  hashes: one 32-byte hash per key, or ONE bytes
+        object that every key signs (a committee or threshold session: one hash, one shared table)."""
+        _, _, _, ser = PrivateKey._sign_device(private_keys, hashes, False, True)
+        return [ser[96 * i:96 * (i + 1)] for i in range(len(ser) // 96)]
+
+    @staticmethod
+    def sign_serialized_batch(private_keys, messages):
+        """[sk.sign(m).serialize() for sk, m in zip(private_keys, messages)] as 96-byte strings (see
+        sign_prehashed_serialized_batch); messages: one per key, or ONE bytes object that every key signs."""
+        if isinstance(messages, (bytes, bytearray)):
+            return PrivateKey.sign_prehashed_serialized_batch(private_keys, hash256(bytes(messages)))
+        return PrivateKey.sign_prehashed_serialized_batch(private_keys, [hash256(m) for m in messages])
+
+    @staticmethod
+    def sign_batch_uniform(private_keys, messages):
+        """The Signature objects of sign_batch(private_keys, messages), AggregationInfo included, with the signature points
+        from blsgpu_sign: the private keys meet only the scalar-independent G2 schedule there.  The public keys of the
+        AggregationInfo come from get_public_key_batch: the fixed-base G1 table is indexed by the digits of the key and
+        stays so -- that half is NOT scalar-independent (a uniform fixed-base form is a change of its own)."""
+        hashes = [hash256(m) for m in messages]
+        sks, hashes, aff, _ = PrivateKey._sign_device(private_keys, hashes, True, False)
+        pks = PrivateKey.get_public_key_batch(sks)
+        out = []
+        for i, (pk, h) in enumerate(zip(pks, hashes)):
+            sig = JacobianPoint._from(H.F2, H.aff_to_jac(H.F2, H.g2_from_abi(aff[192 * i:192 * (i + 1)])), default_ec_twist)
+            out.append(Signature.from_g2(sig, AggregationInfo.from_msg_hash(pk, h)))
+        return out
+
     def sign_threshold(self, m, player, players):
         from .threshold import Threshold
         assert player in players

@@ -25,6 +25,7 @@
 #include "blsgpu_g1poly.hip"
 #include "blsgpu_subgroup.hip"
 #include "blsgpu_lagrange.hip"
+#include "blsgpu_g2smul.hip"
 #include "blsgpu_h2c.hip"
 #include "blsgpu_h2cw.hip"
 #include "blsgpu_msmw.hip"
@@ -1912,6 +1913,110 @@ BLSGPU_EXPORT int blsgpu_map_to_g2(blsgpu_ctx* c, const uint8_t* t, size_t n, ui
     if (int rc = s.up()) return rc;
     if (int rc = blsgpu_map_to_g2_dev(c, s.at(din), n, s.at(dout), nullptr)) return rc;
     return s.down();
+}
+
+// ------------------------------------------------------------ G2 multiplication by secret scalars, signing (blsgpu_g2smul.hip) --
+// enqueues out_i = s_i P_(n_pts == 1 ? 0 : i) on `st` in slices of g2smul::SLICE scalars (caller: StreamGuard); table: room for
+// the tables of one slice (of one point when n_pts == 1: built once, read by every slice)
+static int g2_smul_launch(blsgpu_ctx* c, const void* d_pts, size_t n_pts, const void* d_scalars, size_t n, void* d_out_aff, void* d_out_ser,
+                          void* d_out_inf, uint32_t* table, hipStream_t st) {
+    using namespace blsgpu::g2smul;
+    const bool shared = n_pts == 1;
+    KernelTimer kt(c, st, 8);
+    if (shared) {
+        hipLaunchKernelGGL(k_g2_smul_table, dim3(1), dim3(256), 0, st, (const uint32_t*)d_pts, 1u, table);
+        HIP_TRY(hipGetLastError());
+    }
+    return for_slices(n, SLICE, [&](size_t lo, size_t m) {
+        const unsigned blocks = (unsigned)((m + PAIRS - 1) / PAIRS);
+        if (!shared) hipLaunchKernelGGL(k_g2_smul_table, dim3(blocks), dim3(256), 0, st, (const uint32_t*)d_pts + lo * 48, (uint32_t)m, table);
+        hipLaunchKernelGGL(k_g2_smul, dim3(blocks), dim3(256), 0, st, (const uint32_t*)table, shared ? 2u : (uint32_t)(2 * m), shared ? 1u : 0u,
+                           (const uint32_t*)d_scalars + lo * 8, (uint32_t)m, d_out_aff ? (uint32_t*)d_out_aff + lo * 48 : nullptr,
+                           d_out_ser ? (uint32_t*)d_out_ser + lo * 24 : nullptr, d_out_inf ? (uint8_t*)d_out_inf + lo : nullptr);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    });
+}
+static size_t g2_smul_tables(size_t n_pts, size_t n) {            // points whose tables are held at a time
+    return n_pts == 1 ? 1 : (n < blsgpu::g2smul::SLICE ? n : blsgpu::g2smul::SLICE);
+}
+static int g2_smul_args(size_t n_sel, size_t n, const void* a, const void* b, const void* out_aff, const void* out_ser, const char* what) {
+    if (n_sel != 1 && n_sel != n) return fail(-EINVAL, std::string(what) + " must be 1 or n");
+    if (!a || !b) return fail(-EINVAL, "NULL argument");
+    if (!out_aff && !out_ser) return fail(-EINVAL, "out_aff and out_ser are both NULL");
+    if (n > 0xFFFFFFF0ull) return fail(-EINVAL, "batch too large");
+    return 0;
+}
+
+BLSGPU_EXPORT int blsgpu_g2_mul_secret_dev(blsgpu_ctx* c, const void* d_pts, size_t n_pts, const void* d_scalars, size_t n, void* d_out_aff,
+                                           void* d_out_ser, void* d_out_inf, void* stream) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (n == 0) return 0;
+    if (int rc = g2_smul_args(n_pts, n, d_pts, d_scalars, d_out_aff, d_out_ser, "n_pts")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    StreamGuard sg(c, (hipStream_t)stream);
+    if (int rc = c->grow(B_SMUL_WS, g2_smul_tables(n_pts, n) * blsgpu::g2smul::TABLE_DW * 4)) return rc;
+    return g2_smul_launch(c, d_pts, n_pts, d_scalars, n, d_out_aff, d_out_ser, d_out_inf, c->at<uint32_t>(B_SMUL_WS), (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_g2_mul_secret(blsgpu_ctx* c, const uint8_t* pts, size_t n_pts, const uint8_t* scalars, size_t n, uint8_t* out_aff,
+                                       uint8_t* out_ser, uint8_t* out_inf) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (n == 0) return 0;
+    if (int rc = g2_smul_args(n_pts, n, pts, scalars, out_aff, out_ser, "n_pts")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t S = n < blsgpu::g2smul::SLICE ? n : blsgpu::g2smul::SLICE;
+    const bool per = n_pts != 1;
+    Staging s(c);
+    const int dp = per ? s.in(pts, S, 192) : s.in(pts, 192), dsc = s.in(scalars, S, 32), daff = s.out(out_aff, S, 192),
+              dser = s.out(out_ser, S, 96), dinf = s.out(out_inf, S, 1);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    return for_slices(n, S, [&](size_t lo, size_t m) {
+        if (int rc = s.up(lo, m)) return rc;
+        if (int rc = blsgpu_g2_mul_secret_dev(c, s.at(dp), per ? m : 1, s.at(dsc), m, s.opt(daff), s.opt(dser), s.opt(dinf), nullptr)) return rc;
+        return s.down(lo, m);
+    });
+}
+
+// PrivateKey.sign_prehashed's device work: the hash to G2 of a slice of messages into the workspace, then k_g2_smul on
+// those points; one message (n_msg == 1) is hashed once and its table shared
+BLSGPU_EXPORT int blsgpu_sign_dev(blsgpu_ctx* c, const void* d_sks, const void* d_msg_hashes, size_t n_msg, size_t n, void* d_out_aff,
+                                  void* d_out_ser, void* stream) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (n == 0) return 0;
+    if (int rc = g2_smul_args(n_msg, n, d_sks, d_msg_hashes, d_out_aff, d_out_ser, "n_msg")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t held = g2_smul_tables(n_msg, n), pts_bytes = (held * BLSGPU_G2_BYTES + 255) & ~(size_t)255;
+    if (int rc = c->grow(B_SMUL_WS, pts_bytes + held * blsgpu::g2smul::TABLE_DW * 4)) return rc;
+    char* d_hm = c->at<char>(B_SMUL_WS);
+    uint32_t* table = (uint32_t*)(d_hm + pts_bytes);
+    return for_slices(n, n_msg == 1 ? n : held, [&](size_t lo, size_t m) {
+        const size_t msgs = n_msg == 1 ? 1 : m;
+        if (int rc = map_to_g2_impl(c, (const char*)d_msg_hashes + (n_msg == 1 ? 0 : lo * 32), msgs, d_hm, st, true)) return rc;
+        StreamGuard sg(c, st);
+        return g2_smul_launch(c, d_hm, msgs, (const char*)d_sks + lo * 32, m, d_out_aff ? (char*)d_out_aff + lo * BLSGPU_G2_BYTES : nullptr,
+                              d_out_ser ? (char*)d_out_ser + lo * 96 : nullptr, nullptr, table, st);
+    });
+}
+BLSGPU_EXPORT int blsgpu_sign(blsgpu_ctx* c, const uint8_t* sks, const uint8_t* msg_hashes, size_t n_msg, size_t n, uint8_t* out_aff,
+                              uint8_t* out_ser) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (n == 0) return 0;
+    if (int rc = g2_smul_args(n_msg, n, sks, msg_hashes, out_aff, out_ser, "n_msg")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t S = n < blsgpu::g2smul::SLICE ? n : blsgpu::g2smul::SLICE;
+    const bool per = n_msg != 1;
+    Staging s(c);
+    const int dsk = s.in(sks, S, 32), dh = per ? s.in(msg_hashes, S, 32) : s.in(msg_hashes, 32), daff = s.out(out_aff, S, 192),
+              dser = s.out(out_ser, S, 96);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    return for_slices(n, S, [&](size_t lo, size_t m) {
+        if (int rc = s.up(lo, m)) return rc;
+        if (int rc = blsgpu_sign_dev(c, s.at(dsk), s.at(dh), per ? m : 1, m, s.opt(daff), s.opt(dser), nullptr)) return rc;
+        return s.down(lo, m);
+    });
 }
 
 // ------------------------------------------------------------ decompression --
