@@ -71,15 +71,16 @@ int blsgpu_ctx_reserve(blsgpu_ctx *ctx, size_t max_pairs);
  * counterpart of the n-arrays of mpz_t the reference mallocs per call, fields_t_c.pyx:2348-2388).  out[BLSGPU_WS_TOTAL]
  * is the sum (which also counts the fixed-base G1 table and the HD derivation slice, blsgpu_g1_mul_gen /
  * blsgpu_hd_children, the per-path state of blsgpu_hd_paths, the commitments of blsgpu_g1_poly_check and the Lagrange
- * coefficients of blsgpu_threshold_combine / blsgpu_fr_interpolate_at_zero, and the point tables of blsgpu_g2_mul_secret /
- * blsgpu_sign; they have no field of their own).
+ * coefficients of blsgpu_threshold_combine / blsgpu_fr_interpolate_at_zero, the table of blsgpu_g1_mul_gen_secret, and the
+ * point tables of blsgpu_g2_mul_secret / blsgpu_sign; they have no field of their own).
  * BLSGPU_WS_FLAGS_AND_LISTS counts the flag copy of blsgpu_miller_loop_batch's fast form as well (2 bytes per pair of a
  * slice).  No device call is made. */
 enum { BLSGPU_WS_PARTIALS = 0, BLSGPU_WS_STAGING, BLSGPU_WS_LINES, BLSGPU_WS_LINE_PRODUCTS, BLSGPU_WS_FLAGS_AND_LISTS,
        BLSGPU_WS_GROUP_SUMS, BLSGPU_WS_SLOTS, BLSGPU_WS_TOTAL, BLSGPU_WS_FIELDS };
 int blsgpu_ctx_workspace_bytes(blsgpu_ctx *ctx, size_t out[BLSGPU_WS_FIELDS]);
 /* Wait for the context's enqueued work and free the buffers that larger ones replaced.  The fixed-base G1 table of
- * blsgpu_g1_mul_gen stays (0.9 MB, built once): blsgpu_ctx_destroy frees it. */
+ * blsgpu_g1_mul_gen stays (0.9 MB, built once), and so does the 58 KB table of blsgpu_g1_mul_gen_secret: blsgpu_ctx_destroy
+ * frees them. */
 int blsgpu_ctx_trim(blsgpu_ctx *ctx);
 /* Batches of at least `pairs` pairs run the throughput-oriented Miller kernel
  * (several pairs per wavefront sharing one accumulator); smaller batches the
@@ -289,7 +290,8 @@ int blsgpu_g2_decompress_dev(blsgpu_ctx *ctx, const void *d_in, size_t n, void *
  * big-endian, any value below 2^256 (reduced mod the group order on the device: the same point); its product is a sum of
  * 32 entries of a table of d 2^(8w) G1 (8-bit windows, 0.9 MB) that the context builds on first use and keeps until
  * blsgpu_ctx_destroy -- no doubling, one inversion per scalar (csrc/blsgpu_g1fix.hip).  The table is indexed by the
- * scalar's digits: NOT constant-time (nor is the variable-base path of blsgpu_g1_msm).
+ * scalar's digits: NOT constant-time (nor is the variable-base path of blsgpu_g1_msm); blsgpu_g1_mul_gen_secret below is
+ * the form for private keys.
  * add: NULL (n_add = 0), one point added to every product (n_add = 1) or one per scalar (n_add = n); 96 bytes affine,
  * (0, 0) = infinity.  out_aff: n x 96 bytes affine ((0, 0) for infinity); out_ser: n x 48 bytes, PublicKey.serialize()
  * (ec.py:94-111: x big-endian with 0x80 when y > q // 2; 48 zero bytes for infinity); either may be NULL, not both.
@@ -298,6 +300,24 @@ int blsgpu_g1_mul_gen(blsgpu_ctx *ctx, const uint8_t *scalars, size_t n, const u
                       uint8_t *out_ser);
 int blsgpu_g1_mul_gen_dev(blsgpu_ctx *ctx, const void *d_scalars, size_t n, const void *d_add, size_t n_add, void *d_out_aff,
                           void *d_out_ser, void *stream);
+/* The same product for SECRET scalars (a private key's public key):  out_i = s_i G1  with a schedule independent of s
+ * (csrc/blsgpu_g1fix.hip k_fix_mul_secret; vmgen/g1fixs_model.py is its specification).  s_i is the literal 256-bit integer
+ * of 32 big-endian bytes; G1 has order n, so the bytes equal those of blsgpu_g1_mul_gen.  There is no `add`: the added
+ * point belongs to public derivation.
+ * The claim is exactly that of blsgpu_g2_mul_secret: the sequence of instructions and of memory addresses does not depend
+ * on the scalars.  One scalar per lane; signed 4-bit digits of s + C over 65 windows (plain carries); a second per-context
+ * table of (e + 1) 16^w G1, w < 65, e < 8 (affine, 58 240 bytes, built on first use, kept until blsgpu_ctx_destroy, counted
+ * in BLSGPU_WS_TOTAL only); per window every lane reads all eight entries -- the address depends on the window alone --
+ * keeps one by compare-and-select, its sign by a select between y and -y, and runs one complete mixed addition; for a zero
+ * digit entry 0 is added all the same and the old accumulator kept by select.  65 additions, no doubling, nothing skipped;
+ * the affine conversion is the fixed-length branch-free inversion.  NOT claimed: data-dependent timing inside the hardware
+ * (how long an instruction or a memory access takes for given values).
+ * out_aff / out_ser as in blsgpu_g1_mul_gen: each may be NULL, not both.  A NULL input or both outputs NULL with n > 0 is
+ * -EINVAL before anything is written; n == 0 writes nothing and returns 0. */
+int blsgpu_g1_mul_gen_secret(blsgpu_ctx *ctx, const uint8_t *scalars, size_t n, uint8_t *out_aff, uint8_t *out_ser);
+/* The same with every buffer in device memory, enqueued on `stream` (no synchronisation). */
+int blsgpu_g1_mul_gen_secret_dev(blsgpu_ctx *ctx, const void *d_scalars, size_t n, void *d_out_aff, void *d_out_ser,
+                                 void *stream);
 
 /* HD child derivation of n siblings of one parent (keys.py:167-316 of the reference): for every index i,
  * i_left = hmac256(ser || be32(i) || 0, chain_code), i_right = hmac256(ser || be32(i) || 1, chain_code) (util.hmac256;
@@ -337,7 +357,7 @@ int blsgpu_hd_children_dev(blsgpu_ctx *ctx, const uint8_t chain_code[32], const 
  * reference stores in the child (PublicKey.get_fingerprint, keys.py:47-49); for depth == 1 that of the input parent.
  * -EINVAL before anything is written: depth == 0 or > 255, n_parents == 0 with n > 0, a NULL required buffer, a parent_of
  * entry >= n_parents, and in public mode an index >= 2^31 at any level ("Cannot derive hardened children from public
- * key").  n == 0 writes nothing.  Not constant-time. */
+ * key").  n == 0 writes nothing.  Not constant-time (private keys: blsgpu_hd_paths_secret below). */
 #define BLSGPU_HD_PARENT_BYTES 160
 int blsgpu_hd_paths(blsgpu_ctx *ctx, const uint8_t *parents, size_t n_parents, int priv, const uint32_t *parent_of,
                     const uint32_t *indices, size_t depth, size_t n, uint8_t *out_chain, uint8_t *out_sk, uint8_t *out_pk_aff,
@@ -348,6 +368,18 @@ int blsgpu_hd_paths(blsgpu_ctx *ctx, const uint8_t *parents, size_t n_parents, i
 int blsgpu_hd_paths_dev(blsgpu_ctx *ctx, const void *d_parents, size_t n_parents, int priv, const void *d_parent_of,
                         const void *d_indices, size_t depth, size_t n, void *d_out_chain, void *d_out_sk, void *d_out_pk_aff,
                         void *d_out_pk_ser, void *d_out_parent_fp, void *stream);
+/* blsgpu_hd_paths in private mode for SECRET keys: the same arguments without `priv`, the same validation and the same
+ * outputs, byte for byte.  Every level's child key comes from k_fix_mul_secret (blsgpu_g1_mul_gen_secret above), and
+ * i_left mod n and (i_left + sk) mod n keep their subtraction by a mask instead of a branch on the borrow.  The claim and
+ * its limits are those of blsgpu_g1_mul_gen_secret: the sequence of instructions and of memory addresses does not depend on
+ * the keys (it does depend on the indices, which are public: a hardened index takes the private key as HMAC message);
+ * timing inside the hardware is not claimed.  One parent with depth 1 is the secret form of blsgpu_hd_children. */
+int blsgpu_hd_paths_secret(blsgpu_ctx *ctx, const uint8_t *parents, size_t n_parents, const uint32_t *parent_of,
+                           const uint32_t *indices, size_t depth, size_t n, uint8_t *out_chain, uint8_t *out_sk,
+                           uint8_t *out_pk_aff, uint8_t *out_pk_ser, uint8_t *out_parent_fp);
+int blsgpu_hd_paths_secret_dev(blsgpu_ctx *ctx, const void *d_parents, size_t n_parents, const void *d_parent_of,
+                               const void *d_indices, size_t depth, size_t n, void *d_out_chain, void *d_out_sk,
+                               void *d_out_pk_aff, void *d_out_pk_ser, void *d_out_parent_fp, void *stream);
 
 /* Feldman share check (Threshold.verify_secret_fragment, threshold.py:104-125 of the reference) for n fragments at once.
  * commit: n_polys x t affine G1 points (96 B, (0,0) = infinity; caller guarantees on-curve);
@@ -456,7 +488,8 @@ int blsgpu_sign_dev(blsgpu_ctx *ctx, const void *d_sks, const void *d_msg_hashes
  * the duration in ms and the kernel kind: 0 = k_miller (Miller loops + workgroup
  * product), 1 = k_reduce (partial products), 2 = k_reduce with the final
  * exponentiation, 3 = k_miller_slow (degenerate pairs; empty work list normally); the line-stream stages use 4 .. 7, and
- * 8 = k_g2_smul with its table kernel (one record per blsgpu_g2_mul_secret / per slice of blsgpu_sign).
+ * 8 = k_g2_smul with its table kernel (one record per blsgpu_g2_mul_secret / per slice of blsgpu_sign),
+ * 9 = k_fix_mul_secret (one record per blsgpu_g1_mul_gen_secret_dev call / per level of blsgpu_hd_paths_secret).
  * Reading resets the ring. */
 int blsgpu_timing_enable(blsgpu_ctx *ctx, int enable);
 int blsgpu_timing_read(blsgpu_ctx *ctx, float *ms, int *kind, size_t cap, size_t *count);

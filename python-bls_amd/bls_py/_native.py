@@ -33,6 +33,7 @@ SYMBOLS = (
     "blsgpu_lagrange_at_zero", "blsgpu_lagrange_at_zero_dev", "blsgpu_fr_interpolate_at_zero", "blsgpu_fr_interpolate_at_zero_dev",
     "blsgpu_threshold_combine", "blsgpu_threshold_combine_dev",
     "blsgpu_g2_mul_secret", "blsgpu_g2_mul_secret_dev", "blsgpu_sign", "blsgpu_sign_dev",
+    "blsgpu_g1_mul_gen_secret", "blsgpu_g1_mul_gen_secret_dev", "blsgpu_hd_paths_secret", "blsgpu_hd_paths_secret_dev",
 )
 
 HD_PARENT_BYTES = 160          # BLSGPU_HD_PARENT_BYTES: chain code (32), public key affine (96), private key (32)
@@ -137,6 +138,10 @@ def load_library(path=None):
         L.blsgpu_g2_mul_secret_dev.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp, vp]
         L.blsgpu_sign.argtypes = [vp, cp, cp, sz, sz, vp, vp]
         L.blsgpu_sign_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
+        L.blsgpu_g1_mul_gen_secret.argtypes = [vp, cp, sz, vp, vp]
+        L.blsgpu_g1_mul_gen_secret_dev.argtypes = [vp, vp, sz, vp, vp, vp]
+        L.blsgpu_hd_paths_secret.argtypes = [vp, cp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp]
+        L.blsgpu_hd_paths_secret_dev.argtypes = [vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp]
         L.blsgpu_timing_enable.argtypes = [vp, ctypes.c_int]
         L.blsgpu_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int), sz,
                                          ctypes.POINTER(sz)]
@@ -382,6 +387,25 @@ class Engine:
         self._check(self.lib.blsgpu_g1_mul_gen(self.h, bytes(sb), n, bytes(add) if n_add else None, n_add, oa, os_), "blsgpu_g1_mul_gen")
         return (oa.raw[:96 * n] if aff else None), (os_.raw[:48 * n] if ser else None)
 
+    def g1_mul_gen_secret(self, scalars, aff=True, ser=True):
+        """s_i G1 for n SECRET scalars (n x 32 bytes big-endian, or ints below 2^256) on the scalar-independent schedule of
+        blsgpu_g1_mul_gen_secret; the bytes of g1_mul_gen.
+        -> (n x 96 affine bytes or None, n x 48 serialised bytes or None)"""
+        sb = scalars if isinstance(scalars, (bytes, bytearray)) else b"".join(int(s).to_bytes(32, "big") for s in scalars)
+        if len(sb) % 32:
+            raise ValueError("need n x 32 scalar bytes")
+        n = len(sb) // 32
+        if not (aff or ser):
+            raise ValueError("ask for at least one output")
+        oa = ctypes.create_string_buffer(max(1, 96 * n)) if aff else None
+        os_ = ctypes.create_string_buffer(max(1, 48 * n)) if ser else None
+        self._check(self.lib.blsgpu_g1_mul_gen_secret(self.h, bytes(sb), n, oa, os_), "blsgpu_g1_mul_gen_secret")
+        return (oa.raw[:96 * n] if aff else None), (os_.raw[:48 * n] if ser else None)
+
+    def g1_mul_gen_secret_dev(self, d_scalars, n, d_out_aff, d_out_ser, stream=0):
+        self._check(self.lib.blsgpu_g1_mul_gen_secret_dev(self.h, d_scalars, n, d_out_aff, d_out_ser, stream),
+                    "blsgpu_g1_mul_gen_secret_dev")
+
     def hd_children(self, chain_code, parent_pk_aff, parent_sk, indices, aff=True, ser=True):
         """HD children of one parent (blsgpu_hd_children): parent_sk None = public derivation.
         -> (n x 32 chain codes, n x 32 child keys or None, n x 96 affine keys or None, n x 48 serialised keys or None)"""
@@ -411,7 +435,18 @@ class Engine:
                                                     None if parent_sk is None else bytes(parent_sk), d_indices, n, d_out_chain,
                                                     d_out_sk, d_out_pk_aff, d_out_pk_ser, stream), "blsgpu_hd_children_dev")
 
-    def hd_paths(self, parents, priv, parent_of, paths, aff=True, ser=True, fp=True):
+    def hd_paths_secret(self, parents, parent_of, paths, aff=True, ser=True, fp=True):
+        """hd_paths in private mode on the scalar-independent schedule (blsgpu_hd_paths_secret): the same arguments without
+        `priv`, the same outputs."""
+        return self.hd_paths(parents, True, parent_of, paths, aff, ser, fp, secret=True)
+
+    def hd_paths_secret_dev(self, d_parents, n_parents, d_parent_of, d_indices, depth, n, d_out_chain, d_out_sk, d_out_pk_aff,
+                            d_out_pk_ser, d_out_parent_fp, stream=0):
+        self._check(self.lib.blsgpu_hd_paths_secret_dev(self.h, d_parents, n_parents, d_parent_of, d_indices, depth, n, d_out_chain,
+                                                        d_out_sk, d_out_pk_aff, d_out_pk_ser, d_out_parent_fp, stream),
+                    "blsgpu_hd_paths_secret_dev")
+
+    def hd_paths(self, parents, priv, parent_of, paths, aff=True, ser=True, fp=True, secret=False):
         """HD paths of one depth, a parent per path (blsgpu_hd_paths).  parents: n_parents x 160 bytes (chain code, affine
         public key, private key or 32 zero bytes); priv: private derivation; parent_of: n indices into parents, or None
         (every path starts at parent 0); paths: n sequences of `depth` child indices each.
@@ -437,8 +472,12 @@ class Engine:
         oa = ctypes.create_string_buffer(max(1, 96 * n)) if aff else None
         os_ = ctypes.create_string_buffer(max(1, 48 * n)) if ser else None
         of = ctypes.create_string_buffer(max(1, 4 * n)) if fp else None
-        self._check(self.lib.blsgpu_hd_paths(self.h, bytes(parents), len(parents) // HD_PARENT_BYTES, 1 if priv else 0, pof, idx, depth, n,
-                                             chain, sk, oa, os_, of), "blsgpu_hd_paths")
+        if secret:
+            self._check(self.lib.blsgpu_hd_paths_secret(self.h, bytes(parents), len(parents) // HD_PARENT_BYTES, pof, idx, depth, n,
+                                                        chain, sk, oa, os_, of), "blsgpu_hd_paths_secret")
+        else:
+            self._check(self.lib.blsgpu_hd_paths(self.h, bytes(parents), len(parents) // HD_PARENT_BYTES, 1 if priv else 0, pof, idx, depth, n,
+                                                 chain, sk, oa, os_, of), "blsgpu_hd_paths")
         return (chain.raw[:32 * n], sk.raw[:32 * n] if priv else None, oa.raw[:96 * n] if aff else None,
                 os_.raw[:48 * n] if ser else None, of.raw[:4 * n] if fp else None)
 

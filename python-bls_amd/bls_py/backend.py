@@ -60,6 +60,14 @@ class HipProvider:
         keys, n x 4 parent fingerprints) of the leaves"""
         return self._eng.hd_paths(parents, priv, parent_of, paths)
 
+    def g1_mul_gen_secret(self, scalars: bytes):
+        """s_i G1 on the scalar-independent schedule -> (n x 96 affine bytes, n x 48 serialised bytes)"""
+        return self._eng.g1_mul_gen_secret(scalars)
+
+    def hd_paths_secret(self, parents: bytes, parent_of, paths):
+        """hd_paths in private mode on the scalar-independent schedule: the same outputs"""
+        return self._eng.hd_paths_secret(parents, parent_of, paths)
+
     def g1_poly_check(self, commit: bytes, n_polys: int, t: int, poly, x: bytes, s=None, aff: bool = False):
         """Feldman share checks: -> (n status bytes: 1 (s_i mod n) G1 == sum_k x_i^k C[poly_i][k], 0 not, 2 poly_i has a
         C_k (k >= 1) outside the order-n subgroup; or None for s None) and the n x 96 affine Horner values (aff) or None"""
@@ -122,6 +130,8 @@ def use(provider):
     g1_subgroup / g2_subgroup(affine bytes) -> status bytes (1 in the subgroup, 2 on the curve outside it, 0 off it).
     Optional (a provider without it sends the HD *_path_batch / *_paths_from methods to chained hd_children calls):
     hd_paths(parents, priv, parent_of|None, paths of one depth) -> (chain codes, keys|None, affine, serialised, fingerprints).
+    Optional (the secret=True forms of the key methods raise without them; there is no other path for them):
+    g1_mul_gen_secret(scalars) -> (affine bytes, serialised bytes), hd_paths_secret(parents, parent_of|None, paths) -> as hd_paths.
     Optional (a provider without them sends the Threshold.*_batch methods to the host loop): LAGRANGE_MAX_K,
     lagrange_at_zero(x, k, groups) -> (coefficient bytes, status bytes), fr_interpolate_at_zero(x, y, k, groups) ->
     (32 bytes per group, status bytes), threshold_combine(sigs, x, k, groups) -> (affine bytes, [is_inf], status bytes)."""

@@ -160,14 +160,16 @@ class PrivateKey:
         return PublicKey.from_g1(pt)
 
     @staticmethod
-    def get_public_key_batch(private_keys):
+    def get_public_key_batch(private_keys, secret=False):
         """[sk.get_public_key() for sk in private_keys] in one GPU call on the fixed-base table (blsgpu_g1_mul_gen);
-        the keys come back with their serialisation."""
+        the keys come back with their serialisation.  secret=True: the same keys from blsgpu_g1_mul_gen_secret, whose
+        sequence of instructions and addresses does not depend on the private keys (a provider without it raises)."""
         from . import backend
         sks = list(private_keys)
         if not sks:
             return []
-        aff, ser = backend.get().g1_mul_gen(b"".join(sk.value.to_bytes(32, "big") for sk in sks), None, 0)
+        scalars = b"".join(sk.value.to_bytes(32, "big") for sk in sks)
+        aff, ser = _secret_call("g1_mul_gen_secret")(scalars) if secret else backend.get().g1_mul_gen(scalars, None, 0)
         return [_pk_from_device(aff[96 * i:96 * (i + 1)], ser[48 * i:48 * (i + 1)]) for i in range(len(sks))]
 
     def __setattr__(self, name, v):
@@ -257,14 +259,15 @@ class PrivateKey:
         return PrivateKey.sign_prehashed_serialized_batch(private_keys, [hash256(m) for m in messages])
 
     @staticmethod
-    def sign_batch_uniform(private_keys, messages):
+    def sign_batch_uniform(private_keys, messages, secret=False):
         """The Signature objects of sign_batch(private_keys, messages), AggregationInfo included, with the signature points
         from blsgpu_sign: the private keys meet only the scalar-independent G2 schedule there.  The public keys of the
-        AggregationInfo come from get_public_key_batch: the fixed-base G1 table is indexed by the digits of the key and
-        stays so -- that half is NOT scalar-independent (a uniform fixed-base form is a change of its own)."""
+        AggregationInfo come from get_public_key_batch: by default on the fixed-base G1 table that is indexed by the digits
+        of the key -- that half is NOT scalar-independent -- and with secret=True from blsgpu_g1_mul_gen_secret, so that
+        both halves run on schedules that do not depend on the keys."""
         hashes = [hash256(m) for m in messages]
         sks, hashes, aff, _ = PrivateKey._sign_device(private_keys, hashes, True, False)
-        pks = PrivateKey.get_public_key_batch(sks)
+        pks = PrivateKey.get_public_key_batch(sks, secret=secret)
         out = []
         for i, (pk, h) in enumerate(zip(pks, hashes)):
             sig = JacobianPoint._from(H.F2, H.aff_to_jac(H.F2, H.g2_from_abi(aff[192 * i:192 * (i + 1)])), default_ec_twist)
@@ -327,6 +330,16 @@ def _pk_from_device(aff, ser):
     return pk
 
 
+def _secret_call(name):
+    """the provider's scalar-independent form `name`; a provider without it raises -- secret=True never falls back to the
+    digit-indexed path"""
+    from . import backend
+    fn = getattr(backend.get(), name, None)
+    if fn is None:
+        raise NotImplementedError("the provider has no %s: secret=True needs the scalar-independent device path" % name)
+    return fn
+
+
 def _pk_affine(pk):
     return H.g1_affine_bytes(H.jac_to_affine(H.F1, pk.value._jac()))
 
@@ -340,7 +353,7 @@ def _child_indices(indices):
     return out
 
 
-def _derive_paths(parents, parent_of, paths, priv):
+def _derive_paths(parents, parent_of, paths, priv, secret=False):
     """The leaves of paths[j] from parents[parent_of[j]] (extended keys; private derivation: ExtendedPrivateKeys) as
     (parent, path, chain code, key bytes|None, affine, serialised, parent fingerprint) per path, in input order; None for
     an empty path.  The reference's exceptions are raised before any device work; paths are bucketed by length, one
@@ -362,22 +375,27 @@ def _derive_paths(parents, parent_of, paths, priv):
     if any(len(p) > room[a] for a, p in zip(parent_of, paths)):
         raise Exception("Cannot go further than 255 levels")
     prov = backend.get()
-    if not hasattr(prov, "hd_paths"):
+    if secret:
+        derive = _secret_call("hd_paths_secret")
+    elif not hasattr(prov, "hd_paths"):
         return None
+    else:
+        def derive(records, parent_of, paths):
+            return prov.hd_paths(records, priv, parent_of, paths)
     out = [None] * len(paths)
     lengths = sorted({len(p) for p in paths} - {0})
     if not lengths:
         return out
     if priv:
         cold = [k.private_key for k in parents if k.private_key.__dict__.get("_pk_point") is None]
-        for sk, pk in zip(cold, PrivateKey.get_public_key_batch(cold)):
+        for sk, pk in zip(cold, PrivateKey.get_public_key_batch(cold, secret=secret)):
             sk.__dict__["_pk_point"] = pk.value
         records = b"".join(k.chain_code + _pk_affine(k._public_key()) + k.private_key.serialize() for k in parents)
     else:
         records = b"".join(k.chain_code + _pk_affine(k.public_key) + bytes(32) for k in parents)
     for length in lengths:
         pos = range(len(paths)) if len(lengths) == 1 and all(paths) else [j for j, p in enumerate(paths) if len(p) == length]
-        chain, sks, aff, ser, fps = prov.hd_paths(records, priv, [parent_of[j] for j in pos], [paths[j] for j in pos])
+        chain, sks, aff, ser, fps = derive(records, [parent_of[j] for j in pos], [paths[j] for j in pos])
         for t, j in enumerate(pos):
             out[j] = (parents[parent_of[j]], paths[j], chain[32 * t:32 * t + 32], sks[32 * t:32 * t + 32] if priv else None,
                       aff[96 * t:96 * t + 96], ser[48 * t:48 * t + 48], int.from_bytes(fps[4 * t:4 * t + 4], "big"))
@@ -415,15 +433,18 @@ class ExtendedPrivateKey:
     def private_child(self, i):
         return self.private_child_batch([i])[0]
 
-    def private_child_batch(self, indices):
+    def private_child_batch(self, indices, secret=False):
         """[self.private_child(i) for i in indices] in one GPU call (blsgpu_hd_children, private mode); hardened and
-        non-hardened indices may be mixed."""
+        non-hardened indices may be mixed.  secret=True: the same children as paths of depth 1 on blsgpu_hd_paths_secret,
+        whose sequence of instructions and addresses does not depend on the keys."""
         from . import backend
         if self.depth >= 255:
             raise Exception("Cannot go further than 255 levels")
         idx = _child_indices(indices)
         if not idx:
             return []
+        if secret:
+            return ExtendedPrivateKey.private_paths_from([self], None, [[i] for i in idx], secret=True)
         pk = self.private_key.get_public_key()
         chain, sks, aff, ser = backend.get().hd_children(self.chain_code, _pk_affine(pk), self.private_key.serialize(), idx)
         fp = pk.get_fingerprint()
@@ -444,23 +465,25 @@ class ExtendedPrivateKey:
         """[self.public_child(i) for i in indices] in one GPU call"""
         return [c.get_extended_public_key() for c in self.private_child_batch(indices)]
 
-    def private_path_batch(self, paths):
+    def private_path_batch(self, paths, secret=False):
         """[the fold of private_child over p for p in paths]: whole paths, every level on the GPU, in one call per
         distinct path length (blsgpu_hd_paths, private mode).  Hardened and non-hardened indices may be mixed; an empty
-        path gives a key equal to self."""
+        path gives a key equal to self.  secret=True: on blsgpu_hd_paths_secret (see private_paths_from)."""
         paths = list(paths)
-        return ExtendedPrivateKey.private_paths_from([self], [0] * len(paths), paths)
+        return ExtendedPrivateKey.private_paths_from([self], [0] * len(paths), paths, secret=secret)
 
     def public_path_batch(self, paths):
         """[k.get_extended_public_key() for k in self.private_path_batch(paths)]"""
         return [c.get_extended_public_key() for c in self.private_path_batch(paths)]
 
     @staticmethod
-    def private_paths_from(parents, parent_of, paths):
+    def private_paths_from(parents, parent_of, paths, secret=False):
         """[the fold of private_child over paths[j] from parents[parent_of[j]]]: the paths of many parents in one GPU call
-        per distinct path length (blsgpu_hd_paths) -- the m/a/i grid is parent_of = [a ...], paths = [[i] ...]."""
+        per distinct path length (blsgpu_hd_paths) -- the m/a/i grid is parent_of = [a ...], paths = [[i] ...].
+        secret=True: every level on blsgpu_hd_paths_secret and the parents' own public keys on blsgpu_g1_mul_gen_secret --
+        the sequence of instructions and addresses does not depend on the keys; a provider without them raises."""
         parents, paths = list(parents), [list(p) for p in paths]
-        got = _derive_paths(parents, parent_of, paths, True)
+        got = _derive_paths(parents, parent_of, paths, True, secret)
         if parent_of is None:
             parent_of = [0] * len(paths)
         if got is None:

@@ -455,14 +455,19 @@ int msm_host(blsgpu_ctx* c, const uint8_t* pts, const uint8_t* scalars, size_t k
 constexpr size_t FIX_SLICE = (size_t)1 << 22;          // items per launch of the _dev forms
 constexpr size_t FIX_HOST_SLICE = (size_t)1 << 18;     // items per staged slice of the host-buffer forms (<= 76 MB of staging)
 
+// G1, ec.py:394-396 (little-endian words)
+blsgpu::g1fix::Gen g1_generator() {
+    return {{0xdb22c6bbu, 0xfb3af00au, 0xf97a1aefu, 0x6c55e83fu, 0x171bac58u, 0xa14e3a3fu, 0x9774b905u, 0xc3688c4fu, 0x4fa9ac0fu,
+                    0x2695638cu, 0x3197d794u, 0x17f1d3a7u},
+                   {0x46c5e7e1u, 0x0caa2329u, 0xa2888ae4u, 0xd03cc744u, 0x2c04b3edu, 0x00db18cbu, 0xd5d00af6u, 0xfcf5e095u, 0x741d8ae4u,
+                    0xa09e30edu, 0xe3aaa0f1u, 0x08b3f481u}};
+}
+
 // the table of d 2^(8w) G1, built on `st` the first time a context needs it
 int fix_table(blsgpu_ctx* c, hipStream_t st) {
     if (c->d_fix_table) return 0;
     using namespace blsgpu::g1fix;
-    const Gen g = {{0xdb22c6bbu, 0xfb3af00au, 0xf97a1aefu, 0x6c55e83fu, 0x171bac58u, 0xa14e3a3fu, 0x9774b905u, 0xc3688c4fu, 0x4fa9ac0fu,
-                    0x2695638cu, 0x3197d794u, 0x17f1d3a7u},
-                   {0x46c5e7e1u, 0x0caa2329u, 0xa2888ae4u, 0xd03cc744u, 0x2c04b3edu, 0x00db18cbu, 0xd5d00af6u, 0xfcf5e095u, 0x741d8ae4u,
-                    0xa09e30edu, 0xe3aaa0f1u, 0x08b3f481u}};      // G1, ec.py:394-396 (little-endian words)
+    const Gen g = g1_generator();
     void* p = nullptr;
     HIP_TRY(hipMalloc(&p, TABLE_BYTES));
     hipLaunchKernelGGL(k_fix_table, dim3((ENTRIES + 63) / 64), dim3(64), 0, st, g, (uint32_t*)p);
@@ -472,6 +477,22 @@ int fix_table(blsgpu_ctx* c, hipStream_t st) {
         return fail(-EIO, std::string("k_fix_table: ") + hipGetErrorString(e));
     }
     c->d_fix_table = (uint32_t*)p;
+    return 0;
+}
+
+// the table of (e + 1) 16^w G1 that k_fix_mul_secret reads whole, window by window; likewise
+int fix_table_secret(blsgpu_ctx* c, hipStream_t st) {
+    if (c->d_fix_table_secret) return 0;
+    using namespace blsgpu::g1fix;
+    void* p = nullptr;
+    HIP_TRY(hipMalloc(&p, S_TABLE_BYTES));
+    hipLaunchKernelGGL(k_fix_table_secret, dim3((S_ENTRIES + 63) / 64), dim3(64), 0, st, g1_generator(), (uint32_t*)p);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        return fail(-EIO, std::string("k_fix_table_secret: ") + hipGetErrorString(e));
+    }
+    c->d_fix_table_secret = (uint32_t*)p;
     return 0;
 }
 
@@ -494,6 +515,26 @@ int fix_mul_launch(blsgpu_ctx* c, const void* d_scalars, size_t n, const void* d
         HIP_TRY(hipGetLastError());
     }
     return 0;
+}
+
+// enqueues out_i = s_i G1 on the scalar-independent schedule on `st` (caller: StreamGuard, fix_table_secret)
+int fix_mul_secret_launch(blsgpu_ctx* c, const void* d_scalars, size_t n, void* d_out_aff, void* d_out_ser, hipStream_t st) {
+    KernelTimer kt(c, st, 9);
+    return for_slices(n, FIX_SLICE, [&](size_t lo, size_t m) {
+        hipLaunchKernelGGL(blsgpu::g1fix::k_fix_mul_secret, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
+                           (const uint32_t*)c->d_fix_table_secret, (const uint32_t*)d_scalars + lo * 8, (uint32_t)m,
+                           d_out_aff ? (uint32_t*)d_out_aff + lo * 24 : nullptr, d_out_ser ? (uint32_t*)d_out_ser + lo * 12 : nullptr);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    });
+}
+
+int g1_mul_gen_secret_dev(blsgpu_ctx* c, const void* d_scalars, size_t n, void* d_out_aff, void* d_out_ser, hipStream_t st) {
+    if (n == 0) return 0;
+    if (!d_scalars || (!d_out_aff && !d_out_ser)) return fail(-EINVAL, "NULL argument");
+    StreamGuard sg(c, st);
+    if (int rc = fix_table_secret(c, st)) return rc;
+    return fix_mul_secret_launch(c, d_scalars, n, d_out_aff, d_out_ser, st);
 }
 
 int g1_mul_gen_dev(blsgpu_ctx* c, const void* d_scalars, size_t n, const void* d_add, size_t n_add, void* d_out_aff, void* d_out_ser,
@@ -592,8 +633,10 @@ int hd_paths_args(const void* parents, size_t n_parents, int priv, const void* i
 // state in B_HDP_WS -- [0, 4) the flag of the scan, [256, ..) per path 32 bytes chain code, 32 bytes key (private) or i_left
 // (public), 96 bytes affine key, and in public mode 96 more (k_fix_mul reads the parent key while it writes the child's).
 // `check`: the device scan of parent_of and (public mode) the indices and one synchronising read of its flag first.
+// `secret` (private mode only, blsgpu_hd_paths_secret): k_hd_path_hmac_secret and k_fix_mul_secret in their places.
 int hd_paths_dev(blsgpu_ctx* c, const void* d_parents, size_t n_parents, int priv, const void* d_parent_of, const void* d_idx, size_t depth,
-                 size_t n, void* d_chain, void* d_sk, void* d_pk_aff, void* d_pk_ser, void* d_fp, bool check, hipStream_t st) {
+                 size_t n, void* d_chain, void* d_sk, void* d_pk_aff, void* d_pk_ser, void* d_fp, bool check, hipStream_t st,
+                 bool secret = false) {
     using namespace blsgpu::g1fix;
     if (n == 0) return 0;
     if (int rc = hd_paths_args(d_parents, n_parents, priv, d_idx, depth, n, d_chain, d_sk, d_pk_aff, d_pk_ser)) return rc;
@@ -612,7 +655,7 @@ int hd_paths_dev(blsgpu_ctx* c, const void* d_parents, size_t n_parents, int pri
         if (flag & 2u) return fail(-EINVAL, "parent index out of range");
         if (flag & 1u) return fail(-EINVAL, "Cannot derive hardened children from public key");
     }
-    if (int rc = fix_table(c, st)) return rc;
+    if (int rc = secret ? fix_table_secret(c, st) : fix_table(c, st)) return rc;
     uint32_t* ws_chain = (uint32_t*)(ws + 256);
     uint32_t* ws_scal = ws_chain + S * 8;
     uint32_t* ws_aff[2] = {ws_scal + S * 8, ws_scal + S * 8 + S * 24};
@@ -623,16 +666,18 @@ int hd_paths_dev(blsgpu_ctx* c, const void* d_parents, size_t n_parents, int pri
             const bool first = l == 0, last = l + 1 == depth;
             uint32_t* chain_out = last ? (uint32_t*)d_chain + lo * 8 : ws_chain;
             uint32_t* scal_out = last && priv ? (uint32_t*)d_sk + lo * 8 : ws_scal;
-            hipLaunchKernelGGL(k_hd_path_hmac, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, first ? par : ws_chain,
+            hipLaunchKernelGGL(secret ? k_hd_path_hmac_secret : k_hd_path_hmac, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
+                               first ? par : ws_chain,
                                first ? par + 32 : ws_scal, first ? par + 8 : ws_aff[cur], first ? 40u : 0u,
                                d_parent_of ? (const uint32_t*)d_parent_of + lo : nullptr, first ? 1u : 0u,
                                (const uint32_t*)d_idx + lo * depth + l, (uint32_t)depth, (uint32_t)m, priv ? 1u : 0u, chain_out, scal_out,
                                first && !priv ? ws_aff[0] : nullptr, last && d_fp ? (uint32_t*)d_fp + lo : nullptr);
             HIP_TRY(hipGetLastError());
             const int next = priv ? 0 : cur ^ 1;
-            if (int rc = fix_mul_launch(c, scal_out, m, priv ? nullptr : ws_aff[cur], priv ? 0 : m,
-                                        last ? (d_pk_aff ? (char*)d_pk_aff + lo * 96 : nullptr) : (char*)ws_aff[next],
-                                        last && d_pk_ser ? (char*)d_pk_ser + lo * 48 : nullptr, st))
+            void* aff_out = last ? (d_pk_aff ? (char*)d_pk_aff + lo * 96 : nullptr) : (char*)ws_aff[next];
+            void* ser_out = last && d_pk_ser ? (char*)d_pk_ser + lo * 48 : nullptr;
+            if (int rc = secret ? fix_mul_secret_launch(c, scal_out, m, aff_out, ser_out, st)
+                                : fix_mul_launch(c, scal_out, m, priv ? nullptr : ws_aff[cur], priv ? 0 : m, aff_out, ser_out, st))
                 return rc;
             cur = next;
         }
@@ -916,6 +961,7 @@ BLSGPU_EXPORT void blsgpu_ctx_destroy(blsgpu_ctx* c) {
     if (c->d_tables) (void)hipFree(c->d_tables);
     if (c->d_out) (void)hipFree(c->d_out);
     if (c->d_fix_table) (void)hipFree(c->d_fix_table);
+    if (c->d_fix_table_secret) (void)hipFree(c->d_fix_table_secret);
     for (const Buf& b : c->buf)
         if (b.p) (void)hipFree(b.p);
     for (void* q : c->retired) (void)hipFree(q);
@@ -1093,7 +1139,7 @@ BLSGPU_EXPORT int blsgpu_ctx_reserve(blsgpu_ctx* c, size_t max_pairs) {
 BLSGPU_EXPORT int blsgpu_ctx_workspace_bytes(blsgpu_ctx* c, size_t out[BLSGPU_WS_FIELDS]) {
     if (!c || !out) return fail(-EINVAL, "NULL argument");
     for (int i = 0; i < BLSGPU_WS_FIELDS; i++) out[i] = 0;
-    size_t total = c->d_fix_table ? blsgpu::g1fix::TABLE_BYTES : 0;
+    size_t total = (c->d_fix_table ? blsgpu::g1fix::TABLE_BYTES : 0) + (c->d_fix_table_secret ? blsgpu::g1fix::S_TABLE_BYTES : 0);
     for (int b = 0; b < B_COUNT; b++) {
         const size_t bytes = c->buf[b].cap / BUF_INFO[b].unit * BUF_INFO[b].unit;
         if (BUF_INFO[b].ws_field != BLSGPU_WS_TOTAL) out[BUF_INFO[b].ws_field] += bytes;
@@ -2065,6 +2111,28 @@ BLSGPU_EXPORT int blsgpu_g1_mul_gen_dev(blsgpu_ctx* c, const void* d_scalars, si
     return g1_mul_gen_dev(c, d_scalars, n, d_add, n_add, d_out_aff, d_out_ser, (hipStream_t)stream);
 }
 
+BLSGPU_EXPORT int blsgpu_g1_mul_gen_secret(blsgpu_ctx* c, const uint8_t* scalars, size_t n, uint8_t* out_aff, uint8_t* out_ser) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (n == 0) return 0;
+    if (!scalars || (!out_aff && !out_ser)) return fail(-EINVAL, "NULL argument");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE;
+    Staging s(c);
+    const int dsc = s.in(scalars, S, 32), daff = s.out(out_aff, S, 96), dser = s.out(out_ser, S, 48);
+    if (int rc = s.alloc()) return rc;
+    return for_slices(n, S, [&](size_t lo, size_t m) {
+        if (int rc = s.up(lo, m)) return rc;
+        if (int rc = g1_mul_gen_secret_dev(c, s.at(dsc), m, s.opt(daff), s.opt(dser), nullptr)) return rc;
+        return s.down(lo, m);
+    });
+}
+BLSGPU_EXPORT int blsgpu_g1_mul_gen_secret_dev(blsgpu_ctx* c, const void* d_scalars, size_t n, void* d_out_aff, void* d_out_ser,
+                                               void* stream) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    return g1_mul_gen_secret_dev(c, d_scalars, n, d_out_aff, d_out_ser, (hipStream_t)stream);
+}
+
 BLSGPU_EXPORT int blsgpu_hd_children(blsgpu_ctx* c, const uint8_t chain_code[32], const uint8_t parent_pk_aff[96], const uint8_t* parent_sk,
                                      const uint32_t* indices, size_t n, uint8_t* out_chain, uint8_t* out_sk, uint8_t* out_pk_aff,
                                      uint8_t* out_pk_ser) {
@@ -2097,9 +2165,9 @@ BLSGPU_EXPORT int blsgpu_hd_children_dev(blsgpu_ctx* c, const uint8_t chain_code
                            (hipStream_t)stream);
 }
 
-BLSGPU_EXPORT int blsgpu_hd_paths(blsgpu_ctx* c, const uint8_t* parents, size_t n_parents, int priv, const uint32_t* parent_of,
-                                  const uint32_t* indices, size_t depth, size_t n, uint8_t* out_chain, uint8_t* out_sk, uint8_t* out_pk_aff,
-                                  uint8_t* out_pk_ser, uint8_t* out_parent_fp) {
+static int hd_paths_host(blsgpu_ctx* c, const uint8_t* parents, size_t n_parents, int priv, const uint32_t* parent_of,
+                         const uint32_t* indices, size_t depth, size_t n, uint8_t* out_chain, uint8_t* out_sk, uint8_t* out_pk_aff,
+                         uint8_t* out_pk_ser, uint8_t* out_parent_fp, bool secret) {
     if (!c) return fail(-EINVAL, "ctx is NULL");
     if (depth == 0 || depth > 255) return fail(-EINVAL, "depth must be 1 .. 255");
     if (n == 0) return 0;
@@ -2121,9 +2189,21 @@ BLSGPU_EXPORT int blsgpu_hd_paths(blsgpu_ctx* c, const uint8_t* parents, size_t 
     return for_slices(n, S, [&](size_t lo, size_t m) {
         if (int rc = s.up(lo, m)) return rc;
         if (int rc = hd_paths_dev(c, s.at(dpar), n_parents, priv, s.opt(dof), s.at(didx), depth, m, s.at(dchain), s.opt(dsk), s.opt(daff),
-                                  s.opt(dser), s.opt(dfp), false, nullptr)) return rc;
+                                  s.opt(dser), s.opt(dfp), false, nullptr, secret)) return rc;
         return s.down(lo, m);
     });
+}
+BLSGPU_EXPORT int blsgpu_hd_paths(blsgpu_ctx* c, const uint8_t* parents, size_t n_parents, int priv, const uint32_t* parent_of,
+                                  const uint32_t* indices, size_t depth, size_t n, uint8_t* out_chain, uint8_t* out_sk, uint8_t* out_pk_aff,
+                                  uint8_t* out_pk_ser, uint8_t* out_parent_fp) {
+    return hd_paths_host(c, parents, n_parents, priv, parent_of, indices, depth, n, out_chain, out_sk, out_pk_aff, out_pk_ser, out_parent_fp,
+                         false);
+}
+BLSGPU_EXPORT int blsgpu_hd_paths_secret(blsgpu_ctx* c, const uint8_t* parents, size_t n_parents, const uint32_t* parent_of,
+                                         const uint32_t* indices, size_t depth, size_t n, uint8_t* out_chain, uint8_t* out_sk,
+                                         uint8_t* out_pk_aff, uint8_t* out_pk_ser, uint8_t* out_parent_fp) {
+    return hd_paths_host(c, parents, n_parents, 1, parent_of, indices, depth, n, out_chain, out_sk, out_pk_aff, out_pk_ser, out_parent_fp,
+                         true);
 }
 BLSGPU_EXPORT int blsgpu_hd_paths_dev(blsgpu_ctx* c, const void* d_parents, size_t n_parents, int priv, const void* d_parent_of,
                                       const void* d_indices, size_t depth, size_t n, void* d_out_chain, void* d_out_sk, void* d_out_pk_aff,
@@ -2133,6 +2213,15 @@ BLSGPU_EXPORT int blsgpu_hd_paths_dev(blsgpu_ctx* c, const void* d_parents, size
     HIP_TRY(hipSetDevice(c->device));
     return hd_paths_dev(c, d_parents, n_parents, priv, d_parent_of, d_indices, depth, n, d_out_chain, d_out_sk, d_out_pk_aff, d_out_pk_ser,
                         d_out_parent_fp, true, (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_hd_paths_secret_dev(blsgpu_ctx* c, const void* d_parents, size_t n_parents, const void* d_parent_of,
+                                             const void* d_indices, size_t depth, size_t n, void* d_out_chain, void* d_out_sk,
+                                             void* d_out_pk_aff, void* d_out_pk_ser, void* d_out_parent_fp, void* stream) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (depth == 0 || depth > 255) return fail(-EINVAL, "depth must be 1 .. 255");
+    HIP_TRY(hipSetDevice(c->device));
+    return hd_paths_dev(c, d_parents, n_parents, 1, d_parent_of, d_indices, depth, n, d_out_chain, d_out_sk, d_out_pk_aff, d_out_pk_ser,
+                        d_out_parent_fp, true, (hipStream_t)stream, true);
 }
 
 // ------------------------------------------------------------ Feldman share checks --

@@ -78,6 +78,7 @@ struct blsgpu_ctx {
     void* d_tables = nullptr;          // one allocation holding every table
     uint32_t* d_out = nullptr;         // 576-byte result staging
     uint32_t* d_fix_table = nullptr;   // the fixed-base G1 table (blsgpu_g1fix.hip), built on first use; freed by blsgpu_ctx_destroy only
+    uint32_t* d_fix_table_secret = nullptr;   // the signed 4-bit table of k_fix_mul_secret (58 240 bytes), likewise
     Buf buf[B_COUNT];
     std::vector<void*> retired;        // Buf::grow
     int grow(BufId id, size_t bytes) { return buf[id].grow(retired, bytes); }

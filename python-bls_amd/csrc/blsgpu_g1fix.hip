@@ -13,6 +13,8 @@
 // code as HMAC key: two midstate compressions and four HMAC compressions per level) and k_fix_mul on the scalars it
 // leaves -- over state that stays in device memory between the levels.  Like k_hd_hmac and k_fix_mul it is NOT
 // constant-time: the table gathers follow the digits of secret keys, and lanes branch on hardened indices.
+// blsgpu_g1_mul_gen_secret and blsgpu_hd_paths_secret run k_fix_mul_secret instead: a second, signed 4-bit table read whole
+// per window, a schedule that does not look at the scalar (the section "multiplication by SECRET scalars" below).
 #pragma once
 
 #include "hd_derive.h"
@@ -129,6 +131,126 @@ __global__ void __launch_bounds__(256) k_fix_mul(const uint32_t* __restrict__ ta
 ;
 #endif
 
+// ---- multiplication by SECRET scalars (blsgpu_g1_mul_gen_secret, blsgpu_hd_paths_secret) ---------------------------------
+// out_i = s_i G1 with a schedule that does not look at the scalar; vmgen/g1fixs_model.py is the specification of the
+// table and of the window schedule (tests/test_g1fixs_model.py: its value against the host's double-and-add, its trace the
+// same for every scalar).  k_g2_smul's conventions (blsgpu_g2smul.hip), cheaper because the point is fixed and public:
+//
+// WHAT IS CLAIMED: the sequence of instructions and of memory addresses does not depend on the scalars.  No branch, loop
+// bound, load address or store address is computed from a scalar byte:
+//   recoding   k_g2_smul's: the nibbles of s + C, C = sum_w 8 16^w over 65 windows, minus 8 are digits d_w in [-8, 8) with
+//              sum_w d_w 16^w = s for every s < 2^256 (s + C < 16^65: no case split).  Nine additions with carry; the nine
+//              words lie in LDS at the lane's own slot and are read by the window index.
+//   table      a SECOND table per context: entry (w, e) = (e + 1) 16^w G1 for w < 65, e < 8, affine (x, y) in L28 form --
+//              520 x 112 bytes = 58 240 bytes, built once (k_fix_table_secret).  The 8-bit table above is not used.
+//   window     every lane reads all eight entries of window w -- the address depends on w alone, the same for every lane
+//              (the compiler issues them as scalar loads) -- and keeps one by compare-and-select on |d| == e + 1; y or the
+//              normalised -y by select; then ONE complete mixed addition (r28::pmadd).  A zero digit cannot be an affine
+//              addend: entry 0 is added all the same and the old accumulator kept by a per-limb select.  Nothing is
+//              skipped: 65 mixed additions and no doubling for every scalar, 0 and 2^256 - 1 included.
+//   output     to_affine_raw: fq_inv is the fixed-length branch-free inversion, 0 -> 0, so infinity leaves as (0, 0).
+//              ser_flag looks at the public result only.
+//   tail       spare lanes of the last workgroup repeat the last scalar and store nothing (a matter of the index).
+// WHAT IS NOT CLAIMED: data-dependent timing inside the hardware (the duration of an instruction, of a cache or memory
+// access as a function of the values it handles).  The scalars are the literal 256-bit integers: no reduction mod n is
+// needed, s G1 = (s mod n) G1, so the bytes are those of k_fix_mul.
+constexpr uint32_t S_WINDOWS = 65, S_TAB = 8, S_REC_WORDS = 9;
+constexpr uint32_t S_ENTRIES = S_WINDOWS * S_TAB;
+constexpr size_t S_TABLE_BYTES = (size_t)S_ENTRIES * ENTRY_DW * 4;
+
+// The signed-window table: entry w * 8 + e holds (e + 1) 16^w G1 -- one entry per lane, double-and-add over the 4 bits of
+// e + 1, then 4w doublings, then the affine form.  Once per context; nothing here depends on a scalar.
+__global__ void __launch_bounds__(64) k_fix_table_secret(Gen g, uint32_t* __restrict__ table)
+#if BLSGPU_EMIT(BLSGPU_TU_FIX)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= S_ENTRIES) return;
+    const uint32_t w = i / S_TAB, d = i % S_TAB + 1u;
+    const r28::fe gx = r28::from_raw(g.x), gy = r28::from_raw(g.y);
+    r28::ptT<r28::fe> acc = r28::pt_inf<r28::fe>();
+#pragma unroll 1
+    for (int b = 3; b >= 0; b--) {
+        acc = r28::pdbl(acc);
+        if ((d >> b) & 1u) r28::pmadd(acc, gx, gy);
+    }
+#pragma unroll 1
+    for (uint32_t t = 0; t < 4u * w; t++) acc = r28::pdbl(acc);
+    uint32_t x[12], y[12];
+    to_affine_raw(acc, x, y);
+    r28::st(r28::from_raw(x), table + (size_t)i * ENTRY_DW);
+    r28::st(r28::from_raw(y), table + (size_t)i * ENTRY_DW + r28::NL);
+}
+#else
+;
+#endif
+
+// out_i = s_i G1 for n >= 1 scalars (32 bytes big-endian) on k_fix_table_secret's table.  out_aff (n x 96 bytes, (0, 0) for
+// infinity) and out_ser (n x 48 bytes, PublicKey.serialize()) as k_fix_mul writes them; each may be NULL.
+__global__ void __launch_bounds__(256) k_fix_mul_secret(const uint32_t* __restrict__ table, const uint32_t* __restrict__ scalars, uint32_t n,
+                                                        uint32_t* __restrict__ out_aff, uint32_t* __restrict__ out_ser)
+#if BLSGPU_EMIT(BLSGPU_TU_FIX)
+{
+    __shared__ uint32_t rec[S_REC_WORDS][256];
+    const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x;
+    const uint32_t i = min(tid, n - 1u);
+    const bool store = tid < n;
+    {   // s + C into the lane's own slot
+        uint64_t t = 0;
+#pragma unroll
+        for (int j = 0; j < (int)S_REC_WORDS; j++) {
+            t += (uint64_t)(j < 8 ? bswap32(scalars[(size_t)i * 8 + 7 - j]) : 0u) + (j < 8 ? 0x88888888u : 0x8u);
+            rec[j][lane] = (uint32_t)t;
+            t >>= 32;
+        }
+    }
+    r28::ptT<r28::fe> acc = r28::pt_inf<r28::fe>();
+#pragma unroll 1
+    for (uint32_t w = 0; w < S_WINDOWS; w++) {
+        const int32_t d = (int32_t)((rec[w >> 3][lane] >> (4u * (w & 7u))) & 15u) - 8;
+        const uint32_t sgn = (uint32_t)(d >> 31);                          // all ones for a negative digit
+        const uint32_t ad = ((uint32_t)d ^ sgn) - sgn;                     // |d|: 0 .. 8
+        const uint32_t mz = 0u - (uint32_t)(ad == 0u);                     // zero digit: entry 0 is added, the sum dropped
+        const uint32_t* T = table + (size_t)w * (S_TAB * ENTRY_DW);        // the same address in every lane
+        uint32_t q[ENTRY_DW];
+#pragma unroll
+        for (int j = 0; j < (int)ENTRY_DW; j++) q[j] = T[j] & (mz | (0u - (uint32_t)(ad == 1u)));
+#pragma unroll
+        for (uint32_t e = 1; e < S_TAB; e++) {                             // every entry is read; the mask keeps one
+            const uint32_t m = 0u - (uint32_t)(ad == e + 1u);
+#pragma unroll
+            for (int j = 0; j < (int)ENTRY_DW; j++) q[j] |= T[e * ENTRY_DW + j] & m;
+        }
+        r28::fe x, y;
+#pragma unroll
+        for (int j = 0; j < r28::NL; j++) { x.v[j] = (int32_t)q[j]; y.v[j] = (int32_t)q[r28::NL + j]; }
+        const r28::fe yn = r28::norm(r28::neg(y));
+#pragma unroll
+        for (int j = 0; j < r28::NL; j++) y.v[j] = (int32_t)(((uint32_t)yn.v[j] & sgn) | ((uint32_t)y.v[j] & ~sgn));
+        const r28::ptT<r28::fe> old = acc;
+        r28::pmadd(acc, x, y);
+#pragma unroll
+        for (int j = 0; j < r28::NL; j++) {
+            acc.X.v[j] = (int32_t)(((uint32_t)old.X.v[j] & mz) | ((uint32_t)acc.X.v[j] & ~mz));
+            acc.Y.v[j] = (int32_t)(((uint32_t)old.Y.v[j] & mz) | ((uint32_t)acc.Y.v[j] & ~mz));
+            acc.Z.v[j] = (int32_t)(((uint32_t)old.Z.v[j] & mz) | ((uint32_t)acc.Z.v[j] & ~mz));
+        }
+    }
+    uint32_t x[12], y[12];
+    to_affine_raw(acc, x, y);
+    if (out_aff && store) {
+#pragma unroll
+        for (int w = 0; w < 12; w++) { out_aff[(size_t)i * 24 + w] = bswap32(x[11 - w]); out_aff[(size_t)i * 24 + 12 + w] = bswap32(y[11 - w]); }
+    }
+    if (out_ser && store) {
+        ser_flag(x, y);
+#pragma unroll
+        for (int w = 0; w < 12; w++) out_ser[(size_t)i * 12 + w] = bswap32(x[11 - w]);
+    }
+}
+#else
+;
+#endif
+
 // One call's parent: the HMAC key midstates of the chain code, the parent's serialised keys as big-endian words and, for
 // private derivation, its key mod n (little-endian words).
 struct HdParent {
@@ -194,13 +316,14 @@ __global__ void __launch_bounds__(256) k_hd_check(const uint32_t* __restrict__ i
 // arrays this lane read (no other lane touches them).  aff_copy (or NULL): the parent key's 96 bytes per lane, the `add`
 // of the first public level's k_fix_mul.  fp_out (or NULL): PublicKey.get_fingerprint of the parent key, 4 bytes
 // big-endian -- the last level's parent_fingerprint.
-__global__ void __launch_bounds__(256) k_hd_path_hmac(const uint32_t* chain_in, const uint32_t* sk_in, const uint32_t* __restrict__ aff_in,
-                                                      uint32_t rec_dw, const uint32_t* __restrict__ parent_of, uint32_t first,
-                                                      const uint32_t* __restrict__ idx, uint32_t idx_stride, uint32_t n, uint32_t priv,
-                                                      uint32_t* chain_out, uint32_t* scal_out, uint32_t* __restrict__ aff_copy,
-                                                      uint32_t* __restrict__ fp_out)
-#if BLSGPU_EMIT(BLSGPU_TU_FIX)
-{
+// SECRET (k_hd_path_hmac_secret, private mode): the reductions mod n keep their subtraction by mask (hd_derive.h); the branch
+// on a hardened index stays, indices are public.
+template <bool SECRET>
+__device__ __forceinline__ void hd_path_level(const uint32_t* chain_in, const uint32_t* sk_in, const uint32_t* __restrict__ aff_in,
+                                              uint32_t rec_dw, const uint32_t* __restrict__ parent_of, uint32_t first,
+                                              const uint32_t* __restrict__ idx, uint32_t idx_stride, uint32_t n, uint32_t priv,
+                                              uint32_t* chain_out, uint32_t* scal_out, uint32_t* __restrict__ aff_copy,
+                                              uint32_t* __restrict__ fp_out) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
     const size_t src = first ? (parent_of ? parent_of[p] : 0u) : p;
@@ -238,9 +361,15 @@ __global__ void __launch_bounds__(256) k_hd_path_hmac(const uint32_t* chain_in, 
         uint32_t l[8], k[8], r[8];
 #pragma unroll
         for (int j = 0; j < 8; j++) { l[j] = il[7 - j]; k[j] = sk_ser[7 - j]; }
-        hdk::reduce_n(l);
-        hdk::reduce_n(k);
-        hdk::add_mod_n(r, l, k);
+        if (SECRET) {
+            hdk::reduce_n_masked(l);
+            hdk::reduce_n_masked(k);
+            hdk::add_mod_n_masked(r, l, k);
+        } else {
+            hdk::reduce_n(l);
+            hdk::reduce_n(k);
+            hdk::add_mod_n(r, l, k);
+        }
 #pragma unroll
         for (int j = 0; j < 8; j++) scal_out[(size_t)p * 8 + j] = bswap32(r[7 - j]);
     } else {
@@ -248,9 +377,27 @@ __global__ void __launch_bounds__(256) k_hd_path_hmac(const uint32_t* chain_in, 
         for (int j = 0; j < 8; j++) scal_out[(size_t)p * 8 + j] = bswap32(il[j]);
     }
 }
+#define BLSGPU_HD_PATH_ARGS                                                                                                       \
+    const uint32_t *chain_in, const uint32_t *sk_in, const uint32_t *__restrict__ aff_in, uint32_t rec_dw,                        \
+        const uint32_t *__restrict__ parent_of, uint32_t first, const uint32_t *__restrict__ idx, uint32_t idx_stride, uint32_t n, \
+        uint32_t priv, uint32_t *chain_out, uint32_t *scal_out, uint32_t *__restrict__ aff_copy, uint32_t *__restrict__ fp_out
+__global__ void __launch_bounds__(256) k_hd_path_hmac(BLSGPU_HD_PATH_ARGS)
+#if BLSGPU_EMIT(BLSGPU_TU_FIX)
+{
+    hd_path_level<false>(chain_in, sk_in, aff_in, rec_dw, parent_of, first, idx, idx_stride, n, priv, chain_out, scal_out, aff_copy, fp_out);
+}
 #else
 ;
 #endif
+__global__ void __launch_bounds__(256) k_hd_path_hmac_secret(BLSGPU_HD_PATH_ARGS)
+#if BLSGPU_EMIT(BLSGPU_TU_FIX)
+{
+    hd_path_level<true>(chain_in, sk_in, aff_in, rec_dw, parent_of, first, idx, idx_stride, n, priv, chain_out, scal_out, aff_copy, fp_out);
+}
+#else
+;
+#endif
+#undef BLSGPU_HD_PATH_ARGS
 
 // The validity scan of blsgpu_hd_paths_dev, one path per lane: flag[0] |= 2 if parent_of[p] >= n_parents, |= 1 if (pub)
 // any of the path's `depth` indices is >= 2^31

@@ -175,4 +175,29 @@ HD_FN void add_mod_n(uint32_t r[8], const uint32_t a[8], const uint32_t b[8]) {
     sub_n_if_ge(r);
 }
 
+// ---- the same for SECRET scalars: the subtraction is always computed and kept by a mask, no branch on the borrow --------
+// (blsgpu_hd_paths_secret; values equal those of the forms above for every input, tests/test_g1fixs_host.py)
+HD_FN void sub_n_if_ge_masked(uint32_t s[8]) {
+    const uint32_t nw[8] = HD_N_WORDS;
+    uint32_t t[8];
+    uint64_t borrow = 0;
+    for (int j = 0; j < 8; j++) {
+        const uint64_t d = (uint64_t)s[j] - nw[j] - borrow;
+        t[j] = (uint32_t)d;
+        borrow = (d >> 32) & 1u;
+    }
+    const uint32_t keep = (uint32_t)borrow - 1u;                // all ones when s >= n
+    for (int j = 0; j < 8; j++) s[j] = (t[j] & keep) | (s[j] & ~keep);
+}
+HD_FN void reduce_n_masked(uint32_t s[8]) { sub_n_if_ge_masked(s); sub_n_if_ge_masked(s); }
+HD_FN void add_mod_n_masked(uint32_t r[8], const uint32_t a[8], const uint32_t b[8]) {
+    uint64_t c = 0;
+    for (int j = 0; j < 8; j++) {
+        c += (uint64_t)a[j] + b[j];
+        r[j] = (uint32_t)c;
+        c >>= 32;
+    }
+    sub_n_if_ge_masked(r);
+}
+
 }  // namespace hdk
