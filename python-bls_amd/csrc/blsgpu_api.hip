@@ -463,36 +463,24 @@ blsgpu::g1fix::Gen g1_generator() {
                     0xa09e30edu, 0xe3aaa0f1u, 0x08b3f481u}};
 }
 
-// the table of d 2^(8w) G1, built on `st` the first time a context needs it
-int fix_table(blsgpu_ctx* c, hipStream_t st) {
-    if (c->d_fix_table) return 0;
+// a context's table, built on `st` the first time it is needed: d 2^(8w) G1 for k_fix_mul (fix_sum), or `secret`: the
+// (e + 1) 16^w G1 that k_fix_mul_secret reads whole, window by window
+int fix_table(blsgpu_ctx* c, hipStream_t st, bool secret = false) {
     using namespace blsgpu::g1fix;
-    const Gen g = g1_generator();
+    uint32_t*& slot = secret ? c->d_fix_table_secret : c->d_fix_table;
+    if (slot) return 0;
     void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, TABLE_BYTES));
-    hipLaunchKernelGGL(k_fix_table, dim3((ENTRIES + 63) / 64), dim3(64), 0, st, g, (uint32_t*)p);
+    HIP_TRY(hipMalloc(&p, secret ? S_TABLE_BYTES : TABLE_BYTES));
+    if (secret)
+        hipLaunchKernelGGL(k_fix_table_t<4>, dim3((S_ENTRIES + 63) / 64), dim3(64), 0, st, g1_generator(), (uint32_t*)p);
+    else
+        hipLaunchKernelGGL(k_fix_table_t<8>, dim3((ENTRIES + 63) / 64), dim3(64), 0, st, g1_generator(), (uint32_t*)p);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         (void)hipFree(p);
-        return fail(-EIO, std::string("k_fix_table: ") + hipGetErrorString(e));
+        return fail(-EIO, std::string(secret ? "k_fix_table_secret: " : "k_fix_table: ") + hipGetErrorString(e));
     }
-    c->d_fix_table = (uint32_t*)p;
-    return 0;
-}
-
-// the table of (e + 1) 16^w G1 that k_fix_mul_secret reads whole, window by window; likewise
-int fix_table_secret(blsgpu_ctx* c, hipStream_t st) {
-    if (c->d_fix_table_secret) return 0;
-    using namespace blsgpu::g1fix;
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, S_TABLE_BYTES));
-    hipLaunchKernelGGL(k_fix_table_secret, dim3((S_ENTRIES + 63) / 64), dim3(64), 0, st, g1_generator(), (uint32_t*)p);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        (void)hipFree(p);
-        return fail(-EIO, std::string("k_fix_table_secret: ") + hipGetErrorString(e));
-    }
-    c->d_fix_table_secret = (uint32_t*)p;
+    slot = (uint32_t*)p;
     return 0;
 }
 
@@ -506,18 +494,17 @@ int check_n_add(size_t n, size_t n_add, const void* add) {
 int fix_mul_launch(blsgpu_ctx* c, const void* d_scalars, size_t n, const void* d_add, size_t n_add, void* d_out_aff, void* d_out_ser,
                    hipStream_t st) {
     const bool per = n_add == n && n_add > 1;
-    for (size_t lo = 0; lo < n; lo += FIX_SLICE) {
-        const size_t m = n - lo < FIX_SLICE ? n - lo : FIX_SLICE;
+    return for_slices(n, FIX_SLICE, [&](size_t lo, size_t m) {
         hipLaunchKernelGGL(blsgpu::g1fix::k_fix_mul, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint32_t*)c->d_fix_table,
                            (const uint32_t*)d_scalars + lo * 8, (uint32_t)m,
                            n_add ? (const uint32_t*)d_add + (per ? lo * 24 : 0) : nullptr, per ? 1u : 0u,
                            d_out_aff ? (uint32_t*)d_out_aff + lo * 24 : nullptr, d_out_ser ? (uint32_t*)d_out_ser + lo * 12 : nullptr);
         HIP_TRY(hipGetLastError());
-    }
-    return 0;
+        return 0;
+    });
 }
 
-// enqueues out_i = s_i G1 on the scalar-independent schedule on `st` (caller: StreamGuard, fix_table_secret)
+// enqueues out_i = s_i G1 on the scalar-independent schedule on `st` (caller: StreamGuard, fix_table(secret))
 int fix_mul_secret_launch(blsgpu_ctx* c, const void* d_scalars, size_t n, void* d_out_aff, void* d_out_ser, hipStream_t st) {
     KernelTimer kt(c, st, 9);
     return for_slices(n, FIX_SLICE, [&](size_t lo, size_t m) {
@@ -533,7 +520,7 @@ int g1_mul_gen_secret_dev(blsgpu_ctx* c, const void* d_scalars, size_t n, void* 
     if (n == 0) return 0;
     if (!d_scalars || (!d_out_aff && !d_out_ser)) return fail(-EINVAL, "NULL argument");
     StreamGuard sg(c, st);
-    if (int rc = fix_table_secret(c, st)) return rc;
+    if (int rc = fix_table(c, st, true)) return rc;
     return fix_mul_secret_launch(c, d_scalars, n, d_out_aff, d_out_ser, st);
 }
 
@@ -547,15 +534,13 @@ int g1_mul_gen_dev(blsgpu_ctx* c, const void* d_scalars, size_t n, const void* d
     return fix_mul_launch(c, d_scalars, n, d_add, n_add, d_out_aff, d_out_ser, st);
 }
 
-// 48 big-endian bytes of q // 2 (blsgpu::g1fix::HALF_Q_WORDS)
-bool y_gt_half_q(const uint8_t y[48]) {
-    for (int b = 0; b < 48; b++) {
-        const uint8_t h = (uint8_t)(blsgpu::g1fix::HALF_Q_WORDS[11 - b / 4] >> (24 - 8 * (b % 4)));
-        if (y[b] != h) return y[b] > h;
-    }
-    return false;
-}
 uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
+// y > q // 2 for 48 big-endian bytes
+bool y_gt_half_q(const uint8_t y[48]) {
+    uint32_t w[12];
+    for (int j = 0; j < 12; j++) w[11 - j] = be32(y + 4 * j);
+    return bls::gt_half_q_mask(w) != 0;
+}
 
 // the per-call constants of a parent: HMAC midstates of the chain code, PublicKey.serialize() of the parent key
 // (ec.py:94-111; (0, 0) -> 48 zero bytes), and for private derivation its key's bytes and value mod n
@@ -573,6 +558,19 @@ blsgpu::g1fix::HdParent hd_parent(const uint8_t chain_code[32], const uint8_t pa
     return P;
 }
 
+// The validity scans of the _dev forms: clears the flag word, runs `launch` (which enqueues the scan kernel on `st`) and
+// reads the word back -- one synchronisation, before anything is written
+template <class F>
+int scan_flag(void* d_flag, hipStream_t st, uint32_t& flag, F launch) {
+    HIP_TRY(hipMemsetAsync(d_flag, 0, 4, st));
+    launch((uint32_t*)d_flag);
+    HIP_TRY(hipGetLastError());
+    flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
 // n children of one parent on `st`; public mode (parent_sk NULL) with `check`: a device scan of the indices and one
 // synchronising read of its flag first, -EINVAL before anything is written if one is hardened
 int hd_children_dev(blsgpu_ctx* c, const uint8_t chain_code[32], const uint8_t parent_pk_aff[96], const uint8_t* parent_sk, const void* d_idx,
@@ -588,13 +586,12 @@ int hd_children_dev(blsgpu_ctx* c, const uint8_t chain_code[32], const uint8_t p
     if (int rc = c->grow(B_FIX_WS, 256 + slice * 32)) return rc;
     char* ws = c->at<char>(B_FIX_WS);                                  // [0, 96) parent key, [128, 132) flag, [256, ..) i_left
     if (pub && check) {
-        HIP_TRY(hipMemsetAsync(ws + 128, 0, 4, st));
-        hipLaunchKernelGGL(blsgpu::g1fix::k_hd_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_idx, (uint32_t)n,
-                           (uint32_t*)(ws + 128));
-        HIP_TRY(hipGetLastError());
-        uint32_t flag = 0;
-        HIP_TRY(hipMemcpyAsync(&flag, ws + 128, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        uint32_t flag;
+        if (int rc = scan_flag(ws + 128, st, flag, [&](uint32_t* d_flag) {
+                hipLaunchKernelGGL(blsgpu::g1fix::k_hd_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_idx,
+                                   (uint32_t)n, d_flag);
+            }))
+            return rc;
         if (flag) return fail(-EINVAL, "Cannot derive hardened children from public key");
     }
     const bool pk_out = d_pk_aff || d_pk_ser;
@@ -602,20 +599,15 @@ int hd_children_dev(blsgpu_ctx* c, const uint8_t chain_code[32], const uint8_t p
         if (int rc = fix_table(c, st)) return rc;
     }
     if (pub) HIP_TRY(hipMemcpyAsync(ws, parent_pk_aff, 96, hipMemcpyHostToDevice, st));
-    const size_t step = pub ? slice : FIX_SLICE;
-    for (size_t lo = 0; lo < n; lo += step) {
-        const size_t m = n - lo < step ? n - lo : step;
+    return for_slices(n, pub ? slice : FIX_SLICE, [&](size_t lo, size_t m) {
         uint32_t* scal = pub ? (uint32_t*)(ws + 256) : (uint32_t*)d_sk + lo * 8;
         hipLaunchKernelGGL(blsgpu::g1fix::k_hd_hmac, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, P, (const uint32_t*)d_idx + lo,
                            (uint32_t)m, (uint32_t*)d_chain + lo * 8, scal);
         HIP_TRY(hipGetLastError());
-        if (pk_out) {
-            if (int rc = fix_mul_launch(c, scal, m, pub ? ws : nullptr, pub ? 1 : 0, d_pk_aff ? (char*)d_pk_aff + lo * 96 : nullptr,
-                                        d_pk_ser ? (char*)d_pk_ser + lo * 48 : nullptr, st))
-                return rc;
-        }
-    }
-    return 0;
+        if (!pk_out) return 0;
+        return fix_mul_launch(c, scal, m, pub ? ws : nullptr, pub ? 1 : 0, d_pk_aff ? (char*)d_pk_aff + lo * 96 : nullptr,
+                              d_pk_ser ? (char*)d_pk_ser + lo * 48 : nullptr, st);
+    });
 }
 // blsgpu_hd_paths*: the arguments every form checks before anything is written (after n == 0)
 int hd_paths_args(const void* parents, size_t n_parents, int priv, const void* indices, size_t depth, size_t n, const void* chain,
@@ -645,17 +637,16 @@ int hd_paths_dev(blsgpu_ctx* c, const void* d_parents, size_t n_parents, int pri
     if (int rc = c->grow(B_HDP_WS, 256 + S * (priv ? 160 : 256))) return rc;
     char* ws = c->at<char>(B_HDP_WS);
     if (check && (d_parent_of || !priv)) {
-        HIP_TRY(hipMemsetAsync(ws, 0, 4, st));
-        hipLaunchKernelGGL(k_hd_path_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_parent_of, (uint32_t)n_parents,
-                           (const uint32_t*)d_idx, (uint32_t)depth, priv ? 0u : 1u, (uint32_t)n, (uint32_t*)ws);
-        HIP_TRY(hipGetLastError());
-        uint32_t flag = 0;
-        HIP_TRY(hipMemcpyAsync(&flag, ws, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        uint32_t flag;
+        if (int rc = scan_flag(ws, st, flag, [&](uint32_t* d_flag) {
+                hipLaunchKernelGGL(k_hd_path_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_parent_of,
+                                   (uint32_t)n_parents, (const uint32_t*)d_idx, (uint32_t)depth, priv ? 0u : 1u, (uint32_t)n, d_flag);
+            }))
+            return rc;
         if (flag & 2u) return fail(-EINVAL, "parent index out of range");
         if (flag & 1u) return fail(-EINVAL, "Cannot derive hardened children from public key");
     }
-    if (int rc = secret ? fix_table_secret(c, st) : fix_table(c, st)) return rc;
+    if (int rc = fix_table(c, st, secret)) return rc;
     uint32_t* ws_chain = (uint32_t*)(ws + 256);
     uint32_t* ws_scal = ws_chain + S * 8;
     uint32_t* ws_aff[2] = {ws_scal + S * 8, ws_scal + S * 8 + S * 24};
@@ -2084,12 +2075,14 @@ BLSGPU_EXPORT int blsgpu_g2_decompress_dev(blsgpu_ctx* c, const void* d_in, size
 }
 
 // ------------------------------------------------------------ fixed-base G1, HD derivation --
-BLSGPU_EXPORT int blsgpu_g1_mul_gen(blsgpu_ctx* c, const uint8_t* scalars, size_t n, const uint8_t* add, size_t n_add, uint8_t* out_aff,
-                                    uint8_t* out_ser) {
+// the host-buffer forms of out_i = s_i G1: digit-indexed with the optional addend, or `secret` (no addend)
+static int g1_mul_gen_host(blsgpu_ctx* c, const uint8_t* scalars, size_t n, const uint8_t* add, size_t n_add, uint8_t* out_aff,
+                           uint8_t* out_ser, bool secret) {
     if (!c) return fail(-EINVAL, "ctx is NULL");
     if (n == 0) return 0;
     if (!scalars || (!out_aff && !out_ser)) return fail(-EINVAL, "NULL argument");
-    if (int rc = check_n_add(n, n_add, add)) return rc;
+    if (!secret)
+        if (int rc = check_n_add(n, n_add, add)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const size_t S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE;
     const bool per = n_add == n && n_add > 1;
@@ -2100,9 +2093,15 @@ BLSGPU_EXPORT int blsgpu_g1_mul_gen(blsgpu_ctx* c, const uint8_t* scalars, size_
     if (int rc = s.up()) return rc;
     return for_slices(n, S, [&](size_t lo, size_t m) {
         if (int rc = s.up(lo, m)) return rc;
-        if (int rc = g1_mul_gen_dev(c, s.at(dsc), m, s.opt(dadd), per ? m : n_add, s.opt(daff), s.opt(dser), nullptr)) return rc;
+        if (int rc = secret ? g1_mul_gen_secret_dev(c, s.at(dsc), m, s.opt(daff), s.opt(dser), nullptr)
+                            : g1_mul_gen_dev(c, s.at(dsc), m, s.opt(dadd), per ? m : n_add, s.opt(daff), s.opt(dser), nullptr))
+            return rc;
         return s.down(lo, m);
     });
+}
+BLSGPU_EXPORT int blsgpu_g1_mul_gen(blsgpu_ctx* c, const uint8_t* scalars, size_t n, const uint8_t* add, size_t n_add, uint8_t* out_aff,
+                                    uint8_t* out_ser) {
+    return g1_mul_gen_host(c, scalars, n, add, n_add, out_aff, out_ser, false);
 }
 BLSGPU_EXPORT int blsgpu_g1_mul_gen_dev(blsgpu_ctx* c, const void* d_scalars, size_t n, const void* d_add, size_t n_add, void* d_out_aff,
                                         void* d_out_ser, void* stream) {
@@ -2112,19 +2111,7 @@ BLSGPU_EXPORT int blsgpu_g1_mul_gen_dev(blsgpu_ctx* c, const void* d_scalars, si
 }
 
 BLSGPU_EXPORT int blsgpu_g1_mul_gen_secret(blsgpu_ctx* c, const uint8_t* scalars, size_t n, uint8_t* out_aff, uint8_t* out_ser) {
-    if (!c) return fail(-EINVAL, "ctx is NULL");
-    if (n == 0) return 0;
-    if (!scalars || (!out_aff && !out_ser)) return fail(-EINVAL, "NULL argument");
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE;
-    Staging s(c);
-    const int dsc = s.in(scalars, S, 32), daff = s.out(out_aff, S, 96), dser = s.out(out_ser, S, 48);
-    if (int rc = s.alloc()) return rc;
-    return for_slices(n, S, [&](size_t lo, size_t m) {
-        if (int rc = s.up(lo, m)) return rc;
-        if (int rc = g1_mul_gen_secret_dev(c, s.at(dsc), m, s.opt(daff), s.opt(dser), nullptr)) return rc;
-        return s.down(lo, m);
-    });
+    return g1_mul_gen_host(c, scalars, n, nullptr, 0, out_aff, out_ser, true);
 }
 BLSGPU_EXPORT int blsgpu_g1_mul_gen_secret_dev(blsgpu_ctx* c, const void* d_scalars, size_t n, void* d_out_aff, void* d_out_ser,
                                                void* stream) {

@@ -18,6 +18,7 @@
 #pragma once
 
 #include "hd_derive.h"
+#include "secret_window.h"
 
 namespace blsgpu {
 namespace g1fix {
@@ -26,8 +27,8 @@ constexpr uint32_t WINDOWS = 32, DIGITS = 255;
 constexpr uint32_t ENTRY_DW = 2 * r28::NL;                                   // affine (x, y), L28
 constexpr uint32_t ENTRIES = WINDOWS * DIGITS;
 constexpr size_t TABLE_BYTES = (size_t)ENTRIES * ENTRY_DW * 4;
-constexpr uint32_t HALF_Q_WORDS[12] = {0xffffd555u, 0xdcff7fffu, 0x58a9ffffu, 0x0f55ffffu, 0x7b587b12u, 0xb3986950u,
-                                       0x79c2895fu, 0xb23ba5c2u, 0x21a5d66bu, 0x258dd3dbu, 0x1cbff34du, 0x0d0088f5u};   // q // 2
+constexpr uint32_t S_ENTRIES = swin::WINDOWS * swin::TAB;                     // the signed 4-bit table of k_fix_mul_secret
+constexpr size_t S_TABLE_BYTES = (size_t)S_ENTRIES * ENTRY_DW * 4;
 
 struct Gen { uint32_t x[12], y[12]; };                                        // an affine point, little-endian words
 
@@ -56,32 +57,45 @@ __device__ __forceinline__ void fix_sum(const uint32_t* __restrict__ table, cons
 
 // PublicKey.serialize() of a canonical affine point (ec.py:94-111 of the reference), in place on x: 0x80 in the top byte
 // when y > q // 2 (most significant word first).  Infinity is (0, 0): y = 0, so x stays 0.
-__device__ __forceinline__ void ser_flag(uint32_t x[12], const uint32_t y[12]) {
-    bool gt = false, decided = false;
+__device__ __forceinline__ void ser_flag(uint32_t x[12], const uint32_t y[12]) { x[11] |= bls::gt_half_q_mask(y) & 0x80000000u; }
+
+// The result of lane i, canonical (x, y): out_aff 96 bytes big-endian ((0, 0) for infinity), out_ser 48 bytes
+// (PublicKey.serialize()); each may be NULL
+__device__ __forceinline__ void store_result(uint32_t x[12], const uint32_t y[12], uint32_t i, uint32_t* __restrict__ out_aff,
+                                             uint32_t* __restrict__ out_ser) {
+    if (out_aff) {
 #pragma unroll
-    for (int w = 11; w >= 0; w--) {
-        if (!decided && y[w] != HALF_Q_WORDS[w]) { gt = y[w] > HALF_Q_WORDS[w]; decided = true; }
+        for (int w = 0; w < 12; w++) { out_aff[(size_t)i * 24 + w] = bswap32(x[11 - w]); out_aff[(size_t)i * 24 + 12 + w] = bswap32(y[11 - w]); }
     }
-    x[11] |= gt ? 0x80000000u : 0u;
+    if (out_ser) {
+        ser_flag(x, y);
+#pragma unroll
+        for (int w = 0; w < 12; w++) out_ser[(size_t)i * 12 + w] = bswap32(x[11 - w]);
+    }
 }
 
-// The table: entry e = w * 255 + d - 1 holds d 2^(8w) G1 -- one entry per lane, double-and-add over the 8 bits of d, then 8w
-// doublings, then the affine form.  Once per context (a few hundred microseconds).
-__global__ void __launch_bounds__(64) k_fix_table(Gen g, uint32_t* __restrict__ table)
+// The tables, WBITS bits per window: entry e = w * PER + d - 1 holds d 2^(WBITS w) G1 -- one entry per lane, double-and-add
+// over the WBITS bits of d, then WBITS w doublings, then the affine form.  Once per context (a few hundred microseconds);
+// nothing here depends on a scalar.  <8>: 32 windows of the digits 1 .. 255 (fix_sum); <4>: swin::WINDOWS windows of
+// |d| = 1 .. swin::TAB (k_fix_mul_secret).
+template <uint32_t WBITS>
+__global__ void __launch_bounds__(64) k_fix_table_t(Gen g, uint32_t* __restrict__ table)
 #if BLSGPU_EMIT(BLSGPU_TU_FIX)
 {
+    static_assert(WBITS == 8 || WBITS == 4, "unsigned 8-bit or signed 4-bit windows");
+    constexpr uint32_t PER = WBITS == 8 ? DIGITS : swin::TAB, N = WBITS == 8 ? ENTRIES : S_ENTRIES;
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= ENTRIES) return;
-    const uint32_t w = e / DIGITS, d = e % DIGITS + 1u;
+    if (e >= N) return;
+    const uint32_t w = e / PER, d = e % PER + 1u;
     const r28::fe gx = r28::from_raw(g.x), gy = r28::from_raw(g.y);
     r28::ptT<r28::fe> acc = r28::pt_inf<r28::fe>();
 #pragma unroll 1
-    for (int b = 7; b >= 0; b--) {
+    for (int b = (int)WBITS - 1; b >= 0; b--) {
         acc = r28::pdbl(acc);
         if ((d >> b) & 1u) r28::pmadd(acc, gx, gy);
     }
 #pragma unroll 1
-    for (uint32_t t = 0; t < 8u * w; t++) acc = r28::pdbl(acc);
+    for (uint32_t t = 0; t < WBITS * w; t++) acc = r28::pdbl(acc);
     uint32_t x[12], y[12];
     to_affine_raw(acc, x, y);
     r28::st(r28::from_raw(x), table + (size_t)e * ENTRY_DW);
@@ -89,6 +103,9 @@ __global__ void __launch_bounds__(64) k_fix_table(Gen g, uint32_t* __restrict__ 
 }
 #else
 ;
+#endif
+#if BLSGPU_TU == BLSGPU_TU_FIX          // the instantiations the host side launches: this translation unit emits them (blsgpu_tu.h)
+__attribute__((used)) static const void* const blsgpu_instances_fix[] = {(const void*)&k_fix_table_t<8>, (const void*)&k_fix_table_t<4>};
 #endif
 
 // out_i = (s_i mod n) G1 + A_i.  scalars: n x 32 bytes big-endian; add: NULL, one point (add_per = 0) or n points (add_per = 1),
@@ -117,135 +134,58 @@ __global__ void __launch_bounds__(256) k_fix_mul(const uint32_t* __restrict__ ta
     fix_sum(table, s, acc);
     uint32_t x[12], y[12];
     to_affine_raw(acc, x, y);
-    if (out_aff) {
-#pragma unroll
-        for (int w = 0; w < 12; w++) { out_aff[(size_t)i * 24 + w] = bswap32(x[11 - w]); out_aff[(size_t)i * 24 + 12 + w] = bswap32(y[11 - w]); }
-    }
-    if (out_ser) {
-        ser_flag(x, y);
-#pragma unroll
-        for (int w = 0; w < 12; w++) out_ser[(size_t)i * 12 + w] = bswap32(x[11 - w]);
-    }
+    store_result(x, y, i, out_aff, out_ser);
 }
 #else
 ;
 #endif
 
 // ---- multiplication by SECRET scalars (blsgpu_g1_mul_gen_secret, blsgpu_hd_paths_secret) ---------------------------------
-// out_i = s_i G1 with a schedule that does not look at the scalar; vmgen/g1fixs_model.py is the specification of the
-// table and of the window schedule (tests/test_g1fixs_model.py: its value against the host's double-and-add, its trace the
-// same for every scalar).  k_g2_smul's conventions (blsgpu_g2smul.hip), cheaper because the point is fixed and public:
-//
-// WHAT IS CLAIMED: the sequence of instructions and of memory addresses does not depend on the scalars.  No branch, loop
-// bound, load address or store address is computed from a scalar byte:
-//   recoding   k_g2_smul's: the nibbles of s + C, C = sum_w 8 16^w over 65 windows, minus 8 are digits d_w in [-8, 8) with
-//              sum_w d_w 16^w = s for every s < 2^256 (s + C < 16^65: no case split).  Nine additions with carry; the nine
-//              words lie in LDS at the lane's own slot and are read by the window index.
+// out_i = s_i G1 on secret_window.h's schedule -- the claim and its limits are stated there; vmgen/g1fixs_model.py is the
+// specification of the table and of the window schedule.  Particular to this kernel, cheaper than k_g2_smul because the
+// point is fixed and public:
 //   table      a SECOND table per context: entry (w, e) = (e + 1) 16^w G1 for w < 65, e < 8, affine (x, y) in L28 form --
-//              520 x 112 bytes = 58 240 bytes, built once (k_fix_table_secret).  The 8-bit table above is not used.
-//   window     every lane reads all eight entries of window w -- the address depends on w alone, the same for every lane
-//              (the compiler issues them as scalar loads) -- and keeps one by compare-and-select on |d| == e + 1; y or the
-//              normalised -y by select; then ONE complete mixed addition (r28::pmadd).  A zero digit cannot be an affine
-//              addend: entry 0 is added all the same and the old accumulator kept by a per-limb select.  Nothing is
-//              skipped: 65 mixed additions and no doubling for every scalar, 0 and 2^256 - 1 included.
-//   output     to_affine_raw: fq_inv is the fixed-length branch-free inversion, 0 -> 0, so infinity leaves as (0, 0).
-//              ser_flag looks at the public result only.
-//   tail       spare lanes of the last workgroup repeat the last scalar and store nothing (a matter of the index).
-// WHAT IS NOT CLAIMED: data-dependent timing inside the hardware (the duration of an instruction, of a cache or memory
-// access as a function of the values it handles).  The scalars are the literal 256-bit integers: no reduction mod n is
-// needed, s G1 = (s mod n) G1, so the bytes are those of k_fix_mul.
-constexpr uint32_t S_WINDOWS = 65, S_TAB = 8, S_REC_WORDS = 9;
-constexpr uint32_t S_ENTRIES = S_WINDOWS * S_TAB;
-constexpr size_t S_TABLE_BYTES = (size_t)S_ENTRIES * ENTRY_DW * 4;
-
-// The signed-window table: entry w * 8 + e holds (e + 1) 16^w G1 -- one entry per lane, double-and-add over the 4 bits of
-// e + 1, then 4w doublings, then the affine form.  Once per context; nothing here depends on a scalar.
-__global__ void __launch_bounds__(64) k_fix_table_secret(Gen g, uint32_t* __restrict__ table)
-#if BLSGPU_EMIT(BLSGPU_TU_FIX)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= S_ENTRIES) return;
-    const uint32_t w = i / S_TAB, d = i % S_TAB + 1u;
-    const r28::fe gx = r28::from_raw(g.x), gy = r28::from_raw(g.y);
-    r28::ptT<r28::fe> acc = r28::pt_inf<r28::fe>();
-#pragma unroll 1
-    for (int b = 3; b >= 0; b--) {
-        acc = r28::pdbl(acc);
-        if ((d >> b) & 1u) r28::pmadd(acc, gx, gy);
-    }
-#pragma unroll 1
-    for (uint32_t t = 0; t < 4u * w; t++) acc = r28::pdbl(acc);
-    uint32_t x[12], y[12];
-    to_affine_raw(acc, x, y);
-    r28::st(r28::from_raw(x), table + (size_t)i * ENTRY_DW);
-    r28::st(r28::from_raw(y), table + (size_t)i * ENTRY_DW + r28::NL);
-}
-#else
-;
-#endif
-
-// out_i = s_i G1 for n >= 1 scalars (32 bytes big-endian) on k_fix_table_secret's table.  out_aff (n x 96 bytes, (0, 0) for
-// infinity) and out_ser (n x 48 bytes, PublicKey.serialize()) as k_fix_mul writes them; each may be NULL.
+//              520 x 112 bytes = 58 240 bytes, built once (k_fix_table_t<4>).  The 8-bit table above is not used.  The powers
+//              of 16 are in the table: 65 mixed additions (r28::pmadd) and NO doubling for every scalar.
+//   window     the address of window w's eight entries depends on w alone, the same for every lane (the compiler issues
+//              them as scalar loads).  A zero digit cannot be an affine addend: entry 0 is selected and added all the same
+//              and the old accumulator kept by a per-limb select.
+//   output     to_affine_raw, then store_result as k_fix_mul: s G1 = (s mod n) G1, so the bytes are those of k_fix_mul.
+// out_i = s_i G1 for n >= 1 scalars (32 bytes big-endian).  out_aff (n x 96 bytes, (0, 0) for infinity) and out_ser (n x 48
+// bytes, PublicKey.serialize()) as k_fix_mul writes them; each may be NULL.
 __global__ void __launch_bounds__(256) k_fix_mul_secret(const uint32_t* __restrict__ table, const uint32_t* __restrict__ scalars, uint32_t n,
                                                         uint32_t* __restrict__ out_aff, uint32_t* __restrict__ out_ser)
 #if BLSGPU_EMIT(BLSGPU_TU_FIX)
 {
-    __shared__ uint32_t rec[S_REC_WORDS][256];
+    __shared__ uint32_t rec[swin::REC_WORDS][256];
     const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x;
     const uint32_t i = min(tid, n - 1u);
     const bool store = tid < n;
-    {   // s + C into the lane's own slot
-        uint64_t t = 0;
-#pragma unroll
-        for (int j = 0; j < (int)S_REC_WORDS; j++) {
-            t += (uint64_t)(j < 8 ? bswap32(scalars[(size_t)i * 8 + 7 - j]) : 0u) + (j < 8 ? 0x88888888u : 0x8u);
-            rec[j][lane] = (uint32_t)t;
-            t >>= 32;
-        }
-    }
+    swin::recode(rec, lane, scalars + (size_t)i * 8);
     r28::ptT<r28::fe> acc = r28::pt_inf<r28::fe>();
 #pragma unroll 1
-    for (uint32_t w = 0; w < S_WINDOWS; w++) {
-        const int32_t d = (int32_t)((rec[w >> 3][lane] >> (4u * (w & 7u))) & 15u) - 8;
-        const uint32_t sgn = (uint32_t)(d >> 31);                          // all ones for a negative digit
-        const uint32_t ad = ((uint32_t)d ^ sgn) - sgn;                     // |d|: 0 .. 8
-        const uint32_t mz = 0u - (uint32_t)(ad == 0u);                     // zero digit: entry 0 is added, the sum dropped
-        const uint32_t* T = table + (size_t)w * (S_TAB * ENTRY_DW);        // the same address in every lane
+    for (uint32_t w = 0; w < swin::WINDOWS; w++) {
+        const swin::Digit d = swin::digit(rec, lane, w);
         uint32_t q[ENTRY_DW];
-#pragma unroll
-        for (int j = 0; j < (int)ENTRY_DW; j++) q[j] = T[j] & (mz | (0u - (uint32_t)(ad == 1u)));
-#pragma unroll
-        for (uint32_t e = 1; e < S_TAB; e++) {                             // every entry is read; the mask keeps one
-            const uint32_t m = 0u - (uint32_t)(ad == e + 1u);
-#pragma unroll
-            for (int j = 0; j < (int)ENTRY_DW; j++) q[j] |= T[e * ENTRY_DW + j] & m;
-        }
+        swin::select_entry<ENTRY_DW, true>(q, table + (size_t)w * (swin::TAB * ENTRY_DW), 1, d.ad, d.mz);
         r28::fe x, y;
 #pragma unroll
         for (int j = 0; j < r28::NL; j++) { x.v[j] = (int32_t)q[j]; y.v[j] = (int32_t)q[r28::NL + j]; }
         const r28::fe yn = r28::norm(r28::neg(y));
 #pragma unroll
-        for (int j = 0; j < r28::NL; j++) y.v[j] = (int32_t)(((uint32_t)yn.v[j] & sgn) | ((uint32_t)y.v[j] & ~sgn));
+        for (int j = 0; j < r28::NL; j++) y.v[j] = swin::sel(yn.v[j], y.v[j], d.sgn);
         const r28::ptT<r28::fe> old = acc;
         r28::pmadd(acc, x, y);
 #pragma unroll
-        for (int j = 0; j < r28::NL; j++) {
-            acc.X.v[j] = (int32_t)(((uint32_t)old.X.v[j] & mz) | ((uint32_t)acc.X.v[j] & ~mz));
-            acc.Y.v[j] = (int32_t)(((uint32_t)old.Y.v[j] & mz) | ((uint32_t)acc.Y.v[j] & ~mz));
-            acc.Z.v[j] = (int32_t)(((uint32_t)old.Z.v[j] & mz) | ((uint32_t)acc.Z.v[j] & ~mz));
+        for (int j = 0; j < r28::NL; j++) {                                // a zero digit: the sum is dropped
+            acc.X.v[j] = swin::sel(old.X.v[j], acc.X.v[j], d.mz);
+            acc.Y.v[j] = swin::sel(old.Y.v[j], acc.Y.v[j], d.mz);
+            acc.Z.v[j] = swin::sel(old.Z.v[j], acc.Z.v[j], d.mz);
         }
     }
     uint32_t x[12], y[12];
     to_affine_raw(acc, x, y);
-    if (out_aff && store) {
-#pragma unroll
-        for (int w = 0; w < 12; w++) { out_aff[(size_t)i * 24 + w] = bswap32(x[11 - w]); out_aff[(size_t)i * 24 + 12 + w] = bswap32(y[11 - w]); }
-    }
-    if (out_ser && store) {
-        ser_flag(x, y);
-#pragma unroll
-        for (int w = 0; w < 12; w++) out_ser[(size_t)i * 12 + w] = bswap32(x[11 - w]);
-    }
+    store_result(x, y, i, store ? out_aff : nullptr, store ? out_ser : nullptr);
 }
 #else
 ;

@@ -145,8 +145,7 @@ __global__ void __launch_bounds__(256) k_poly_eval(const uint32_t* __restrict__ 
     if (out_aff) {
         uint32_t ax[12], ay[12];
         g1fix::to_affine_raw(R, ax, ay);
-#pragma unroll
-        for (int w = 0; w < 12; w++) { out_aff[(size_t)i * 24 + w] = bswap32(ax[11 - w]); out_aff[(size_t)i * 24 + 12 + w] = bswap32(ay[11 - w]); }
+        g1fix::store_result(ax, ay, i, out_aff, nullptr);
     }
 }
 #else

@@ -1,45 +1,34 @@
 // blsgpu_g2smul.hip -- G2 scalar multiplication with a schedule that does not look at the scalar: out_i = s_i P_i, one scalar
 // per LANE PAIR on sp2's point arithmetic (blsgpu_msm.hip), for blsgpu_g2_mul_secret and blsgpu_sign (included by
-// blsgpu_api.hip).  vmgen/g2smul_model.py is the specification of the recoding and of the window schedule; tests/
-// test_g2smul_model.py holds it against the host's curve arithmetic and checks that its trace is the same for every scalar.
-//
-// WHAT IS CLAIMED: the sequence of instructions and of memory addresses does not depend on the scalars.  No branch, loop
-// bound, load address or store address is computed from a scalar byte:
-//   recoding   signed 4-bit digits by the sorted sums' trick (blsgpu_msm.hip SIGNED digits): the nibbles of s + C,
-//              C = sum_w 8 16^w over 65 windows, minus 8 are digits d_w in [-8, 8) with sum_w d_w 16^w = s for every
-//              s < 2^256 (s + C < 16^65).  Nine additions with carry, no branch on a value; the nine words lie in LDS
-//              at the lane pair's own slot and are read by the window index.
+// blsgpu_api.hip).  The schedule, the claim and its limits are secret_window.h's; vmgen/g2smul_model.py is the specification
+// (tests/test_g2smul_model.py).  Particular to this kernel:
 //   table      1P .. 8P per scalar in the L28 projective form (k_g2_smul_table: seven complete additions of P), dword j of
-//              entry e of lane t at table[(e 42 + j) stride + t]: the lanes of a wavefront read consecutive dwords.  When
-//              every scalar multiplies the same point the table is built once (stride 2) and every pair reads the same entries.
-//   window     four complete doublings (RCB algorithm 9), then ONE complete addition (algorithm 7) of the selected entry:
-//              all eight entries are read and one is kept by compare-and-select, y or -y is kept by select, and a zero
-//              digit selects the constant (0 : 1 : 0) -- the complete addition makes that a no-op, nothing is skipped.
-//              65 windows: 260 doublings and 65 additions for every scalar, 0 and 2^256 - 1 included.
+//              entry e of lane t at table[(e 42 + j) stride + t]: the lanes of a wavefront read consecutive dwords (vector
+//              loads, a loop of eight rounds).  When every scalar multiplies the same point the table is built once
+//              (stride 2) and every pair reads the same entries.
+//   window     from the top window down, four complete doublings (RCB algorithm 9), then ONE complete addition (algorithm
+//              7) of the selected entry; a zero digit selects nothing and ORs in the constant (0 : 1 : 0) -- the complete
+//              addition makes that a no-op.  260 doublings and 65 additions for every scalar.
 //   input      an input point (0, 0) enters as (0 : 1 : 0) by select (the point is public all the same).
-//   output     (X, Y) / Z through the norm of Z and fq32.h's fq_inv: 37 batches of 30 division steps, branch-free and of
-//              fixed length (the form k_msm_horner_quads and the hash use), 0 -> 0, so infinity leaves as (0, 0); the
-//              compression of Signature.serialize() (ec.py:94-111) is done here by masks.
-//   tail       spare pairs of the last workgroup repeat the last scalar and store nothing (a matter of the index).
-// WHAT IS NOT CLAIMED: data-dependent timing inside the hardware (the duration of an instruction, of a cache or memory
-// access as a function of the values it handles), and anything about H(m): the message-dependent hash to G2 that
-// blsgpu_sign runs first is public and keeps its own kernels.  The scalars are the literal 256-bit integers, not reduced
-// mod the group order -- the `scalars` of blsgpu_g2_msm.
+//   output     (X, Y) / Z through the norm of Z and fq_inv; the compression of Signature.serialize() (ec.py:94-111) is done
+//              here by masks.  Nothing is claimed about H(m): the message-dependent hash to G2 that blsgpu_sign runs first
+//              is public and keeps its own kernels.  The scalars are the `scalars` of blsgpu_g2_msm.
 //
 // Slices: a launch takes at most SLICE = 65 536 scalars (two wavefronts on every SIMD of the chip), so the table
 // workspace is bounded by 65 536 x 2688 bytes = 168 MiB whatever the size of the call.
 #pragma once
 
+#include "secret_window.h"
+
 namespace blsgpu {
 namespace g2smul {
 using namespace sp2;
+using swin::TAB;
 
-constexpr uint32_t WINDOWS = 65, TAB = 8;
 constexpr uint32_t PT_DW = 3 * r28::NL;                       // a lane's half of a projective point: X, Y, Z
 constexpr uint32_t TABLE_DW = TAB * 2 * PT_DW;                // dwords of one pair's table
 constexpr uint32_t PAIRS = 128;                               // lane pairs per 256-thread workgroup
 constexpr size_t SLICE = 65536;                               // scalars per launch
-constexpr uint32_t REC_WORDS = 9;                             // words of s + C
 
 // table of point u (n_tab points, 192 bytes affine big-endian each, (0, 0) = infinity): entry e = (e + 1) P
 __global__ void __launch_bounds__(256, 2) k_g2_smul_table(const uint32_t* __restrict__ pts, uint32_t n_tab, uint32_t* __restrict__ table)
@@ -84,17 +73,6 @@ __global__ void __launch_bounds__(256, 2) k_g2_smul_table(const uint32_t* __rest
 ;
 #endif
 
-// all ones when y > q // 2 (twelve words, least significant first), by masks
-__device__ __forceinline__ uint32_t gt_half_q_mask(const uint32_t y[12]) {
-    uint32_t gt = 0, eq = ~0u;
-#pragma unroll
-    for (int w = 11; w >= 0; w--) {
-        gt |= eq & (0u - (uint32_t)(y[w] > g1fix::HALF_Q_WORDS[w]));
-        eq &= 0u - (uint32_t)(y[w] == g1fix::HALF_Q_WORDS[w]);
-    }
-    return gt;
-}
-
 // out_i = s_i (the table's point) for n <= SLICE scalars (32 bytes big-endian).  table / tstride: k_g2_smul_table's, of n
 // points (tstride 2 n) or, shared != 0, of one point (tstride 2).  out_aff: n x 192 bytes ((0, 0) for infinity), out_ser: n x 96
 // bytes (Signature.serialize(): x.c0 || x.c1 with 0x80 on the first byte when the imaginary part of y exceeds q // 2; zeros
@@ -104,49 +82,31 @@ __global__ void __launch_bounds__(256, 2) k_g2_smul(const uint32_t* __restrict__
                                                    uint32_t* __restrict__ out_ser, uint8_t* __restrict__ out_inf)
 #if BLSGPU_EMIT(BLSGPU_TU_MSM)
 {
-    __shared__ uint32_t rec[REC_WORDS][PAIRS];
+    __shared__ uint32_t rec[swin::REC_WORDS][PAIRS];
     const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t g = min(tid >> 1, n - 1u), part = tid & 1u, lp = threadIdx.x >> 1;
     const bool store = (tid >> 1) < n;
-    {   // s + C: both lanes of the pair write the same words to the pair's slot
-        uint64_t t = 0;
-#pragma unroll
-        for (int j = 0; j < (int)REC_WORDS; j++) {
-            t += (uint64_t)(j < 8 ? bswap32(scalars[(size_t)g * 8 + 7 - j]) : 0u) + (j < 8 ? 0x88888888u : 0x8u);
-            rec[j][lp] = (uint32_t)t;
-            t >>= 32;
-        }
-    }
+    swin::recode(rec, lp, scalars + (size_t)g * 8);                        // both lanes of the pair write the same words
     const uint32_t* T = table + (shared ? part : 2u * g + part);
     const int32_t one[r28::NL] = BLS28_ONE;
     pt acc = pt_inf();
 #pragma unroll 1
-    for (int w = (int)WINDOWS - 1; w >= 0; w--) {
+    for (int w = (int)swin::WINDOWS - 1; w >= 0; w--) {
 #pragma unroll 1
         for (int s = 0; s < 4; s++) acc = pdbl(acc);
-        const int32_t d = (int32_t)((rec[w >> 3][lp] >> (4 * (w & 7))) & 15u) - 8;
-        const uint32_t sgn = (uint32_t)(d >> 31);                          // all ones for a negative digit
-        const uint32_t ad = ((uint32_t)d ^ sgn) - sgn;                     // |d|: 0 .. 8
+        const swin::Digit d = swin::digit(rec, lp, (uint32_t)w);
         uint32_t q[PT_DW];
-#pragma unroll
-        for (int j = 0; j < (int)PT_DW; j++) q[j] = 0;
-#pragma unroll 1
-        for (uint32_t e = 0; e < TAB; e++) {                               // every entry is read; the mask keeps one
-            const uint32_t m = 0u - (uint32_t)(ad == e + 1u);
-#pragma unroll
-            for (int j = 0; j < (int)PT_DW; j++) q[j] |= T[(size_t)(e * PT_DW + j) * tstride] & m;
-        }
-        const uint32_t mz = 0u - (uint32_t)(ad == 0u);                     // zero digit: (0 : 1 : 0)
+        swin::select_entry<PT_DW, false>(q, T, tstride, d.ad, 0u);
         pt Q;
 #pragma unroll
-        for (int j = 0; j < r28::NL; j++) {
+        for (int j = 0; j < r28::NL; j++) {                                // zero digit: q = 0, (0 : 1 : 0)
             Q.X.v[j] = (int32_t)q[j];
-            Q.Y.v[j] = (int32_t)(q[r28::NL + j] | ((uint32_t)(odd() ? 0 : one[j]) & mz));
+            Q.Y.v[j] = (int32_t)(q[r28::NL + j] | ((uint32_t)(odd() ? 0 : one[j]) & d.mz));
             Q.Z.v[j] = (int32_t)q[2 * r28::NL + j];
         }
         const h yn = norm(neg(Q.Y));
 #pragma unroll
-        for (int j = 0; j < r28::NL; j++) Q.Y.v[j] = (int32_t)(((uint32_t)yn.v[j] & sgn) | ((uint32_t)Q.Y.v[j] & ~sgn));
+        for (int j = 0; j < r28::NL; j++) Q.Y.v[j] = swin::sel(yn.v[j], Q.Y.v[j], d.sgn);
         acc = padd(acc, Q);
     }
     // affine: (X, Y) / Z with 1 / Z = conj(Z) / N(Z); Z = 0 gives (0, 0) (the tail of k_msm_horner_quads on a lane pair)
@@ -182,7 +142,7 @@ __global__ void __launch_bounds__(256, 2) k_g2_smul(const uint32_t* __restrict__
     }
     if (out_inf && store && part == 0u) out_inf[g] = any ? 0 : 1;
     if (out_ser) {
-        const uint32_t big = gt_half_q_mask(yr);                          // the odd lane's decides: the imaginary part of y
+        const uint32_t big = bls::gt_half_q_mask(yr);                          // the odd lane's decides: the imaginary part of y
         const uint32_t flag = (uint32_t)__shfl_xor((int)big, 1) & (part ? 0u : 0x80000000u);
         xr[11] |= flag;
         if (store) {

@@ -519,6 +519,31 @@ __global__ void __launch_bounds__(256) k_lane_prep(const uint32_t* __restrict__ 
 ;
 #endif
 
+// Digit `win` of scalar i (32 bytes big-endian; scalars NULL: every scalar is 1) for k_msm_lane / k_msm_lane2x.  Signed
+// digits: the nibbles of s + 0x88..8 minus 8 are digits in [-8, 7] with the same value (no carry out of 256 bits while
+// s < 2^256 - 0x88..8, which covers every scalar below the group order), so 8 buckets take +-P and the running sums cover 8
+// buckets instead of 15.  A larger scalar (`big`) keeps its plain nibbles (buckets 1 .. 15); the lanes of a wavefront see
+// the same scalars, so `big` is uniform.  Variable-time: it branches on the scalar (secret_window.h is the form that does not).
+__device__ __forceinline__ int lane_digit(const uint32_t* __restrict__ scalars, uint32_t i, uint32_t win, bool& big) {
+    uint32_t word;                                                              // the 32 bits that hold this window's nibble
+    big = false;
+    if (scalars) {
+        const uint32_t* sc = scalars + (size_t)i * 8;
+        big = bswap32(sc[0]) > 0x77777776u;
+        if (!big) {
+            uint32_t c = 0;
+            word = 0;
+            for (uint32_t j = 0; j <= win / 8; j++) word = bls::addc(bswap32(sc[7u - j]), 0x88888888u, c);
+        } else {
+            word = bswap32(sc[7 - win / 8]);
+        }
+    } else {
+        word = (win < 8) ? 0x88888889u : 0x88888888u;
+    }
+    const int nib = (int)((word >> (4 * (win % 8))) & 15u);
+    return big ? nib : nib - 8;
+}
+
 // prep / live: k_lane_prep's; partial (win, chunk) of group g is written at partials[((g * PIP_W + win) * chunks +
 // chunk) * PJ] -- the layout k_msm_pip_windows reads -- in the VM's form (PJ = 36 DEG) when vm_out, else L28 (42 DEG).
 template <int DEG>
@@ -539,31 +564,12 @@ __global__ void __launch_bounds__(64) k_msm_lane(const uint32_t* __restrict__ pr
         const r28::ptT<E> inf = r28::pt_inf<E>();
         for (int j = 0; j < PIP_NB - 1; j++) r28::pt_st(inf, B + j * PJ_DW);
     }
-    // Signed digits: the nibbles of s + 0x88..8 minus 8 are digits in [-8, 7] with the same value (no carry out of
-    // 256 bits while s < 2^256 - 0x88..8, which covers every scalar below the group order), so 8 buckets take
-    // +-P and the running sums below cover 8 buckets instead of 15.  A larger scalar keeps its plain nibbles
-    // (buckets 1 .. 15); the lanes of a wavefront see the same scalars, so `wide` is uniform.
-    bool wide = false;
+    bool wide = false;                                                          // (lane_digit; uniform over the wavefront)
 #pragma unroll 1
     for (uint32_t i = lo; i < hi; i++) {
         if (!live[i]) continue;                                                 // the point at infinity
-        uint32_t word;                                                          // the 32 bits that hold this window's nibble
-        bool big = false;
-        if (scalars) {
-            const uint32_t* sc = scalars + (size_t)i * 8;
-            big = bswap32(sc[0]) > 0x77777776u;
-            if (!big) {
-                uint32_t c = 0;
-                word = 0;
-                for (uint32_t j = 0; j <= win / 8; j++) word = bls::addc(bswap32(sc[7u - j]), 0x88888888u, c);
-            } else {
-                word = bswap32(sc[7 - win / 8]);
-            }
-        } else {
-            word = (win < 8) ? 0x88888889u : 0x88888888u;
-        }
-        const int nib = (int)((word >> (4 * (win % 8))) & 15u);
-        const int d = big ? nib : nib - 8;
+        bool big;
+        const int d = lane_digit(scalars, i, win, big);
         wide = wide || big;
         if (d != 0) {
             uint32_t* b = B + ((d < 0 ? -d : d) - 1) * PJ_DW;
@@ -913,23 +919,8 @@ __global__ void __launch_bounds__(64, BLSGPU_MSM_LANE2X_WAVES) k_msm_lane2x(cons
 #pragma unroll 1
     for (uint32_t i = lo; i < hi; i++) {
         if (!live[i]) continue;
-        uint32_t word;
-        bool big = false;
-        if (scalars) {
-            const uint32_t* sc = scalars + (size_t)i * 8;
-            big = bswap32(sc[0]) > 0x77777776u;
-            if (!big) {
-                uint32_t c = 0;
-                word = 0;
-                for (uint32_t j = 0; j <= win / 8; j++) word = bls::addc(bswap32(sc[7u - j]), 0x88888888u, c);
-            } else {
-                word = bswap32(sc[7 - win / 8]);
-            }
-        } else {
-            word = (win < 8) ? 0x88888889u : 0x88888888u;
-        }
-        const int nib = (int)((word >> (4 * (win % 8))) & 15u);
-        const int d = big ? nib : nib - 8;
+        bool big;
+        const int d = lane_digit(scalars, i, win, big);
         wide = wide || big;
         if (d != 0) {
             uint32_t* b = B + ((d < 0 ? -d : d) - 1) * PJ_DW;

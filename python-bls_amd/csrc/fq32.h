@@ -569,4 +569,18 @@ BLS_HD int fq_jacobi_var(const uint32_t* __restrict__ a) {
     return res;
 }
 
+// q // 2 and the test of the compressed forms (ec.py:94-111 of the reference: 0x80 on x when y > q // 2): all ones when
+// the canonical y (twelve words, least significant first) exceeds it, by masks -- no branch on y
+constexpr uint32_t HALF_Q_WORDS[12] = {0xffffd555u, 0xdcff7fffu, 0x58a9ffffu, 0x0f55ffffu, 0x7b587b12u, 0xb3986950u,
+                                       0x79c2895fu, 0xb23ba5c2u, 0x21a5d66bu, 0x258dd3dbu, 0x1cbff34du, 0x0d0088f5u};
+BLS_HD uint32_t gt_half_q_mask(const uint32_t y[12]) {
+    uint32_t gt = 0, eq = ~0u;
+#pragma unroll
+    for (int w = 11; w >= 0; w--) {
+        gt |= eq & (0u - (uint32_t)(y[w] > HALF_Q_WORDS[w]));
+        eq &= 0u - (uint32_t)(y[w] == HALF_Q_WORDS[w]);
+    }
+    return gt;
+}
+
 }  // namespace bls

@@ -1,9 +1,9 @@
-"""Integer model of the scalar-independent fixed-base G1 multiplication (csrc/blsgpu_g1fix.hip k_fix_table_secret /
+"""Integer model of the scalar-independent fixed-base G1 multiplication (csrc/blsgpu_g1fix.hip k_fix_table_t<4> /
 k_fix_mul_secret): the SPECIFICATION of its table and of its schedule.  out = s G1 for the literal integer s < 2^256 (G1 has
 order n, so this is (s mod n) G1, the value of k_fix_mul), computed so that WHAT is done and WHICH table entries are touched
-is the same for every s.
+is the same for every s -- what that claims and what it does not is stated once, in csrc/secret_window.h.
 
-  recode(s)      g2smul_model's: signed 4-bit digits d_w in [-8, 8), 65 windows, sum_w d_w 16^w = s.
+  recode(s)      g2smul_model's, as are WINDOWS and TABLE: signed 4-bit digits d_w in [-8, 8), 65 windows.
   build_table()  T[w][e] = (e + 1) 16^w G1 for w < 65, e < 8 -- 520 affine points, built once per context.  The base point
                  is fixed and public, so the powers of 16 are in the table and the schedule has NO doubling.
   mul_gen(s)     for every window, least significant first: READ ALL EIGHT entries of the window and keep T[w][|d| - 1]
@@ -16,16 +16,14 @@ Every step appends (operation, entries read) to a trace; the trace is what must 
 not appear in the trace, as it does not appear in the device's instruction stream or addresses.
 """
 from bls_py import hostmath as H
-from .g2smul_model import recode
+from .g2smul_model import TABLE, WINDOWS, recode
 
-WINDOWS = 65
-TABLE = 8
 ENTRY_BYTES = 112                                         # affine (x, y) in L28 form: 2 x 14 limbs of 4 bytes
 TABLE_BYTES = WINDOWS * TABLE * ENTRY_BYTES
 
 
 def build_table():
-    """T[w][e] = (e + 1) 16^w G1 as Jacobian points; k_fix_table_secret"""
+    """T[w][e] = (e + 1) 16^w G1 as Jacobian points; k_fix_table_t<4>"""
     T = []
     base = H.aff_to_jac(H.F1, H.G1_GEN)
     for _ in range(WINDOWS):

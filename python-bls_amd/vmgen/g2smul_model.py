@@ -1,6 +1,7 @@
 """Integer model of the scalar-independent G2 multiplication (csrc/blsgpu_g2smul.hip k_g2_smul_table / k_g2_smul): the
 SPECIFICATION of its schedule.  out = s P for the literal integer s < 2^256 (no reduction mod the group order, as the
 `scalars` of blsgpu_g2_msm), computed so that WHAT is done and WHICH table entries are touched is the same for every s.
+What that claims and what it does not is stated once, in csrc/secret_window.h.
 
 Two parts:
 

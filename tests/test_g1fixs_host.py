@@ -1,6 +1,8 @@
 """The masked scalar helpers of csrc/hd_derive.h (reduce_n_masked, add_mod_n_masked: the subtraction kept by a mask, no
 branch on the borrow -- blsgpu_hd_paths_secret) compiled for the host against Python integers and against the branching
-forms beside them; and the secret=True keyword of the key methods on a provider that lacks the device calls."""
+forms beside them; the y > q // 2 test of the compressed forms (fq32.h gt_half_q_mask, shared by the G1 and G2 kernels and
+the host) at its tie and single-word cases; and the secret=True keyword of the key methods on a provider that lacks the
+device calls."""
 import os
 import random
 import subprocess
@@ -69,6 +71,48 @@ def test_masked_addition(exe):
     combos = [(a, b) for a in EDGES for b in EDGES]
     got = _run(exe, ["addn %064x %064x" % (red[a], red[b]) for a, b in combos])
     assert [g[0] for g in got] == [(a + b) % N for a, b in combos]
+
+
+HALF_Q_TEST = r'''
+#include "fq32.h"
+#include <stdio.h>
+int main() {
+    char a[128];
+    while (scanf("%127s", a) == 1) {
+        uint32_t y[12];
+        for (int j = 0; j < 12; j++) { unsigned v; sscanf(a + 8 * j, "%8x", &v); y[11 - j] = v; }
+        printf("%08x\n", bls::gt_half_q_mask(y));
+    }
+    return 0;
+}
+'''
+Q = 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab
+
+
+def test_gt_half_q_mask(tmp_path):
+    """all ones exactly when y > q // 2: the ends, the tie and its neighbours, and values that differ from q // 2 in one
+    word only (the lowest, the highest, one in the middle), below and above -- cases no curve coordinate of the device tests
+    reaches"""
+    src, out = tmp_path / "h.cpp", tmp_path / "h"
+    src.write_text(HALF_Q_TEST)
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-I", CSRC, "-o", str(out), str(src)])
+    half = Q // 2
+    low, high = half & 0xFFFFFFFF, half >> 352
+
+    def word(j, v):
+        return (half & ~(0xFFFFFFFF << (32 * j))) | (v << (32 * j))
+    vals = [0, half - 1, half, half + 1, Q - 1]
+    vals += [word(0, 0), word(0, low - 0x1000), word(0, low + 1), word(0, 0xFFFFFFFF)]
+    vals += [word(11, 0), word(11, high - 1), word(11, high + 1), word(11, Q >> 352)]
+    mid = (half >> 160) & 0xFFFFFFFF
+    vals += [word(5, mid - 1), word(5, mid + 1)]
+    rnd = random.Random(33)
+    vals += [rnd.randrange(Q) for _ in range(200)]
+    assert all(0 <= v < 1 << 384 for v in vals)
+    res = subprocess.run([str(out)], input="\n".join("%096x" % v for v in vals) + "\n", capture_output=True, text=True, check=True)
+    got = [int(ln, 16) for ln in res.stdout.split()]
+    assert got == [0xFFFFFFFF if v > half else 0 for v in vals]
+    assert sum(1 for g in got if g) > 50 and sum(1 for g in got if not g) > 50
 
 
 class _DigitIndexedOnly:

@@ -1,5 +1,5 @@
 """The integer model of the scalar-independent fixed-base G1 multiplication (vmgen/g1fixs_model.py, the specification of
-csrc/blsgpu_g1fix.hip k_fix_table_secret / k_fix_mul_secret): its table, the value of the window schedule against the
+csrc/blsgpu_g1fix.hip k_fix_table_t<4> / k_fix_mul_secret): its table, the value of the window schedule against the
 host's double-and-add and the reference's public keys (tests/golden/keygen.json), and the uniformity of its trace -- the
 same operations on the same table entries for every scalar."""
 import json
