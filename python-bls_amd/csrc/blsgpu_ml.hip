@@ -66,11 +66,27 @@ __device__ __forceinline__ fe load_coord(const uint32_t* __restrict__ src) {    
 namespace sp {
 template <int M> struct S { int32_t v[NL]; };          // the lane's part; limbs in (-M 2^28, M 2^28)
 typedef S<1> h;
+// An h whose limbs 0 .. 12 are DIGITS, in [0, 2^28): what a product, a carry pass or a load returns (h alone may be a negated value).
+// A sum of two of them has limbs in [0, 2^29) -- half the range of an S<2> --, which is what lets sqr() take it as it is (round 8).
+struct hn : h {};
+struct hn2 { int32_t v[NL]; };
+__device__ __forceinline__ hn2 addn(const hn& x, const hn& y) { hn2 r;
+#pragma unroll
+    for (int j = 0; j < NL; j++) r.v[j] = x.v[j] + y.v[j];
+    return r; }
 __device__ __forceinline__ bool odd() { return (threadIdx.x & 1u) != 0; }
+// A lane reads a part of its pair through DPP quad_perm: the partner's part [1,0,3,2], the real part on both lanes [0,0,2,2],
+// the imaginary part on both [1,1,3,3].  Where the read feeds an add, a sub or a bit operation it is that instruction's
+// operand (v_add_u32_dpp ...), not a move of its own -- the forms below are written so that every read has such a use
+// (round 8: no select, whose VOP3 form takes no DPP operand; the lane's parity enters as the mask even_mask()).
+constexpr int QP_SWAP = 0xB1, QP_RE = 0xA0, QP_IM = 0xF5;
+template <int QP> __device__ __forceinline__ int32_t qp(int32_t x) { return __builtin_amdgcn_update_dpp(0, x, QP, 0xF, 0xF, true); }
+// even lane: all ones, odd lane: 0 -- opaque to the optimiser, which would turn x & mask back into a select
+__device__ __forceinline__ int32_t even_mask() { int32_t m = (int32_t)(threadIdx.x & 1u) - 1; asm("" : "+v"(m)); return m; }
 template <int M> __device__ __forceinline__ S<M> swp(const S<M>& x) {
     S<M> r;
 #pragma unroll
-    for (int j = 0; j < NL; j++) r.v[j] = __builtin_amdgcn_update_dpp(0, x.v[j], 0xB1, 0xF, 0xF, true);
+    for (int j = 0; j < NL; j++) r.v[j] = qp<QP_SWAP>(x.v[j]);
     return r;
 }
 template <int A, int B> __device__ __forceinline__ S<A + B> add(const S<A>& x, const S<B>& y) { S<A + B> r;
@@ -89,18 +105,18 @@ template <int C, int A> __device__ __forceinline__ S<C * A> mulc(const S<A>& x) 
 #pragma unroll
     for (int j = 0; j < NL; j++) r.v[j] = x.v[j] * C;
     return r; }
-template <int A> __device__ __forceinline__ h norm(const S<A>& x) {
+template <int A> __device__ __forceinline__ hn norm(const S<A>& x) {
     static_assert(A <= 8, "limb range leaves int32");
-    h r;
+    hn r;
     int32_t c = 0;
 #pragma unroll
     for (int j = 0; j < NL - 1; j++) { const int32_t t = x.v[j] + c; r.v[j] = t & r28::LMASK; c = t >> r28::LW; }
     r.v[NL - 1] = x.v[NL - 1] + c;
     return r;
 }
-template <int C, int A> __device__ __forceinline__ h mulc_norm(const S<A>& x) {
-    static_assert(C > 0 && C < (1 << 20) && A <= 8, "constant too large");
-    h r;
+template <int C, int A> __device__ __forceinline__ hn mulc_norm(const S<A>& x) {
+    static_assert(C != 0 && C > -(1 << 20) && C < (1 << 20) && A <= 8, "constant too large");       // (C < 0: the sign goes to digit 13)
+    hn r;
     int64_t c = 0;
 #pragma unroll
     for (int j = 0; j < NL - 1; j++) { c += (int64_t)x.v[j] * C; r.v[j] = (int32_t)((uint32_t)c & (uint32_t)r28::LMASK); c >>= r28::LW; }
@@ -109,22 +125,23 @@ template <int C, int A> __device__ __forceinline__ h mulc_norm(const S<A>& x) {
 }
 // (1 + u) x: re = a - b, im = a + b
 template <int A> __device__ __forceinline__ S<2 * A> mul_xi(const S<A>& x) {
-    const S<A> p = swp(x);
+    const int32_t m = even_mask();
     S<2 * A> r;
 #pragma unroll
-    for (int j = 0; j < NL; j++) r.v[j] = odd() ? x.v[j] + p.v[j] : x.v[j] - p.v[j];
+    for (int j = 0; j < NL; j++) r.v[j] = qp<QP_RE>(x.v[j]) + ((qp<QP_IM>(x.v[j]) ^ m) - m);
     return r;
 }
-template <int A> __device__ __forceinline__ h b3(const S<A>& x) { return mulc_norm<12>(mul_xi(x)); }      // 12 (1 + u) x
+template <int A> __device__ __forceinline__ hn b3(const S<A>& x) { return mulc_norm<12>(mul_xi(x)); }     // 12 (1 + u) x
 // operands of a product x y: re = x.re y.re - x.im y.im, im = x.re y.im + x.im y.re.  With o = own part, p = partner's:
-// even lane  o_x o_y + (-p_x) p_y,  odd lane  p_x o_y + o_x p_y  -- both lanes  a o_y + b p_y.
+// even lane  o_x o_y + (-p_x) p_y,  odd lane  p_x o_y + o_x p_y  -- both lanes  a o_y + b p_y:  a is the real part on both lanes,
+// b the imaginary part, negated on the even lane ((v ^ m) - m with m = even_mask()).
 template <int M> struct Lop { int32_t a[NL], b[NL]; };
 template <int M> struct Rop { int32_t o[NL], p[NL]; };
 template <int M> __device__ __forceinline__ Lop<M> left(const S<M>& x) {
-    const S<M> p = swp(x);
+    const int32_t m = even_mask();
     Lop<M> r;
 #pragma unroll
-    for (int j = 0; j < NL; j++) { r.a[j] = odd() ? p.v[j] : x.v[j]; r.b[j] = odd() ? x.v[j] : -p.v[j]; }
+    for (int j = 0; j < NL; j++) { r.a[j] = qp<QP_RE>(x.v[j]); r.b[j] = (qp<QP_IM>(x.v[j]) ^ m) - m; }
     return r;
 }
 template <int M> __device__ __forceinline__ Rop<M> right(const S<M>& x) {
@@ -135,55 +152,62 @@ template <int M> __device__ __forceinline__ Rop<M> right(const S<M>& x) {
     return r;
 }
 // column bound of fp28.h: 14 * (sum of |a||b| in units of 2^56) + 14 <= 126
-template <int MA, int MB> __device__ __forceinline__ h mul(const Lop<MA>& x, const Rop<MB>& y) {
+template <int MA, int MB> __device__ __forceinline__ hn mul(const Lop<MA>& x, const Rop<MB>& y) {
     static_assert(2 * MA * MB <= 8, "a column of this product may overflow 64 bits");
-    h r;
+    hn r;
     bls28::fp28_dot2(r.v, x.a, y.o, x.b, y.p);
     return r;
 }
 template <int MA, int MB, int MC, int MD>
-__device__ __forceinline__ h dot2(const Lop<MA>& x0, const Rop<MB>& y0, const Lop<MC>& x1, const Rop<MD>& y1) {
+__device__ __forceinline__ hn dot2(const Lop<MA>& x0, const Rop<MB>& y0, const Lop<MC>& x1, const Rop<MD>& y1) {
     static_assert(2 * MA * MB + 2 * MC * MD <= 8, "a column of this sum of products may overflow 64 bits");
-    h r;
+    hn r;
     bls28::fp28_dot4(r.v, x0.a, y0.o, x0.b, y0.p, x1.a, y1.o, x1.b, y1.p);
     return r;
 }
-// x^2: re = (a + b)(a - b), im = (2 b) a
-__device__ __forceinline__ h sqr(const h& x) {
-    const h p = swp(x);
+// x^2: re = (a + b)(a - b), im = (2 b) a.  u = own part + b on both lanes; w = a - (b on the even lane, 0 on the odd one)
+template <class T> __device__ __forceinline__ hn sqr_parts(const T& x) {
+    const int32_t m = even_mask();
     int32_t u[NL], w[NL];
 #pragma unroll
-    for (int j = 0; j < NL; j++) { u[j] = x.v[j] + (odd() ? x.v[j] : p.v[j]); w[j] = odd() ? p.v[j] : x.v[j] - p.v[j]; }
-    h r;
-    bls28::fp28_dot1(r.v, u, w);                                       // |u|, |w| < 2^29: 4 units
+    for (int j = 0; j < NL; j++) { u[j] = qp<QP_IM>(x.v[j]) + x.v[j]; w[j] = qp<QP_RE>(x.v[j]) - (qp<QP_IM>(x.v[j]) & m); }
+    hn r;
+    bls28::fp28_dot1(r.v, u, w);
     return r;
+}
+__device__ __forceinline__ hn sqr(const h& x) { return sqr_parts(x); }        // |u|, |w| < 2^29: 4 units
+// the square of a sum of two values in digits, without a carry pass: a, b in [0, 2^29), so u = a + b or 2 b in [0, 2^30) and
+// w = a - b or a in (-2^29, 2^29) -- 8 units, the whole column (an S<2> would be 16)
+__device__ __forceinline__ hn sqr(const hn2& x) {
+    static_assert(14 * (4 * 2) + 14 <= 126, "a column of this square may overflow 64 bits");
+    return sqr_parts(x);
 }
 // g^2 - 12 e^2 (round 5): the lane's part of a square is ONE product -- (a + b)(a - b) on the even lane, (2 b) a on the odd one --,
 // so the difference of the two squares is a sum of two products with one reduction (588 multiply-adds; two squares, a
 // scaling and a carry pass before: 784 + 84).  Column bound: |u|, |w| < 2^29 for g (4 units), 12 u normalised x |w| < 2^29 for e (2).
-__device__ __forceinline__ h sqr_m12sqr(const h& g, const h& e) {
-    const h pg = swp(g), pe = swp(e);
-    int32_t ug[NL], wg[NL], nwe[NL];
+__device__ __forceinline__ hn sqr_m12sqr(const h& g, const h& e) {
+    const int32_t m = even_mask();
+    int32_t ug[NL], wg[NL], we[NL];
     S<2> ue;
 #pragma unroll
     for (int j = 0; j < NL; j++) {
-        ug[j] = g.v[j] + (odd() ? g.v[j] : pg.v[j]); wg[j] = odd() ? pg.v[j] : g.v[j] - pg.v[j];
-        ue.v[j] = e.v[j] + (odd() ? e.v[j] : pe.v[j]); nwe[j] = odd() ? -pe.v[j] : pe.v[j] - e.v[j];
+        ug[j] = qp<QP_IM>(g.v[j]) + g.v[j]; wg[j] = qp<QP_RE>(g.v[j]) - (qp<QP_IM>(g.v[j]) & m);
+        ue.v[j] = qp<QP_IM>(e.v[j]) + e.v[j]; we[j] = qp<QP_RE>(e.v[j]) - (qp<QP_IM>(e.v[j]) & m);
     }
-    const h ue12 = mulc_norm<12>(ue);
-    h r;
-    bls28::fp28_dot2(r.v, ug, wg, ue12.v, nwe);
+    const h nue12 = mulc_norm<-12>(ue);                                // (the minus sign rides on the scaling)
+    hn r;
+    bls28::fp28_dot2(r.v, ug, wg, nue12.v, we);
     return r;
 }
-template <int M> __device__ __forceinline__ h mulf(const S<M>& x, const fe& k) {     // by an Fq value (both lanes hold it)
+template <int M> __device__ __forceinline__ hn mulf(const S<M>& x, const fe& k) {     // by an Fq value (both lanes hold it)
     static_assert(M <= 8, "");
-    h r;
+    hn r;
     bls28::fp28_dot1(r.v, x.v, k.v);
     return r;
 }
-__device__ __forceinline__ h load_part(const uint32_t* __restrict__ src) {       // the lane's 48 bytes -> x R
+__device__ __forceinline__ hn load_part(const uint32_t* __restrict__ src) {       // the lane's 48 bytes -> x R
     const fe t = load_coord(src);
-    h r;
+    hn r;
 #pragma unroll
     for (int j = 0; j < NL; j++) r.v[j] = t.v[j];
     return r;
@@ -229,22 +253,22 @@ struct Slab {
     __device__ __forceinline__ h yq() const { return get<h>(3); }
 };
 
-__device__ __forceinline__ void tangent_step(h& X, h& Y, h& Z, const Slab& k, int32_t* __restrict__ rec) {
+__device__ __forceinline__ void tangent_step(hn& X, hn& Y, hn& Z, const Slab& k, int32_t* __restrict__ rec) {
     // (the statements are asm volatile underneath, so this order IS the execution order: every value is consumed as
     // early as the data flow allows, which keeps the step inside 256 registers)
     // Round 4: the two mixed products as squares -- 2YZ = (Y + Z)^2 - Y^2 - Z^2 and 2XY = (X + Y)^2 - X^2 - Y^2 with the
     // squares the step computes anyway: a complex squaring is ONE product per lane (392 multiply-adds), a product a sum
-    // of two (588); the sums are normalised first (a square of 2^29-limbs would not fit the columns).  Same field
-    // elements, same line records.
+    // of two (588); the sums are taken as they are (round 8: X, Y, Z are in digits, see sqr(hn2); a carry
+    // pass each before).  Same field elements, same line records.
     const h XX = sqr(X);
     store_part(rec, 1, mulf(XX, k.px3n()));                           // X^2 (-3 px)
     const h C = sqr(Z);
     const h B = sqr(Y);
-    const S<3> H = sub(sub(sqr(norm(add(Y, Z))), B), C);              // 2YZ
+    const S<3> H = sub(sub(sqr(addn(Y, Z)), B), C);                   // 2YZ
     store_part(rec, 2, mulf(H, k.py()));                              // 2YZ py
     const h z8 = mulc_norm<4>(H);                                     // 8YZ
     const h E = b3(C);
-    const S<3> A2 = sub(sub(sqr(norm(add(X, Y))), XX), B);            // 2XY
+    const S<3> A2 = sub(sub(sqr(addn(X, Y)), XX), B);                 // 2XY
     store_part(rec, 0, sub(B, E));
     const S<3> F3 = mulc<3>(E);
     const h BmF = norm(sub(B, F3)), G = norm(add(B, F3));
@@ -252,21 +276,22 @@ __device__ __forceinline__ void tangent_step(h& X, h& Y, h& Z, const Slab& k, in
     Y = sqr_m12sqr(G, E);                                             // G^2 - 12 E^2: one sum of two products (round 4: two squares, 2 x 392 + the scaling)
     Z = mul(left(B), right(z8));
 }
-__device__ __forceinline__ void chord_step(h& X, h& Y, h& Z, const Slab& k, int32_t* __restrict__ rec) {
+__device__ __forceinline__ void chord_step(hn& X, hn& Y, hn& Z, const Slab& k, int32_t* __restrict__ rec) {
     const Rop<1> rz = right(Z);
     const h th = norm(sub(Y, mul(left(k.yq()), rz))), la = norm(sub(X, mul(left(k.xq()), rz)));
     const Lop<1> lth = left(th), lla = left(la);
+    // (round 8: the line record first -- th and la end with their squares instead of staying live beside lth and lla)
+    const h xq3 = mulc_norm<3>(k.xq()), nyq3 = mulc_norm<3>(neg(k.yq()));
+    store_part(rec, 0, dot2(lth, right(xq3), lla, right(nyq3)));
+    store_part(rec, 1, mulf(th, k.px3n()));
+    store_part(rec, 2, mulf(la, r28::mulc_norm<3>(k.py())));
     const h C = sqr(th), D = sqr(la);
     const Rop<1> rd = right(D);
     const h E = mul(lla, rd), Fz = mul(left(Z), right(C)), Gg = mul(left(X), rd);
     const h H = norm(sub(add(E, Fz), add(Gg, Gg)));
     const h GH = norm(sub(Gg, H));
-    const h xq3 = mulc_norm<3>(k.xq()), nyq3 = mulc_norm<3>(neg(k.yq()));
-    store_part(rec, 0, dot2(lth, right(xq3), lla, right(nyq3)));
-    store_part(rec, 1, mulf(th, k.px3n()));
-    store_part(rec, 2, mulf(la, r28::mulc_norm<3>(k.py())));
     const h nE = norm(neg(E));
-    const h Y3 = dot2(lth, right(GH), left(nE), right(Y));
+    const hn Y3 = dot2(lth, right(GH), left(nE), right(Y));
     X = mul(lla, right(H));
     Z = mul(left(Z), right(E));
     Y = Y3;
@@ -285,6 +310,10 @@ template <int M> __device__ __forceinline__ S<M> oth(const S<M>& x) {           
     for (int j = 0; j < NL; j++) r.v[j] = __builtin_amdgcn_update_dpp(0, x.v[j], 0x4E, 0xF, 0xF, true);
     return r;
 }
+__device__ __forceinline__ hn in_digits(const h& x) { hn r;        // for a selection or a move among values that all are
+#pragma unroll
+    for (int j = 0; j < NL; j++) r.v[j] = x.v[j];
+    return r; }
 template <int M> __device__ __forceinline__ S<M> pick(const S<M>& a, const S<M>& b) {    // pair 0: a, pair 1: b
     S<M> r;
 #pragma unroll
@@ -301,7 +330,7 @@ template <int W, int M> __device__ __forceinline__ S<W> widen(const S<M>& x) {  
 // The tangent step of sp::tangent_step dealt out over the two pairs: level 1 the five squares (X^2, Y^2, (X + Y)^2 | Z^2,
 // (Y + Z)^2), level 2 {2XY (B - F), G^2, X^2 (-3 px) | B 8YZ, E^2, 2YZ py}: 3 squares + product + square + product by an Fq
 // value deep (2548 multiply-adds per lane) instead of 4718.  Pair 0 stores the line's coefficients 0 and 1, pair 1 the third.
-__device__ __forceinline__ void tangent_step(h& X, h& Y, h& Z, const Slab& k, int32_t* __restrict__ rec) {
+__device__ __forceinline__ void tangent_step(hn& X, hn& Y, hn& Z, const Slab& k, int32_t* __restrict__ rec) {
     const h sa = sqr(pick(X, Z)), sb = sqr(pick(Y, norm(add(Y, Z)))), sc = sqr(norm(add(X, Y)));
     const h oa = oth(sa), ob = oth(sb);
     const h XX = pick(sa, oa), C = pick(oa, sa), B = pick(sb, ob), T1 = pick(ob, sb);
@@ -323,8 +352,8 @@ __device__ __forceinline__ void tangent_step(h& X, h& Y, h& Z, const Slab& k, in
     const h m = mul(left(pick(A2, widen<3>(B))), right(pick(BmF, z8)));   // X' | Z'
     const h q = sqr(pick(G, E));                                       // G^2 | E^2
     const h om = oth(m), oq = oth(q);
-    X = pick(m, om);
-    Z = pick(om, m);
+    X = in_digits(pick(m, om));
+    Z = in_digits(pick(om, m));
     Y = norm(sub(pick(q, oq), mulc_norm<12>(pick(oq, q))));            // G^2 - 12 E^2
 }
 }  // namespace sq
@@ -356,7 +385,7 @@ __device__ __forceinline__ void lines_chain(const uint32_t* __restrict__ g1, con
     const uint32_t* s1 = g1 + (size_t)p * 24;
     const uint32_t* s2 = g2 + (size_t)p * 48 + part * 12;
     const sp::Slab sl{(sp::lds_i32*)ml_slab + (threadIdx.x >> 6) * (sp::SLAB_SLOTS * NL * 64) + (threadIdx.x & 63u)};
-    sp::h X, Y, Z;
+    sp::hn X, Y, Z;
     bool ok = !q_flagged(dg, p);
     {
         const fe px = load_coord(s1), py = load_coord(s1 + 12);
