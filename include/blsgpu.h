@@ -71,8 +71,9 @@ int blsgpu_ctx_reserve(blsgpu_ctx *ctx, size_t max_pairs);
  * counterpart of the n-arrays of mpz_t the reference mallocs per call, fields_t_c.pyx:2348-2388).  out[BLSGPU_WS_TOTAL]
  * is the sum (which also counts the fixed-base G1 table and the HD derivation slice, blsgpu_g1_mul_gen /
  * blsgpu_hd_children, the per-path state of blsgpu_hd_paths, the commitments of blsgpu_g1_poly_check and the Lagrange
- * coefficients of blsgpu_threshold_combine / blsgpu_fr_interpolate_at_zero, the table of blsgpu_g1_mul_gen_secret, and the
- * point tables of blsgpu_g2_mul_secret / blsgpu_sign; they have no field of their own).
+ * coefficients of blsgpu_threshold_combine / blsgpu_fr_interpolate_at_zero, the table of blsgpu_g1_mul_gen_secret, the
+ * point tables of blsgpu_g2_mul_secret / blsgpu_sign, and the scalars and point copies of blsgpu_sign_threshold; they have no
+ * field of their own).
  * BLSGPU_WS_FLAGS_AND_LISTS counts the flag copy of blsgpu_miller_loop_batch's fast form as well (2 bytes per pair of a
  * slice).  No device call is made. */
 enum { BLSGPU_WS_PARTIALS = 0, BLSGPU_WS_STAGING, BLSGPU_WS_LINES, BLSGPU_WS_LINE_PRODUCTS, BLSGPU_WS_FLAGS_AND_LISTS,
@@ -391,7 +392,8 @@ int blsgpu_hd_paths_secret_dev(blsgpu_ctx *ctx, const void *d_parents, size_t n_
  * The commitments are prepared once per call (csrc/blsgpu_g1poly.hip): L28 form, and a check [n] C_k == O per commitment;
  * then one fragment per lane: Horner in the exponent over the bits of x_i mod n, (s_i mod n) G1 on blsgpu_g1_mul_gen's
  * table, a projective comparison.  Sort the fragments by polynomial: a wavefront then reads one polynomial.  The loops
- * follow the bits of the (public) x_i and the table gathers the digits of s_i: NOT constant-time. */
+ * follow the bits of the (public) x_i and the table gathers the digits of s_i: NOT constant-time (there is no secret form
+ * of this check; the dealer's side is blsgpu_threshold_deal_secret). */
 int blsgpu_g1_poly_check(blsgpu_ctx *ctx, const uint8_t *commit, size_t n_polys, size_t t, const uint32_t *poly,
                          const uint8_t *x, const uint8_t *s, size_t n, uint8_t *status, uint8_t *out_aff);
 /* The same with every buffer in device memory, enqueued on `stream`.  The indices are first scanned on the device and the
@@ -432,7 +434,7 @@ int blsgpu_lagrange_at_zero_dev(blsgpu_ctx *ctx, const void *d_x, size_t k, size
 /* Threshold.interpolate_at_zero (threshold.py:91-101): out[g] = sum_j L_j y_j mod n, 32 bytes big-endian per group, with
  * the coefficients of group g computed as above into the context's workspace; y: groups x k x 32 bytes big-endian, any
  * value below 2^256 (reduced mod n on the device).  A group with status 0 yields 0.  The y_j are secrets (shares): the
- * reductions branch on their values, NOT constant-time. */
+ * reductions branch on their values, NOT constant-time; blsgpu_fr_interpolate_at_zero_secret below is the form for shares. */
 int blsgpu_fr_interpolate_at_zero(blsgpu_ctx *ctx, const uint8_t *x, const uint8_t *y, size_t k, size_t groups,
                                   uint8_t *out, uint8_t *status);
 int blsgpu_fr_interpolate_at_zero_dev(blsgpu_ctx *ctx, const void *d_x, const void *d_y, size_t k, size_t groups,
@@ -482,6 +484,55 @@ int blsgpu_sign(blsgpu_ctx *ctx, const uint8_t *sks, const uint8_t *msg_hashes, 
 int blsgpu_sign_dev(blsgpu_ctx *ctx, const void *d_sks, const void *d_msg_hashes, size_t n_msg, size_t n, void *d_out_aff,
                     void *d_out_ser, void *stream);
 
+/* The threshold scheme's work on SECRET scalars (csrc/blsgpu_frsecret.hip on the masked forms of csrc/fr_scalar.h).  The claim
+ * of the three calls below is exactly that of blsgpu_g1_mul_gen_secret and blsgpu_g2_mul_secret: the sequence of instructions
+ * and of memory addresses does not depend on the coefficients, shares or keys.  It does depend on t, k, the counts and the
+ * evaluation points x (player numbers), which are public -- and so do the Lagrange coefficients computed from them.  NOT
+ * claimed: data-dependent timing inside the hardware (how long an instruction or a memory access takes for given values).
+ *
+ * Joint-Feldman dealing (PrivateKey.new_threshold, keys.py:92-117 of the reference) of n_polys polynomials of t coefficients
+ * at once.  coeffs: n_polys x t x 32 bytes big-endian, coefficient k of polynomial p at index p * t + k, any value below
+ * 2^256; x: n_x x 32 bytes big-endian, the points the fragments are taken at (1 .. N in the reference), any value below 2^256
+ * (reduced mod n).  out_commit_aff: n_polys x t x 96 bytes, c_k G1 from k_fix_mul_secret (the bytes of blsgpu_g1_mul_gen);
+ * out_frag: n_polys x n_x x 32 bytes big-endian canonical, P_p(x_j) = sum_k c[p][k] x_j^k mod n at index p * n_x + j, from
+ * k_fr_poly_eval_secret: one lane per (p, j), the polynomial's coefficients reduced by mask, in Montgomery form in LDS, Horner
+ * from the top coefficient with t - 1 masked products and additions, coefficient k read at step k by every lane.  Either
+ * output may be NULL, not both; without out_frag, x and n_x are ignored.  -EINVAL before anything is written: t == 0 or
+ * t > BLSGPU_LAGRANGE_MAX_K (a polynomial's coefficients fit one workgroup's LDS), a NULL required buffer, n_x == 0 with
+ * out_frag given.  n_polys == 0 writes nothing and returns 0. */
+int blsgpu_threshold_deal_secret(blsgpu_ctx *ctx, const uint8_t *coeffs, size_t n_polys, size_t t, const uint8_t *x, size_t n_x,
+                                 uint8_t *out_commit_aff, uint8_t *out_frag);
+/* The same with every buffer in device memory, enqueued on `stream` (no synchronisation). */
+int blsgpu_threshold_deal_secret_dev(blsgpu_ctx *ctx, const void *d_coeffs, size_t n_polys, size_t t, const void *d_x, size_t n_x,
+                                     void *d_out_commit_aff, void *d_out_frag, void *stream);
+/* blsgpu_fr_interpolate_at_zero for SECRET y_j (recombining shares into a private key): the same arguments, validation and
+ * bytes, status 0 groups included.  k_lagrange on the public points, then k_fr_dot_secret: y_j mod n, L_j y_j and the sum
+ * over the group keep every subtraction by a mask.  The claim and its limits are stated above. */
+int blsgpu_fr_interpolate_at_zero_secret(blsgpu_ctx *ctx, const uint8_t *x, const uint8_t *y, size_t k, size_t groups,
+                                         uint8_t *out, uint8_t *status);
+int blsgpu_fr_interpolate_at_zero_secret_dev(blsgpu_ctx *ctx, const void *d_x, const void *d_y, size_t k, size_t groups,
+                                             void *d_out, void *d_status, void *stream);
+/* Unit signatures of `groups` threshold sessions of k signers each (PrivateKey.sign_threshold, keys.py:134-141 of the
+ * reference): out[g * k + j] = (lambda_gj sk_gj mod n) H(h_(n_msg == 1 ? 0 : g)) with lambda_g the Lagrange coefficients at
+ * zero of session g's players.  sks and x: groups x k x 32 bytes big-endian (share and player number of signer j of session
+ * g; sk any value below 2^256); msg_hashes: n_msg x 32 bytes, n_msg = 1 (every session signs the same message) or groups.
+ * The call enqueues k_lagrange, then k_fr_scale_secret (lambda sk mod n with the masked reduction and product, into the
+ * workspace), blsgpu_hash_to_g2_dev of the n_msg hashes, then k_g2_smul -- on ONE shared table when n_msg == 1, otherwise
+ * session g's point is copied to its k slots and the per-scalar tables are used; nothing returns to the host between the
+ * stages, and a call is processed in the slices of 65 536 scalars of blsgpu_g2_mul_secret.  1 <= k <= BLSGPU_LAGRANGE_MAX_K.
+ * status: groups bytes as in blsgpu_lagrange_at_zero; a session with status 0 has all-zero coefficients, hence scalar 0 and
+ * the point at infinity for each of its signers.  out_aff (groups x k x 192), out_ser (groups x k x 96), out_inf (groups x
+ * k, may be NULL) as in blsgpu_g2_mul_secret: out_aff and out_ser may each be NULL, not both.  -EINVAL before anything is
+ * written: k == 0 or above the limit, n_msg neither 1 nor groups, a NULL required buffer.  groups == 0 writes nothing and
+ * returns 0.  The claim is the one stated above; H(m) and the players are public. */
+int blsgpu_sign_threshold(blsgpu_ctx *ctx, const uint8_t *sks, const uint8_t *x, size_t k, size_t groups,
+                          const uint8_t *msg_hashes, size_t n_msg, uint8_t *out_aff, uint8_t *out_ser, uint8_t *out_inf,
+                          uint8_t *status);
+/* The same with every buffer in device memory, enqueued on `stream` (no synchronisation). */
+int blsgpu_sign_threshold_dev(blsgpu_ctx *ctx, const void *d_sks, const void *d_x, size_t k, size_t groups,
+                              const void *d_msg_hashes, size_t n_msg, void *d_out_aff, void *d_out_ser, void *d_out_inf,
+                              void *d_status, void *stream);
+
 /* Measurement aid (bench.py): when enabled, HIP events are recorded on the
  * launch stream around every kernel this context launches (up to 1024 launches
  * between reads).  blsgpu_timing_read waits for them and returns, per launch,
@@ -489,7 +540,10 @@ int blsgpu_sign_dev(blsgpu_ctx *ctx, const void *d_sks, const void *d_msg_hashes
  * product), 1 = k_reduce (partial products), 2 = k_reduce with the final
  * exponentiation, 3 = k_miller_slow (degenerate pairs; empty work list normally); the line-stream stages use 4 .. 7, and
  * 8 = k_g2_smul with its table kernel (one record per blsgpu_g2_mul_secret / per slice of blsgpu_sign),
- * 9 = k_fix_mul_secret (one record per blsgpu_g1_mul_gen_secret_dev call / per level of blsgpu_hd_paths_secret).
+ * 9 = k_fix_mul_secret (one record per blsgpu_g1_mul_gen_secret_dev call / per level of blsgpu_hd_paths_secret),
+ * 10 = the scalar kernels on secrets: k_fr_poly_eval_secret, k_fr_dot_secret, k_fr_scale_secret (one record per call of
+ * blsgpu_threshold_deal_secret_dev with fragments, blsgpu_fr_interpolate_at_zero_secret_dev, blsgpu_sign_threshold_dev; the
+ * G1 / G2 halves of those calls keep their kinds 9 and 8).
  * Reading resets the ring. */
 int blsgpu_timing_enable(blsgpu_ctx *ctx, int enable);
 int blsgpu_timing_read(blsgpu_ctx *ctx, float *ms, int *kind, size_t cap, size_t *count);

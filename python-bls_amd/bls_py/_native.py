@@ -34,6 +34,9 @@ SYMBOLS = (
     "blsgpu_threshold_combine", "blsgpu_threshold_combine_dev",
     "blsgpu_g2_mul_secret", "blsgpu_g2_mul_secret_dev", "blsgpu_sign", "blsgpu_sign_dev",
     "blsgpu_g1_mul_gen_secret", "blsgpu_g1_mul_gen_secret_dev", "blsgpu_hd_paths_secret", "blsgpu_hd_paths_secret_dev",
+    "blsgpu_threshold_deal_secret", "blsgpu_threshold_deal_secret_dev",
+    "blsgpu_fr_interpolate_at_zero_secret", "blsgpu_fr_interpolate_at_zero_secret_dev",
+    "blsgpu_sign_threshold", "blsgpu_sign_threshold_dev",
 )
 
 HD_PARENT_BYTES = 160          # BLSGPU_HD_PARENT_BYTES: chain code (32), public key affine (96), private key (32)
@@ -142,6 +145,12 @@ def load_library(path=None):
         L.blsgpu_g1_mul_gen_secret_dev.argtypes = [vp, vp, sz, vp, vp, vp]
         L.blsgpu_hd_paths_secret.argtypes = [vp, cp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp]
         L.blsgpu_hd_paths_secret_dev.argtypes = [vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp]
+        L.blsgpu_threshold_deal_secret.argtypes = [vp, cp, sz, sz, cp, sz, vp, vp]
+        L.blsgpu_threshold_deal_secret_dev.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, vp]
+        L.blsgpu_fr_interpolate_at_zero_secret.argtypes = [vp, cp, cp, sz, sz, vp, vp]
+        L.blsgpu_fr_interpolate_at_zero_secret_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
+        L.blsgpu_sign_threshold.argtypes = [vp, cp, cp, sz, sz, cp, sz, vp, vp, vp, vp]
+        L.blsgpu_sign_threshold_dev.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp]
         L.blsgpu_timing_enable.argtypes = [vp, ctypes.c_int]
         L.blsgpu_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int), sz,
                                          ctypes.POINTER(sz)]
@@ -625,6 +634,63 @@ class Engine:
 
     def sign_dev(self, d_sks, d_msg_hashes, n_msg, n, d_out_aff, d_out_ser, stream=0):
         self._check(self.lib.blsgpu_sign_dev(self.h, d_sks, d_msg_hashes, n_msg, n, d_out_aff, d_out_ser, stream), "blsgpu_sign_dev")
+
+    def threshold_deal_secret(self, coeffs, t, x, commit=True, frag=True):
+        """Commitments and fragments of len(coeffs) / t polynomials with SECRET coefficients (blsgpu_threshold_deal_secret):
+        coeffs n_polys x t x 32 bytes big-endian (or ints below 2^256), x the n_x points the fragments are taken at, likewise
+        (ignored without frag).
+        -> (n_polys x t x 96 affine bytes c_k G1 or None, n_polys x n_x x 32 bytes P_p(x_j) mod n or None)"""
+        cb = coeffs if isinstance(coeffs, (bytes, bytearray)) else b"".join(int(c).to_bytes(32, "big") for c in coeffs)
+        xb = b"" if not frag else x if isinstance(x, (bytes, bytearray)) else b"".join(int(v).to_bytes(32, "big") for v in x)
+        if t < 1 or len(cb) % (32 * t) or len(xb) % 32:
+            raise ValueError("need n_polys x t x 32 coefficient bytes and n_x x 32 bytes of points")
+        if not (commit or frag):
+            raise ValueError("ask for at least one output")
+        n_polys, n_x = len(cb) // (32 * t), len(xb) // 32
+        oc = ctypes.create_string_buffer(max(1, 96 * n_polys * t)) if commit else None
+        of = ctypes.create_string_buffer(max(1, 32 * n_polys * n_x)) if frag else None
+        self._check(self.lib.blsgpu_threshold_deal_secret(self.h, bytes(cb), n_polys, t, bytes(xb) if frag else None, n_x, oc, of),
+                    "blsgpu_threshold_deal_secret")
+        return (oc.raw[:96 * n_polys * t] if commit else None), (of.raw[:32 * n_polys * n_x] if frag else None)
+
+    def threshold_deal_secret_dev(self, d_coeffs, n_polys, t, d_x, n_x, d_out_commit_aff, d_out_frag, stream=0):
+        self._check(self.lib.blsgpu_threshold_deal_secret_dev(self.h, d_coeffs, n_polys, t, d_x, n_x, d_out_commit_aff, d_out_frag, stream),
+                    "blsgpu_threshold_deal_secret_dev")
+
+    def fr_interpolate_at_zero_secret(self, x, y, k, groups=1):
+        """fr_interpolate_at_zero for SECRET y (shares) on the masked sums of blsgpu_fr_interpolate_at_zero_secret: the same
+        arguments, the same bytes.  -> (groups x 32 bytes, groups status bytes)"""
+        n = k * groups
+        out = ctypes.create_string_buffer(max(1, 32 * groups))
+        st = ctypes.create_string_buffer(max(1, groups))
+        self._check(self.lib.blsgpu_fr_interpolate_at_zero_secret(self.h, self._scalars(x, n, "x"), self._scalars(y, n, "y"), k, groups,
+                                                                  out, st), "blsgpu_fr_interpolate_at_zero_secret")
+        return out.raw[:32 * groups], st.raw[:groups]
+
+    def fr_interpolate_at_zero_secret_dev(self, d_x, d_y, k, groups, d_out, d_status, stream=0):
+        self._check(self.lib.blsgpu_fr_interpolate_at_zero_secret_dev(self.h, d_x, d_y, k, groups, d_out, d_status, stream),
+                    "blsgpu_fr_interpolate_at_zero_secret_dev")
+
+    def sign_threshold(self, sks, x, k, msg_hashes, groups=1, aff=True, ser=True):
+        """Unit signatures (lambda_j sk_j mod n) H(h) of `groups` sessions of k signers (blsgpu_sign_threshold): sks, x
+        groups x k x 32 bytes big-endian (or ints below 2^256), msg_hashes ONE hash of 32 bytes or one per session.
+        -> (groups x k x 192 affine bytes or None, groups x k x 96 serialised bytes or None, [is_infinity], groups status bytes)"""
+        n = k * groups
+        if len(msg_hashes) % 32:
+            raise ValueError("message hashes are 32 bytes")
+        if not (aff or ser):
+            raise ValueError("ask for at least one output")
+        oa = ctypes.create_string_buffer(max(1, 192 * n)) if aff else None
+        os_ = ctypes.create_string_buffer(max(1, 96 * n)) if ser else None
+        inf = ctypes.create_string_buffer(max(1, n))
+        st = ctypes.create_string_buffer(max(1, groups))
+        self._check(self.lib.blsgpu_sign_threshold(self.h, self._scalars(sks, n, "sks"), self._scalars(x, n, "x"), k, groups, bytes(msg_hashes),
+                                                   len(msg_hashes) // 32, oa, os_, inf, st), "blsgpu_sign_threshold")
+        return (oa.raw[:192 * n] if aff else None), (os_.raw[:96 * n] if ser else None), [bool(b) for b in inf.raw[:n]], st.raw[:groups]
+
+    def sign_threshold_dev(self, d_sks, d_x, k, groups, d_msg_hashes, n_msg, d_out_aff, d_out_ser, d_out_inf, d_status, stream=0):
+        self._check(self.lib.blsgpu_sign_threshold_dev(self.h, d_sks, d_x, k, groups, d_msg_hashes, n_msg, d_out_aff, d_out_ser, d_out_inf,
+                                                       d_status, stream), "blsgpu_sign_threshold_dev")
 
     def timing_enable(self, on=True):
         self._check(self.lib.blsgpu_timing_enable(self.h, int(on)), "blsgpu_timing_enable")

@@ -109,6 +109,19 @@ class HipProvider:
         -> (n x 192 affine bytes, n x 96 bytes of Signature.serialize())"""
         return self._eng.sign(sks, msg_hashes, aff, ser)
 
+    # ---- the threshold scheme's work on secrets: schedules that do not depend on coefficients, shares or keys ----
+    def threshold_deal_secret(self, coeffs, t: int, x, commit: bool = True, frag: bool = True):
+        """-> (n_polys x t x 96 affine bytes c_k G1, n_polys x n_x x 32 bytes P_p(x_j) mod n)"""
+        return self._eng.threshold_deal_secret(coeffs, t, x, commit, frag)
+
+    def fr_interpolate_at_zero_secret(self, x, y, k: int, groups: int = 1):
+        """fr_interpolate_at_zero on the masked sums: the same outputs"""
+        return self._eng.fr_interpolate_at_zero_secret(x, y, k, groups)
+
+    def sign_threshold(self, sks, x, k: int, msg_hashes: bytes, groups: int = 1, aff: bool = True, ser: bool = True):
+        """(lambda_j sk_j mod n) H(h) per signer: -> (affine bytes, serialised bytes, [is_infinity], groups status bytes)"""
+        return self._eng.sign_threshold(sks, x, k, msg_hashes, groups, aff, ser)
+
     # ---- the whole of BLS.verify's device work without a host round trip between its steps (bls.py:153-201) ----
     def verify_pipeline(self, neg_g1: bytes, sig: bytes, hashes: bytes, n: int, keys_affine=None, key_pts=None, key_scalars=None, k=0) -> bytes:
         """e(-G1, sig) * prod_i e(P_i, H(m_i)) for n message hashes (32 bytes each): blsgpu_verify_pipeline -- ONE upload,
@@ -131,7 +144,9 @@ def use(provider):
     Optional (a provider without it sends the HD *_path_batch / *_paths_from methods to chained hd_children calls):
     hd_paths(parents, priv, parent_of|None, paths of one depth) -> (chain codes, keys|None, affine, serialised, fingerprints).
     Optional (the secret=True forms of the key methods raise without them; there is no other path for them):
-    g1_mul_gen_secret(scalars) -> (affine bytes, serialised bytes), hd_paths_secret(parents, parent_of|None, paths) -> as hd_paths.
+    g1_mul_gen_secret(scalars) -> (affine bytes, serialised bytes), hd_paths_secret(parents, parent_of|None, paths) -> as hd_paths,
+    threshold_deal_secret(coeffs, t, x) -> (commitment bytes, fragment bytes), fr_interpolate_at_zero_secret(x, y, k, groups) ->
+    as fr_interpolate_at_zero, sign_threshold(sks, x, k, msg_hashes, groups) -> (affine bytes, serialised bytes, [is_inf], status bytes).
     Optional (a provider without them sends the Threshold.*_batch methods to the host loop): LAGRANGE_MAX_K,
     lagrange_at_zero(x, k, groups) -> (coefficient bytes, status bytes), fr_interpolate_at_zero(x, y, k, groups) ->
     (32 bytes per group, status bytes), threshold_combine(sigs, x, k, groups) -> (affine bytes, [is_inf], status bytes)."""

@@ -126,26 +126,36 @@ class PrivateKey:
         return PrivateKey(poly[0]), commitments, fragments
 
     @staticmethod
-    def new_threshold_batch(T, N, count):
+    def new_threshold_batch(T, N, count, secret=False):
         """[PrivateKey.new_threshold(T, N) for _ in range(count)]: the coefficients drawn from RNG in the same order, the
         count x T commitments g1*c in one GPU call on the fixed-base table (blsgpu_g1_mul_gen), the fragments P(1..N)
-        by Horner mod n on the host (as Fq(n, .) values)."""
+        by Horner mod n on the host (as Fq(n, .) values).  secret=True: the same objects with commitments and fragments
+        from ONE blsgpu_threshold_deal_secret call, whose sequence of instructions and addresses does not depend on the
+        coefficients (a provider without it raises)."""
         from . import backend
         from .ec import AffinePoint
         assert 1 <= T <= N
+        deal = _secret_call("threshold_deal_secret") if secret else None
         polys = [[RNG.randint(1, GROUP_ORDER - 1) for _ in range(T)] for _ in range(count)]
         if not polys:
             return []
-        aff, _ = backend.get().g1_mul_gen(b"".join(c.to_bytes(32, "big") for poly in polys for c in poly))
+        coeffs = b"".join(c.to_bytes(32, "big") for poly in polys for c in poly)
+        if secret:
+            aff, frag = deal(coeffs, T, b"".join(x.to_bytes(32, "big") for x in range(1, N + 1)))
+        else:
+            aff, _ = backend.get().g1_mul_gen(coeffs)
         out = []
         for d, poly in enumerate(polys):
             commitments = [AffinePoint._from(H.F1, H.g1_from_abi(aff[96 * (d * T + k):96 * (d * T + k + 1)]), default_ec)
                            for k in range(T)]
             fragments = []
             for x in range(1, N + 1):
-                acc = 0
-                for c in reversed(poly):
-                    acc = (acc * x + c) % GROUP_ORDER
+                if secret:
+                    acc = int.from_bytes(frag[32 * (d * N + x - 1):32 * (d * N + x)], "big")
+                else:
+                    acc = 0
+                    for c in reversed(poly):
+                        acc = (acc * x + c) % GROUP_ORDER
                 fragments.append(Fq(GROUP_ORDER, acc))
             out.append((PrivateKey(poly[0]), commitments, fragments))
         return out
@@ -282,11 +292,14 @@ class PrivateKey:
         return Signature.from_g2(self.value * (r * lam))
 
     @staticmethod
-    def sign_threshold_batch(private_keys, m, players):
+    def sign_threshold_batch(private_keys, m, players, secret=False):
         """[sk.sign_threshold(m, p, players) for sk, p in zip(private_keys, players)]: the unit signatures of one session,
         the share of players[i] being private_keys[i].  One Lagrange evaluation for the session
         (Threshold.lagrange_coeffs_at_zero_batch: on the GPU), one hash to G2 and one grouped G2 sum of
-        (lambda_i sk_i mod n) H(m) -- where every signer's own sign_threshold pays a full host Lagrange evaluation."""
+        (lambda_i sk_i mod n) H(m) -- where every signer's own sign_threshold pays a full host Lagrange evaluation.
+        secret=True: ONE blsgpu_sign_threshold call -- the coefficients, lambda_i sk_i mod n on masked arithmetic, the hash
+        and the scalar-independent G2 multiplication, nothing returning to the host in between (a provider without it
+        raises; so does a session of more than its LAGRANGE_MAX_K signers)."""
         from . import backend
         from .ec import hash_to_points_prehashed_Fq2
         from .threshold import Threshold
@@ -294,12 +307,23 @@ class PrivateKey:
         sks, players = list(private_keys), list(players)
         if len(sks) != len(players):
             raise ValueError("one private key per player")
-        if not sks:
-            return []
-        lam = Threshold.lagrange_coeffs_at_zero_batch([players])[0]
-        r = H.g2_affine_bytes(hash_to_points_prehashed_Fq2([hash256(m)])[0]._aff())
-        scalars = [int(l) * sk.value % GROUP_ORDER for l, sk in zip(lam, sks)]
-        out, inf = backend.get().g2_msm(r * len(sks), scalars, 1, len(sks))
+        if secret:
+            sign = _secret_call("sign_threshold")
+            if not sks:
+                return []
+            assert len(set(players)) == len(players) and all(type(x) is int and 0 < x < GROUP_ORDER for x in players)
+            if len(sks) > backend.get().LAGRANGE_MAX_K:
+                raise ValueError("secret=True takes at most %d signers per session" % backend.get().LAGRANGE_MAX_K)
+            out, _, inf, status = sign(b"".join(sk.serialize() for sk in sks), b"".join(x.to_bytes(32, "big") for x in players),
+                                       len(sks), hash256(m), 1, True, False)
+            assert status == b"\x01"
+        else:
+            if not sks:
+                return []
+            lam = Threshold.lagrange_coeffs_at_zero_batch([players])[0]
+            r = H.g2_affine_bytes(hash_to_points_prehashed_Fq2([hash256(m)])[0]._aff())
+            scalars = [int(l) * sk.value % GROUP_ORDER for l, sk in zip(lam, sks)]
+            out, inf = backend.get().g2_msm(r * len(sks), scalars, 1, len(sks))
         return [Signature.from_g2(JacobianPoint._from(
             H.F2, None if inf[i] else H.aff_to_jac(H.F2, H.g2_from_abi(out[192 * i:192 * (i + 1)])), default_ec_twist))
             for i in range(len(sks))]

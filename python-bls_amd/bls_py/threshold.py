@@ -149,9 +149,13 @@ class Threshold:
         return [Threshold.lagrange_coeffs_at_zero(X, ec) if r is None else r for X, r in zip(Xs, out)]
 
     @staticmethod
-    def interpolate_at_zero_batch(Xs, Ys, ec=default_ec):
+    def interpolate_at_zero_batch(Xs, Ys, ec=default_ec, secret=False):
         """[interpolate_at_zero(X, Y, ec) for X, Y in zip(Xs, Ys)]: coefficients and the sums sum_j L_j y_j on the GPU
-        (blsgpu_fr_interpolate_at_zero) for groups whose Y holds one Fq mod n or int per player."""
+        (blsgpu_fr_interpolate_at_zero) for groups whose Y holds one Fq mod n or int per player.
+        secret=True (the Y are shares of a private key): every group on blsgpu_fr_interpolate_at_zero_secret, whose
+        sequence of instructions and addresses does not depend on the Y.  Nothing takes the host loop then: a provider
+        without the entry raises NotImplementedError, a group the device cannot take -- wider than its LAGRANGE_MAX_K,
+        empty, players that are not positive ints, values that are not Fq mod n or int, another curve -- ValueError."""
         Xs, Ys = [list(X) for X in Xs], [list(Y) for Y in Ys]
         m = min(len(Xs), len(Ys))
         Xs, Ys = Xs[:m], Ys[:m]
@@ -159,15 +163,23 @@ class Threshold:
 
         def values(i):
             return len(Ys[i]) == len(Xs[i]) and all((type(y) is Fq and y.Q == n) or type(y) is int for y in Ys[i])
-        prov, buckets = Threshold._device_buckets(Xs, ec, "fr_interpolate_at_zero", values)
+        entry = "fr_interpolate_at_zero"
+        if secret:
+            from .keys import _secret_call
+            entry = "fr_interpolate_at_zero_secret"
+            _secret_call(entry)
+        prov, buckets = Threshold._device_buckets(Xs, ec, entry, values)
+        if secret and sum(len(idx) for idx in buckets.values()) != m:
+            raise ValueError("secret=True: a group that the device cannot take (see interpolate_at_zero_batch)")
         out = [None] * m
         for k, idx in buckets.items():
             xb = b"".join(x.to_bytes(32, "big") for i in idx for x in Xs[i])
             yb = b"".join((int(y) % n).to_bytes(32, "big") for i in idx for y in Ys[i])
-            res, status = prov.fr_interpolate_at_zero(xb, yb, k, len(idx))
+            res, status = getattr(prov, entry)(xb, yb, k, len(idx))
             for q, i in enumerate(idx):
                 if status[q] == 1:
                     out[i] = Fq(n, int.from_bytes(res[32 * q:32 * (q + 1)], "big"))
+        assert not secret or all(r is not None for r in out)       # (the assertion of _device_buckets has passed: status 1)
         return [Threshold.interpolate_at_zero(X, Y, ec) if r is None else r for X, Y, r in zip(Xs, Ys, out)]
 
     @staticmethod

@@ -25,6 +25,7 @@
 #include "blsgpu_g1poly.hip"
 #include "blsgpu_subgroup.hip"
 #include "blsgpu_lagrange.hip"
+#include "blsgpu_frsecret.hip"
 #include "blsgpu_g2smul.hip"
 #include "blsgpu_h2c.hip"
 #include "blsgpu_h2cw.hip"
@@ -827,6 +828,61 @@ int threshold_combine_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_x, si
         if (int rc = lagrange_launch(c, d_x, k, groups, c->at<void>(B_LAGR_WS), d_status, st)) return rc;
     }
     return msm_dev<2>(c, d_sigs, c->at<void>(B_LAGR_WS), k, groups, d_out, d_out_inf, st);
+}
+
+// ------------------------------------------------------------ scalar-field work on secrets (blsgpu_frsecret.hip) --
+// blsgpu_fr_interpolate_at_zero_secret: fr_interpolate_dev with the masked sums (timing kind 10)
+int fr_interpolate_secret_dev(blsgpu_ctx* c, const void* d_x, const void* d_y, size_t k, size_t groups, void* d_out, void* d_status,
+                              hipStream_t st) {
+    StreamGuard sg(c, st);
+    if (int rc = c->grow(B_LAGR_WS, groups * k * 32)) return rc;
+    if (int rc = lagrange_launch(c, d_x, k, groups, c->at<void>(B_LAGR_WS), d_status, st)) return rc;
+    const blsgpu::lagr::Shape sh = blsgpu::lagr::shape((uint32_t)k);
+    KernelTimer kt(c, st, 10);
+    hipLaunchKernelGGL(blsgpu::frsec::k_fr_dot_secret, dim3((unsigned)((groups + sh.gpb - 1) / sh.gpb)), dim3(sh.threads), sh.lds, st,
+                       c->at<uint8_t>(B_LAGR_WS), (const uint8_t*)d_y, (uint32_t)k, (uint32_t)groups, sh.gpb, (uint8_t*)d_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// the argument checks of blsgpu_threshold_deal_secret* (before anything is written); 1: nothing to do
+int deal_args(const blsgpu_ctx* c, const void* coeffs, size_t n_polys, size_t t, const void* x, size_t n_x, const void* out_commit,
+              const void* out_frag) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (t == 0 || t > blsgpu::lagr::MAX_K) return fail(-EINVAL, "t must be 1 .. BLSGPU_LAGRANGE_MAX_K");
+    if (n_polys == 0) return 1;
+    if (!coeffs) return fail(-EINVAL, "NULL argument");
+    if (!out_commit && !out_frag) return fail(-EINVAL, "out_commit_aff and out_frag are both NULL");
+    if (out_frag && (n_x == 0 || !x)) return fail(-EINVAL, "fragments need at least one point");
+    const size_t bpp = (n_x + blsgpu::frsec::EVAL_THREADS - 1) / blsgpu::frsec::EVAL_THREADS;
+    if (n_polys > 0x7FFFFFFFull || n_x > 0xFFFFFF00ull || (out_frag && n_polys * bpp > 0x7FFFFFFFull) || n_polys * t > 0xFFFFFFF0ull)
+        return fail(-EINVAL, "batch too large");
+    return 0;
+}
+// commitments c_k G1 (k_fix_mul_secret) and fragments P(x_j) (k_fr_poly_eval_secret) of n_polys polynomials, all on the device
+int deal_secret_dev(blsgpu_ctx* c, const void* d_coeffs, size_t n_polys, size_t t, const void* d_x, size_t n_x, void* d_out_commit,
+                    void* d_out_frag, hipStream_t st) {
+    StreamGuard sg(c, st);
+    if (d_out_commit) {
+        if (int rc = fix_table(c, st, true)) return rc;
+        if (int rc = fix_mul_secret_launch(c, d_coeffs, n_polys * t, d_out_commit, nullptr, st)) return rc;
+    }
+    if (d_out_frag) {
+        const size_t bpp = (n_x + blsgpu::frsec::EVAL_THREADS - 1) / blsgpu::frsec::EVAL_THREADS;
+        KernelTimer kt(c, st, 10);
+        hipLaunchKernelGGL(blsgpu::frsec::k_fr_poly_eval_secret, dim3((unsigned)(n_polys * bpp)), dim3(blsgpu::frsec::EVAL_THREADS), t * 32, st,
+                           (const uint8_t*)d_coeffs, (uint32_t)t, (const uint8_t*)d_x, (uint32_t)n_x, (uint32_t)bpp, (uint8_t*)d_out_frag);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+// the argument checks of blsgpu_sign_threshold* (before anything is written); 1: nothing to do
+int sign_threshold_args(const blsgpu_ctx* c, size_t k, size_t groups, size_t n_msg, bool null_buffer, const void* out_aff, const void* out_ser) {
+    if (int rc = lagrange_args(c, k, groups, null_buffer)) return rc;
+    if (n_msg != 1 && n_msg != groups) return fail(-EINVAL, "n_msg must be 1 or groups");
+    if (!out_aff && !out_ser) return fail(-EINVAL, "out_aff and out_ser are both NULL");
+    return 0;
 }
 }  // namespace
 
@@ -2319,6 +2375,104 @@ BLSGPU_EXPORT int blsgpu_threshold_combine(blsgpu_ctx* c, const uint8_t* sigs_af
     if (int rc = s.alloc()) return rc;
     if (int rc = s.up()) return rc;
     if (int rc = threshold_combine_dev(c, s.at(dsig), s.at(dx), k, groups, s.at(dout), s.opt(dinf), s.at(dst), nullptr)) return rc;
+    return s.down();
+}
+
+// ------------------------------------------------------------ threshold dealing, recovery and share signing for secrets --
+BLSGPU_EXPORT int blsgpu_threshold_deal_secret_dev(blsgpu_ctx* c, const void* d_coeffs, size_t n_polys, size_t t, const void* d_x, size_t n_x,
+                                                   void* d_out_commit_aff, void* d_out_frag, void* stream) {
+    if (int rc = deal_args(c, d_coeffs, n_polys, t, d_x, n_x, d_out_commit_aff, d_out_frag)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return deal_secret_dev(c, d_coeffs, n_polys, t, d_x, n_x, d_out_commit_aff, d_out_frag, (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_threshold_deal_secret(blsgpu_ctx* c, const uint8_t* coeffs, size_t n_polys, size_t t, const uint8_t* x, size_t n_x,
+                                               uint8_t* out_commit_aff, uint8_t* out_frag) {
+    if (int rc = deal_args(c, coeffs, n_polys, t, x, n_x, out_commit_aff, out_frag)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    // whole polynomials per staged slice: about 64 MB of staging
+    const size_t per_poly = t * (32 + 96) + (out_frag ? n_x * 32 : 0), fit = ((size_t)1 << 26) / per_poly;
+    const size_t S = n_polys < fit ? n_polys : (fit ? fit : 1);
+    Staging s(c);
+    const int dco = s.in(coeffs, S, t * 32), dx = s.in(out_frag ? x : nullptr, n_x * 32), dcm = s.out(out_commit_aff, S, t * 96),
+              dfr = s.out(out_frag, S, n_x * 32);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    return for_slices(n_polys, S, [&](size_t lo, size_t m) {
+        if (int rc = s.up(lo, m)) return rc;
+        if (int rc = deal_secret_dev(c, s.at(dco), m, t, s.opt(dx), n_x, s.opt(dcm), s.opt(dfr), nullptr)) return rc;
+        return s.down(lo, m);
+    });
+}
+
+BLSGPU_EXPORT int blsgpu_fr_interpolate_at_zero_secret_dev(blsgpu_ctx* c, const void* d_x, const void* d_y, size_t k, size_t groups, void* d_out,
+                                                           void* d_status, void* stream) {
+    if (int rc = lagrange_args(c, k, groups, !d_x || !d_y || !d_out || !d_status)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return fr_interpolate_secret_dev(c, d_x, d_y, k, groups, d_out, d_status, (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_fr_interpolate_at_zero_secret(blsgpu_ctx* c, const uint8_t* x, const uint8_t* y, size_t k, size_t groups, uint8_t* out,
+                                                       uint8_t* status) {
+    if (int rc = lagrange_args(c, k, groups, !x || !y || !out || !status)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    Staging s(c);
+    const int dx = s.in(x, groups * k * 32), dy = s.in(y, groups * k * 32), dout = s.out(out, groups * 32), dst = s.out(status, groups);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    if (int rc = fr_interpolate_secret_dev(c, s.at(dx), s.at(dy), k, groups, s.at(dout), s.at(dst), nullptr)) return rc;
+    return s.down();
+}
+
+// PrivateKey.sign_threshold's device work for `groups` sessions of k signers: the coefficients (k_lagrange) into the
+// workspace, lambda_i sk_i mod n (k_fr_scale_secret) beside them, H(m) per message, then k_g2_smul -- with ONE message its
+// table is built once and shared; with a message per session, session g's point is copied to its k slots slice by slice
+BLSGPU_EXPORT int blsgpu_sign_threshold_dev(blsgpu_ctx* c, const void* d_sks, const void* d_x, size_t k, size_t groups, const void* d_msg_hashes,
+                                            size_t n_msg, void* d_out_aff, void* d_out_ser, void* d_out_inf, void* d_status, void* stream) {
+    if (int rc = sign_threshold_args(c, k, groups, n_msg, !d_sks || !d_x || !d_msg_hashes || !d_status, d_out_aff, d_out_ser)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    using namespace blsgpu::g2smul;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = k * groups;
+    const bool shared = n_msg == 1;
+    const size_t held = g2_smul_tables(shared ? 1 : n, n);
+    const size_t sc_bytes = (n * 32 + 255) & ~(size_t)255, hm_bytes = (n_msg * BLSGPU_G2_BYTES + 255) & ~(size_t)255;
+    if (int rc = c->grow(B_LAGR_WS, n * 32)) return rc;
+    if (int rc = c->grow(B_FRS_WS, sc_bytes + (shared ? 0 : held * BLSGPU_G2_BYTES))) return rc;
+    if (int rc = c->grow(B_SMUL_WS, hm_bytes + held * TABLE_DW * 4)) return rc;
+    char* d_sc = c->at<char>(B_FRS_WS);
+    char* d_rep = d_sc + sc_bytes;
+    char* d_hm = c->at<char>(B_SMUL_WS);
+    uint32_t* table = (uint32_t*)(d_hm + hm_bytes);
+    {
+        StreamGuard sg(c, st);
+        if (int rc = lagrange_launch(c, d_x, k, groups, c->at<void>(B_LAGR_WS), d_status, st)) return rc;
+        KernelTimer kt(c, st, 10);
+        hipLaunchKernelGGL(blsgpu::frsec::k_fr_scale_secret, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c->at<uint8_t>(B_LAGR_WS),
+                           (const uint8_t*)d_sks, (uint32_t)n, (uint8_t*)d_sc);
+        HIP_TRY(hipGetLastError());
+    }
+    if (int rc = map_to_g2_impl(c, d_msg_hashes, n_msg, d_hm, st, true)) return rc;
+    StreamGuard sg(c, st);
+    if (shared) return g2_smul_launch(c, d_hm, 1, d_sc, n, d_out_aff, d_out_ser, d_out_inf, table, st);
+    return for_slices(n, SLICE, [&](size_t lo, size_t m) {
+        hipLaunchKernelGGL(blsgpu::frsec::k_g2_spread, dim3((unsigned)((m * 48 + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_hm, (uint32_t)k,
+                           lo, (uint32_t)m, (uint32_t*)d_rep);
+        HIP_TRY(hipGetLastError());
+        return g2_smul_launch(c, d_rep, m, d_sc + lo * 32, m, d_out_aff ? (char*)d_out_aff + lo * BLSGPU_G2_BYTES : nullptr,
+                              d_out_ser ? (char*)d_out_ser + lo * 96 : nullptr, d_out_inf ? (char*)d_out_inf + lo : nullptr, table, st);
+    });
+}
+BLSGPU_EXPORT int blsgpu_sign_threshold(blsgpu_ctx* c, const uint8_t* sks, const uint8_t* x, size_t k, size_t groups, const uint8_t* msg_hashes,
+                                        size_t n_msg, uint8_t* out_aff, uint8_t* out_ser, uint8_t* out_inf, uint8_t* status) {
+    if (int rc = sign_threshold_args(c, k, groups, n_msg, !sks || !x || !msg_hashes || !status, out_aff, out_ser)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = k * groups;
+    Staging s(c);
+    const int dsk = s.in(sks, n * 32), dx = s.in(x, n * 32), dh = s.in(msg_hashes, n_msg * 32), daff = s.out(out_aff, n * BLSGPU_G2_BYTES),
+              dser = s.out(out_ser, n * 96), dinf = s.out(out_inf, n), dst = s.out(status, groups);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    if (int rc = blsgpu_sign_threshold_dev(c, s.at(dsk), s.at(dx), k, groups, s.at(dh), n_msg, s.opt(daff), s.opt(dser), s.opt(dinf), s.at(dst),
+                                           nullptr)) return rc;
     return s.down();
 }
 

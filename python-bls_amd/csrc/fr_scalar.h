@@ -8,7 +8,8 @@
 // (uint64_t)a * b + t + carry is one v_mad_u64_u32 on the device; n = 1 mod 2^32, so the quotient word of every
 // reduction step is just -t[0].  Nothing here is generated.  The inversion is Fermat's x^(n-2) by square-and-multiply over
 // the public bits of n - 2; inv(0) = 0.
-// Not constant-time where it matters to a caller: is_zero and the status decisions branch on values.
+// Not constant-time where it matters to a caller: is_zero and the status decisions branch on values.  The forms for secret
+// operands -- mul_masked, add_masked, dot_term_masked and the polynomial evaluation on them -- are at the end of the file.
 //
 // The Lagrange step, exactly the reference's second barycentric form:
 //     w_j = prod_{i != j} (x_j - x_i),  shift_j = w_j^-1 (-x_j)^-1,  den = (sum_j shift_j)^-1,  L_j = shift_j den.
@@ -212,6 +213,101 @@ HD_FN void dot_term(const uint8_t* l_be, const uint8_t* y_be, uint32_t t[8]) {
     hdk::reduce_n(y);
     to_mont(l, l);
     mul(t, l, y);                                          // (L R) y / R
+}
+
+// ---- the same for SECRET operands (coefficients of a dealing, shares, keys) ----------------------------------------------
+// The last subtraction of every step is always computed and kept by a mask (hdk::sub_n_if_ge_masked): no branch, no ?:,
+// no early exit and no address that depends on an operand.  frs::sub above is already of this kind.  Values equal those of
+// mul / add / dot_term for every input (tests/test_frsecret_host.py).
+// mul's operand scanning (straight-line code that looks at no value) with the masked last subtraction
+HD_FN void mul_masked(uint32_t r[8], const uint32_t a[8], const uint32_t b[8]) {
+    const uint32_t nw[8] = HD_N_WORDS;
+    uint32_t t[9];
+#pragma unroll
+    for (int j = 0; j < 9; j++) t[j] = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        uint64_t c = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            c += (uint64_t)a[j] * b[i] + t[j];
+            t[j] = (uint32_t)c;
+            c >>= 32;
+        }
+        t[8] = (uint32_t)c;
+        const uint32_t m = 0u - t[0];                      // -n^-1 = -1 mod 2^32
+        c = ((uint64_t)m * nw[0] + t[0]) >> 32;
+#pragma unroll
+        for (int j = 1; j < 8; j++) {
+            c += (uint64_t)m * nw[j] + t[j];
+            t[j - 1] = (uint32_t)c;
+            c >>= 32;
+        }
+        t[7] = t[8] + (uint32_t)c;
+    }
+    hdk::sub_n_if_ge_masked(t);
+    copy(r, t);
+}
+HD_FN void add_masked(uint32_t r[8], const uint32_t a[8], const uint32_t b[8]) { hdk::add_mod_n_masked(r, a, b); }
+HD_FN void to_mont_masked(uint32_t r[8], const uint32_t a[8]) {
+    const uint32_t r2[8] = FRS_R2_WORDS;
+    mul_masked(r, a, r2);
+}
+HD_FN void from_mont_masked(uint32_t r[8], const uint32_t a[8]) {
+    uint32_t one[8];
+    set_zero(one);
+    one[0] = 1;
+    mul_masked(r, a, one);
+}
+// dot_term for a PUBLIC coefficient L (below n) and a SECRET y < 2^256
+HD_FN void dot_term_masked(const uint8_t* l_be, const uint8_t* y_be, uint32_t t[8]) {
+    uint32_t l[8], y[8];
+    from_be(l_be, l);
+    from_be(y_be, y);
+    hdk::reduce_n_masked(y);
+    to_mont(l, l);                                         // L is public
+    mul_masked(t, l, y);
+}
+
+// ---- a dealing's fragments: P(x) = sum_k c_k x^k mod n for SECRET coefficients and PUBLIC points ---------------------------
+// a coefficient (32 bytes big-endian, any value below 2^256) reduced and in Montgomery form
+HD_FN void poly_coeff_masked(const uint8_t* be, uint32_t cm[8]) {
+    uint32_t c[8];
+    from_be(be, c);
+    hdk::reduce_n_masked(c);
+    to_mont_masked(cm, c);
+}
+// a point (a player number: public, so the reduction may branch), reduced and in Montgomery form
+HD_FN void poly_point(const uint8_t* be, uint32_t xm[8]) {
+    uint32_t x[8];
+    from_be(be, x);
+    hdk::reduce_n(x);
+    to_mont(xm, x);
+}
+// Horner from the top coefficient over the t >= 1 coefficients C (Montgomery form, 8 words each): t - 1 masked products
+// and additions; step k reads coefficient k, whatever the values.  r: canonical, not in Montgomery form.
+HD_FN void poly_horner_masked(const uint32_t* C, uint32_t t, const uint32_t xm[8], uint32_t r[8]) {
+    uint32_t acc[8];
+    copy(acc, C + 8 * (size_t)(t - 1));
+#if defined(__HIPCC__)
+#pragma unroll 1
+#endif
+    for (uint32_t k = t - 1; k-- > 0;) {
+        mul_masked(acc, acc, xm);
+        add_masked(acc, acc, C + 8 * (size_t)k);
+    }
+    from_mont_masked(r, acc);
+}
+// One polynomial at n_x points, serially (the host test's view of what k_fr_poly_eval_secret spreads over lanes): coeffs
+// t x 32 bytes, x and out n_x x 32 bytes big-endian, work 8 t words.
+HD_FN void poly_eval_masked(const uint8_t* coeffs, uint32_t t, const uint8_t* x, uint32_t n_x, uint32_t* work, uint8_t* out) {
+    for (uint32_t k = 0; k < t; k++) poly_coeff_masked(coeffs + 32 * (size_t)k, work + 8 * (size_t)k);
+    for (uint32_t j = 0; j < n_x; j++) {
+        uint32_t xm[8], r[8];
+        poly_point(x + 32 * (size_t)j, xm);
+        poly_horner_masked(work, t, xm, r);
+        to_be(r, out + 32 * (size_t)j);
+    }
 }
 
 }  // namespace frs
