@@ -392,8 +392,8 @@ int blsgpu_hd_paths_secret_dev(blsgpu_ctx *ctx, const void *d_parents, size_t n_
  * The commitments are prepared once per call (csrc/blsgpu_g1poly.hip): L28 form, and a check [n] C_k == O per commitment;
  * then one fragment per lane: Horner in the exponent over the bits of x_i mod n, (s_i mod n) G1 on blsgpu_g1_mul_gen's
  * table, a projective comparison.  Sort the fragments by polynomial: a wavefront then reads one polynomial.  The loops
- * follow the bits of the (public) x_i and the table gathers the digits of s_i: NOT constant-time (there is no secret form
- * of this check; the dealer's side is blsgpu_threshold_deal_secret). */
+ * follow the bits of the (public) x_i and the table gathers the digits of s_i: NOT constant-time.  A player checking the
+ * fragments it was dealt uses blsgpu_g1_poly_check_secret below; the dealer's side is blsgpu_threshold_deal_secret. */
 int blsgpu_g1_poly_check(blsgpu_ctx *ctx, const uint8_t *commit, size_t n_polys, size_t t, const uint32_t *poly,
                          const uint8_t *x, const uint8_t *s, size_t n, uint8_t *status, uint8_t *out_aff);
 /* The same with every buffer in device memory, enqueued on `stream`.  The indices are first scanned on the device and the
@@ -484,11 +484,13 @@ int blsgpu_sign(blsgpu_ctx *ctx, const uint8_t *sks, const uint8_t *msg_hashes, 
 int blsgpu_sign_dev(blsgpu_ctx *ctx, const void *d_sks, const void *d_msg_hashes, size_t n_msg, size_t n, void *d_out_aff,
                     void *d_out_ser, void *stream);
 
-/* The threshold scheme's work on SECRET scalars (csrc/blsgpu_frsecret.hip on the masked forms of csrc/fr_scalar.h).  The claim
- * of the three calls below is exactly that of blsgpu_g1_mul_gen_secret and blsgpu_g2_mul_secret: the sequence of instructions
- * and of memory addresses does not depend on the coefficients, shares or keys.  It does depend on t, k, the counts and the
- * evaluation points x (player numbers), which are public -- and so do the Lagrange coefficients computed from them.  NOT
- * claimed: data-dependent timing inside the hardware (how long an instruction or a memory access takes for given values).
+/* The threshold scheme's work on SECRET scalars (csrc/blsgpu_frsecret.hip on the masked forms of csrc/fr_scalar.h, and
+ * k_poly_eval_secret of csrc/blsgpu_g1poly.hip).  The claim of the five calls below is exactly that of blsgpu_g1_mul_gen_secret
+ * and blsgpu_g2_mul_secret: the sequence of instructions and of memory addresses does not depend on the coefficients,
+ * fragments, shares or keys.  It does depend on t, k, the counts and the evaluation points x (player numbers), which are
+ * public -- and so do the Lagrange coefficients computed from them -- and, in the share check, on the commitments, the
+ * polynomial indices and the OUTCOME of the check: the status is what a player publishes as a complaint.  NOT claimed:
+ * data-dependent timing inside the hardware (how long an instruction or a memory access takes for given values).
  *
  * Joint-Feldman dealing (PrivateKey.new_threshold, keys.py:92-117 of the reference) of n_polys polynomials of t coefficients
  * at once.  coeffs: n_polys x t x 32 bytes big-endian, coefficient k of polynomial p at index p * t + k, any value below
@@ -512,6 +514,34 @@ int blsgpu_fr_interpolate_at_zero_secret(blsgpu_ctx *ctx, const uint8_t *x, cons
                                          uint8_t *out, uint8_t *status);
 int blsgpu_fr_interpolate_at_zero_secret_dev(blsgpu_ctx *ctx, const void *d_x, const void *d_y, size_t k, size_t groups,
                                              void *d_out, void *d_status, void *stream);
+/* blsgpu_g1_poly_check for SECRET fragments s_i (step 2 of Joint-Feldman: a player checks what it was dealt): the same
+ * arguments, validation and layout, and for every s below 2^256 the same status and out_aff bytes.  s and status are
+ * required -- NULL with n > 0 is -EINVAL before anything is written; there is no evaluation-only mode -- and out_aff may be
+ * NULL.  The commitments are prepared as in blsgpu_g1_poly_check (k_poly_prep, k_poly_subgroup); then k_poly_eval_secret, one
+ * fragment per lane: the left-hand side is s_i G1 for the LITERAL 256-bit s_i (no reduction mod n; G1 has order n) on the
+ * schedule and the 58 KB table of blsgpu_g1_mul_gen_secret -- 65 windows, all eight entries of a window read and one kept by
+ * select, one complete addition each, no inversion -- and the right-hand side and the projective comparison are those of
+ * k_poly_eval over the bits of the public x_i.  The claim and its limits are stated above. */
+int blsgpu_g1_poly_check_secret(blsgpu_ctx *ctx, const uint8_t *commit, size_t n_polys, size_t t, const uint32_t *poly,
+                                const uint8_t *x, const uint8_t *s, size_t n, uint8_t *status, uint8_t *out_aff);
+/* The same with every buffer in device memory, enqueued on `stream`; the one synchronisation of the index scan stays. */
+int blsgpu_g1_poly_check_secret_dev(blsgpu_ctx *ctx, const void *d_commit, size_t n_polys, size_t t, const void *d_poly,
+                                    const void *d_x, const void *d_s, size_t n, void *d_status, void *d_out_aff,
+                                    void *stream);
+/* A player's share (step 3 of Joint-Feldman, BLS.aggregate_priv_keys without secure aggregation) for `groups` players at
+ * once: out[g] = sum_j y[g * k + j] mod n, the canonical integer below n, 32 bytes big-endian.  y: groups x k x 32 bytes
+ * big-endian, any value below 2^256; k >= 1 has no upper limit.  k_fr_sum_secret: a masked reduction and a masked addition per
+ * term (no Montgomery form, no product); whole groups share a workgroup of 256 lanes while k <= 256, above that a group has a
+ * workgroup to itself and its lanes stride over the terms.  out (groups x 32) is required.  out_pk_aff (groups x 96) and
+ * out_pk_ser (groups x 48) may each be NULL: the public key of every sum as blsgpu_g1_mul_gen_secret writes it, from
+ * k_fix_mul_secret reading the sums where the first kernel left them -- nothing returns to the host in between.  -EINVAL
+ * before anything is written: k == 0, or a NULL required buffer with groups > 0.  groups == 0 writes nothing and returns 0.
+ * The claim and its limits are stated above. */
+int blsgpu_fr_sum_secret(blsgpu_ctx *ctx, const uint8_t *y, size_t k, size_t groups, uint8_t *out, uint8_t *out_pk_aff,
+                         uint8_t *out_pk_ser);
+/* The same with every buffer in device memory, enqueued on `stream` (no synchronisation). */
+int blsgpu_fr_sum_secret_dev(blsgpu_ctx *ctx, const void *d_y, size_t k, size_t groups, void *d_out, void *d_out_pk_aff,
+                             void *d_out_pk_ser, void *stream);
 /* Unit signatures of `groups` threshold sessions of k signers each (PrivateKey.sign_threshold, keys.py:134-141 of the
  * reference): out[g * k + j] = (lambda_gj sk_gj mod n) H(h_(n_msg == 1 ? 0 : g)) with lambda_g the Lagrange coefficients at
  * zero of session g's players.  sks and x: groups x k x 32 bytes big-endian (share and player number of signer j of session
@@ -540,10 +570,12 @@ int blsgpu_sign_threshold_dev(blsgpu_ctx *ctx, const void *d_sks, const void *d_
  * product), 1 = k_reduce (partial products), 2 = k_reduce with the final
  * exponentiation, 3 = k_miller_slow (degenerate pairs; empty work list normally); the line-stream stages use 4 .. 7, and
  * 8 = k_g2_smul with its table kernel (one record per blsgpu_g2_mul_secret / per slice of blsgpu_sign),
- * 9 = k_fix_mul_secret (one record per blsgpu_g1_mul_gen_secret_dev call / per level of blsgpu_hd_paths_secret),
- * 10 = the scalar kernels on secrets: k_fr_poly_eval_secret, k_fr_dot_secret, k_fr_scale_secret (one record per call of
- * blsgpu_threshold_deal_secret_dev with fragments, blsgpu_fr_interpolate_at_zero_secret_dev, blsgpu_sign_threshold_dev; the
- * G1 / G2 halves of those calls keep their kinds 9 and 8).
+ * 9 = the G1 kernels on secrets: k_fix_mul_secret (one record per blsgpu_g1_mul_gen_secret_dev call / per level of
+ * blsgpu_hd_paths_secret / per blsgpu_fr_sum_secret_dev call with keys) and k_poly_eval_secret (one record per
+ * blsgpu_g1_poly_check_secret_dev call / per staged slice of the host form),
+ * 10 = the scalar kernels on secrets: k_fr_poly_eval_secret, k_fr_dot_secret, k_fr_scale_secret, k_fr_sum_secret (one record
+ * per call of blsgpu_threshold_deal_secret_dev with fragments, blsgpu_fr_interpolate_at_zero_secret_dev,
+ * blsgpu_sign_threshold_dev, blsgpu_fr_sum_secret_dev; the G1 / G2 halves of those calls keep their kinds 9 and 8).
  * Reading resets the ring. */
 int blsgpu_timing_enable(blsgpu_ctx *ctx, int enable);
 int blsgpu_timing_read(blsgpu_ctx *ctx, float *ms, int *kind, size_t cap, size_t *count);

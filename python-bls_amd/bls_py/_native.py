@@ -37,6 +37,7 @@ SYMBOLS = (
     "blsgpu_threshold_deal_secret", "blsgpu_threshold_deal_secret_dev",
     "blsgpu_fr_interpolate_at_zero_secret", "blsgpu_fr_interpolate_at_zero_secret_dev",
     "blsgpu_sign_threshold", "blsgpu_sign_threshold_dev",
+    "blsgpu_g1_poly_check_secret", "blsgpu_g1_poly_check_secret_dev", "blsgpu_fr_sum_secret", "blsgpu_fr_sum_secret_dev",
 )
 
 HD_PARENT_BYTES = 160          # BLSGPU_HD_PARENT_BYTES: chain code (32), public key affine (96), private key (32)
@@ -151,6 +152,10 @@ def load_library(path=None):
         L.blsgpu_fr_interpolate_at_zero_secret_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
         L.blsgpu_sign_threshold.argtypes = [vp, cp, cp, sz, sz, cp, sz, vp, vp, vp, vp]
         L.blsgpu_sign_threshold_dev.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp]
+        L.blsgpu_g1_poly_check_secret.argtypes = [vp, cp, sz, sz, vp, cp, cp, sz, vp, vp]
+        L.blsgpu_g1_poly_check_secret_dev.argtypes = [vp, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp]
+        L.blsgpu_fr_sum_secret.argtypes = [vp, cp, sz, sz, vp, vp, vp]
+        L.blsgpu_fr_sum_secret_dev.argtypes = [vp, vp, sz, sz, vp, vp, vp, vp]
         L.blsgpu_timing_enable.argtypes = [vp, ctypes.c_int]
         L.blsgpu_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int), sz,
                                          ctypes.POINTER(sz)]
@@ -496,7 +501,19 @@ class Engine:
                                                  d_out_chain, d_out_sk, d_out_pk_aff, d_out_pk_ser, d_out_parent_fp, stream),
                     "blsgpu_hd_paths_dev")
 
-    def g1_poly_check(self, commit, n_polys, t, poly, x, s=None, aff=False):
+    def g1_poly_check_secret(self, commit, n_polys, t, poly, x, s, aff=False):
+        """g1_poly_check for SECRET fragments s on the scalar-independent schedule of blsgpu_g1_poly_check_secret: the same
+        arguments (s is required: there is no evaluation-only mode), the same bytes.
+        -> (n status bytes (1 equal, 0 not, 2 undecided), n x 96 affine Horner values or None)"""
+        if s is None:
+            raise ValueError("the secret form has no evaluation-only mode")
+        return self.g1_poly_check(commit, n_polys, t, poly, x, s, aff, secret=True)
+
+    def g1_poly_check_secret_dev(self, d_commit, n_polys, t, d_poly, d_x, d_s, n, d_status, d_out_aff, stream=0):
+        self._check(self.lib.blsgpu_g1_poly_check_secret_dev(self.h, d_commit, n_polys, t, d_poly, d_x, d_s, n, d_status, d_out_aff,
+                                                             stream), "blsgpu_g1_poly_check_secret_dev")
+
+    def g1_poly_check(self, commit, n_polys, t, poly, x, s=None, aff=False, secret=False):
         """Feldman share checks (blsgpu_g1_poly_check): commit n_polys x t x 96 affine bytes, poly n indices, x / s n x 32
         bytes big-endian (or ints below 2^256); s None = evaluation only.
         -> (n status bytes (1 equal, 0 not, 2 undecided) or None, n x 96 affine Horner values or None)"""
@@ -514,8 +531,9 @@ class Engine:
         idx = (ctypes.c_uint32 * max(1, n))(*poly)
         st = ctypes.create_string_buffer(max(1, n)) if sb is not None else None
         oa = ctypes.create_string_buffer(max(1, 96 * n)) if aff else None
-        self._check(self.lib.blsgpu_g1_poly_check(self.h, bytes(commit), n_polys, t, idx, bytes(xb), None if sb is None else bytes(sb), n,
-                                                  st, oa), "blsgpu_g1_poly_check")
+        name = "blsgpu_g1_poly_check_secret" if secret else "blsgpu_g1_poly_check"
+        self._check(getattr(self.lib, name)(self.h, bytes(commit), n_polys, t, idx, bytes(xb), None if sb is None else bytes(sb), n,
+                                            st, oa), name)
         return (st.raw[:n] if st is not None else None), (oa.raw[:96 * n] if aff else None)
 
     def g1_poly_check_dev(self, d_commit, n_polys, t, d_poly, d_x, d_s, n, d_status, d_out_aff, stream=0):
@@ -670,6 +688,24 @@ class Engine:
     def fr_interpolate_at_zero_secret_dev(self, d_x, d_y, k, groups, d_out, d_status, stream=0):
         self._check(self.lib.blsgpu_fr_interpolate_at_zero_secret_dev(self.h, d_x, d_y, k, groups, d_out, d_status, stream),
                     "blsgpu_fr_interpolate_at_zero_secret_dev")
+
+    def fr_sum_secret(self, y, k, groups=1, pk=False, aff=False, ser=False):
+        """sum_j y_j mod n per group for SECRET y (blsgpu_fr_sum_secret: a player's share from the fragments it was dealt): y
+        groups x k x 32 bytes big-endian (or ints below 2^256), k >= 1.  pk: both forms of the public key of every sum
+        (aff / ser: one of them), multiplied on the device by k_fix_mul_secret.
+        -> (groups x 32 bytes, groups x 96 affine bytes or None, groups x 48 serialised bytes or None)"""
+        if k < 1:
+            raise ValueError("k must be at least 1")
+        aff, ser = aff or pk, ser or pk
+        out = ctypes.create_string_buffer(max(1, 32 * groups))
+        oa = ctypes.create_string_buffer(max(1, 96 * groups)) if aff else None
+        os_ = ctypes.create_string_buffer(max(1, 48 * groups)) if ser else None
+        self._check(self.lib.blsgpu_fr_sum_secret(self.h, self._scalars(y, k * groups, "y"), k, groups, out, oa, os_), "blsgpu_fr_sum_secret")
+        return out.raw[:32 * groups], (oa.raw[:96 * groups] if aff else None), (os_.raw[:48 * groups] if ser else None)
+
+    def fr_sum_secret_dev(self, d_y, k, groups, d_out, d_out_pk_aff, d_out_pk_ser, stream=0):
+        self._check(self.lib.blsgpu_fr_sum_secret_dev(self.h, d_y, k, groups, d_out, d_out_pk_aff, d_out_pk_ser, stream),
+                    "blsgpu_fr_sum_secret_dev")
 
     def sign_threshold(self, sks, x, k, msg_hashes, groups=1, aff=True, ser=True):
         """Unit signatures (lambda_j sk_j mod n) H(h) of `groups` sessions of k signers (blsgpu_sign_threshold): sks, x

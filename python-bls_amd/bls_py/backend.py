@@ -118,6 +118,16 @@ class HipProvider:
         """fr_interpolate_at_zero on the masked sums: the same outputs"""
         return self._eng.fr_interpolate_at_zero_secret(x, y, k, groups)
 
+    def g1_poly_check_secret(self, commit: bytes, n_polys: int, t: int, poly, x: bytes, s, aff: bool = False):
+        """g1_poly_check for secret fragments (s is required), the left-hand sides on the scalar-independent schedule: the
+        same outputs"""
+        return self._eng.g1_poly_check_secret(commit, n_polys, t, poly, x, s, aff)
+
+    def fr_sum_secret(self, y, k: int, groups: int = 1, pk: bool = False):
+        """-> (groups x 32 bytes: sum_j y_j mod n on the masked sums, and with pk the public key of every sum, multiplied on the
+        device: groups x 96 affine bytes, groups x 48 serialised bytes -- else None, None)"""
+        return self._eng.fr_sum_secret(y, k, groups, pk)
+
     def sign_threshold(self, sks, x, k: int, msg_hashes: bytes, groups: int = 1, aff: bool = True, ser: bool = True):
         """(lambda_j sk_j mod n) H(h) per signer: -> (affine bytes, serialised bytes, [is_infinity], groups status bytes)"""
         return self._eng.sign_threshold(sks, x, k, msg_hashes, groups, aff, ser)
@@ -146,7 +156,9 @@ def use(provider):
     Optional (the secret=True forms of the key methods raise without them; there is no other path for them):
     g1_mul_gen_secret(scalars) -> (affine bytes, serialised bytes), hd_paths_secret(parents, parent_of|None, paths) -> as hd_paths,
     threshold_deal_secret(coeffs, t, x) -> (commitment bytes, fragment bytes), fr_interpolate_at_zero_secret(x, y, k, groups) ->
-    as fr_interpolate_at_zero, sign_threshold(sks, x, k, msg_hashes, groups) -> (affine bytes, serialised bytes, [is_inf], status bytes).
+    as fr_interpolate_at_zero, sign_threshold(sks, x, k, msg_hashes, groups) -> (affine bytes, serialised bytes, [is_inf], status bytes),
+    g1_poly_check_secret(commit, n_polys, t, poly, x, s, aff) -> as g1_poly_check, fr_sum_secret(y, k, groups, pk) ->
+    (32 bytes per group, affine bytes|None, serialised bytes|None).
     Optional (a provider without them sends the Threshold.*_batch methods to the host loop): LAGRANGE_MAX_K,
     lagrange_at_zero(x, k, groups) -> (coefficient bytes, status bytes), fr_interpolate_at_zero(x, y, k, groups) ->
     (32 bytes per group, status bytes), threshold_combine(sigs, x, k, groups) -> (affine bytes, [is_inf], status bytes)."""

@@ -338,3 +338,33 @@ class BLS:
             ts = hash_pks(len(private_keys), public_keys)
             total = sum(sk.value * t for t, (_, sk) in zip(ts, pairs)) % GROUP_ORDER
         return PrivateKey.from_bytes(total.to_bytes(32, "big"))
+
+    @staticmethod
+    def aggregate_priv_keys_batch(groups, secret=False, public_keys=False):
+        """[BLS.aggregate_priv_keys(g, None, False) for g in groups] -- step 3 of Joint-Feldman, a player's share as the sum
+        of the fragments it was dealt -- and with public_keys=True (keys, [k.get_public_key() for k in keys]).  The
+        default is that loop on the host.  secret=True: one blsgpu_fr_sum_secret call per distinct group length, whose
+        sequence of instructions and addresses does not depend on the keys; with public_keys=True the same call
+        multiplies the sums by G1 on the device (k_fix_mul_secret) before anything returns.  A provider without the
+        entry raises NotImplementedError, an empty group ValueError.  Secure aggregation (hash_pks) has no batch form."""
+        groups = [list(g) for g in groups]
+        if not secret:
+            keys = [BLS.aggregate_priv_keys(g, None, False) for g in groups]
+            return (keys, [k.get_public_key() for k in keys]) if public_keys else keys
+        from .keys import _pk_from_device, _secret_call
+        fr_sum = _secret_call("fr_sum_secret")
+        if any(not g for g in groups):
+            raise ValueError("secret=True: an empty group has no device form")
+        buckets = {}
+        for i, g in enumerate(groups):
+            buckets.setdefault(len(g), []).append(i)
+        keys, pks = [None] * len(groups), [None] * len(groups)
+        for k, idx in buckets.items():
+            yb = b"".join(sk.value.to_bytes(32, "big") for i in idx for sk in groups[i])
+            out, aff, ser = fr_sum(yb, k, len(idx), public_keys)
+            for q, i in enumerate(idx):
+                keys[i] = PrivateKey.from_bytes(out[32 * q:32 * (q + 1)])
+                if public_keys:
+                    pks[i] = _pk_from_device(aff[96 * q:96 * (q + 1)], ser[48 * q:48 * (q + 1)])
+                    keys[i].__dict__["_pk_point"] = pks[i].value          # the cache get_public_key fills (same point)
+        return (keys, pks) if public_keys else keys

@@ -40,14 +40,20 @@ class Threshold:
         return lhs == rhs
 
     @staticmethod
-    def verify_secret_fragment_batch(T, secret_fragments, players, commitments, ec=default_ec):
+    def verify_secret_fragment_batch(T, secret_fragments, players, commitments, ec=default_ec, secret=False):
         """[verify_secret_fragment(T, s, p, C) for s, p, C in zip(secret_fragments, players, commitments)] with the
         checks of on-curve G1 commitments on the GPU (blsgpu_g1_poly_check): the commitment lists are deduplicated into
         polynomials, every fragment is one lane of a Horner evaluation in the exponent.  The assertions of the single
         call run for every element first.  Lists holding anything but on-curve G1 AffinePoints, fragments that are
         neither an Fq mod n nor an int in [1, n) and players that are not ints take the host loop; a polynomial with a
         commitment C_k (k >= 1) outside the order-n subgroup (where Horner's x^k and the reference's x^k mod n differ)
-        is decided exactly by one grouped multi-scalar sum with the scalars x^k mod n."""
+        is decided exactly by one grouped multi-scalar sum with the scalars x^k mod n.
+        secret=True (a player checking what it was dealt): every record on blsgpu_g1_poly_check_secret, whose sequence of
+        instructions and addresses does not depend on the fragments -- the left-hand sides of the undecided records come
+        from blsgpu_g1_mul_gen_secret likewise.  Nothing takes the host loop then: a provider without the entries raises
+        NotImplementedError, a record the device cannot take -- a commitment list that is not all on-curve G1
+        AffinePoints, a player that is not an int, a fragment that is neither an Fq mod n nor an int in [1, n), another
+        curve, T < 1 -- ValueError.  The results themselves are public: a player publishes them as complaints."""
         secret_fragments, players, commitments = list(secret_fragments), list(players), list(commitments)
         if not (len(secret_fragments) == len(players) == len(commitments)):
             raise ValueError("need one player and one commitment list per fragment")
@@ -56,6 +62,10 @@ class Threshold:
             assert s != 0
             assert p != 0
         n = ec.n
+        check = mul_gen = None
+        if secret:
+            from .keys import _secret_call
+            check, mul_gen = _secret_call("g1_poly_check_secret"), _secret_call("g1_mul_gen_secret")
         host_only = T < 1 or ec is not default_ec          # (the device knows the one curve, and t >= 1)
         results = [None] * len(players)
         polys, by_id, by_content = [], {}, {}      # device polynomials: commitment lists deduplicated
@@ -71,6 +81,8 @@ class Threshold:
                 by_id[id(C)] = j
             if (j < 0 or host_only or type(p) is not int
                     or not ((type(s) is Fq and s.Q == n) or (type(s) is int and 0 < s < n))):
+                if secret:
+                    raise ValueError("secret=True: a record that the device cannot take (see verify_secret_fragment_batch)")
                 results[i] = Threshold.verify_secret_fragment(T, s, p, C, ec)
             else:
                 dev.append((i, j))
@@ -81,7 +93,10 @@ class Threshold:
         commit = b"".join(H.g1_affine_bytes(pt._aff()) for C in polys for pt in C)
         xb = b"".join((players[i] % n).to_bytes(32, "big") for i, _ in dev)
         sb = b"".join(int(secret_fragments[i]).to_bytes(32, "big") for i, _ in dev)
-        status, _ = backend.get().g1_poly_check(commit, len(polys), T, [j for _, j in dev], xb, sb)
+        if secret:
+            status, _ = check(commit, len(polys), T, [j for _, j in dev], xb, sb)
+        else:
+            status, _ = backend.get().g1_poly_check(commit, len(polys), T, [j for _, j in dev], xb, sb)
         undecided = []
         for (i, j), st in zip(dev, status):
             if st == 2:
@@ -93,7 +108,8 @@ class Threshold:
             from .bls import _g1_sums
             sums = _g1_sums([[pt.to_jacobian() for pt in polys[j]] for _, j in undecided],
                             [[pow(players[i], k, n) for k in range(T)] for i, _ in undecided])
-            lhs, _ = backend.get().g1_mul_gen(b"".join(int(secret_fragments[i]).to_bytes(32, "big") for i, _ in undecided))
+            ub = b"".join(int(secret_fragments[i]).to_bytes(32, "big") for i, _ in undecided)
+            lhs, _ = mul_gen(ub) if secret else backend.get().g1_mul_gen(ub)
             for e, ((i, _), J) in enumerate(zip(undecided, sums)):
                 rhs = bytes(96) if J.infinity else H.g1_affine_bytes(J.to_affine()._aff())
                 results[i] = lhs[96 * e:96 * (e + 1)] == rhs

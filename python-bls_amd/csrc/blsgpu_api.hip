@@ -694,11 +694,12 @@ int poly_ws(blsgpu_ctx* c, size_t n_polys, size_t t) {
     return c->grow(B_POLY_WS, poly_ws_l28(n_polys) + n_polys * t * blsgpu::g1poly::ENTRY_DW * 4);
 }
 
-// the commitments of the call, once: L28 entries, then the subgroup flags (caller: StreamGuard, poly_ws)
-int poly_prep(blsgpu_ctx* c, const void* d_commit, size_t n_polys, size_t t, bool table, hipStream_t st) {
+// the commitments of the call, once: L28 entries, then the subgroup flags (caller: StreamGuard, poly_ws); `table`: the
+// left-hand sides need the fixed-base table -- `secret`: the signed 4-bit one of k_poly_eval_secret
+int poly_prep(blsgpu_ctx* c, const void* d_commit, size_t n_polys, size_t t, bool table, hipStream_t st, bool secret = false) {
     using namespace blsgpu::g1poly;
     if (table) {
-        if (int rc = fix_table(c, st)) return rc;
+        if (int rc = fix_table(c, st, secret)) return rc;
     }
     char* ws = c->at<char>(B_POLY_WS);
     const size_t m = n_polys * t;
@@ -715,27 +716,35 @@ int poly_prep(blsgpu_ctx* c, const void* d_commit, size_t n_polys, size_t t, boo
     return 0;
 }
 
-// n fragments against the prepared commitments, FIX_SLICE per launch (caller: StreamGuard, poly_prep)
+// n fragments against the prepared commitments, FIX_SLICE per launch (caller: StreamGuard, poly_prep); `secret`:
+// k_poly_eval_secret on the signed 4-bit table (timing kind 9, one record per call)
 int poly_eval_launch(blsgpu_ctx* c, size_t n_polys, size_t t, const void* d_poly, const void* d_x, const void* d_s, size_t n, void* d_status,
-                     void* d_out_aff, hipStream_t st) {
+                     void* d_out_aff, hipStream_t st, bool secret = false) {
     char* ws = c->at<char>(B_POLY_WS);
-    for (size_t lo = 0; lo < n; lo += FIX_SLICE) {
-        const size_t m = n - lo < FIX_SLICE ? n - lo : FIX_SLICE;
-        hipLaunchKernelGGL(blsgpu::g1poly::k_poly_eval, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
-                           (const uint32_t*)c->d_fix_table, (const uint32_t*)(ws + poly_ws_l28(n_polys)), (const uint32_t*)(ws + 256),
-                           (uint32_t)n_polys, (uint32_t)t, (const uint32_t*)d_poly + lo, (const uint32_t*)d_x + lo * 8,
-                           d_s ? (const uint32_t*)d_s + lo * 8 : nullptr, (uint32_t)m, d_status ? (uint8_t*)d_status + lo : nullptr,
-                           d_out_aff ? (uint32_t*)d_out_aff + lo * 24 : nullptr);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
+    auto launches = [&]() {
+        return for_slices(n, FIX_SLICE, [&](size_t lo, size_t m) {
+            hipLaunchKernelGGL(secret ? blsgpu::g1poly::k_poly_eval_secret : blsgpu::g1poly::k_poly_eval, dim3((unsigned)((m + 255) / 256)),
+                               dim3(256), 0, st, (const uint32_t*)(secret ? c->d_fix_table_secret : c->d_fix_table),
+                               (const uint32_t*)(ws + poly_ws_l28(n_polys)), (const uint32_t*)(ws + 256), (uint32_t)n_polys, (uint32_t)t,
+                               (const uint32_t*)d_poly + lo, (const uint32_t*)d_x + lo * 8, d_s ? (const uint32_t*)d_s + lo * 8 : nullptr,
+                               (uint32_t)m, d_status ? (uint8_t*)d_status + lo : nullptr,
+                               d_out_aff ? (uint32_t*)d_out_aff + lo * 24 : nullptr);
+            HIP_TRY(hipGetLastError());
+            return 0;
+        });
+    };
+    if (!secret) return launches();
+    KernelTimer kt(c, st, 9);
+    return launches();
 }
 
 // the _dev form: a device scan of the indices and one synchronising read of its flag first (-EINVAL before anything is written)
+// (`secret`: blsgpu_g1_poly_check_secret_dev -- s and status are required)
 int poly_check_dev(blsgpu_ctx* c, const void* d_commit, size_t n_polys, size_t t, const void* d_poly, const void* d_x, const void* d_s,
-                   size_t n, void* d_status, void* d_out_aff, hipStream_t st) {
+                   size_t n, void* d_status, void* d_out_aff, hipStream_t st, bool secret = false) {
     if (t == 0) return fail(-EINVAL, "t must be at least 1");
     if (n == 0) return 0;
+    if (secret && (!d_s || !d_status)) return fail(-EINVAL, "s and status are required");
     if (int rc = poly_args(n_polys, t, d_commit, d_poly, d_x, d_s, d_status, d_out_aff)) return rc;
     StreamGuard sg(c, st);
     if (int rc = poly_ws(c, n_polys, t)) return rc;
@@ -751,8 +760,8 @@ int poly_check_dev(blsgpu_ctx* c, const void* d_commit, size_t n_polys, size_t t
     HIP_TRY(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (bad) return fail(-EINVAL, "polynomial index out of range");
-    if (int rc = poly_prep(c, d_commit, n_polys, t, d_status != nullptr, st)) return rc;
-    return poly_eval_launch(c, n_polys, t, d_poly, d_x, d_s, n, d_status, d_out_aff, st);
+    if (int rc = poly_prep(c, d_commit, n_polys, t, d_status != nullptr, st, secret)) return rc;
+    return poly_eval_launch(c, n_polys, t, d_poly, d_x, d_s, n, d_status, d_out_aff, st, secret);
 }
 // ------------------------------------------------------------ subgroup membership (blsgpu_subgroup.hip) --
 // n affine points of G1 (g = 1, 96 B each) or G2 (g = 2, 192 B each) -> n status bytes, FIX_SLICE per launch
@@ -843,6 +852,35 @@ int fr_interpolate_secret_dev(blsgpu_ctx* c, const void* d_x, const void* d_y, s
                        c->at<uint8_t>(B_LAGR_WS), (const uint8_t*)d_y, (uint32_t)k, (uint32_t)groups, sh.gpb, (uint8_t*)d_out);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+// the argument checks of blsgpu_fr_sum_secret* (before anything is written); 1: nothing to do
+int fr_sum_args(const blsgpu_ctx* c, const void* y, size_t k, size_t groups, const void* out) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (k == 0) return fail(-EINVAL, "k must be at least 1");
+    if (groups == 0) return 1;
+    if (!y || !out) return fail(-EINVAL, "NULL argument");
+    if (groups > 0x7FFFFFFFull || k > (~(size_t)0 >> 6) / groups) return fail(-EINVAL, "batch too large");
+    return 0;
+}
+// out[g] = sum_j y[g k + j] mod n (k_fr_sum_secret, timing kind 10), then the public key of every sum from k_fix_mul_secret
+// reading `d_out` where it lies, all on the device
+int fr_sum_secret_dev(blsgpu_ctx* c, const void* d_y, size_t k, size_t groups, void* d_out, void* d_out_pk_aff, void* d_out_pk_ser,
+                      hipStream_t st) {
+    using namespace blsgpu::frsec;
+    StreamGuard sg(c, st);
+    const bool pk = d_out_pk_aff || d_out_pk_ser;
+    if (pk) {
+        if (int rc = fix_table(c, st, true)) return rc;
+    }
+    const uint32_t per = k <= SUM_THREADS ? (uint32_t)k : SUM_THREADS, gpb = SUM_THREADS / per;
+    {
+        KernelTimer kt(c, st, 10);
+        hipLaunchKernelGGL(k_fr_sum_secret, dim3((unsigned)((groups + gpb - 1) / gpb)), dim3(SUM_THREADS), 0, st, (const uint8_t*)d_y, k,
+                           (uint32_t)groups, gpb, per, (uint8_t*)d_out);
+        HIP_TRY(hipGetLastError());
+    }
+    return pk ? fix_mul_secret_launch(c, d_out, groups, d_out_pk_aff, d_out_pk_ser, st) : 0;
 }
 
 // the argument checks of blsgpu_threshold_deal_secret* (before anything is written); 1: nothing to do
@@ -2268,11 +2306,12 @@ BLSGPU_EXPORT int blsgpu_hd_paths_secret_dev(blsgpu_ctx* c, const void* d_parent
 }
 
 // ------------------------------------------------------------ Feldman share checks --
-BLSGPU_EXPORT int blsgpu_g1_poly_check(blsgpu_ctx* c, const uint8_t* commit, size_t n_polys, size_t t, const uint32_t* poly, const uint8_t* x,
-                                       const uint8_t* s, size_t n, uint8_t* status, uint8_t* out_aff) {
+static int poly_check_host(blsgpu_ctx* c, const uint8_t* commit, size_t n_polys, size_t t, const uint32_t* poly, const uint8_t* x,
+                           const uint8_t* s, size_t n, uint8_t* status, uint8_t* out_aff, bool secret) {
     if (!c) return fail(-EINVAL, "ctx is NULL");
     if (t == 0) return fail(-EINVAL, "t must be at least 1");
     if (n == 0) return 0;
+    if (secret && (!s || !status)) return fail(-EINVAL, "s and status are required");
     if (int rc = poly_args(n_polys, t, commit, poly, x, s, status, out_aff)) return rc;
     for (size_t i = 0; i < n; i++)
         if (poly[i] >= n_polys) return fail(-EINVAL, "polynomial index out of range");
@@ -2286,22 +2325,37 @@ BLSGPU_EXPORT int blsgpu_g1_poly_check(blsgpu_ctx* c, const uint8_t* commit, siz
     {
         StreamGuard sg(c, nullptr);
         if (int rc = poly_ws(c, n_polys, t)) return rc;
-        if (int rc = poly_prep(c, st.at(dcommit), n_polys, t, status != nullptr, nullptr)) return rc;
+        if (int rc = poly_prep(c, st.at(dcommit), n_polys, t, status != nullptr, nullptr, secret)) return rc;
     }
     return for_slices(n, S, [&](size_t lo, size_t m) {
         if (int rc = st.up(lo, m)) return rc;
         {
             StreamGuard sg(c, nullptr);
-            if (int rc = poly_eval_launch(c, n_polys, t, st.at(dpoly), st.at(dx), st.opt(ds), m, st.opt(dstatus), st.opt(daff), nullptr)) return rc;
+            if (int rc = poly_eval_launch(c, n_polys, t, st.at(dpoly), st.at(dx), st.opt(ds), m, st.opt(dstatus), st.opt(daff), nullptr, secret))
+                return rc;
         }
         return st.down(lo, m);
     });
+}
+BLSGPU_EXPORT int blsgpu_g1_poly_check(blsgpu_ctx* c, const uint8_t* commit, size_t n_polys, size_t t, const uint32_t* poly, const uint8_t* x,
+                                       const uint8_t* s, size_t n, uint8_t* status, uint8_t* out_aff) {
+    return poly_check_host(c, commit, n_polys, t, poly, x, s, n, status, out_aff, false);
+}
+BLSGPU_EXPORT int blsgpu_g1_poly_check_secret(blsgpu_ctx* c, const uint8_t* commit, size_t n_polys, size_t t, const uint32_t* poly,
+                                              const uint8_t* x, const uint8_t* s, size_t n, uint8_t* status, uint8_t* out_aff) {
+    return poly_check_host(c, commit, n_polys, t, poly, x, s, n, status, out_aff, true);
 }
 BLSGPU_EXPORT int blsgpu_g1_poly_check_dev(blsgpu_ctx* c, const void* d_commit, size_t n_polys, size_t t, const void* d_poly, const void* d_x,
                                            const void* d_s, size_t n, void* d_status, void* d_out_aff, void* stream) {
     if (!c) return fail(-EINVAL, "ctx is NULL");
     HIP_TRY(hipSetDevice(c->device));
     return poly_check_dev(c, d_commit, n_polys, t, d_poly, d_x, d_s, n, d_status, d_out_aff, (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_g1_poly_check_secret_dev(blsgpu_ctx* c, const void* d_commit, size_t n_polys, size_t t, const void* d_poly,
+                                                  const void* d_x, const void* d_s, size_t n, void* d_status, void* d_out_aff, void* stream) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    return poly_check_dev(c, d_commit, n_polys, t, d_poly, d_x, d_s, n, d_status, d_out_aff, (hipStream_t)stream, true);
 }
 
 // ------------------------------------------------------------ subgroup membership --
@@ -2420,6 +2474,29 @@ BLSGPU_EXPORT int blsgpu_fr_interpolate_at_zero_secret(blsgpu_ctx* c, const uint
     if (int rc = s.up()) return rc;
     if (int rc = fr_interpolate_secret_dev(c, s.at(dx), s.at(dy), k, groups, s.at(dout), s.at(dst), nullptr)) return rc;
     return s.down();
+}
+
+BLSGPU_EXPORT int blsgpu_fr_sum_secret_dev(blsgpu_ctx* c, const void* d_y, size_t k, size_t groups, void* d_out, void* d_out_pk_aff,
+                                           void* d_out_pk_ser, void* stream) {
+    if (int rc = fr_sum_args(c, d_y, k, groups, d_out)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return fr_sum_secret_dev(c, d_y, k, groups, d_out, d_out_pk_aff, d_out_pk_ser, (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_fr_sum_secret(blsgpu_ctx* c, const uint8_t* y, size_t k, size_t groups, uint8_t* out, uint8_t* out_pk_aff,
+                                       uint8_t* out_pk_ser) {
+    if (int rc = fr_sum_args(c, y, k, groups, out)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    // whole groups per staged slice: about 64 MB of staging
+    const size_t fit = ((size_t)1 << 26) / (k * 32 + 176);
+    const size_t S = groups < fit ? groups : (fit ? fit : 1);
+    Staging s(c);
+    const int dy = s.in(y, S, k * 32), dout = s.out(out, S, 32), daff = s.out(out_pk_aff, S, 96), dser = s.out(out_pk_ser, S, 48);
+    if (int rc = s.alloc()) return rc;
+    return for_slices(groups, S, [&](size_t lo, size_t m) {
+        if (int rc = s.up(lo, m)) return rc;
+        if (int rc = fr_sum_secret_dev(c, s.at(dy), k, m, s.at(dout), s.opt(daff), s.opt(dser), nullptr)) return rc;
+        return s.down(lo, m);
+    });
 }
 
 // PrivateKey.sign_threshold's device work for `groups` sessions of k signers: the coefficients (k_lagrange) into the

@@ -16,6 +16,11 @@
 //                           additions: out[g] = sum_j L_j y_j mod n for secret y_j.
 //   k_fr_scale_secret       lane i: out_i = L_i (sk_i mod n) mod n, 32 bytes big-endian: the scalar blsgpu_sign_threshold
 //                           hands to k_g2_smul.
+//   k_fr_sum_secret         out[g] = sum_j y[g k + j] mod n for secret y below 2^256 (a player's share: the fragments it was
+//                           dealt, BLS.aggregate_priv_keys): frs::sum_term_masked per term -- a masked reduction and a masked
+//                           addition, no Montgomery form, no product -- in k_fr_dot_secret's lane layout: whole groups share a
+//                           workgroup of 256 lanes while k <= 256; above that a group has a workgroup to itself and lane l adds
+//                           up the terms l, l + 256, ... before the reduction through LDS.  k has no upper limit.
 //   k_g2_spread             (public data) session g's point H(m_g) copied to the k slots of its signers.
 // Every store is a plain C++ store.
 #pragma once
@@ -25,6 +30,7 @@ namespace blsgpu {
 namespace frsec {
 
 constexpr uint32_t EVAL_THREADS = 256;                                       // points per workgroup of k_fr_poly_eval_secret
+constexpr uint32_t SUM_THREADS = 256;                                        // lanes per workgroup of k_fr_sum_secret
 
 // secrets: coeffs (every line that touches C, v or acc below).  Public: t, n_x, bpp, x.
 __global__ void __launch_bounds__(256) k_fr_poly_eval_secret(const uint8_t* __restrict__ coeffs, uint32_t t, const uint8_t* __restrict__ x,
@@ -72,6 +78,33 @@ __global__ void __launch_bounds__(1024) k_fr_dot_secret(const uint8_t* __restric
         uint32_t acc[8];
         frs::set_zero(acc);
         for (uint32_t i = 0; i < k; i++) frs::add_masked(acc, acc, T + ((size_t)t * k + i) * 8);
+        frs::to_be(acc, out + gs * 32);
+    }
+}
+#else
+;
+#endif
+
+// secrets: y (v, T, acc).  Public: k, groups, gpb, per (the lanes a group has: min(k, 256)).
+__global__ void __launch_bounds__(256) k_fr_sum_secret(const uint8_t* __restrict__ y, size_t k, uint32_t groups, uint32_t gpb, uint32_t per,
+                                                       uint8_t* __restrict__ out)
+#if BLSGPU_EMIT(BLSGPU_TU_FIX)
+{
+    __shared__ __align__(16) uint32_t T[SUM_THREADS * 8];                    // one partial sum per lane
+    const uint32_t items = gpb * per, t = threadIdx.x;
+    const uint32_t gl = t / per, j = t - gl * per;
+    const size_t g = (size_t)blockIdx.x * gpb + gl;
+    uint32_t v[8];
+    frs::set_zero(v);
+    if (t < items && g < groups)
+        for (size_t i = j; i < k; i += per) frs::sum_term_masked(y + (g * k + i) * 32, v);
+    frs::copy(T + (size_t)t * 8, v);
+    __syncthreads();
+    const size_t gs = (size_t)blockIdx.x * gpb + t;
+    if (t < gpb && gs < groups) {
+        uint32_t acc[8];
+        frs::set_zero(acc);
+        for (uint32_t i = 0; i < per; i++) frs::add_masked(acc, acc, T + ((size_t)t * per + i) * 8);
         frs::to_be(acc, out + gs * 32);
     }
 }

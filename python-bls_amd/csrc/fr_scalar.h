@@ -9,7 +9,7 @@
 // reduction step is just -t[0].  Nothing here is generated.  The inversion is Fermat's x^(n-2) by square-and-multiply over
 // the public bits of n - 2; inv(0) = 0.
 // Not constant-time where it matters to a caller: is_zero and the status decisions branch on values.  The forms for secret
-// operands -- mul_masked, add_masked, dot_term_masked and the polynomial evaluation on them -- are at the end of the file.
+// operands -- mul_masked, add_masked, dot_term_masked, the sums and the polynomial evaluation on them -- are at the end of the file.
 //
 // The Lagrange step, exactly the reference's second barycentric form:
 //     w_j = prod_{i != j} (x_j - x_i),  shift_j = w_j^-1 (-x_j)^-1,  den = (sum_j shift_j)^-1,  L_j = shift_j den.
@@ -267,6 +267,23 @@ HD_FN void dot_term_masked(const uint8_t* l_be, const uint8_t* y_be, uint32_t t[
     hdk::reduce_n_masked(y);
     to_mont(l, l);                                         // L is public
     mul_masked(t, l, y);
+}
+
+// ---- a player's share: the sum of the fragments it was dealt, sum_j y_j mod n for SECRET y_j below 2^256 ------------------
+// acc = acc + (y mod n) for a canonical acc: one masked reduction, one masked addition (no Montgomery form, no product)
+HD_FN void sum_term_masked(const uint8_t* y_be, uint32_t acc[8]) {
+    uint32_t y[8];
+    from_be(y_be, y);
+    hdk::reduce_n_masked(y);
+    add_masked(acc, acc, y);
+}
+// One group of k values (32 bytes big-endian each), serially (the host test's view of what k_fr_sum_secret spreads over
+// lanes): out = the canonical sum, 32 bytes big-endian.
+HD_FN void sum_group_masked(const uint8_t* y, size_t k, uint8_t* out) {
+    uint32_t acc[8];
+    set_zero(acc);
+    for (size_t j = 0; j < k; j++) sum_term_masked(y + 32 * j, acc);
+    to_be(acc, out);
 }
 
 // ---- a dealing's fragments: P(x) = sum_k c_k x^k mod n for SECRET coefficients and PUBLIC points ---------------------------
