@@ -563,6 +563,64 @@ int blsgpu_sign_threshold_dev(blsgpu_ctx *ctx, const void *d_sks, const void *d_
                               const void *d_msg_hashes, size_t n_msg, void *d_out_aff, void *d_out_ser, void *d_out_inf,
                               void *d_status, void *stream);
 
+/* Secure aggregation (util.hash_pks, util.py:36-50 of the reference; BLS.aggregate_sigs_secure, bls.py:28-56;
+ * BLS.aggregate_pub_keys and BLS.aggregate_priv_keys, bls.py:203-249) for `groups` independent groups at once, the exponents
+ *     t_gi = SHA256(be32(i) || SHA256(ser(pk_g0) || ... || ser(pk_g,k-1))) mod n
+ * computed on the device (csrc/blsgpu_hashpks.hip on csrc/hash_pks.h) and handed to the sums without a host round trip.
+ * pks_ser: groups x k x 48 bytes, PublicKey.serialize() of every key IN THE ORDER TO BE HASHED (the reference sorts the keys
+ * before it hashes them in aggregate_pub_keys and does not in aggregate_sigs_secure / aggregate_priv_keys: the order is the
+ * caller's), 16-byte aligned; one k per call.  pk_hash_in (may be NULL): groups x 32 bytes, the inner SHA-256 of every group
+ * computed by the caller; then k_hash_pks_digest is not launched and pks_ser is not read (it may be NULL).  One group per lane
+ * is 0.75 k compressions in sequence: below 64 groups the kernel cannot fill one wavefront, and a single group of 2^20 keys
+ * is 786 433 sequential compressions -- there the host's SHA-256 is the right tool and the caller passes its digest.
+ * k_hash_pks_exp then writes one exponent per lane, 32 bytes big-endian, below n.  All of this is PUBLIC data.
+ * Common to the entries below: -EINVAL before anything is written for k == 0 or m == 0 (also with groups == 0), a NULL
+ * context, a NULL required buffer with groups > 0 (pks_ser and pk_hash_in both NULL included); groups == 0 writes nothing and
+ * returns 0.  The _dev forms take every buffer in device memory (4-byte aligned, pks_ser 16) and enqueue on `stream` without
+ * synchronising.
+ *
+ * blsgpu_hash_pks (util.py:36-50): out_ts[(g * m + i) * 32 ..] = t_gi for i < m -- m, the reference's num_outputs, is
+ * independent of k.  out_pk_hash (may be NULL): groups x 32 bytes, the inner digests (computed or copied from pk_hash_in). */
+int blsgpu_hash_pks(blsgpu_ctx *ctx, const uint8_t *pks_ser, size_t k, size_t groups, const uint8_t *pk_hash_in, size_t m,
+                    uint8_t *out_ts, uint8_t *out_pk_hash);
+int blsgpu_hash_pks_dev(blsgpu_ctx *ctx, const void *d_pks_ser, size_t k, size_t groups, const void *d_pk_hash_in, size_t m,
+                        void *d_out_ts, void *d_out_pk_hash, void *stream);
+/* BLS.aggregate_pub_keys(keys, secure=True) (bls.py:203-223): out[g] = sum_i t_gi P_gi.  pts_aff: groups x k x 96 bytes, the
+ * affine points of the same keys in the same order as pks_ser (the caller has both: sorting needs the serialisations; taking
+ * both means no decompression step and no new failure mode).  The exponents (m = k) go to the context's workspace, then the
+ * sums are those of blsgpu_g1_msm_dev over the same groups x k layout: out_aff (groups x 96, (0,0) for infinity) and out_inf
+ * (groups flags, may be NULL) as there.  The order is the caller's: the reference sorts the keys first. */
+int blsgpu_aggregate_pub_keys_secure(blsgpu_ctx *ctx, const uint8_t *pts_aff, const uint8_t *pks_ser, const uint8_t *pk_hash_in,
+                                     size_t k, size_t groups, uint8_t *out_aff, uint8_t *out_inf);
+int blsgpu_aggregate_pub_keys_secure_dev(blsgpu_ctx *ctx, const void *d_pts_aff, const void *d_pks_ser, const void *d_pk_hash_in,
+                                         size_t k, size_t groups, void *d_out_aff, void *d_out_inf, void *stream);
+/* BLS.aggregate_sigs_secure (bls.py:28-56; the colliding part of BLS.aggregate_sigs, bls.py:58-151): out[g] = sum_{i<k}
+ * t_gi S_gi for k signatures per group (sigs_aff: groups x k x 192 bytes affine, in the order the exponents multiply them:
+ * the reference sorts them by (message hash, key, signature)) with the m = k exponents hashed over k_pks keys per group --
+ * BLS.aggregate_sigs hashes a different number of keys than it has signatures.  Then blsgpu_g2_msm_dev: out_aff
+ * (groups x 192), out_inf (may be NULL). */
+int blsgpu_aggregate_sigs_secure(blsgpu_ctx *ctx, const uint8_t *sigs_aff, size_t k, const uint8_t *pks_ser, size_t k_pks,
+                                 const uint8_t *pk_hash_in, size_t groups, uint8_t *out_aff, uint8_t *out_inf);
+int blsgpu_aggregate_sigs_secure_dev(blsgpu_ctx *ctx, const void *d_sigs_aff, size_t k, const void *d_pks_ser, size_t k_pks,
+                                     const void *d_pk_hash_in, size_t groups, void *d_out_aff, void *d_out_inf, void *stream);
+/* BLS.aggregate_priv_keys(keys, public_keys, secure=True) (bls.py:225-249): out[g] = sum_i t_gi sks[g * k + i] mod n, the
+ * canonical integer below n, 32 bytes big-endian.  sks: groups x k x 32 bytes big-endian, any value below 2^256;
+ * sks[g * k + i] is the key that t_gi multiplies, pks_ser is in the order to be hashed -- in the reference these two orders
+ * DIFFER (the pairs are sorted by public key, bls.py:239-240, the exponents hashed over the keys as given, bls.py:241), so no
+ * permutation between them is assumed.  The exponents go to the workspace; k_fr_dot_secret takes them as its public
+ * coefficients and the keys as its secret y (masked reduction, product and additions); out_pk_aff (groups x 96) and
+ * out_pk_ser (groups x 48) may each be NULL: the public key of every sum from k_fix_mul_secret reading the sums where they
+ * were left, as in blsgpu_fr_sum_secret.  1 <= k <= BLSGPU_LAGRANGE_MAX_K as in blsgpu_fr_interpolate_at_zero_secret (a group
+ * is one workgroup of k_fr_dot_secret); beyond it -EINVAL with a blsgpu_last_error text.
+ * The claim is the one stated above for the calls on secrets: the sequence of instructions and of memory addresses does not
+ * depend on sks.  It does depend on k, groups and the public keys.  Timing inside the hardware is not claimed.  The two hash
+ * kernels touch no secret. */
+int blsgpu_aggregate_priv_keys_secure(blsgpu_ctx *ctx, const uint8_t *sks, const uint8_t *pks_ser, const uint8_t *pk_hash_in,
+                                      size_t k, size_t groups, uint8_t *out, uint8_t *out_pk_aff, uint8_t *out_pk_ser);
+int blsgpu_aggregate_priv_keys_secure_dev(blsgpu_ctx *ctx, const void *d_sks, const void *d_pks_ser, const void *d_pk_hash_in,
+                                          size_t k, size_t groups, void *d_out, void *d_out_pk_aff, void *d_out_pk_ser,
+                                          void *stream);
+
 /* Measurement aid (bench.py): when enabled, HIP events are recorded on the
  * launch stream around every kernel this context launches (up to 1024 launches
  * between reads).  blsgpu_timing_read waits for them and returns, per launch,
@@ -575,7 +633,10 @@ int blsgpu_sign_threshold_dev(blsgpu_ctx *ctx, const void *d_sks, const void *d_
  * blsgpu_g1_poly_check_secret_dev call / per staged slice of the host form),
  * 10 = the scalar kernels on secrets: k_fr_poly_eval_secret, k_fr_dot_secret, k_fr_scale_secret, k_fr_sum_secret (one record
  * per call of blsgpu_threshold_deal_secret_dev with fragments, blsgpu_fr_interpolate_at_zero_secret_dev,
- * blsgpu_sign_threshold_dev, blsgpu_fr_sum_secret_dev; the G1 / G2 halves of those calls keep their kinds 9 and 8).
+ * blsgpu_sign_threshold_dev, blsgpu_fr_sum_secret_dev, blsgpu_aggregate_priv_keys_secure_dev; the G1 / G2 halves of those
+ * calls keep their kinds 9 and 8),
+ * 11 = k_hash_pks_digest and 12 = k_hash_pks_exp (one record each per blsgpu_hash_pks_dev / blsgpu_aggregate_*_secure_dev
+ * call; no record of kind 11 when the caller hands in the digests).
  * Reading resets the ring. */
 int blsgpu_timing_enable(blsgpu_ctx *ctx, int enable);
 int blsgpu_timing_read(blsgpu_ctx *ctx, float *ms, int *kind, size_t cap, size_t *count);

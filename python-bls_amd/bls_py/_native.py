@@ -38,10 +38,15 @@ SYMBOLS = (
     "blsgpu_fr_interpolate_at_zero_secret", "blsgpu_fr_interpolate_at_zero_secret_dev",
     "blsgpu_sign_threshold", "blsgpu_sign_threshold_dev",
     "blsgpu_g1_poly_check_secret", "blsgpu_g1_poly_check_secret_dev", "blsgpu_fr_sum_secret", "blsgpu_fr_sum_secret_dev",
+    "blsgpu_hash_pks", "blsgpu_hash_pks_dev", "blsgpu_aggregate_pub_keys_secure", "blsgpu_aggregate_pub_keys_secure_dev",
+    "blsgpu_aggregate_sigs_secure", "blsgpu_aggregate_sigs_secure_dev",
+    "blsgpu_aggregate_priv_keys_secure", "blsgpu_aggregate_priv_keys_secure_dev",
 )
 
 HD_PARENT_BYTES = 160          # BLSGPU_HD_PARENT_BYTES: chain code (32), public key affine (96), private key (32)
 LAGRANGE_MAX_K = 1024          # BLSGPU_LAGRANGE_MAX_K of include/blsgpu.h: players per group the device takes
+HASH_PKS_DEVICE_GROUPS = 64    # groups per call from which the device hashes the keys itself: below, one group per lane cannot
+                               # fill a wavefront and the host's digest is handed in (pk_hash_in of include/blsgpu.h)
 
 _lib = None
 _lock = threading.Lock()
@@ -156,6 +161,14 @@ def load_library(path=None):
         L.blsgpu_g1_poly_check_secret_dev.argtypes = [vp, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp]
         L.blsgpu_fr_sum_secret.argtypes = [vp, cp, sz, sz, vp, vp, vp]
         L.blsgpu_fr_sum_secret_dev.argtypes = [vp, vp, sz, sz, vp, vp, vp, vp]
+        L.blsgpu_hash_pks.argtypes = [vp, cp, sz, sz, cp, sz, vp, vp]
+        L.blsgpu_hash_pks_dev.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, vp]
+        L.blsgpu_aggregate_pub_keys_secure.argtypes = [vp, cp, cp, cp, sz, sz, vp, vp]
+        L.blsgpu_aggregate_pub_keys_secure_dev.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp]
+        L.blsgpu_aggregate_sigs_secure.argtypes = [vp, cp, sz, cp, sz, cp, sz, vp, vp]
+        L.blsgpu_aggregate_sigs_secure_dev.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, vp, vp]
+        L.blsgpu_aggregate_priv_keys_secure.argtypes = [vp, cp, cp, cp, sz, sz, vp, vp, vp]
+        L.blsgpu_aggregate_priv_keys_secure_dev.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp, vp]
         L.blsgpu_timing_enable.argtypes = [vp, ctypes.c_int]
         L.blsgpu_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int), sz,
                                          ctypes.POINTER(sz)]
@@ -728,12 +741,98 @@ class Engine:
         self._check(self.lib.blsgpu_sign_threshold_dev(self.h, d_sks, d_x, k, groups, d_msg_hashes, n_msg, d_out_aff, d_out_ser, d_out_inf,
                                                        d_status, stream), "blsgpu_sign_threshold_dev")
 
+    # ---- secure aggregation: the hash_pks exponents on the device and the three sums behind them ----
+    @staticmethod
+    def _pk_hashes(pks_ser, k, groups, pk_hash):
+        """the pk_hash_in of a call: the caller's digests, the host's for fewer than HASH_PKS_DEVICE_GROUPS groups (one group
+        per lane cannot fill a wavefront; hashlib runs at memory speed), or None: the device hashes the keys.
+        pk_hash: bytes, None (that rule) or False (the device, whatever the count)"""
+        if len(pks_ser) != 48 * k * groups:
+            raise ValueError("need groups x k serialised keys of 48 bytes")
+        if pk_hash is False or (pk_hash is None and groups >= HASH_PKS_DEVICE_GROUPS):
+            return None
+        if pk_hash is None:
+            import hashlib
+            mv = memoryview(pks_ser)
+            return b"".join(hashlib.sha256(mv[48 * k * g:48 * k * (g + 1)]).digest() for g in range(groups))
+        if len(pk_hash) != 32 * groups:
+            raise ValueError("need one digest of 32 bytes per group")
+        return bytes(pk_hash)
+
+    def hash_pks(self, pks_ser, k, m, groups=1, pk_hash=None, want_pk_hash=False):
+        """util.hash_pks(m, keys) of `groups` groups of k serialised keys (blsgpu_hash_pks): groups x m exponents below n,
+        32 bytes big-endian each.  pk_hash: see _pk_hashes.  -> exponent bytes (, groups x 32 digest bytes)"""
+        pks_ser = bytes(pks_ser)
+        ph = self._pk_hashes(pks_ser, k, groups, pk_hash)
+        out = ctypes.create_string_buffer(max(1, 32 * m * groups))
+        dg = ctypes.create_string_buffer(max(1, 32 * groups)) if want_pk_hash else None
+        self._check(self.lib.blsgpu_hash_pks(self.h, None if ph else pks_ser, k, groups, ph, m, out, dg), "blsgpu_hash_pks")
+        return (out.raw[:32 * m * groups], dg.raw[:32 * groups]) if want_pk_hash else out.raw[:32 * m * groups]
+
+    def aggregate_pub_keys_secure(self, pts_aff, pks_ser, k, groups=1, pk_hash=None):
+        """sum_i t_i P_i per group (blsgpu_aggregate_pub_keys_secure): pts_aff groups x k x 96 affine bytes, pks_ser the same
+        keys serialised, both in the order to be hashed.  -> (groups x 96 affine bytes, [is_infinity])"""
+        pks_ser = bytes(pks_ser)
+        if len(pts_aff) != 96 * k * groups:
+            raise ValueError("point buffer length does not match k * groups")
+        ph = self._pk_hashes(pks_ser, k, groups, pk_hash)
+        out = ctypes.create_string_buffer(max(1, 96 * groups))
+        inf = ctypes.create_string_buffer(max(1, groups))
+        self._check(self.lib.blsgpu_aggregate_pub_keys_secure(self.h, bytes(pts_aff), None if ph else pks_ser, ph, k, groups, out, inf),
+                    "blsgpu_aggregate_pub_keys_secure")
+        return out.raw[:96 * groups], [bool(b) for b in inf.raw[:groups]]
+
+    def aggregate_sigs_secure(self, sigs_aff, k, pks_ser, k_pks, groups=1, pk_hash=None):
+        """sum_i t_i S_i per group (blsgpu_aggregate_sigs_secure): sigs_aff groups x k x 192 affine bytes in the order the
+        exponents multiply them, the k exponents hashed over k_pks serialised keys per group.
+        -> (groups x 192 affine bytes, [is_infinity])"""
+        pks_ser = bytes(pks_ser)
+        if len(sigs_aff) != 192 * k * groups:
+            raise ValueError("signature buffer length does not match k * groups")
+        ph = self._pk_hashes(pks_ser, k_pks, groups, pk_hash)
+        out = ctypes.create_string_buffer(max(1, 192 * groups))
+        inf = ctypes.create_string_buffer(max(1, groups))
+        self._check(self.lib.blsgpu_aggregate_sigs_secure(self.h, bytes(sigs_aff), k, None if ph else pks_ser, k_pks, ph, groups, out, inf),
+                    "blsgpu_aggregate_sigs_secure")
+        return out.raw[:192 * groups], [bool(b) for b in inf.raw[:groups]]
+
+    def aggregate_priv_keys_secure(self, sks, pks_ser, k, groups=1, pk=False, aff=False, ser=False, pk_hash=None):
+        """sum_i t_i sk_i mod n per group for SECRET keys (blsgpu_aggregate_priv_keys_secure): sks groups x k x 32 bytes
+        big-endian (or ints below 2^256) in the order the exponents multiply them, pks_ser in the order to be hashed,
+        1 <= k <= LAGRANGE_MAX_K.  pk: both forms of the public key of every sum (aff / ser: one of them).
+        -> (groups x 32 bytes, groups x 96 affine bytes or None, groups x 48 serialised bytes or None)"""
+        pks_ser = bytes(pks_ser)
+        ph = self._pk_hashes(pks_ser, k, groups, pk_hash)
+        aff, ser = aff or pk, ser or pk
+        out = ctypes.create_string_buffer(max(1, 32 * groups))
+        oa = ctypes.create_string_buffer(max(1, 96 * groups)) if aff else None
+        os_ = ctypes.create_string_buffer(max(1, 48 * groups)) if ser else None
+        self._check(self.lib.blsgpu_aggregate_priv_keys_secure(self.h, self._scalars(sks, k * groups, "sks"), None if ph else pks_ser, ph, k,
+                                                               groups, out, oa, os_), "blsgpu_aggregate_priv_keys_secure")
+        return out.raw[:32 * groups], (oa.raw[:96 * groups] if aff else None), (os_.raw[:48 * groups] if ser else None)
+
+    def hash_pks_dev(self, d_pks_ser, k, groups, d_pk_hash_in, m, d_out_ts, d_out_pk_hash=None, stream=0):
+        self._check(self.lib.blsgpu_hash_pks_dev(self.h, d_pks_ser, k, groups, d_pk_hash_in, m, d_out_ts, d_out_pk_hash, stream),
+                    "blsgpu_hash_pks_dev")
+
+    def aggregate_pub_keys_secure_dev(self, d_pts_aff, d_pks_ser, d_pk_hash_in, k, groups, d_out_aff, d_out_inf=None, stream=0):
+        self._check(self.lib.blsgpu_aggregate_pub_keys_secure_dev(self.h, d_pts_aff, d_pks_ser, d_pk_hash_in, k, groups, d_out_aff, d_out_inf,
+                                                                  stream), "blsgpu_aggregate_pub_keys_secure_dev")
+
+    def aggregate_sigs_secure_dev(self, d_sigs_aff, k, d_pks_ser, k_pks, d_pk_hash_in, groups, d_out_aff, d_out_inf=None, stream=0):
+        self._check(self.lib.blsgpu_aggregate_sigs_secure_dev(self.h, d_sigs_aff, k, d_pks_ser, k_pks, d_pk_hash_in, groups, d_out_aff,
+                                                              d_out_inf, stream), "blsgpu_aggregate_sigs_secure_dev")
+
+    def aggregate_priv_keys_secure_dev(self, d_sks, d_pks_ser, d_pk_hash_in, k, groups, d_out, d_out_pk_aff=None, d_out_pk_ser=None, stream=0):
+        self._check(self.lib.blsgpu_aggregate_priv_keys_secure_dev(self.h, d_sks, d_pks_ser, d_pk_hash_in, k, groups, d_out, d_out_pk_aff,
+                                                                   d_out_pk_ser, stream), "blsgpu_aggregate_priv_keys_secure_dev")
+
     def timing_enable(self, on=True):
         self._check(self.lib.blsgpu_timing_enable(self.h, int(on)), "blsgpu_timing_enable")
 
     def timing_read(self):
         """[(kind, ms)] for every kernel launched since the last read; kinds:
-        0 k_miller, 1 k_reduce, 2 k_reduce + final exponentiation, 3 k_miller_slow."""
+        0 k_miller, 1 k_reduce, 2 k_reduce + final exponentiation, 3 k_miller_slow (the rest: include/blsgpu.h)."""
         cap = 1024
         ms = (ctypes.c_float * cap)()
         kind = (ctypes.c_int * cap)()

@@ -132,6 +132,25 @@ class HipProvider:
         """(lambda_j sk_j mod n) H(h) per signer: -> (affine bytes, serialised bytes, [is_infinity], groups status bytes)"""
         return self._eng.sign_threshold(sks, x, k, msg_hashes, groups, aff, ser)
 
+    # ---- secure aggregation (util.py:36-50, bls.py:28-56 and 203-249): the hash_pks exponents never visit the host ----
+    def hash_pks(self, pks_ser: bytes, k: int, m: int, groups: int = 1):
+        """-> groups x m x 32 bytes: t_i = sha256(be32(i) || sha256(the group's k serialised keys)) mod n"""
+        return self._eng.hash_pks(pks_ser, k, m, groups)
+
+    def aggregate_pub_keys_secure(self, pts_aff: bytes, pks_ser: bytes, k: int, groups: int = 1):
+        """-> (groups x 96 affine bytes: sum_i t_i P_i, [is_infinity]); both buffers in the order to be hashed"""
+        return self._eng.aggregate_pub_keys_secure(pts_aff, pks_ser, k, groups)
+
+    def aggregate_sigs_secure(self, sigs_aff: bytes, k: int, pks_ser: bytes, k_pks: int, groups: int = 1):
+        """-> (groups x 192 affine bytes: sum_i t_i S_i, [is_infinity]); k exponents hashed over k_pks keys per group"""
+        return self._eng.aggregate_sigs_secure(sigs_aff, k, pks_ser, k_pks, groups)
+
+    def aggregate_priv_keys_secure(self, sks, pks_ser: bytes, k: int, groups: int = 1, pk: bool = False):
+        """-> (groups x 32 bytes: sum_i t_i sk_i mod n on the masked sums, and with pk the public key of every sum: groups x 96
+        affine bytes, groups x 48 serialised bytes -- else None, None); sks in the order the exponents multiply them, pks_ser in
+        the order to be hashed"""
+        return self._eng.aggregate_priv_keys_secure(sks, pks_ser, k, groups, pk)
+
     # ---- the whole of BLS.verify's device work without a host round trip between its steps (bls.py:153-201) ----
     def verify_pipeline(self, neg_g1: bytes, sig: bytes, hashes: bytes, n: int, keys_affine=None, key_pts=None, key_scalars=None, k=0) -> bytes:
         """e(-G1, sig) * prod_i e(P_i, H(m_i)) for n message hashes (32 bytes each): blsgpu_verify_pipeline -- ONE upload,
@@ -158,7 +177,12 @@ def use(provider):
     threshold_deal_secret(coeffs, t, x) -> (commitment bytes, fragment bytes), fr_interpolate_at_zero_secret(x, y, k, groups) ->
     as fr_interpolate_at_zero, sign_threshold(sks, x, k, msg_hashes, groups) -> (affine bytes, serialised bytes, [is_inf], status bytes),
     g1_poly_check_secret(commit, n_polys, t, poly, x, s, aff) -> as g1_poly_check, fr_sum_secret(y, k, groups, pk) ->
-    (32 bytes per group, affine bytes|None, serialised bytes|None).
+    (32 bytes per group, affine bytes|None, serialised bytes|None), aggregate_priv_keys_secure(sks, pks_ser, k, groups, pk) ->
+    likewise.
+    Optional (a provider without them sends util.hash_pks_batch, BLS.aggregate_pub_keys_batch and
+    BLS.aggregate_sigs_secure_batch to the per-call loop): hash_pks(pks_ser, k, m, groups) -> exponent bytes,
+    aggregate_pub_keys_secure(pts_aff, pks_ser, k, groups) -> (affine bytes, [is_inf]),
+    aggregate_sigs_secure(sigs_aff, k, pks_ser, k_pks, groups) -> (affine bytes, [is_inf]).
     Optional (a provider without them sends the Threshold.*_batch methods to the host loop): LAGRANGE_MAX_K,
     lagrange_at_zero(x, k, groups) -> (coefficient bytes, status bytes), fr_interpolate_at_zero(x, y, k, groups) ->
     (32 bytes per group, status bytes), threshold_combine(sigs, x, k, groups) -> (affine bytes, [is_inf], status bytes)."""

@@ -340,14 +340,83 @@ class BLS:
         return PrivateKey.from_bytes(total.to_bytes(32, "big"))
 
     @staticmethod
-    def aggregate_priv_keys_batch(groups, secret=False, public_keys=False):
+    def aggregate_pub_keys_batch(groups, secure):
+        """[BLS.aggregate_pub_keys(list(g), secure) for g in groups] without sorting the caller's lists: one device call per
+        distinct group length.  secure=True: blsgpu_aggregate_pub_keys_secure -- the hash_pks exponents of every group
+        (both SHA-256 steps and the reduction mod n) and the G1 sums behind them in one call, the exponents never on the
+        host; a provider without the entry runs the loop above.  secure=False: one grouped plain sum (g1_msm)."""
+        groups = [sorted(g) for g in groups]                 # copies: the reference sorts in place (bls.py:210)
+        if any(not g for g in groups):
+            raise Exception("Invalid number of keys")
+        prov = backend.get()
+        fn = getattr(prov, "aggregate_pub_keys_secure", None) if secure else prov.g1_msm
+        if fn is None:
+            return [BLS.aggregate_pub_keys(g, secure) for g in groups]
+        buckets = {}
+        for j, g in enumerate(groups):
+            buckets.setdefault(len(g), []).append(j)
+        out = [None] * len(groups)
+        for k, js in buckets.items():
+            pts = b"".join(_jac_g1_bytes(pk.value) for j in js for pk in groups[j])
+            if secure:
+                res, inf = fn(pts, b"".join(pk.serialize() for j in js for pk in groups[j]), k, len(js))
+            else:
+                res, inf = fn(pts, None, k, len(js))
+            for q, j in enumerate(js):
+                out[j] = PublicKey.from_g1(JacobianPoint._from(H.F1, None if inf[q] else H.aff_to_jac(H.F1, H.g1_from_abi(res[96 * q:96 * (q + 1)]))))
+        return out
+
+    @staticmethod
+    def aggregate_sigs_secure_batch(sig_groups, pk_groups, mh_groups):
+        """[BLS.aggregate_sigs_secure(s, p, m) for s, p, m in zip(sig_groups, pk_groups, mh_groups)]: one
+        blsgpu_aggregate_sigs_secure call per distinct group length.  As in bls.py:39-45 the signatures are ordered by
+        (message hash, public key, signature) and the exponents hashed over the public keys in the CALLER's order.  A
+        provider without the entry runs that loop."""
+        trip = [(list(s), list(p), list(m)) for s, p, m in zip(sig_groups, pk_groups, mh_groups)]
+        for s, p, m in trip:
+            if not (len(s) == len(p) == len(m)):
+                raise Exception("Invalid number of keys")
+        fn = getattr(backend.get(), "aggregate_sigs_secure", None)
+        if fn is None:
+            return [BLS.aggregate_sigs_secure(s, p, m) for s, p, m in trip]
+        buckets = {}
+        for j, (s, _, _) in enumerate(trip):
+            buckets.setdefault(len(s), []).append(j)
+        out = [None] * len(trip)
+        for k, js in buckets.items():
+            if k == 0:                                       # an empty sum: infinity, no exponents
+                for j in js:
+                    out[j] = Signature.from_g2(JacobianPoint._from(H.F2, None))
+                continue
+            sigs, sers = bytearray(), bytearray()
+            for j in js:
+                s, p, m = trip[j]
+                for _, _, sig in sorted(zip(m, p, s)):
+                    sigs += H.g2_affine_bytes(sig.value.to_affine()._aff())
+                for pk in p:
+                    sers += pk.serialize()
+            res, inf = fn(bytes(sigs), k, bytes(sers), k, len(js))
+            for q, j in enumerate(js):
+                out[j] = Signature.from_g2(JacobianPoint._from(H.F2, None if inf[q] else H.aff_to_jac(H.F2, H.g2_from_abi(res[192 * q:192 * (q + 1)]))))
+        return out
+
+    @staticmethod
+    def aggregate_priv_keys_batch(groups, secret=False, public_keys=False, secure_with=None):
         """[BLS.aggregate_priv_keys(g, None, False) for g in groups] -- step 3 of Joint-Feldman, a player's share as the sum
         of the fragments it was dealt -- and with public_keys=True (keys, [k.get_public_key() for k in keys]).  The
         default is that loop on the host.  secret=True: one blsgpu_fr_sum_secret call per distinct group length, whose
         sequence of instructions and addresses does not depend on the keys; with public_keys=True the same call
         multiplies the sums by G1 on the device (k_fix_mul_secret) before anything returns.  A provider without the
-        entry raises NotImplementedError, an empty group ValueError.  Secure aggregation (hash_pks) has no batch form."""
+        entry raises NotImplementedError, an empty group ValueError.
+        secure_with: a list of public-key lists, one per group -- secure aggregation: the result equals
+        [BLS.aggregate_priv_keys(g, pks, True) for g, pks in zip(groups, secure_with)], the reference's order included
+        (bls.py:239-241: the pairs sorted by public key, the exponents hashed over the public keys as given).  With
+        secret=True that is one blsgpu_aggregate_priv_keys_secure call per distinct group length (at most
+        LAGRANGE_MAX_K keys per group): the hash_pks exponents on the device, the sums on k_fr_dot_secret's masked
+        arithmetic, the public keys from k_fix_mul_secret; a provider without the entry raises NotImplementedError."""
         groups = [list(g) for g in groups]
+        if secure_with is not None:
+            return BLS._aggregate_priv_keys_secure_batch(groups, [list(p) for p in secure_with], secret, public_keys)
         if not secret:
             keys = [BLS.aggregate_priv_keys(g, None, False) for g in groups]
             return (keys, [k.get_public_key() for k in keys]) if public_keys else keys
@@ -362,6 +431,36 @@ class BLS:
         for k, idx in buckets.items():
             yb = b"".join(sk.value.to_bytes(32, "big") for i in idx for sk in groups[i])
             out, aff, ser = fr_sum(yb, k, len(idx), public_keys)
+            for q, i in enumerate(idx):
+                keys[i] = PrivateKey.from_bytes(out[32 * q:32 * (q + 1)])
+                if public_keys:
+                    pks[i] = _pk_from_device(aff[96 * q:96 * (q + 1)], ser[48 * q:48 * (q + 1)])
+                    keys[i].__dict__["_pk_point"] = pks[i].value          # the cache get_public_key fills (same point)
+        return (keys, pks) if public_keys else keys
+
+    @staticmethod
+    def _aggregate_priv_keys_secure_batch(groups, pk_groups, secret, public_keys):
+        if len(groups) != len(pk_groups):
+            raise ValueError("secure_with holds one list of public keys per group")
+        if not secret:
+            keys = [BLS.aggregate_priv_keys(g, p, True) for g, p in zip(groups, pk_groups)]
+            return (keys, [k.get_public_key() for k in keys]) if public_keys else keys
+        from .keys import _pk_from_device, _secret_call
+        agg = _secret_call("aggregate_priv_keys_secure")
+        for g, p in zip(groups, pk_groups):
+            if not p:
+                raise Exception("Must include public keys in secure aggregation")
+            if len(g) != len(p):
+                raise Exception("Invalid number of keys")
+        buckets = {}
+        for i, g in enumerate(groups):
+            buckets.setdefault(len(g), []).append(i)
+        keys, pks = [None] * len(groups), [None] * len(groups)
+        for k, idx in buckets.items():
+            # bls.py:239-241: key i of the SORTED pairs meets exponent i, hashed over the public keys in the caller's order
+            yb = b"".join(sk.value.to_bytes(32, "big") for i in idx for _, sk in sorted(zip(pk_groups[i], groups[i])))
+            sers = b"".join(pk.serialize() for i in idx for pk in pk_groups[i])
+            out, aff, ser = agg(yb, sers, k, len(idx), public_keys)
             for q, i in enumerate(idx):
                 keys[i] = PrivateKey.from_bytes(out[32 * q:32 * (q + 1)])
                 if public_keys:

@@ -30,3 +30,27 @@ def hash_pks(num_outputs, public_keys):
     from .bls12381 import n
     digest = hash256(b"".join(pk.serialize() for pk in public_keys))
     return [int.from_bytes(hash256(i.to_bytes(4, "big") + digest), "big") % n for i in range(num_outputs)]
+
+
+def hash_pks_batch(num_outputs, key_groups):
+    """[hash_pks(num_outputs, g) for g in key_groups] with ONE device call per distinct group length (blsgpu_hash_pks: both
+    SHA-256 steps and the reduction mod n on the GPU) when the provider has hash_pks; otherwise that loop.  Empty groups and
+    num_outputs = 0 never reach the device."""
+    from . import backend
+    key_groups = [list(g) for g in key_groups]
+    fn = getattr(backend.get(), "hash_pks", None) if key_groups and num_outputs > 0 else None
+    if fn is None:
+        return [hash_pks(num_outputs, g) for g in key_groups]
+    out = [None] * len(key_groups)
+    buckets = {}
+    for j, g in enumerate(key_groups):
+        buckets.setdefault(len(g), []).append(j)
+    for k, js in buckets.items():
+        if k == 0:
+            for j in js:
+                out[j] = hash_pks(num_outputs, [])
+            continue
+        ts = fn(b"".join(pk.serialize() for j in js for pk in key_groups[j]), k, num_outputs, len(js))
+        for q, j in enumerate(js):
+            out[j] = [int.from_bytes(ts[32 * (q * num_outputs + i):32 * (q * num_outputs + i + 1)], "big") for i in range(num_outputs)]
+    return out

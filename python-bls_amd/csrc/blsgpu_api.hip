@@ -26,6 +26,7 @@
 #include "blsgpu_subgroup.hip"
 #include "blsgpu_lagrange.hip"
 #include "blsgpu_frsecret.hip"
+#include "blsgpu_hashpks.hip"
 #include "blsgpu_g2smul.hip"
 #include "blsgpu_h2c.hip"
 #include "blsgpu_h2cw.hip"
@@ -881,6 +882,105 @@ int fr_sum_secret_dev(blsgpu_ctx* c, const void* d_y, size_t k, size_t groups, v
         HIP_TRY(hipGetLastError());
     }
     return pk ? fix_mul_secret_launch(c, d_out, groups, d_out_pk_aff, d_out_pk_ser, st) : 0;
+}
+
+// ------------------------------------------------------------ secure aggregation (blsgpu_hashpks.hip) --
+// the argument checks of blsgpu_hash_pks* and blsgpu_aggregate_*_secure* (before anything is written); 1: nothing to do.
+// k: keys hashed per group, m: exponents per group
+int hash_pks_args(const blsgpu_ctx* c, size_t k, size_t m, size_t groups, bool null_buffer) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (k == 0 || m == 0) return fail(-EINVAL, "k and m must be at least 1");
+    if (groups == 0) return 1;
+    if (null_buffer) return fail(-EINVAL, "NULL argument");
+    if (groups > 0x7FFFFFFFull || m > 0xFFFFFFFFull || m * groups > 0xFFFFFFF0ull || k > (~(size_t)0 >> 6) / groups)
+        return fail(-EINVAL, "batch too large");
+    return 0;
+}
+// the workspace of a call: the digests, then the exponents (when they are not the caller's buffers)
+struct HashPksWs { uint32_t* digest; uint32_t* ts; };
+int hash_pks_ws(blsgpu_ctx* c, size_t m, size_t groups, HashPksWs& w) {
+    const size_t dg_bytes = (groups * 32 + 255) & ~(size_t)255;
+    if (int rc = c->grow(B_HPK_WS, dg_bytes + groups * m * 32)) return rc;
+    w.digest = c->at<uint32_t>(B_HPK_WS);
+    w.ts = (uint32_t*)(c->at<char>(B_HPK_WS) + dg_bytes);
+    return 0;
+}
+// enqueues the digests of `groups` groups of k keys (k_hash_pks_digest, timing kind 11; skipped when the caller has them:
+// d_pk_hash_in) and m exponents per group into d_ts (k_hash_pks_exp, kind 12) on `st` (caller: StreamGuard, arguments
+// checked by hash_pks_args).  d_digest_ws: groups x 32 bytes the digests go to when they are computed here.
+int hash_pks_launch(blsgpu_ctx* c, const void* d_pks_ser, size_t k, size_t groups, const void* d_pk_hash_in, size_t m, void* d_ts,
+                    void* d_digest_ws, hipStream_t st) {
+    using namespace blsgpu::hashpks;
+    const void* d_digest = d_pk_hash_in;
+    if (!d_digest) {
+        KernelTimer kt(c, st, 11);
+        hipLaunchKernelGGL(k_hash_pks_digest, dim3((unsigned)((groups + DIGEST_THREADS - 1) / DIGEST_THREADS)), dim3(DIGEST_THREADS), 0, st,
+                           (const uint32_t*)d_pks_ser, k, (uint32_t)groups, (uint32_t*)d_digest_ws);
+        HIP_TRY(hipGetLastError());
+        d_digest = d_digest_ws;
+    }
+    const size_t total = groups * m;
+    KernelTimer kt(c, st, 12);
+    hipLaunchKernelGGL(k_hash_pks_exp, dim3((unsigned)((total + EXP_THREADS - 1) / EXP_THREADS)), dim3(EXP_THREADS), 0, st,
+                       (const uint32_t*)d_digest, (uint32_t)m, total, (uint32_t*)d_ts);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+// blsgpu_hash_pks_dev: the exponents into the caller's buffer, the digests into the caller's if it asks for them
+int hash_pks_dev(blsgpu_ctx* c, const void* d_pks_ser, size_t k, size_t groups, const void* d_pk_hash_in, size_t m, void* d_out_ts,
+                 void* d_out_pk_hash, hipStream_t st) {
+    StreamGuard sg(c, st);
+    void* d_digest_ws = d_out_pk_hash;
+    if (!d_pk_hash_in && !d_digest_ws) {
+        HashPksWs w;
+        if (int rc = hash_pks_ws(c, 0, groups, w)) return rc;
+        d_digest_ws = w.digest;
+    }
+    if (d_pk_hash_in && d_out_pk_hash && d_pk_hash_in != d_out_pk_hash)
+        HIP_TRY(hipMemcpyAsync(d_out_pk_hash, d_pk_hash_in, groups * 32, hipMemcpyDeviceToDevice, st));
+    return hash_pks_launch(c, d_pks_ser, k, groups, d_pk_hash_in, m, d_out_ts, d_digest_ws, st);
+}
+// the exponents of `groups` groups (m each, from k_pks keys each) into the workspace, then the sums of msm_dev<DEG> over
+// groups x k points with them as its device scalars (m == k)
+template <int DEG>
+int aggregate_secure_dev(blsgpu_ctx* c, const void* d_pts, size_t k, const void* d_pks_ser, size_t k_pks, const void* d_pk_hash_in,
+                         size_t groups, void* d_out, void* d_out_inf, hipStream_t st) {
+    HashPksWs w;
+    {
+        StreamGuard sg(c, st);
+        if (int rc = hash_pks_ws(c, k, groups, w)) return rc;
+        if (int rc = hash_pks_launch(c, d_pks_ser, k_pks, groups, d_pk_hash_in, k, w.ts, w.digest, st)) return rc;
+    }
+    return msm_dev<DEG>(c, d_pts, w.ts, k, groups, d_out, d_out_inf, st);
+}
+// the exponents into the workspace, out[g] = sum_i t_gi sks[g k + i] mod n by k_fr_dot_secret (the exponents are its public
+// coefficients, the keys its secret y; timing kind 10), then the public key of every sum from k_fix_mul_secret reading
+// `d_out` where it lies
+int aggregate_priv_keys_secure_dev(blsgpu_ctx* c, const void* d_sks, const void* d_pks_ser, const void* d_pk_hash_in, size_t k, size_t groups,
+                                   void* d_out, void* d_out_pk_aff, void* d_out_pk_ser, hipStream_t st) {
+    StreamGuard sg(c, st);
+    const bool pk = d_out_pk_aff || d_out_pk_ser;
+    if (pk) {
+        if (int rc = fix_table(c, st, true)) return rc;
+    }
+    HashPksWs w;
+    if (int rc = hash_pks_ws(c, k, groups, w)) return rc;
+    if (int rc = hash_pks_launch(c, d_pks_ser, k, groups, d_pk_hash_in, k, w.ts, w.digest, st)) return rc;
+    const blsgpu::lagr::Shape sh = blsgpu::lagr::shape((uint32_t)k);
+    {
+        KernelTimer kt(c, st, 10);
+        hipLaunchKernelGGL(blsgpu::frsec::k_fr_dot_secret, dim3((unsigned)((groups + sh.gpb - 1) / sh.gpb)), dim3(sh.threads), sh.lds, st,
+                           (const uint8_t*)w.ts, (const uint8_t*)d_sks, (uint32_t)k, (uint32_t)groups, sh.gpb, (uint8_t*)d_out);
+        HIP_TRY(hipGetLastError());
+    }
+    return pk ? fix_mul_secret_launch(c, d_out, groups, d_out_pk_aff, d_out_pk_ser, st) : 0;
+}
+// blsgpu_aggregate_priv_keys_secure*: hash_pks_args and the limit on k of k_fr_dot_secret (a group is one workgroup)
+int aggregate_priv_args(const blsgpu_ctx* c, size_t k, size_t groups, bool null_buffer) {
+    if (c && k > blsgpu::lagr::MAX_K) return fail(-EINVAL, "k must be 1 .. BLSGPU_LAGRANGE_MAX_K");
+    if (int rc = hash_pks_args(c, k, k, groups, null_buffer)) return rc;
+    if (k * groups > 0xFFFFFFF0ull) return fail(-EINVAL, "batch too large");
+    return 0;
 }
 
 // the argument checks of blsgpu_threshold_deal_secret* (before anything is written); 1: nothing to do
@@ -2550,6 +2650,82 @@ BLSGPU_EXPORT int blsgpu_sign_threshold(blsgpu_ctx* c, const uint8_t* sks, const
     if (int rc = s.up()) return rc;
     if (int rc = blsgpu_sign_threshold_dev(c, s.at(dsk), s.at(dx), k, groups, s.at(dh), n_msg, s.opt(daff), s.opt(dser), s.opt(dinf), s.at(dst),
                                            nullptr)) return rc;
+    return s.down();
+}
+
+// ------------------------------------------------------------ secure aggregation: hash_pks exponents and the three sums --
+BLSGPU_EXPORT int blsgpu_hash_pks_dev(blsgpu_ctx* c, const void* d_pks_ser, size_t k, size_t groups, const void* d_pk_hash_in, size_t m,
+                                      void* d_out_ts, void* d_out_pk_hash, void* stream) {
+    if (int rc = hash_pks_args(c, k, m, groups, (!d_pks_ser && !d_pk_hash_in) || !d_out_ts)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return hash_pks_dev(c, d_pks_ser, k, groups, d_pk_hash_in, m, d_out_ts, d_out_pk_hash, (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_hash_pks(blsgpu_ctx* c, const uint8_t* pks_ser, size_t k, size_t groups, const uint8_t* pk_hash_in, size_t m,
+                                  uint8_t* out_ts, uint8_t* out_pk_hash) {
+    if (int rc = hash_pks_args(c, k, m, groups, (!pks_ser && !pk_hash_in) || !out_ts)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    Staging s(c);
+    // (with the digests given the keys are not read: they stay on the host)
+    const int dpk = s.in(pk_hash_in ? nullptr : pks_ser, groups * k * 48), dh = s.in(pk_hash_in, groups * 32), dts = s.out(out_ts, groups * m * 32),
+              ddg = s.out(out_pk_hash, groups * 32);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    if (int rc = hash_pks_dev(c, s.opt(dpk), k, groups, s.opt(dh), m, s.at(dts), s.opt(ddg), nullptr)) return rc;
+    return s.down();
+}
+BLSGPU_EXPORT int blsgpu_aggregate_pub_keys_secure_dev(blsgpu_ctx* c, const void* d_pts_aff, const void* d_pks_ser, const void* d_pk_hash_in,
+                                                       size_t k, size_t groups, void* d_out_aff, void* d_out_inf, void* stream) {
+    if (int rc = hash_pks_args(c, k, k, groups, !d_pts_aff || (!d_pks_ser && !d_pk_hash_in) || !d_out_aff)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return aggregate_secure_dev<1>(c, d_pts_aff, k, d_pks_ser, k, d_pk_hash_in, groups, d_out_aff, d_out_inf, (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_aggregate_pub_keys_secure(blsgpu_ctx* c, const uint8_t* pts_aff, const uint8_t* pks_ser, const uint8_t* pk_hash_in,
+                                                   size_t k, size_t groups, uint8_t* out_aff, uint8_t* out_inf) {
+    if (int rc = hash_pks_args(c, k, k, groups, !pts_aff || (!pks_ser && !pk_hash_in) || !out_aff)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    Staging s(c);
+    const int dp = s.in(pts_aff, groups * k * BLSGPU_G1_BYTES), dpk = s.in(pk_hash_in ? nullptr : pks_ser, groups * k * 48),
+              dh = s.in(pk_hash_in, groups * 32), dout = s.out(out_aff, groups * BLSGPU_G1_BYTES), dinf = s.out(out_inf, groups);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    if (int rc = aggregate_secure_dev<1>(c, s.at(dp), k, s.opt(dpk), k, s.opt(dh), groups, s.at(dout), s.opt(dinf), nullptr)) return rc;
+    return s.down();
+}
+BLSGPU_EXPORT int blsgpu_aggregate_sigs_secure_dev(blsgpu_ctx* c, const void* d_sigs_aff, size_t k, const void* d_pks_ser, size_t k_pks,
+                                                   const void* d_pk_hash_in, size_t groups, void* d_out_aff, void* d_out_inf, void* stream) {
+    if (int rc = hash_pks_args(c, k_pks, k, groups, !d_sigs_aff || (!d_pks_ser && !d_pk_hash_in) || !d_out_aff)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return aggregate_secure_dev<2>(c, d_sigs_aff, k, d_pks_ser, k_pks, d_pk_hash_in, groups, d_out_aff, d_out_inf, (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_aggregate_sigs_secure(blsgpu_ctx* c, const uint8_t* sigs_aff, size_t k, const uint8_t* pks_ser, size_t k_pks,
+                                               const uint8_t* pk_hash_in, size_t groups, uint8_t* out_aff, uint8_t* out_inf) {
+    if (int rc = hash_pks_args(c, k_pks, k, groups, !sigs_aff || (!pks_ser && !pk_hash_in) || !out_aff)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    Staging s(c);
+    const int dp = s.in(sigs_aff, groups * k * BLSGPU_G2_BYTES), dpk = s.in(pk_hash_in ? nullptr : pks_ser, groups * k_pks * 48),
+              dh = s.in(pk_hash_in, groups * 32), dout = s.out(out_aff, groups * BLSGPU_G2_BYTES), dinf = s.out(out_inf, groups);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    if (int rc = aggregate_secure_dev<2>(c, s.at(dp), k, s.opt(dpk), k_pks, s.opt(dh), groups, s.at(dout), s.opt(dinf), nullptr)) return rc;
+    return s.down();
+}
+BLSGPU_EXPORT int blsgpu_aggregate_priv_keys_secure_dev(blsgpu_ctx* c, const void* d_sks, const void* d_pks_ser, const void* d_pk_hash_in, size_t k,
+                                                        size_t groups, void* d_out, void* d_out_pk_aff, void* d_out_pk_ser, void* stream) {
+    if (int rc = aggregate_priv_args(c, k, groups, !d_sks || (!d_pks_ser && !d_pk_hash_in) || !d_out)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return aggregate_priv_keys_secure_dev(c, d_sks, d_pks_ser, d_pk_hash_in, k, groups, d_out, d_out_pk_aff, d_out_pk_ser, (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_aggregate_priv_keys_secure(blsgpu_ctx* c, const uint8_t* sks, const uint8_t* pks_ser, const uint8_t* pk_hash_in, size_t k,
+                                                    size_t groups, uint8_t* out, uint8_t* out_pk_aff, uint8_t* out_pk_ser) {
+    if (int rc = aggregate_priv_args(c, k, groups, !sks || (!pks_ser && !pk_hash_in) || !out)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    Staging s(c);
+    const int dsk = s.in(sks, groups * k * 32), dpk = s.in(pk_hash_in ? nullptr : pks_ser, groups * k * 48), dh = s.in(pk_hash_in, groups * 32),
+              dout = s.out(out, groups * 32), daff = s.out(out_pk_aff, groups * 96), dser = s.out(out_pk_ser, groups * 48);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    if (int rc = aggregate_priv_keys_secure_dev(c, s.at(dsk), s.opt(dpk), s.opt(dh), k, groups, s.at(dout), s.opt(daff), s.opt(dser), nullptr))
+        return rc;
     return s.down();
 }
 
