@@ -20,7 +20,11 @@
 // induction a value of type F<LO, HI> lies in (-(2 LO + HI) q, (2 HI + LO) q), so the column bound above also bounds
 // |sum a_t b_t| by a few hundred q^2, far inside the 2520 q^2 = R q that the reduction tolerates.  The signed top
 // digit (|.| < 2^23 for such values) is not counted in LO / HI: its products are below 2^52 per column, inside the
-// two units (2^57) of slack the column bound leaves.
+// two units (2^57) of slack the column bound leaves.  F<8, 8> fills int32 exactly, so what adds to a limb without
+// widening refuses it: norm (the carry) and neg / conj (the negative of -2^31).
+// Evidence: tests/test_fp28_vectors_model.py (the integer model and the compile-time bounds, at the range ends of
+// every type) and tests/test_gpu_fp28.py (the compiled code against that model limb for limb, through
+// blsgpu_fp28_check.hip).
 //
 // Boundaries: the wavefront VM keeps x 2^384 in 12 x 32-bit words; from_vm / to_vm convert with one product by a
 // constant (2^400 resp. 2^384 mod q).  canon() gives the canonical residue where it is observable (bytes, zero tests).
@@ -55,6 +59,7 @@ template <int A, int B, int C, int D> __device__ __forceinline__ F<A + D, B + C>
     return r;
 }
 template <int A, int B> __device__ __forceinline__ F<B, A> neg(const F<A, B>& x) {
+    static_assert(A < 8, "the negative of -2^31 leaves int32");
     F<B, A> r;
 #pragma unroll
     for (int j = 0; j < NL; j++) r.v[j] = -x.v[j];
@@ -68,7 +73,10 @@ template <int C, int A, int B> __device__ __forceinline__ F<C * A, C * B> mulc(c
     return r;
 }
 // carry pass: any limb range -> digits 0..12 in [0, 2^28), the sign moves to digit 13 (3 instructions per limb)
+// (the VALUE is kept: norm(neg(x)) of an fe x lies in (-2q, q), outside fe's (-q, 2q) -- fine as an operand of a
+// product, but it has to pass through one before canon or is_zero, which take (-q, 2q))
 template <int A, int B> __device__ __forceinline__ fe norm(const F<A, B>& x) {
+    static_assert(A < 8 && B < 8, "a limb at the end of F<8, 8> plus the carry leaves int32: use mulc_norm");
     fe r;
     int32_t c = 0;
 #pragma unroll
@@ -302,6 +310,7 @@ template <int C, int A, int B> __device__ __forceinline__ F2<C * A, C * B> mulc(
 template <int A, int B> __device__ __forceinline__ fe2 norm(const F2<A, B>& x) { return {norm(x.a), norm(x.b)}; }
 template <int C, int A, int B> __device__ __forceinline__ fe2 mulc_norm(const F2<A, B>& x) { return {mulc_norm<C>(x.a), mulc_norm<C>(x.b)}; }
 template <int A, int B> __device__ __forceinline__ F2<cmax(A, B), cmax(A, B)> conj(const F2<A, B>& x) {
+    static_assert(A < 8, "the negative of -2^31 leaves int32");
     F2<cmax(A, B), cmax(A, B)> r;
 #pragma unroll
     for (int j = 0; j < NL; j++) { r.a.v[j] = x.a.v[j]; r.b.v[j] = -x.b.v[j]; }
@@ -321,8 +330,9 @@ template <int A, int B, int C, int D> __device__ __forceinline__ fe2 mul(const F
     return from_raw2(f2_mul_call(to_raw2(x), to_raw2(y)));
 }
 template <int A, int B> __device__ __forceinline__ fe2 sqr(const F2<A, B>& x) {
-    typedef Term<A + B, A + B, A + B, A + B> T0;             // (a + b)(a - b) and (2 a) b
-    (void)sizeof(ColumnsFit<T0::pos, T0::neg>);
+    typedef Term<2 * A, 2 * B, A + B, A + B> T0;             // (a + b)(a - b): a + b is F<2A, 2B>, a - b is F<A + B, A + B>
+    typedef Term<2 * A, 2 * B, A, B> T1;                     // (2 a) b
+    (void)sizeof(ColumnsFit<cmax(T0::pos, T1::pos), cmax(T0::neg, T1::neg)>);
     return from_raw2(f2_sqr_call(to_raw2(x)));
 }
 template <int A0, int B0, int C0, int D0, int A1, int B1, int C1, int D1>
@@ -424,6 +434,7 @@ __device__ __forceinline__ ptT<E> pdbl(const ptT<E>& P) {
 // per code object; the two points travel through the ABI's 32 argument registers and scratch, < 1 % of the addition
 template <class E> __device__ __attribute__((noinline)) ptT<E> padd_fn(ptT<E> P, ptT<E> Q) { return padd(P, Q); }
 template <class E> __device__ __attribute__((noinline)) ptT<E> pdbl_fn(ptT<E> P) { return pdbl(P); }
+// pneg: Y comes back as norm(neg(Y)), a value in (-2q, q): an operand for padd / pmadd / pdbl, not for canon / is_zero
 template <class E> __device__ __forceinline__ ptT<E> pneg(const ptT<E>& P) { return {P.X, norm(neg(P.Y)), P.Z}; }
 }  // namespace r28
 }  // namespace blsgpu
