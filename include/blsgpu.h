@@ -72,8 +72,8 @@ int blsgpu_ctx_reserve(blsgpu_ctx *ctx, size_t max_pairs);
  * is the sum (which also counts the fixed-base G1 table and the HD derivation slice, blsgpu_g1_mul_gen /
  * blsgpu_hd_children, the per-path state of blsgpu_hd_paths, the commitments of blsgpu_g1_poly_check and the Lagrange
  * coefficients of blsgpu_threshold_combine / blsgpu_fr_interpolate_at_zero, the table of blsgpu_g1_mul_gen_secret, the
- * point tables of blsgpu_g2_mul_secret / blsgpu_sign, and the scalars and point copies of blsgpu_sign_threshold; they have no
- * field of their own).
+ * point tables of blsgpu_g2_mul_secret / blsgpu_sign, the scalars and point copies of blsgpu_sign_threshold, and the leaves and
+ * round buffers of blsgpu_sig_shares_check; they have no field of their own).
  * BLSGPU_WS_FLAGS_AND_LISTS counts the flag copy of blsgpu_miller_loop_batch's fast form as well (2 bytes per pair of a
  * slice).  No device call is made. */
 enum { BLSGPU_WS_PARTIALS = 0, BLSGPU_WS_STAGING, BLSGPU_WS_LINES, BLSGPU_WS_LINE_PRODUCTS, BLSGPU_WS_FLAGS_AND_LISTS,
@@ -448,6 +448,47 @@ int blsgpu_threshold_combine(blsgpu_ctx *ctx, const uint8_t *sigs_affine, const 
                              uint8_t *out, uint8_t *out_inf, uint8_t *status);
 int blsgpu_threshold_combine_dev(blsgpu_ctx *ctx, const void *d_sigs_affine, const void *d_x, size_t k, size_t groups,
                                  void *d_out, void *d_out_inf, void *d_status, void *stream);
+
+/* Signature shares of `groups` threshold sessions of k shares each, checked on the device, and the wrong ones named
+ * (csrc/blsgpu_sigshares.hip; one k per call, 1 <= k <= BLSGPU_LAGRANGE_MAX_K).  Share i of a session with message hash h is
+ * VALID iff
+ *   scaled = 1:  e(G1, sig_i) = e(lambda_i PK_i, H(h))  -- a unit signature of PrivateKey.sign_threshold (keys.py:134-141 of the
+ *                reference), lambda the Lagrange coefficients at zero of the session's players x;
+ *   scaled = 0:  e(G1, sig_i) = e(PK_i, H(h))           -- a plain share, secret_share.sign(m), as Threshold.aggregate_unit_sigs
+ *                (threshold.py:127-136) combines them;
+ * PK_i = sk_i G1 the player's share public key, H = hash_to_point_prehashed_Fq2 (ec.py:528-550).
+ * sigs: groups x k x 192 bytes affine G2, (0,0) = infinity.  keys: n_keys x 96 bytes affine G1; key_idx: groups x k uint32 into
+ * keys (as `poly` of blsgpu_g1_poly_check).  x: groups x k x 32 bytes big-endian player numbers, required when scaled, ignored
+ * (may be NULL) otherwise.  msg_hashes: groups x 32 bytes.  weights: groups x k x 8 bytes big-endian, the random 64-bit
+ * multipliers of the check, drawn by the CALLER (as BLS.verify_batch_randomized draws them: unpredictable to whoever made the
+ * shares); a ZERO weight is taken as 1 on the device.
+ * status: groups x k bytes -- 1 valid; 0 invalid, which includes a share off the twist, outside the order-n subgroup or at
+ * infinity (whatever its key); 2 not decided: the share's key is off the curve or outside G1.  session_status: groups bytes --
+ * 0 where blsgpu_lagrange_at_zero refuses the player set (a zero, a value >= n, a repeated x): all of that session's shares
+ * are then 0; 1 otherwise, and always 1 when not scaled.  stats (HOST memory in both forms, may be NULL): [0] the rounds run,
+ * summed over the slices of the call, [1] the node tests (two-pair pairings) performed.
+ * Once per call: the subgroup checks of keys and shares, H(h), the coefficients, k_share_weights (w_i = r_i lambda_i mod n,
+ * or r_i), and the leaves A_i = r_i sig_i, B_i = w_i PK_i from the G2 / G1 sums with device scalars.  Then rounds over NODES
+ * (session, offset, length): round 0 tests every session whole; a node's leaves are gathered, summed by the plain G2 / G1
+ * group sums to S and P, and e(-G1, S) e(P, H(h)) = 1 is tested by blsgpu_pairing_multi_batch_dev (two pairs per node).  A sum
+ * at infinity is never fed to the pairing: with H(h) != O a node whose two sums are both at infinity passes and one with
+ * exactly one at infinity fails (every point is in its prime-order subgroup); with H(h) = O it passes iff S = O.  The host
+ * reads ONE byte per node and round, halves the nodes that failed and stops at the leaves: at most log2 K + 1 rounds (K: k
+ * rounded up to a power of two), one stream synchronisation each -- the calls are NOT asynchronous.  Sessions are processed in
+ * slices that keep the leaves, and the largest round, below 2 GB each (counted in BLSGPU_WS_TOTAL).
+ * What is claimed: a failing leaf test is exact (0 < r_i < 2^64 is not 0 mod n); a node that passes although it holds an
+ * invalid eligible share does so with probability at most 2^-64 over the weights, per node.  Nothing stronger.
+ * -EINVAL before anything is written: k == 0 or above the limit (also with groups == 0), n_keys == 0, a key_idx >= n_keys, a
+ * NULL required buffer.  groups == 0 writes nothing and returns 0.  All of this is PUBLIC data: not constant-time. */
+int blsgpu_sig_shares_check(blsgpu_ctx *ctx, const uint8_t *sigs, const uint8_t *keys, size_t n_keys, const uint32_t *key_idx,
+                            const uint8_t *x, const uint8_t *msg_hashes, const uint8_t *weights, int scaled, size_t k,
+                            size_t groups, uint8_t *status, uint8_t *session_status, uint64_t *stats);
+/* The same with every buffer but stats in device memory (16-byte aligned where it holds points, 4-byte otherwise), on
+ * `stream`.  The key indices are first scanned on the device and the stream is synchronised once to read the result of that
+ * check; then once per round. */
+int blsgpu_sig_shares_check_dev(blsgpu_ctx *ctx, const void *d_sigs, const void *d_keys, size_t n_keys, const void *d_key_idx,
+                                const void *d_x, const void *d_msg_hashes, const void *d_weights, int scaled, size_t k,
+                                size_t groups, void *d_status, void *d_session_status, uint64_t *stats, void *stream);
 
 /* G2 scalar multiplication for SECRET scalars:  out_i = s_i P_(n_pts == 1 ? 0 : i)  with a schedule independent of s
  * (csrc/blsgpu_g2smul.hip k_g2_smul; vmgen/g2smul_model.py is its specification).  s_i is the literal 256-bit integer of

@@ -31,7 +31,7 @@ SYMBOLS = (
     "blsgpu_g1_poly_check", "blsgpu_g1_poly_check_dev",
     "blsgpu_g1_subgroup_check", "blsgpu_g1_subgroup_check_dev", "blsgpu_g2_subgroup_check", "blsgpu_g2_subgroup_check_dev",
     "blsgpu_lagrange_at_zero", "blsgpu_lagrange_at_zero_dev", "blsgpu_fr_interpolate_at_zero", "blsgpu_fr_interpolate_at_zero_dev",
-    "blsgpu_threshold_combine", "blsgpu_threshold_combine_dev",
+    "blsgpu_threshold_combine", "blsgpu_threshold_combine_dev", "blsgpu_sig_shares_check", "blsgpu_sig_shares_check_dev",
     "blsgpu_g2_mul_secret", "blsgpu_g2_mul_secret_dev", "blsgpu_sign", "blsgpu_sign_dev",
     "blsgpu_g1_mul_gen_secret", "blsgpu_g1_mul_gen_secret_dev", "blsgpu_hd_paths_secret", "blsgpu_hd_paths_secret_dev",
     "blsgpu_threshold_deal_secret", "blsgpu_threshold_deal_secret_dev",
@@ -143,6 +143,8 @@ def load_library(path=None):
         L.blsgpu_fr_interpolate_at_zero_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
         L.blsgpu_threshold_combine.argtypes = [vp, cp, cp, sz, sz, vp, vp, vp]
         L.blsgpu_threshold_combine_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
+        L.blsgpu_sig_shares_check.argtypes = [vp, cp, cp, sz, vp, cp, cp, cp, ctypes.c_int, sz, sz, vp, vp, vp]
+        L.blsgpu_sig_shares_check_dev.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, ctypes.c_int, sz, sz, vp, vp, vp, vp]
         L.blsgpu_g2_mul_secret.argtypes = [vp, cp, sz, cp, sz, vp, vp, vp]
         L.blsgpu_g2_mul_secret_dev.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp, vp]
         L.blsgpu_sign.argtypes = [vp, cp, cp, sz, sz, vp, vp]
@@ -627,6 +629,39 @@ class Engine:
     def threshold_combine_dev(self, d_sigs, d_x, k, groups, d_out, d_out_inf, d_status, stream=0):
         self._check(self.lib.blsgpu_threshold_combine_dev(self.h, d_sigs, d_x, k, groups, d_out, d_out_inf, d_status, stream),
                     "blsgpu_threshold_combine_dev")
+
+    def sig_shares_check(self, sigs, keys, key_idx, x, msg_hashes, weights, k, groups=1, scaled=True):
+        """Signature shares of `groups` sessions of k shares checked on the device (blsgpu_sig_shares_check): sigs groups x k x
+        192 affine bytes, keys n_keys x 96 affine bytes, key_idx groups x k indices into them, x groups x k x 32 bytes
+        big-endian (or ints below 2^256; None when not scaled), msg_hashes groups x 32 bytes, weights groups x k x 8 bytes
+        big-endian (or ints below 2^64; a zero weight is taken as 1).
+        -> (groups x k status bytes: 1 valid, 0 invalid, 2 not decided (the key is off the curve or outside G1); groups session
+        status bytes: 0 where the player set is refused; (rounds, node tests))"""
+        n = k * groups
+        wb = bytes(weights) if isinstance(weights, (bytes, bytearray)) else b"".join(int(w).to_bytes(8, "big") for w in weights)
+        if len(sigs) != 192 * n or len(keys) % 96 or len(key_idx) != n or len(msg_hashes) != 32 * groups or len(wb) != 8 * n:
+            raise ValueError("buffer lengths do not match k * groups")
+        if scaled and x is None:
+            raise ValueError("scaled shares need the player numbers")
+        if any(i < 0 or i >= 1 << 32 for i in key_idx):
+            raise OverflowError("key indices are 32-bit")
+        idx = (ctypes.c_uint32 * max(1, n))(*key_idx)
+        st = ctypes.create_string_buffer(max(1, n))
+        ss = ctypes.create_string_buffer(max(1, groups))
+        stats = (ctypes.c_uint64 * 2)()
+        self._check(self.lib.blsgpu_sig_shares_check(self.h, bytes(sigs), bytes(keys), len(keys) // 96, idx,
+                                                     self._scalars(x, n, "x") if scaled else None, bytes(msg_hashes), wb,
+                                                     1 if scaled else 0, k, groups, st, ss, stats), "blsgpu_sig_shares_check")
+        return st.raw[:n], ss.raw[:groups], (int(stats[0]), int(stats[1]))
+
+    def sig_shares_check_dev(self, d_sigs, d_keys, n_keys, d_key_idx, d_x, d_msg_hashes, d_weights, scaled, k, groups, d_status,
+                             d_session_status, stream=0):
+        """-> (rounds, node tests); the status bytes are in d_status / d_session_status when the call returns"""
+        stats = (ctypes.c_uint64 * 2)()
+        self._check(self.lib.blsgpu_sig_shares_check_dev(self.h, d_sigs, d_keys, n_keys, d_key_idx, d_x, d_msg_hashes, d_weights,
+                                                         1 if scaled else 0, k, groups, d_status, d_session_status, stats, stream),
+                    "blsgpu_sig_shares_check_dev")
+        return int(stats[0]), int(stats[1])
 
     def g2_mul_secret(self, pts, scalars, aff=True, ser=True):
         """s_i P_i (or s_i P for ONE point of 192 bytes) for n scalars (n x 32 bytes big-endian, or ints below 2^256, taken as

@@ -99,6 +99,13 @@ class HipProvider:
         """-> (groups x 192 affine bytes: sum_j L_j sig_j, [is_infinity], groups status bytes)"""
         return self._eng.threshold_combine(sigs, x, k, groups)
 
+    def sig_shares_check(self, sigs: bytes, keys: bytes, key_idx, x, msg_hashes: bytes, weights, k: int, groups: int = 1,
+                         scaled: bool = True):
+        """signature shares against their share public keys, a session by one random linear combination and the failing ones
+        bisected: -> (groups x k status bytes: 1 valid, 0 invalid, 2 not decided (bad key), groups session status bytes,
+        (rounds, node tests))"""
+        return self._eng.sig_shares_check(sigs, keys, key_idx, x, msg_hashes, weights, k, groups, scaled)
+
     def g2_mul_secret(self, pts: bytes, scalars, aff: bool = True, ser: bool = True):
         """s_i P_i (one point of 192 bytes: s_i P) on the scalar-independent schedule
         -> (n x 192 affine bytes, n x 96 serialised bytes, [is_infinity])"""
@@ -185,7 +192,10 @@ def use(provider):
     aggregate_sigs_secure(sigs_aff, k, pks_ser, k_pks, groups) -> (affine bytes, [is_inf]).
     Optional (a provider without them sends the Threshold.*_batch methods to the host loop): LAGRANGE_MAX_K,
     lagrange_at_zero(x, k, groups) -> (coefficient bytes, status bytes), fr_interpolate_at_zero(x, y, k, groups) ->
-    (32 bytes per group, status bytes), threshold_combine(sigs, x, k, groups) -> (affine bytes, [is_inf], status bytes)."""
+    (32 bytes per group, status bytes), threshold_combine(sigs, x, k, groups) -> (affine bytes, [is_inf], status bytes).
+    Optional (a provider without it sends Threshold.verify_sig_shares_batch to the exact per-share pairings):
+    sig_shares_check(sigs, keys, key_idx, x|None, msg_hashes, weights, k, groups, scaled) -> (status bytes, session status
+    bytes, (rounds, node tests))."""
     global _provider
     _provider = provider
 

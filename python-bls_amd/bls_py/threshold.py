@@ -227,6 +227,164 @@ class Threshold:
         return [Threshold.aggregate_unit_sigs(s, X, T, ec) if r is None else r for s, X, r in zip(sigs, Xs, out)]
 
 
+    # ---- signature shares: which of them are valid (blsgpu_sig_shares_check) ----
+    @staticmethod
+    def _sig_shares_exact(prov, items):
+        """[e(G1, sig) == e(c PK, H(m))] for items (sig bytes, key bytes, c, message hash): the exact check, one two-pair
+        pairing per share -- c PK by one grouped G1 sum of single points, H(m) of the distinct messages, then
+        pairing_multi_batch.  A share at infinity is invalid; c PK = O or H(m) = O leaves e(G1, sig) == 1, false for
+        every other share in G2 -- and the pairing decides a share outside it."""
+        if not items:
+            return []
+        from .fields import Fq12
+        ONE = Fq12.one(default_ec.q).serialize()
+        neg_g1 = H.g1_affine_bytes((generator_Fq() * (GROUP_ORDER - 1))._aff())
+        terms, _ = prov.g1_msm(b"".join(it[1] for it in items), [it[2] % GROUP_ORDER for it in items], 1, len(items))
+        msgs = list(dict.fromkeys(it[3] for it in items))
+        hm = prov.hash_to_g2(b"".join(msgs))
+        hm = {mh: hm[192 * j:192 * (j + 1)] for j, mh in enumerate(msgs)}
+        live = [i for i, it in enumerate(items) if any(it[0])]
+        out = [False] * len(items)
+        if live:
+            g1 = b"".join(neg_g1 + terms[96 * i:96 * (i + 1)] for i in live)
+            g2 = b"".join(items[i][0] + hm[items[i][3]] for i in live)
+            res = prov.pairing_multi_batch(g1, g2, 2, len(live))
+            for j, i in enumerate(live):
+                out[i] = res[576 * j:576 * (j + 1)] == ONE
+        return out
+
+    @staticmethod
+    def verify_sig_shares_batch(signature_groups, player_groups, public_key_groups, message_hashes, scaled=True, rng=None,
+                                ec=default_ec):
+        """For every session, which of its signature shares are valid: a list of lists of bool.  Session g holds the shares
+        signature_groups[g] (Signature objects) of the players player_groups[g] with the share public keys
+        public_key_groups[g] (PublicKey objects, PK_i = sk_i G1) over the 32-byte message hash message_hashes[g].
+        scaled=True: unit signatures of PrivateKey.sign_threshold -- valid iff e(G1, sig_i) == e(lambda_i PK_i, H(m)) with
+        lambda = lagrange_coeffs_at_zero(players); scaled=False: plain shares secret_share.sign(m) -- valid iff
+        e(G1, sig_i) == e(PK_i, H(m)) (the players are not looked at).
+        On the GPU (blsgpu_sig_shares_check, one call per distinct session length): a session is checked by ONE random
+        linear combination with weights rng.getrandbits(64) drawn in list order (default secrets.SystemRandom(); a zero is
+        drawn again), and only the sessions that fail are bisected down to the wrong shares.  An invalid share is reported
+        valid with probability at most 2^-64 per tested node; a share reported invalid IS invalid.  A share the device does
+        not decide (its key is off the curve or outside G1), a session it does not take (routing: _device_buckets) and a
+        provider without the entry get the exact per-share pairings.  A player set lagrange_coeffs_at_zero asserts on
+        raises the same AssertionError (scaled only)."""
+        import secrets
+        from . import backend
+        sigs = [list(s) for s in signature_groups]
+        Xs = [list(p) for p in player_groups]
+        pks = [list(p) for p in public_key_groups]
+        mhs = list(message_hashes)
+        m = len(sigs)
+        if not (len(Xs) == len(pks) == len(mhs) == m):
+            raise ValueError("need one player list, one key list and one message hash per session")
+        for g in range(m):
+            if not (len(sigs[g]) == len(pks[g]) and (not scaled or len(Xs[g]) == len(sigs[g]))):
+                raise ValueError("a session needs one key (and, scaled, one player) per share")
+        rng = rng or secrets.SystemRandom()
+        n = ec.n
+
+        def fits(i):
+            return len(mhs[i]) == 32
+        if scaled:
+            prov, buckets = Threshold._device_buckets(Xs, ec, "sig_shares_check", fits)
+        else:
+            prov, buckets = Threshold._device_buckets([list(range(1, len(s) + 1)) for s in sigs], ec, "sig_shares_check", fits)
+        results = [None] * m
+        seen_sig, key_row, key_bytes = {}, {}, []
+
+        def sig_affine(sig):
+            b = seen_sig.get(id(sig))
+            if b is None:
+                b = seen_sig[id(sig)] = H.g2_affine_bytes(sig.value.to_affine()._aff())
+            return b
+
+        def key_affine(pk):
+            return H.g1_affine_bytes(pk.value.to_affine()._aff())
+        undecided = []                                      # (session, share)
+        for k, idx in buckets.items():
+            for i in idx:                                   # the key table: keys deduplicated over the whole call
+                for pk in pks[i]:
+                    if pk not in key_row:
+                        key_row[pk] = len(key_bytes)
+                        key_bytes.append(key_affine(pk))
+        for k, idx in buckets.items():
+            weights = []
+            for _ in range(k * len(idx)):
+                w = 0
+                while w == 0:
+                    w = rng.getrandbits(64)
+                weights.append(w)
+            status, sess, _ = prov.sig_shares_check(
+                b"".join(sig_affine(sg) for i in idx for sg in sigs[i]), b"".join(key_bytes),
+                [key_row[pk] for i in idx for pk in pks[i]],
+                b"".join(x.to_bytes(32, "big") for i in idx for x in Xs[i]) if scaled else None,
+                b"".join(bytes(mhs[i]) for i in idx), weights, k, len(idx), scaled)
+            for q, i in enumerate(idx):
+                assert sess[q] == 1                         # (the assertion of _device_buckets has passed)
+                results[i] = [st == 1 for st in status[q * k:(q + 1) * k]]
+                undecided += [(i, j) for j in range(k) if status[q * k + j] == 2]
+        for i in range(m):
+            if results[i] is None:
+                results[i] = [None] * len(sigs[i])
+                undecided += [(i, j) for j in range(len(sigs[i]))]
+        if undecided:
+            if scaled:
+                lam = {i: [int(l) for l in Threshold.lagrange_coeffs_at_zero(Xs[i], ec)] for i in {i for i, _ in undecided}}
+            exact = Threshold._sig_shares_exact(
+                prov or backend.get(),
+                [(sig_affine(sigs[i][j]), key_affine(pks[i][j]), lam[i][j] if scaled else 1, bytes(mhs[i])) for i, j in undecided])
+            for (i, j), ok in zip(undecided, exact):
+                results[i][j] = ok
+        return results
+
+    @staticmethod
+    def share_public_keys(commitments, players, ec=default_ec):
+        """The share public keys PK_x = sum_d sum_j x^j C[d][j] of the players x (ints) from the dealers' commitment
+        polynomials (commitments[d]: the T on-curve G1 points dealer d published, Joint-Feldman) as PublicKey objects --
+        what a combiner checks signature shares against.  One plain grouped G1 sum adds the dealers' commitments per
+        coefficient index, then the evaluation-only form of g1_poly_check (blsgpu_g1_poly_check with s = None) evaluates the
+        summed polynomial at every player in the exponent."""
+        from . import backend
+        from .keys import PublicKey
+        commitments, players = [list(C) for C in commitments], list(players)
+        T = len(commitments[0])
+        assert T >= 1 and all(len(C) == T for C in commitments)
+        prov = backend.get()
+        D = len(commitments)
+
+        def aff(pt):
+            return H.g1_affine_bytes((pt if type(pt) is AffinePoint else pt.to_affine())._aff())
+        summed, _ = prov.g1_msm(b"".join(aff(commitments[d][j]) for j in range(T) for d in range(D)), None, D, T)
+        if not players:
+            return []
+        _, out = prov.g1_poly_check(summed, 1, T, [0] * len(players), b"".join((x % ec.n).to_bytes(32, "big") for x in players),
+                                    None, True)
+        return [PublicKey.from_g1(JacobianPoint._from(H.F1, H.aff_to_jac(H.F1, H.g1_from_abi(out[96 * i:96 * (i + 1)]))))
+                for i in range(len(players))]
+
+    @staticmethod
+    def recover_batch(signature_groups, player_groups, public_key_groups, message_hashes, T, rng=None, ec=default_ec):
+        """Recover the signature of every session from PLAIN shares (secret_share.sign(m)) of which some may be wrong:
+        verify_sig_shares_batch(..., scaled=False), then the first T valid shares of each session, in the order given,
+        combined by aggregate_unit_sigs_batch.  -> [(Signature or None, flags)] per session: None when fewer than T
+        shares are valid; flags are the session's list of verify_sig_shares_batch."""
+        sigs = [list(s) for s in signature_groups]
+        Xs = [list(p) for p in player_groups]
+        flags = Threshold.verify_sig_shares_batch(sigs, Xs, public_key_groups, message_hashes, scaled=False, rng=rng, ec=ec)
+        take = []
+        for s, X, f in zip(sigs, Xs, flags):
+            good = [j for j, ok in enumerate(f) if ok][:T]
+            take.append(good if len(good) == T else None)
+        live = [g for g, t in enumerate(take) if t is not None]
+        combined = Threshold.aggregate_unit_sigs_batch([[sigs[g][j] for j in take[g]] for g in live],
+                                                       [[Xs[g][j] for j in take[g]] for g in live], T, ec)
+        out = [(None, f) for f in flags]
+        for g, sig in zip(live, combined):
+            out[g] = (sig, flags[g])
+        return out
+
+
 def _g1_content(C):
     """the content key of a commitment list whose every element is an on-curve G1 AffinePoint (the device's input), or
     None (the host loop takes it)"""

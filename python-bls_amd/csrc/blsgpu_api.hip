@@ -27,6 +27,7 @@
 #include "blsgpu_lagrange.hip"
 #include "blsgpu_frsecret.hip"
 #include "blsgpu_hashpks.hip"
+#include "blsgpu_sigshares.hip"
 #include "blsgpu_g2smul.hip"
 #include "blsgpu_h2c.hip"
 #include "blsgpu_h2cw.hip"
@@ -838,6 +839,136 @@ int threshold_combine_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_x, si
         if (int rc = lagrange_launch(c, d_x, k, groups, c->at<void>(B_LAGR_WS), d_status, st)) return rc;
     }
     return msm_dev<2>(c, d_sigs, c->at<void>(B_LAGR_WS), k, groups, d_out, d_out_inf, st);
+}
+
+// ------------------------------------------------------------ signature shares (blsgpu_sigshares.hip) --
+// the argument checks of blsgpu_sig_shares_check* (before anything is written); 1: nothing to do
+int sig_shares_args(const blsgpu_ctx* c, size_t k, size_t groups, size_t n_keys, bool null_buffer) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (k == 0 || k > blsgpu::lagr::MAX_K) return fail(-EINVAL, "k must be 1 .. BLSGPU_LAGRANGE_MAX_K");
+    if (groups == 0) return 1;
+    if (n_keys == 0) return fail(-EINVAL, "key index out of range");
+    if (null_buffer) return fail(-EINVAL, "NULL argument");
+    if (groups > 0x7FFFFFFFull || n_keys > 0x7FFFFFFFull || k * groups > 0xFFFFFFF0ull) return fail(-EINVAL, "batch too large");
+    return 0;
+}
+// Sessions in slices; per slice the once-per-call stages into B_SHR_WS, then the rounds: the nodes of a round (all of one
+// length) go up, their verdict bytes come back -- the one synchronisation of a round -- and the host halves the nodes that
+// failed.  `scan`: the _dev form's device scan of the key indices first.  stats (host, may be NULL): rounds, node tests.
+int sig_shares_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_t n_keys, const void* d_key_idx, const void* d_x,
+                   const void* d_hashes, const void* d_weights, int scaled, size_t k, size_t groups, void* d_status, void* d_sess,
+                   uint64_t* stats, bool scan, hipStream_t st) {
+    using namespace blsgpu::sigsh;
+    uint32_t lg_k = 0;
+    while (((size_t)1 << lg_k) < k) lg_k++;
+    const size_t K = (size_t)1 << lg_k;                                    // k rounded up to a power of two
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    // slices of sessions whose kept arrays, and whose largest possible round (every leaf a node), stay below 2 GB each
+    const size_t keep_per = k * (2 + 3 * 32 + 2 * BLSGPU_G1_BYTES + BLSGPU_G2_BYTES) + BLSGPU_G2_BYTES + 1;
+    const size_t round_per = K * (sizeof(Node) + 3 * BLSGPU_G1_BYTES + 4 * BLSGPU_G2_BYTES + BLSGPU_FQ12_BYTES + 3);
+    size_t slice = ((size_t)2 << 30) / (keep_per > round_per ? keep_per : round_per);
+    if (slice < 1) slice = 1;
+    if (slice > groups) slice = groups;
+    const size_t n0 = slice * k;
+    size_t off = 256;                                                        // [0, 4): the flag word of the index scan
+    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
+    const size_t o_keyst = take(n_keys), o_sigst = take(n0), o_h = take(slice * BLSGPU_G2_BYTES), o_hinf = take(slice),
+                 o_lam = take(scaled ? n0 * 32 : 0), o_r = take(n0 * 32), o_w = take(n0 * 32), o_pk = take(n0 * BLSGPU_G1_BYTES),
+                 o_elig = take(n0), o_a = take(n0 * BLSGPU_G2_BYTES), o_b = take(n0 * BLSGPU_G1_BYTES);
+    StreamGuard sg(c, st);
+    if (int rc = c->grow(B_SHR_WS, off)) return rc;
+    char* const W = c->at<char>(B_SHR_WS);
+    if (scan) {
+        uint32_t bad = 0;
+        if (int rc = scan_flag(W, st, bad, [&](uint32_t* flag) {
+                for (size_t lo = 0; lo < groups * k; lo += FIX_SLICE) {
+                    const size_t m = groups * k - lo < FIX_SLICE ? groups * k - lo : FIX_SLICE;
+                    hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
+                                       (const uint32_t*)d_key_idx + lo, (uint32_t)m, (uint32_t)n_keys, flag);
+                }
+            }))
+            return rc;
+        if (bad) return fail(-EINVAL, "key index out of range");
+    }
+    if (int rc = subgroup_dev(c, 1, d_keys, n_keys, W + o_keyst, st)) return rc;
+    if (!scaled) HIP_TRY(hipMemsetAsync(d_sess, 1, groups, st));
+    uint64_t rounds = 0, tests = 0;
+    std::vector<Node> cur, next;
+    std::vector<uint8_t> verdict;
+    int rc = for_slices(groups, slice, [&](size_t lo, size_t m) {
+        const size_t n = m * k;
+        const char* sigs = (const char*)d_sigs + lo * k * BLSGPU_G2_BYTES;
+        uint8_t* status = (uint8_t*)d_status + lo * k;
+        if (int rc = subgroup_dev(c, 2, sigs, n, W + o_sigst, st)) return rc;
+        if (int rc = blsgpu_hash_to_g2_dev(c, (const char*)d_hashes + lo * 32, m, W + o_h, st)) return rc;
+        if (scaled) {
+            if (int rc = lagrange_launch(c, (const char*)d_x + lo * k * 32, k, m, W + o_lam, (uint8_t*)d_sess + lo, st)) return rc;
+        }
+        hipLaunchKernelGGL(k_share_weights, dim3((unsigned)((n + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, (const uint32_t*)sigs,
+                           (const uint8_t*)(W + o_sigst), (const uint32_t*)d_keys, (const uint8_t*)(W + o_keyst),
+                           (const uint32_t*)d_key_idx + lo * k, scaled ? (const uint8_t*)(W + o_lam) : nullptr,
+                           scaled ? (const uint8_t*)d_sess + lo : nullptr, (const uint8_t*)d_weights + lo * k * 8,
+                           (const uint32_t*)(W + o_h), (uint32_t)k, (uint32_t)n, (uint8_t*)(W + o_r), (uint8_t*)(W + o_w),
+                           (uint32_t*)(W + o_pk), (uint8_t*)(W + o_elig), (uint8_t*)(W + o_hinf), status);
+        HIP_TRY(hipGetLastError());
+        // the leaves: scalar multiplications as sums of one point with device scalars
+        if (int rc = msm_dev<2>(c, sigs, W + o_r, 1, n, W + o_a, nullptr, st)) return rc;
+        if (int rc = msm_dev<1>(c, W + o_pk, W + o_w, 1, n, W + o_b, nullptr, st)) return rc;
+        cur.resize(m);
+        for (size_t s = 0; s < m; s++) cur[s] = {(uint32_t)s, 0u};
+        for (uint32_t lg = lg_k;; lg--) {
+            const size_t nn = cur.size(), len = (size_t)1 << lg, slots = nn * len;
+            size_t ro = 0;
+            auto rtake = [&](size_t bytes) { size_t o = ro; ro += al(bytes); return o; };
+            const size_t r_nodes = rtake(nn * sizeof(Node)), r_ga = rtake(slots * BLSGPU_G2_BYTES), r_gb = rtake(slots * BLSGPU_G1_BYTES),
+                         r_s = rtake(nn * BLSGPU_G2_BYTES), r_p = rtake(nn * BLSGPU_G1_BYTES), r_sinf = rtake(nn), r_pinf = rtake(nn),
+                         r_g1 = rtake(nn * 2 * BLSGPU_G1_BYTES), r_g2 = rtake(nn * 2 * BLSGPU_G2_BYTES),
+                         r_e = rtake(nn * BLSGPU_FQ12_BYTES), r_v = rtake(nn);
+            if (int rc = c->grow(B_SHR_ROUND, ro)) return rc;
+            char* const R = c->at<char>(B_SHR_ROUND);
+            const Node* d_nodes = (const Node*)(R + r_nodes);
+            HIP_TRY(hipMemcpyAsync(R + r_nodes, cur.data(), nn * sizeof(Node), hipMemcpyHostToDevice, st));
+            const size_t gtotal = slots * (G1_Q + G2_Q);
+            hipLaunchKernelGGL(k_share_gather, dim3((unsigned)((gtotal + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, d_nodes, lg, gtotal,
+                               (uint32_t)k, (const uint4*)(W + o_a), (const uint4*)(W + o_b), (const uint8_t*)(W + o_elig),
+                               (uint4*)(R + r_ga), (uint4*)(R + r_gb));
+            HIP_TRY(hipGetLastError());
+            if (int rc = msm_dev<2>(c, R + r_ga, nullptr, len, nn, R + r_s, R + r_sinf, st)) return rc;
+            if (int rc = msm_dev<1>(c, R + r_gb, nullptr, len, nn, R + r_p, R + r_pinf, st)) return rc;
+            const size_t ptotal = nn * (2 * G1_Q + 2 * G2_Q);
+            hipLaunchKernelGGL(k_share_pairs, dim3((unsigned)((ptotal + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, d_nodes, ptotal,
+                               (const uint4*)(R + r_s), (const uint8_t*)(R + r_sinf), (const uint4*)(R + r_p), (const uint8_t*)(R + r_pinf),
+                               (const uint4*)(W + o_h), (const uint8_t*)(W + o_hinf), (uint4*)(R + r_g1), (uint4*)(R + r_g2));
+            HIP_TRY(hipGetLastError());
+            if (int rc = blsgpu_pairing_multi_batch_dev(c, R + r_g1, R + r_g2, nullptr, 2, nn, R + r_e, st)) return rc;
+            hipLaunchKernelGGL(k_share_verdict, dim3((unsigned)((nn + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, d_nodes, (uint32_t)nn,
+                               (const uint4*)(R + r_e), (const uint8_t*)(R + r_sinf), (const uint8_t*)(R + r_pinf),
+                               (const uint8_t*)(W + o_hinf), lg == 0 ? 1u : 0u, (uint32_t)k, (uint8_t*)(R + r_v), status);
+            HIP_TRY(hipGetLastError());
+            verdict.resize(nn);
+            HIP_TRY(hipMemcpyAsync(verdict.data(), R + r_v, nn, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            rounds++;
+            tests += nn;
+            if (lg == 0) break;
+            // a node that failed is halved; a half that lies past the session's k shares holds nothing and is not tested
+            next.clear();
+            for (size_t i = 0; i < nn; i++)
+                if (!verdict[i]) {
+                    next.push_back({cur[i].session, cur[i].offset});
+                    if (cur[i].offset + len / 2 < k) next.push_back({cur[i].session, (uint32_t)(cur[i].offset + len / 2)});
+                }
+            if (next.empty()) break;
+            cur.swap(next);
+        }
+        return 0;
+    });
+    if (rc) return rc;
+    if (stats) {
+        stats[0] = rounds;
+        stats[1] = tests;
+    }
+    return 0;
 }
 
 // ------------------------------------------------------------ scalar-field work on secrets (blsgpu_frsecret.hip) --
@@ -2529,6 +2660,39 @@ BLSGPU_EXPORT int blsgpu_threshold_combine(blsgpu_ctx* c, const uint8_t* sigs_af
     if (int rc = s.alloc()) return rc;
     if (int rc = s.up()) return rc;
     if (int rc = threshold_combine_dev(c, s.at(dsig), s.at(dx), k, groups, s.at(dout), s.opt(dinf), s.at(dst), nullptr)) return rc;
+    return s.down();
+}
+
+// ------------------------------------------------------------ signature shares --
+BLSGPU_EXPORT int blsgpu_sig_shares_check_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_t n_keys, const void* d_key_idx,
+                                              const void* d_x, const void* d_msg_hashes, const void* d_weights, int scaled, size_t k,
+                                              size_t groups, void* d_status, void* d_session_status, uint64_t* stats, void* stream) {
+    if (int rc = sig_shares_args(c, k, groups, n_keys, !d_sigs || !d_keys || !d_key_idx || (scaled && !d_x) || !d_msg_hashes || !d_weights ||
+                                                           !d_status || !d_session_status))
+        return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return sig_shares_dev(c, d_sigs, d_keys, n_keys, d_key_idx, d_x, d_msg_hashes, d_weights, scaled, k, groups, d_status, d_session_status,
+                          stats, true, (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_sig_shares_check(blsgpu_ctx* c, const uint8_t* sigs, const uint8_t* keys, size_t n_keys, const uint32_t* key_idx,
+                                          const uint8_t* x, const uint8_t* msg_hashes, const uint8_t* weights, int scaled, size_t k,
+                                          size_t groups, uint8_t* status, uint8_t* session_status, uint64_t* stats) {
+    if (int rc = sig_shares_args(c, k, groups, n_keys, !sigs || !keys || !key_idx || (scaled && !x) || !msg_hashes || !weights || !status ||
+                                                           !session_status))
+        return rc < 0 ? rc : 0;
+    const size_t n = groups * k;
+    for (size_t i = 0; i < n; i++)
+        if (key_idx[i] >= n_keys) return fail(-EINVAL, "key index out of range");
+    HIP_TRY(hipSetDevice(c->device));
+    Staging s(c);
+    const int dsig = s.in(sigs, n * BLSGPU_G2_BYTES), dkey = s.in(keys, n_keys * BLSGPU_G1_BYTES), didx = s.in(key_idx, n * 4),
+              dx = s.in(scaled ? x : nullptr, n * 32), dh = s.in(msg_hashes, groups * 32), dw = s.in(weights, n * 8),
+              dst = s.out(status, n), dss = s.out(session_status, groups);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    if (int rc = sig_shares_dev(c, s.at(dsig), s.at(dkey), n_keys, s.at(didx), s.opt(dx), s.at(dh), s.at(dw), scaled, k, groups, s.at(dst),
+                                s.at(dss), stats, false, nullptr))
+        return rc;
     return s.down();
 }
 
