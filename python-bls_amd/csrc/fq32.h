@@ -2,7 +2,11 @@
 // limb order, Montgomery form with R = 2^384).  Written for gfx950: the inner
 // product step is one v_mad_u64_u32 per limb pair (full-rate on CDNA4, see
 // profiles/r01_intrate_microbench.txt).  The same source compiles for the host
-// (BLS_HD empty) so tests/test_fq32_host.py can check it against Python ints.
+// (BLS_HD empty) so tests/test_abi_and_host.py and tests/test_fq32_vectors_model.py
+// can check it against Python ints.  Where the device compiles OTHER code than the
+// host (fq_mul_dev<> / fq_sqr_dev, fat_reduce, inv_mad32, the addc / subc builtins),
+// tests/test_gpu_fq32.py runs every function here as a kernel of its own
+// (blsgpu_fq32_check.hip) on the operand sets of tests/fq32_vectors.py.
 #pragma once
 #include <stdint.h>
 
@@ -157,7 +161,8 @@ BLS_HD void fq_mul_relaxed(uint32_t* __restrict__ r, const uint32_t* __restrict_
 #endif
 }
 // r = a^2 * R^-1 mod q with r < 2q for a < 3q: the dedicated squaring columns on the GPU
-// (fq_mul_gfx950.h: 78 + 144 multiply-accumulates instead of 288), the product on the host
+// (fq_mul_gfx950.h: 78 + 144 multiply-accumulates instead of 288), the product on the host.
+// No kernel calls it: only the check library (blsgpu_fq32_check.hip) instantiates fq_sqr_dev.
 BLS_HD void fq_sqr_relaxed(uint32_t* __restrict__ r, const uint32_t* __restrict__ a) {
 #if defined(__HIP_DEVICE_COMPILE__)
     fq_sqr_dev(r, a);

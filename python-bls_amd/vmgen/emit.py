@@ -81,6 +81,32 @@ def plan_lin_round(lanes):
     return plan, mn, mp, lv
 
 
+NEG_CF_MAX = 255                             # 255 (2^32 - 1) < 2^40: what fat_flip (csrc/fq32.h) admits per limb
+BIAS_LIMB_MAX = (1 << 40) + (1 << 32) - 1    # every 64-bit limb of BIAS is 2^40 + (a 32-bit digit)
+Q_BITS = 381
+BIAS_MAX = (BIAS_LIMB_MAX + 1) * ((1 << 352) + (1 << 321))   # above BIAS = sum limb_j 2^(32 j)
+
+
+def check_lin_bounds(plan, mn):
+    """The ranges csrc/fq32.h states for a LIN round, for operand limbs up to 2^32 - 1 and operands below 2q:
+    every limb of a lane's negative sum below 2^40 at the flip (fat_flip), every limb of a group's merged accumulator
+    below 2^44 and its value below 2^396 at the reduce (fat_reduce).  A group is 4 / 2 / 1 adjacent lanes (flags)."""
+    at = 0
+    while at < len(plan):
+        g = 4 if plan[at][1] >> 15 & 1 else 2 if plan[at][1] >> 14 & 1 else 1
+        grp = plan[at:at + g]
+        at += g
+        tot = pos = 0
+        for d, flags, negs, poss in grp:
+            assert len(negs) <= mn
+            nsum = sum(cf for neg, cf, s in negs)
+            assert nsum <= NEG_CF_MAX, "negative coefficients of a lane share sum to %d: a limb may reach 2^40 at the flip" % nsum
+            tot += nsum + sum(cf for neg, cf, s in poss)
+            pos += sum(cf for neg, cf, s in poss)
+        assert tot * 0xFFFFFFFF + 4 * BIAS_LIMB_MAX < 1 << 44, "a limb of a group's accumulator may reach 2^44 (coefficients sum to %d)" % tot
+        assert g * BIAS_MAX + pos * (2 << Q_BITS) < 1 << 396, "a group's value may reach 2^396"
+
+
 def pack(segs, order):
     """-> (per-segment list of (data_off, meta), data)"""
     seg_rounds, data = {}, []
@@ -115,6 +141,7 @@ def pack(segs, order):
                 plan, mn, mp, lv = plan_lin_round(lanes)
                 K = mn + mp
                 assert K < 256 and len(plan) <= LANES
+                check_lin_bounds(plan, mn)
                 kp = kpad(K)
                 for ln in range(LANES):
                     rec = [0] * kp

@@ -10,6 +10,7 @@ import subprocess
 import pytest
 
 from conftest import ROOT
+from fq32_vectors import INV_CORNERS, INV_PATTERNS, JACOBI_CORNERS      # shared with the device check (tests/test_gpu_fq32.py)
 
 Q = 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab
 CSRC = os.path.join(ROOT, "python-bls_amd", "csrc")
@@ -65,7 +66,7 @@ def test_fq32_host_build_matches_python_ints(tmp_path):
     R = 1 << 384
     Ri = pow(R, -1, Q)
     rnd = random.Random(7)
-    vals = [0, 1, 2, Q - 1, Q - 2, R % Q] + [rnd.randrange(Q) for _ in range(150)]
+    vals = INV_CORNERS + [rnd.randrange(Q) for _ in range(150)]
     inp, exp = [], []
     for _ in range(400):
         a, b = rnd.choice(vals), rnd.choice(vals)
@@ -76,12 +77,12 @@ def test_fq32_host_build_matches_python_ints(tmp_path):
     # the inversion (safegcd division steps) on many more values, also relaxed ones (q <= a < 2q)
     # and values with long runs of zero / one bits
     more = [rnd.randrange(Q) for _ in range(3000)] + [Q + rnd.randrange(Q) for _ in range(200)]
-    more += [(1 << k) % Q for k in range(0, 384, 7)] + [(Q - (1 << k)) % Q for k in range(0, 380, 11)] + [Q, Q + 1, 2 * Q - 1]
+    more += INV_PATTERNS                                    # 2^k mod q, q - 2^k, q, q + 1, 2q - 1
     for a in more:
         inp.append("inv %096x %096x" % (a, 0))
         exp.append((pow(a % Q, -1, Q) * R * R) % Q if a % Q else 0)
     # the quadratic character from division steps (fq_jacobi_var) against Euler's criterion: canonical values, corners
-    jvals = [0, 1, 2, 3, 4, Q - 1, Q - 2, (Q - 1) // 2, (Q + 1) // 2, 1 << 380] + [rnd.randrange(Q) for _ in range(4000)]
+    jvals = JACOBI_CORNERS + [rnd.randrange(Q) for _ in range(4000)]
     jvals += [rnd.randrange(1 << k) for k in (8, 64, 200, 380) for _ in range(100)]
     ninp = len(inp)
     for a in jvals:
