@@ -29,6 +29,54 @@ def test_header_symbols_exported():
     assert lib.blsgpu_version().startswith(b"blsgpu/")
 
 
+def header_declarations():
+    """{function: (return type, [parameter kinds])} of every declaration of include/blsgpu.h; an unknown type raises"""
+    with open(os.path.join(ROOT, "include", "blsgpu.h")) as f:
+        hdr = f.read()
+    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)                    # comments name functions too
+    hdr = re.sub(r"^\s*#.*$", " ", hdr, flags=re.M).replace('extern "C" {', " ")
+    scalar = {"size_t": "size_t", "int": "int", "unsigned": "unsigned", "double": "double"}
+    out = {}
+    for stmt in hdr.split(";"):
+        if "(" not in stmt:                                             # the typedef, the enum, the closing brace
+            continue
+        m = re.fullmatch(r"\s*(.+?)\s*\b(blsgpu_[a-z0-9_]+)\s*\((.*)\)\s*", stmt, flags=re.S)
+        assert m, "not a function declaration: %r" % stmt
+        ret, name, params = " ".join(m.group(1).split()), m.group(2), " ".join(m.group(3).split())
+        assert ret in ("int", "void", "const char *"), (name, ret)
+        kinds = []
+        for p in ([] if params == "void" else params.split(",")):
+            if "*" in p or "[" in p:
+                kinds.append("pointer")
+            else:
+                words = p.replace("const", " ").split()
+                assert len(words) == 2 and words[0] in scalar, "%s: parameter %r" % (name, p)
+                kinds.append(scalar[words[0]])
+        assert name not in out, name
+        out[name] = (ret, kinds)
+    return out
+
+
+def test_prototypes_match_header():
+    """the argument and return types ctypes is told (bls_py._native.PROTOTYPES) against the header's declarations: a wrong
+    count or a size_t taken for a pointer is accepted by ctypes and corrupts the call.  The library is not loaded."""
+    import ctypes
+    from bls_py import _native
+
+    def kind(t):
+        if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+            return "pointer"
+        return {ctypes.c_size_t: "size_t", ctypes.c_int: "int", ctypes.c_uint: "unsigned", ctypes.c_double: "double"}[t]
+
+    declared = header_declarations()
+    assert set(declared) == set(_native.PROTOTYPES) == set(_native.SYMBOLS) and len(_native.SYMBOLS) == len(_native.PROTOTYPES)
+    restypes = {"int": ctypes.c_int, "void": None, "const char *": ctypes.c_char_p}
+    for name, (ret, kinds) in declared.items():
+        row = _native.PROTOTYPES[name]
+        assert [kind(t) for t in row] == kinds, name
+        assert getattr(row, "restype", ctypes.c_int) is restypes[ret], name
+
+
 def test_no_cpu_fallback():
     """Without a GPU the engine must raise, never compute on the CPU."""
     import torch
