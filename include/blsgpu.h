@@ -72,8 +72,8 @@ int blsgpu_ctx_reserve(blsgpu_ctx *ctx, size_t max_pairs);
  * is the sum (which also counts the fixed-base G1 table and the HD derivation slice, blsgpu_g1_mul_gen /
  * blsgpu_hd_children, the per-path state of blsgpu_hd_paths, the commitments of blsgpu_g1_poly_check and the Lagrange
  * coefficients of blsgpu_threshold_combine / blsgpu_fr_interpolate_at_zero, the table of blsgpu_g1_mul_gen_secret, the
- * point tables of blsgpu_g2_mul_secret / blsgpu_sign, the scalars and point copies of blsgpu_sign_threshold, and the leaves and
- * round buffers of blsgpu_sig_shares_check; they have no field of their own).
+ * point tables of blsgpu_g2_mul_secret / blsgpu_sign, the scalars and point copies of blsgpu_sign_threshold, the leaves and
+ * round buffers of blsgpu_sig_shares_check, and the keys blsgpu_keys_from_seeds holds back; they have no field of their own).
  * BLSGPU_WS_FLAGS_AND_LISTS counts the flag copy of blsgpu_miller_loop_batch's fast form as well (2 bytes per pair of a
  * slice).  No device call is made. */
 enum { BLSGPU_WS_PARTIALS = 0, BLSGPU_WS_STAGING, BLSGPU_WS_LINES, BLSGPU_WS_LINE_PRODUCTS, BLSGPU_WS_FLAGS_AND_LISTS,
@@ -382,6 +382,32 @@ int blsgpu_hd_paths_secret_dev(blsgpu_ctx *ctx, const void *d_parents, size_t n_
                                const void *d_indices, size_t depth, size_t n, void *d_out_chain, void *d_out_sk,
                                void *d_out_pk_aff, void *d_out_pk_ser, void *d_out_parent_fp, void *stream);
 
+/* Keys from seeds, n at once, one seed per lane (csrc/blsgpu_seeds.hip k_seed_keys): the first step of a key's life on the
+ * device, so that seeds -> masters -> leaves never visits the host.
+ *   hd == 0  PrivateKey.from_seed (keys.py:89-92 of the reference): sk = hmac256(seed, "BLS private key seed") mod n;
+ *            out_chain and out_parents must be NULL.
+ *   hd == 1  ExtendedPrivateKey.from_seed (keys.py:180-189): sk = hmac256(seed || 0x00, "BLS HD seed") mod n, chain code =
+ *            hmac256(seed || 0x01, "BLS HD seed"); the blocks that hold seed bytes alone are hashed once for both.
+ * seeds: n x seed_len bytes, 0 <= seed_len <= BLSGPU_SEED_MAX_BYTES, one length per call (seed_len == 0: seeds may be NULL;
+ * the reference accepts b"").  The midstates of the two fixed keys are public constants computed once on the host.
+ * Outputs, any of them NULL but not all: out_sk n x 32 bytes big-endian, canonical (below n); out_chain n x 32; out_pk_aff
+ * n x 96 and out_pk_ser n x 48 as blsgpu_g1_mul_gen_secret writes them, from k_fix_mul_secret reading the keys where
+ * k_seed_keys left them (no multiplication is launched when none of out_pk_aff, out_pk_ser, out_parents is asked for);
+ * out_parents n records of BLSGPU_HD_PARENT_BYTES (chain code, public key affine, private key), exactly what
+ * blsgpu_hd_paths_secret reads as `parents`.  Keys and affine public keys that the caller does not ask for but a later
+ * step needs lie in the workspace (counted in BLSGPU_WS_TOTAL).
+ * The claim and its limits are those of blsgpu_g1_mul_gen_secret: the sequence of instructions and of memory addresses does
+ * not depend on the seeds, digests or keys (i_left mod n keeps its subtractions by a mask).  It does depend on seed_len, n,
+ * hd and which outputs are asked for; timing inside the hardware is not claimed.
+ * -EINVAL before anything is written: seed_len above the limit; hd not 0 or 1; out_chain or out_parents given with hd == 0;
+ * and with n > 0: seeds NULL with seed_len > 0, all outputs NULL.  n == 0 writes nothing and returns 0. */
+#define BLSGPU_SEED_MAX_BYTES 1024
+int blsgpu_keys_from_seeds(blsgpu_ctx *ctx, const uint8_t *seeds, size_t seed_len, size_t n, int hd, uint8_t *out_sk,
+                           uint8_t *out_chain, uint8_t *out_pk_aff, uint8_t *out_pk_ser, uint8_t *out_parents);
+/* The same with every buffer in device memory, enqueued on `stream` (no synchronisation). */
+int blsgpu_keys_from_seeds_dev(blsgpu_ctx *ctx, const void *d_seeds, size_t seed_len, size_t n, int hd, void *d_out_sk,
+                               void *d_out_chain, void *d_out_pk_aff, void *d_out_pk_ser, void *d_out_parents, void *stream);
+
 /* Feldman share check (Threshold.verify_secret_fragment, threshold.py:104-125 of the reference) for n fragments at once.
  * commit: n_polys x t affine G1 points (96 B, (0,0) = infinity; caller guarantees on-curve);
  * poly: n uint32 polynomial indices; x, s: n x 32 B big-endian (any value < 2^256, reduced mod n on the device).
@@ -677,7 +703,9 @@ int blsgpu_aggregate_priv_keys_secure_dev(blsgpu_ctx *ctx, const void *d_sks, co
  * blsgpu_sign_threshold_dev, blsgpu_fr_sum_secret_dev, blsgpu_aggregate_priv_keys_secure_dev; the G1 / G2 halves of those
  * calls keep their kinds 9 and 8),
  * 11 = k_hash_pks_digest and 12 = k_hash_pks_exp (one record each per blsgpu_hash_pks_dev / blsgpu_aggregate_*_secure_dev
- * call; no record of kind 11 when the caller hands in the digests).
+ * call; no record of kind 11 when the caller hands in the digests),
+ * 13 = k_seed_keys (one record per slice of 2^20 seeds of blsgpu_keys_from_seeds_dev / per staged slice of the host form; the
+ * multiplication behind it keeps kind 9, the copy into the parent records has no record).
  * Reading resets the ring. */
 int blsgpu_timing_enable(blsgpu_ctx *ctx, int enable);
 int blsgpu_timing_read(blsgpu_ctx *ctx, float *ms, int *kind, size_t cap, size_t *count);

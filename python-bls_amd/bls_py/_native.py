@@ -88,6 +88,8 @@ PROTOTYPES = {
     "blsgpu_hd_paths_dev": (vp, vp, sz, ci, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp),
     "blsgpu_hd_paths_secret": (vp, cp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp),
     "blsgpu_hd_paths_secret_dev": (vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp),
+    "blsgpu_keys_from_seeds": (vp, cp, sz, sz, ci, vp, vp, vp, vp, vp),
+    "blsgpu_keys_from_seeds_dev": (vp, vp, sz, sz, ci, vp, vp, vp, vp, vp, vp),
     "blsgpu_g1_poly_check": (vp, cp, sz, sz, vp, cp, cp, sz, vp, vp),
     "blsgpu_g1_poly_check_dev": (vp, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp),
     "blsgpu_g1_subgroup_check": (vp, cp, sz, vp),
@@ -132,6 +134,7 @@ del vp, sz, cp, ci
 SYMBOLS = tuple(PROTOTYPES)
 
 HD_PARENT_BYTES = 160          # BLSGPU_HD_PARENT_BYTES: chain code (32), public key affine (96), private key (32)
+SEED_MAX_BYTES = 1024          # BLSGPU_SEED_MAX_BYTES: the longest seed blsgpu_keys_from_seeds takes
 LAGRANGE_MAX_K = 1024          # BLSGPU_LAGRANGE_MAX_K of include/blsgpu.h: players per group the device takes
 HASH_PKS_DEVICE_GROUPS = 64    # groups per call from which the device hashes the keys itself: below, one group per lane cannot
                                # fill a wavefront and the host's digest is handed in (pk_hash_in of include/blsgpu.h)

@@ -88,9 +88,34 @@ def use(provider):
     (32 bytes per group, status bytes), threshold_combine(sigs, x, k, groups) -> (affine bytes, [is_inf], status bytes).
     Optional (a provider without it sends Threshold.verify_sig_shares_batch to the exact per-share pairings):
     sig_shares_check(sigs, keys, key_idx, x|None, msg_hashes, weights, k, groups, scaled) -> (status bytes, session status
-    bytes, (rounds, node tests))."""
+    bytes, (rounds, node tests)).
+    Extensions are looked up by extension(name), not by hasattr: a stand-in offers one as an attribute of that name, the
+    HipProvider's come from EXTENSIONS.  Optional (without it PrivateKey.from_seed_batch and
+    ExtendedPrivateKey.from_seed_batch run the per-seed host calls): keys_from_seeds(seeds, seed_len, n, hd) -> (key bytes,
+    chain codes|None, affine bytes, serialised bytes, None) for n seeds of one length, at most 1024 bytes each, on the
+    device's one schedule, which does not depend on the seeds."""
     global _provider
     _provider = provider
+
+
+# What a HipProvider has beyond PROVIDER_METHODS: name -> the module of bls_py whose function of that name takes the
+# provider's engine first.
+EXTENSIONS = {"keys_from_seeds": "_native_seeds"}
+
+
+def extension(name):
+    """The installed provider's extension `name`: the provider's own attribute of that name if it has one (stand-ins), for
+    a HipProvider the function of EXTENSIONS bound to its engine, otherwise None."""
+    prov = get()
+    fn = getattr(prov, name, None)
+    if fn is not None:
+        return fn
+    if isinstance(prov, HipProvider) and name in EXTENSIONS:
+        import functools
+        import importlib
+        module = importlib.import_module("." + EXTENSIONS[name], __package__)
+        return functools.partial(getattr(module, name), prov._eng)
+    return None
 
 
 def get():

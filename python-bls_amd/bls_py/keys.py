@@ -13,7 +13,7 @@ from .ec import (JacobianPoint, default_ec, default_ec_twist, generator_Fq, hash
                  hash_to_point_prehashed_Fq2)
 from .fields import Fq
 from .signature import Signature
-from .util import hash256, hmac256
+from .util import _b, hash256, hmac256
 
 RNG = SystemRandom()
 
@@ -113,6 +113,23 @@ class PrivateKey:
     @staticmethod
     def from_seed(seed):
         return PrivateKey(int.from_bytes(hmac256(seed, b"BLS private key seed"), "big") % GROUP_ORDER)
+
+    @staticmethod
+    def from_seed_batch(seeds):
+        """[PrivateKey.from_seed(s) for s in seeds] with the HMACs, the reduction mod n and the public keys on the GPU
+        (blsgpu_keys_from_seeds): one call per distinct seed length, on a schedule that does not depend on the seeds, and
+        every key comes back with its public key (get_public_key costs nothing).  A str seed is UTF-8 encoded as from_seed
+        does.  Seeds longer than the device's limit, and every seed on a provider without the call, take from_seed."""
+        seeds = [bytes(_b(s)) for s in seeds]
+        out = []
+        for seed, rec in zip(seeds, _keys_from_seeds(seeds, False)):
+            if rec is None:
+                out.append(PrivateKey.from_seed(seed))
+                continue
+            sk = PrivateKey.from_bytes(rec[0])
+            sk.__dict__["_pk_point"] = _pk_from_device(rec[2], rec[3]).value
+            out.append(sk)
+        return out
 
     @staticmethod
     def new_threshold(T, N):
@@ -354,6 +371,28 @@ def _pk_from_device(aff, ser):
     return pk
 
 
+def _keys_from_seeds(seeds, hd):
+    """(key bytes, chain code|None, affine, serialised) per seed (bytes), in input order, from the provider's
+    keys_from_seeds extension -- the seeds bucketed by length, one device call per distinct length; None for a seed longer
+    than the device takes, and for every seed when the provider has no such extension"""
+    from . import backend
+    from ._native_seeds import SEED_MAX_BYTES
+    out = [None] * len(seeds)
+    fn = backend.extension("keys_from_seeds") if seeds else None
+    if fn is None:
+        return out
+    buckets = {}
+    for j, s in enumerate(seeds):
+        if len(s) <= SEED_MAX_BYTES:
+            buckets.setdefault(len(s), []).append(j)
+    for length, js in buckets.items():
+        sks, chain, aff, ser = fn(b"".join(seeds[j] for j in js), length, len(js), hd)[:4]
+        for t, j in enumerate(js):
+            out[j] = (sks[32 * t:32 * t + 32], chain[32 * t:32 * t + 32] if hd else None, aff[96 * t:96 * t + 96],
+                      ser[48 * t:48 * t + 48])
+    return out
+
+
 def _secret_call(name):
     """the provider's scalar-independent form `name`; a provider without it raises -- secret=True never falls back to the
     digit-indexed path"""
@@ -453,6 +492,27 @@ class ExtendedPrivateKey:
         sk_int = int.from_bytes(i_left, "big") % GROUP_ORDER
         sk = PrivateKey.from_bytes(sk_int.to_bytes(PrivateKey.PRIVATE_KEY_SIZE, "big"))
         return ExtendedPrivateKey(ExtendedPrivateKey.version, 0, 0, 0, i_right, sk)
+
+    @staticmethod
+    def from_seed_batch(seeds):
+        """[ExtendedPrivateKey.from_seed(s) for s in seeds] with both HMACs, the reduction mod n and the public keys on the
+        GPU (blsgpu_keys_from_seeds, hd form): one call per distinct seed length, on a schedule that does not depend on the
+        seeds.  Every master comes back with its public key, so private_paths_from(masters, ..., secret=True) starts without
+        a multiplication of its own.  A str seed raises TypeError as from_seed does (it concatenates bytes), before any
+        device work.  Seeds longer than the device's limit, and every seed on a provider without the call, take from_seed."""
+        seeds = [bytes(s + b"") for s in seeds]
+        out = []
+        for seed, rec in zip(seeds, _keys_from_seeds(seeds, True)):
+            if rec is None:
+                out.append(ExtendedPrivateKey.from_seed(seed))
+                continue
+            sk = PrivateKey.from_bytes(rec[0])
+            pk = _pk_from_device(rec[2], rec[3])
+            sk.__dict__["_pk_point"] = pk.value                 # the cache get_public_key fills (same point)
+            master = ExtendedPrivateKey(ExtendedPrivateKey.version, 0, 0, 0, rec[1], sk)
+            master.__dict__["_pk"] = pk
+            out.append(master)
+        return out
 
     def private_child(self, i):
         return self.private_child_batch([i])[0]

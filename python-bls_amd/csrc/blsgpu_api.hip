@@ -22,6 +22,7 @@
 #include "blsgpu_lsw.hip"
 #include "blsgpu_msm.hip"
 #include "blsgpu_g1fix.hip"
+#include "blsgpu_seeds.hip"
 #include "blsgpu_g1poly.hip"
 #include "blsgpu_subgroup.hip"
 #include "blsgpu_lagrange.hip"
@@ -678,6 +679,74 @@ int hd_paths_dev(blsgpu_ctx* c, const void* d_parents, size_t n_parents, int pri
         return 0;
     });
 }
+// ------------------------------------------------------------ keys from seeds (blsgpu_seeds.hip) --
+constexpr size_t SEED_SLICE = (size_t)1 << 20;         // seeds per launch of the _dev form (<= 128 MB of workspace)
+
+// the midstates of the two fixed keys (public constants), computed once: [0] "BLS private key seed", [1] "BLS HD seed"
+const hdk::HmacKey& seed_key(int hd) {
+    static const struct Keys {
+        hdk::HmacKey k[2];
+        Keys() {
+            hdk::hmac_key((const uint8_t*)"BLS private key seed", 20, k[0]);
+            hdk::hmac_key((const uint8_t*)"BLS HD seed", 11, k[1]);
+        }
+    } keys;
+    return keys.k[hd];
+}
+
+// blsgpu_keys_from_seeds*: the arguments every form checks before anything is written; 1: nothing to do
+int seeds_args(const blsgpu_ctx* c, const void* seeds, size_t seed_len, size_t n, int hd, const void* sk, const void* chain, const void* aff,
+               const void* ser, const void* parents) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (hd != 0 && hd != 1) return fail(-EINVAL, "hd must be 0 or 1");
+    if (seed_len > BLSGPU_SEED_MAX_BYTES) return fail(-EINVAL, "seeds are at most BLSGPU_SEED_MAX_BYTES bytes");
+    if (!hd && (chain || parents)) return fail(-EINVAL, "out_chain and out_parents belong to hd = 1");
+    if (n == 0) return 1;
+    if (!seeds && seed_len) return fail(-EINVAL, "NULL seed buffer");
+    if (!sk && !chain && !aff && !ser && !parents) return fail(-EINVAL, "ask for at least one output");
+    if (n > 0xFFFFFFFFull) return fail(-EINVAL, "batch too large");
+    return 0;
+}
+
+// n keys from n seeds of seed_len bytes on `st`, every buffer in device memory (caller: seeds_args): per slice k_seed_keys
+// (timing kind 13), then -- when a public key is asked for -- k_fix_mul_secret on the keys where k_seed_keys left them (the
+// caller's out_sk or B_SEED_WS) and k_seed_pack_aff for the records.  B_SEED_WS: [0, S x 32) the keys when out_sk is NULL,
+// then S x 96 the affine keys when the records need them and out_pk_aff is NULL.
+int keys_from_seeds_dev(blsgpu_ctx* c, const void* d_seeds, size_t seed_len, size_t n, int hd, void* d_sk, void* d_chain, void* d_pk_aff,
+                        void* d_pk_ser, void* d_parents, hipStream_t st) {
+    using namespace blsgpu::seeds;
+    StreamGuard sg(c, st);
+    const bool pk = d_pk_aff || d_pk_ser || d_parents;
+    const size_t S = n < SEED_SLICE ? n : SEED_SLICE;
+    const size_t ws_sk = d_sk ? 0 : S * 32, ws_aff = d_parents && !d_pk_aff ? S * 96 : 0;
+    if (ws_sk + ws_aff) {
+        if (int rc = c->grow(B_SEED_WS, ws_sk + ws_aff)) return rc;
+    }
+    if (pk) {
+        if (int rc = fix_table(c, st, true)) return rc;
+    }
+    char* ws = c->at<char>(B_SEED_WS);
+    return for_slices(n, S, [&](size_t lo, size_t m) {
+        uint32_t* sk = d_sk ? (uint32_t*)d_sk + lo * 8 : (uint32_t*)ws;
+        uint32_t* par = d_parents ? (uint32_t*)d_parents + lo * PARENT_DW : nullptr;
+        {
+            KernelTimer kt(c, st, 13);
+            hipLaunchKernelGGL(k_seed_keys, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, seed_key(hd),
+                               (const uint8_t*)d_seeds + lo * seed_len, (uint32_t)seed_len, (uint32_t)m, (uint32_t)hd, sk,
+                               d_chain ? (uint32_t*)d_chain + lo * 8 : nullptr, par);
+            HIP_TRY(hipGetLastError());
+        }
+        if (!pk) return 0;
+        uint32_t* aff = d_pk_aff ? (uint32_t*)d_pk_aff + lo * 24 : (par ? (uint32_t*)(ws + ws_sk) : nullptr);
+        if (int rc = fix_mul_secret_launch(c, sk, m, aff, d_pk_ser ? (char*)d_pk_ser + lo * 48 : nullptr, st)) return rc;
+        if (par) {
+            hipLaunchKernelGGL(k_seed_pack_aff, dim3((unsigned)((m * 24 + 255) / 256)), dim3(256), 0, st, (const uint32_t*)aff, (uint32_t)m, par);
+            HIP_TRY(hipGetLastError());
+        }
+        return 0;
+    });
+}
+
 // ------------------------------------------------------------ Feldman share checks (blsgpu_g1poly.hip) --
 // the arguments every form checks before anything is written (after t == 0 and n == 0)
 int poly_args(size_t n_polys, size_t t, const void* commit, const void* poly, const void* x, const void* s, const void* status,
@@ -2534,6 +2603,34 @@ BLSGPU_EXPORT int blsgpu_hd_paths_secret_dev(blsgpu_ctx* c, const void* d_parent
     HIP_TRY(hipSetDevice(c->device));
     return hd_paths_dev(c, d_parents, n_parents, 1, d_parent_of, d_indices, depth, n, d_out_chain, d_out_sk, d_out_pk_aff, d_out_pk_ser,
                         d_out_parent_fp, true, (hipStream_t)stream, true);
+}
+
+// ------------------------------------------------------------ keys from seeds --
+BLSGPU_EXPORT int blsgpu_keys_from_seeds_dev(blsgpu_ctx* c, const void* d_seeds, size_t seed_len, size_t n, int hd, void* d_out_sk,
+                                             void* d_out_chain, void* d_out_pk_aff, void* d_out_pk_ser, void* d_out_parents, void* stream) {
+    if (int rc = seeds_args(c, d_seeds, seed_len, n, hd, d_out_sk, d_out_chain, d_out_pk_aff, d_out_pk_ser, d_out_parents)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return keys_from_seeds_dev(c, d_seeds, seed_len, n, hd, d_out_sk, d_out_chain, d_out_pk_aff, d_out_pk_ser, d_out_parents,
+                               (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_keys_from_seeds(blsgpu_ctx* c, const uint8_t* seeds, size_t seed_len, size_t n, int hd, uint8_t* out_sk,
+                                         uint8_t* out_chain, uint8_t* out_pk_aff, uint8_t* out_pk_ser, uint8_t* out_parents) {
+    if (int rc = seeds_args(c, seeds, seed_len, n, hd, out_sk, out_chain, out_pk_aff, out_pk_ser, out_parents)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    // about 64 MB of staging per slice
+    const size_t fit = ((size_t)1 << 26) / (seed_len + 368);
+    const size_t S = n < fit ? n : fit;
+    Staging s(c);
+    const int dseed = s.in(seed_len ? seeds : nullptr, S, seed_len), dsk = s.out(out_sk, S, 32), dchain = s.out(out_chain, S, 32),
+              daff = s.out(out_pk_aff, S, 96), dser = s.out(out_pk_ser, S, 48), dpar = s.out(out_parents, S, BLSGPU_HD_PARENT_BYTES);
+    if (int rc = s.alloc()) return rc;
+    return for_slices(n, S, [&](size_t lo, size_t m) {
+        if (int rc = s.up(lo, m)) return rc;
+        if (int rc = keys_from_seeds_dev(c, s.opt(dseed), seed_len, m, hd, s.opt(dsk), s.opt(dchain), s.opt(daff), s.opt(dser), s.opt(dpar),
+                                         nullptr))
+            return rc;
+        return s.down(lo, m);
+    });
 }
 
 // ------------------------------------------------------------ Feldman share checks --

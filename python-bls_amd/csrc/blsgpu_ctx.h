@@ -64,6 +64,7 @@ enum BufId {
     B_HPK_WS,            // blsgpu_hash_pks* / blsgpu_aggregate_*_secure*: groups digests (32 bytes each), then groups x m exponents (32 bytes each)
     B_SHR_WS,            // blsgpu_sig_shares_check*: what one slice of sessions keeps over its rounds -- a flag word, the subgroup flags, H(m), the scalars r and w, the key copies and the leaves A, B
     B_SHR_ROUND,         // ... and what one round of it takes: the node table, the gathered leaves, the node sums, the pairs, the pairing results and the verdict bytes
+    B_SEED_WS,           // blsgpu_keys_from_seeds*: one slice of the keys (32 bytes each) and of their affine public keys (96) where the caller does not ask for them
     B_COUNT
 };
 // (unit: what the buffer is counted in -- whole partials, whole u32 entries, bytes)
@@ -72,7 +73,7 @@ constexpr BufInfo BUF_INFO[B_COUNT] = {
     {BLSGPU_WS_PARTIALS, BLSGPU_FQ12_BYTES}, {BLSGPU_WS_PARTIALS, BLSGPU_FQ12_BYTES}, {BLSGPU_WS_STAGING, 1}, {BLSGPU_WS_LINES, 1},
     {BLSGPU_WS_LINE_PRODUCTS, 1}, {BLSGPU_WS_LINE_PRODUCTS, 1}, {BLSGPU_WS_FLAGS_AND_LISTS, 1}, {BLSGPU_WS_FLAGS_AND_LISTS, 4},
     {BLSGPU_WS_FLAGS_AND_LISTS, 1}, {BLSGPU_WS_GROUP_SUMS, 4}, {BLSGPU_WS_GROUP_SUMS, 4}, {BLSGPU_WS_SLOTS, 1}, {BLSGPU_WS_SLOTS, 1},
-    {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}};   // no field of their own: they count in the total only
+    {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}};   // no field of their own: they count in the total only
 
 }  // namespace
 

@@ -10,7 +10,8 @@
 // After them a message of at most 55 bytes is one padded block, and the outer hash of the 32-byte inner digest one more:
 // two compressions per HMAC, four per child.  A PATH (blsgpu_hd_paths: one path per lane, a parent of its own) changes its
 // chain code level by level, so there the midstates are per lane and per level -- hmac_key_words, six compressions per
-// level -- and the parent fingerprint of the leaf is one more (fingerprint).
+// level -- and the parent fingerprint of the leaf is one more (fingerprint).  A SEED (blsgpu_keys_from_seeds, blsgpu_seeds.hip:
+// one seed per lane) is a message of any length under a fixed key: hmac_long / hmac_long_pair (tests/test_seeds_host.py).
 #pragma once
 #include <stdint.h>
 
@@ -144,6 +145,77 @@ HD_FN uint32_t fingerprint(const uint32_t ser[12]) {
     w[15] = 48 * 8;
     sha256_compress(st, w);
     return st[0];
+}
+
+// ---- seeds: HMAC of a message of any length (PrivateKey.from_seed / ExtendedPrivateKey.from_seed, keys.py:89-92 and 180-189
+// of the reference) --------------------------------------------------------------------------------------------------------
+// The message is m[0 .. len) followed, when suffix >= 0, by the one byte `suffix`: M = len or len + 1 bytes behind the key
+// block.  Standard padding: the 0x80 byte at M, zeros, the bit length (64 + M) * 8 in the last word -- (M + 8) / 64 + 1 blocks.
+// Nothing below branches on a message byte or forms an address from one: block counts and byte positions follow from len
+// and from whether there is a suffix.  m is read at p < len only (len == 0: never, m may be NULL).
+HD_FN uint32_t long_blocks(uint32_t len, int suffix) { return (len + (suffix >= 0 ? 1u : 0u) + 8u) / 64u + 1u; }
+
+// the big-endian word at byte offset off (a multiple of 4) of the padded message without its length field
+HD_FN uint32_t long_word(const uint8_t* m, uint32_t len, uint32_t M, uint32_t suffix, uint32_t off) {
+    uint32_t v = 0;
+#pragma unroll
+    for (uint32_t b = 0; b < 4; b++) {
+        const uint32_t p = off + b;
+        uint32_t byte = 0;
+        if (p < len) byte = m[p];
+        else if (p < M) byte = suffix;                          // p == len: the suffix byte
+        else if (p == M) byte = 0x80u;
+        v = (v << 8) | byte;
+    }
+    return v;
+}
+
+// The inner state after the len / 64 blocks that hold message bytes alone -- the same whatever follows the message, so the
+// two HMACs of a seed (suffix 0 and 1) share it.
+HD_FN void hmac_long_prefix(const HmacKey& k, const uint8_t* m, uint32_t len, uint32_t in[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; j++) in[j] = k.ipad[j];
+    for (uint32_t b = 0; b < len / 64u; b++) {
+        uint32_t w[16];
+#pragma unroll
+        for (uint32_t j = 0; j < 16; j++) w[j] = long_word(m, len, len, 0u, 64u * b + 4u * j);
+        sha256_compress(in, w);
+    }
+}
+
+// From hmac_long_prefix's state `in`: the one or two blocks that are left (the message's last len % 64 bytes, the suffix,
+// the padding), then the outer hash.  out: the digest as 8 big-endian words.
+HD_FN void hmac_long_finish(const HmacKey& k, const uint32_t in[8], const uint8_t* m, uint32_t len, int suffix, uint32_t out[8]) {
+    const uint32_t M = len + (suffix >= 0 ? 1u : 0u), blocks = long_blocks(len, suffix);
+    uint32_t st[8], w[16];
+#pragma unroll
+    for (int j = 0; j < 8; j++) st[j] = in[j];
+    for (uint32_t b = len / 64u; b < blocks; b++) {
+#pragma unroll
+        for (uint32_t j = 0; j < 16; j++) w[j] = long_word(m, len, M, (uint32_t)suffix & 0xffu, 64u * b + 4u * j);
+        if (b + 1u == blocks) w[15] = (64u + M) * 8u;           // (the 0x80 byte lies at least nine bytes before the end)
+        sha256_compress(st, w);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++) { w[j] = st[j]; w[j + 8] = 0; out[j] = k.opad[j]; }
+    w[8] = 0x80000000u;
+    w[15] = (64 + 32) * 8;
+    sha256_compress(out, w);
+}
+
+// HMAC-SHA256 under the midstates k of m[0 .. len) (suffix < 0) or of m[0 .. len) || suffix
+HD_FN void hmac_long(const HmacKey& k, const uint8_t* m, uint32_t len, int suffix, uint32_t out[8]) {
+    uint32_t in[8];
+    hmac_long_prefix(k, m, len, in);
+    hmac_long_finish(k, in, m, len, suffix, out);
+}
+
+// The two HMACs of ExtendedPrivateKey.from_seed: i_left of m || 0x00, i_right of m || 0x01, the shared blocks hashed once
+HD_FN void hmac_long_pair(const HmacKey& k, const uint8_t* m, uint32_t len, uint32_t i_left[8], uint32_t i_right[8]) {
+    uint32_t in[8];
+    hmac_long_prefix(k, m, len, in);
+    hmac_long_finish(k, in, m, len, 0, i_left);
+    hmac_long_finish(k, in, m, len, 1, i_right);
 }
 
 // ---- scalars mod n (the order of G1): 8 little-endian words -----------------------------------------------------------
