@@ -516,6 +516,63 @@ int blsgpu_sig_shares_check_dev(blsgpu_ctx *ctx, const void *d_sigs, const void 
                                 const void *d_x, const void *d_msg_hashes, const void *d_weights, int scaled, size_t k,
                                 size_t groups, void *d_status, void *d_session_status, uint64_t *stats, void *stream);
 
+/* Multiplication by SHORT PUBLIC scalars:  out_i = w_i P_i  for 64-bit weights (csrc/blsgpu_smul64.hip k_smul64;
+ * vmgen/smul64_model.py is its specification).  pts: n x 96 (G1) / n x 192 (G2) bytes affine, (0,0) = infinity; w: n x 8 bytes
+ * big-endian; out_aff: n points likewise, (0,0) for infinity; out_inf (may be NULL): n flags, 1 for infinity.  w = 0 gives
+ * infinity.  One point per lane (G1) or lane pair (G2), 4-bit windows from the top: 16 windows -- 60 doublings and 16
+ * additions against the 252 and 64 that blsgpu_g1_msm / blsgpu_g2_msm(k = 1, groups = n) spend on the same weight zero-extended
+ * to 32 bytes, whose result bytes this call reproduces byte for byte for every input those calls accept.  The weights are
+ * PUBLIC data: the schedule reads a table entry the digit chooses and is NOT scalar-independent (secret scalars:
+ * blsgpu_g2_mul_secret, blsgpu_g1_mul_gen_secret).  A launch takes 131 072 G1 / 65 536 G2 points, which bounds the table
+ * workspace at 352 MB (counted in BLSGPU_WS_TOTAL).  n == 0 writes nothing and returns 0; a NULL required buffer is -EINVAL
+ * before anything is written. */
+int blsgpu_g1_mul_short(blsgpu_ctx *ctx, const uint8_t *pts, const uint8_t *w, size_t n, uint8_t *out_aff, uint8_t *out_inf);
+int blsgpu_g2_mul_short(blsgpu_ctx *ctx, const uint8_t *pts, const uint8_t *w, size_t n, uint8_t *out_aff, uint8_t *out_inf);
+/* The same with every buffer in device memory (points 16-byte aligned), enqueued on `stream` (no synchronisation). */
+int blsgpu_g1_mul_short_dev(blsgpu_ctx *ctx, const void *d_pts, const void *d_w, size_t n, void *d_out_aff, void *d_out_inf,
+                            void *stream);
+int blsgpu_g2_mul_short_dev(blsgpu_ctx *ctx, const void *d_pts, const void *d_w, size_t n, void *d_out_aff, void *d_out_inf,
+                            void *stream);
+
+/* Batch verification that NAMES the forgeries (csrc/blsgpu_batchfind.hip): n signatures with their own keys and messages,
+ * all of them checked by one random linear combination and only what fails bisected.  Item i is (sig_i,
+ * P_i = keys[key_idx[i]], h_i = msg_hashes[msg_idx[i]]); it is VALID iff e(G1, sig_i) = e(P_i, H(h_i)),
+ * H = hash_to_point_prehashed_Fq2 (ec.py:528-550 of the reference).
+ * sigs: n x 192 bytes affine G2, (0,0) = infinity.  keys: n_keys x 96 bytes affine G1; key_idx: n uint32 into keys.
+ * msg_hashes: n_msgs x 32 bytes; msg_idx: n uint32 into them -- a hash is mapped to G2 ONCE however many items name it.
+ * weights: n x 8 bytes big-endian, the random 64-bit multipliers r_i, drawn by the CALLER (unpredictable to whoever made the
+ * signatures); a ZERO weight is taken as 1 on the device.
+ * status: n bytes -- 1 valid; 0 invalid, which includes a signature off the twist, outside G2 or at infinity (whatever its
+ * key); 2 not decided: the key is off the curve, outside G1 or at infinity, or H(h) is at infinity.  stats (HOST memory in
+ * both forms, may be NULL): [0] the rounds run, summed over the slices of the call, [1] the node tests, [2] the pairs fed to
+ * the pairing by those tests.
+ * Once per call: k_g1_subgroup over the key table, k_g2_subgroup over the signatures, H of the n_msgs hashes, k_find_settle
+ * (the items that cannot enter a sum get their status; the others are ELIGIBLE), the dense order of the n_e eligible items
+ * (input order kept; the host reads n_e: one synchronisation), and the leaves A_i = r_i sig_i, B_i = r_i P_i from k_smul64.
+ * Then rounds over aligned NODES (offset, length L) of the dense order, L from K = 2^ceil(log2 n_e) halving: a node's test is
+ * e(-G1, S) prod_(i in node) e(B_i, H(h_i)) = 1 with S = sum A_i from the plain G2 group sum; the full nodes of a round go
+ * through one blsgpu_pairing_multi_batch_dev of L + 1 pairs each, the one node that crosses n_e through a call of its own size
+ * (no flagged pair pads it), a node wholly past n_e is not tested.  A sum at infinity is never fed to the pairing: a node with
+ * S = O carries (-G1, G2) in that place and its result is compared with e(-G1, G2) (computed by the pairing once per context),
+ * so it is decided by prod e(B_i, H(h_i)) = 1 alone; B_i and H(h_i) of an eligible item are never at infinity, nor is a leaf's
+ * S.  The host reads ONE byte per node and round, halves the nodes that failed -- both halves are tested -- and in the round
+ * L = 1 the verdict is the item's status: at most log2 K + 1 rounds, one stream synchronisation each; the calls are NOT
+ * asynchronous.  One forgery costs at most 1 + 2 log2 K node tests.  Items are processed in slices that keep the leaves, and
+ * the largest round, below 2 GB each (counted in BLSGPU_WS_TOTAL).
+ * What is claimed: a failing leaf test is exact (0 < r_i < 2^64 is not 0 mod n); a node that passes although it holds an
+ * invalid eligible item does so with probability at most 2^-64 over the weights, per node.  Nothing stronger.
+ * -EINVAL before anything is written: a NULL required buffer, n_keys == 0 or n_msgs == 0 with n > 0, a key_idx >= n_keys or a
+ * msg_idx >= n_msgs.  n == 0 writes nothing and returns 0.  All of this is PUBLIC data: not constant-time. */
+int blsgpu_verify_find(blsgpu_ctx *ctx, const uint8_t *sigs, const uint8_t *keys, size_t n_keys, const uint32_t *key_idx,
+                       const uint8_t *msg_hashes, size_t n_msgs, const uint32_t *msg_idx, const uint8_t *weights, size_t n,
+                       uint8_t *status, uint64_t *stats);
+/* The same with every buffer but stats in device memory (16-byte aligned where it holds points, 4-byte otherwise), on
+ * `stream`.  The indices are first scanned on the device and the stream is synchronised once to read the result of that
+ * check; then once for n_e and once per round. */
+int blsgpu_verify_find_dev(blsgpu_ctx *ctx, const void *d_sigs, const void *d_keys, size_t n_keys, const void *d_key_idx,
+                           const void *d_msg_hashes, size_t n_msgs, const void *d_msg_idx, const void *d_weights, size_t n,
+                           void *d_status, uint64_t *stats, void *stream);
+
 /* G2 scalar multiplication for SECRET scalars:  out_i = s_i P_(n_pts == 1 ? 0 : i)  with a schedule independent of s
  * (csrc/blsgpu_g2smul.hip k_g2_smul; vmgen/g2smul_model.py is its specification).  s_i is the literal 256-bit integer of
  * 32 big-endian bytes, NOT reduced mod the group order -- exactly the `scalars` of blsgpu_g2_msm, whose results this call

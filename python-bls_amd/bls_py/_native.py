@@ -104,6 +104,12 @@ PROTOTYPES = {
     "blsgpu_threshold_combine_dev": (vp, vp, vp, sz, sz, vp, vp, vp, vp),
     "blsgpu_sig_shares_check": (vp, cp, cp, sz, vp, cp, cp, cp, ci, sz, sz, vp, vp, vp),
     "blsgpu_sig_shares_check_dev": (vp, vp, vp, sz, vp, vp, vp, vp, ci, sz, sz, vp, vp, vp, vp),
+    "blsgpu_g1_mul_short": (vp, cp, cp, sz, vp, vp),
+    "blsgpu_g2_mul_short": (vp, cp, cp, sz, vp, vp),
+    "blsgpu_g1_mul_short_dev": (vp, vp, vp, sz, vp, vp, vp),
+    "blsgpu_g2_mul_short_dev": (vp, vp, vp, sz, vp, vp, vp),
+    "blsgpu_verify_find": (vp, cp, cp, sz, vp, cp, sz, vp, cp, sz, vp, vp),
+    "blsgpu_verify_find_dev": (vp, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, vp),
     "blsgpu_g2_mul_secret": (vp, cp, sz, cp, sz, vp, vp, vp),
     "blsgpu_g2_mul_secret_dev": (vp, vp, sz, vp, sz, vp, vp, vp, vp),
     "blsgpu_sign": (vp, cp, cp, sz, sz, vp, vp),

@@ -89,6 +89,9 @@ def use(provider):
     Optional (a provider without it sends Threshold.verify_sig_shares_batch to the exact per-share pairings):
     sig_shares_check(sigs, keys, key_idx, x|None, msg_hashes, weights, k, groups, scaled) -> (status bytes, session status
     bytes, (rounds, node tests)).
+    Optional extension (without it BLS.verify_batch_find sends everything to verify_batch): verify_find(sigs, keys, key_idx,
+    msg_hashes, msg_idx, weights) -> (status bytes, (rounds, node tests, pairs)); with it g1_mul_short / g2_mul_short(pts,
+    weights) -> (affine bytes, [is_inf]) for 64-bit public weights.
     Extensions are looked up by extension(name), not by hasattr: a stand-in offers one as an attribute of that name, the
     HipProvider's come from EXTENSIONS.  Optional (without it PrivateKey.from_seed_batch and
     ExtendedPrivateKey.from_seed_batch run the per-seed host calls): keys_from_seeds(seeds, seed_len, n, hd) -> (key bytes,
@@ -101,6 +104,9 @@ def use(provider):
 # What a HipProvider has beyond PROVIDER_METHODS: name -> the module of bls_py whose function of that name takes the
 # provider's engine first.
 EXTENSIONS = {"keys_from_seeds": "_native_seeds"}
+# ... and the calls on short public scalars and the batch verification that names the forgeries (BLS.verify_batch_find), looked
+# up by extension(name) in the same way.
+FIND_EXTENSIONS = {"g1_mul_short": "_native_find", "g2_mul_short": "_native_find", "verify_find": "_native_find"}
 
 
 def extension(name):
@@ -110,10 +116,11 @@ def extension(name):
     fn = getattr(prov, name, None)
     if fn is not None:
         return fn
-    if isinstance(prov, HipProvider) and name in EXTENSIONS:
+    where = EXTENSIONS.get(name) or FIND_EXTENSIONS.get(name)
+    if isinstance(prov, HipProvider) and where:
         import functools
         import importlib
-        module = importlib.import_module("." + EXTENSIONS[name], __package__)
+        module = importlib.import_module("." + where, __package__)
         return functools.partial(getattr(module, name), prov._eng)
     return None
 

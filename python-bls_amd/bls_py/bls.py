@@ -318,6 +318,82 @@ class BLS:
         return results
 
     @staticmethod
+    def verify_batch_find(signatures, rng=None):
+        """verify_batch(signatures) with the forgeries NAMED on the device (blsgpu_verify_find): every signature over exactly
+        one 32-byte message hash is an item (signature, key, message) of one call that checks all items by a random linear
+        combination and bisects only what fails -- one forgery among n costs about 2 log2 n node tests, not n pairings.  The
+        item's key is the signature's one key when its exponent is 1, otherwise the per-message key sum sum_j e_j pk_j (one
+        grouped G1 sum, every contributing key checked for G1 membership first); keys and message hashes are deduplicated
+        into the call's two tables.  The weights are rng.getrandbits(64), redrawn while zero, in the order of the list
+        (default secrets.SystemRandom()).  Status 1 is True and 0 False; every other signature -- several messages, status 2
+        (a key or key sum outside G1 or at infinity, H(m) at infinity), a tree without one of its keys, an infinity signature,
+        a provider without the verify_find extension -- is decided by verify_batch in the same call.  The answers equal verify_batch's
+        except that an invalid item is reported True with probability at most 2^-64 per node that holds it (DESIGN.md
+        section 2u)."""
+        prov = backend.get()
+        rng = rng or secrets.SystemRandom()
+        results = [None] * len(signatures)
+        plans = []                                        # (index, message hashes, key groups (PublicKey), exponent groups)
+        for i, sig in enumerate(signatures):
+            info = sig.aggregation_info
+            by_message = {}
+            for mh, pk in zip(info.message_hashes, info.public_keys):
+                by_message.setdefault(mh, []).append(pk)
+            kg, eg = [], []
+            try:
+                for mh, keys in by_message.items():
+                    uniq = list(set(keys))
+                    eg.append([info.tree[(mh, pk)] for pk in uniq])
+                    kg.append(uniq)
+            except KeyError:
+                results[i] = False                        # bls.py:189-190
+                continue
+            plans.append((i, list(by_message), kg, eg))
+        items = []
+        find = backend.extension("verify_find")
+        if find is not None:
+            items = [p for p in plans if not signatures[p[0]].value.infinity and len(p[1]) == 1 and len(p[1][0]) == 32]
+
+        # the item's key: the one key itself, or the key sum of keys that are all in G1
+        def single(p):
+            return len(p[2][0]) == 1 and int(p[3][0][0]) % GROUP_ORDER == 1
+        key_bytes = {}
+        for p in items:
+            for pk in p[2][0]:
+                if pk not in key_bytes:
+                    key_bytes[pk] = _jac_g1_bytes(pk.value)
+        summed = [p for p in items if not single(p)]
+        if summed:
+            contributing = list(dict.fromkeys(pk for p in summed for pk in p[2][0]))
+            st = prov.g1_subgroup(b"".join(key_bytes[pk] for pk in contributing))
+            in_g1 = {pk: st[j] == 1 for j, pk in enumerate(contributing)}
+            bad = {p[0] for p in summed if not all(in_g1[pk] for pk in p[2][0])}
+            items = [p for p in items if p[0] not in bad]
+            summed = [p for p in summed if p[0] not in bad]
+        sums = iter(_g1_group_sums(prov, [[(key_bytes[pk], int(e) % GROUP_ORDER) for pk, e in zip(p[2][0], p[3][0])] for p in summed]))
+
+        if items:
+            keys, msgs, key_idx, msg_idx, sigs, weights = {}, {}, [], [], [], []
+            for p in items:
+                kb = key_bytes[p[2][0][0]] if single(p) else next(sums)[0]
+                key_idx.append(keys.setdefault(kb, len(keys)))
+                msg_idx.append(msgs.setdefault(p[1][0], len(msgs)))
+                sigs.append(H.g2_affine_bytes(signatures[p[0]].value.to_affine()._aff()))
+                x = 0
+                while x == 0:
+                    x = rng.getrandbits(64)
+                weights.append(x)
+            status, _ = find(b"".join(sigs), b"".join(keys), key_idx, b"".join(msgs), msg_idx, weights)
+            for p, s in zip(items, status):
+                if s != 2:
+                    results[p[0]] = s == 1
+        rest = [p[0] for p in plans if results[p[0]] is None]
+        if rest:
+            for i, v in zip(rest, BLS.verify_batch([signatures[i] for i in rest])):
+                results[i] = v
+        return results
+
+    @staticmethod
     def aggregate_pub_keys(public_keys, secure):
         if len(public_keys) < 1:
             raise Exception("Invalid number of keys")

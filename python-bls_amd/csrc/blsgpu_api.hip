@@ -29,7 +29,9 @@
 #include "blsgpu_frsecret.hip"
 #include "blsgpu_hashpks.hip"
 #include "blsgpu_sigshares.hip"
+#include "blsgpu_batchfind.hip"
 #include "blsgpu_g2smul.hip"
+#include "blsgpu_smul64.hip"
 #include "blsgpu_h2c.hip"
 #include "blsgpu_h2cw.hip"
 #include "blsgpu_msmw.hip"
@@ -1036,6 +1038,237 @@ int sig_shares_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_t
     if (stats) {
         stats[0] = rounds;
         stats[1] = tests;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------ short public scalars (blsgpu_smul64.hip) --
+// enqueues out_i = w_i P_(d_idx ? idx[i] : i) on `st` for n 64-bit weights (caller: StreamGuard, arguments checked, idx in
+// range): launches of at most SRT_LANES / LP units, each with tables of its own in B_SM64_WS.  With d_idx the n_pts points are
+// prepared once and every launch indexes them; without, a launch prepares its own points.
+template <int DEG>
+int smul64_launch(blsgpu_ctx* c, const void* d_pts, size_t n_pts, const void* d_idx, const void* d_w, size_t n, void* d_out, void* d_out_inf,
+                  hipStream_t st) {
+    typedef blsgpu::SrtG<DEG> G;
+    const size_t upw = 64 / G::LP, S = blsgpu::SRT_LANES / G::LP;
+    const size_t m0 = n < S ? n : S, units0 = (m0 + upw - 1) / upw * upw, np0 = d_idx ? n_pts : m0;
+    size_t off = 0;
+    auto take = [&](size_t words) { size_t o = off; off += (words + 3) & ~(size_t)3; return o; };
+    const size_t o_prep = take(np0 * blsgpu::L28_AFF * DEG), o_live = take((np0 + 3) / 4), o_tab = take(units0 * blsgpu::SMUL_T * G::PJ);
+    if (int rc = c->grow(B_SM64_WS, off * 4)) return rc;
+    uint32_t* W = c->at<uint32_t>(B_SM64_WS);
+    uint8_t* live = (uint8_t*)(W + o_live);
+    if (d_idx) {
+        hipLaunchKernelGGL(blsgpu::k_lane_prep<DEG>, dim3((unsigned)((n_pts + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_pts, (uint32_t)n_pts,
+                           W + o_prep, live);
+        HIP_TRY(hipGetLastError());
+    }
+    return for_slices(n, S, [&](size_t lo, size_t m) {
+        if (!d_idx)
+            hipLaunchKernelGGL(blsgpu::k_lane_prep<DEG>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_pts + lo * 24 * DEG,
+                               (uint32_t)m, W + o_prep, live);
+        const size_t units = (m + upw - 1) / upw * upw;
+        hipLaunchKernelGGL(blsgpu::k_smul64<DEG>, dim3((unsigned)(units * G::LP / 64)), dim3(64), 0, st, W + o_prep, live,
+                           d_idx ? (const uint32_t*)d_idx + lo : nullptr, (const uint8_t*)d_w + lo * 8, (uint32_t)m, W + o_tab,
+                           (uint32_t*)d_out + lo * 24 * DEG, d_out_inf ? (uint8_t*)d_out_inf + lo : nullptr);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    });
+}
+// the argument checks of blsgpu_g?_mul_short* (before anything is written); 1: nothing to do
+int mul_short_args(const blsgpu_ctx* c, const void* pts, const void* w, size_t n, const void* out) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (n == 0) return 1;
+    if (!pts || !w || !out) return fail(-EINVAL, "NULL argument");
+    if (n > 0x7FFFFFFFull) return fail(-EINVAL, "batch too large");
+    return 0;
+}
+template <int DEG>
+int mul_short_dev(blsgpu_ctx* c, const void* d_pts, const void* d_w, size_t n, void* d_out, void* d_out_inf, hipStream_t st) {
+    if (int rc = mul_short_args(c, d_pts, d_w, n, d_out)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    StreamGuard sg(c, st);
+    return smul64_launch<DEG>(c, d_pts, n, nullptr, d_w, n, d_out, d_out_inf, st);
+}
+// the host-buffer form: FIX_HOST_SLICE points per staged slice
+template <int DEG>
+int mul_short_host(blsgpu_ctx* c, const uint8_t* pts, const uint8_t* w, size_t n, uint8_t* out, uint8_t* out_inf) {
+    if (int rc = mul_short_args(c, pts, w, n, out)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE;
+    Staging s(c);
+    const int dp = s.in(pts, S, 96 * DEG), dw = s.in(w, S, 8), dout = s.out(out, S, 96 * DEG), dinf = s.out(out_inf, S, 1);
+    if (int rc = s.alloc()) return rc;
+    return for_slices(n, S, [&](size_t lo, size_t m) {
+        if (int rc = s.up(lo, m)) return rc;
+        {
+            StreamGuard sg(c, nullptr);
+            if (int rc = smul64_launch<DEG>(c, s.at(dp), m, nullptr, s.at(dw), m, s.at(dout), s.opt(dinf), nullptr)) return rc;
+        }
+        return s.down(lo, m);
+    });
+}
+
+// ------------------------------------------------------------ batch verification that names the forgeries (blsgpu_batchfind.hip) --
+// the argument checks of blsgpu_verify_find* (before anything is written); 1: nothing to do
+int verify_find_args(const blsgpu_ctx* c, size_t n, size_t n_keys, size_t n_msgs, bool null_buffer) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (n == 0) return 1;
+    if (null_buffer) return fail(-EINVAL, "NULL argument");
+    if (n_keys == 0) return fail(-EINVAL, "key index out of range");
+    if (n_msgs == 0) return fail(-EINVAL, "message index out of range");
+    if (n > 0x7FFFFFF0ull || n_keys > 0x7FFFFFFFull || n_msgs > ((size_t)2 << 30) / BLSGPU_G2_BYTES) return fail(-EINVAL, "batch too large");
+    return 0;
+}
+// e(-G1, G2) in B_FIND_UNIT (+512), from the pairing itself, once per context: what k_find_verdict compares a node with S = O with
+int find_unit(blsgpu_ctx* c, hipStream_t st) {
+    if (c->find_unit_ready) return 0;
+    static const uint32_t neg_g1[24] = SIGSH_NEG_G1_WORDS, g2_gen[48] = SIGSH_G2_GEN_WORDS;
+    if (int rc = c->grow(B_FIND_UNIT, 512 + BLSGPU_FQ12_BYTES)) return rc;
+    char* const U = c->at<char>(B_FIND_UNIT);
+    HIP_TRY(hipMemcpyAsync(U, neg_g1, sizeof(neg_g1), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(U + 256, g2_gen, sizeof(g2_gen), hipMemcpyHostToDevice, st));
+    if (int rc = blsgpu_pairing_multi_batch_dev(c, U, U + 256, nullptr, 1, 1, U + 512, st)) return rc;
+    c->find_unit_ready = true;
+    return 0;
+}
+// Items in slices; per slice the once-per-call stages into B_FIND_WS and ONE read of n_e, then the rounds over aligned nodes
+// (offset, length L) of the dense order, L from K = 2^ceil(log2 n_e) halving: the full nodes of a round go through one
+// multi-pairing batch of L + 1 pairs each, the one node that crosses n_e through a call of its own size, a node wholly past n_e
+// does not exist; the verdict bytes come back -- the one synchronisation of a round -- and the host halves the nodes that failed.
+// `scan`: the _dev form's device scan of the indices first.  stats (host, may be NULL): rounds, node tests, pairs fed.
+int verify_find_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_t n_keys, const void* d_key_idx, const void* d_hashes,
+                    size_t n_msgs, const void* d_msg_idx, const void* d_weights, size_t n, void* d_status, uint64_t* stats, bool scan,
+                    hipStream_t st) {
+    using namespace blsgpu::bfind;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    // slices of items whose kept arrays, and whose largest possible round (every leaf a node), stay below 2 GB each
+    const size_t keep_per = 1 + 8 + 1 + 4 + BLSGPU_G2_BYTES + BLSGPU_G1_BYTES;
+    const size_t round_per = 4 + 2 * BLSGPU_G2_BYTES + 1 + 2 * BLSGPU_G1_BYTES + 2 * BLSGPU_G2_BYTES + BLSGPU_FQ12_BYTES + 1;
+    size_t slice = (((size_t)2 << 30) - ((size_t)1 << 20)) / (keep_per > round_per ? keep_per : round_per);
+    if (slice > n) slice = n;
+    size_t off = 256;                                                        // [0, 4): the flag word of the index scan, [4, 8): n_e
+    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
+    const size_t o_keyst = take(n_keys), o_h = take(n_msgs * BLSGPU_G2_BYTES), o_sigst = take(slice), o_r = take(slice * 8), o_elig = take(slice),
+                 o_dense = take(slice * 4), o_a = take(slice * BLSGPU_G2_BYTES), o_b = take(slice * BLSGPU_G1_BYTES);
+    StreamGuard sg(c, st);
+    if (int rc = c->grow(B_FIND_WS, off)) return rc;
+    char* const W = c->at<char>(B_FIND_WS);
+    if (scan) {
+        uint32_t bad = 0;
+        if (int rc = scan_flag(W, st, bad, [&](uint32_t* flag) {
+                for (size_t lo = 0; lo < n; lo += FIX_SLICE) {
+                    const size_t m = n - lo < FIX_SLICE ? n - lo : FIX_SLICE;
+                    hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
+                                       (const uint32_t*)d_key_idx + lo, (uint32_t)m, (uint32_t)n_keys, flag);
+                    hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
+                                       (const uint32_t*)d_msg_idx + lo, (uint32_t)m, (uint32_t)n_msgs, flag);
+                }
+            }))
+            return rc;
+        if (bad) return fail(-EINVAL, "key or message index out of range");
+    }
+    if (int rc = find_unit(c, st)) return rc;
+    const uint4* d_unit = (const uint4*)(c->at<char>(B_FIND_UNIT) + 512);
+    if (int rc = subgroup_dev(c, 1, d_keys, n_keys, W + o_keyst, st)) return rc;
+    if (int rc = blsgpu_hash_to_g2_dev(c, d_hashes, n_msgs, W + o_h, st)) return rc;   // the distinct hashes, once each
+    uint64_t rounds = 0, tests = 0, pairs = 0;
+    std::vector<uint32_t> cur, next, order;
+    std::vector<uint8_t> verdict;
+    int rc = for_slices(n, slice, [&](size_t lo, size_t m) {
+        const char* sigs = (const char*)d_sigs + lo * BLSGPU_G2_BYTES;
+        const uint32_t* kidx = (const uint32_t*)d_key_idx + lo;
+        const uint32_t* midx = (const uint32_t*)d_msg_idx + lo;
+        uint8_t* status = (uint8_t*)d_status + lo;
+        const uint32_t* dense = (const uint32_t*)(W + o_dense);
+        if (int rc = subgroup_dev(c, 2, sigs, m, W + o_sigst, st)) return rc;
+        hipLaunchKernelGGL(k_find_settle, dim3((unsigned)((m + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, (const uint32_t*)sigs,
+                           (const uint8_t*)(W + o_sigst), (const uint32_t*)d_keys, (const uint8_t*)(W + o_keyst), kidx,
+                           (const uint32_t*)(W + o_h), midx, (const uint8_t*)d_weights + lo * 8, (uint32_t)m, (uint8_t*)(W + o_r),
+                           (uint8_t*)(W + o_elig), status);
+        hipLaunchKernelGGL(k_find_dense, dim3(1), dim3(DENSE_THREADS), 0, st, (const uint8_t*)(W + o_elig), (uint32_t)m,
+                           (uint32_t*)(W + o_dense), (uint32_t*)(W + 4));
+        HIP_TRY(hipGetLastError());
+        // the leaves A_i = r_i sig_i, B_i = r_i keys[key_idx[i]] by item (those of items that are not eligible are never read)
+        if (int rc = smul64_launch<2>(c, sigs, m, nullptr, W + o_r, m, W + o_a, nullptr, st)) return rc;
+        if (int rc = smul64_launch<1>(c, d_keys, n_keys, kidx, W + o_r, m, W + o_b, nullptr, st)) return rc;
+        uint32_t n_e = 0;
+        HIP_TRY(hipMemcpyAsync(&n_e, W + 4, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (n_e == 0) return 0;
+        size_t K = 1;
+        while (K < n_e) K <<= 1;
+        cur.assign(1, 0u);
+        for (size_t L = K;; L >>= 1) {
+            // full nodes first, then the one that crosses n_e (every node begins before n_e)
+            order.clear();
+            uint32_t short_off = 0;
+            bool has_short = false;
+            for (uint32_t o : cur) {
+                if ((size_t)o + L <= n_e) order.push_back(o);
+                else { short_off = o; has_short = true; }
+            }
+            const size_t nf = order.size(), ns = has_short ? 1 : 0, ls = has_short ? n_e - short_off : 0, nn = nf + ns;
+            if (has_short) order.push_back(short_off);
+            struct Part { size_t nodes, len, ga, s, sinf, g1, g2, e; } part[2] = {{nf, L}, {ns, ls}};
+            size_t ro = 0;
+            auto rtake = [&](size_t bytes) { size_t o = ro; ro += al(bytes); return o; };
+            const size_t r_off = rtake(nn * 4), r_v = rtake(nn);
+            for (Part& p : part) {
+                p.ga = rtake(p.nodes * p.len * BLSGPU_G2_BYTES);
+                p.s = rtake(p.nodes * BLSGPU_G2_BYTES);
+                p.sinf = rtake(p.nodes);
+                p.g1 = rtake(p.nodes * (p.len + 1) * BLSGPU_G1_BYTES);
+                p.g2 = rtake(p.nodes * (p.len + 1) * BLSGPU_G2_BYTES);
+                p.e = rtake(p.nodes * BLSGPU_FQ12_BYTES);
+            }
+            if (int rc = c->grow(B_FIND_ROUND, ro)) return rc;
+            char* const R = c->at<char>(B_FIND_ROUND);
+            HIP_TRY(hipMemcpyAsync(R + r_off, order.data(), nn * 4, hipMemcpyHostToDevice, st));
+            size_t first = 0;
+            for (const Part& p : part) {
+                if (p.nodes == 0) continue;
+                const uint32_t* d_off = (const uint32_t*)(R + r_off) + first;
+                const size_t gtotal = p.nodes * p.len * G2_Q, ptotal = p.nodes * (p.len + 1) * (G1_Q + G2_Q);
+                hipLaunchKernelGGL(k_find_gather, dim3((unsigned)((gtotal + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, d_off,
+                                   (uint32_t)p.len, gtotal, dense, (const uint4*)(W + o_a), (uint4*)(R + p.ga));
+                HIP_TRY(hipGetLastError());
+                if (int rc = msm_dev<2>(c, R + p.ga, nullptr, p.len, p.nodes, R + p.s, R + p.sinf, st)) return rc;
+                hipLaunchKernelGGL(k_find_pairs, dim3((unsigned)((ptotal + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, d_off,
+                                   (uint32_t)p.len, ptotal, dense, (const uint4*)(R + p.s), (const uint8_t*)(R + p.sinf),
+                                   (const uint4*)(W + o_b), (const uint4*)(W + o_h), midx, (uint4*)(R + p.g1), (uint4*)(R + p.g2));
+                HIP_TRY(hipGetLastError());
+                if (int rc = blsgpu_pairing_multi_batch_dev(c, R + p.g1, R + p.g2, nullptr, p.len + 1, p.nodes, R + p.e, st)) return rc;
+                hipLaunchKernelGGL(k_find_verdict, dim3((unsigned)((p.nodes + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, d_off,
+                                   (uint32_t)p.nodes, (const uint4*)(R + p.e), (const uint8_t*)(R + p.sinf), d_unit, L == 1 ? 1u : 0u, dense,
+                                   (uint8_t*)(R + r_v) + first, status);
+                HIP_TRY(hipGetLastError());
+                first += p.nodes;
+                pairs += p.nodes * (p.len + 1);
+            }
+            verdict.resize(nn);
+            HIP_TRY(hipMemcpyAsync(verdict.data(), R + r_v, nn, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            rounds++;
+            tests += nn;
+            if (L == 1) break;
+            // a node that failed is halved; a half that begins at or past n_e holds nothing and is not tested
+            next.clear();
+            for (size_t i = 0; i < nn; i++)
+                if (!verdict[i]) {
+                    next.push_back(order[i]);
+                    if ((size_t)order[i] + L / 2 < n_e) next.push_back((uint32_t)(order[i] + L / 2));
+                }
+            if (next.empty()) break;
+            cur.swap(next);
+        }
+        return 0;
+    });
+    if (rc) return rc;
+    if (stats) {
+        stats[0] = rounds;
+        stats[1] = tests;
+        stats[2] = pairs;
     }
     return 0;
 }
@@ -2789,6 +3022,51 @@ BLSGPU_EXPORT int blsgpu_sig_shares_check(blsgpu_ctx* c, const uint8_t* sigs, co
     if (int rc = s.up()) return rc;
     if (int rc = sig_shares_dev(c, s.at(dsig), s.at(dkey), n_keys, s.at(didx), s.opt(dx), s.at(dh), s.at(dw), scaled, k, groups, s.at(dst),
                                 s.at(dss), stats, false, nullptr))
+        return rc;
+    return s.down();
+}
+
+// ------------------------------------------------------------ short public scalars, batch verification that names the forgeries --
+BLSGPU_EXPORT int blsgpu_g1_mul_short(blsgpu_ctx* c, const uint8_t* pts, const uint8_t* w, size_t n, uint8_t* out_aff, uint8_t* out_inf) {
+    return mul_short_host<1>(c, pts, w, n, out_aff, out_inf);
+}
+BLSGPU_EXPORT int blsgpu_g2_mul_short(blsgpu_ctx* c, const uint8_t* pts, const uint8_t* w, size_t n, uint8_t* out_aff, uint8_t* out_inf) {
+    return mul_short_host<2>(c, pts, w, n, out_aff, out_inf);
+}
+BLSGPU_EXPORT int blsgpu_g1_mul_short_dev(blsgpu_ctx* c, const void* d_pts, const void* d_w, size_t n, void* d_out_aff, void* d_out_inf,
+                                          void* stream) {
+    return mul_short_dev<1>(c, d_pts, d_w, n, d_out_aff, d_out_inf, (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_g2_mul_short_dev(blsgpu_ctx* c, const void* d_pts, const void* d_w, size_t n, void* d_out_aff, void* d_out_inf,
+                                          void* stream) {
+    return mul_short_dev<2>(c, d_pts, d_w, n, d_out_aff, d_out_inf, (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_verify_find_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_t n_keys, const void* d_key_idx,
+                                         const void* d_msg_hashes, size_t n_msgs, const void* d_msg_idx, const void* d_weights, size_t n,
+                                         void* d_status, uint64_t* stats, void* stream) {
+    if (int rc = verify_find_args(c, n, n_keys, n_msgs, !d_sigs || !d_keys || !d_key_idx || !d_msg_hashes || !d_msg_idx || !d_weights || !d_status))
+        return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return verify_find_dev(c, d_sigs, d_keys, n_keys, d_key_idx, d_msg_hashes, n_msgs, d_msg_idx, d_weights, n, d_status, stats, true,
+                           (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_verify_find(blsgpu_ctx* c, const uint8_t* sigs, const uint8_t* keys, size_t n_keys, const uint32_t* key_idx,
+                                     const uint8_t* msg_hashes, size_t n_msgs, const uint32_t* msg_idx, const uint8_t* weights, size_t n,
+                                     uint8_t* status, uint64_t* stats) {
+    if (int rc = verify_find_args(c, n, n_keys, n_msgs, !sigs || !keys || !key_idx || !msg_hashes || !msg_idx || !weights || !status))
+        return rc < 0 ? rc : 0;
+    for (size_t i = 0; i < n; i++) {
+        if (key_idx[i] >= n_keys) return fail(-EINVAL, "key index out of range");
+        if (msg_idx[i] >= n_msgs) return fail(-EINVAL, "message index out of range");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    Staging s(c);
+    const int dsig = s.in(sigs, n * BLSGPU_G2_BYTES), dkey = s.in(keys, n_keys * BLSGPU_G1_BYTES), dki = s.in(key_idx, n * 4),
+              dh = s.in(msg_hashes, n_msgs * 32), dmi = s.in(msg_idx, n * 4), dw = s.in(weights, n * 8), dst = s.out(status, n);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    if (int rc = verify_find_dev(c, s.at(dsig), s.at(dkey), n_keys, s.at(dki), s.at(dh), n_msgs, s.at(dmi), s.at(dw), n, s.at(dst), stats,
+                                 false, nullptr))
         return rc;
     return s.down();
 }

@@ -65,6 +65,10 @@ enum BufId {
     B_SHR_WS,            // blsgpu_sig_shares_check*: what one slice of sessions keeps over its rounds -- a flag word, the subgroup flags, H(m), the scalars r and w, the key copies and the leaves A, B
     B_SHR_ROUND,         // ... and what one round of it takes: the node table, the gathered leaves, the node sums, the pairs, the pairing results and the verdict bytes
     B_SEED_WS,           // blsgpu_keys_from_seeds*: one slice of the keys (32 bytes each) and of their affine public keys (96) where the caller does not ask for them
+    B_SM64_WS,           // blsgpu_g1_mul_short* / blsgpu_g2_mul_short* and the leaves of blsgpu_verify_find*: the prepared points, their live flags and one launch's tables 0 .. 15 P (k_smul64)
+    B_FIND_WS,           // blsgpu_verify_find*: what one slice of items keeps over its rounds -- a flag word, n_e, the subgroup flags, H(h), the weights, the dense order and the leaves A, B
+    B_FIND_ROUND,        // ... and what one round of it takes: the node offsets, the gathered leaves, the node sums, the pairs, the pairing results and the verdict bytes
+    B_FIND_UNIT,         // ... and e(-G1, G2) with the pair it comes from, computed once per context (find_unit_ready)
     B_COUNT
 };
 // (unit: what the buffer is counted in -- whole partials, whole u32 entries, bytes)
@@ -73,7 +77,8 @@ constexpr BufInfo BUF_INFO[B_COUNT] = {
     {BLSGPU_WS_PARTIALS, BLSGPU_FQ12_BYTES}, {BLSGPU_WS_PARTIALS, BLSGPU_FQ12_BYTES}, {BLSGPU_WS_STAGING, 1}, {BLSGPU_WS_LINES, 1},
     {BLSGPU_WS_LINE_PRODUCTS, 1}, {BLSGPU_WS_LINE_PRODUCTS, 1}, {BLSGPU_WS_FLAGS_AND_LISTS, 1}, {BLSGPU_WS_FLAGS_AND_LISTS, 4},
     {BLSGPU_WS_FLAGS_AND_LISTS, 1}, {BLSGPU_WS_GROUP_SUMS, 4}, {BLSGPU_WS_GROUP_SUMS, 4}, {BLSGPU_WS_SLOTS, 1}, {BLSGPU_WS_SLOTS, 1},
-    {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}};   // no field of their own: they count in the total only
+    {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1},
+    {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}};   // no field of their own: they count in the total only
 
 }  // namespace
 
@@ -84,6 +89,7 @@ struct blsgpu_ctx {
     uint32_t* d_out = nullptr;         // 576-byte result staging
     uint32_t* d_fix_table = nullptr;   // the fixed-base G1 table (blsgpu_g1fix.hip), built on first use; freed by blsgpu_ctx_destroy only
     uint32_t* d_fix_table_secret = nullptr;   // the signed 4-bit table of k_fix_mul_secret (58 240 bytes), likewise
+    bool find_unit_ready = false;      // B_FIND_UNIT holds e(-G1, G2) (blsgpu_verify_find), enqueued on first use
     Buf buf[B_COUNT];
     std::vector<void*> retired;        // Buf::grow
     int grow(BufId id, size_t bytes) { return buf[id].grow(retired, bytes); }
