@@ -573,6 +573,55 @@ int blsgpu_verify_find_dev(blsgpu_ctx *ctx, const void *d_sigs, const void *d_ke
                            const void *d_msg_hashes, size_t n_msgs, const void *d_msg_idx, const void *d_weights, size_t n,
                            void *d_status, uint64_t *stats, void *stream);
 
+/* Sums over RANGES of a list of points (csrc/blsgpu_pscan.hip; vmgen/pscan_model.py is its specification):
+ * out_j = sum of pts[begin_j .. end_j) for m ranges of ANY lengths over n points, from prefix sums S[i] = sum_{k<i} pts[k] kept
+ * as projective records on the device: three passes of about 2 n mixed additions, then ONE complete addition
+ * S[end] + (-S[begin]) and one inversion per range.
+ * pts: n x 96 (G1) / n x 192 (G2) bytes affine, (0,0) = infinity.  ranges: m x 2 uint32 (begin, end), begin <= end <= n; ranges
+ * may overlap, repeat or be empty.  out_aff: m points likewise, (0,0) for infinity.  out_flag: m bytes -- 0 a finite sum, 1
+ * infinity (an empty range gives infinity), 2 the range holds a point that is neither (0,0) nor on the curve: its output is
+ * (0,0).  Such a point is counted and enters every sum as infinity, so the ranges that do not hold it are not disturbed.
+ * A coordinate that is not below q is taken mod q, as blsgpu_g1_msm / blsgpu_g2_msm take it: x + q is accepted as x.
+ * The arithmetic is the complete formulas of Renes-Costello-Batina; both curves have odd order, so the formulas hold for every
+ * point of either curve and the points are NOT checked for (and need not lie in) the prime-order subgroups.  Equal-length
+ * ranges [j k, (j + 1) k) give the bytes of blsgpu_g1_msm / blsgpu_g2_msm(scalars = NULL, k, groups).
+ * More points than keep the prefix records below 2 GB (12.7 M in G1, 6.3 M in G2) are processed in slices; the carry goes into
+ * the next slice and a range is finished in the slice that holds its end.  The workspace counts in BLSGPU_WS_TOTAL.
+ * -EINVAL before anything is written: a NULL required buffer (pts with n > 0; ranges, out_aff, out_flag with m > 0), a range
+ * with begin > end or end > n.  m == 0 writes nothing and returns 0; n == 0 with every range empty writes m times (0,0) and
+ * flag 1.  All of this is PUBLIC data: not constant-time. */
+int blsgpu_g1_range_sums(blsgpu_ctx *ctx, const uint8_t *pts, size_t n, const uint32_t *ranges, size_t m, uint8_t *out_aff,
+                         uint8_t *out_flag);
+int blsgpu_g2_range_sums(blsgpu_ctx *ctx, const uint8_t *pts, size_t n, const uint32_t *ranges, size_t m, uint8_t *out_aff,
+                         uint8_t *out_flag);
+/* The same with every buffer in device memory (points 16-byte aligned, ranges 4-byte), on `stream`.  The ranges are first
+ * scanned on the device and the stream is synchronised once to read the result of that check; the rest is enqueued. */
+int blsgpu_g1_range_sums_dev(blsgpu_ctx *ctx, const void *d_pts, size_t n, const void *d_ranges, size_t m, void *d_out_aff,
+                             void *d_out_flag, void *stream);
+int blsgpu_g2_range_sums_dev(blsgpu_ctx *ctx, const void *d_pts, size_t n, const void *d_ranges, size_t m, void *d_out_aff,
+                             void *d_out_flag, void *stream);
+
+/* blsgpu_verify_find with the items of one message FOLDED inside every node: arguments, status bytes and stats as there, with
+ * ONE precondition -- msg_idx is non-decreasing over the items (a decrease is -EINVAL before anything is written; the _dev form
+ * finds it in the device scan that checks the indices).  The dense order keeps input order, so every message is one
+ * contiguous run of it, and by bilinearity a node (off, L), end = min(off + L, n_e), is tested as
+ *   e(-G1, SA[end] - SA[off])  prod_r e(SB[min(end, rb[r+1])] - SB[max(off, rb[r])], H(h_r)) = 1
+ * over the runs r (begins rb) that meet it: one pair per distinct message in the node plus one, where blsgpu_verify_find takes
+ * one per item plus one.  SA / SB are the prefix sums of the leaves A_i = r_i sig_i (G2) / B_i = r_i P_i (G1) in the dense
+ * order, scanned once per call; every sum of every round is one point subtraction (blsgpu_g?_range_sums' kernels).  A sum at
+ * infinity never reaches the pairing as a point: the pairs whose sum is at infinity take (G1, G2) and (-G1, G2) in turn -- a
+ * couple that cancels -- and when their number is odd the node's result is compared with e(-G1, G2) instead of one.  The
+ * nodes of a round that have the SAME pair count go through one blsgpu_pairing_multi_batch_dev; nothing is padded, and
+ * stats[2] counts exactly the pairs fed.  A batch without a forgery costs (messages among the eligible items) + 1 pairs.
+ * Bisection, leaf verdicts, slicing, synchronisations (one for n_e and the run table, one per round) and what is claimed about
+ * the 2^-64 bound are blsgpu_verify_find's. */
+int blsgpu_verify_find_folded(blsgpu_ctx *ctx, const uint8_t *sigs, const uint8_t *keys, size_t n_keys, const uint32_t *key_idx,
+                              const uint8_t *msg_hashes, size_t n_msgs, const uint32_t *msg_idx, const uint8_t *weights, size_t n,
+                              uint8_t *status, uint64_t *stats);
+int blsgpu_verify_find_folded_dev(blsgpu_ctx *ctx, const void *d_sigs, const void *d_keys, size_t n_keys, const void *d_key_idx,
+                                  const void *d_msg_hashes, size_t n_msgs, const void *d_msg_idx, const void *d_weights, size_t n,
+                                  void *d_status, uint64_t *stats, void *stream);
+
 /* G2 scalar multiplication for SECRET scalars:  out_i = s_i P_(n_pts == 1 ? 0 : i)  with a schedule independent of s
  * (csrc/blsgpu_g2smul.hip k_g2_smul; vmgen/g2smul_model.py is its specification).  s_i is the literal 256-bit integer of
  * 32 big-endian bytes, NOT reduced mod the group order -- exactly the `scalars` of blsgpu_g2_msm, whose results this call

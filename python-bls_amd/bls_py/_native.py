@@ -110,6 +110,12 @@ PROTOTYPES = {
     "blsgpu_g2_mul_short_dev": (vp, vp, vp, sz, vp, vp, vp),
     "blsgpu_verify_find": (vp, cp, cp, sz, vp, cp, sz, vp, cp, sz, vp, vp),
     "blsgpu_verify_find_dev": (vp, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, vp),
+    "blsgpu_g1_range_sums": (vp, cp, sz, vp, sz, vp, vp),
+    "blsgpu_g2_range_sums": (vp, cp, sz, vp, sz, vp, vp),
+    "blsgpu_g1_range_sums_dev": (vp, vp, sz, vp, sz, vp, vp, vp),
+    "blsgpu_g2_range_sums_dev": (vp, vp, sz, vp, sz, vp, vp, vp),
+    "blsgpu_verify_find_folded": (vp, cp, cp, sz, vp, cp, sz, vp, cp, sz, vp, vp),
+    "blsgpu_verify_find_folded_dev": (vp, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, vp),
     "blsgpu_g2_mul_secret": (vp, cp, sz, cp, sz, vp, vp, vp),
     "blsgpu_g2_mul_secret_dev": (vp, vp, sz, vp, sz, vp, vp, vp, vp),
     "blsgpu_sign": (vp, cp, cp, sz, sz, vp, vp),

@@ -91,7 +91,9 @@ def use(provider):
     bytes, (rounds, node tests)).
     Optional extension (without it BLS.verify_batch_find sends everything to verify_batch): verify_find(sigs, keys, key_idx,
     msg_hashes, msg_idx, weights) -> (status bytes, (rounds, node tests, pairs)); with it g1_mul_short / g2_mul_short(pts,
-    weights) -> (affine bytes, [is_inf]) for 64-bit public weights.
+    weights) -> (affine bytes, [is_inf]) for 64-bit public weights.  Optional extension (without it
+    BLS.verify_batch_find(fold=True) takes the path of fold=False): verify_find_folded, verify_find's arguments and results
+    with msg_idx non-decreasing; with it g1_range_sums / g2_range_sums(pts, ranges) -> (affine bytes, flag bytes).
     Extensions are looked up by extension(name), not by hasattr: a stand-in offers one as an attribute of that name, the
     HipProvider's come from EXTENSIONS.  Optional (without it PrivateKey.from_seed_batch and
     ExtendedPrivateKey.from_seed_batch run the per-seed host calls): keys_from_seeds(seeds, seed_len, n, hd) -> (key bytes,
@@ -107,16 +109,18 @@ EXTENSIONS = {"keys_from_seeds": "_native_seeds"}
 # ... and the calls on short public scalars and the batch verification that names the forgeries (BLS.verify_batch_find), looked
 # up by extension(name) in the same way.
 FIND_EXTENSIONS = {"g1_mul_short": "_native_find", "g2_mul_short": "_native_find", "verify_find": "_native_find"}
+# ... and the sums over ranges of points and the batch verification that folds shared messages (BLS.verify_batch_find(fold=True)).
+RANGE_EXTENSIONS = {"g1_range_sums": "_native_ranges", "g2_range_sums": "_native_ranges", "verify_find_folded": "_native_ranges"}
 
 
 def extension(name):
     """The installed provider's extension `name`: the provider's own attribute of that name if it has one (stand-ins), for
-    a HipProvider the function of EXTENSIONS bound to its engine, otherwise None."""
+    a HipProvider the function of EXTENSIONS (or FIND_EXTENSIONS, RANGE_EXTENSIONS) bound to its engine, otherwise None."""
     prov = get()
     fn = getattr(prov, name, None)
     if fn is not None:
         return fn
-    where = EXTENSIONS.get(name) or FIND_EXTENSIONS.get(name)
+    where = EXTENSIONS.get(name) or FIND_EXTENSIONS.get(name) or RANGE_EXTENSIONS.get(name)
     if isinstance(prov, HipProvider) and where:
         import functools
         import importlib

@@ -318,7 +318,7 @@ class BLS:
         return results
 
     @staticmethod
-    def verify_batch_find(signatures, rng=None):
+    def verify_batch_find(signatures, rng=None, fold=False):
         """verify_batch(signatures) with the forgeries NAMED on the device (blsgpu_verify_find): every signature over exactly
         one 32-byte message hash is an item (signature, key, message) of one call that checks all items by a random linear
         combination and bisects only what fails -- one forgery among n costs about 2 log2 n node tests, not n pairings.  The
@@ -329,7 +329,11 @@ class BLS:
         (a key or key sum outside G1 or at infinity, H(m) at infinity), a tree without one of its keys, an infinity signature,
         a provider without the verify_find extension -- is decided by verify_batch in the same call.  The answers equal verify_batch's
         except that an invalid item is reported True with probability at most 2^-64 per node that holds it (DESIGN.md
-        section 2u)."""
+        section 2u).
+        fold=True (many signers over few messages): the items, their weights drawn as above, are stably sorted by message hash
+        and go to the verify_find_folded extension (blsgpu_verify_find_folded), whose node tests take one
+        pair per distinct message instead of one per item; the verdicts come back in the order of the list.  A provider without
+        that extension takes the path of fold=False."""
         prov = backend.get()
         rng = rng or secrets.SystemRandom()
         results = [None] * len(signatures)
@@ -383,7 +387,16 @@ class BLS:
                 while x == 0:
                     x = rng.getrandbits(64)
                 weights.append(x)
-            status, _ = find(b"".join(sigs), b"".join(keys), key_idx, b"".join(msgs), msg_idx, weights)
+            folded = backend.extension("verify_find_folded") if fold else None
+            if folded is not None:
+                table = sorted(msgs)
+                order = sorted(range(len(items)), key=lambda j: items[j][1][0])          # stable: input order within a message
+                place = {mh: j for j, mh in enumerate(table)}
+                status, _ = folded(b"".join(sigs[j] for j in order), b"".join(keys), [key_idx[j] for j in order], b"".join(table),
+                                   [place[items[j][1][0]] for j in order], [weights[j] for j in order])
+                items = [items[j] for j in order]
+            else:
+                status, _ = find(b"".join(sigs), b"".join(keys), key_idx, b"".join(msgs), msg_idx, weights)
             for p, s in zip(items, status):
                 if s != 2:
                     results[p[0]] = s == 1

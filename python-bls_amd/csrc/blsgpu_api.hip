@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -32,6 +33,7 @@
 #include "blsgpu_batchfind.hip"
 #include "blsgpu_g2smul.hip"
 #include "blsgpu_smul64.hip"
+#include "blsgpu_pscan.hip"
 #include "blsgpu_h2c.hip"
 #include "blsgpu_h2cw.hip"
 #include "blsgpu_msmw.hip"
@@ -1258,6 +1260,313 @@ int verify_find_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_
                 if (!verdict[i]) {
                     next.push_back(order[i]);
                     if ((size_t)order[i] + L / 2 < n_e) next.push_back((uint32_t)(order[i] + L / 2));
+                }
+            if (next.empty()) break;
+            cur.swap(next);
+        }
+        return 0;
+    });
+    if (rc) return rc;
+    if (stats) {
+        stats[0] = rounds;
+        stats[1] = tests;
+        stats[2] = pairs;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------ point prefix sums and range sums (blsgpu_pscan.hip) --
+// One scan's workspace (B_PSCAN_G1 / B_PSCAN_G2): the prepared points of a slice, their live and kind bytes, the chunk totals
+// and counts, the n + 1 prefix records and counts, and the carry into the next slice.
+struct PscanWs { uint32_t *prep, *ct, *cb, *s, *cnt, *carry, *carryc; uint8_t *live, *kind; };
+constexpr size_t PSCAN_RECORD_BYTES = ((size_t)2 << 30) - ((size_t)1 << 20);    // what the prefix records of one slice may take
+template <int DEG> constexpr size_t pscan_slice() { return PSCAN_RECORD_BYTES / (blsgpu::L28_PJ * DEG * 4) - 1; }   // points
+template <int DEG>
+int pscan_ws(blsgpu_ctx* c, size_t pts, PscanWs& w) {
+    const size_t PJ = blsgpu::L28_PJ * DEG, chunks = pts ? (pts + blsgpu::pscan::CHUNK - 1) / blsgpu::pscan::CHUNK : 1;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_prep = take(pts * blsgpu::L28_AFF * DEG * 4), o_live = take(pts), o_kind = take(pts), o_ct = take(chunks * PJ * 4),
+                 o_cb = take(chunks * 4), o_s = take((pts + 1) * PJ * 4), o_cnt = take((pts + 1) * 4), o_carry = take(PJ * 4), o_cc = take(4);
+    const BufId id = DEG == 1 ? B_PSCAN_G1 : B_PSCAN_G2;
+    if (int rc = c->grow(id, off)) return rc;
+    char* const W = c->at<char>(id);
+    w = {(uint32_t*)(W + o_prep), (uint32_t*)(W + o_ct), (uint32_t*)(W + o_cb), (uint32_t*)(W + o_s), (uint32_t*)(W + o_cnt),
+         (uint32_t*)(W + o_carry), (uint32_t*)(W + o_cc), (uint8_t*)(W + o_live), (uint8_t*)(W + o_kind)};
+    return 0;
+}
+// enqueues the prefix records of the m points at d_pts (one slice) into w; `first`: no carry comes in; `more`: the last record
+// is kept as the carry of the next slice
+template <int DEG>
+int pscan_launch(const PscanWs& w, const void* d_pts, size_t m, bool first, bool more, hipStream_t st) {
+    namespace ps = blsgpu::pscan;
+    const size_t PJ = blsgpu::L28_PJ * DEG, chunks = m ? (m + ps::CHUNK - 1) / ps::CHUNK : 1;
+    if (m) hipLaunchKernelGGL(blsgpu::k_lane_prep<DEG>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_pts, (uint32_t)m, w.prep, w.live);
+    hipLaunchKernelGGL(ps::k_pscan_totals<DEG>, dim3((unsigned)((chunks + 63) / 64)), dim3(64), 0, st, w.prep, w.live, (uint32_t)m, w.kind, w.ct, w.cb);
+    hipLaunchKernelGGL(ps::k_pscan_mid<DEG>, dim3(1), dim3(ps::MID_THREADS), 0, st, w.ct, w.cb, (uint32_t)chunks, first ? nullptr : w.carry,
+                       first ? nullptr : w.carryc);
+    hipLaunchKernelGGL(ps::k_pscan_replay<DEG>, dim3((unsigned)((chunks + 63) / 64)), dim3(64), 0, st, w.prep, w.kind, (uint32_t)m, w.ct, w.cb, w.s, w.cnt);
+    HIP_TRY(hipGetLastError());
+    if (more) {
+        HIP_TRY(hipMemcpyAsync(w.carry, w.s + m * PJ, PJ * 4, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(w.carryc, w.cnt + m, 4, hipMemcpyDeviceToDevice, st));
+    }
+    return 0;
+}
+// enqueues the sums of the m ranges whose end lies among the records [lo, hi] of w (base / basec: the records at the begins, NULL
+// when every begin lies there too)
+template <int DEG>
+int pscan_ranges_launch(const PscanWs& w, size_t lo, size_t hi, bool last, const void* d_ranges, size_t m, const uint32_t* base,
+                        const uint32_t* basec, void* d_out, void* d_flag, hipStream_t st) {
+    const size_t lanes = m * blsgpu::SrtG<DEG>::LP;
+    hipLaunchKernelGGL(blsgpu::pscan::k_pscan_range<DEG>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, w.s, w.cnt, (uint32_t)lo, (uint32_t)hi,
+                       last ? 1u : 0u, (const uint32_t*)d_ranges, (uint32_t)m, base, basec, (uint32_t*)d_out, (uint8_t*)d_flag);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+// the argument checks of blsgpu_g?_range_sums* (before anything is written); 1: nothing to do
+int range_sums_args(const blsgpu_ctx* c, const void* pts, size_t n, const void* ranges, size_t m, const void* out, const void* flag) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if ((n && !pts) || (m && (!ranges || !out || !flag))) return fail(-EINVAL, "NULL argument");
+    if (n > 0xFFFFFFF0ull || m > 0x7FFFFFF0ull / blsgpu::SrtG<2>::LP) return fail(-EINVAL, "batch too large");
+    return m == 0 ? 1 : 0;
+}
+// Points in slices of pscan_slice<DEG>() whose records carry on from the slice before; a range is finished in the slice that
+// holds its end.  With more than one slice the record at a range's begin is copied beside the range (B_PSCAN_RANGE) while its
+// slice is there.  `scan`: the _dev form's device scan of the ranges first -- one synchronisation, before anything is written.
+template <int DEG>
+int range_sums_dev(blsgpu_ctx* c, const void* d_pts, size_t n, const void* d_ranges, size_t m, void* d_out, void* d_flag, bool scan,
+                   hipStream_t st) {
+    namespace ps = blsgpu::pscan;
+    const size_t PJ = blsgpu::L28_PJ * DEG, SL = pscan_slice<DEG>(), S = n < SL ? n : SL;
+    const bool single = n <= SL;
+    StreamGuard sg(c, st);
+    const size_t o_base = 256, o_basec = o_base + ((single ? 0 : m * PJ * 4 + 255) & ~(size_t)255);
+    if (int rc = c->grow(B_PSCAN_RANGE, o_basec + (single ? 0 : m * 4))) return rc;
+    char* const R = c->at<char>(B_PSCAN_RANGE);
+    if (scan) {
+        uint32_t bad = 0;
+        if (int rc = scan_flag(R, st, bad, [&](uint32_t* flag) {
+                hipLaunchKernelGGL(ps::k_pscan_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_ranges, (uint32_t)m,
+                                   (uint32_t)n, flag);
+            }))
+            return rc;
+        if (bad) return fail(-EINVAL, "range out of order or past the points");
+    }
+    PscanWs w;
+    if (int rc = pscan_ws<DEG>(c, S, w)) return rc;
+    uint32_t* const base = single ? nullptr : (uint32_t*)(R + o_base);
+    uint32_t* const basec = single ? nullptr : (uint32_t*)(R + o_basec);
+    size_t lo = 0;
+    do {
+        const size_t len = n - lo < SL ? n - lo : SL, hi = lo + len;
+        const bool last = hi == n;
+        if (int rc = pscan_launch<DEG>(w, (const char*)d_pts + lo * 96 * DEG, len, lo == 0, !last, st)) return rc;
+        if (!single) {
+            const size_t total = m * PJ;
+            hipLaunchKernelGGL(ps::k_pscan_begin<DEG>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w.s, w.cnt, (uint32_t)lo, (uint32_t)hi,
+                               last ? 1u : 0u, (const uint32_t*)d_ranges, total, base, basec);
+        }
+        if (int rc = pscan_ranges_launch<DEG>(w, lo, hi, last, d_ranges, m, base, basec, d_out, d_flag, st)) return rc;
+        lo = hi;
+    } while (lo < n);
+    return 0;
+}
+template <int DEG>
+int range_sums_host(blsgpu_ctx* c, const uint8_t* pts, size_t n, const uint32_t* ranges, size_t m, uint8_t* out, uint8_t* flag) {
+    if (int rc = range_sums_args(c, pts, n, ranges, m, out, flag)) return rc < 0 ? rc : 0;
+    for (size_t i = 0; i < m; i++)
+        if (ranges[2 * i] > ranges[2 * i + 1] || ranges[2 * i + 1] > n) return fail(-EINVAL, "range out of order or past the points");
+    HIP_TRY(hipSetDevice(c->device));
+    Staging s(c);
+    const int dp = s.in(n ? pts : nullptr, n * 96 * DEG), dr = s.in(ranges, m * 8), dout = s.out(out, m * 96 * DEG), df = s.out(flag, m);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    if (int rc = range_sums_dev<DEG>(c, s.opt(dp), n, s.at(dr), m, s.at(dout), s.at(df), false, nullptr)) return rc;
+    return s.down();
+}
+
+// ------------------------------------------------------------ batch verification that folds shared messages (blsgpu_pscan.hip) --
+// verify_find_dev with the items of one message FOLDED inside every node.  msg_idx is non-decreasing, so in the dense order
+// every message is one contiguous run.  Once per slice, beyond verify_find_dev's stages: the run table (k_fold_runs; the host
+// reads it with n_e in the same synchronisation), the leaves in the dense order (k_fold_leaves) and their prefix records SA
+// (G2) and SB (G1).  A round's node (off, L), end = min(off + L, n_e), is e(-G1, SA[end] - SA[off]) prod_r e(SB[min(end,
+// rb[r+1])] - SB[max(off, rb[r])], H(h_r)) = 1 over the runs r that meet it: the host lays out one SLOT per pair -- node after
+// node, the nodes of a round ordered by their pair count --, the two range kernels give the sums (the B sums of the slots that are
+// no head, the S of the nodes), k_fold_codes / k_fold_fill lay out the pairs, and the nodes of EQUAL pair count go through one blsgpu_pairing_multi_batch_dev each: nothing is padded.
+int verify_find_folded_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_t n_keys, const void* d_key_idx, const void* d_hashes,
+                           size_t n_msgs, const void* d_msg_idx, const void* d_weights, size_t n, void* d_status, uint64_t* stats, bool scan,
+                           hipStream_t st) {
+    using namespace blsgpu::bfind;
+    namespace ps = blsgpu::pscan;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    // slices of items whose kept arrays, and whose largest possible round, stay below 2 GB each: a round has at most one node
+    // per item and at most 2 nodes + runs <= 3 items slots
+    const size_t keep_per = 1 + 8 + 1 + 4 + 2 * (BLSGPU_G2_BYTES + BLSGPU_G1_BYTES) + 8;
+    const size_t slot_per = 8 + 4 + 4 + 1 + 1 + 2 * BLSGPU_G1_BYTES + BLSGPU_G2_BYTES;
+    const size_t round_per = 3 * slot_per + 4 + 8 + 4 + BLSGPU_G2_BYTES + 3 + BLSGPU_FQ12_BYTES;
+    size_t slice = (((size_t)2 << 30) - ((size_t)1 << 20)) / (keep_per > round_per ? keep_per : round_per);
+    if (slice > n) slice = n;
+    const size_t rcap = (slice < n_msgs ? slice : n_msgs) + 1;                 // entries of the run table
+    size_t off = 256;                                                        // [0, 4): the flag word of the index scan, [4, 8): n_e, [8, 12): the runs
+    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
+    const size_t o_keyst = take(n_keys), o_h = take(n_msgs * BLSGPU_G2_BYTES), o_sigst = take(slice), o_r = take(slice * 8), o_elig = take(slice),
+                 o_dense = take(slice * 4), o_a = take(slice * BLSGPU_G2_BYTES), o_b = take(slice * BLSGPU_G1_BYTES),
+                 o_ad = take(slice * BLSGPU_G2_BYTES), o_bd = take(slice * BLSGPU_G1_BYTES), o_rb = take(rcap * 4), o_rmsg = take(rcap * 4);
+    StreamGuard sg(c, st);
+    if (int rc = c->grow(B_FIND_WS, off)) return rc;
+    char* const W = c->at<char>(B_FIND_WS);
+    if (scan) {
+        uint32_t bad = 0;
+        if (int rc = scan_flag(W, st, bad, [&](uint32_t* flag) {
+                for (size_t lo = 0; lo < n; lo += FIX_SLICE) {
+                    const size_t m = n - lo < FIX_SLICE ? n - lo : FIX_SLICE;
+                    hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
+                                       (const uint32_t*)d_key_idx + lo, (uint32_t)m, (uint32_t)n_keys, flag);
+                    hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
+                                       (const uint32_t*)d_msg_idx + lo, (uint32_t)m, (uint32_t)n_msgs, flag);
+                    hipLaunchKernelGGL(ps::k_fold_mono, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_msg_idx,
+                                       (uint32_t)lo, (uint32_t)m, flag);
+                }
+            }))
+            return rc;
+        if (bad & 1u) return fail(-EINVAL, "key or message index out of range");
+        if (bad) return fail(-EINVAL, "message indices decrease");
+    }
+    if (int rc = find_unit(c, st)) return rc;
+    const uint4* d_unit = (const uint4*)(c->at<char>(B_FIND_UNIT) + 512);
+    if (int rc = subgroup_dev(c, 1, d_keys, n_keys, W + o_keyst, st)) return rc;
+    if (int rc = blsgpu_hash_to_g2_dev(c, d_hashes, n_msgs, W + o_h, st)) return rc;   // the distinct hashes, once each
+    uint64_t rounds = 0, tests = 0, pairs = 0;
+    struct NodeRec { uint32_t off, r0, cnt; };                               // a node, its first run and its pair count
+    std::vector<uint32_t> cur, next, rb(rcap), rmsg(rcap), tab;
+    std::vector<NodeRec> order;
+    std::vector<uint8_t> verdict;
+    int rc = for_slices(n, slice, [&](size_t lo, size_t m) {
+        const char* sigs = (const char*)d_sigs + lo * BLSGPU_G2_BYTES;
+        const uint32_t* kidx = (const uint32_t*)d_key_idx + lo;
+        const uint32_t* midx = (const uint32_t*)d_msg_idx + lo;
+        uint8_t* status = (uint8_t*)d_status + lo;
+        const uint32_t* dense = (const uint32_t*)(W + o_dense);
+        if (int rc = subgroup_dev(c, 2, sigs, m, W + o_sigst, st)) return rc;
+        hipLaunchKernelGGL(k_find_settle, dim3((unsigned)((m + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, (const uint32_t*)sigs,
+                           (const uint8_t*)(W + o_sigst), (const uint32_t*)d_keys, (const uint8_t*)(W + o_keyst), kidx,
+                           (const uint32_t*)(W + o_h), midx, (const uint8_t*)d_weights + lo * 8, (uint32_t)m, (uint8_t*)(W + o_r),
+                           (uint8_t*)(W + o_elig), status);
+        hipLaunchKernelGGL(k_find_dense, dim3(1), dim3(DENSE_THREADS), 0, st, (const uint8_t*)(W + o_elig), (uint32_t)m,
+                           (uint32_t*)(W + o_dense), (uint32_t*)(W + 4));
+        hipLaunchKernelGGL(ps::k_fold_runs, dim3(1), dim3(ps::RUN_THREADS), 0, st, dense, (const uint32_t*)(W + 4), midx, (uint32_t*)(W + o_rb),
+                           (uint32_t*)(W + o_rmsg), (uint32_t*)(W + 8));
+        HIP_TRY(hipGetLastError());
+        // the leaves A_i = r_i sig_i, B_i = r_i keys[key_idx[i]] by item, then those of the eligible items in the dense order
+        if (int rc = smul64_launch<2>(c, sigs, m, nullptr, W + o_r, m, W + o_a, nullptr, st)) return rc;
+        if (int rc = smul64_launch<1>(c, d_keys, n_keys, kidx, W + o_r, m, W + o_b, nullptr, st)) return rc;
+        const size_t ltotal = m * 18;
+        hipLaunchKernelGGL(ps::k_fold_leaves, dim3((unsigned)((ltotal + ps::THREADS - 1) / ps::THREADS)), dim3(ps::THREADS), 0, st, dense,
+                           (const uint32_t*)(W + 4), ltotal, (const uint4*)(W + o_a), (const uint4*)(W + o_b), (uint4*)(W + o_ad), (uint4*)(W + o_bd));
+        HIP_TRY(hipGetLastError());
+        uint32_t head[2] = {0, 0};                                           // n_e, the number of runs
+        const size_t rn = (m < n_msgs ? m : n_msgs) + 1;
+        HIP_TRY(hipMemcpyAsync(head, W + 4, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(rb.data(), W + o_rb, rn * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(rmsg.data(), W + o_rmsg, rn * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const uint32_t n_e = head[0], n_runs = head[1];
+        if (n_e == 0) return 0;
+        if (n_runs == 0 || n_runs >= rn || rb[0] != 0 || rb[n_runs] != n_e) return fail(-EIO, "run table inconsistent");
+        PscanWs wa, wb;
+        if (int rc = pscan_ws<2>(c, n_e, wa)) return rc;
+        if (int rc = pscan_ws<1>(c, n_e, wb)) return rc;
+        if (int rc = pscan_launch<2>(wa, W + o_ad, n_e, true, false, st)) return rc;
+        if (int rc = pscan_launch<1>(wb, W + o_bd, n_e, true, false, st)) return rc;
+        size_t K = 1;
+        while (K < n_e) K <<= 1;
+        cur.assign(1, 0u);
+        for (size_t L = K;; L >>= 1) {
+            // every node with its first run and pair count, ordered by pair count (the order of the offsets kept within one)
+            order.clear();
+            for (uint32_t o : cur) {
+                const uint32_t end = (size_t)o + L < n_e ? (uint32_t)(o + L) : n_e;
+                const uint32_t r0 = (uint32_t)(std::upper_bound(rb.begin(), rb.begin() + n_runs, o) - rb.begin()) - 1u;
+                uint32_t r1 = r0;
+                while (rb[r1 + 1] < end) r1++;
+                order.push_back({o, r0, r1 - r0 + 2u});
+            }
+            std::stable_sort(order.begin(), order.end(), [](const NodeRec& a, const NodeRec& b) { return a.cnt < b.cnt; });
+            const size_t nn = order.size();
+            size_t slots = 0;
+            for (const NodeRec& nd : order) slots += nd.cnt;
+            // the table the host uploads: first[nn + 1], off[nn], rng2[2 nn], node_of[slots], slot_msg[slots] and rng1: the ranges of
+            // the B sums, one per slot that is not a node's head (node i's slot sl has the sum sl - i - 1)
+            size_t to = 0;
+            auto ttake = [&](size_t words) { size_t o = to; to += (words + 63) & ~(size_t)63; return o; };
+            const size_t nb = slots - nn;
+            const size_t t_first = ttake(nn + 1), t_off = ttake(nn), t_rng2 = ttake(2 * nn), t_node = ttake(slots), t_msg = ttake(slots),
+                         t_rng1 = ttake(2 * nb);
+            tab.assign(to, 0u);
+            size_t sl = 0;
+            for (size_t i = 0; i < nn; i++) {
+                const NodeRec& nd = order[i];
+                const uint32_t end = (size_t)nd.off + L < n_e ? (uint32_t)(nd.off + L) : n_e;
+                tab[t_first + i] = (uint32_t)sl;
+                tab[t_off + i] = nd.off;
+                tab[t_rng2 + 2 * i] = nd.off;
+                tab[t_rng2 + 2 * i + 1] = end;
+                for (uint32_t j = 0; j < nd.cnt; j++, sl++) {
+                    tab[t_node + sl] = (uint32_t)i;
+                    if (j == 0) continue;                                    // the head slot: (-G1, S)
+                    const uint32_t r = nd.r0 + j - 1u;
+                    const size_t bi = sl - i - 1;
+                    tab[t_msg + sl] = rmsg[r];
+                    tab[t_rng1 + 2 * bi] = rb[r] > nd.off ? rb[r] : nd.off;
+                    tab[t_rng1 + 2 * bi + 1] = rb[r + 1] < end ? rb[r + 1] : end;
+                }
+            }
+            tab[t_first + nn] = (uint32_t)sl;
+            size_t ro = 0;
+            auto rtake = [&](size_t bytes) { size_t o = ro; ro += al(bytes); return o; };
+            const size_t r_tab = rtake(to * 4), r_code = rtake(slots), r_bflag = rtake(nb), r_b = rtake(nb * BLSGPU_G1_BYTES), r_sflag = rtake(nn), r_odd = rtake(nn), r_v = rtake(nn),
+                         r_s = rtake(nn * BLSGPU_G2_BYTES), r_g1 = rtake(slots * BLSGPU_G1_BYTES), r_g2 = rtake(slots * BLSGPU_G2_BYTES),
+                         r_e = rtake(nn * BLSGPU_FQ12_BYTES);
+            if (int rc = c->grow(B_FIND_ROUND, ro)) return rc;
+            char* const R = c->at<char>(B_FIND_ROUND);
+            const uint32_t* const T = (const uint32_t*)(R + r_tab);
+            HIP_TRY(hipMemcpyAsync(R + r_tab, tab.data(), to * 4, hipMemcpyHostToDevice, st));
+            if (int rc = pscan_ranges_launch<1>(wb, 0, n_e, true, T + t_rng1, nb, nullptr, nullptr, R + r_b, R + r_bflag, st)) return rc;
+            if (int rc = pscan_ranges_launch<2>(wa, 0, n_e, true, T + t_rng2, nn, nullptr, nullptr, R + r_s, R + r_sflag, st)) return rc;
+            hipLaunchKernelGGL(ps::k_fold_codes, dim3((unsigned)((nn + ps::THREADS - 1) / ps::THREADS)), dim3(ps::THREADS), 0, st, T + t_first,
+                               (uint32_t)nn, (const uint8_t*)(R + r_bflag), (const uint8_t*)(R + r_sflag), (uint8_t*)(R + r_code),
+                               (uint8_t*)(R + r_odd));
+            const size_t ftotal = slots * 18;
+            hipLaunchKernelGGL(ps::k_fold_fill, dim3((unsigned)((ftotal + ps::THREADS - 1) / ps::THREADS)), dim3(ps::THREADS), 0, st, T + t_node,
+                               T + t_first, T + t_msg, ftotal, (const uint8_t*)(R + r_code), (const uint4*)(R + r_b), (const uint4*)(R + r_s), (const uint4*)(W + o_h),
+                               (uint4*)(R + r_g1), (uint4*)(R + r_g2));
+            HIP_TRY(hipGetLastError());
+            for (size_t i = 0; i < nn;) {                                    // the nodes of one pair count: one multi-pairing batch
+                size_t j = i;
+                while (j < nn && order[j].cnt == order[i].cnt) j++;
+                const size_t s0 = tab[t_first + i];
+                if (int rc = blsgpu_pairing_multi_batch_dev(c, R + r_g1 + s0 * BLSGPU_G1_BYTES, R + r_g2 + s0 * BLSGPU_G2_BYTES, nullptr,
+                                                            order[i].cnt, j - i, R + r_e + i * BLSGPU_FQ12_BYTES, st))
+                    return rc;
+                i = j;
+            }
+            hipLaunchKernelGGL(k_find_verdict, dim3((unsigned)((nn + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, T + t_off, (uint32_t)nn,
+                               (const uint4*)(R + r_e), (const uint8_t*)(R + r_odd), d_unit, L == 1 ? 1u : 0u, dense, (uint8_t*)(R + r_v), status);
+            HIP_TRY(hipGetLastError());
+            verdict.resize(nn);
+            HIP_TRY(hipMemcpyAsync(verdict.data(), R + r_v, nn, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            rounds++;
+            tests += nn;
+            pairs += slots;
+            if (L == 1) break;
+            // a node that failed is halved; a half that begins at or past n_e holds nothing and is not tested
+            next.clear();
+            for (size_t i = 0; i < nn; i++)
+                if (!verdict[i]) {
+                    next.push_back(order[i].off);
+                    if ((size_t)order[i].off + L / 2 < n_e) next.push_back((uint32_t)(order[i].off + L / 2));
                 }
             if (next.empty()) break;
             cur.swap(next);
@@ -3067,6 +3376,58 @@ BLSGPU_EXPORT int blsgpu_verify_find(blsgpu_ctx* c, const uint8_t* sigs, const u
     if (int rc = s.up()) return rc;
     if (int rc = verify_find_dev(c, s.at(dsig), s.at(dkey), n_keys, s.at(dki), s.at(dh), n_msgs, s.at(dmi), s.at(dw), n, s.at(dst), stats,
                                  false, nullptr))
+        return rc;
+    return s.down();
+}
+
+// ------------------------------------------------------------ point range sums, batch verification that folds shared messages --
+BLSGPU_EXPORT int blsgpu_g1_range_sums(blsgpu_ctx* c, const uint8_t* pts, size_t n, const uint32_t* ranges, size_t m, uint8_t* out_aff,
+                                       uint8_t* out_flag) {
+    return range_sums_host<1>(c, pts, n, ranges, m, out_aff, out_flag);
+}
+BLSGPU_EXPORT int blsgpu_g2_range_sums(blsgpu_ctx* c, const uint8_t* pts, size_t n, const uint32_t* ranges, size_t m, uint8_t* out_aff,
+                                       uint8_t* out_flag) {
+    return range_sums_host<2>(c, pts, n, ranges, m, out_aff, out_flag);
+}
+BLSGPU_EXPORT int blsgpu_g1_range_sums_dev(blsgpu_ctx* c, const void* d_pts, size_t n, const void* d_ranges, size_t m, void* d_out_aff,
+                                           void* d_out_flag, void* stream) {
+    if (int rc = range_sums_args(c, d_pts, n, d_ranges, m, d_out_aff, d_out_flag)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return range_sums_dev<1>(c, d_pts, n, d_ranges, m, d_out_aff, d_out_flag, true, (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_g2_range_sums_dev(blsgpu_ctx* c, const void* d_pts, size_t n, const void* d_ranges, size_t m, void* d_out_aff,
+                                           void* d_out_flag, void* stream) {
+    if (int rc = range_sums_args(c, d_pts, n, d_ranges, m, d_out_aff, d_out_flag)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return range_sums_dev<2>(c, d_pts, n, d_ranges, m, d_out_aff, d_out_flag, true, (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_verify_find_folded_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_t n_keys, const void* d_key_idx,
+                                                const void* d_msg_hashes, size_t n_msgs, const void* d_msg_idx, const void* d_weights, size_t n,
+                                                void* d_status, uint64_t* stats, void* stream) {
+    if (int rc = verify_find_args(c, n, n_keys, n_msgs, !d_sigs || !d_keys || !d_key_idx || !d_msg_hashes || !d_msg_idx || !d_weights || !d_status))
+        return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return verify_find_folded_dev(c, d_sigs, d_keys, n_keys, d_key_idx, d_msg_hashes, n_msgs, d_msg_idx, d_weights, n, d_status, stats, true,
+                                  (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_verify_find_folded(blsgpu_ctx* c, const uint8_t* sigs, const uint8_t* keys, size_t n_keys, const uint32_t* key_idx,
+                                            const uint8_t* msg_hashes, size_t n_msgs, const uint32_t* msg_idx, const uint8_t* weights, size_t n,
+                                            uint8_t* status, uint64_t* stats) {
+    if (int rc = verify_find_args(c, n, n_keys, n_msgs, !sigs || !keys || !key_idx || !msg_hashes || !msg_idx || !weights || !status))
+        return rc < 0 ? rc : 0;
+    for (size_t i = 0; i < n; i++) {
+        if (key_idx[i] >= n_keys) return fail(-EINVAL, "key index out of range");
+        if (msg_idx[i] >= n_msgs) return fail(-EINVAL, "message index out of range");
+        if (i && msg_idx[i] < msg_idx[i - 1]) return fail(-EINVAL, "message indices decrease");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    Staging s(c);
+    const int dsig = s.in(sigs, n * BLSGPU_G2_BYTES), dkey = s.in(keys, n_keys * BLSGPU_G1_BYTES), dki = s.in(key_idx, n * 4),
+              dh = s.in(msg_hashes, n_msgs * 32), dmi = s.in(msg_idx, n * 4), dw = s.in(weights, n * 8), dst = s.out(status, n);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    if (int rc = verify_find_folded_dev(c, s.at(dsig), s.at(dkey), n_keys, s.at(dki), s.at(dh), n_msgs, s.at(dmi), s.at(dw), n, s.at(dst),
+                                        stats, false, nullptr))
         return rc;
     return s.down();
 }

@@ -66,9 +66,12 @@ enum BufId {
     B_SHR_ROUND,         // ... and what one round of it takes: the node table, the gathered leaves, the node sums, the pairs, the pairing results and the verdict bytes
     B_SEED_WS,           // blsgpu_keys_from_seeds*: one slice of the keys (32 bytes each) and of their affine public keys (96) where the caller does not ask for them
     B_SM64_WS,           // blsgpu_g1_mul_short* / blsgpu_g2_mul_short* and the leaves of blsgpu_verify_find*: the prepared points, their live flags and one launch's tables 0 .. 15 P (k_smul64)
-    B_FIND_WS,           // blsgpu_verify_find*: what one slice of items keeps over its rounds -- a flag word, n_e, the subgroup flags, H(h), the weights, the dense order and the leaves A, B
+    B_FIND_WS,           // blsgpu_verify_find* / blsgpu_verify_find_folded* (which adds the leaves in the dense order and the run table): what one slice of items keeps over its rounds -- a flag word, n_e, the subgroup flags, H(h), the weights, the dense order and the leaves A, B
     B_FIND_ROUND,        // ... and what one round of it takes: the node offsets, the gathered leaves, the node sums, the pairs, the pairing results and the verdict bytes
     B_FIND_UNIT,         // ... and e(-G1, G2) with the pair it comes from, computed once per context (find_unit_ready)
+    B_PSCAN_G1,          // blsgpu_g1_range_sums* and SB of blsgpu_verify_find_folded*: one slice of prepared points, their live and kind bytes, the chunk totals and counts, the prefix records and counts, the carry (blsgpu_pscan.hip)
+    B_PSCAN_G2,          // ... the same for blsgpu_g2_range_sums* and SA
+    B_PSCAN_RANGE,       // blsgpu_g?_range_sums*: a flag word and, when the points take several slices, the record and count at every range's begin
     B_COUNT
 };
 // (unit: what the buffer is counted in -- whole partials, whole u32 entries, bytes)
@@ -78,7 +81,7 @@ constexpr BufInfo BUF_INFO[B_COUNT] = {
     {BLSGPU_WS_LINE_PRODUCTS, 1}, {BLSGPU_WS_LINE_PRODUCTS, 1}, {BLSGPU_WS_FLAGS_AND_LISTS, 1}, {BLSGPU_WS_FLAGS_AND_LISTS, 4},
     {BLSGPU_WS_FLAGS_AND_LISTS, 1}, {BLSGPU_WS_GROUP_SUMS, 4}, {BLSGPU_WS_GROUP_SUMS, 4}, {BLSGPU_WS_SLOTS, 1}, {BLSGPU_WS_SLOTS, 1},
     {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1},
-    {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}};   // no field of their own: they count in the total only
+    {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}};   // no field of their own: they count in the total only
 
 }  // namespace
 

@@ -41,6 +41,10 @@ struct Node { uint32_t session, offset; };
     0xa7d3f117u, 0x94d79731u, 0x8c639526u, 0x0faca94fu, 0x4f8c68c3u, 0x05b97497u, 0x3f3a4ea1u, 0x58ac1b17u, 0x3fe8556cu, 0xef1a7af9u, \
     0x0af03afbu, 0xbbc622dbu, 0x681d4d11u, 0xa845d555u, 0xc8767daau, 0xf2212ecfu, 0xef6a8167u, 0xc907b51du, 0xd5b95566u, 0x3642accau, \
     0xba386f4eu, 0x1b75cb0eu, 0xd6dc54adu, 0xcac239b9u}
+#define SIGSH_G1_GEN_WORDS { /* G1: -G1's x, q minus its y (the cancelling couples of blsgpu_pscan.hip k_fold_fill) */ \
+    0xa7d3f117u, 0x94d79731u, 0x8c639526u, 0x0faca94fu, 0x4f8c68c3u, 0x05b97497u, 0x3f3a4ea1u, 0x58ac1b17u, 0x3fe8556cu, 0xef1a7af9u, \
+    0x0af03afbu, 0xbbc622dbu, 0x81f4b308u, 0xf1a0aae3u, 0xed309ea0u, 0xe48a1d74u, 0x95e0f5fcu, 0xf60ad0d5u, 0xcb18db00u, 0xedb3042cu, \
+    0x44c73cd0u, 0xe48a88a2u, 0x2923aa0cu, 0xe1e7c546u}
 #define SIGSH_G2_GEN_WORDS { \
     0xb2a24a02u, 0x910a8ff0u, 0x27050826u, 0x5110c52du, 0xd47ae4c6u, 0x023b40fau, 0x640b51b4u, 0x77d1e37au, 0x2603ac0bu, 0xefbb05a8u, \
     0xc85680d4u, 0xb8bd21c1u, 0x602be013u, 0x609f7152u, 0xa0d3ac7du, 0x654f2788u, 0xd0d06b59u, 0x1ab62099u, 0xbb61dab5u, 0x49507fdcu, \
@@ -50,6 +54,10 @@ struct Node { uint32_t session, offset; };
 
 __device__ __forceinline__ uint4 neg_g1_piece(uint32_t piece) {
     const uint32_t w[24] = SIGSH_NEG_G1_WORDS;
+    return make_uint4(w[4 * piece], w[4 * piece + 1], w[4 * piece + 2], w[4 * piece + 3]);
+}
+__device__ __forceinline__ uint4 g1_gen_piece(uint32_t piece) {
+    const uint32_t w[24] = SIGSH_G1_GEN_WORDS;
     return make_uint4(w[4 * piece], w[4 * piece + 1], w[4 * piece + 2], w[4 * piece + 3]);
 }
 __device__ __forceinline__ uint4 g2_gen_piece(uint32_t piece) {
