@@ -289,6 +289,7 @@ static int msm_small_groups(blsgpu_ctx* c, const void* d_pts, const void* d_scal
     const size_t upw = 64 / G::LP, per_group = k * blsgpu::SMUL_T * G::PJ * 4;
     size_t slice = ((size_t)2 << 30) / per_group / upw * upw;
     if (slice < upw) slice = upw;
+    slice = slice_len(c, slice, upw);
     if (slice > groups) slice = groups;
     const size_t units0 = (slice + upw - 1) / upw * upw, n0 = k * slice;
     size_t off = 0;
@@ -502,7 +503,7 @@ int check_n_add(size_t n, size_t n_add, const void* add) {
 int fix_mul_launch(blsgpu_ctx* c, const void* d_scalars, size_t n, const void* d_add, size_t n_add, void* d_out_aff, void* d_out_ser,
                    hipStream_t st) {
     const bool per = n_add == n && n_add > 1;
-    return for_slices(n, FIX_SLICE, [&](size_t lo, size_t m) {
+    return for_slices(n, slice_len(c, FIX_SLICE), [&](size_t lo, size_t m) {
         hipLaunchKernelGGL(blsgpu::g1fix::k_fix_mul, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint32_t*)c->d_fix_table,
                            (const uint32_t*)d_scalars + lo * 8, (uint32_t)m,
                            n_add ? (const uint32_t*)d_add + (per ? lo * 24 : 0) : nullptr, per ? 1u : 0u,
@@ -515,7 +516,7 @@ int fix_mul_launch(blsgpu_ctx* c, const void* d_scalars, size_t n, const void* d
 // enqueues out_i = s_i G1 on the scalar-independent schedule on `st` (caller: StreamGuard, fix_table(secret))
 int fix_mul_secret_launch(blsgpu_ctx* c, const void* d_scalars, size_t n, void* d_out_aff, void* d_out_ser, hipStream_t st) {
     KernelTimer kt(c, st, 9);
-    return for_slices(n, FIX_SLICE, [&](size_t lo, size_t m) {
+    return for_slices(n, slice_len(c, FIX_SLICE), [&](size_t lo, size_t m) {
         hipLaunchKernelGGL(blsgpu::g1fix::k_fix_mul_secret, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
                            (const uint32_t*)c->d_fix_table_secret, (const uint32_t*)d_scalars + lo * 8, (uint32_t)m,
                            d_out_aff ? (uint32_t*)d_out_aff + lo * 24 : nullptr, d_out_ser ? (uint32_t*)d_out_ser + lo * 12 : nullptr);
@@ -590,7 +591,8 @@ int hd_children_dev(blsgpu_ctx* c, const uint8_t chain_code[32], const uint8_t p
     const blsgpu::g1fix::HdParent P = hd_parent(chain_code, parent_pk_aff, parent_sk);
     StreamGuard sg(c, st);
     const bool pub = parent_sk == nullptr;
-    const size_t slice = pub ? (n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE) : 0;
+    const size_t host_slice = slice_len(c, FIX_HOST_SLICE);
+    const size_t slice = pub ? (n < host_slice ? n : host_slice) : 0;
     if (int rc = c->grow(B_FIX_WS, 256 + slice * 32)) return rc;
     char* ws = c->at<char>(B_FIX_WS);                                  // [0, 96) parent key, [128, 132) flag, [256, ..) i_left
     if (pub && check) {
@@ -607,7 +609,7 @@ int hd_children_dev(blsgpu_ctx* c, const uint8_t chain_code[32], const uint8_t p
         if (int rc = fix_table(c, st)) return rc;
     }
     if (pub) HIP_TRY(hipMemcpyAsync(ws, parent_pk_aff, 96, hipMemcpyHostToDevice, st));
-    return for_slices(n, pub ? slice : FIX_SLICE, [&](size_t lo, size_t m) {
+    return for_slices(n, pub ? slice : slice_len(c, FIX_SLICE), [&](size_t lo, size_t m) {
         uint32_t* scal = pub ? (uint32_t*)(ws + 256) : (uint32_t*)d_sk + lo * 8;
         hipLaunchKernelGGL(blsgpu::g1fix::k_hd_hmac, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, P, (const uint32_t*)d_idx + lo,
                            (uint32_t)m, (uint32_t*)d_chain + lo * 8, scal);
@@ -641,7 +643,7 @@ int hd_paths_dev(blsgpu_ctx* c, const void* d_parents, size_t n_parents, int pri
     if (n == 0) return 0;
     if (int rc = hd_paths_args(d_parents, n_parents, priv, d_idx, depth, n, d_chain, d_sk, d_pk_aff, d_pk_ser)) return rc;
     StreamGuard sg(c, st);
-    const size_t S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE;
+    const size_t HS = slice_len(c, FIX_HOST_SLICE), S = n < HS ? n : HS;
     if (int rc = c->grow(B_HDP_WS, 256 + S * (priv ? 160 : 256))) return rc;
     char* ws = c->at<char>(B_HDP_WS);
     if (check && (d_parent_of || !priv)) {
@@ -721,7 +723,7 @@ int keys_from_seeds_dev(blsgpu_ctx* c, const void* d_seeds, size_t seed_len, siz
     using namespace blsgpu::seeds;
     StreamGuard sg(c, st);
     const bool pk = d_pk_aff || d_pk_ser || d_parents;
-    const size_t S = n < SEED_SLICE ? n : SEED_SLICE;
+    const size_t SS = slice_len(c, SEED_SLICE), S = n < SS ? n : SS;
     const size_t ws_sk = d_sk ? 0 : S * 32, ws_aff = d_parents && !d_pk_aff ? S * 96 : 0;
     if (ws_sk + ws_aff) {
         if (int rc = c->grow(B_SEED_WS, ws_sk + ws_aff)) return rc;
@@ -797,7 +799,7 @@ int poly_eval_launch(blsgpu_ctx* c, size_t n_polys, size_t t, const void* d_poly
                      void* d_out_aff, hipStream_t st, bool secret = false) {
     char* ws = c->at<char>(B_POLY_WS);
     auto launches = [&]() {
-        return for_slices(n, FIX_SLICE, [&](size_t lo, size_t m) {
+        return for_slices(n, slice_len(c, FIX_SLICE), [&](size_t lo, size_t m) {
             hipLaunchKernelGGL(secret ? blsgpu::g1poly::k_poly_eval_secret : blsgpu::g1poly::k_poly_eval, dim3((unsigned)((m + 255) / 256)),
                                dim3(256), 0, st, (const uint32_t*)(secret ? c->d_fix_table_secret : c->d_fix_table),
                                (const uint32_t*)(ws + poly_ws_l28(n_polys)), (const uint32_t*)(ws + 256), (uint32_t)n_polys, (uint32_t)t,
@@ -825,8 +827,9 @@ int poly_check_dev(blsgpu_ctx* c, const void* d_commit, size_t n_polys, size_t t
     if (int rc = poly_ws(c, n_polys, t)) return rc;
     uint32_t* flag = c->at<uint32_t>(B_POLY_WS);
     HIP_TRY(hipMemsetAsync(flag, 0, 4, st));
-    for (size_t lo = 0; lo < n; lo += FIX_SLICE) {
-        const size_t m = n - lo < FIX_SLICE ? n - lo : FIX_SLICE;
+    const size_t FS = slice_len(c, FIX_SLICE);
+    for (size_t lo = 0; lo < n; lo += FS) {
+        const size_t m = n - lo < FS ? n - lo : FS;
         hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_poly + lo,
                            (uint32_t)m, (uint32_t)n_polys, flag);
         HIP_TRY(hipGetLastError());
@@ -844,9 +847,9 @@ int subgroup_dev(blsgpu_ctx* c, int g, const void* d_pts, size_t n, void* d_stat
     if (n == 0) return 0;
     if (!d_pts || !d_status) return fail(-EINVAL, "NULL argument");
     StreamGuard sg(c, st);
-    const size_t dw = g == 1 ? 24 : 48;
-    for (size_t lo = 0; lo < n; lo += FIX_SLICE) {
-        const size_t m = n - lo < FIX_SLICE ? n - lo : FIX_SLICE;
+    const size_t dw = g == 1 ? 24 : 48, FS = slice_len(c, FIX_SLICE);
+    for (size_t lo = 0; lo < n; lo += FS) {
+        const size_t m = n - lo < FS ? n - lo : FS;
         const dim3 grid((unsigned)((m + 255) / 256));
         const uint32_t* p = (const uint32_t*)d_pts + lo * dw;
         uint8_t* s = (uint8_t*)d_status + lo;
@@ -864,7 +867,7 @@ int subgroup_host(blsgpu_ctx* c, int g, const uint8_t* pts, size_t n, uint8_t* s
     if (n == 0) return 0;
     if (!pts || !status) return fail(-EINVAL, "NULL argument");
     HIP_TRY(hipSetDevice(c->device));
-    const size_t S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE;
+    const size_t HS = slice_len(c, FIX_HOST_SLICE), S = n < HS ? n : HS;
     Staging s(c);
     const int dp = s.in(pts, S, g == 1 ? 96 : 192), dst = s.out(status, S, 1);
     if (int rc = s.alloc()) return rc;
@@ -941,6 +944,7 @@ int sig_shares_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_t
     const size_t round_per = K * (sizeof(Node) + 3 * BLSGPU_G1_BYTES + 4 * BLSGPU_G2_BYTES + BLSGPU_FQ12_BYTES + 3);
     size_t slice = ((size_t)2 << 30) / (keep_per > round_per ? keep_per : round_per);
     if (slice < 1) slice = 1;
+    slice = slice_len(c, slice);
     if (slice > groups) slice = groups;
     const size_t n0 = slice * k;
     size_t off = 256;                                                        // [0, 4): the flag word of the index scan
@@ -953,9 +957,10 @@ int sig_shares_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_t
     char* const W = c->at<char>(B_SHR_WS);
     if (scan) {
         uint32_t bad = 0;
+        const size_t FS = slice_len(c, FIX_SLICE);
         if (int rc = scan_flag(W, st, bad, [&](uint32_t* flag) {
-                for (size_t lo = 0; lo < groups * k; lo += FIX_SLICE) {
-                    const size_t m = groups * k - lo < FIX_SLICE ? groups * k - lo : FIX_SLICE;
+                for (size_t lo = 0; lo < groups * k; lo += FS) {
+                    const size_t m = groups * k - lo < FS ? groups * k - lo : FS;
                     hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
                                        (const uint32_t*)d_key_idx + lo, (uint32_t)m, (uint32_t)n_keys, flag);
                 }
@@ -1052,7 +1057,7 @@ template <int DEG>
 int smul64_launch(blsgpu_ctx* c, const void* d_pts, size_t n_pts, const void* d_idx, const void* d_w, size_t n, void* d_out, void* d_out_inf,
                   hipStream_t st) {
     typedef blsgpu::SrtG<DEG> G;
-    const size_t upw = 64 / G::LP, S = blsgpu::SRT_LANES / G::LP;
+    const size_t upw = 64 / G::LP, S = slice_len(c, blsgpu::SRT_LANES / G::LP);
     const size_t m0 = n < S ? n : S, units0 = (m0 + upw - 1) / upw * upw, np0 = d_idx ? n_pts : m0;
     size_t off = 0;
     auto take = [&](size_t words) { size_t o = off; off += (words + 3) & ~(size_t)3; return o; };
@@ -1097,7 +1102,7 @@ template <int DEG>
 int mul_short_host(blsgpu_ctx* c, const uint8_t* pts, const uint8_t* w, size_t n, uint8_t* out, uint8_t* out_inf) {
     if (int rc = mul_short_args(c, pts, w, n, out)) return rc < 0 ? rc : 0;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE;
+    const size_t HS = slice_len(c, FIX_HOST_SLICE), S = n < HS ? n : HS;
     Staging s(c);
     const int dp = s.in(pts, S, 96 * DEG), dw = s.in(w, S, 8), dout = s.out(out, S, 96 * DEG), dinf = s.out(out_inf, S, 1);
     if (int rc = s.alloc()) return rc;
@@ -1147,7 +1152,7 @@ int verify_find_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_
     // slices of items whose kept arrays, and whose largest possible round (every leaf a node), stay below 2 GB each
     const size_t keep_per = 1 + 8 + 1 + 4 + BLSGPU_G2_BYTES + BLSGPU_G1_BYTES;
     const size_t round_per = 4 + 2 * BLSGPU_G2_BYTES + 1 + 2 * BLSGPU_G1_BYTES + 2 * BLSGPU_G2_BYTES + BLSGPU_FQ12_BYTES + 1;
-    size_t slice = (((size_t)2 << 30) - ((size_t)1 << 20)) / (keep_per > round_per ? keep_per : round_per);
+    size_t slice = slice_len(c, (((size_t)2 << 30) - ((size_t)1 << 20)) / (keep_per > round_per ? keep_per : round_per));
     if (slice > n) slice = n;
     size_t off = 256;                                                        // [0, 4): the flag word of the index scan, [4, 8): n_e
     auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
@@ -1158,9 +1163,10 @@ int verify_find_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_
     char* const W = c->at<char>(B_FIND_WS);
     if (scan) {
         uint32_t bad = 0;
+        const size_t FS = slice_len(c, FIX_SLICE);
         if (int rc = scan_flag(W, st, bad, [&](uint32_t* flag) {
-                for (size_t lo = 0; lo < n; lo += FIX_SLICE) {
-                    const size_t m = n - lo < FIX_SLICE ? n - lo : FIX_SLICE;
+                for (size_t lo = 0; lo < n; lo += FS) {
+                    const size_t m = n - lo < FS ? n - lo : FS;
                     hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
                                        (const uint32_t*)d_key_idx + lo, (uint32_t)m, (uint32_t)n_keys, flag);
                     hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
@@ -1338,7 +1344,7 @@ template <int DEG>
 int range_sums_dev(blsgpu_ctx* c, const void* d_pts, size_t n, const void* d_ranges, size_t m, void* d_out, void* d_flag, bool scan,
                    hipStream_t st) {
     namespace ps = blsgpu::pscan;
-    const size_t PJ = blsgpu::L28_PJ * DEG, SL = pscan_slice<DEG>(), S = n < SL ? n : SL;
+    const size_t PJ = blsgpu::L28_PJ * DEG, SL = slice_len(c, pscan_slice<DEG>()), S = n < SL ? n : SL;
     const bool single = n <= SL;
     StreamGuard sg(c, st);
     const size_t o_base = 256, o_basec = o_base + ((single ? 0 : m * PJ * 4 + 255) & ~(size_t)255);
@@ -1405,7 +1411,7 @@ int verify_find_folded_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys
     const size_t keep_per = 1 + 8 + 1 + 4 + 2 * (BLSGPU_G2_BYTES + BLSGPU_G1_BYTES) + 8;
     const size_t slot_per = 8 + 4 + 4 + 1 + 1 + 2 * BLSGPU_G1_BYTES + BLSGPU_G2_BYTES;
     const size_t round_per = 3 * slot_per + 4 + 8 + 4 + BLSGPU_G2_BYTES + 3 + BLSGPU_FQ12_BYTES;
-    size_t slice = (((size_t)2 << 30) - ((size_t)1 << 20)) / (keep_per > round_per ? keep_per : round_per);
+    size_t slice = slice_len(c, (((size_t)2 << 30) - ((size_t)1 << 20)) / (keep_per > round_per ? keep_per : round_per));
     if (slice > n) slice = n;
     const size_t rcap = (slice < n_msgs ? slice : n_msgs) + 1;                 // entries of the run table
     size_t off = 256;                                                        // [0, 4): the flag word of the index scan, [4, 8): n_e, [8, 12): the runs
@@ -1418,9 +1424,10 @@ int verify_find_folded_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys
     char* const W = c->at<char>(B_FIND_WS);
     if (scan) {
         uint32_t bad = 0;
+        const size_t FS = slice_len(c, FIX_SLICE);
         if (int rc = scan_flag(W, st, bad, [&](uint32_t* flag) {
-                for (size_t lo = 0; lo < n; lo += FIX_SLICE) {
-                    const size_t m = n - lo < FIX_SLICE ? n - lo : FIX_SLICE;
+                for (size_t lo = 0; lo < n; lo += FS) {
+                    const size_t m = n - lo < FS ? n - lo : FS;
                     hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
                                        (const uint32_t*)d_key_idx + lo, (uint32_t)m, (uint32_t)n_keys, flag);
                     hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
@@ -2900,7 +2907,7 @@ static int g2_smul_launch(blsgpu_ctx* c, const void* d_pts, size_t n_pts, const 
         hipLaunchKernelGGL(k_g2_smul_table, dim3(1), dim3(256), 0, st, (const uint32_t*)d_pts, 1u, table);
         HIP_TRY(hipGetLastError());
     }
-    return for_slices(n, SLICE, [&](size_t lo, size_t m) {
+    return for_slices(n, slice_len(c, SLICE), [&](size_t lo, size_t m) {
         const unsigned blocks = (unsigned)((m + PAIRS - 1) / PAIRS);
         if (!shared) hipLaunchKernelGGL(k_g2_smul_table, dim3(blocks), dim3(256), 0, st, (const uint32_t*)d_pts + lo * 48, (uint32_t)m, table);
         hipLaunchKernelGGL(k_g2_smul, dim3(blocks), dim3(256), 0, st, (const uint32_t*)table, shared ? 2u : (uint32_t)(2 * m), shared ? 1u : 0u,
@@ -2910,8 +2917,9 @@ static int g2_smul_launch(blsgpu_ctx* c, const void* d_pts, size_t n_pts, const 
         return 0;
     });
 }
-static size_t g2_smul_tables(size_t n_pts, size_t n) {            // points whose tables are held at a time
-    return n_pts == 1 ? 1 : (n < blsgpu::g2smul::SLICE ? n : blsgpu::g2smul::SLICE);
+static size_t g2_smul_tables(const blsgpu_ctx* c, size_t n_pts, size_t n) {   // points whose tables are held at a time
+    const size_t S = slice_len(c, blsgpu::g2smul::SLICE);
+    return n_pts == 1 ? 1 : (n < S ? n : S);
 }
 static int g2_smul_args(size_t n_sel, size_t n, const void* a, const void* b, const void* out_aff, const void* out_ser, const char* what) {
     if (n_sel != 1 && n_sel != n) return fail(-EINVAL, std::string(what) + " must be 1 or n");
@@ -2928,7 +2936,7 @@ BLSGPU_EXPORT int blsgpu_g2_mul_secret_dev(blsgpu_ctx* c, const void* d_pts, siz
     if (int rc = g2_smul_args(n_pts, n, d_pts, d_scalars, d_out_aff, d_out_ser, "n_pts")) return rc;
     HIP_TRY(hipSetDevice(c->device));
     StreamGuard sg(c, (hipStream_t)stream);
-    if (int rc = c->grow(B_SMUL_WS, g2_smul_tables(n_pts, n) * blsgpu::g2smul::TABLE_DW * 4)) return rc;
+    if (int rc = c->grow(B_SMUL_WS, g2_smul_tables(c, n_pts, n) * blsgpu::g2smul::TABLE_DW * 4)) return rc;
     return g2_smul_launch(c, d_pts, n_pts, d_scalars, n, d_out_aff, d_out_ser, d_out_inf, c->at<uint32_t>(B_SMUL_WS), (hipStream_t)stream);
 }
 BLSGPU_EXPORT int blsgpu_g2_mul_secret(blsgpu_ctx* c, const uint8_t* pts, size_t n_pts, const uint8_t* scalars, size_t n, uint8_t* out_aff,
@@ -2937,7 +2945,7 @@ BLSGPU_EXPORT int blsgpu_g2_mul_secret(blsgpu_ctx* c, const uint8_t* pts, size_t
     if (n == 0) return 0;
     if (int rc = g2_smul_args(n_pts, n, pts, scalars, out_aff, out_ser, "n_pts")) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t S = n < blsgpu::g2smul::SLICE ? n : blsgpu::g2smul::SLICE;
+    const size_t GS = slice_len(c, blsgpu::g2smul::SLICE), S = n < GS ? n : GS;
     const bool per = n_pts != 1;
     Staging s(c);
     const int dp = per ? s.in(pts, S, 192) : s.in(pts, 192), dsc = s.in(scalars, S, 32), daff = s.out(out_aff, S, 192),
@@ -2960,7 +2968,7 @@ BLSGPU_EXPORT int blsgpu_sign_dev(blsgpu_ctx* c, const void* d_sks, const void* 
     if (int rc = g2_smul_args(n_msg, n, d_sks, d_msg_hashes, d_out_aff, d_out_ser, "n_msg")) return rc;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
-    const size_t held = g2_smul_tables(n_msg, n), pts_bytes = (held * BLSGPU_G2_BYTES + 255) & ~(size_t)255;
+    const size_t held = g2_smul_tables(c, n_msg, n), pts_bytes = (held * BLSGPU_G2_BYTES + 255) & ~(size_t)255;
     if (int rc = c->grow(B_SMUL_WS, pts_bytes + held * blsgpu::g2smul::TABLE_DW * 4)) return rc;
     char* d_hm = c->at<char>(B_SMUL_WS);
     uint32_t* table = (uint32_t*)(d_hm + pts_bytes);
@@ -2978,7 +2986,7 @@ BLSGPU_EXPORT int blsgpu_sign(blsgpu_ctx* c, const uint8_t* sks, const uint8_t* 
     if (n == 0) return 0;
     if (int rc = g2_smul_args(n_msg, n, sks, msg_hashes, out_aff, out_ser, "n_msg")) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t S = n < blsgpu::g2smul::SLICE ? n : blsgpu::g2smul::SLICE;
+    const size_t GS = slice_len(c, blsgpu::g2smul::SLICE), S = n < GS ? n : GS;
     const bool per = n_msg != 1;
     Staging s(c);
     const int dsk = s.in(sks, S, 32), dh = per ? s.in(msg_hashes, S, 32) : s.in(msg_hashes, 32), daff = s.out(out_aff, S, 192),
@@ -3020,7 +3028,7 @@ static int g1_mul_gen_host(blsgpu_ctx* c, const uint8_t* scalars, size_t n, cons
     if (!secret)
         if (int rc = check_n_add(n, n_add, add)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE;
+    const size_t HS = slice_len(c, FIX_HOST_SLICE), S = n < HS ? n : HS;
     const bool per = n_add == n && n_add > 1;
     Staging s(c);
     const int dsc = s.in(scalars, S, 32), dadd = per ? s.in(add, S, 96) : s.in(n_add ? add : nullptr, 96), daff = s.out(out_aff, S, 96),
@@ -3067,7 +3075,7 @@ BLSGPU_EXPORT int blsgpu_hd_children(blsgpu_ctx* c, const uint8_t chain_code[32]
         for (size_t i = 0; i < n; i++)
             if (indices[i] >> 31) return fail(-EINVAL, "Cannot derive hardened children from public key");
     HIP_TRY(hipSetDevice(c->device));
-    const size_t S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE;
+    const size_t HS = slice_len(c, FIX_HOST_SLICE), S = n < HS ? n : HS;
     Staging s(c);
     const int didx = s.in(indices, S, 4), dchain = s.out(out_chain, S, 32), dsk = s.out(parent_sk ? out_sk : nullptr, S, 32),
               daff = s.out(out_pk_aff, S, 96), dser = s.out(out_pk_ser, S, 48);
@@ -3102,7 +3110,7 @@ static int hd_paths_host(blsgpu_ctx* c, const uint8_t* parents, size_t n_parents
         for (size_t i = 0; i < n * depth; i++)
             if (indices[i] >> 31) return fail(-EINVAL, "Cannot derive hardened children from public key");
     HIP_TRY(hipSetDevice(c->device));
-    const size_t S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE;
+    const size_t HS = slice_len(c, FIX_HOST_SLICE), S = n < HS ? n : HS;
     Staging s(c);
     const int dpar = s.in(parents, n_parents * BLSGPU_HD_PARENT_BYTES), dof = s.in(parent_of, S, 4), didx = s.in(indices, S, depth * 4),
               dchain = s.out(out_chain, S, 32), dsk = s.out(priv ? out_sk : nullptr, S, 32), daff = s.out(out_pk_aff, S, 96),
@@ -3160,7 +3168,7 @@ BLSGPU_EXPORT int blsgpu_keys_from_seeds(blsgpu_ctx* c, const uint8_t* seeds, si
     if (int rc = seeds_args(c, seeds, seed_len, n, hd, out_sk, out_chain, out_pk_aff, out_pk_ser, out_parents)) return rc < 0 ? rc : 0;
     HIP_TRY(hipSetDevice(c->device));
     // about 64 MB of staging per slice
-    const size_t fit = ((size_t)1 << 26) / (seed_len + 368);
+    const size_t fit = slice_len(c, ((size_t)1 << 26) / (seed_len + 368));
     const size_t S = n < fit ? n : fit;
     Staging s(c);
     const int dseed = s.in(seed_len ? seeds : nullptr, S, seed_len), dsk = s.out(out_sk, S, 32), dchain = s.out(out_chain, S, 32),
@@ -3186,7 +3194,7 @@ static int poly_check_host(blsgpu_ctx* c, const uint8_t* commit, size_t n_polys,
     for (size_t i = 0; i < n; i++)
         if (poly[i] >= n_polys) return fail(-EINVAL, "polynomial index out of range");
     HIP_TRY(hipSetDevice(c->device));
-    const size_t S = n < FIX_HOST_SLICE ? n : FIX_HOST_SLICE;
+    const size_t HS = slice_len(c, FIX_HOST_SLICE), S = n < HS ? n : HS;
     Staging st(c);
     const int dcommit = st.in(commit, n_polys * t * 96), dpoly = st.in(poly, S, 4), dx = st.in(x, S, 32), ds = st.in(s, S, 32),
               dstatus = st.out(status, S, 1), daff = st.out(out_aff, S, 96);
@@ -3444,7 +3452,7 @@ BLSGPU_EXPORT int blsgpu_threshold_deal_secret(blsgpu_ctx* c, const uint8_t* coe
     if (int rc = deal_args(c, coeffs, n_polys, t, x, n_x, out_commit_aff, out_frag)) return rc < 0 ? rc : 0;
     HIP_TRY(hipSetDevice(c->device));
     // whole polynomials per staged slice: about 64 MB of staging
-    const size_t per_poly = t * (32 + 96) + (out_frag ? n_x * 32 : 0), fit = ((size_t)1 << 26) / per_poly;
+    const size_t per_poly = t * (32 + 96) + (out_frag ? n_x * 32 : 0), fit = slice_len(c, ((size_t)1 << 26) / per_poly);
     const size_t S = n_polys < fit ? n_polys : (fit ? fit : 1);
     Staging s(c);
     const int dco = s.in(coeffs, S, t * 32), dx = s.in(out_frag ? x : nullptr, n_x * 32), dcm = s.out(out_commit_aff, S, t * 96),
@@ -3487,7 +3495,7 @@ BLSGPU_EXPORT int blsgpu_fr_sum_secret(blsgpu_ctx* c, const uint8_t* y, size_t k
     if (int rc = fr_sum_args(c, y, k, groups, out)) return rc < 0 ? rc : 0;
     HIP_TRY(hipSetDevice(c->device));
     // whole groups per staged slice: about 64 MB of staging
-    const size_t fit = ((size_t)1 << 26) / (k * 32 + 176);
+    const size_t fit = slice_len(c, ((size_t)1 << 26) / (k * 32 + 176));
     const size_t S = groups < fit ? groups : (fit ? fit : 1);
     Staging s(c);
     const int dy = s.in(y, S, k * 32), dout = s.out(out, S, 32), daff = s.out(out_pk_aff, S, 96), dser = s.out(out_pk_ser, S, 48);
@@ -3510,7 +3518,7 @@ BLSGPU_EXPORT int blsgpu_sign_threshold_dev(blsgpu_ctx* c, const void* d_sks, co
     hipStream_t st = (hipStream_t)stream;
     const size_t n = k * groups;
     const bool shared = n_msg == 1;
-    const size_t held = g2_smul_tables(shared ? 1 : n, n);
+    const size_t held = g2_smul_tables(c, shared ? 1 : n, n);
     const size_t sc_bytes = (n * 32 + 255) & ~(size_t)255, hm_bytes = (n_msg * BLSGPU_G2_BYTES + 255) & ~(size_t)255;
     if (int rc = c->grow(B_LAGR_WS, n * 32)) return rc;
     if (int rc = c->grow(B_FRS_WS, sc_bytes + (shared ? 0 : held * BLSGPU_G2_BYTES))) return rc;
@@ -3530,7 +3538,7 @@ BLSGPU_EXPORT int blsgpu_sign_threshold_dev(blsgpu_ctx* c, const void* d_sks, co
     if (int rc = map_to_g2_impl(c, d_msg_hashes, n_msg, d_hm, st, true)) return rc;
     StreamGuard sg(c, st);
     if (shared) return g2_smul_launch(c, d_hm, 1, d_sc, n, d_out_aff, d_out_ser, d_out_inf, table, st);
-    return for_slices(n, SLICE, [&](size_t lo, size_t m) {
+    return for_slices(n, held, [&](size_t lo, size_t m) {
         hipLaunchKernelGGL(blsgpu::frsec::k_g2_spread, dim3((unsigned)((m * 48 + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_hm, (uint32_t)k,
                            lo, (uint32_t)m, (uint32_t*)d_rep);
         HIP_TRY(hipGetLastError());

@@ -120,6 +120,7 @@ struct blsgpu_ctx {
     size_t h2c_jacobi_threshold = 16384;   // ... from this many messages (below, five parallel powers finish sooner than three serial symbol loops)
     size_t h2c_quad_max = 16384;       // ... on lane QUADS up to this many messages (k_h2c_clear_quads: half the depth while the chip is not full)
     bool test_ls_nomem = false;        // test hook (BLSGPU_TEST_LS_NOMEM=1): the line-stream workspace "cannot be allocated"
+    size_t test_slice_cap = 0;         // test hook (BLSGPU_TEST_SLICE_CAP=items): the host loops cut their work into slices of at most this many items (slice_len), so a test crosses every slice boundary with a few items; 0: the natural slice lengths
     size_t msm_sort_threshold = 1;      // points from which one G1 sum with scalars uses sorted buckets (k_srt_*): since the tail runs on the wide machine (round 5) they win at every size -- 1 point 1.24 ms against 1.63, 8192 points 1.45 against 2.59 (profiles/r05_c5_window_bits.txt)
     size_t msm_sort2_threshold = 1;     // the same for ONE G2 sum with scalars (round 5: BLS.aggregate_sigs(secure) as a multi-scalar sum)
     size_t msm_plain_threshold = 2;     // points from which ONE plain sum (no scalars) runs on the register kernels (k_sum_chunks + folds; round 5) instead of the wavefront VM's k_msm
@@ -202,6 +203,7 @@ const Knob KNOBS[] = {
     {"BLSGPU_H2C_REG_THRESHOLD", &blsgpu_ctx::h2c_reg_threshold},
     {"BLSGPU_H2C_QUAD_MAX", &blsgpu_ctx::h2c_quad_max},
     {"BLSGPU_TEST_LS_NOMEM", &blsgpu_ctx::test_ls_nomem},
+    {"BLSGPU_TEST_SLICE_CAP", &blsgpu_ctx::test_slice_cap},
     {"BLSGPU_H2C_JACOBI", &blsgpu_ctx::h2c_jacobi},
     {"BLSGPU_H2C_JACOBI_THRESHOLD", &blsgpu_ctx::h2c_jacobi_threshold},
     {"BLSGPU_H2C_LANE_THRESHOLD", &blsgpu_ctx::h2c_lane_threshold},
@@ -303,6 +305,16 @@ struct Staging {
         return 0;
     }
 };
+
+// The slice length of a host loop: `natural` -- unless the test hook caps it (blsgpu_ctx::test_slice_cap), then at most the cap
+// rounded up to a whole number of `unit`s and never less than one unit.  Every workspace size that follows from a slice length
+// is derived from this value, so loop and buffer cannot disagree.
+size_t slice_len(const blsgpu_ctx* c, size_t natural, size_t unit = 1) {
+    if (!c->test_slice_cap) return natural;
+    const size_t cap = (c->test_slice_cap + unit - 1) / unit * unit;
+    const size_t s = natural < cap ? natural : cap;
+    return s < unit ? unit : s;
+}
 
 // body(lo, m) over [0, n) in runs of at most `step` items
 template <class F>
