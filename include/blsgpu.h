@@ -601,6 +601,38 @@ int blsgpu_g1_range_sums_dev(blsgpu_ctx *ctx, const void *d_pts, size_t n, const
 int blsgpu_g2_range_sums_dev(blsgpu_ctx *ctx, const void *d_pts, size_t n, const void *d_ranges, size_t m, void *d_out_aff,
                              void *d_out_flag, void *stream);
 
+/* RAGGED multi-scalar sums (csrc/blsgpu_msmr.hip; vmgen/msmr_model.py is its specification):
+ * out_j = sum_{i in [begin_j, end_j)} scalars[i] * pts[i] for m ranges of ANY lengths over n points, in one call and with
+ * nothing padded.  Every range is cut into chunks of at most 8 consecutive points; one chunk runs on one lane (G1) or lane pair
+ * (G2) on the fixed 4-bit windows of blsgpu_g1_msm's small-group kernel -- 252 doublings per chunk, 14 mixed and 64 complete
+ * additions per point --, and the chunks' partial sums are summed per range by the passes of blsgpu_g?_range_sums.
+ * pts: n x 96 (G1) / n x 192 (G2) bytes affine, (0,0) = infinity.  scalars: n x 32 bytes big-endian, taken as the 256-bit
+ * integers they are (not reduced).  ranges: m x 2 uint32 (begin, end), begin <= end <= n; ranges may overlap, repeat or be empty,
+ * and each pays for its own chunks.  out_aff: m points, (0,0) for infinity.  out_flag: m bytes -- 0 a finite sum, 1 infinity
+ * (an empty range, a range of (0,0) points, zero scalars, terms that cancel), 2 the range holds a point that is neither (0,0)
+ * nor on the curve: its output is (0,0).  Such a point enters every sum as infinity, so the ranges that do not hold it are not
+ * disturbed.  The points are not checked for the prime-order subgroups (both curves have odd order: the complete formulas
+ * hold for every point of either curve).
+ * Equal-length ranges [j k, (j + 1) k) over on-curve points give the bytes of blsgpu_g1_msm / blsgpu_g2_msm(scalars, k, groups),
+ * and out_inf == (flag == 1).
+ * Both forms check the ranges and count the chunks on the device and synchronise ONCE to read the result, before anything is
+ * written to the outputs; the rest is enqueued.  The chunks are processed in slices whose tables stay below 2 GB (at most 99 840
+ * chunks in G1, 49 920 in G2, a launch); the workspace counts in BLSGPU_WS_TOTAL.
+ * -EINVAL before anything is written: a NULL required buffer (pts or scalars with n > 0; ranges, out_aff or out_flag with
+ * m > 0; scalars == NULL is an error here: plain sums are blsgpu_g?_range_sums' business), a range with begin > end or end > n,
+ * 2^31 chunks or more in all.  m == 0 writes nothing and returns 0; n == 0 with every range empty writes m times (0,0) and
+ * flag 1.  All of this is PUBLIC data: not constant-time. */
+int blsgpu_g1_msm_ranges(blsgpu_ctx *ctx, const uint8_t *pts, const uint8_t *scalars, size_t n, const uint32_t *ranges, size_t m,
+                         uint8_t *out_aff, uint8_t *out_flag);
+int blsgpu_g2_msm_ranges(blsgpu_ctx *ctx, const uint8_t *pts, const uint8_t *scalars, size_t n, const uint32_t *ranges, size_t m,
+                         uint8_t *out_aff, uint8_t *out_flag);
+/* The same with every buffer in device memory (points 16-byte aligned, scalars and ranges 4-byte), on `stream`; the one
+ * synchronisation is of that stream. */
+int blsgpu_g1_msm_ranges_dev(blsgpu_ctx *ctx, const void *d_pts, const void *d_scalars, size_t n, const void *d_ranges, size_t m,
+                             void *d_out_aff, void *d_out_flag, void *stream);
+int blsgpu_g2_msm_ranges_dev(blsgpu_ctx *ctx, const void *d_pts, const void *d_scalars, size_t n, const void *d_ranges, size_t m,
+                             void *d_out_aff, void *d_out_flag, void *stream);
+
 /* blsgpu_verify_find with the items of one message FOLDED inside every node: arguments, status bytes and stats as there, with
  * ONE precondition -- msg_idx is non-decreasing over the items (a decrease is -EINVAL before anything is written; the _dev form
  * finds it in the device scan that checks the indices).  The dense order keeps input order, so every message is one

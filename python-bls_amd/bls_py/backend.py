@@ -94,6 +94,10 @@ def use(provider):
     weights) -> (affine bytes, [is_inf]) for 64-bit public weights.  Optional extension (without it
     BLS.verify_batch_find(fold=True) takes the path of fold=False): verify_find_folded, verify_find's arguments and results
     with msg_idx non-decreasing; with it g1_range_sums / g2_range_sums(pts, ranges) -> (affine bytes, flag bytes).
+    Optional extension (for callers; bls.py itself keeps its padded and per-length-class g1_msm calls, which measured faster
+    on the skewed shape: DESIGN.md section 2w): g1_msm_ranges / g2_msm_ranges(pts, scalars, ranges) -> (affine bytes, flag
+    bytes: 0 finite, 1 infinity, 2 a point off the curve in the range) -- sum_{i in [begin, end)} scalars[i] pts[i] for ranges
+    (begin, end) of any lengths over one list of points, scalars as ints below 2^256 or 32-byte big-endian values.
     Extensions are looked up by extension(name), not by hasattr: a stand-in offers one as an attribute of that name, the
     HipProvider's come from EXTENSIONS.  Optional (without it PrivateKey.from_seed_batch and
     ExtendedPrivateKey.from_seed_batch run the per-seed host calls): keys_from_seeds(seeds, seed_len, n, hd) -> (key bytes,
@@ -111,16 +115,19 @@ EXTENSIONS = {"keys_from_seeds": "_native_seeds"}
 FIND_EXTENSIONS = {"g1_mul_short": "_native_find", "g2_mul_short": "_native_find", "verify_find": "_native_find"}
 # ... and the sums over ranges of points and the batch verification that folds shared messages (BLS.verify_batch_find(fold=True)).
 RANGE_EXTENSIONS = {"g1_range_sums": "_native_ranges", "g2_range_sums": "_native_ranges", "verify_find_folded": "_native_ranges"}
+# ... and the multi-scalar sums over ranges of any lengths.
+MSM_RANGE_EXTENSIONS = {"g1_msm_ranges": "_native_msmr", "g2_msm_ranges": "_native_msmr"}
 
 
 def extension(name):
     """The installed provider's extension `name`: the provider's own attribute of that name if it has one (stand-ins), for
-    a HipProvider the function of EXTENSIONS (or FIND_EXTENSIONS, RANGE_EXTENSIONS) bound to its engine, otherwise None."""
+    a HipProvider the function of EXTENSIONS (or FIND_EXTENSIONS, RANGE_EXTENSIONS, MSM_RANGE_EXTENSIONS) bound to its engine,
+    otherwise None."""
     prov = get()
     fn = getattr(prov, name, None)
     if fn is not None:
         return fn
-    where = EXTENSIONS.get(name) or FIND_EXTENSIONS.get(name) or RANGE_EXTENSIONS.get(name)
+    where = EXTENSIONS.get(name) or FIND_EXTENSIONS.get(name) or RANGE_EXTENSIONS.get(name) or MSM_RANGE_EXTENSIONS.get(name)
     if isinstance(prov, HipProvider) and where:
         import functools
         import importlib

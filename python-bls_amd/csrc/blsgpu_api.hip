@@ -34,6 +34,7 @@
 #include "blsgpu_g2smul.hip"
 #include "blsgpu_smul64.hip"
 #include "blsgpu_pscan.hip"
+#include "blsgpu_msmr.hip"
 #include "blsgpu_h2c.hip"
 #include "blsgpu_h2cw.hip"
 #include "blsgpu_msmw.hip"
@@ -1341,12 +1342,20 @@ int range_sums_args(const blsgpu_ctx* c, const void* pts, size_t n, const void* 
 // holds its end.  With more than one slice the record at a range's begin is copied beside the range (B_PSCAN_RANGE) while its
 // slice is there.  `scan`: the _dev form's device scan of the ranges first -- one synchronisation, before anything is written.
 template <int DEG>
+int range_sums_run(blsgpu_ctx* c, const void* d_pts, size_t n, const void* d_ranges, size_t m, void* d_out, void* d_flag, bool scan, hipStream_t st);
+template <int DEG>
 int range_sums_dev(blsgpu_ctx* c, const void* d_pts, size_t n, const void* d_ranges, size_t m, void* d_out, void* d_flag, bool scan,
+                   hipStream_t st) {
+    StreamGuard sg(c, st);
+    return range_sums_run<DEG>(c, d_pts, n, d_ranges, m, d_out, d_flag, scan, st);
+}
+// ... the same inside a caller's StreamGuard (msm_ranges_dev sums its chunk partials with scan = false)
+template <int DEG>
+int range_sums_run(blsgpu_ctx* c, const void* d_pts, size_t n, const void* d_ranges, size_t m, void* d_out, void* d_flag, bool scan,
                    hipStream_t st) {
     namespace ps = blsgpu::pscan;
     const size_t PJ = blsgpu::L28_PJ * DEG, SL = slice_len(c, pscan_slice<DEG>()), S = n < SL ? n : SL;
     const bool single = n <= SL;
-    StreamGuard sg(c, st);
     const size_t o_base = 256, o_basec = o_base + ((single ? 0 : m * PJ * 4 + 255) & ~(size_t)255);
     if (int rc = c->grow(B_PSCAN_RANGE, o_basec + (single ? 0 : m * 4))) return rc;
     char* const R = c->at<char>(B_PSCAN_RANGE);
@@ -1389,6 +1398,100 @@ int range_sums_host(blsgpu_ctx* c, const uint8_t* pts, size_t n, const uint32_t*
     if (int rc = s.alloc()) return rc;
     if (int rc = s.up()) return rc;
     if (int rc = range_sums_dev<DEG>(c, s.opt(dp), n, s.at(dr), m, s.at(dout), s.at(df), false, nullptr)) return rc;
+    return s.down();
+}
+
+// ------------------------------------------------------------ ragged multi-scalar sums (blsgpu_msmr.hip) --
+// the argument checks of blsgpu_g?_msm_ranges* (before anything is written); 1: nothing to do
+int msm_ranges_args(const blsgpu_ctx* c, const void* pts, const void* scalars, size_t n, const void* ranges, size_t m, const void* out,
+                    const void* flag) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if ((n && (!pts || !scalars)) || (m && (!ranges || !out || !flag))) return fail(-EINVAL, "NULL argument");
+    if (n > 0xFFFFFFF0ull || m > 0x7FFFFFF0ull / blsgpu::SrtG<2>::LP) return fail(-EINVAL, "batch too large");
+    return m == 0 ? 1 : 0;
+}
+// The ranges are checked and cut into chunks of at most eight points on the device (k_msmr_count, k_msmr_scan, k_msmr_fill); ONE
+// synchronisation reads the check flag and the number of chunks, before anything is written to the outputs.  Then the n points
+// are prepared once, the chunks go through k_smul_seg in slices whose tables stay below 2 GB and whose launches take at most
+// SRT_LANES / LP units, and the chunk partials -- affine points in chunk order, range j's being the chunks [first[j],
+// first[j + 1]) -- are summed per range by the range-sum passes (range_sums_run without its scan).  A range one of whose chunks
+// counted a point off the curve gets flag 2 last (k_msmr_offcurve over the prefix sums of the counts).  A range of a single
+// chunk takes the same passes (writing it straight from k_smul_seg: NOT MEASURED).
+// Workspace: B_MSM_PART holds the head words, the chunk counts, first[] and the chunk ranges; B_BUCKETS the prepared points, the
+// chunk table, the partials, the counts with their prefix sums and one slice's tables.
+template <int DEG>
+int msm_ranges_dev(blsgpu_ctx* c, const void* d_pts, const void* d_scalars, size_t n, const void* d_ranges, size_t m, void* d_out,
+                   void* d_flag, hipStream_t st) {
+    namespace mr = blsgpu::msmr;
+    typedef blsgpu::SrtG<DEG> G;
+    StreamGuard sg(c, st);
+    auto words = [](size_t w) { return (w + 63) & ~(size_t)63; };                 // every region on a 256-byte boundary
+    const size_t h_cnt = 64, h_first = h_cnt + words(m), h_cr = h_first + words(m + 1), h_end = h_cr + words(2 * m);
+    if (int rc = c->grow(B_MSM_PART, h_end * 4)) return rc;
+    uint32_t* const Hd = c->at<uint32_t>(B_MSM_PART);
+    HIP_TRY(hipMemsetAsync(Hd, 0, 16, st));
+    hipLaunchKernelGGL(mr::k_msmr_count, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_ranges, (uint32_t)m, (uint32_t)n, Hd,
+                       Hd + h_cnt);
+    hipLaunchKernelGGL(mr::k_msmr_scan, dim3(1), dim3(mr::SCAN_THREADS), 0, st, Hd + h_cnt, (uint32_t)m, Hd + h_first);
+    HIP_TRY(hipGetLastError());
+    uint32_t head[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(head, Hd, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (head[0]) return fail(-EINVAL, "range out of order or past the points");
+    const uint64_t total64 = (uint64_t)head[2] | ((uint64_t)head[3] << 32);
+    if (total64 >= ((uint64_t)1 << 31)) return fail(-EINVAL, "too many chunks");
+    const size_t total = (size_t)total64;
+    // slices of chunks: tables below 2 GB, a launch of at most SRT_LANES / LP units
+    const size_t upw = 64 / G::LP, per_unit = (size_t)mr::CHUNK * blsgpu::SMUL_T * G::PJ * 4;
+    size_t slice = ((size_t)2 << 30) / per_unit / upw * upw;
+    if (slice > blsgpu::SRT_LANES / G::LP) slice = blsgpu::SRT_LANES / G::LP;
+    slice = slice_len(c, slice, upw);
+    const size_t units0 = ((total < slice ? total : slice) + upw - 1) / upw * upw;
+    const size_t o_prep = 0, o_live = o_prep + words(n * blsgpu::L28_AFF * DEG), o_tab = o_live + words((n + 3) / 4), o_part = o_tab + words(2 * total),
+                 o_bad = o_part + words(total * 24 * DEG), o_bpre = o_bad + words(total), o_table = o_bpre + words(total + 1),
+                 o_end = o_table + units0 * mr::CHUNK * blsgpu::SMUL_T * G::PJ;
+    if (int rc = c->grow(B_BUCKETS, o_end * 4)) return rc;
+    uint32_t* const W = c->at<uint32_t>(B_BUCKETS);
+    uint8_t* const live = (uint8_t*)(W + o_live);
+    const size_t fill = total > m ? total : m;
+    hipLaunchKernelGGL(mr::k_msmr_fill, dim3((unsigned)((fill + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_ranges, Hd + h_first, (uint32_t)m,
+                       (uint32_t)total, W + o_tab, Hd + h_cr);
+    HIP_TRY(hipGetLastError());
+    if (total) {
+        hipLaunchKernelGGL(blsgpu::k_lane_prep<DEG>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_pts, (uint32_t)n, W + o_prep, live);
+        HIP_TRY(hipGetLastError());
+        if (int rc = for_slices(total, slice, [&](size_t lo, size_t k) {
+                const size_t units = (k + upw - 1) / upw * upw;
+                hipLaunchKernelGGL(mr::k_smul_seg<DEG>, dim3((unsigned)(units * G::LP / 64)), dim3(64), 0, st, W + o_prep, live, (const uint32_t*)d_scalars,
+                                   W + o_tab + 2 * lo, (uint32_t)k, W + o_table, W + o_part + lo * 24 * DEG, W + o_bad + lo);
+                HIP_TRY(hipGetLastError());
+                return 0;
+            }))
+            return rc;
+        hipLaunchKernelGGL(mr::k_msmr_scan, dim3(1), dim3(mr::SCAN_THREADS), 0, st, W + o_bad, (uint32_t)total, W + o_bpre);
+        HIP_TRY(hipGetLastError());
+    }
+    if (int rc = range_sums_run<DEG>(c, W + o_part, total, Hd + h_cr, m, d_out, d_flag, false, st)) return rc;
+    if (total) {
+        hipLaunchKernelGGL(mr::k_msmr_offcurve<DEG>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, W + o_bpre, Hd + h_first, (uint32_t)m,
+                           (uint32_t*)d_out, (uint8_t*)d_flag);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+template <int DEG>
+int msm_ranges_host(blsgpu_ctx* c, const uint8_t* pts, const uint8_t* scalars, size_t n, const uint32_t* ranges, size_t m, uint8_t* out,
+                    uint8_t* flag) {
+    if (int rc = msm_ranges_args(c, pts, scalars, n, ranges, m, out, flag)) return rc < 0 ? rc : 0;
+    for (size_t i = 0; i < m; i++)
+        if (ranges[2 * i] > ranges[2 * i + 1] || ranges[2 * i + 1] > n) return fail(-EINVAL, "range out of order or past the points");
+    HIP_TRY(hipSetDevice(c->device));
+    Staging s(c);
+    const int dp = s.in(n ? pts : nullptr, n * 96 * DEG), dsc = s.in(n ? scalars : nullptr, n * 32), dr = s.in(ranges, m * 8),
+              dout = s.out(out, m * 96 * DEG), df = s.out(flag, m);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    if (int rc = msm_ranges_dev<DEG>(c, s.opt(dp), s.opt(dsc), n, s.at(dr), m, s.at(dout), s.at(df), nullptr)) return rc;
     return s.down();
 }
 
@@ -3408,6 +3511,26 @@ BLSGPU_EXPORT int blsgpu_g2_range_sums_dev(blsgpu_ctx* c, const void* d_pts, siz
     if (int rc = range_sums_args(c, d_pts, n, d_ranges, m, d_out_aff, d_out_flag)) return rc < 0 ? rc : 0;
     HIP_TRY(hipSetDevice(c->device));
     return range_sums_dev<2>(c, d_pts, n, d_ranges, m, d_out_aff, d_out_flag, true, (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_g1_msm_ranges(blsgpu_ctx* c, const uint8_t* pts, const uint8_t* scalars, size_t n, const uint32_t* ranges, size_t m,
+                                       uint8_t* out_aff, uint8_t* out_flag) {
+    return msm_ranges_host<1>(c, pts, scalars, n, ranges, m, out_aff, out_flag);
+}
+BLSGPU_EXPORT int blsgpu_g2_msm_ranges(blsgpu_ctx* c, const uint8_t* pts, const uint8_t* scalars, size_t n, const uint32_t* ranges, size_t m,
+                                       uint8_t* out_aff, uint8_t* out_flag) {
+    return msm_ranges_host<2>(c, pts, scalars, n, ranges, m, out_aff, out_flag);
+}
+BLSGPU_EXPORT int blsgpu_g1_msm_ranges_dev(blsgpu_ctx* c, const void* d_pts, const void* d_scalars, size_t n, const void* d_ranges, size_t m,
+                                           void* d_out_aff, void* d_out_flag, void* stream) {
+    if (int rc = msm_ranges_args(c, d_pts, d_scalars, n, d_ranges, m, d_out_aff, d_out_flag)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return msm_ranges_dev<1>(c, d_pts, d_scalars, n, d_ranges, m, d_out_aff, d_out_flag, (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_g2_msm_ranges_dev(blsgpu_ctx* c, const void* d_pts, const void* d_scalars, size_t n, const void* d_ranges, size_t m,
+                                           void* d_out_aff, void* d_out_flag, void* stream) {
+    if (int rc = msm_ranges_args(c, d_pts, d_scalars, n, d_ranges, m, d_out_aff, d_out_flag)) return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return msm_ranges_dev<2>(c, d_pts, d_scalars, n, d_ranges, m, d_out_aff, d_out_flag, (hipStream_t)stream);
 }
 BLSGPU_EXPORT int blsgpu_verify_find_folded_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_t n_keys, const void* d_key_idx,
                                                 const void* d_msg_hashes, size_t n_msgs, const void* d_msg_idx, const void* d_weights, size_t n,

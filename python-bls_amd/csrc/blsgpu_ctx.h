@@ -51,8 +51,8 @@ enum BufId {
     B_BAD,               // one byte per pair: left to the slow program
     B_DEGEN,             // u32 [0] count, [1 ..] block indices of degenerate pairs (k_miller_slow's work list)
     B_EXFLAGS,           // blsgpu_miller_loop_batch's fast form: the caller's flags with "py = 0" marked (2 bytes per pair)
-    B_MSM_PART,          // MSM partials; the stage images of decompression and hash to G2
-    B_BUCKETS,           // the bucket sums' buckets (HBM); the workspace of the sorted, plain and small-group sums
+    B_MSM_PART,          // MSM partials; the stage images of decompression and hash to G2; blsgpu_g?_msm_ranges*: the head words, the chunk counts, first_chunk[] and the chunk ranges
+    B_BUCKETS,           // the bucket sums' buckets (HBM); the workspace of the sorted, plain and small-group sums; blsgpu_g?_msm_ranges*: the prepared points, the chunk table, the partials, the off-curve counts and one slice's tables (k_smul_seg)
     B_FEXP_WS,           // the slots of k_fexp_team
     B_H2C_WS,            // the lane-private point slots of k_h2c_clear_pairs
     B_FIX_WS,            // blsgpu_hd_children*: the parent key, a flag word and one slice of HMAC outputs
