@@ -41,6 +41,7 @@
 #include "blsgpu_probe.hip"
 
 #if BLSGPU_EMIT(BLSGPU_TU_HOST)
+#include "bisect_plan.h"
 #include "blsgpu_ctx.h"
 
 namespace {
@@ -581,6 +582,40 @@ int scan_flag(void* d_flag, hipStream_t st, uint32_t& flag, F launch) {
     return 0;
 }
 
+// The rounds of a bisecting check on `st` (bisect::run owns the loop).  `round(nodes, len, d_verdict)` enqueues one round -- it may
+// reorder `nodes` first -- and names the device bytes that get one verdict per node, in the order of `nodes`; they come back here,
+// the one synchronisation of a round.  What a round uploads asynchronously from the host is `nodes` itself or storage that only
+// `round` writes: nothing touches `nodes` between a round and its synchronisation, and `round` runs again only after it.
+template <class N, class Round>
+int bisect_rounds(bisect::State<N>& b, size_t top, size_t limit, hipStream_t st, Round round) {
+    return bisect::run(b, top, limit, [&](std::vector<N>& nodes, size_t len, uint8_t* verdict) {
+        const void* d_verdict = nullptr;
+        if (int rc = round(nodes, len, d_verdict)) return rc;
+        HIP_TRY(hipMemcpyAsync(verdict, d_verdict, nodes.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return 0;
+    });
+}
+// the validity scan of the three checks' _dev forms: key_idx < n_keys and, with d_msg_idx, msg_idx < n_msgs (bit 0 of `bad`)
+// over n entries in launches of FIX_SLICE; `mono`: that msg_idx does not decrease as well (another bit)
+int scan_indices(blsgpu_ctx* c, void* d_flag, const void* d_key_idx, size_t n_keys, const void* d_msg_idx, size_t n_msgs, size_t n, bool mono,
+                 uint32_t& bad, hipStream_t st) {
+    const size_t FS = slice_len(c, FIX_SLICE);
+    return scan_flag(d_flag, st, bad, [&](uint32_t* flag) {
+        for (size_t lo = 0; lo < n; lo += FS) {
+            const size_t m = n - lo < FS ? n - lo : FS;
+            hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
+                               (const uint32_t*)d_key_idx + lo, (uint32_t)m, (uint32_t)n_keys, flag);
+            if (d_msg_idx)
+                hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
+                                   (const uint32_t*)d_msg_idx + lo, (uint32_t)m, (uint32_t)n_msgs, flag);
+            if (mono)
+                hipLaunchKernelGGL(blsgpu::pscan::k_fold_mono, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_msg_idx,
+                                   (uint32_t)lo, (uint32_t)m, flag);
+        }
+    });
+}
+
 // n children of one parent on `st`; public mode (parent_sk NULL) with `check`: a device scan of the indices and one
 // synchronising read of its flag first, -EINVAL before anything is written if one is hardened
 int hd_children_dev(blsgpu_ctx* c, const uint8_t chain_code[32], const uint8_t parent_pk_aff[96], const uint8_t* parent_sk, const void* d_idx,
@@ -929,17 +964,15 @@ int sig_shares_args(const blsgpu_ctx* c, size_t k, size_t groups, size_t n_keys,
     if (groups > 0x7FFFFFFFull || n_keys > 0x7FFFFFFFull || k * groups > 0xFFFFFFF0ull) return fail(-EINVAL, "batch too large");
     return 0;
 }
-// Sessions in slices; per slice the once-per-call stages into B_SHR_WS, then the rounds: the nodes of a round (all of one
-// length) go up, their verdict bytes come back -- the one synchronisation of a round -- and the host halves the nodes that
-// failed.  `scan`: the _dev form's device scan of the key indices first.  stats (host, may be NULL): rounds, node tests.
+// Sessions in slices; per slice the once-per-call stages into B_SHR_WS, then the rounds (bisect_rounds): the nodes of a round
+// (all of one length) go up and their verdict bytes come back.  A node's second half that lies past the session's k shares holds
+// nothing and is not tested.  `scan`: the _dev form's device scan of the key indices first.  stats (host, may be NULL): rounds,
+// node tests.
 int sig_shares_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_t n_keys, const void* d_key_idx, const void* d_x,
                    const void* d_hashes, const void* d_weights, int scaled, size_t k, size_t groups, void* d_status, void* d_sess,
                    uint64_t* stats, bool scan, hipStream_t st) {
     using namespace blsgpu::sigsh;
-    uint32_t lg_k = 0;
-    while (((size_t)1 << lg_k) < k) lg_k++;
-    const size_t K = (size_t)1 << lg_k;                                    // k rounded up to a power of two
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t K = bisect::ceil_pow2(k);
     // slices of sessions whose kept arrays, and whose largest possible round (every leaf a node), stay below 2 GB each
     const size_t keep_per = k * (2 + 3 * 32 + 2 * BLSGPU_G1_BYTES + BLSGPU_G2_BYTES) + BLSGPU_G2_BYTES + 1;
     const size_t round_per = K * (sizeof(Node) + 3 * BLSGPU_G1_BYTES + 4 * BLSGPU_G2_BYTES + BLSGPU_FQ12_BYTES + 3);
@@ -948,32 +981,21 @@ int sig_shares_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_t
     slice = slice_len(c, slice);
     if (slice > groups) slice = groups;
     const size_t n0 = slice * k;
-    size_t off = 256;                                                        // [0, 4): the flag word of the index scan
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
-    const size_t o_keyst = take(n_keys), o_sigst = take(n0), o_h = take(slice * BLSGPU_G2_BYTES), o_hinf = take(slice),
-                 o_lam = take(scaled ? n0 * 32 : 0), o_r = take(n0 * 32), o_w = take(n0 * 32), o_pk = take(n0 * BLSGPU_G1_BYTES),
-                 o_elig = take(n0), o_a = take(n0 * BLSGPU_G2_BYTES), o_b = take(n0 * BLSGPU_G1_BYTES);
+    bisect::Layout w{256, 256};                                              // [0, 4): the flag word of the index scan
+    const size_t o_keyst = w.take(n_keys), o_sigst = w.take(n0), o_h = w.take(slice * BLSGPU_G2_BYTES), o_hinf = w.take(slice),
+                 o_lam = w.take(scaled ? n0 * 32 : 0), o_r = w.take(n0 * 32), o_w = w.take(n0 * 32), o_pk = w.take(n0 * BLSGPU_G1_BYTES),
+                 o_elig = w.take(n0), o_a = w.take(n0 * BLSGPU_G2_BYTES), o_b = w.take(n0 * BLSGPU_G1_BYTES);
     StreamGuard sg(c, st);
-    if (int rc = c->grow(B_SHR_WS, off)) return rc;
+    if (int rc = c->grow(B_SHR_WS, w.off)) return rc;
     char* const W = c->at<char>(B_SHR_WS);
     if (scan) {
         uint32_t bad = 0;
-        const size_t FS = slice_len(c, FIX_SLICE);
-        if (int rc = scan_flag(W, st, bad, [&](uint32_t* flag) {
-                for (size_t lo = 0; lo < groups * k; lo += FS) {
-                    const size_t m = groups * k - lo < FS ? groups * k - lo : FS;
-                    hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
-                                       (const uint32_t*)d_key_idx + lo, (uint32_t)m, (uint32_t)n_keys, flag);
-                }
-            }))
-            return rc;
+        if (int rc = scan_indices(c, W, d_key_idx, n_keys, nullptr, 0, groups * k, false, bad, st)) return rc;
         if (bad) return fail(-EINVAL, "key index out of range");
     }
     if (int rc = subgroup_dev(c, 1, d_keys, n_keys, W + o_keyst, st)) return rc;
     if (!scaled) HIP_TRY(hipMemsetAsync(d_sess, 1, groups, st));
-    uint64_t rounds = 0, tests = 0;
-    std::vector<Node> cur, next;
-    std::vector<uint8_t> verdict;
+    bisect::State<Node> bis;
     int rc = for_slices(groups, slice, [&](size_t lo, size_t m) {
         const size_t n = m * k;
         const char* sigs = (const char*)d_sigs + lo * k * BLSGPU_G2_BYTES;
@@ -993,17 +1015,17 @@ int sig_shares_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_t
         // the leaves: scalar multiplications as sums of one point with device scalars
         if (int rc = msm_dev<2>(c, sigs, W + o_r, 1, n, W + o_a, nullptr, st)) return rc;
         if (int rc = msm_dev<1>(c, W + o_pk, W + o_w, 1, n, W + o_b, nullptr, st)) return rc;
-        cur.resize(m);
-        for (size_t s = 0; s < m; s++) cur[s] = {(uint32_t)s, 0u};
-        for (uint32_t lg = lg_k;; lg--) {
-            const size_t nn = cur.size(), len = (size_t)1 << lg, slots = nn * len;
-            size_t ro = 0;
-            auto rtake = [&](size_t bytes) { size_t o = ro; ro += al(bytes); return o; };
-            const size_t r_nodes = rtake(nn * sizeof(Node)), r_ga = rtake(slots * BLSGPU_G2_BYTES), r_gb = rtake(slots * BLSGPU_G1_BYTES),
-                         r_s = rtake(nn * BLSGPU_G2_BYTES), r_p = rtake(nn * BLSGPU_G1_BYTES), r_sinf = rtake(nn), r_pinf = rtake(nn),
-                         r_g1 = rtake(nn * 2 * BLSGPU_G1_BYTES), r_g2 = rtake(nn * 2 * BLSGPU_G2_BYTES),
-                         r_e = rtake(nn * BLSGPU_FQ12_BYTES), r_v = rtake(nn);
-            if (int rc = c->grow(B_SHR_ROUND, ro)) return rc;
+        bis.nodes.resize(m);
+        for (size_t s = 0; s < m; s++) bis.nodes[s] = {(uint32_t)s, 0u};
+        return bisect_rounds(bis, K, k, st, [&](std::vector<Node>& cur, size_t len, const void*& d_verdict) {
+            const size_t nn = cur.size(), slots = nn * len;
+            const uint32_t lg = (uint32_t)__builtin_ctzll(len);
+            bisect::Layout r{256, 0};
+            const size_t r_nodes = r.take(nn * sizeof(Node)), r_ga = r.take(slots * BLSGPU_G2_BYTES), r_gb = r.take(slots * BLSGPU_G1_BYTES),
+                         r_s = r.take(nn * BLSGPU_G2_BYTES), r_p = r.take(nn * BLSGPU_G1_BYTES), r_sinf = r.take(nn), r_pinf = r.take(nn),
+                         r_g1 = r.take(nn * 2 * BLSGPU_G1_BYTES), r_g2 = r.take(nn * 2 * BLSGPU_G2_BYTES),
+                         r_e = r.take(nn * BLSGPU_FQ12_BYTES), r_v = r.take(nn);
+            if (int rc = c->grow(B_SHR_ROUND, r.off)) return rc;
             char* const R = c->at<char>(B_SHR_ROUND);
             const Node* d_nodes = (const Node*)(R + r_nodes);
             HIP_TRY(hipMemcpyAsync(R + r_nodes, cur.data(), nn * sizeof(Node), hipMemcpyHostToDevice, st));
@@ -1022,32 +1044,14 @@ int sig_shares_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_t
             if (int rc = blsgpu_pairing_multi_batch_dev(c, R + r_g1, R + r_g2, nullptr, 2, nn, R + r_e, st)) return rc;
             hipLaunchKernelGGL(k_share_verdict, dim3((unsigned)((nn + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, d_nodes, (uint32_t)nn,
                                (const uint4*)(R + r_e), (const uint8_t*)(R + r_sinf), (const uint8_t*)(R + r_pinf),
-                               (const uint8_t*)(W + o_hinf), lg == 0 ? 1u : 0u, (uint32_t)k, (uint8_t*)(R + r_v), status);
+                               (const uint8_t*)(W + o_hinf), len == 1 ? 1u : 0u, (uint32_t)k, (uint8_t*)(R + r_v), status);
             HIP_TRY(hipGetLastError());
-            verdict.resize(nn);
-            HIP_TRY(hipMemcpyAsync(verdict.data(), R + r_v, nn, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            rounds++;
-            tests += nn;
-            if (lg == 0) break;
-            // a node that failed is halved; a half that lies past the session's k shares holds nothing and is not tested
-            next.clear();
-            for (size_t i = 0; i < nn; i++)
-                if (!verdict[i]) {
-                    next.push_back({cur[i].session, cur[i].offset});
-                    if (cur[i].offset + len / 2 < k) next.push_back({cur[i].session, (uint32_t)(cur[i].offset + len / 2)});
-                }
-            if (next.empty()) break;
-            cur.swap(next);
-        }
-        return 0;
+            d_verdict = R + r_v;
+            return 0;
+        });
     });
-    if (rc) return rc;
-    if (stats) {
-        stats[0] = rounds;
-        stats[1] = tests;
-    }
-    return 0;
+    if (!rc) bis.report(stats, 2);
+    return rc;
 }
 
 // ------------------------------------------------------------ short public scalars (blsgpu_smul64.hip) --
@@ -1140,146 +1144,136 @@ int find_unit(blsgpu_ctx* c, hipStream_t st) {
     c->find_unit_ready = true;
     return 0;
 }
-// Items in slices; per slice the once-per-call stages into B_FIND_WS and ONE read of n_e, then the rounds over aligned nodes
-// (offset, length L) of the dense order, L from K = 2^ceil(log2 n_e) halving: the full nodes of a round go through one
-// multi-pairing batch of L + 1 pairs each, the one node that crosses n_e through a call of its own size, a node wholly past n_e
-// does not exist; the verdict bytes come back -- the one synchronisation of a round -- and the host halves the nodes that failed.
-// `scan`: the _dev form's device scan of the indices first.  stats (host, may be NULL): rounds, node tests, pairs fed.
+// What the two verify_find forms share.  The slice: items whose kept arrays (`keep_per` bytes an item), and whose largest
+// possible round (`round_per`), stay below 2 GB each
+size_t find_slice(const blsgpu_ctx* c, size_t n, size_t keep_per, size_t round_per) {
+    const size_t slice = slice_len(c, (((size_t)2 << 30) - ((size_t)1 << 20)) / (keep_per > round_per ? keep_per : round_per));
+    return slice < n ? slice : n;
+}
+// B_FIND_WS: [0, 4) the flag word of the index scan, [4, 8) n_e, [8, 12) the number of runs, then the arrays of the call (key
+// flags, hashes) and of a slice; with `rcap` (the folded form: entries of the run table) its dense leaves and run table as well
+struct FindWs { size_t o_keyst, o_h, o_sigst, o_r, o_elig, o_dense, o_a, o_b, o_ad, o_bd, o_rb, o_rmsg, bytes; };
+FindWs find_ws(size_t n_keys, size_t n_msgs, size_t slice, size_t rcap) {
+    bisect::Layout l{256, 256};
+    FindWs w = {};
+    w.o_keyst = l.take(n_keys), w.o_h = l.take(n_msgs * BLSGPU_G2_BYTES), w.o_sigst = l.take(slice), w.o_r = l.take(slice * 8);
+    w.o_elig = l.take(slice), w.o_dense = l.take(slice * 4), w.o_a = l.take(slice * BLSGPU_G2_BYTES), w.o_b = l.take(slice * BLSGPU_G1_BYTES);
+    if (rcap)
+        w.o_ad = l.take(slice * BLSGPU_G2_BYTES), w.o_bd = l.take(slice * BLSGPU_G1_BYTES), w.o_rb = l.take(rcap * 4), w.o_rmsg = l.take(rcap * 4);
+    w.bytes = l.off;
+    return w;
+}
+// once per call: the workspace, the _dev form's device scan of the indices (`scan`; `mono`: the folded form's precondition too),
+// e(-G1, G2), the key subgroup flags and the distinct hashes, once each
+int find_call_stages(blsgpu_ctx* c, const FindWs& w, const void* d_keys, size_t n_keys, const void* d_key_idx, const void* d_hashes,
+                     size_t n_msgs, const void* d_msg_idx, size_t n, bool scan, bool mono, hipStream_t st) {
+    if (int rc = c->grow(B_FIND_WS, w.bytes)) return rc;
+    char* const W = c->at<char>(B_FIND_WS);
+    if (scan) {
+        uint32_t bad = 0;
+        if (int rc = scan_indices(c, W, d_key_idx, n_keys, d_msg_idx, n_msgs, n, mono, bad, st)) return rc;
+        if (mono ? bad & 1u : bad) return fail(-EINVAL, "key or message index out of range");
+        if (bad) return fail(-EINVAL, "message indices decrease");
+    }
+    if (int rc = find_unit(c, st)) return rc;
+    if (int rc = subgroup_dev(c, 1, d_keys, n_keys, W + w.o_keyst, st)) return rc;
+    return blsgpu_hash_to_g2_dev(c, d_hashes, n_msgs, W + w.o_h, st);
+}
+// once per slice of m items from `lo`: the signature subgroup flags, the weights, eligibility and status bytes (k_find_settle),
+// the dense order and n_e (k_find_dense), what `after_dense` enqueues, and the leaves A_i = r_i sig_i, B_i = r_i keys[key_idx[i]]
+// by item (those of items that are not eligible are never read)
+struct FindSlice { const char* sigs; const uint32_t *kidx, *midx, *dense; uint8_t* status; };
+template <class F>
+int find_slice_stages(blsgpu_ctx* c, const FindWs& w, char* W, const void* d_sigs, const void* d_keys, size_t n_keys, const void* d_key_idx,
+                      const void* d_msg_idx, const void* d_weights, void* d_status, size_t lo, size_t m, hipStream_t st, FindSlice& s,
+                      F after_dense) {
+    using namespace blsgpu::bfind;
+    s = {(const char*)d_sigs + lo * BLSGPU_G2_BYTES, (const uint32_t*)d_key_idx + lo, (const uint32_t*)d_msg_idx + lo,
+         (const uint32_t*)(W + w.o_dense), (uint8_t*)d_status + lo};
+    if (int rc = subgroup_dev(c, 2, s.sigs, m, W + w.o_sigst, st)) return rc;
+    hipLaunchKernelGGL(k_find_settle, dim3((unsigned)((m + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, (const uint32_t*)s.sigs,
+                       (const uint8_t*)(W + w.o_sigst), (const uint32_t*)d_keys, (const uint8_t*)(W + w.o_keyst), s.kidx,
+                       (const uint32_t*)(W + w.o_h), s.midx, (const uint8_t*)d_weights + lo * 8, (uint32_t)m, (uint8_t*)(W + w.o_r),
+                       (uint8_t*)(W + w.o_elig), s.status);
+    hipLaunchKernelGGL(k_find_dense, dim3(1), dim3(DENSE_THREADS), 0, st, (const uint8_t*)(W + w.o_elig), (uint32_t)m,
+                       (uint32_t*)(W + w.o_dense), (uint32_t*)(W + 4));
+    after_dense();
+    HIP_TRY(hipGetLastError());
+    if (int rc = smul64_launch<2>(c, s.sigs, m, nullptr, W + w.o_r, m, W + w.o_a, nullptr, st)) return rc;
+    return smul64_launch<1>(c, d_keys, n_keys, s.kidx, W + w.o_r, m, W + w.o_b, nullptr, st);
+}
+
+// Items in slices; per slice the shared stages into B_FIND_WS and ONE read of n_e, then the rounds (bisect_rounds) over aligned
+// nodes (offset, length L) of the dense order, L from ceil_pow2(n_e) halving: the full nodes of a round go through one
+// multi-pairing batch of L + 1 pairs each, the one node that crosses n_e through a call of its own size (bisect::plain_round), a
+// node wholly past n_e does not exist.  `scan`: the _dev form's device scan of the indices first.  stats (host, may be NULL):
+// rounds, node tests, pairs fed.
 int verify_find_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_t n_keys, const void* d_key_idx, const void* d_hashes,
                     size_t n_msgs, const void* d_msg_idx, const void* d_weights, size_t n, void* d_status, uint64_t* stats, bool scan,
                     hipStream_t st) {
     using namespace blsgpu::bfind;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    // slices of items whose kept arrays, and whose largest possible round (every leaf a node), stay below 2 GB each
     const size_t keep_per = 1 + 8 + 1 + 4 + BLSGPU_G2_BYTES + BLSGPU_G1_BYTES;
-    const size_t round_per = 4 + 2 * BLSGPU_G2_BYTES + 1 + 2 * BLSGPU_G1_BYTES + 2 * BLSGPU_G2_BYTES + BLSGPU_FQ12_BYTES + 1;
-    size_t slice = slice_len(c, (((size_t)2 << 30) - ((size_t)1 << 20)) / (keep_per > round_per ? keep_per : round_per));
-    if (slice > n) slice = n;
-    size_t off = 256;                                                        // [0, 4): the flag word of the index scan, [4, 8): n_e
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
-    const size_t o_keyst = take(n_keys), o_h = take(n_msgs * BLSGPU_G2_BYTES), o_sigst = take(slice), o_r = take(slice * 8), o_elig = take(slice),
-                 o_dense = take(slice * 4), o_a = take(slice * BLSGPU_G2_BYTES), o_b = take(slice * BLSGPU_G1_BYTES);
+    const size_t round_per = 4 + 2 * BLSGPU_G2_BYTES + 1 + 2 * BLSGPU_G1_BYTES + 2 * BLSGPU_G2_BYTES + BLSGPU_FQ12_BYTES + 1;   // every leaf a node
+    const size_t slice = find_slice(c, n, keep_per, round_per);
+    const FindWs w = find_ws(n_keys, n_msgs, slice, 0);
     StreamGuard sg(c, st);
-    if (int rc = c->grow(B_FIND_WS, off)) return rc;
+    if (int rc = find_call_stages(c, w, d_keys, n_keys, d_key_idx, d_hashes, n_msgs, d_msg_idx, n, scan, false, st)) return rc;
     char* const W = c->at<char>(B_FIND_WS);
-    if (scan) {
-        uint32_t bad = 0;
-        const size_t FS = slice_len(c, FIX_SLICE);
-        if (int rc = scan_flag(W, st, bad, [&](uint32_t* flag) {
-                for (size_t lo = 0; lo < n; lo += FS) {
-                    const size_t m = n - lo < FS ? n - lo : FS;
-                    hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
-                                       (const uint32_t*)d_key_idx + lo, (uint32_t)m, (uint32_t)n_keys, flag);
-                    hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
-                                       (const uint32_t*)d_msg_idx + lo, (uint32_t)m, (uint32_t)n_msgs, flag);
-                }
-            }))
-            return rc;
-        if (bad) return fail(-EINVAL, "key or message index out of range");
-    }
-    if (int rc = find_unit(c, st)) return rc;
     const uint4* d_unit = (const uint4*)(c->at<char>(B_FIND_UNIT) + 512);
-    if (int rc = subgroup_dev(c, 1, d_keys, n_keys, W + o_keyst, st)) return rc;
-    if (int rc = blsgpu_hash_to_g2_dev(c, d_hashes, n_msgs, W + o_h, st)) return rc;   // the distinct hashes, once each
-    uint64_t rounds = 0, tests = 0, pairs = 0;
-    std::vector<uint32_t> cur, next, order;
-    std::vector<uint8_t> verdict;
+    bisect::State<uint32_t> bis;
     int rc = for_slices(n, slice, [&](size_t lo, size_t m) {
-        const char* sigs = (const char*)d_sigs + lo * BLSGPU_G2_BYTES;
-        const uint32_t* kidx = (const uint32_t*)d_key_idx + lo;
-        const uint32_t* midx = (const uint32_t*)d_msg_idx + lo;
-        uint8_t* status = (uint8_t*)d_status + lo;
-        const uint32_t* dense = (const uint32_t*)(W + o_dense);
-        if (int rc = subgroup_dev(c, 2, sigs, m, W + o_sigst, st)) return rc;
-        hipLaunchKernelGGL(k_find_settle, dim3((unsigned)((m + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, (const uint32_t*)sigs,
-                           (const uint8_t*)(W + o_sigst), (const uint32_t*)d_keys, (const uint8_t*)(W + o_keyst), kidx,
-                           (const uint32_t*)(W + o_h), midx, (const uint8_t*)d_weights + lo * 8, (uint32_t)m, (uint8_t*)(W + o_r),
-                           (uint8_t*)(W + o_elig), status);
-        hipLaunchKernelGGL(k_find_dense, dim3(1), dim3(DENSE_THREADS), 0, st, (const uint8_t*)(W + o_elig), (uint32_t)m,
-                           (uint32_t*)(W + o_dense), (uint32_t*)(W + 4));
-        HIP_TRY(hipGetLastError());
-        // the leaves A_i = r_i sig_i, B_i = r_i keys[key_idx[i]] by item (those of items that are not eligible are never read)
-        if (int rc = smul64_launch<2>(c, sigs, m, nullptr, W + o_r, m, W + o_a, nullptr, st)) return rc;
-        if (int rc = smul64_launch<1>(c, d_keys, n_keys, kidx, W + o_r, m, W + o_b, nullptr, st)) return rc;
+        FindSlice s;
+        if (int rc = find_slice_stages(c, w, W, d_sigs, d_keys, n_keys, d_key_idx, d_msg_idx, d_weights, d_status, lo, m, st, s, [] {})) return rc;
         uint32_t n_e = 0;
         HIP_TRY(hipMemcpyAsync(&n_e, W + 4, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (n_e == 0) return 0;
-        size_t K = 1;
-        while (K < n_e) K <<= 1;
-        cur.assign(1, 0u);
-        for (size_t L = K;; L >>= 1) {
-            // full nodes first, then the one that crosses n_e (every node begins before n_e)
-            order.clear();
-            uint32_t short_off = 0;
-            bool has_short = false;
-            for (uint32_t o : cur) {
-                if ((size_t)o + L <= n_e) order.push_back(o);
-                else { short_off = o; has_short = true; }
+        bis.nodes.assign(1, 0u);
+        return bisect_rounds(bis, bisect::ceil_pow2(n_e), n_e, st, [&](std::vector<uint32_t>& order, size_t L, const void*& d_verdict) {
+            bisect::Part shape[2];
+            bisect::plain_round(order, L, n_e, shape);
+            const size_t nn = order.size();
+            struct { size_t nodes, len, ga, s, sinf, g1, g2, e; } part[2] = {{shape[0].nodes, shape[0].len}, {shape[1].nodes, shape[1].len}};
+            bisect::Layout r{256, 0};
+            const size_t r_off = r.take(nn * 4), r_v = r.take(nn);
+            for (auto& p : part) {
+                p.ga = r.take(p.nodes * p.len * BLSGPU_G2_BYTES);
+                p.s = r.take(p.nodes * BLSGPU_G2_BYTES);
+                p.sinf = r.take(p.nodes);
+                p.g1 = r.take(p.nodes * (p.len + 1) * BLSGPU_G1_BYTES);
+                p.g2 = r.take(p.nodes * (p.len + 1) * BLSGPU_G2_BYTES);
+                p.e = r.take(p.nodes * BLSGPU_FQ12_BYTES);
             }
-            const size_t nf = order.size(), ns = has_short ? 1 : 0, ls = has_short ? n_e - short_off : 0, nn = nf + ns;
-            if (has_short) order.push_back(short_off);
-            struct Part { size_t nodes, len, ga, s, sinf, g1, g2, e; } part[2] = {{nf, L}, {ns, ls}};
-            size_t ro = 0;
-            auto rtake = [&](size_t bytes) { size_t o = ro; ro += al(bytes); return o; };
-            const size_t r_off = rtake(nn * 4), r_v = rtake(nn);
-            for (Part& p : part) {
-                p.ga = rtake(p.nodes * p.len * BLSGPU_G2_BYTES);
-                p.s = rtake(p.nodes * BLSGPU_G2_BYTES);
-                p.sinf = rtake(p.nodes);
-                p.g1 = rtake(p.nodes * (p.len + 1) * BLSGPU_G1_BYTES);
-                p.g2 = rtake(p.nodes * (p.len + 1) * BLSGPU_G2_BYTES);
-                p.e = rtake(p.nodes * BLSGPU_FQ12_BYTES);
-            }
-            if (int rc = c->grow(B_FIND_ROUND, ro)) return rc;
+            if (int rc = c->grow(B_FIND_ROUND, r.off)) return rc;
             char* const R = c->at<char>(B_FIND_ROUND);
             HIP_TRY(hipMemcpyAsync(R + r_off, order.data(), nn * 4, hipMemcpyHostToDevice, st));
             size_t first = 0;
-            for (const Part& p : part) {
+            for (const auto& p : part) {
                 if (p.nodes == 0) continue;
                 const uint32_t* d_off = (const uint32_t*)(R + r_off) + first;
                 const size_t gtotal = p.nodes * p.len * G2_Q, ptotal = p.nodes * (p.len + 1) * (G1_Q + G2_Q);
                 hipLaunchKernelGGL(k_find_gather, dim3((unsigned)((gtotal + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, d_off,
-                                   (uint32_t)p.len, gtotal, dense, (const uint4*)(W + o_a), (uint4*)(R + p.ga));
+                                   (uint32_t)p.len, gtotal, s.dense, (const uint4*)(W + w.o_a), (uint4*)(R + p.ga));
                 HIP_TRY(hipGetLastError());
                 if (int rc = msm_dev<2>(c, R + p.ga, nullptr, p.len, p.nodes, R + p.s, R + p.sinf, st)) return rc;
                 hipLaunchKernelGGL(k_find_pairs, dim3((unsigned)((ptotal + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, d_off,
-                                   (uint32_t)p.len, ptotal, dense, (const uint4*)(R + p.s), (const uint8_t*)(R + p.sinf),
-                                   (const uint4*)(W + o_b), (const uint4*)(W + o_h), midx, (uint4*)(R + p.g1), (uint4*)(R + p.g2));
+                                   (uint32_t)p.len, ptotal, s.dense, (const uint4*)(R + p.s), (const uint8_t*)(R + p.sinf),
+                                   (const uint4*)(W + w.o_b), (const uint4*)(W + w.o_h), s.midx, (uint4*)(R + p.g1), (uint4*)(R + p.g2));
                 HIP_TRY(hipGetLastError());
                 if (int rc = blsgpu_pairing_multi_batch_dev(c, R + p.g1, R + p.g2, nullptr, p.len + 1, p.nodes, R + p.e, st)) return rc;
                 hipLaunchKernelGGL(k_find_verdict, dim3((unsigned)((p.nodes + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, d_off,
-                                   (uint32_t)p.nodes, (const uint4*)(R + p.e), (const uint8_t*)(R + p.sinf), d_unit, L == 1 ? 1u : 0u, dense,
-                                   (uint8_t*)(R + r_v) + first, status);
+                                   (uint32_t)p.nodes, (const uint4*)(R + p.e), (const uint8_t*)(R + p.sinf), d_unit, L == 1 ? 1u : 0u, s.dense,
+                                   (uint8_t*)(R + r_v) + first, s.status);
                 HIP_TRY(hipGetLastError());
                 first += p.nodes;
-                pairs += p.nodes * (p.len + 1);
+                bis.pairs += p.nodes * (p.len + 1);
             }
-            verdict.resize(nn);
-            HIP_TRY(hipMemcpyAsync(verdict.data(), R + r_v, nn, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            rounds++;
-            tests += nn;
-            if (L == 1) break;
-            // a node that failed is halved; a half that begins at or past n_e holds nothing and is not tested
-            next.clear();
-            for (size_t i = 0; i < nn; i++)
-                if (!verdict[i]) {
-                    next.push_back(order[i]);
-                    if ((size_t)order[i] + L / 2 < n_e) next.push_back((uint32_t)(order[i] + L / 2));
-                }
-            if (next.empty()) break;
-            cur.swap(next);
-        }
-        return 0;
+            d_verdict = R + r_v;
+            return 0;
+        });
     });
-    if (rc) return rc;
-    if (stats) {
-        stats[0] = rounds;
-        stats[1] = tests;
-        stats[2] = pairs;
-    }
-    return 0;
+    if (!rc) bis.report(stats, 3);
+    return rc;
 }
 
 // ------------------------------------------------------------ point prefix sums and range sums (blsgpu_pscan.hip) --
@@ -1508,188 +1502,90 @@ int verify_find_folded_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys
                            hipStream_t st) {
     using namespace blsgpu::bfind;
     namespace ps = blsgpu::pscan;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    // slices of items whose kept arrays, and whose largest possible round, stay below 2 GB each: a round has at most one node
-    // per item and at most 2 nodes + runs <= 3 items slots
+    // a round has at most one node per item and at most 2 nodes + runs <= 3 items slots
     const size_t keep_per = 1 + 8 + 1 + 4 + 2 * (BLSGPU_G2_BYTES + BLSGPU_G1_BYTES) + 8;
     const size_t slot_per = 8 + 4 + 4 + 1 + 1 + 2 * BLSGPU_G1_BYTES + BLSGPU_G2_BYTES;
     const size_t round_per = 3 * slot_per + 4 + 8 + 4 + BLSGPU_G2_BYTES + 3 + BLSGPU_FQ12_BYTES;
-    size_t slice = slice_len(c, (((size_t)2 << 30) - ((size_t)1 << 20)) / (keep_per > round_per ? keep_per : round_per));
-    if (slice > n) slice = n;
+    const size_t slice = find_slice(c, n, keep_per, round_per);
     const size_t rcap = (slice < n_msgs ? slice : n_msgs) + 1;                 // entries of the run table
-    size_t off = 256;                                                        // [0, 4): the flag word of the index scan, [4, 8): n_e, [8, 12): the runs
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
-    const size_t o_keyst = take(n_keys), o_h = take(n_msgs * BLSGPU_G2_BYTES), o_sigst = take(slice), o_r = take(slice * 8), o_elig = take(slice),
-                 o_dense = take(slice * 4), o_a = take(slice * BLSGPU_G2_BYTES), o_b = take(slice * BLSGPU_G1_BYTES),
-                 o_ad = take(slice * BLSGPU_G2_BYTES), o_bd = take(slice * BLSGPU_G1_BYTES), o_rb = take(rcap * 4), o_rmsg = take(rcap * 4);
+    const FindWs w = find_ws(n_keys, n_msgs, slice, rcap);
     StreamGuard sg(c, st);
-    if (int rc = c->grow(B_FIND_WS, off)) return rc;
+    if (int rc = find_call_stages(c, w, d_keys, n_keys, d_key_idx, d_hashes, n_msgs, d_msg_idx, n, scan, true, st)) return rc;
     char* const W = c->at<char>(B_FIND_WS);
-    if (scan) {
-        uint32_t bad = 0;
-        const size_t FS = slice_len(c, FIX_SLICE);
-        if (int rc = scan_flag(W, st, bad, [&](uint32_t* flag) {
-                for (size_t lo = 0; lo < n; lo += FS) {
-                    const size_t m = n - lo < FS ? n - lo : FS;
-                    hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
-                                       (const uint32_t*)d_key_idx + lo, (uint32_t)m, (uint32_t)n_keys, flag);
-                    hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
-                                       (const uint32_t*)d_msg_idx + lo, (uint32_t)m, (uint32_t)n_msgs, flag);
-                    hipLaunchKernelGGL(ps::k_fold_mono, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_msg_idx,
-                                       (uint32_t)lo, (uint32_t)m, flag);
-                }
+    const uint4* d_unit = (const uint4*)(c->at<char>(B_FIND_UNIT) + 512);
+    bisect::State<uint32_t> bis;
+    bisect::FoldPlan plan;                                                   // plan.tab goes up in every round: written by the round alone
+    std::vector<uint32_t> rb(rcap), rmsg(rcap);
+    int rc = for_slices(n, slice, [&](size_t lo, size_t m) {
+        FindSlice s;
+        if (int rc = find_slice_stages(c, w, W, d_sigs, d_keys, n_keys, d_key_idx, d_msg_idx, d_weights, d_status, lo, m, st, s, [&] {
+                hipLaunchKernelGGL(ps::k_fold_runs, dim3(1), dim3(ps::RUN_THREADS), 0, st, s.dense, (const uint32_t*)(W + 4), s.midx,
+                                   (uint32_t*)(W + w.o_rb), (uint32_t*)(W + w.o_rmsg), (uint32_t*)(W + 8));
             }))
             return rc;
-        if (bad & 1u) return fail(-EINVAL, "key or message index out of range");
-        if (bad) return fail(-EINVAL, "message indices decrease");
-    }
-    if (int rc = find_unit(c, st)) return rc;
-    const uint4* d_unit = (const uint4*)(c->at<char>(B_FIND_UNIT) + 512);
-    if (int rc = subgroup_dev(c, 1, d_keys, n_keys, W + o_keyst, st)) return rc;
-    if (int rc = blsgpu_hash_to_g2_dev(c, d_hashes, n_msgs, W + o_h, st)) return rc;   // the distinct hashes, once each
-    uint64_t rounds = 0, tests = 0, pairs = 0;
-    struct NodeRec { uint32_t off, r0, cnt; };                               // a node, its first run and its pair count
-    std::vector<uint32_t> cur, next, rb(rcap), rmsg(rcap), tab;
-    std::vector<NodeRec> order;
-    std::vector<uint8_t> verdict;
-    int rc = for_slices(n, slice, [&](size_t lo, size_t m) {
-        const char* sigs = (const char*)d_sigs + lo * BLSGPU_G2_BYTES;
-        const uint32_t* kidx = (const uint32_t*)d_key_idx + lo;
-        const uint32_t* midx = (const uint32_t*)d_msg_idx + lo;
-        uint8_t* status = (uint8_t*)d_status + lo;
-        const uint32_t* dense = (const uint32_t*)(W + o_dense);
-        if (int rc = subgroup_dev(c, 2, sigs, m, W + o_sigst, st)) return rc;
-        hipLaunchKernelGGL(k_find_settle, dim3((unsigned)((m + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, (const uint32_t*)sigs,
-                           (const uint8_t*)(W + o_sigst), (const uint32_t*)d_keys, (const uint8_t*)(W + o_keyst), kidx,
-                           (const uint32_t*)(W + o_h), midx, (const uint8_t*)d_weights + lo * 8, (uint32_t)m, (uint8_t*)(W + o_r),
-                           (uint8_t*)(W + o_elig), status);
-        hipLaunchKernelGGL(k_find_dense, dim3(1), dim3(DENSE_THREADS), 0, st, (const uint8_t*)(W + o_elig), (uint32_t)m,
-                           (uint32_t*)(W + o_dense), (uint32_t*)(W + 4));
-        hipLaunchKernelGGL(ps::k_fold_runs, dim3(1), dim3(ps::RUN_THREADS), 0, st, dense, (const uint32_t*)(W + 4), midx, (uint32_t*)(W + o_rb),
-                           (uint32_t*)(W + o_rmsg), (uint32_t*)(W + 8));
-        HIP_TRY(hipGetLastError());
-        // the leaves A_i = r_i sig_i, B_i = r_i keys[key_idx[i]] by item, then those of the eligible items in the dense order
-        if (int rc = smul64_launch<2>(c, sigs, m, nullptr, W + o_r, m, W + o_a, nullptr, st)) return rc;
-        if (int rc = smul64_launch<1>(c, d_keys, n_keys, kidx, W + o_r, m, W + o_b, nullptr, st)) return rc;
+        // the leaves of the eligible items in the dense order
         const size_t ltotal = m * 18;
-        hipLaunchKernelGGL(ps::k_fold_leaves, dim3((unsigned)((ltotal + ps::THREADS - 1) / ps::THREADS)), dim3(ps::THREADS), 0, st, dense,
-                           (const uint32_t*)(W + 4), ltotal, (const uint4*)(W + o_a), (const uint4*)(W + o_b), (uint4*)(W + o_ad), (uint4*)(W + o_bd));
+        hipLaunchKernelGGL(ps::k_fold_leaves, dim3((unsigned)((ltotal + ps::THREADS - 1) / ps::THREADS)), dim3(ps::THREADS), 0, st, s.dense,
+                           (const uint32_t*)(W + 4), ltotal, (const uint4*)(W + w.o_a), (const uint4*)(W + w.o_b), (uint4*)(W + w.o_ad),
+                           (uint4*)(W + w.o_bd));
         HIP_TRY(hipGetLastError());
         uint32_t head[2] = {0, 0};                                           // n_e, the number of runs
         const size_t rn = (m < n_msgs ? m : n_msgs) + 1;
         HIP_TRY(hipMemcpyAsync(head, W + 4, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(rb.data(), W + o_rb, rn * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(rmsg.data(), W + o_rmsg, rn * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(rb.data(), W + w.o_rb, rn * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(rmsg.data(), W + w.o_rmsg, rn * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         const uint32_t n_e = head[0], n_runs = head[1];
         if (n_e == 0) return 0;
-        if (n_runs == 0 || n_runs >= rn || rb[0] != 0 || rb[n_runs] != n_e) return fail(-EIO, "run table inconsistent");
+        if (!bisect::run_table_ok(n_e, n_runs, rn, rb.data())) return fail(-EIO, "run table inconsistent");
         PscanWs wa, wb;
         if (int rc = pscan_ws<2>(c, n_e, wa)) return rc;
         if (int rc = pscan_ws<1>(c, n_e, wb)) return rc;
-        if (int rc = pscan_launch<2>(wa, W + o_ad, n_e, true, false, st)) return rc;
-        if (int rc = pscan_launch<1>(wb, W + o_bd, n_e, true, false, st)) return rc;
-        size_t K = 1;
-        while (K < n_e) K <<= 1;
-        cur.assign(1, 0u);
-        for (size_t L = K;; L >>= 1) {
-            // every node with its first run and pair count, ordered by pair count (the order of the offsets kept within one)
-            order.clear();
-            for (uint32_t o : cur) {
-                const uint32_t end = (size_t)o + L < n_e ? (uint32_t)(o + L) : n_e;
-                const uint32_t r0 = (uint32_t)(std::upper_bound(rb.begin(), rb.begin() + n_runs, o) - rb.begin()) - 1u;
-                uint32_t r1 = r0;
-                while (rb[r1 + 1] < end) r1++;
-                order.push_back({o, r0, r1 - r0 + 2u});
-            }
-            std::stable_sort(order.begin(), order.end(), [](const NodeRec& a, const NodeRec& b) { return a.cnt < b.cnt; });
-            const size_t nn = order.size();
-            size_t slots = 0;
-            for (const NodeRec& nd : order) slots += nd.cnt;
-            // the table the host uploads: first[nn + 1], off[nn], rng2[2 nn], node_of[slots], slot_msg[slots] and rng1: the ranges of
-            // the B sums, one per slot that is not a node's head (node i's slot sl has the sum sl - i - 1)
-            size_t to = 0;
-            auto ttake = [&](size_t words) { size_t o = to; to += (words + 63) & ~(size_t)63; return o; };
-            const size_t nb = slots - nn;
-            const size_t t_first = ttake(nn + 1), t_off = ttake(nn), t_rng2 = ttake(2 * nn), t_node = ttake(slots), t_msg = ttake(slots),
-                         t_rng1 = ttake(2 * nb);
-            tab.assign(to, 0u);
-            size_t sl = 0;
-            for (size_t i = 0; i < nn; i++) {
-                const NodeRec& nd = order[i];
-                const uint32_t end = (size_t)nd.off + L < n_e ? (uint32_t)(nd.off + L) : n_e;
-                tab[t_first + i] = (uint32_t)sl;
-                tab[t_off + i] = nd.off;
-                tab[t_rng2 + 2 * i] = nd.off;
-                tab[t_rng2 + 2 * i + 1] = end;
-                for (uint32_t j = 0; j < nd.cnt; j++, sl++) {
-                    tab[t_node + sl] = (uint32_t)i;
-                    if (j == 0) continue;                                    // the head slot: (-G1, S)
-                    const uint32_t r = nd.r0 + j - 1u;
-                    const size_t bi = sl - i - 1;
-                    tab[t_msg + sl] = rmsg[r];
-                    tab[t_rng1 + 2 * bi] = rb[r] > nd.off ? rb[r] : nd.off;
-                    tab[t_rng1 + 2 * bi + 1] = rb[r + 1] < end ? rb[r + 1] : end;
-                }
-            }
-            tab[t_first + nn] = (uint32_t)sl;
-            size_t ro = 0;
-            auto rtake = [&](size_t bytes) { size_t o = ro; ro += al(bytes); return o; };
-            const size_t r_tab = rtake(to * 4), r_code = rtake(slots), r_bflag = rtake(nb), r_b = rtake(nb * BLSGPU_G1_BYTES), r_sflag = rtake(nn), r_odd = rtake(nn), r_v = rtake(nn),
-                         r_s = rtake(nn * BLSGPU_G2_BYTES), r_g1 = rtake(slots * BLSGPU_G1_BYTES), r_g2 = rtake(slots * BLSGPU_G2_BYTES),
-                         r_e = rtake(nn * BLSGPU_FQ12_BYTES);
-            if (int rc = c->grow(B_FIND_ROUND, ro)) return rc;
+        if (int rc = pscan_launch<2>(wa, W + w.o_ad, n_e, true, false, st)) return rc;
+        if (int rc = pscan_launch<1>(wb, W + w.o_bd, n_e, true, false, st)) return rc;
+        bis.nodes.assign(1, 0u);
+        return bisect_rounds(bis, bisect::ceil_pow2(n_e), n_e, st, [&](std::vector<uint32_t>& nodes, size_t L, const void*& d_verdict) {
+            bisect::fold_round(nodes, L, n_e, rb.data(), rmsg.data(), n_runs, plan);
+            const bisect::FoldPlan& t = plan;
+            const size_t nn = nodes.size(), slots = t.slots, nb = t.nb;
+            bisect::Layout r{256, 0};
+            const size_t r_tab = r.take(t.tab.size() * 4), r_code = r.take(slots), r_bflag = r.take(nb), r_b = r.take(nb * BLSGPU_G1_BYTES),
+                         r_sflag = r.take(nn), r_odd = r.take(nn), r_v = r.take(nn), r_s = r.take(nn * BLSGPU_G2_BYTES),
+                         r_g1 = r.take(slots * BLSGPU_G1_BYTES), r_g2 = r.take(slots * BLSGPU_G2_BYTES), r_e = r.take(nn * BLSGPU_FQ12_BYTES);
+            if (int rc = c->grow(B_FIND_ROUND, r.off)) return rc;
             char* const R = c->at<char>(B_FIND_ROUND);
             const uint32_t* const T = (const uint32_t*)(R + r_tab);
-            HIP_TRY(hipMemcpyAsync(R + r_tab, tab.data(), to * 4, hipMemcpyHostToDevice, st));
-            if (int rc = pscan_ranges_launch<1>(wb, 0, n_e, true, T + t_rng1, nb, nullptr, nullptr, R + r_b, R + r_bflag, st)) return rc;
-            if (int rc = pscan_ranges_launch<2>(wa, 0, n_e, true, T + t_rng2, nn, nullptr, nullptr, R + r_s, R + r_sflag, st)) return rc;
-            hipLaunchKernelGGL(ps::k_fold_codes, dim3((unsigned)((nn + ps::THREADS - 1) / ps::THREADS)), dim3(ps::THREADS), 0, st, T + t_first,
+            HIP_TRY(hipMemcpyAsync(R + r_tab, t.tab.data(), t.tab.size() * 4, hipMemcpyHostToDevice, st));
+            if (int rc = pscan_ranges_launch<1>(wb, 0, n_e, true, T + t.t_rng1, nb, nullptr, nullptr, R + r_b, R + r_bflag, st)) return rc;
+            if (int rc = pscan_ranges_launch<2>(wa, 0, n_e, true, T + t.t_rng2, nn, nullptr, nullptr, R + r_s, R + r_sflag, st)) return rc;
+            hipLaunchKernelGGL(ps::k_fold_codes, dim3((unsigned)((nn + ps::THREADS - 1) / ps::THREADS)), dim3(ps::THREADS), 0, st, T + t.t_first,
                                (uint32_t)nn, (const uint8_t*)(R + r_bflag), (const uint8_t*)(R + r_sflag), (uint8_t*)(R + r_code),
                                (uint8_t*)(R + r_odd));
             const size_t ftotal = slots * 18;
-            hipLaunchKernelGGL(ps::k_fold_fill, dim3((unsigned)((ftotal + ps::THREADS - 1) / ps::THREADS)), dim3(ps::THREADS), 0, st, T + t_node,
-                               T + t_first, T + t_msg, ftotal, (const uint8_t*)(R + r_code), (const uint4*)(R + r_b), (const uint4*)(R + r_s), (const uint4*)(W + o_h),
-                               (uint4*)(R + r_g1), (uint4*)(R + r_g2));
+            hipLaunchKernelGGL(ps::k_fold_fill, dim3((unsigned)((ftotal + ps::THREADS - 1) / ps::THREADS)), dim3(ps::THREADS), 0, st, T + t.t_node,
+                               T + t.t_first, T + t.t_msg, ftotal, (const uint8_t*)(R + r_code), (const uint4*)(R + r_b), (const uint4*)(R + r_s),
+                               (const uint4*)(W + w.o_h), (uint4*)(R + r_g1), (uint4*)(R + r_g2));
             HIP_TRY(hipGetLastError());
             for (size_t i = 0; i < nn;) {                                    // the nodes of one pair count: one multi-pairing batch
                 size_t j = i;
-                while (j < nn && order[j].cnt == order[i].cnt) j++;
-                const size_t s0 = tab[t_first + i];
+                while (j < nn && t.order[j].cnt == t.order[i].cnt) j++;
+                const size_t s0 = t.tab[t.t_first + i];
                 if (int rc = blsgpu_pairing_multi_batch_dev(c, R + r_g1 + s0 * BLSGPU_G1_BYTES, R + r_g2 + s0 * BLSGPU_G2_BYTES, nullptr,
-                                                            order[i].cnt, j - i, R + r_e + i * BLSGPU_FQ12_BYTES, st))
+                                                            t.order[i].cnt, j - i, R + r_e + i * BLSGPU_FQ12_BYTES, st))
                     return rc;
                 i = j;
             }
-            hipLaunchKernelGGL(k_find_verdict, dim3((unsigned)((nn + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, T + t_off, (uint32_t)nn,
-                               (const uint4*)(R + r_e), (const uint8_t*)(R + r_odd), d_unit, L == 1 ? 1u : 0u, dense, (uint8_t*)(R + r_v), status);
+            hipLaunchKernelGGL(k_find_verdict, dim3((unsigned)((nn + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, T + t.t_off, (uint32_t)nn,
+                               (const uint4*)(R + r_e), (const uint8_t*)(R + r_odd), d_unit, L == 1 ? 1u : 0u, s.dense, (uint8_t*)(R + r_v),
+                               s.status);
             HIP_TRY(hipGetLastError());
-            verdict.resize(nn);
-            HIP_TRY(hipMemcpyAsync(verdict.data(), R + r_v, nn, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            rounds++;
-            tests += nn;
-            pairs += slots;
-            if (L == 1) break;
-            // a node that failed is halved; a half that begins at or past n_e holds nothing and is not tested
-            next.clear();
-            for (size_t i = 0; i < nn; i++)
-                if (!verdict[i]) {
-                    next.push_back(order[i].off);
-                    if ((size_t)order[i].off + L / 2 < n_e) next.push_back((uint32_t)(order[i].off + L / 2));
-                }
-            if (next.empty()) break;
-            cur.swap(next);
-        }
-        return 0;
+            bis.pairs += slots;
+            d_verdict = R + r_v;
+            return 0;
+        });
     });
-    if (rc) return rc;
-    if (stats) {
-        stats[0] = rounds;
-        stats[1] = tests;
-        stats[2] = pairs;
-    }
-    return 0;
+    if (!rc) bis.report(stats, 3);
+    return rc;
 }
 
 // ------------------------------------------------------------ scalar-field work on secrets (blsgpu_frsecret.hip) --
@@ -3461,23 +3357,27 @@ BLSGPU_EXPORT int blsgpu_g2_mul_short_dev(blsgpu_ctx* c, const void* d_pts, cons
                                           void* stream) {
     return mul_short_dev<2>(c, d_pts, d_w, n, d_out_aff, d_out_inf, (hipStream_t)stream);
 }
-BLSGPU_EXPORT int blsgpu_verify_find_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_t n_keys, const void* d_key_idx,
-                                         const void* d_msg_hashes, size_t n_msgs, const void* d_msg_idx, const void* d_weights, size_t n,
-                                         void* d_status, uint64_t* stats, void* stream) {
+// blsgpu_verify_find* and blsgpu_verify_find_folded*: `find` is verify_find_dev or verify_find_folded_dev; the host form checks
+// the indices itself and, with `mono` (the folded form), refuses message indices that decrease
+typedef int FindDev(blsgpu_ctx*, const void*, const void*, size_t, const void*, const void*, size_t, const void*, const void*, size_t, void*,
+                    uint64_t*, bool, hipStream_t);
+int verify_find_abi_dev(FindDev* find, blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_t n_keys, const void* d_key_idx,
+                        const void* d_msg_hashes, size_t n_msgs, const void* d_msg_idx, const void* d_weights, size_t n, void* d_status,
+                        uint64_t* stats, void* stream) {
     if (int rc = verify_find_args(c, n, n_keys, n_msgs, !d_sigs || !d_keys || !d_key_idx || !d_msg_hashes || !d_msg_idx || !d_weights || !d_status))
         return rc < 0 ? rc : 0;
     HIP_TRY(hipSetDevice(c->device));
-    return verify_find_dev(c, d_sigs, d_keys, n_keys, d_key_idx, d_msg_hashes, n_msgs, d_msg_idx, d_weights, n, d_status, stats, true,
-                           (hipStream_t)stream);
+    return find(c, d_sigs, d_keys, n_keys, d_key_idx, d_msg_hashes, n_msgs, d_msg_idx, d_weights, n, d_status, stats, true, (hipStream_t)stream);
 }
-BLSGPU_EXPORT int blsgpu_verify_find(blsgpu_ctx* c, const uint8_t* sigs, const uint8_t* keys, size_t n_keys, const uint32_t* key_idx,
-                                     const uint8_t* msg_hashes, size_t n_msgs, const uint32_t* msg_idx, const uint8_t* weights, size_t n,
-                                     uint8_t* status, uint64_t* stats) {
+int verify_find_abi_host(FindDev* find, bool mono, blsgpu_ctx* c, const uint8_t* sigs, const uint8_t* keys, size_t n_keys, const uint32_t* key_idx,
+                         const uint8_t* msg_hashes, size_t n_msgs, const uint32_t* msg_idx, const uint8_t* weights, size_t n, uint8_t* status,
+                         uint64_t* stats) {
     if (int rc = verify_find_args(c, n, n_keys, n_msgs, !sigs || !keys || !key_idx || !msg_hashes || !msg_idx || !weights || !status))
         return rc < 0 ? rc : 0;
     for (size_t i = 0; i < n; i++) {
         if (key_idx[i] >= n_keys) return fail(-EINVAL, "key index out of range");
         if (msg_idx[i] >= n_msgs) return fail(-EINVAL, "message index out of range");
+        if (mono && i && msg_idx[i] < msg_idx[i - 1]) return fail(-EINVAL, "message indices decrease");
     }
     HIP_TRY(hipSetDevice(c->device));
     Staging s(c);
@@ -3485,10 +3385,20 @@ BLSGPU_EXPORT int blsgpu_verify_find(blsgpu_ctx* c, const uint8_t* sigs, const u
               dh = s.in(msg_hashes, n_msgs * 32), dmi = s.in(msg_idx, n * 4), dw = s.in(weights, n * 8), dst = s.out(status, n);
     if (int rc = s.alloc()) return rc;
     if (int rc = s.up()) return rc;
-    if (int rc = verify_find_dev(c, s.at(dsig), s.at(dkey), n_keys, s.at(dki), s.at(dh), n_msgs, s.at(dmi), s.at(dw), n, s.at(dst), stats,
-                                 false, nullptr))
+    if (int rc = find(c, s.at(dsig), s.at(dkey), n_keys, s.at(dki), s.at(dh), n_msgs, s.at(dmi), s.at(dw), n, s.at(dst), stats, false, nullptr))
         return rc;
     return s.down();
+}
+BLSGPU_EXPORT int blsgpu_verify_find_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_t n_keys, const void* d_key_idx,
+                                         const void* d_msg_hashes, size_t n_msgs, const void* d_msg_idx, const void* d_weights, size_t n,
+                                         void* d_status, uint64_t* stats, void* stream) {
+    return verify_find_abi_dev(verify_find_dev, c, d_sigs, d_keys, n_keys, d_key_idx, d_msg_hashes, n_msgs, d_msg_idx, d_weights, n, d_status,
+                               stats, stream);
+}
+BLSGPU_EXPORT int blsgpu_verify_find(blsgpu_ctx* c, const uint8_t* sigs, const uint8_t* keys, size_t n_keys, const uint32_t* key_idx,
+                                     const uint8_t* msg_hashes, size_t n_msgs, const uint32_t* msg_idx, const uint8_t* weights, size_t n,
+                                     uint8_t* status, uint64_t* stats) {
+    return verify_find_abi_host(verify_find_dev, false, c, sigs, keys, n_keys, key_idx, msg_hashes, n_msgs, msg_idx, weights, n, status, stats);
 }
 
 // ------------------------------------------------------------ point range sums, batch verification that folds shared messages --
@@ -3535,32 +3445,14 @@ BLSGPU_EXPORT int blsgpu_g2_msm_ranges_dev(blsgpu_ctx* c, const void* d_pts, con
 BLSGPU_EXPORT int blsgpu_verify_find_folded_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_t n_keys, const void* d_key_idx,
                                                 const void* d_msg_hashes, size_t n_msgs, const void* d_msg_idx, const void* d_weights, size_t n,
                                                 void* d_status, uint64_t* stats, void* stream) {
-    if (int rc = verify_find_args(c, n, n_keys, n_msgs, !d_sigs || !d_keys || !d_key_idx || !d_msg_hashes || !d_msg_idx || !d_weights || !d_status))
-        return rc < 0 ? rc : 0;
-    HIP_TRY(hipSetDevice(c->device));
-    return verify_find_folded_dev(c, d_sigs, d_keys, n_keys, d_key_idx, d_msg_hashes, n_msgs, d_msg_idx, d_weights, n, d_status, stats, true,
-                                  (hipStream_t)stream);
+    return verify_find_abi_dev(verify_find_folded_dev, c, d_sigs, d_keys, n_keys, d_key_idx, d_msg_hashes, n_msgs, d_msg_idx, d_weights, n,
+                               d_status, stats, stream);
 }
 BLSGPU_EXPORT int blsgpu_verify_find_folded(blsgpu_ctx* c, const uint8_t* sigs, const uint8_t* keys, size_t n_keys, const uint32_t* key_idx,
                                             const uint8_t* msg_hashes, size_t n_msgs, const uint32_t* msg_idx, const uint8_t* weights, size_t n,
                                             uint8_t* status, uint64_t* stats) {
-    if (int rc = verify_find_args(c, n, n_keys, n_msgs, !sigs || !keys || !key_idx || !msg_hashes || !msg_idx || !weights || !status))
-        return rc < 0 ? rc : 0;
-    for (size_t i = 0; i < n; i++) {
-        if (key_idx[i] >= n_keys) return fail(-EINVAL, "key index out of range");
-        if (msg_idx[i] >= n_msgs) return fail(-EINVAL, "message index out of range");
-        if (i && msg_idx[i] < msg_idx[i - 1]) return fail(-EINVAL, "message indices decrease");
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    Staging s(c);
-    const int dsig = s.in(sigs, n * BLSGPU_G2_BYTES), dkey = s.in(keys, n_keys * BLSGPU_G1_BYTES), dki = s.in(key_idx, n * 4),
-              dh = s.in(msg_hashes, n_msgs * 32), dmi = s.in(msg_idx, n * 4), dw = s.in(weights, n * 8), dst = s.out(status, n);
-    if (int rc = s.alloc()) return rc;
-    if (int rc = s.up()) return rc;
-    if (int rc = verify_find_folded_dev(c, s.at(dsig), s.at(dkey), n_keys, s.at(dki), s.at(dh), n_msgs, s.at(dmi), s.at(dw), n, s.at(dst),
-                                        stats, false, nullptr))
-        return rc;
-    return s.down();
+    return verify_find_abi_host(verify_find_folded_dev, true, c, sigs, keys, n_keys, key_idx, msg_hashes, n_msgs, msg_idx, weights, n, status,
+                                stats);
 }
 
 // ------------------------------------------------------------ threshold dealing, recovery and share signing for secrets --

@@ -9,6 +9,7 @@ import struct
 
 import pytest
 
+import bisect_model
 from bls_py import _native_find as F
 from bls_py import hostmath as H
 
@@ -101,6 +102,7 @@ def test_sizes_and_forgery_positions(engine, world, n):
         status, stats = run(engine, items, seed=100 * n + c)
         print("n", n, "forged", forged, "stats", stats)
         assert status == want
+        assert stats == bisect_model.plain(n, sorted(forged))["stats"]
         if not forged:
             assert stats[:2] == (1, 1) and stats[2] == n + 1
         elif len(forged) == 1:
@@ -118,13 +120,15 @@ def test_work_bound_of_the_bisection(engine, world):
         status, (rounds, tests, pairs) = run(engine, items, seed=n)
         print("n", n, "one forgery: rounds", rounds, "node tests", tests, "pairs", pairs)
         assert status == want and status.count(0) == 1
+        assert (rounds, tests, pairs) == bisect_model.plain(n, [at])["stats"]
         assert tests <= 1 + 2 * lg(n) and rounds <= lg(n) + 1
         assert tests <= (13 if n == 64 else 15)
         if n == 100:
             assert BLS.verify_batch(objects(items)) == [s == 1 for s in want]
     items, want = items_of(world, 8, {i: KINDS[i % 3] for i in range(8)})
-    status, (rounds, tests, _) = run(engine, items, seed=8)
+    status, (rounds, tests, pairs) = run(engine, items, seed=8)
     assert status == want == bytes(8) and tests <= 2 * 8 - 1 and rounds == 4
+    assert (rounds, tests, pairs) == bisect_model.plain(8, range(8))["stats"]
 
 
 def test_ineligible_items_among_valid_ones(engine, world, golden):

@@ -7,6 +7,7 @@ import struct
 
 import pytest
 
+import bisect_model
 from bls_py import hostmath as H
 
 from sigshares_vectors import (N, SK, Session, fixture_objects, fixture_truth, msg_hash, outside_g1, outside_g2, pack, pk_bytes,
@@ -55,6 +56,8 @@ def test_sizes_and_bad_share_patterns(engine, k):
                 print("k", k, "groups", groups, "scaled", scaled, "stats", stats)
                 assert status == truth_bytes(sessions)
                 assert sess == b"\x01" * groups
+                bad = [[j for j, ok in enumerate(truth_bytes([s])) if not ok] for s in sessions]
+                assert stats == bisect_model.shares(k, bad)["stats"]
                 if not any(0 in truth_bytes([s]) for s in sessions):
                     assert stats == (1, groups)
 
@@ -239,6 +242,7 @@ def test_work_bound_of_the_bisection(engine):
     assert status == truth_bytes(sessions) and status.count(0) == groups
     print("one bad share per session: rounds", rounds, "node tests", tests)
     assert tests <= groups * (1 + 2 * 6) and rounds <= 7
+    assert (rounds, tests) == bisect_model.shares(64, [[(11 * g + 3) % 64] for g in range(groups)])["stats"]
     clean = [Session(players, mh, False) for _ in range(groups)]
     status, sess, (rounds, tests) = check(engine, clean, False, seed=16)
     assert status == b"\x01" * (64 * groups) and (rounds, tests) == (1, groups)

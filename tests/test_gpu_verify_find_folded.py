@@ -9,6 +9,7 @@ import struct
 
 import pytest
 
+import bisect_model
 from bls_py import _native_find as F
 from bls_py import _native_ranges as R
 from bls_py import hostmath as H
@@ -73,6 +74,8 @@ def test_sizes_messages_and_forgery_positions(engine, keys, n):
             plain, pstats = F.verify_find(engine, *args, weights)
             print("n", n, "m", m, "forged", forged, "stats", stats, "verify_find", pstats)
             assert status == want == plain
+            assert stats == bisect_model.folded(w["msg"], sorted(forged))["stats"]
+            assert pstats == bisect_model.plain(n, sorted(forged))["stats"]
             if not forged:
                 assert stats == (1, 1, m + 1)
             elif len(forged) == 1:
