@@ -38,8 +38,9 @@ __device__ __forceinline__ void st14n(char* vf, uint32_t a, const int32_t* __res
     for (int j = 0; j < NL; j++) *reinterpret_cast<int32_t*>(p + 256 * j) = -V[j];
 }
 // One step of a wavefront: `vf` already points at the lane's pair (value file base + 4 x pair index).  line: the pair's record of
-// this line index in HBM, or nullptr.  Column bounds (units of 2^56, 8 fit): asserted per kind by the model's digit-level run; the
-// formulas keep every output at <= 8 (vmgen/lsw_model.py).
+// this line index in HBM, or nullptr.  Column bounds (units of 2^56, 8 fit, 9 on the negative side): four products of sums of two
+// full slots would be 16 -- the formulas stay at 4 / 7 in the worst case only because of the slots they name (lone slots, ZERO, a
+// value beside its own negative); vmgen/gen_lsw.py asserts the bound for every record it packs from the kind of each slot.
 template <int K, bool HAS2>
 __device__ __forceinline__ void lstep(char* vf, const RecN<2 * K + 3>& r, int32_t* __restrict__ line) {
     int32_t A[K][NL], B[K][NL], p[NL], V[NL];

@@ -56,8 +56,10 @@ __device__ __forceinline__ void rd2(int32_t* __restrict__ out, const char* vf, u
 #pragma unroll
     for (int j = 0; j < NL; j++) out[j] = *reinterpret_cast<const int32_t*>(pa + 256 * j) + *reinterpret_cast<const int32_t*>(pb + 256 * j);
 }
-// limbs of s t - k q, normalised (limbs 0 .. 12 in [0, 2^28), the sign in limb 13), k = floor(s t[13] M47 / 2^47) ~ s t / q:
-// the result lies in (-q/64, q + q/64) whatever s (vmgen/mlw_model.scale_reduce_norm is this routine)
+// limbs of s t - k q, normalised (limbs 0 .. 12 in [0, 2^28), the sign in limb 13), k = floor(s t[13] M47 / 2^47) ~ s t / q.
+// With t the sum of g product results (limbs 0 .. 12 below g 2^364 together) the result is top (2^364 - M47 q / 2^47) + s low + [0, q),
+// top = s t[13]: both terms stay below |s| g q / 106 513, so it lies in (-q/64, q + q/64) while |s| g < 1664 -- the tables reach 288
+// (72 x 4), and vmgen/gen_mlw.record_words refuses a record past 832, half of it (vmgen/mlw_model.scale_reduce_norm is this routine)
 __device__ __forceinline__ void srn(int32_t* __restrict__ V, const int32_t* __restrict__ t, int32_t s) {
     const int32_t qd[NL] = BLS28_Q;
     const int32_t top = t[NL - 1] * s;

@@ -383,12 +383,13 @@ def programs3():
 
 
 # ---- digit-level interpreter ---------------------------------------------------------------------------------------------
-def scale_reduce_norm(t, s):
+def scale_reduce_norm(t, s, m47=M47, quotient_top=None):
     """what every lane does with the quad's sum t (14 limbs) and its scale s: limbs of s t - k q, normalised, with
-    k = floor(s t[13] M47 / 2^47) ~ s t / q"""
+    k = floor(s t[13] M47 / 2^47) ~ s t / q.  (m47, quotient_top: a wrong reciprocal / a wrong top limb for the quotient -- the
+    mutants of tests/test_wide_vectors_model.py; the routine itself has neither)"""
     top = t[L - 1] * s
     assert -(1 << 31) <= top < (1 << 31)
-    k = (top * M47) >> 47
+    k = ((top if quotient_top is None else quotient_top) * m47) >> 47
     out, c = [], 0
     for j in range(L - 1):
         c += t[j] * s - k * QD[j]

@@ -58,16 +58,15 @@ def test_pairing_batches_through_the_team_final_exponentiation(fx, seeded_pairs,
     assert fx.pairing_multi(cat(d["g1"]), cat(d["g2"]), n, inf).hex() == d["out"]
 
 
-def test_sharded_form_with_several_partials_per_result(fx, seeded_pairs, golden):
-    """blsgpu_final_exp_product_batch_dev with 4 partials per result (what an all-gather over 4 ranks hands over)"""
+def _sharded(fx, seeded_pairs, golden, cuts):
+    """blsgpu_final_exp_product_batch_dev with len(cuts) - 1 partials per result (what an all-gather over that many ranks hands over)"""
     import torch
     g1, g2 = seeded_pairs
     dev = torch.device("cuda", 0)
     up = lambda x: torch.frombuffer(bytearray(x), dtype=torch.uint8).to(dev)
-    B, W = 3, 4
+    B, W = 3, len(cuts) - 1
     parts = torch.zeros(W * B * 144, dtype=torch.int32, device=dev)
     out = torch.zeros(576 * B, dtype=torch.uint8, device=dev)
-    cuts = [0, 200, 513, 800, 1025]
     keep = []
     for r in range(W):
         lo, hi = cuts[r], cuts[r + 1]
@@ -78,3 +77,13 @@ def test_sharded_form_with_several_partials_per_result(fx, seeded_pairs, golden)
     torch.cuda.synchronize()
     res = bytes(out.cpu().numpy())
     assert all(res[576 * b:576 * (b + 1)].hex() == golden("pairing.json")["seeded"]["1025"]["out"] for b in range(B))
+
+
+def test_sharded_form_with_several_partials_per_result(fx, seeded_pairs, golden):
+    """4 partials per result"""
+    _sharded(fx, seeded_pairs, golden, [0, 200, 513, 800, 1025])
+
+
+def test_sharded_form_with_eight_partials_per_result(fx, seeded_pairs, golden):
+    """8 = fexp_wide_max_partials: the most the one-result kernel is handed to multiply itself"""
+    _sharded(fx, seeded_pairs, golden, [0, 100, 200, 399, 513, 640, 800, 1000, 1025])
