@@ -271,6 +271,27 @@ int blsgpu_map_to_g2_dev(blsgpu_ctx *ctx, const void *d_t, size_t n, void *d_out
 int blsgpu_hash_to_g2(blsgpu_ctx *ctx, const uint8_t *msg_hashes, size_t n, uint8_t *out);
 int blsgpu_hash_to_g2_dev(blsgpu_ctx *ctx, const void *d_msg_hashes, size_t n, void *d_out, void *stream);
 
+/* Hash to G1 after the SHA-256 step: hash_to_point_prehashed_Fq (ec.py:511-520) from the two field elements t0, t1
+ * onwards -- sw_encode over Fq twice (ec.py:449-507), their sum, multiplication by the cofactor
+ * h = 0x396c8c005555e1568c00aaab0000aaab -- one message per lane in registers (k_h2g1, blsgpu_h2g1.hip).
+ * t: n x 96 bytes, t0 || t1 as 48-byte big-endian integers; any value below 2^384 is taken mod q, as Fq(q, v) does.
+ * t = 0 encodes to infinity (ec.py:450-452); t^2 = -5 (reachable: -5 is a square mod q) encodes to the generator, negated
+ * when t > q - t (ec.py:466-473).  out_aff: n x 96 bytes affine, (0, 0) for infinity; out_ser: n x 48 bytes, the compression
+ * blsgpu_g1_mul_gen writes (x with 0x80 on the first byte when y > q // 2, 48 zero bytes for infinity); out_inf (may be
+ * NULL): n flags, 1 for infinity.  out_aff and out_ser may each be NULL, not both: both NULL, or a NULL input, with n > 0
+ * is -EINVAL before anything is written.  n == 0 writes nothing and returns 0.  The calls take no workspace; the host-buffer
+ * form stages slices of 262 144 messages.  Every input is public data: NOT constant-time. */
+int blsgpu_map_to_g1(blsgpu_ctx *ctx, const uint8_t *t, size_t n, uint8_t *out_aff, uint8_t *out_ser, uint8_t *out_inf);
+/* The same with every buffer in device memory, enqueued on `stream` (no synchronisation). */
+int blsgpu_map_to_g1_dev(blsgpu_ctx *ctx, const void *d_t, size_t n, void *d_out_aff, void *d_out_ser, void *d_out_inf, void *stream);
+
+/* The whole hash_to_point_prehashed_Fq(m) (ec.py:511-520) for n 32-byte messages m: t_j = hash512(m || "G1_j") mod q for
+ * j = 0, 1 (util.py:13-16: four one-block SHA-256 compressions per message, in the same kernel -- the digests never visit
+ * the host), then as blsgpu_map_to_g1.  msg_hashes: n x 32 bytes; outputs and argument rules as blsgpu_map_to_g1. */
+int blsgpu_hash_to_g1(blsgpu_ctx *ctx, const uint8_t *msg_hashes, size_t n, uint8_t *out_aff, uint8_t *out_ser, uint8_t *out_inf);
+/* The same with every buffer in device memory, enqueued on `stream` (no synchronisation). */
+int blsgpu_hash_to_g1_dev(blsgpu_ctx *ctx, const void *d_msg_hashes, size_t n, void *d_out_aff, void *d_out_ser, void *d_out_inf, void *stream);
+
 /* Batched point decompression: PublicKey.from_bytes (keys.py:28-40) and
  * Signature.from_bytes (signature.py:21-38) from the serialised bytes: mask the top
  * three bits (`& 0x1f`), y_for_x (ec.py:255-269; square roots fields.py:199-205 and

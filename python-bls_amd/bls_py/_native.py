@@ -74,6 +74,10 @@ PROTOTYPES = {
     "blsgpu_map_to_g2_dev": (vp, vp, sz, vp, vp),
     "blsgpu_hash_to_g2": (vp, cp, sz, cp),
     "blsgpu_hash_to_g2_dev": (vp, vp, sz, vp, vp),
+    "blsgpu_map_to_g1": (vp, cp, sz, vp, vp, vp),
+    "blsgpu_map_to_g1_dev": (vp, vp, sz, vp, vp, vp, vp),
+    "blsgpu_hash_to_g1": (vp, cp, sz, vp, vp, vp),
+    "blsgpu_hash_to_g1_dev": (vp, vp, sz, vp, vp, vp, vp),
     "blsgpu_g1_decompress": (vp, cp, sz, cp, cp),
     "blsgpu_g2_decompress": (vp, cp, sz, cp, cp),
     "blsgpu_g1_decompress_dev": (vp, vp, sz, vp, vp, vp),

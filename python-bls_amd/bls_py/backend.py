@@ -98,6 +98,9 @@ def use(provider):
     on the skewed shape: DESIGN.md section 2w): g1_msm_ranges / g2_msm_ranges(pts, scalars, ranges) -> (affine bytes, flag
     bytes: 0 finite, 1 infinity, 2 a point off the curve in the range) -- sum_{i in [begin, end)} scalars[i] pts[i] for ranges
     (begin, end) of any lengths over one list of points, scalars as ints below 2^256 or 32-byte big-endian values.
+    Optional extension (without it ec.hash_to_points_prehashed_Fq / hash_to_points_Fq run the per-message host calls):
+    hash_to_g1(n x 32-byte message hashes, aff=True, ser=False) and map_to_g1(t: n x 96 bytes t0 || t1, aff=True, ser=False) ->
+    (n x 96 affine bytes|None, n x 48 serialised bytes|None, [is_inf]).
     Extensions are looked up by extension(name), not by hasattr: a stand-in offers one as an attribute of that name, the
     HipProvider's come from EXTENSIONS.  Optional (without it PrivateKey.from_seed_batch and
     ExtendedPrivateKey.from_seed_batch run the per-seed host calls): keys_from_seeds(seeds, seed_len, n, hd) -> (key bytes,
@@ -117,17 +120,20 @@ FIND_EXTENSIONS = {"g1_mul_short": "_native_find", "g2_mul_short": "_native_find
 RANGE_EXTENSIONS = {"g1_range_sums": "_native_ranges", "g2_range_sums": "_native_ranges", "verify_find_folded": "_native_ranges"}
 # ... and the multi-scalar sums over ranges of any lengths.
 MSM_RANGE_EXTENSIONS = {"g1_msm_ranges": "_native_msmr", "g2_msm_ranges": "_native_msmr"}
+# ... and hash to G1 (ec.hash_to_points_prehashed_Fq / hash_to_points_Fq).
+H2G1_EXTENSIONS = {"map_to_g1": "_native_h2g1", "hash_to_g1": "_native_h2g1"}
 
 
 def extension(name):
     """The installed provider's extension `name`: the provider's own attribute of that name if it has one (stand-ins), for
-    a HipProvider the function of EXTENSIONS (or FIND_EXTENSIONS, RANGE_EXTENSIONS, MSM_RANGE_EXTENSIONS) bound to its engine,
-    otherwise None."""
+    a HipProvider the function of EXTENSIONS (or FIND_EXTENSIONS, RANGE_EXTENSIONS, MSM_RANGE_EXTENSIONS, H2G1_EXTENSIONS) bound to its
+    engine, otherwise None."""
     prov = get()
     fn = getattr(prov, name, None)
     if fn is not None:
         return fn
-    where = EXTENSIONS.get(name) or FIND_EXTENSIONS.get(name) or RANGE_EXTENSIONS.get(name) or MSM_RANGE_EXTENSIONS.get(name)
+    where = (EXTENSIONS.get(name) or FIND_EXTENSIONS.get(name) or RANGE_EXTENSIONS.get(name) or MSM_RANGE_EXTENSIONS.get(name)
+             or H2G1_EXTENSIONS.get(name))
     if isinstance(prov, HipProvider) and where:
         import functools
         import importlib

@@ -201,6 +201,27 @@ def hash_to_point_Fq(m, ec=default_ec):
     return hash_to_point_prehashed_Fq(hash256(m), ec)
 
 
+def hash_to_points_prehashed_Fq(ms, ec=default_ec):
+    """Batch form of hash_to_point_prehashed_Fq, element for element the loop of the single call: 32-byte messages go to the
+    provider's hash_to_g1 (the SHA-256 chain on the GPU too), messages of other lengths to map_to_g1 with the field elements
+    of the host's hash512 -- one GPU call either way.  A provider without the extension: the host loop."""
+    from . import backend
+    ms = [_as_bytes(m) for m in ms]
+    if not ms:
+        return []
+    prehashed = all(len(m) == 32 for m in ms)
+    fn = backend.extension("hash_to_g1" if prehashed else "map_to_g1")
+    if fn is None:
+        return [hash_to_point_prehashed_Fq(m, ec) for m in ms]
+    out, _, inf = fn(b"".join(ms) if prehashed else b"".join(H.g1_hash_field_elements(m, hash512) for m in ms))
+    return [AffinePoint._from(H.F1, None if inf[i] else H.g1_from_abi(out[96 * i:96 * (i + 1)]), ec) for i in range(len(ms))]
+
+
+def hash_to_points_Fq(ms, ec=default_ec):
+    """Batch form of hash_to_point_Fq: hash256 on the host, then hash_to_points_prehashed_Fq."""
+    return hash_to_points_prehashed_Fq([hash256(m) for m in ms], ec)
+
+
 def hash_to_point_prehashed_Fq2(m, ec=default_ec_twist):
     return AffinePoint._from(H.F2, H.hash_to_g2_prehashed(_as_bytes(m), hash512), ec)
 

@@ -343,6 +343,11 @@ def hash_to_g1_prehashed(m, hash512):
     return jac_to_affine(F1, jac_mul(F1, P, C.h))
 
 
+def g1_hash_field_elements(m, hash512):
+    """The two field elements of ec.py:514-515 as 96 bytes (t0, t1): the input of blsgpu_map_to_g1."""
+    return b"".join(fq_bytes(int.from_bytes(hash512(m + tag), "big") % Q) for tag in (b"G1_0", b"G1_1"))
+
+
 def g2_hash_field_elements(m, hash512):
     """The four field elements of ec.py:531-534 as 192 bytes (t0.c0, t0.c1, t1.c0, t1.c1):
     the input of blsgpu_map_to_g2."""

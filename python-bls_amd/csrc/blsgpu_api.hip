@@ -36,6 +36,7 @@
 #include "blsgpu_pscan.hip"
 #include "blsgpu_msmr.hip"
 #include "blsgpu_h2c.hip"
+#include "blsgpu_h2g1.hip"
 #include "blsgpu_h2cw.hip"
 #include "blsgpu_msmw.hip"
 #include "blsgpu_probe.hip"
@@ -2892,6 +2893,66 @@ BLSGPU_EXPORT int blsgpu_map_to_g2(blsgpu_ctx* c, const uint8_t* t, size_t n, ui
     if (int rc = s.up()) return rc;
     if (int rc = blsgpu_map_to_g2_dev(c, s.at(din), n, s.at(dout), nullptr)) return rc;
     return s.down();
+}
+
+// ------------------------------------------------------------ hash to G1 (blsgpu_h2g1.hip) --
+// One kernel per slice and nothing between the slices: a message lives in one lane's registers from its bytes to its point, so
+// these calls take no workspace.  `hash`: n x 32-byte message hashes (the SHA-256 chain on the device), otherwise n x 96 bytes
+// t0 || t1.  The argument checks come before anything is written.
+static int h2g1_dev(blsgpu_ctx* c, bool hash, const void* d_in, size_t n, void* d_out_aff, void* d_out_ser, void* d_out_inf, hipStream_t st) {
+    if (n == 0) return 0;
+    if (!d_in || (!d_out_aff && !d_out_ser)) return fail(-EINVAL, "NULL argument");
+    StreamGuard sg(c, st);
+    const size_t in_dw = hash ? 8 : 24;
+    return for_slices(n, slice_len(c, FIX_SLICE), [&](size_t lo, size_t m) {
+        const dim3 grid((unsigned)((m + 255) / 256));
+        const uint32_t* in = (const uint32_t*)d_in + lo * in_dw;
+        uint32_t* aff = d_out_aff ? (uint32_t*)d_out_aff + lo * 24 : nullptr;
+        uint32_t* ser = d_out_ser ? (uint32_t*)d_out_ser + lo * 12 : nullptr;
+        uint8_t* inf = d_out_inf ? (uint8_t*)d_out_inf + lo : nullptr;
+        if (hash)
+            hipLaunchKernelGGL(blsgpu::h2g1::k_h2g1<1>, grid, dim3(256), 0, st, g1_generator(), in, (uint32_t)m, aff, ser, inf);
+        else
+            hipLaunchKernelGGL(blsgpu::h2g1::k_h2g1<0>, grid, dim3(256), 0, st, g1_generator(), in, (uint32_t)m, aff, ser, inf);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    });
+}
+// the host-buffer forms: FIX_HOST_SLICE messages per staged slice
+static int h2g1_host(blsgpu_ctx* c, bool hash, const uint8_t* in, size_t n, uint8_t* out_aff, uint8_t* out_ser, uint8_t* out_inf) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (n == 0) return 0;
+    if (!in || (!out_aff && !out_ser)) return fail(-EINVAL, "NULL argument");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t HS = slice_len(c, FIX_HOST_SLICE), S = n < HS ? n : HS;
+    Staging s(c);
+    const int din = s.in(in, S, hash ? 32 : 96), daff = s.out(out_aff, S, 96), dser = s.out(out_ser, S, 48), dinf = s.out(out_inf, S, 1);
+    if (int rc = s.alloc()) return rc;
+    return for_slices(n, S, [&](size_t lo, size_t m) {
+        if (int rc = s.up(lo, m)) return rc;
+        if (int rc = h2g1_dev(c, hash, s.at(din), m, s.opt(daff), s.opt(dser), s.opt(dinf), nullptr)) return rc;
+        return s.down(lo, m);
+    });
+}
+BLSGPU_EXPORT int blsgpu_map_to_g1(blsgpu_ctx* c, const uint8_t* t, size_t n, uint8_t* out_aff, uint8_t* out_ser, uint8_t* out_inf) {
+    return h2g1_host(c, false, t, n, out_aff, out_ser, out_inf);
+}
+BLSGPU_EXPORT int blsgpu_map_to_g1_dev(blsgpu_ctx* c, const void* d_t, size_t n, void* d_out_aff, void* d_out_ser, void* d_out_inf,
+                                       void* stream) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    return h2g1_dev(c, false, d_t, n, d_out_aff, d_out_ser, d_out_inf, (hipStream_t)stream);
+}
+// The whole hash_to_point_prehashed_Fq (ec.py:511-520) for 32-byte message hashes.
+BLSGPU_EXPORT int blsgpu_hash_to_g1(blsgpu_ctx* c, const uint8_t* msg_hashes, size_t n, uint8_t* out_aff, uint8_t* out_ser,
+                                    uint8_t* out_inf) {
+    return h2g1_host(c, true, msg_hashes, n, out_aff, out_ser, out_inf);
+}
+BLSGPU_EXPORT int blsgpu_hash_to_g1_dev(blsgpu_ctx* c, const void* d_msg_hashes, size_t n, void* d_out_aff, void* d_out_ser,
+                                        void* d_out_inf, void* stream) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    return h2g1_dev(c, true, d_msg_hashes, n, d_out_aff, d_out_ser, d_out_inf, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------ G2 multiplication by secret scalars, signing (blsgpu_g2smul.hip) --

@@ -11,7 +11,7 @@
 #define BLSGPU_TU_ML 3      // blsgpu_ml.hip: line-stream Miller stage
 #define BLSGPU_TU_FX 4      // blsgpu_fexp.hip: batched final exponentiations
 #define BLSGPU_TU_MSM 5     // blsgpu_msm.hip: multi-scalar sums; blsgpu_g2smul.hip, blsgpu_smul64.hip: scalar multiplication on their point arithmetic
-#define BLSGPU_TU_H2C 6     // blsgpu_h2c.hip: hash to G2, decompression
+#define BLSGPU_TU_H2C 6     // blsgpu_h2c.hip: hash to G2, decompression; blsgpu_h2g1.hip: hash to G1
 #define BLSGPU_TU_FXW 7     // blsgpu_fexpw.hip: one final exponentiation per wavefront
 #define BLSGPU_TU_FIX 8     // blsgpu_g1fix.hip / blsgpu_g1poly.hip / blsgpu_subgroup.hip / blsgpu_lagrange.hip / blsgpu_frsecret.hip /
                             // blsgpu_hashpks.hip / blsgpu_sigshares.hip / blsgpu_seeds.hip / blsgpu_batchfind.hip: fixed-base G1 multiplication, HD child derivation, keys from seeds, share checks, subgroup
