@@ -2,7 +2,7 @@
 workspace cannot be allocated (VERDICT r3 item 1 d / e): each is reachable through an environment knob read at context
 creation (csrc/blsgpu_api.hip), so each gets the reference's vectors.
 
-  BLSGPU_LS_WIDE_MAX=0      k_ml_lines4 (one pair per lane QUAD) where the default is k_ml_lines_wide (sixteen lanes per pair, up to 10 240 pairs)
+  BLSGPU_LS_WIDE_MAX=0      k_ml_lines4 (one pair per lane QUAD) where the default is k_ml_lines_wide (sixteen lanes per pair, up to 5120 pairs)
   BLSGPU_LS_QUAD_MAX=0      (with the former) k_ml_lines2 (one pair per lane PAIR) for calls of every size: the kernel of bench.py's
                             524 800-pair step, which calls of up to 20 480 pairs -- every vector here -- otherwise leave to the other two
   BLSGPU_LS_MERGE_WIDE_MAX=0  k_ml_merge (six lanes per value) for every merge level (default: k_ml_merge_wide, one wavefront per

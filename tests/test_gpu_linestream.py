@@ -22,7 +22,7 @@ def flags(v):
 # kernel of bench.py's 524 800-pair step).  Every test below that takes `ls` runs once per form: "lane_pairs" creates the
 # context with BLSGPU_LS_QUAD_MAX=0, so k_ml_lines2's own flagging path (Q flagged / off the twist / final Z = 0 behind
 # sp::tangent_step) meets the edge and degenerate vectors at these sizes too.
-# Round 5 added a third form for calls of up to 10 240 pairs: sixteen lanes per pair with the values in LDS (k_ml_lines_wide,
+# Round 5 added a third form for calls of up to 5120 pairs: sixteen lanes per pair with the values in LDS (k_ml_lines_wide,
 # csrc/blsgpu_lsw.hip) -- "sixteen_lanes" below is the default selection at these sizes, "lane_quads" switches it off.
 CHAIN_FORMS = {"sixteen_lanes": {}, "lane_quads": {"BLSGPU_LS_WIDE_MAX": "0"}, "lane_pairs": {"BLSGPU_LS_WIDE_MAX": "0", "BLSGPU_LS_QUAD_MAX": "0"}}
 
