@@ -654,6 +654,43 @@ int blsgpu_g1_msm_ranges_dev(blsgpu_ctx *ctx, const void *d_pts, const void *d_s
 int blsgpu_g2_msm_ranges_dev(blsgpu_ctx *ctx, const void *d_pts, const void *d_scalars, size_t n, const void *d_ranges, size_t m,
                              void *d_out_aff, void *d_out_flag, void *stream);
 
+/* Batched Signature.divide_by (signature.py:44-103 of the reference; csrc/sigdiv.h, csrc/blsgpu_sigdiv.hip): m dividends, each
+ * with any number of divisors, in one call.  The caller has done the dictionary work: for every entry (message hash, public
+ * key) of every divisor's aggregation tree it hands in the dividend's exponent a and the divisor's exponent b of that entry.
+ *   out_aff[j] = pts[first of j] + sum over j's divisors d of (-q_d) pts[d],   q_d = a_0 / b_0 mod n from d's FIRST entry,
+ * and every further entry e of d is held against it by a_e b_0 == a_0 b_e (mod n): with every b non-zero that is the
+ * reference's `quotient != new_quotient`.  One inversion mod n per divisor, two products per entry.
+ * pts: n_pts x 192 bytes affine G2, (0,0) = infinity.  pt_off: m + 1 uint32, dividend j owns the points [pt_off[j], pt_off[j+1]):
+ * the first is its own signature, the others its divisors.  ent_off: n_pts + 1 uint32, point p owns the entries [ent_off[p],
+ * ent_off[p+1]): none for a dividend's own point, at least one for a divisor.  ent_dividend / ent_divisor: n_ent x 32 bytes
+ * big-endian each, any value below 2^256, taken mod n.
+ * out_aff: m points, (0,0) for infinity.  out_flag: m bytes -- 0 finite, 1 infinity, 2 the range holds a point that is neither
+ * (0,0) nor on the twist (as blsgpu_g2_msm_ranges reports it), 3 a divisor of j has status 1 or 2: the output is (0,0).
+ * out_status: n_pts bytes -- 0 fine (always for a dividend's own point), 1 the pairs of this divisor are not unique (an entry
+ * fails the test above), 2 an exponent b of this divisor is 0 mod n: not decided here (the reference divides by zero its own
+ * way; the caller's host loop decides it).  out_scalars (may be NULL): n_pts x 32 bytes big-endian, the scalar of every point
+ * in the layout blsgpu_g2_msm_ranges takes -- 1 for a dividend's own point, (n - q_d) mod n for a divisor, 0 for a refused one.
+ * stats (may be NULL; host memory in BOTH forms): [0] 0 the plain path ran, 1 the scalar path; [1] the divisors with q != 1.
+ * The plain path: when every accepted quotient of the call is 1 -- aggregates that were never merged securely, the common
+ * case -- the sums are blsgpu_g2_range_sums over a working copy of the points in which every divisor is replaced by its
+ * negative; no scalar multiplication runs.  Otherwise the sums are blsgpu_g2_msm_ranges over the points as given with the
+ * scalars above.  Both give the same bytes; BLSGPU_SIGDIV_PLAIN=0 at context creation sends every call down the scalar path.
+ * Both forms check the offsets on the device and synchronise ONCE, reading that check and the number of non-unit quotients
+ * together, before anything is written to the outputs (the sums then synchronise once more for their own plan where
+ * blsgpu_g2_msm_ranges does).  The workspace -- the scalars, the working copy, the statuses and the ranges -- counts in
+ * BLSGPU_WS_TOTAL.
+ * -EINVAL before anything is written: a NULL required buffer (everything but out_scalars and stats; ent_dividend / ent_divisor
+ * with n_ent > 0), offsets that decrease, pt_off[0] != 0, pt_off[m] != n_pts, ent_off[0] != 0, ent_off[n_pts] != n_ent, an
+ * empty dividend range, a dividend's own row with entries, a divisor's row with none.  m == 0 writes nothing and returns 0.
+ * Signatures, trees and exponents are PUBLIC data: not constant-time. */
+int blsgpu_sig_divide(blsgpu_ctx *ctx, const uint8_t *pts, size_t n_pts, const uint32_t *pt_off, size_t m, const uint32_t *ent_off,
+                      const uint8_t *ent_dividend, const uint8_t *ent_divisor, size_t n_ent, uint8_t *out_aff, uint8_t *out_flag,
+                      uint8_t *out_status, uint8_t *out_scalars, uint32_t stats[2]);
+/* The same with every buffer but stats in device memory (points 16-byte aligned, offsets and exponents 4-byte), on `stream`. */
+int blsgpu_sig_divide_dev(blsgpu_ctx *ctx, const void *d_pts, size_t n_pts, const void *d_pt_off, size_t m, const void *d_ent_off,
+                          const void *d_ent_dividend, const void *d_ent_divisor, size_t n_ent, void *d_out_aff, void *d_out_flag,
+                          void *d_out_status, void *d_out_scalars, uint32_t stats[2], void *stream);
+
 /* blsgpu_verify_find with the items of one message FOLDED inside every node: arguments, status bytes and stats as there, with
  * ONE precondition -- msg_idx is non-decreasing over the items (a decrease is -EINVAL before anything is written; the _dev form
  * finds it in the device scan that checks the indices).  The dense order keeps input order, so every message is one

@@ -87,6 +87,76 @@ class Signature:
         out.aggregation_info.public_keys = [k[1] for k in keys]
         return out
 
+    @staticmethod
+    def divide_by_batch(dividends, divisor_lists):
+        """[d.divide_by(ds) for d, ds in zip(dividends, divisor_lists)] with the quotient scalars of every divisor and the G2
+        sums of every dividend in one device call (blsgpu_sig_divide through backend.extension("sig_divide")); without that
+        extension it is the loop.  The host keeps the dictionary work: the tree lookups that pair the dividend's exponent
+        with the divisor's for every entry, and the removal and re-sort of the tree.  Raises what the loop raises for the
+        first failing dividend in input order: a dividend whose lookups fail ends the batch there -- the dividends before
+        it are still checked on the device, since the loop would have met their errors first -- and is then handed to
+        divide_by, which raises.  A dividend with a divisor exponent that is 0 mod n, with a point off the twist or with a
+        point the 192-byte form cannot carry goes through divide_by as well."""
+        from . import backend
+        from .aggregation_info import AggregationInfo
+        dividends, divisor_lists = list(dividends), [list(ds) for ds in divisor_lists]
+        if len(dividends) != len(divisor_lists):
+            raise ValueError("one list of divisors per dividend")
+        fn = backend.extension("sig_divide")
+        if fn is None or not dividends:
+            return [d.divide_by(ds) for d, ds in zip(dividends, divisor_lists)]
+        # the host pass: per dividend its points (own signature first), per divisor its entries' exponents
+        pts, pt_off, ent_off, ea, eb, drops, fails_at = [], [0], [0], [], [], [], None
+        for j, (sig, divs) in enumerate(zip(dividends, divisor_lists)):
+            mine, rows, a, b, drop = [sig.value], [0], [], [], []
+            try:
+                own = sig.aggregation_info.tree
+                for div in divs:
+                    info = div.aggregation_info
+                    if len(info.public_keys) != len(info.message_hashes):
+                        raise LookupError
+                    for key in zip(info.message_hashes, info.public_keys):
+                        b.append(info.tree[key] % GROUP_ORDER)
+                        a.append(own[key] % GROUP_ORDER)
+                        drop.append(key)
+                    if info.public_keys:                     # a divisor with no entries has no quotient: skipped, as in the loop
+                        mine.append(div.value)
+                        rows.append(len(info.public_keys))
+            except Exception:                                # divide_by names it, after whatever the loop meets before it
+                fails_at = j
+                break
+            pts += mine
+            for r in rows:
+                ent_off.append(ent_off[-1] + r)
+            pt_off.append(len(pts))
+            ea += a
+            eb += b
+            drops.append(drop)
+        m = len(drops)
+        out = [None] * m
+        if m:
+            affs = [P.to_affine()._aff() for P in pts]
+            enc = [H.g2_affine_bytes(A) for A in affs]
+            odd = [A is not None and e == bytes(192) for A, e in zip(affs, enc)]
+            res, flag, status, _, _ = fn(b"".join(enc), pt_off, ent_off, ea, eb)
+            for j in range(m):
+                sig, lo, hi = dividends[j], pt_off[j], pt_off[j + 1]
+                if flag[j] == 2 or 2 in status[lo:hi] or any(odd[lo:hi]):
+                    out[j] = sig.divide_by(divisor_lists[j])
+                    continue
+                if 1 in status[lo:hi]:
+                    raise Exception("Cannot divide by aggregate signature,msg/pk pairs are not unique")
+                value = JacobianPoint._from(H.F2, None if flag[j] == 1 else H.aff_to_jac(H.F2, H.g2_from_abi(res[192 * j:192 * (j + 1)])),
+                                            default_ec_twist)
+                tree = deepcopy(sig.aggregation_info.tree)
+                for key in drops[j]:
+                    tree.pop(key, None)
+                out[j] = Signature(value, AggregationInfo._from_tree(tree))
+        if fails_at is not None:
+            dividends[fails_at].divide_by(divisor_lists[fails_at])
+            raise AssertionError("divide_by accepted what the lookups refused")
+        return out
+
     def serialize(self):
         return self.value.serialize()
 

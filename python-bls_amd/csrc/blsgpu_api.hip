@@ -27,6 +27,7 @@
 #include "blsgpu_g1poly.hip"
 #include "blsgpu_subgroup.hip"
 #include "blsgpu_lagrange.hip"
+#include "blsgpu_sigdiv.hip"
 #include "blsgpu_frsecret.hip"
 #include "blsgpu_hashpks.hip"
 #include "blsgpu_sigshares.hip"
@@ -1487,6 +1488,93 @@ int msm_ranges_host(blsgpu_ctx* c, const uint8_t* pts, const uint8_t* scalars, s
     if (int rc = s.alloc()) return rc;
     if (int rc = s.up()) return rc;
     if (int rc = msm_ranges_dev<DEG>(c, s.opt(dp), s.opt(dsc), n, s.at(dr), m, s.at(dout), s.at(df), nullptr)) return rc;
+    return s.down();
+}
+
+// ------------------------------------------------------------ batched Signature.divide_by (blsgpu_sigdiv.hip) --
+// the argument checks of blsgpu_sig_divide* (before anything is written); 1: nothing to do
+int sig_divide_args(const blsgpu_ctx* c, const void* pts, size_t n_pts, const void* pt_off, size_t m, const void* ent_off, const void* ea,
+                    const void* eb, size_t n_ent, const void* out, const void* flag, const void* status) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (m == 0) return 1;
+    if (!pts || !pt_off || !ent_off || !out || !flag || !status || (n_ent && (!ea || !eb))) return fail(-EINVAL, "NULL argument");
+    if (n_pts > 0xFFFFFFF0ull || n_ent > 0xFFFFFFF0ull || m > 0x7FFFFFF0ull / blsgpu::SrtG<2>::LP) return fail(-EINVAL, "batch too large");
+    if (n_pts < m) return fail(-EINVAL, "a dividend without a point");
+    return 0;
+}
+// The offsets are checked on the device (k_sigdiv_check), the entries tested (k_sigdiv_cross), the scalars, statuses and the
+// working copy written into the WORKSPACE (k_sigdiv_quot, k_sigdiv_fold), and ONE synchronisation reads the head words: the
+// verdict on the offsets and the number of non-unit quotients.  Only then do the statuses and scalars go to the caller and
+// the sums run: the plain sums of the working copy when no accepted quotient differs from 1 (and the knob allows it), the
+// ragged multi-scalar sums of the points as given otherwise.  A refused dividend gets flag 3 and (0,0) last.
+int sig_divide_dev(blsgpu_ctx* c, const void* d_pts, size_t n_pts, const void* d_pt_off, size_t m, const void* d_ent_off, const void* d_ea,
+                   const void* d_eb, size_t n_ent, void* d_out, void* d_flag, void* d_status, void* d_scalars, uint32_t* stats, hipStream_t st) {
+    namespace sd = blsgpu::sigdiv;
+    StreamGuard sg(c, st);
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_mism = 256, o_zero = o_mism + al(n_pts), o_nonunit = o_zero + al(n_pts), o_status = o_nonunit + al(n_pts),
+                 o_refused = o_status + al(n_pts), o_ranges = o_refused + al(m), o_scalars = o_ranges + al(8 * m), o_work = o_scalars + al(32 * n_pts),
+                 o_end = o_work + al(192 * n_pts);
+    if (int rc = c->grow(B_SIGDIV_WS, o_end)) return rc;
+    char* const W = c->at<char>(B_SIGDIV_WS);
+    uint32_t* const head = (uint32_t*)W;
+    HIP_TRY(hipMemsetAsync(W, 0, o_nonunit, st));                              // the head words, mism and zero
+    const size_t idx = (m > n_pts ? m : n_pts) + 1;
+    hipLaunchKernelGGL(sd::k_sigdiv_check, dim3((unsigned)((idx + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_pt_off, (uint32_t)m,
+                       (const uint32_t*)d_ent_off, (uint32_t)n_pts, (uint32_t)n_ent, head);
+    if (n_ent)
+        hipLaunchKernelGGL(sd::k_sigdiv_cross, dim3((unsigned)((n_ent + 255) / 256)), dim3(256), 0, st, head, (const uint32_t*)d_ent_off, (uint32_t)n_pts,
+                           (const uint8_t*)d_ea, (const uint8_t*)d_eb, (uint32_t)n_ent, (uint8_t*)(W + o_mism), (uint8_t*)(W + o_zero));
+    hipLaunchKernelGGL(sd::k_sigdiv_quot, dim3((unsigned)((n_pts + 255) / 256)), dim3(256), 0, st, head, (const uint32_t*)d_ent_off, (uint32_t)n_pts,
+                       (const uint8_t*)d_ea, (const uint8_t*)d_eb, (const uint8_t*)(W + o_mism), (const uint8_t*)(W + o_zero), (const uint32_t*)d_pts,
+                       (uint8_t*)(W + o_status), (uint8_t*)(W + o_scalars), (uint8_t*)(W + o_nonunit), (uint32_t*)(W + o_work));
+    hipLaunchKernelGGL(sd::k_sigdiv_fold, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, head, (const uint32_t*)d_pt_off, (uint32_t)m,
+                       (const uint8_t*)(W + o_status), (uint8_t*)(W + o_refused), (uint32_t*)(W + o_ranges));
+    HIP_TRY(hipGetLastError());
+    uint32_t h[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h, head, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h[0]) return fail(-EINVAL, "offsets out of order, a dividend without a point or with entries of its own");
+    if (h[1] != m) return fail(-EINVAL, "a divisor without entries");
+    const bool plain = c->sigdiv_plain && h[2] == 0;
+    if (stats) {
+        stats[0] = plain ? 0u : 1u;
+        stats[1] = h[2];
+    }
+    HIP_TRY(hipMemcpyAsync(d_status, W + o_status, n_pts, hipMemcpyDeviceToDevice, st));
+    if (d_scalars) HIP_TRY(hipMemcpyAsync(d_scalars, W + o_scalars, 32 * n_pts, hipMemcpyDeviceToDevice, st));
+    if (plain) {
+        if (int rc = range_sums_run<2>(c, W + o_work, n_pts, W + o_ranges, m, d_out, d_flag, false, st)) return rc;
+    } else {
+        if (int rc = msm_ranges_dev<2>(c, d_pts, W + o_scalars, n_pts, W + o_ranges, m, d_out, d_flag, st)) return rc;
+    }
+    hipLaunchKernelGGL(sd::k_sigdiv_refuse, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint8_t*)(W + o_refused), (uint32_t)m,
+                       (uint32_t*)d_out, (uint8_t*)d_flag);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+int sig_divide_host(blsgpu_ctx* c, const uint8_t* pts, size_t n_pts, const uint32_t* pt_off, size_t m, const uint32_t* ent_off, const uint8_t* ea,
+                    const uint8_t* eb, size_t n_ent, uint8_t* out, uint8_t* flag, uint8_t* status, uint8_t* scalars, uint32_t* stats) {
+    if (int rc = sig_divide_args(c, pts, n_pts, pt_off, m, ent_off, ea, eb, n_ent, out, flag, status)) return rc < 0 ? rc : 0;
+    if (pt_off[0] != 0 || pt_off[m] != n_pts || ent_off[0] != 0 || ent_off[n_pts] != n_ent) return fail(-EINVAL, "offsets do not span the lists");
+    for (size_t p = 0; p < n_pts; p++)
+        if (ent_off[p] > ent_off[p + 1] || ent_off[p + 1] > n_ent) return fail(-EINVAL, "entry offsets out of order");
+    for (size_t j = 0; j < m; j++) {
+        if (pt_off[j] >= pt_off[j + 1] || pt_off[j + 1] > n_pts) return fail(-EINVAL, "point offsets out of order or a dividend without a point");
+        if (ent_off[pt_off[j]] != ent_off[pt_off[j] + 1]) return fail(-EINVAL, "a dividend with entries of its own");
+        for (size_t p = pt_off[j] + 1; p < pt_off[j + 1]; p++)
+            if (ent_off[p] == ent_off[p + 1]) return fail(-EINVAL, "a divisor without entries");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    Staging s(c);
+    const int dp = s.in(pts, n_pts * 192), dpo = s.in(pt_off, (m + 1) * 4), deo = s.in(ent_off, (n_pts + 1) * 4),
+              da = s.in(n_ent ? ea : nullptr, n_ent * 32), db = s.in(n_ent ? eb : nullptr, n_ent * 32), dout = s.out(out, m * 192), df = s.out(flag, m),
+              dst = s.out(status, n_pts), dsc = s.out(scalars, n_pts * 32);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    if (int rc = sig_divide_dev(c, s.at(dp), n_pts, s.at(dpo), m, s.at(deo), s.opt(da), s.opt(db), n_ent, s.at(dout), s.at(df), s.at(dst), s.opt(dsc),
+                                stats, nullptr))
+        return rc;
     return s.down();
 }
 
@@ -3502,6 +3590,20 @@ BLSGPU_EXPORT int blsgpu_g2_msm_ranges_dev(blsgpu_ctx* c, const void* d_pts, con
     if (int rc = msm_ranges_args(c, d_pts, d_scalars, n, d_ranges, m, d_out_aff, d_out_flag)) return rc < 0 ? rc : 0;
     HIP_TRY(hipSetDevice(c->device));
     return msm_ranges_dev<2>(c, d_pts, d_scalars, n, d_ranges, m, d_out_aff, d_out_flag, (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_sig_divide(blsgpu_ctx* c, const uint8_t* pts, size_t n_pts, const uint32_t* pt_off, size_t m, const uint32_t* ent_off,
+                                    const uint8_t* ent_dividend, const uint8_t* ent_divisor, size_t n_ent, uint8_t* out_aff, uint8_t* out_flag,
+                                    uint8_t* out_status, uint8_t* out_scalars, uint32_t stats[2]) {
+    return sig_divide_host(c, pts, n_pts, pt_off, m, ent_off, ent_dividend, ent_divisor, n_ent, out_aff, out_flag, out_status, out_scalars, stats);
+}
+BLSGPU_EXPORT int blsgpu_sig_divide_dev(blsgpu_ctx* c, const void* d_pts, size_t n_pts, const void* d_pt_off, size_t m, const void* d_ent_off,
+                                        const void* d_ent_dividend, const void* d_ent_divisor, size_t n_ent, void* d_out_aff, void* d_out_flag,
+                                        void* d_out_status, void* d_out_scalars, uint32_t stats[2], void* stream) {
+    if (int rc = sig_divide_args(c, d_pts, n_pts, d_pt_off, m, d_ent_off, d_ent_dividend, d_ent_divisor, n_ent, d_out_aff, d_out_flag, d_out_status))
+        return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return sig_divide_dev(c, d_pts, n_pts, d_pt_off, m, d_ent_off, d_ent_dividend, d_ent_divisor, n_ent, d_out_aff, d_out_flag, d_out_status,
+                          d_out_scalars, stats, (hipStream_t)stream);
 }
 BLSGPU_EXPORT int blsgpu_verify_find_folded_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_t n_keys, const void* d_key_idx,
                                                 const void* d_msg_hashes, size_t n_msgs, const void* d_msg_idx, const void* d_weights, size_t n,

@@ -72,6 +72,7 @@ enum BufId {
     B_PSCAN_G1,          // blsgpu_g1_range_sums* and SB of blsgpu_verify_find_folded*: one slice of prepared points, their live and kind bytes, the chunk totals and counts, the prefix records and counts, the carry (blsgpu_pscan.hip)
     B_PSCAN_G2,          // ... the same for blsgpu_g2_range_sums* and SA
     B_PSCAN_RANGE,       // blsgpu_g?_range_sums*: a flag word and, when the points take several slices, the record and count at every range's begin
+    B_SIGDIV_WS,         // blsgpu_sig_divide*: the head words, the mismatch / zero / non-unit / status bytes per point, the refused byte and the range per dividend, the scalars and the working copy of the points
     B_COUNT
 };
 // (unit: what the buffer is counted in -- whole partials, whole u32 entries, bytes)
@@ -81,7 +82,7 @@ constexpr BufInfo BUF_INFO[B_COUNT] = {
     {BLSGPU_WS_LINE_PRODUCTS, 1}, {BLSGPU_WS_LINE_PRODUCTS, 1}, {BLSGPU_WS_FLAGS_AND_LISTS, 1}, {BLSGPU_WS_FLAGS_AND_LISTS, 4},
     {BLSGPU_WS_FLAGS_AND_LISTS, 1}, {BLSGPU_WS_GROUP_SUMS, 4}, {BLSGPU_WS_GROUP_SUMS, 4}, {BLSGPU_WS_SLOTS, 1}, {BLSGPU_WS_SLOTS, 1},
     {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1},
-    {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}};   // no field of their own: they count in the total only
+    {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}};   // no field of their own: they count in the total only
 
 }  // namespace
 
@@ -127,6 +128,7 @@ struct blsgpu_ctx {
     size_t smul_min_groups = 4096;      // sums per call from which a batch of SMALL sums with scalars (scalar multiplications: groups x 1 point) runs one group per lane / lane pair (k_smul, round 5) instead of the wavefront VM's k_msm
     size_t smul_max_k = 8;              // ... for sums of up to this many points
     static uint32_t msm_sort2_bits(size_t n) { return n >= 16384 ? 13 : (n >= 512 ? 11 : 9); }   // window bits of the G2 path by size (tools/g2_single_sum_probe.py, profiles/r05_g2_single_sum.txt)
+    bool sigdiv_plain = true;           // blsgpu_sig_divide*: a call whose accepted quotients are all 1 sums the negated divisors (blsgpu_g2_range_sums' passes) and multiplies nothing; false: every call takes the scalars through blsgpu_g2_msm_ranges' kernels (the tests hold the two against each other)
     size_t horner_np_threshold = 1024; // G2 sums per call from which the window Horner runs several sums per team
     size_t horner_quads_threshold = 2; // G2 sums per call (lane-pair bucket kernel) from which the window Horner runs one sum per lane quad
     size_t wg256_max_waves = 4096;     // register kernels: launches of up to this many wavefronts go out as 256-thread workgroups (blsgpu_tu.h)
@@ -221,6 +223,7 @@ const Knob KNOBS[] = {
     {"BLSGPU_WG256_MAX_WAVES", &blsgpu_ctx::wg256_max_waves},
     {"BLSGPU_MSM_LANE_THRESHOLD", &blsgpu_ctx::msm_lane_threshold},
     {"BLSGPU_MSM_LANE_PAIRS", &blsgpu_ctx::msm_lane_pairs},
+    {"BLSGPU_SIGDIV_PLAIN", &blsgpu_ctx::sigdiv_plain},
 };
 void read_knobs(blsgpu_ctx* c) {
     for (const Knob& k : KNOBS)
@@ -270,7 +273,7 @@ WaveShape wave_shape(const blsgpu_ctx* c, size_t waves) {
 struct Staging {
     struct Region { size_t off, bytes, item; const char* src; char* dst; bool absent; };
     blsgpu_ctx* c;
-    Region r[8];
+    Region r[10];
     int n = 0;
     size_t total = 0;
     explicit Staging(blsgpu_ctx* c_) : c(c_) {}

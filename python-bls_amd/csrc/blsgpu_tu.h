@@ -13,11 +13,11 @@
 #define BLSGPU_TU_MSM 5     // blsgpu_msm.hip: multi-scalar sums; blsgpu_g2smul.hip, blsgpu_smul64.hip: scalar multiplication on their point arithmetic
 #define BLSGPU_TU_H2C 6     // blsgpu_h2c.hip: hash to G2, decompression; blsgpu_h2g1.hip: hash to G1
 #define BLSGPU_TU_FXW 7     // blsgpu_fexpw.hip: one final exponentiation per wavefront
-#define BLSGPU_TU_FIX 8     // blsgpu_g1fix.hip / blsgpu_g1poly.hip / blsgpu_subgroup.hip / blsgpu_lagrange.hip / blsgpu_frsecret.hip /
+#define BLSGPU_TU_FIX 8     // blsgpu_g1fix.hip / blsgpu_g1poly.hip / blsgpu_subgroup.hip / blsgpu_lagrange.hip / blsgpu_sigdiv.hip / blsgpu_frsecret.hip /
                             // blsgpu_hashpks.hip / blsgpu_sigshares.hip / blsgpu_seeds.hip / blsgpu_batchfind.hip: fixed-base G1 multiplication, HD child derivation, keys from seeds, share checks, subgroup
                             // membership, Lagrange coefficients, the scalar-field work on secrets (dealing, recovery, threshold
                             // signing), the exponents of secure aggregation, the glue of the signature-share check and of the
-                            // batch verification that names the forgeries
+                            // batch verification that names the forgeries, the quotient scalars of Signature.divide_by
 #ifndef BLSGPU_TU
 #define BLSGPU_TU 0
 #endif
