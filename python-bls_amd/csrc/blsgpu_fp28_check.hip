@@ -5,8 +5,7 @@
 //
 // One kernel per op (a template on the op): each op is compiled the way the kernels compile it, not as one switch
 // with every product alive at once.  Raw products run 64 lanes per workgroup, everything else 256; spare lanes of
-// the last workgroup store nothing.  The host function puts a guard record of 0xAA bytes on either side of the
-// device output and reports a written guard.
+// the last workgroup store nothing.  The guard records and the return codes are check_runner.h's.
 //
 // Ranges.  The limb arithmetic of add / sub / neg / mulc / norm / mulc_norm / conj / mul_xi is the same code for every
 // F<LO, HI>; the type only says which inputs are admitted.  Each linear op is therefore instantiated here at a range
@@ -39,30 +38,31 @@
 //   padd / pmadd / pdbl / pneg / padd_fn / pdbl_fn  fe and fe2: blsgpu_g1fix.hip, blsgpu_g1poly.hip, blsgpu_g2smul.hip,
 //                                          blsgpu_subgroup.hip, blsgpu_h2c.hip:797 - :930, blsgpu_msm.hip:579
 // (blsgpu_ml.hip and blsgpu_msm.hip keep lane-pair types of their own, S<A> / h, over the same fp28_dotK products.)
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <string.h>
-#include <vector>
+#include "check_runner.h"
 #include "fp28.h"
 
 namespace {
 using namespace blsgpu::r28;
 
-enum Op {
-    // raw products
-    RAW_DOT1 = 0, RAW_DOT2, RAW_DOT3, RAW_DOT4, RAW_DOT6, RAW_SQR1, RAW_SQR2,
-    // linear / carry
-    LIN_ADD = 10, LIN_SUB, LIN_NEG, LIN_MULC3, LIN_NORM, LIN_MULC_NORM3, LIN_MULC_NORM8, LIN_MULC_NORM12, LIN_CANON, LIN_IS_ZERO,
-    // typed products
-    T_MUL = 20, T_MUL_8x1, T_MUL_4x2, T_MUL_2x4, T_MUL_NEG9, T_SQR, T_SQR_2, T_DOT2, T_DOT2_2222, T_DOT2_4122, T_DOT4, T_DOT4_21,
-    // boundaries
-    B_UNPACK32 = 40, B_PACK32, B_FROM_VM, B_TO_VM, B_FROM_RAW, B_TO_RAW, B_VM_MUL28,
-    // Fq2
-    F2_MUL = 50, F2_MUL_W, F2_SQR, F2_SQR_W, F2_DOT2, F2_DOT2_W, F2_MUL_XI, F2_CONJ, F2_B3, F2_NORM, F2_CANON, F2_IS_ZERO,
-    // curve: G1 at 70, the twist at 80
-    G1_PADD = 70, G1_PMADD, G1_PDBL, G1_PNEG, G1_PADD_FN, G1_PDBL_FN, G1_CHAIN8,
-    G2_PADD = 80, G2_PMADD, G2_PDBL, G2_PNEG, G2_PADD_FN, G2_PDBL_FN, G2_CHAIN8,
-};
+// every op, once, with its code (tests/fp28_vectors.py pins the codes)
+#define FP28CHECK_OPS(X) \
+    /* raw products */ \
+    X(RAW_DOT1, 0) X(RAW_DOT2, 1) X(RAW_DOT3, 2) X(RAW_DOT4, 3) X(RAW_DOT6, 4) X(RAW_SQR1, 5) X(RAW_SQR2, 6) \
+    /* linear / carry */ \
+    X(LIN_ADD, 10) X(LIN_SUB, 11) X(LIN_NEG, 12) X(LIN_MULC3, 13) X(LIN_NORM, 14) X(LIN_MULC_NORM3, 15) X(LIN_MULC_NORM8, 16) \
+    X(LIN_MULC_NORM12, 17) X(LIN_CANON, 18) X(LIN_IS_ZERO, 19) \
+    /* typed products */ \
+    X(T_MUL, 20) X(T_MUL_8x1, 21) X(T_MUL_4x2, 22) X(T_MUL_2x4, 23) X(T_MUL_NEG9, 24) X(T_SQR, 25) X(T_SQR_2, 26) X(T_DOT2, 27) \
+    X(T_DOT2_2222, 28) X(T_DOT2_4122, 29) X(T_DOT4, 30) X(T_DOT4_21, 31) \
+    /* boundaries */ \
+    X(B_UNPACK32, 40) X(B_PACK32, 41) X(B_FROM_VM, 42) X(B_TO_VM, 43) X(B_FROM_RAW, 44) X(B_TO_RAW, 45) X(B_VM_MUL28, 46) \
+    /* Fq2 */ \
+    X(F2_MUL, 50) X(F2_MUL_W, 51) X(F2_SQR, 52) X(F2_SQR_W, 53) X(F2_DOT2, 54) X(F2_DOT2_W, 55) X(F2_MUL_XI, 56) X(F2_CONJ, 57) \
+    X(F2_B3, 58) X(F2_NORM, 59) X(F2_CANON, 60) X(F2_IS_ZERO, 61) \
+    /* curve: G1 at 70, the twist at 80 */ \
+    X(G1_PADD, 70) X(G1_PMADD, 71) X(G1_PDBL, 72) X(G1_PNEG, 73) X(G1_PADD_FN, 74) X(G1_PDBL_FN, 75) X(G1_CHAIN8, 76) \
+    X(G2_PADD, 80) X(G2_PMADD, 81) X(G2_PDBL, 82) X(G2_PNEG, 83) X(G2_PADD_FN, 84) X(G2_PDBL_FN, 85) X(G2_CHAIN8, 86)
+CHECK_ENUM(FP28CHECK_OPS)
 
 template <int LO, int HI> __device__ __forceinline__ F<LO, HI> ldF(const int32_t* p) {
     F<LO, HI> r;
@@ -215,50 +215,13 @@ template <int OP> __global__ void __launch_bounds__(OP < LIN_ADD ? 64 : 256) k_c
     Do<OP>::run(in + i * Do<OP>::win, out + i * Do<OP>::wout);
 }
 
-constexpr size_t GUARD = 256;                              // bytes of 0xAA on either side of the output
-
 template <int OP> int run_op(const int32_t* in, size_t words_in, size_t n, int32_t* out, size_t words_out) {
     if (words_in != n * (size_t)Do<OP>::win || words_out != n * (size_t)Do<OP>::wout || n == 0 || n > (1u << 20)) return -2;
-    const size_t bin = words_in * 4, bout = words_out * 4;
     const unsigned threads = OP < LIN_ADD ? 64u : 256u;
-    char *din = nullptr, *dout = nullptr;
-    hipError_t e = hipMalloc((void**)&din, bin);
-    if (e == hipSuccess) e = hipMalloc((void**)&dout, bout + 2 * GUARD);
-    if (e == hipSuccess) e = hipMemcpy(din, in, bin, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(dout, 0xAA, bout + 2 * GUARD);
-    if (e == hipSuccess) {
-        k_check<OP><<<dim3((unsigned)((n + threads - 1) / threads)), dim3(threads)>>>((const int32_t*)din, n, (int32_t*)(dout + GUARD));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    std::vector<unsigned char> back(bout + 2 * GUARD);
-    if (e == hipSuccess) e = hipMemcpy(back.data(), dout, back.size(), hipMemcpyDeviceToHost);
-    if (din) (void)hipFree(din);
-    if (dout) (void)hipFree(dout);
-    if (e != hipSuccess) return (int)e;
-    for (size_t j = 0; j < GUARD; j++)
-        if (back[j] != 0xAA || back[GUARD + bout + j] != 0xAA) return -3;   // a lane stored outside its record
-    memcpy(out, back.data() + GUARD, bout);
-    return 0;
+    return check::guarded_run(in, words_in * 4, out, words_out * 4, 0, [=](const int32_t* din, int32_t* dout) {
+        k_check<OP><<<dim3((unsigned)((n + threads - 1) / threads)), dim3(threads)>>>(din, n, dout);
+    });
 }
 }  // namespace
 
-// 0, a HIP error code, -1 unknown op, -2 sizes that do not match the op, -3 guard record written
-extern "C" __attribute__((visibility("default")))
-int blsgpu_fp28_check(int op, const int32_t* in, size_t words_in, size_t n, int32_t* out, size_t words_out) {
-    switch (op) {
-#define CASE(OP) case OP: return run_op<OP>(in, words_in, n, out, words_out);
-        CASE(RAW_DOT1) CASE(RAW_DOT2) CASE(RAW_DOT3) CASE(RAW_DOT4) CASE(RAW_DOT6) CASE(RAW_SQR1) CASE(RAW_SQR2)
-        CASE(LIN_ADD) CASE(LIN_SUB) CASE(LIN_NEG) CASE(LIN_MULC3) CASE(LIN_NORM) CASE(LIN_MULC_NORM3) CASE(LIN_MULC_NORM8)
-        CASE(LIN_MULC_NORM12) CASE(LIN_CANON) CASE(LIN_IS_ZERO)
-        CASE(T_MUL) CASE(T_MUL_8x1) CASE(T_MUL_4x2) CASE(T_MUL_2x4) CASE(T_MUL_NEG9) CASE(T_SQR) CASE(T_SQR_2) CASE(T_DOT2)
-        CASE(T_DOT2_2222) CASE(T_DOT2_4122) CASE(T_DOT4) CASE(T_DOT4_21)
-        CASE(B_UNPACK32) CASE(B_PACK32) CASE(B_FROM_VM) CASE(B_TO_VM) CASE(B_FROM_RAW) CASE(B_TO_RAW) CASE(B_VM_MUL28)
-        CASE(F2_MUL) CASE(F2_MUL_W) CASE(F2_SQR) CASE(F2_SQR_W) CASE(F2_DOT2) CASE(F2_DOT2_W) CASE(F2_MUL_XI) CASE(F2_CONJ)
-        CASE(F2_B3) CASE(F2_NORM) CASE(F2_CANON) CASE(F2_IS_ZERO)
-        CASE(G1_PADD) CASE(G1_PMADD) CASE(G1_PDBL) CASE(G1_PNEG) CASE(G1_PADD_FN) CASE(G1_PDBL_FN) CASE(G1_CHAIN8)
-        CASE(G2_PADD) CASE(G2_PMADD) CASE(G2_PDBL) CASE(G2_PNEG) CASE(G2_PADD_FN) CASE(G2_PDBL_FN) CASE(G2_CHAIN8)
-#undef CASE
-    }
-    return -1;
-}
+CHECK_EXPORT(blsgpu_fp28_check, int32_t, FP28CHECK_OPS)

@@ -6,7 +6,9 @@
 // addc / subc builtins and the DPP absorb.  Not linked into libblsgpu.so, not declared in include/blsgpu.h, not an ABI.
 //
 // One kernel per op (a template on the op), 256 lanes per workgroup; spare lanes of the last workgroup store nothing.
-// The host function puts a guard record of 0xAA bytes on either side of the device output and reports a written guard.
+// The guard records and the return codes are check_runner.h's.  The op bodies (struct Do<OP>) also compile for the host:
+// tests/test_fq32_vectors_model.py includes this file with the host compiler and runs the same bodies on fq32.h's host code
+// (LIN_ABSORB and the kernels are device only).
 //
 // Item layouts (32-bit words):
 //   a field value                     12 words, least significant first
@@ -21,52 +23,54 @@
 //                                     (they flip with the rest) and store nothing: no lane leaves before the DPP reads.
 //   FQ_INV_UNI, FQ_INV_VAR_UNI        eight values per item, inverted one after the other: the caller gives every lane
 //                                     of a wavefront the same item, the case fq_inv_var was written for
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <string.h>
-#include <vector>
+#include "check_runner.h"
 #include "fq32.h"
+#if defined(__HIPCC__)
 #include "blsgpu_lin_absorb.h"
+#endif
 
 namespace {
 
-enum Op {
-    // products
-    FQ_MUL = 0, FQ_MUL_RELAXED, FQ_SQR_RELAXED,
-    // linear
-    FQ_ADD_MOD = 10, FQ_NEG_RAW, FQ_SUB_MOD, FQ_CANON, FQ_IS_ZERO,
-    // fat accumulators and LIN shares
-    FAT_MAC_PLAIN = 20, FAT_FLIP, FAT_REDUCE, LIN, LIN_ABSORB,
-    // decisions
-    FQ_SGN = 30, GT_HALF_Q_MASK, FQ_JACOBI_VAR,
-    // inversions
-    FQ_INV = 40, FQ_INV_VAR, FQ_INV_UNI, FQ_INV_VAR_UNI,
-};
+// every op, once, with its code (tests/fq32_vectors.py pins the codes): those that also build for the host, then the device-only one
+#define FQ32CHECK_HOST_OPS(X) \
+    /* products */ \
+    X(FQ_MUL, 0) X(FQ_MUL_RELAXED, 1) X(FQ_SQR_RELAXED, 2) \
+    /* linear */ \
+    X(FQ_ADD_MOD, 10) X(FQ_NEG_RAW, 11) X(FQ_SUB_MOD, 12) X(FQ_CANON, 13) X(FQ_IS_ZERO, 14) \
+    /* fat accumulators and LIN shares */ \
+    X(FAT_MAC_PLAIN, 20) X(FAT_FLIP, 21) X(FAT_REDUCE, 22) X(LIN, 23) \
+    /* decisions */ \
+    X(FQ_SGN, 30) X(GT_HALF_Q_MASK, 31) X(FQ_JACOBI_VAR, 32) \
+    /* inversions */ \
+    X(FQ_INV, 40) X(FQ_INV_VAR, 41) X(FQ_INV_UNI, 42) X(FQ_INV_VAR_UNI, 43)
+#define FQ32CHECK_DEVICE_OPS(X) X(LIN_ABSORB, 24)
+#define FQ32CHECK_OPS(X) FQ32CHECK_HOST_OPS(X) FQ32CHECK_DEVICE_OPS(X)
+CHECK_ENUM(FQ32CHECK_OPS)
 
 constexpr int NW = 12, FATW = 24;
 constexpr int LIN_MAXK = 30, LIN_HDR = 4, LIN_OPS = LIN_HDR + LIN_MAXK, LIN_WIN = LIN_OPS + LIN_MAXK * NW;
 constexpr int UNI = 8;
 
-__device__ __forceinline__ void ld12(uint32_t* d, const uint32_t* p) {
+CHECK_FN void ld12(uint32_t* d, const uint32_t* p) {
 #pragma unroll
     for (int j = 0; j < NW; j++) d[j] = p[j];
 }
-__device__ __forceinline__ void st12(const uint32_t* x, uint32_t* p) {
+CHECK_FN void st12(const uint32_t* x, uint32_t* p) {
 #pragma unroll
     for (int j = 0; j < NW; j++) p[j] = x[j];
 }
-__device__ __forceinline__ void ldfat(uint64_t* a, const uint32_t* p) {
+CHECK_FN void ldfat(uint64_t* a, const uint32_t* p) {
 #pragma unroll
     for (int j = 0; j < NW; j++) a[j] = (uint64_t)p[2 * j] | ((uint64_t)p[2 * j + 1] << 32);
 }
-__device__ __forceinline__ void stfat(const uint64_t* a, uint32_t* p) {
+CHECK_FN void stfat(const uint64_t* a, uint32_t* p) {
 #pragma unroll
     for (int j = 0; j < NW; j++) { p[2 * j] = (uint32_t)a[j]; p[2 * j + 1] = (uint32_t)(a[j] >> 32); }
 }
 
 // one lane's share of a LIN round, in run_rounds' order: micro-ops 0 .. MN - 1, the flip, micro-ops MN .. K - 1
 // (K >= 1); a lane that is not live runs zero coefficients on zero operands and reads nothing
-__device__ __forceinline__ void lin_share(uint64_t (&acc)[NW], const uint32_t* in, uint32_t MN, uint32_t K, bool live) {
+CHECK_FN void lin_share(uint64_t (&acc)[NW], const uint32_t* in, uint32_t MN, uint32_t K, bool live) {
 #pragma unroll
     for (int j = 0; j < NW; j++) acc[j] = 0;
 #pragma unroll 1
@@ -87,8 +91,8 @@ __device__ __forceinline__ void lin_share(uint64_t (&acc)[NW], const uint32_t* i
 // in / out words per item and the op's body
 template <int OP> struct Do;
 #define CHECK_OP(OP, WIN, WOUT) \
-    template <> struct Do<OP> { static constexpr int win = WIN, wout = WOUT; static __device__ __forceinline__ void run(const uint32_t* in, uint32_t* out); }; \
-    __device__ __forceinline__ void Do<OP>::run(const uint32_t* in, uint32_t* out)
+    template <> struct Do<OP> { static constexpr int win = WIN, wout = WOUT; static CHECK_MEMBER void run(const uint32_t* in, uint32_t* out); }; \
+    CHECK_MEMBER void Do<OP>::run(const uint32_t* in, uint32_t* out)
 
 // ---- products ---------------------------------------------------------------------------------------------------
 CHECK_OP(FQ_MUL, 2 * NW, NW) { uint32_t a[NW], b[NW], r[NW]; ld12(a, in); ld12(b, in + NW); bls::fq_mul(r, a, b); st12(r, out); }
@@ -129,6 +133,7 @@ CHECK_OP(FQ_INV_VAR_UNI, UNI * NW, UNI * NW) {
     for (int t = 0; t < UNI; t++) { uint32_t a[NW], r[NW]; ld12(a, in + t * NW); bls::fq_inv_var(r, a); st12(r, out + t * NW); }
 }
 
+#if defined(__HIPCC__)
 template <int OP> __global__ void __launch_bounds__(256) k_check(const uint32_t* __restrict__ in, size_t n, uint32_t* __restrict__ out) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -157,45 +162,18 @@ template <> __global__ void __launch_bounds__(256) k_check<LIN_ABSORB>(const uin
     if (live) st12(r, out + i * NW);
 }
 
-constexpr size_t GUARD = 256;                              // bytes of 0xAA on either side of the output
-
 template <int OP> int run_op(const uint32_t* in, size_t words_in, size_t n, uint32_t* out, size_t words_out) {
     if (words_in != n * (size_t)Do<OP>::win || words_out != n * (size_t)Do<OP>::wout || n == 0 || n > (1u << 20)) return -2;
-    const size_t bin = words_in * 4, bout = words_out * 4;
     const unsigned threads = 256u;
-    char *din = nullptr, *dout = nullptr;
-    hipError_t e = hipMalloc((void**)&din, bin);
-    if (e == hipSuccess) e = hipMalloc((void**)&dout, bout + 2 * GUARD);
-    if (e == hipSuccess) e = hipMemcpy(din, in, bin, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(dout, 0xAA, bout + 2 * GUARD);
-    if (e == hipSuccess) {
-        k_check<OP><<<dim3((unsigned)((n + threads - 1) / threads)), dim3(threads)>>>((const uint32_t*)din, n, (uint32_t*)(dout + GUARD));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    std::vector<unsigned char> back(bout + 2 * GUARD);
-    if (e == hipSuccess) e = hipMemcpy(back.data(), dout, back.size(), hipMemcpyDeviceToHost);
-    if (din) (void)hipFree(din);
-    if (dout) (void)hipFree(dout);
-    if (e != hipSuccess) return (int)e;
-    for (size_t j = 0; j < GUARD; j++)
-        if (back[j] != 0xAA || back[GUARD + bout + j] != 0xAA) return -3;   // a lane stored outside its record
-    memcpy(out, back.data() + GUARD, bout);
-    return 0;
+    return check::guarded_run(in, words_in * 4, out, words_out * 4, 0, [=](const uint32_t* din, uint32_t* dout) {
+        k_check<OP><<<dim3((unsigned)((n + threads - 1) / threads)), dim3(threads)>>>(din, n, dout);
+    });
 }
+#endif
 }  // namespace
 
-// 0, a HIP error code, -1 unknown op, -2 sizes that do not match the op, -3 guard record written
-extern "C" __attribute__((visibility("default")))
-int blsgpu_fq32_check(int op, const uint32_t* in, size_t words_in, size_t n, uint32_t* out, size_t words_out) {
-    switch (op) {
-#define CASE(OP) case OP: return run_op<OP>(in, words_in, n, out, words_out);
-        CASE(FQ_MUL) CASE(FQ_MUL_RELAXED) CASE(FQ_SQR_RELAXED)
-        CASE(FQ_ADD_MOD) CASE(FQ_NEG_RAW) CASE(FQ_SUB_MOD) CASE(FQ_CANON) CASE(FQ_IS_ZERO)
-        CASE(FAT_MAC_PLAIN) CASE(FAT_FLIP) CASE(FAT_REDUCE) CASE(LIN) CASE(LIN_ABSORB)
-        CASE(FQ_SGN) CASE(GT_HALF_Q_MASK) CASE(FQ_JACOBI_VAR)
-        CASE(FQ_INV) CASE(FQ_INV_VAR) CASE(FQ_INV_UNI) CASE(FQ_INV_VAR_UNI)
-#undef CASE
-    }
-    return -1;
-}
+#if defined(__HIPCC__)
+CHECK_EXPORT(blsgpu_fq32_check, uint32_t, FQ32CHECK_OPS)
+#else
+CHECK_HOST_ENTRY(fq32check_host, FQ32CHECK_HOST_OPS)   // (tests/test_fq32_vectors_model.py)
+#endif

@@ -9,7 +9,7 @@
 // Not linked into libblsgpu.so, not declared in include/blsgpu.h, not an ABI.
 //
 // One kernel per op (a template on the op), 256 lanes per workgroup; spare lanes of the last workgroup store nothing.  The
-// host function puts a guard record of 0xAA bytes on either side of the device output and reports a written guard.
+// guard records and the return codes are check_runner.h's.
 // The op bodies (struct Do<OP>) also compile for the host: tests/test_fr_vectors_model.py includes this file with the host
 // compiler and runs the same bodies on the same records (the `window` group and the kernels are device only).
 //
@@ -71,10 +71,8 @@
 //   swin::recode          any 256-bit scalar (NOT reduced): digits in [-8, 8), the top digit (w = 64) is 0 or +1 -- s + C <
 //                         2^256 + 8 (16^65 - 1) / 15 < 2 * 16^64 so its nibble is 8 or 9 -- never negative
 //   swin::select_entry    ad 0 .. 8; keep0 = 0 (k_g2_smul) or the digit's mz (k_fix_mul_secret, k_poly_eval_secret)
+#include "check_runner.h"
 #if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#include <string.h>
-#include <vector>
 #define BLSGPU_TU 99                                       // no kernel group: declarations only
 #include "blsgpu_tu.h"
 #include "blsgpu_kernels.hip"                              // bswap32 for secret_window.h
@@ -83,49 +81,47 @@
 #include "blsgpu_msm.hip"                                  // sp2, the point arithmetic blsgpu_g2smul.hip names
 #include "blsgpu_g1fix.hip"                                // g1fix::ENTRY_DW, secret_window.h
 #include "blsgpu_g2smul.hip"                               // g2smul::PT_DW, g2smul::PAIRS
-#define FRC_FN __device__ __forceinline__
-#define FRC_MEMBER __device__ __forceinline__
-#else
-#define FRC_FN static inline
-#define FRC_MEMBER inline
 #endif
-#include <stdint.h>
 #include "fr_scalar.h"
 #include "sigdiv.h"
 #include "hash_pks.h"
 
 namespace frcheck {
 
-enum Op {
-    // reduce
-    SUB_N_IF_GE = 0, REDUCE_N, ADD_MOD_N, SUB_N_IF_GE_MASKED, REDUCE_N_MASKED, ADD_MOD_N_MASKED, BELOW_N, IS_ZERO, SUB, NEG, ADD, ADD_MASKED,
-    // products
-    MUL = 20, MUL_MASKED, SQR, TO_MONT, FROM_MONT, TO_MONT_MASKED, FROM_MONT_MASKED,
-    // inversions
-    INV = 30, INV_UNI, QUOTIENT_SCALAR,
-    // lagrange
-    LAGRANGE_POINT = 40, LAGRANGE_WEIGHT, LAGRANGE_DEN, DOT_TERM, DOT_TERM_MASKED, SUM_TERM_MASKED, POLY_COEFF_MASKED, POLY_POINT, POLY_HORNER_MASKED,
-    // sigdiv
-    SD_EXPONENT = 50, SD_CROSS_EQUAL, SD_ENTRY_BITS, SD_STATUS_OF, SD_NEG_COORD, SD_NEG_POINT,
-    // sha
-    SHA_COMPRESS = 60, HMAC_KEY, HMAC_KEY_WORDS, PAD_HMAC_BLOCK, CHILD_HMACS, PATH_STEP, FINGERPRINT, LONG_BLOCKS, LONG_WORD, HMAC_LONG,
-    HMAC_LONG_PAIR, HPK_DIGEST, HPK_EXPONENT,
-    // window (device only)
-    RECODE_G1 = 80, RECODE_G2, SEL, SELECT_G1, SELECT_G2,
-};
+// every op, once, with its code (tests/fr_vectors.py pins the codes): those that also build for the host, then the device-only ones
+#define FRCHECK_HOST_OPS(X) \
+    /* reduce */ \
+    X(SUB_N_IF_GE, 0) X(REDUCE_N, 1) X(ADD_MOD_N, 2) X(SUB_N_IF_GE_MASKED, 3) X(REDUCE_N_MASKED, 4) X(ADD_MOD_N_MASKED, 5) X(BELOW_N, 6) \
+    X(IS_ZERO, 7) X(SUB, 8) X(NEG, 9) X(ADD, 10) X(ADD_MASKED, 11) \
+    /* products */ \
+    X(MUL, 20) X(MUL_MASKED, 21) X(SQR, 22) X(TO_MONT, 23) X(FROM_MONT, 24) X(TO_MONT_MASKED, 25) X(FROM_MONT_MASKED, 26) \
+    /* inversions */ \
+    X(INV, 30) X(INV_UNI, 31) X(QUOTIENT_SCALAR, 32) \
+    /* lagrange */ \
+    X(LAGRANGE_POINT, 40) X(LAGRANGE_WEIGHT, 41) X(LAGRANGE_DEN, 42) X(DOT_TERM, 43) X(DOT_TERM_MASKED, 44) X(SUM_TERM_MASKED, 45) \
+    X(POLY_COEFF_MASKED, 46) X(POLY_POINT, 47) X(POLY_HORNER_MASKED, 48) \
+    /* sigdiv */ \
+    X(SD_EXPONENT, 50) X(SD_CROSS_EQUAL, 51) X(SD_ENTRY_BITS, 52) X(SD_STATUS_OF, 53) X(SD_NEG_COORD, 54) X(SD_NEG_POINT, 55) \
+    /* sha */ \
+    X(SHA_COMPRESS, 60) X(HMAC_KEY, 61) X(HMAC_KEY_WORDS, 62) X(PAD_HMAC_BLOCK, 63) X(CHILD_HMACS, 64) X(PATH_STEP, 65) X(FINGERPRINT, 66) \
+    X(LONG_BLOCKS, 67) X(LONG_WORD, 68) X(HMAC_LONG, 69) X(HMAC_LONG_PAIR, 70) X(HPK_DIGEST, 71) X(HPK_EXPONENT, 72)
+// window (device only)
+#define FRCHECK_DEVICE_OPS(X) X(RECODE_G1, 80) X(RECODE_G2, 81) X(SEL, 82) X(SELECT_G1, 83) X(SELECT_G2, 84)
+#define FRCHECK_OPS(X) FRCHECK_HOST_OPS(X) FRCHECK_DEVICE_OPS(X)
+CHECK_ENUM(FRCHECK_OPS)
 
 constexpr int W = 8, MAXK = 67, MAXT = 16, MSGW = 52, MAXKEYS = 9, DIGITS = 65;
 
-FRC_FN void ld(uint32_t* d, const uint32_t* p, int n = W) { for (int j = 0; j < n; j++) d[j] = p[j]; }
-FRC_FN void st(const uint32_t* x, uint32_t* p, int n = W) { for (int j = 0; j < n; j++) p[j] = x[j]; }
-FRC_FN const uint8_t* bytes(const uint32_t* p) { return (const uint8_t*)p; }
-FRC_FN void ldkey(hdk::HmacKey& k, const uint32_t* p) { ld(k.ipad, p); ld(k.opad, p + W); }
+CHECK_FN void ld(uint32_t* d, const uint32_t* p, int n = W) { for (int j = 0; j < n; j++) d[j] = p[j]; }
+CHECK_FN void st(const uint32_t* x, uint32_t* p, int n = W) { for (int j = 0; j < n; j++) p[j] = x[j]; }
+CHECK_FN const uint8_t* bytes(const uint32_t* p) { return (const uint8_t*)p; }
+CHECK_FN void ldkey(hdk::HmacKey& k, const uint32_t* p) { ld(k.ipad, p); ld(k.opad, p + W); }
 
 // in / out words per item and the op's body
 template <int OP> struct Do;
 #define CHECK_OP(OP, WIN, WOUT) \
-    template <> struct Do<OP> { static constexpr int win = WIN, wout = WOUT; static FRC_MEMBER void run(const uint32_t* in, uint32_t* out); }; \
-    FRC_MEMBER void Do<OP>::run(const uint32_t* in, uint32_t* out)
+    template <> struct Do<OP> { static constexpr int win = WIN, wout = WOUT; static CHECK_MEMBER void run(const uint32_t* in, uint32_t* out); }; \
+    CHECK_MEMBER void Do<OP>::run(const uint32_t* in, uint32_t* out)
 #define OP1(OP, CALL) CHECK_OP(OP, W, W) { uint32_t s[W]; ld(s, in); CALL; st(s, out); }
 #define OP2(OP, CALL) CHECK_OP(OP, 2 * W, W) { uint32_t a[W], b[W], r[W]; ld(a, in); ld(b, in + W); CALL; st(r, out); }
 
@@ -193,7 +189,7 @@ CHECK_OP(PATH_STEP, 2 + W + 12, 2 * W) { uint32_t chain[W], ser[12], il[W], ir[W
 CHECK_OP(FINGERPRINT, 12, 1) { uint32_t ser[12]; ld(ser, in, 12); out[0] = hdk::fingerprint(ser); }
 CHECK_OP(LONG_BLOCKS, 2, 1) { out[0] = hdk::long_blocks(in[0], (int)in[1]); }
 // a record's message: `shift` bytes into its MSGW words, len bytes long at the most that fit
-FRC_FN uint32_t fit(uint32_t len, uint32_t shift) { const uint32_t room = 4u * MSGW - (shift & 3u); return len < room ? len : room; }
+CHECK_FN uint32_t fit(uint32_t len, uint32_t shift) { const uint32_t room = 4u * MSGW - (shift & 3u); return len < room ? len : room; }
 CHECK_OP(LONG_WORD, 5 + MSGW, 1) { const uint32_t len = fit(in[0], in[4]);
     out[0] = hdk::long_word(bytes(in + 5) + (in[4] & 3u), len, len + (in[1] ? 1u : 0u), in[2] & 0xffu, in[3]); }
 CHECK_OP(HMAC_LONG, 3 + 2 * W + MSGW, W) { hdk::HmacKey k; ldkey(k, in + 3); uint32_t d[W];
@@ -255,74 +251,20 @@ template <> __global__ void __launch_bounds__(256) k_check<SELECT_G2>(const uint
     st(q, out + i * PT_DW, (int)PT_DW);
 }
 
-constexpr size_t GUARD = 256;                              // bytes of 0xAA on either side of the output
-
 template <int OP> int run_op(const uint32_t* in, size_t words_in, size_t n, uint32_t* out, size_t words_out) {
     if (words_in != n * (size_t)Do<OP>::win || words_out != n * (size_t)Do<OP>::wout || n == 0 || n > (1u << 20)) return -2;
-    const size_t bin = words_in * 4, bout = words_out * 4;
     const unsigned threads = 256u;
     const size_t lanes = OP == RECODE_G2 ? 2 * n : n;
-    char *din = nullptr, *dout = nullptr;
-    hipError_t e = hipMalloc((void**)&din, bin);
-    if (e == hipSuccess) e = hipMalloc((void**)&dout, bout + 2 * GUARD);
-    if (e == hipSuccess) e = hipMemcpy(din, in, bin, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(dout, 0xAA, bout + 2 * GUARD);
-    if (e == hipSuccess) {
-        k_check<OP><<<dim3((unsigned)((lanes + threads - 1) / threads)), dim3(threads)>>>((const uint32_t*)din, n, (uint32_t*)(dout + GUARD));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    std::vector<unsigned char> back(bout + 2 * GUARD);
-    if (e == hipSuccess) e = hipMemcpy(back.data(), dout, back.size(), hipMemcpyDeviceToHost);
-    if (din) (void)hipFree(din);
-    if (dout) (void)hipFree(dout);
-    if (e != hipSuccess) return (int)e;
-    for (size_t j = 0; j < GUARD; j++)
-        if (back[j] != 0xAA || back[GUARD + bout + j] != 0xAA) return -3;   // a lane stored outside its record
-    memcpy(out, back.data() + GUARD, bout);
-    return 0;
+    return check::guarded_run(in, words_in * 4, out, words_out * 4, 0, [=](const uint32_t* din, uint32_t* dout) {
+        k_check<OP><<<dim3((unsigned)((lanes + threads - 1) / threads)), dim3(threads)>>>(din, n, dout);
+    });
 }
 #endif
 }  // namespace frcheck
 
+using namespace frcheck;
 #if defined(__HIPCC__)
-// 0, a HIP error code, -1 unknown op, -2 sizes that do not match the op, -3 guard record written
-extern "C" __attribute__((visibility("default")))
-int blsgpu_fr_check(int op, const uint32_t* in, size_t words_in, size_t n, uint32_t* out, size_t words_out) {
-    using namespace frcheck;
-    switch (op) {
-#define CASE(OP) case OP: return run_op<OP>(in, words_in, n, out, words_out);
-        CASE(SUB_N_IF_GE) CASE(REDUCE_N) CASE(ADD_MOD_N) CASE(SUB_N_IF_GE_MASKED) CASE(REDUCE_N_MASKED) CASE(ADD_MOD_N_MASKED)
-        CASE(BELOW_N) CASE(IS_ZERO) CASE(SUB) CASE(NEG) CASE(ADD) CASE(ADD_MASKED)
-        CASE(MUL) CASE(MUL_MASKED) CASE(SQR) CASE(TO_MONT) CASE(FROM_MONT) CASE(TO_MONT_MASKED) CASE(FROM_MONT_MASKED)
-        CASE(INV) CASE(INV_UNI) CASE(QUOTIENT_SCALAR)
-        CASE(LAGRANGE_POINT) CASE(LAGRANGE_WEIGHT) CASE(LAGRANGE_DEN) CASE(DOT_TERM) CASE(DOT_TERM_MASKED) CASE(SUM_TERM_MASKED)
-        CASE(POLY_COEFF_MASKED) CASE(POLY_POINT) CASE(POLY_HORNER_MASKED)
-        CASE(SD_EXPONENT) CASE(SD_CROSS_EQUAL) CASE(SD_ENTRY_BITS) CASE(SD_STATUS_OF) CASE(SD_NEG_COORD) CASE(SD_NEG_POINT)
-        CASE(SHA_COMPRESS) CASE(HMAC_KEY) CASE(HMAC_KEY_WORDS) CASE(PAD_HMAC_BLOCK) CASE(CHILD_HMACS) CASE(PATH_STEP) CASE(FINGERPRINT)
-        CASE(LONG_BLOCKS) CASE(LONG_WORD) CASE(HMAC_LONG) CASE(HMAC_LONG_PAIR) CASE(HPK_DIGEST) CASE(HPK_EXPONENT)
-        CASE(RECODE_G1) CASE(RECODE_G2) CASE(SEL) CASE(SELECT_G1) CASE(SELECT_G2)
-#undef CASE
-    }
-    return -1;
-}
+CHECK_EXPORT(blsgpu_fr_check, uint32_t, FRCHECK_OPS)
 #else
-// the host build's entry (tests/test_fr_vectors_model.py): one item of a lane-layout op; false for an op it does not have
-static inline bool frcheck_host(int op, const uint32_t* in, uint32_t* out) {
-    using namespace frcheck;
-    switch (op) {
-#define CASE(OP) case OP: Do<OP>::run(in, out); return true;
-        CASE(SUB_N_IF_GE) CASE(REDUCE_N) CASE(ADD_MOD_N) CASE(SUB_N_IF_GE_MASKED) CASE(REDUCE_N_MASKED) CASE(ADD_MOD_N_MASKED)
-        CASE(BELOW_N) CASE(IS_ZERO) CASE(SUB) CASE(NEG) CASE(ADD) CASE(ADD_MASKED)
-        CASE(MUL) CASE(MUL_MASKED) CASE(SQR) CASE(TO_MONT) CASE(FROM_MONT) CASE(TO_MONT_MASKED) CASE(FROM_MONT_MASKED)
-        CASE(INV) CASE(INV_UNI) CASE(QUOTIENT_SCALAR)
-        CASE(LAGRANGE_POINT) CASE(LAGRANGE_WEIGHT) CASE(LAGRANGE_DEN) CASE(DOT_TERM) CASE(DOT_TERM_MASKED) CASE(SUM_TERM_MASKED)
-        CASE(POLY_COEFF_MASKED) CASE(POLY_POINT) CASE(POLY_HORNER_MASKED)
-        CASE(SD_EXPONENT) CASE(SD_CROSS_EQUAL) CASE(SD_ENTRY_BITS) CASE(SD_STATUS_OF) CASE(SD_NEG_COORD) CASE(SD_NEG_POINT)
-        CASE(SHA_COMPRESS) CASE(HMAC_KEY) CASE(HMAC_KEY_WORDS) CASE(PAD_HMAC_BLOCK) CASE(CHILD_HMACS) CASE(PATH_STEP) CASE(FINGERPRINT)
-        CASE(LONG_BLOCKS) CASE(LONG_WORD) CASE(HMAC_LONG) CASE(HMAC_LONG_PAIR) CASE(HPK_DIGEST) CASE(HPK_EXPONENT)
-#undef CASE
-    }
-    return false;
-}
+CHECK_HOST_ENTRY(frcheck_host, FRCHECK_HOST_OPS)        // (tests/test_fr_vectors_model.py)
 #endif

@@ -9,7 +9,8 @@
 // Pair and quad kernels have the launch bounds of k_ml_lines2 and its slab of constants in dynamic LDS, laid out as
 // lines_chain lays it out; team kernels have the launch bounds of k_ml_accum.  Spare lanes (past the last item) and the idle
 // lanes 60 .. 63 of a team wavefront repeat the last item, run every DPP / ds_bpermute read with the others and store nothing.
-// The host function puts a guard record of 0xAA bytes on either side of the device output and reports a written guard.
+// The host function refuses a position outside 0 .. 5 before anything is launched (-4); the guard records and the return codes are
+// check_runner.h's.
 //
 // Lane-pair ops: an item is one lane pair, a value 2 x 14 words (the even lane's part, then the odd lane's), 128 items per
 // 256-thread workgroup.  Each op at the ranges of its call sites in blsgpu_ml.hip:
@@ -42,10 +43,7 @@
 //   TEAM_SQUARE         f -> mul_dense with TeamRec on its own value (k_ml_small)
 //   TEAM_TEAMREC        f, g per lane -> mul_dense with TeamRec on another value (k_fexp_team)
 //   (publish<false> and LdsRec have no production instantiation; LdsRec's body is GlobalRec's.)
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <string.h>
-#include <vector>
+#include "check_runner.h"
 #define BLSGPU_TU 99                                       // no kernel group: declarations only
 #include "blsgpu_tu.h"
 #include "blsgpu_kernels.hip"
@@ -58,13 +56,16 @@ using r28::NL;
 namespace sp = ml::sp;
 namespace sq = ml::sq;
 
-enum Op {
-    MUL_XI = 0, B3, MUL_31, MUL_11, DOT2_1111, SQR_H, SQR_HN2, SQR_M12SQR, MULF_1, MULF_3, NORM_2, NORM_4,
-    MULC_NORM_4_S3, MULC_NORM_3_S2, MULC_NORM_12_S2, MULC_NORM_N12_S2, IS_ZERO2, LOAD_STORE, SP_TANGENT, SP_CHORD,
-    OTH = 30, PICK, SQ_TANGENT,
-    SET_ONE = 40, PUBLISH_RAW, PUBLISH_NORM, FETCH_0, FETCH_1, FETCH_2, FETCH_3, FETCH_4, FETCH_5, FETCH2_RT,
-    MUL3_012, MUL3_345, MUL3_012_RAW, TEAM_LINE, TEAM_DENSE, TEAM_SQUARE, TEAM_TEAMREC,
-};
+// every op, once, with its code (tests/ml_vectors.py pins the codes)
+#define MLCHECK_OPS(X) \
+    X(MUL_XI, 0) X(B3, 1) X(MUL_31, 2) X(MUL_11, 3) X(DOT2_1111, 4) X(SQR_H, 5) X(SQR_HN2, 6) X(SQR_M12SQR, 7) X(MULF_1, 8) X(MULF_3, 9) \
+    X(NORM_2, 10) X(NORM_4, 11) X(MULC_NORM_4_S3, 12) X(MULC_NORM_3_S2, 13) X(MULC_NORM_12_S2, 14) X(MULC_NORM_N12_S2, 15) X(IS_ZERO2, 16) \
+    X(LOAD_STORE, 17) X(SP_TANGENT, 18) X(SP_CHORD, 19) \
+    X(OTH, 30) X(PICK, 31) X(SQ_TANGENT, 32) \
+    X(SET_ONE, 40) X(PUBLISH_RAW, 41) X(PUBLISH_NORM, 42) X(FETCH_0, 43) X(FETCH_1, 44) X(FETCH_2, 45) X(FETCH_3, 46) X(FETCH_4, 47) \
+    X(FETCH_5, 48) X(FETCH2_RT, 49) X(MUL3_012, 50) X(MUL3_345, 51) X(MUL3_012_RAW, 52) X(TEAM_LINE, 53) X(TEAM_DENSE, 54) \
+    X(TEAM_SQUARE, 55) X(TEAM_TEAMREC, 56)
+CHECK_ENUM(MLCHECK_OPS)
 constexpr int V2 = 2 * NL, REC = ml::LINE_DW, TV = 6 * V2, STEP_IN = 3 * V2 + 2 * NL + 2 * V2, STEP_OUT = 3 * V2 + REC;
 
 // words per item in and out, lanes per item
@@ -252,7 +253,6 @@ template <int OP> bool positions_ok(const int32_t* in, size_t n) {
     return true;
 }
 
-constexpr size_t GUARD = 256;                              // bytes of 0xAA on either side of the output
 constexpr size_t DUMP = REC * 4;                           // behind the second guard: where spare lanes of the step ops put their line record
 
 template <int OP> void launch(const int32_t* din, uint32_t n, int32_t* dout, int32_t* dump) {
@@ -268,41 +268,10 @@ template <int OP> void launch(const int32_t* din, uint32_t n, int32_t* dout, int
 template <int OP> int run_op(const int32_t* in, size_t words_in, size_t n, int32_t* out, size_t words_out) {
     if (n == 0 || n > (1u << 16) || words_in != n * (size_t)Shape<OP>::win || words_out != n * (size_t)Shape<OP>::wout) return -2;
     if (!positions_ok<OP>(in, n)) return -4;
-    const size_t bin = words_in * 4, bout = words_out * 4;
-    char *din = nullptr, *dout = nullptr;
-    hipError_t e = hipMalloc((void**)&din, bin);
-    if (e == hipSuccess) e = hipMalloc((void**)&dout, bout + 2 * GUARD + DUMP);
-    if (e == hipSuccess) e = hipMemcpy(din, in, bin, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(dout, 0xAA, bout + 2 * GUARD + DUMP);
-    if (e == hipSuccess) {
-        launch<OP>((const int32_t*)din, (uint32_t)n, (int32_t*)(dout + GUARD), (int32_t*)(dout + GUARD + bout + GUARD));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    std::vector<unsigned char> back(bout + 2 * GUARD);
-    if (e == hipSuccess) e = hipMemcpy(back.data(), dout, back.size(), hipMemcpyDeviceToHost);
-    if (din) (void)hipFree(din);
-    if (dout) (void)hipFree(dout);
-    if (e != hipSuccess) return (int)e;
-    for (size_t j = 0; j < GUARD; j++)
-        if (back[j] != 0xAA || back[GUARD + bout + j] != 0xAA) return -3;   // a lane stored outside its record
-    memcpy(out, back.data() + GUARD, bout);
-    return 0;
+    return check::guarded_run(in, words_in * 4, out, words_out * 4, DUMP, [=](const int32_t* din, int32_t* dout) {
+        launch<OP>(din, (uint32_t)n, dout, dout + words_out + check::GUARD / 4);
+    });
 }
 }  // namespace
 
-// 0, a HIP error code, -1 unknown op, -2 sizes that do not match the op, -3 guard record written, -4 a position outside 0 .. 5
-// (nothing is launched)
-extern "C" __attribute__((visibility("default")))
-int blsgpu_ml_check(int op, const int32_t* in, size_t words_in, size_t n, int32_t* out, size_t words_out) {
-    switch (op) {
-#define CASE(OP) case OP: return run_op<OP>(in, words_in, n, out, words_out);
-        CASE(MUL_XI) CASE(B3) CASE(MUL_31) CASE(MUL_11) CASE(DOT2_1111) CASE(SQR_H) CASE(SQR_HN2) CASE(SQR_M12SQR) CASE(MULF_1) CASE(MULF_3)
-        CASE(NORM_2) CASE(NORM_4) CASE(MULC_NORM_4_S3) CASE(MULC_NORM_3_S2) CASE(MULC_NORM_12_S2) CASE(MULC_NORM_N12_S2) CASE(IS_ZERO2)
-        CASE(LOAD_STORE) CASE(SP_TANGENT) CASE(SP_CHORD) CASE(OTH) CASE(PICK) CASE(SQ_TANGENT)
-        CASE(SET_ONE) CASE(PUBLISH_RAW) CASE(PUBLISH_NORM) CASE(FETCH_0) CASE(FETCH_1) CASE(FETCH_2) CASE(FETCH_3) CASE(FETCH_4) CASE(FETCH_5)
-        CASE(FETCH2_RT) CASE(MUL3_012) CASE(MUL3_345) CASE(MUL3_012_RAW) CASE(TEAM_LINE) CASE(TEAM_DENSE) CASE(TEAM_SQUARE) CASE(TEAM_TEAMREC)
-#undef CASE
-    }
-    return -1;
-}
+CHECK_EXPORT(blsgpu_ml_check, int32_t, MLCHECK_OPS)

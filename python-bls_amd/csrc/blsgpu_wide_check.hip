@@ -6,8 +6,7 @@
 // The routines are the production ones: this file includes the kernel texts the way blsgpu_api.hip does, with a BLSGPU_TU value
 // no kernel group has, so no production kernel body is emitted (blsgpu_tu.h).  One kernel per op (a template on the op): each
 // step shape is compiled the way the production kernels compile it.  The host function checks every address of every record
-// against the value file before anything is launched, puts a guard record of 0xAA bytes on either side of the device output and
-// reports a written guard.
+// against the value file before anything is launched (-4); the guard records and the return codes are check_runner.h's.
 //
 //   per lane (256 threads per workgroup, one item per lane):
 //     SRN             t[14], s                      -> mlw::srn
@@ -26,10 +25,7 @@
 //     FXW_STEP_VV     V, P1 as 4 x 64 words         -> V          FXW_STEP_VG   V, G, P3 as 9 x 64 words -> V, G
 //     FXW_VV_CSQ / FXW_VV_CONJ / FXW_VG_MUL / FXW_VG_FROB / FXW_VG_FROBC: the same through load_p1 / load_p3 on the real tables
 //     FXW_TINV        V -> V
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <string.h>
-#include <vector>
+#include "check_runner.h"
 #define BLSGPU_TU 99                                       // no kernel group: declarations only
 #include "blsgpu_tu.h"
 #include "blsgpu_kernels.hip"
@@ -46,15 +42,18 @@ namespace {
 using namespace blsgpu;
 using r28::NL;
 
-enum Op {
-    SRN = 0, FXW_SCALE_NORM, STORED_ZERO,
-    WSTEP_2 = 10, WSTEP_2BS, WSTEP_1, WSTEP_1OCT, WSTEP_2_X4, WSTEP_1_X4, WLOAD,
-    LSTEP_2 = 20, LSTEP_3, LSTEP_4, LSTEP_4_HAS2, LSTEP_2_HAS2, LSTEP_3_HAS2,
-    // the same steps with the record fetched by mlw::load_rec / lsw::load_rec<K> from the real tables: an item names a KIND
-    TREC_MLW_2 = 40, TREC_MLW_2BS, TREC_MLW_1, TREC_MLW_1OCT, TREC_H2CW_2, TREC_H2CW_2BS, TREC_H2CW_1, TREC_G1W_1,
-    LREC_2 = 50, LREC_3, LREC_4, LREC_4_HAS2, LREC_2_HAS2, LREC_3_HAS2,
-    FXW_STEP_VV = 30, FXW_STEP_VG, FXW_VV_CSQ, FXW_VV_CONJ, FXW_VG_MUL, FXW_VG_FROB, FXW_VG_FROBC, FXW_TINV,
-};
+// every op, once, with its code (tests/wide_vectors.py pins the codes)
+#define WIDECHECK_OPS(X) \
+    X(SRN, 0) X(FXW_SCALE_NORM, 1) X(STORED_ZERO, 2) \
+    X(WSTEP_2, 10) X(WSTEP_2BS, 11) X(WSTEP_1, 12) X(WSTEP_1OCT, 13) X(WSTEP_2_X4, 14) X(WSTEP_1_X4, 15) X(WLOAD, 16) \
+    X(LSTEP_2, 20) X(LSTEP_3, 21) X(LSTEP_4, 22) X(LSTEP_4_HAS2, 23) X(LSTEP_2_HAS2, 24) X(LSTEP_3_HAS2, 25) \
+    /* the same steps with the record fetched by mlw::load_rec / lsw::load_rec<K> from the real tables: an item names a KIND */ \
+    X(TREC_MLW_2, 40) X(TREC_MLW_2BS, 41) X(TREC_MLW_1, 42) X(TREC_MLW_1OCT, 43) X(TREC_H2CW_2, 44) X(TREC_H2CW_2BS, 45) X(TREC_H2CW_1, 46) \
+    X(TREC_G1W_1, 47) \
+    X(LREC_2, 50) X(LREC_3, 51) X(LREC_4, 52) X(LREC_4_HAS2, 53) X(LREC_2_HAS2, 54) X(LREC_3_HAS2, 55) \
+    X(FXW_STEP_VV, 30) X(FXW_STEP_VG, 31) X(FXW_VV_CSQ, 32) X(FXW_VV_CONJ, 33) X(FXW_VG_MUL, 34) X(FXW_VG_FROB, 35) X(FXW_VG_FROBC, 36) \
+    X(FXW_TINV, 37)
+CHECK_ENUM(WIDECHECK_OPS)
 constexpr int MVF = mlw::VF_DW, LVF = lsw::VF_DW, LINES_OUT = 4 * ml::LINE_DW, REGS = 64 * NL;
 
 // words per item in and out, threads per workgroup, items per workgroup
@@ -289,8 +288,6 @@ template <int OP> bool records_ok(const int32_t* in, size_t n) {
     return true;
 }
 
-constexpr size_t GUARD = 256;                              // bytes of 0xAA on either side of the output
-
 template <int OP> void launch(const int32_t* din, size_t n, int32_t* dout) {
     const unsigned per = (unsigned)Shape<OP>::per, blocks = (unsigned)((n + per - 1) / per);
     if constexpr (OP <= STORED_ZERO) k_lane<OP><<<dim3(blocks), dim3((unsigned)Shape<OP>::threads)>>>(din, n, dout);
@@ -302,43 +299,8 @@ template <int OP> void launch(const int32_t* din, size_t n, int32_t* dout) {
 template <int OP> int run_op(const int32_t* in, size_t words_in, size_t n, int32_t* out, size_t words_out) {
     if (n == 0 || n > (1u << 16) || words_in != n * (size_t)Shape<OP>::win || words_out != n * (size_t)Shape<OP>::wout) return -2;
     if (!records_ok<OP>(in, n)) return -4;
-    const size_t bin = words_in * 4, bout = words_out * 4;
-    char *din = nullptr, *dout = nullptr;
-    hipError_t e = hipMalloc((void**)&din, bin);
-    if (e == hipSuccess) e = hipMalloc((void**)&dout, bout + 2 * GUARD);
-    if (e == hipSuccess) e = hipMemcpy(din, in, bin, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(dout, 0xAA, bout + 2 * GUARD);
-    if (e == hipSuccess) {
-        launch<OP>((const int32_t*)din, n, (int32_t*)(dout + GUARD));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    std::vector<unsigned char> back(bout + 2 * GUARD);
-    if (e == hipSuccess) e = hipMemcpy(back.data(), dout, back.size(), hipMemcpyDeviceToHost);
-    if (din) (void)hipFree(din);
-    if (dout) (void)hipFree(dout);
-    if (e != hipSuccess) return (int)e;
-    for (size_t j = 0; j < GUARD; j++)
-        if (back[j] != 0xAA || back[GUARD + bout + j] != 0xAA) return -3;   // a lane stored outside its record
-    memcpy(out, back.data() + GUARD, bout);
-    return 0;
+    return check::guarded_run(in, words_in * 4, out, words_out * 4, 0, [=](const int32_t* din, int32_t* dout) { launch<OP>(din, n, dout); });
 }
 }  // namespace
 
-// 0, a HIP error code, -1 unknown op, -2 sizes that do not match the op, -3 guard record written, -4 a record names an address
-// outside the value file (nothing is launched)
-extern "C" __attribute__((visibility("default")))
-int blsgpu_wide_check(int op, const int32_t* in, size_t words_in, size_t n, int32_t* out, size_t words_out) {
-    switch (op) {
-#define CASE(OP) case OP: return run_op<OP>(in, words_in, n, out, words_out);
-        CASE(SRN) CASE(FXW_SCALE_NORM) CASE(STORED_ZERO)
-        CASE(WSTEP_2) CASE(WSTEP_2BS) CASE(WSTEP_1) CASE(WSTEP_1OCT) CASE(WSTEP_2_X4) CASE(WSTEP_1_X4) CASE(WLOAD)
-        CASE(LSTEP_2) CASE(LSTEP_3) CASE(LSTEP_4) CASE(LSTEP_4_HAS2) CASE(LSTEP_2_HAS2) CASE(LSTEP_3_HAS2)
-        CASE(FXW_STEP_VV) CASE(FXW_STEP_VG) CASE(FXW_VV_CSQ) CASE(FXW_VV_CONJ) CASE(FXW_VG_MUL) CASE(FXW_VG_FROB) CASE(FXW_VG_FROBC)
-        CASE(FXW_TINV)
-        CASE(TREC_MLW_2) CASE(TREC_MLW_2BS) CASE(TREC_MLW_1) CASE(TREC_MLW_1OCT) CASE(TREC_H2CW_2) CASE(TREC_H2CW_2BS) CASE(TREC_H2CW_1) CASE(TREC_G1W_1)
-        CASE(LREC_2) CASE(LREC_3) CASE(LREC_4) CASE(LREC_4_HAS2) CASE(LREC_2_HAS2) CASE(LREC_3_HAS2)
-#undef CASE
-    }
-    return -1;
-}
+CHECK_EXPORT(blsgpu_wide_check, int32_t, WIDECHECK_OPS)

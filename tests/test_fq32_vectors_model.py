@@ -1,6 +1,6 @@
 """CPU: the operand sets of tests/fq32_vectors.py (a) through the HOST build of csrc/fq32.h (g++, as
-tests/test_abi_and_host.py compiles it) against the same Python-integer references the GPU test uses -- the first direct
-test of fat_flip / fat_mac_plain / fat_reduce, fq_sgn, fq_mul_relaxed, fq_canon and fq_sub_mod, and the proof of the
+tests/test_abi_and_host.py compiles it; the op bodies are csrc/blsgpu_fq32_check.hip's own, included by the driver)
+against the same Python-integer references the GPU test uses -- the first direct test of fat_flip / fat_mac_plain / fat_reduce, fq_sgn, fq_mul_relaxed, fq_canon and fq_sub_mod, and the proof of the
 references before a GPU sees them; (b) inside the preconditions each set claims; (c) a range audit of every LIN round
 that vmgen packs into vm_tables.h, against the bounds fat_flip and fat_reduce state (no other test asserts them:
 vmgen/tablesim.py checks 0 <= V < 2^396 on residues below q only).  Needs no GPU."""
@@ -16,54 +16,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "python-bls_amd", "csrc")
 Q, M32 = V.Q, V.M32
 
-# the host side of csrc/blsgpu_fq32_check.hip: the same op numbers and item layouts, fq32.h's host code
+# the op bodies of csrc/blsgpu_fq32_check.hip themselves, compiled for the host on fq32.h's host code
 HOST_DRIVER = r'''
-#include "fq32.h"
+#include "blsgpu_fq32_check.hip"
 #include <stdio.h>
 #include <vector>
-static void ldfat(uint64_t* a, const uint32_t* p) { for (int j = 0; j < 12; j++) a[j] = (uint64_t)p[2 * j] | ((uint64_t)p[2 * j + 1] << 32); }
-static void stfat(const uint64_t* a, uint32_t* p) { for (int j = 0; j < 12; j++) { p[2 * j] = (uint32_t)a[j]; p[2 * j + 1] = (uint32_t)(a[j] >> 32); } }
-static void cp(uint32_t* d, const uint32_t* s) { for (int j = 0; j < 12; j++) d[j] = s[j]; }
-static void run(int op, const uint32_t* in, uint32_t* out) {
-    uint32_t a[12], b[12]; uint64_t acc[12];
-    switch (op) {
-    case 0: bls::fq_mul(out, in, in + 12); break;
-    case 1: bls::fq_mul_relaxed(out, in, in + 12); break;
-    case 2: bls::fq_sqr_relaxed(out, in); break;
-    case 10: cp(a, in); cp(b, in + 12); bls::fq_add_mod(a, b); cp(out, a); break;
-    case 11: cp(a, in); bls::fq_neg_raw(a); cp(out, a); break;
-    case 12: cp(a, in); bls::fq_sub_mod(a, in + 12); cp(out, a); break;
-    case 13: cp(a, in); bls::fq_canon(a); cp(out, a); break;
-    case 14: out[0] = bls::fq_is_zero(in) ? 1u : 0u; break;
-    case 20: ldfat(acc, in); bls::fat_mac_plain(acc, in + 24, in[36]); stfat(acc, out); break;
-    case 21: ldfat(acc, in); bls::fat_flip(acc); stfat(acc, out); break;
-    case 22: ldfat(acc, in); bls::fat_reduce(out, acc); break;
-    case 23: {                                            // a LIN share in run_rounds' order
-        const uint32_t MN = in[0], K = in[1];
-        for (int j = 0; j < 12; j++) acc[j] = 0;
-        for (uint32_t p = 0; p < K; p++) {
-            if (p > 0 && p == MN) bls::fat_flip(acc);
-            bls::fat_mac_plain(acc, in + 34 + 12 * p, in[4 + p] & 31u);
-        }
-        if (MN == K) bls::fat_flip(acc);
-        bls::fat_reduce(out, acc);
-        break; }
-    case 30: bls::fq_sgn(out, in); break;
-    case 31: out[0] = bls::gt_half_q_mask(in); break;
-    case 32: out[0] = (uint32_t)bls::fq_jacobi_var(in); break;
-    case 40: bls::fq_inv(out, in); break;
-    case 41: bls::fq_inv_var(out, in); break;
-    case 42: for (int t = 0; t < 8; t++) bls::fq_inv(out + 12 * t, in + 12 * t); break;
-    case 43: for (int t = 0; t < 8; t++) bls::fq_inv_var(out + 12 * t, in + 12 * t); break;
-    }
-}
 int main() {
     int op, win, wout, n;
     while (scanf("%d %d %d %d", &op, &win, &wout, &n) == 4) {
         std::vector<uint32_t> in(win), out(wout);
         for (int i = 0; i < n; i++) {
             for (int j = 0; j < win; j++) if (scanf("%x", &in[j]) != 1) return 1;
-            run(op, in.data(), out.data());
+            for (int j = 0; j < wout; j++) out[j] = 0xAAAAAAAAu;
+            if (!fq32check_host(op, in.data(), out.data())) return 2;
             for (int j = 0; j < wout; j++) printf("%08x ", out[j]);
             printf("\n");
         }

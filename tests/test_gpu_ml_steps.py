@@ -5,27 +5,18 @@ tests/ml_vectors.py's; tests/test_ml_vectors_model.py checks them on the CPU.  L
 items, quad ops with 1, 15, 16, 17 and 65, team ops with 1, 9, 10, 11 and 41 (either side of a wavefront and of a workgroup), and
 further calls of the largest count until every set has run; item i is the same set in every call.  No tolerances: every output
 word is compared exactly."""
-import ctypes
-import os
-
 import numpy as np
 import pytest
 
+import checklib
 import ml_vectors as V
 
 pytestmark = pytest.mark.gpu
 
-LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "python-bls_amd", "csrc", "libblsgpu_mlcheck.so")
-
 
 @pytest.fixture(scope="module")
 def check_lib():
-    import torch  # noqa: F401  (first, as bls_py._native.load_library: both bind to one HIP runtime)
-    assert os.path.exists(LIB), "libblsgpu_mlcheck.so is not built: run __graft_entry__.build() (make -C python-bls_amd/csrc)"
-    lib = ctypes.CDLL(LIB)
-    lib.blsgpu_ml_check.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
-    lib.blsgpu_ml_check.restype = ctypes.c_int
-    return lib
+    return checklib.load("libblsgpu_mlcheck", "blsgpu_ml_check")
 
 
 @pytest.fixture(scope="module")
@@ -33,35 +24,8 @@ def ops():
     return V.ops()
 
 
-def _call(lib, op, sets):
-    n = len(sets)
-    cin = np.array([w for k in sets for w in op.sets[k][1]], dtype=np.int32)
-    cout = np.zeros(n * op.wout, dtype=np.int32)
-    rc = lib.blsgpu_ml_check(op.code, cin.ctypes.data, cin.size, n, cout.ctypes.data, cout.size)
-    assert rc == 0, "%s, %d items: blsgpu_ml_check returned %d (-3: a guard record was written; > 0: HIP error)" % (op.name, n, rc)
-    got = cout.reshape(n, op.wout)
-    for i, k in enumerate(sets):
-        tag, _, want, _ = op.sets[k]
-        if (got[i] == np.array(want, dtype=np.int32)).all():
-            continue
-        g = got[i].tolist()
-        bad = [(j, g[j], w) for j, w in enumerate(want) if g[j] != w]
-        assert not bad, "%s, %d items, item %d, set %s: %d words differ, first (word, got, want) %s" % (op.name, n, i, tag, len(bad), bad[:4])
-
-
 def _run(lib, op):
-    counts = op.counts
-    seen = set()
-    for n in counts:
-        sets = V.call_sets(op, n)
-        _call(lib, op, sets)
-        seen |= set(sets)
-    base = counts[-1]
-    while len(seen) < len(op.sets):                # the sets a call of the largest count has not reached yet
-        sets = V.call_sets(op, counts[-1], base)
-        _call(lib, op, sets)
-        seen |= set(sets)
-        base += counts[-1]
+    checklib.run_sets(lib, V, op, op.counts)
 
 
 def test_lane_pair_linear_and_carry_ops(check_lib, ops):
@@ -118,7 +82,7 @@ def test_bad_arguments_are_refused(check_lib, ops):
     op = ops["TEAM_LINE"]
     words = np.array(op.sets[0][1], dtype=np.int32)
     out = np.zeros(op.wout, dtype=np.int32)
-    call = lambda code, w, n, o: check_lib.blsgpu_ml_check(code, w.ctypes.data, w.size, n, o.ctypes.data, o.size)
+    call = lambda code, w, n, o: check_lib(code, w.ctypes.data, w.size, n, o.ctypes.data, o.size)
     assert call(op.code, words[:-1], 1, out) == -2
     assert call(op.code, words, 1, out[:-1]) == -2
     assert call(25, words, 1, out) == -1

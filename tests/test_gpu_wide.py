@@ -4,27 +4,18 @@ csrc/blsgpu_wide_check.hip (libblsgpu_widecheck.so: one kernel per op).  Operand
 tests/wide_vectors.py's; tests/test_wide_vectors_model.py checks them on the CPU.  Per lane ops run with 1, 63, 64, 65 and 257
 items, per wavefront ops with 1, 3, 4, 5 and 65 wavefronts (and further calls of 65 until every set has run); every output word
 is compared exactly -- the stored results, the unchanged rest of the value file and the guards -- except the write sink's."""
-import ctypes
-import os
-
 import numpy as np
 import pytest
 
+import checklib
 import wide_vectors as V
 
 pytestmark = pytest.mark.gpu
 
-LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "python-bls_amd", "csrc", "libblsgpu_widecheck.so")
-
 
 @pytest.fixture(scope="module")
 def check_lib():
-    import torch  # noqa: F401  (first, as bls_py._native.load_library: both bind to one HIP runtime)
-    assert os.path.exists(LIB), "libblsgpu_widecheck.so is not built: run __graft_entry__.build() (make -C python-bls_amd/csrc)"
-    lib = ctypes.CDLL(LIB)
-    lib.blsgpu_wide_check.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
-    lib.blsgpu_wide_check.restype = ctypes.c_int
-    return lib
+    return checklib.load("libblsgpu_widecheck", "blsgpu_wide_check")
 
 
 @pytest.fixture(scope="module")
@@ -32,34 +23,8 @@ def ops():
     return V.ops()
 
 
-def _call(lib, op, sets):
-    n = len(sets)
-    cin = np.array([w for k in sets for w in op.sets[k][1]], dtype=np.int32)
-    cout = np.zeros(n * op.wout, dtype=np.int32)
-    rc = lib.blsgpu_wide_check(op.code, cin.ctypes.data, cin.size, n, cout.ctypes.data, cout.size)
-    assert rc == 0, "%s, %d items: blsgpu_wide_check returned %d (-3: a guard record was written; -4: an address outside the value file; > 0: HIP error)" % (op.name, n, rc)
-    got = cout.tolist()
-    for i, k in enumerate(sets):
-        tag, _, want = op.sets[k]
-        g = got[i * op.wout:(i + 1) * op.wout]
-        bad = [(j, g[j], w) for j, w in enumerate(want) if w is not None and g[j] != w]
-        assert not bad, "%s, %d items, item %d, set %s: %d words differ, first (word, got, want) %s" % (op.name, n, i, tag, len(bad), bad[:4])
-
-
 def _run(lib, op):
-    counts = V.N_WAVE_ITEMS if op.wave else V.N_LANE_ITEMS
-    seen = set()
-    for n in counts:
-        sets = V.call_sets(op, n)
-        _call(lib, op, sets)
-        seen |= set(sets)
-    base = counts[-1]
-    while len(seen) < len(op.sets):                # the sets a call of the largest count has not reached yet
-        assert base < 64 * counts[-1], op.name
-        sets = V.call_sets(op, counts[-1], base)
-        _call(lib, op, sets)
-        seen |= set(sets)
-        base += counts[-1]
+    checklib.run_sets(lib, V, op, V.N_WAVE_ITEMS if op.wave else V.N_LANE_ITEMS)
 
 
 def test_per_lane_ops(check_lib, ops):
@@ -106,7 +71,7 @@ def test_bad_arguments_are_refused(check_lib, ops):
     op = ops["WSTEP_1"]
     words = np.array(op.sets[0][1], dtype=np.int32)
     out = np.zeros(op.wout, dtype=np.int32)
-    call = lambda code, w, n, o: check_lib.blsgpu_wide_check(code, w.ctypes.data, w.size, n, o.ctypes.data, o.size)
+    call = lambda code, w, n, o: check_lib(code, w.ctypes.data, w.size, n, o.ctypes.data, o.size)
     assert call(op.code, words[:-1], 1, out) == -2
     assert call(op.code, words, 1, out[:-1]) == -2
     assert call(9, words, 1, out) == -1
