@@ -1,5 +1,5 @@
 // check_runner.h -- TEST-ONLY: the host side the check libraries share (blsgpu_fp28_check.hip, blsgpu_fq32_check.hip,
-// blsgpu_wide_check.hip, blsgpu_ml_check.hip, blsgpu_fr_check.hip).  Not part of libblsgpu.so, not an ABI.
+// blsgpu_wide_check.hip, blsgpu_ml_check.hip, blsgpu_fr_check.hip, blsgpu_curve_check.hip).  Not part of libblsgpu.so, not an ABI.
 //
 // Every library exports ONE function, int blsgpu_<layer>_check(op, in, words_in, n, out, words_out), over 32-bit words.
 // It returns

@@ -1,5 +1,5 @@
-"""The Python side the five check-library GPU tests share (test_gpu_fp28, test_gpu_fq32, test_gpu_wide, test_gpu_ml_steps,
-test_gpu_fr): loading a library, one call with its return-code message, the per-lane comparison loop of the lane-layout
+"""The Python side the six check-library GPU tests share (test_gpu_fp28, test_gpu_fq32, test_gpu_wide, test_gpu_ml_steps,
+test_gpu_fr, test_gpu_curve): loading a library, one call with its return-code message, the per-lane comparison loop of the lane-layout
 libraries and the per-set comparison loop of wide and ml.  The return codes are csrc/check_runner.h's."""
 import ctypes
 import os
@@ -63,16 +63,29 @@ def run_group(lib_fn, V, group, dtype=np.uint32, item_call=None):
     assert ran and ran % len(V.N_ITEMS) == 0
 
 
-def run_sets(lib_fn, V, op, counts):
-    """an op of a per-set vectors module (wide, ml) with every count, then further calls of the largest count until every set
-    has run; every output word is compared exactly, except where the expected word is None (wide's write sink)"""
+def run_sets(lib_fn, V, op, counts, checks=False):
+    """an op of a per-set vectors module (wide, ml, curve) with every count, then further calls of the largest count until every set
+    has run; every output word is compared exactly, except where the expected word is None (wide's write sink).  checks: a set's
+    fifth entry is its independent check (or None), run on the device's own words once per set; where device and model differ it
+    says which of them is wrong"""
+    checked = set()
+
     def one(sets):
         n = len(sets)
         got = call(lib_fn, op, [w for k in sets for w in op.sets[k][1]], n, np.int32)
         for i, k in enumerate(sets):
             tag, want = op.sets[k][0], op.sets[k][2]
+            chk = op.sets[k][4] if checks else None
             if got[i] == want:
+                if chk is not None and k not in checked:
+                    checked.add(k)
+                    chk(got[i])
                 continue
+            if chk is not None:                       # who is wrong: the independent check on the device's words decides
+                try:
+                    chk(got[i])
+                except AssertionError as err:
+                    raise AssertionError("%s, %d items, item %d, set %s: the device is wrong (%s)" % (op.name, n, i, tag, err))
             bad = [(j, got[i][j], w) for j, w in enumerate(want) if w is not None and got[i][j] != w]
             assert not bad, "%s, %d items, item %d, set %s: %d words differ, first (word, got, want) %s" % (op.name, n, i, tag, len(bad), bad[:4])
         return set(sets)
