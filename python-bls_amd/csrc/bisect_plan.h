@@ -10,14 +10,11 @@
 #include <algorithm>
 #include <vector>
 
+#include "layout.h"
+
 namespace bisect {
 
-// consecutive arrays in one buffer, each rounded up to `unit` (a power of two: 256 bytes in the workspaces, 64 words in the
-// folded table); `off` is the running offset and, at the end, the size
-struct Layout {
-    size_t unit, off;
-    size_t take(size_t count) { const size_t o = off; off += (count + unit - 1) & ~(unit - 1); return o; }
-};
+using ws::Layout;
 
 // the top length: n rounded up to a power of two
 inline size_t ceil_pow2(size_t n) { size_t K = 1; while (K < n) K <<= 1; return K; }

@@ -44,6 +44,7 @@
 
 #if BLSGPU_EMIT(BLSGPU_TU_HOST)
 #include "bisect_plan.h"
+#include "msm_plan.h"
 #include "blsgpu_ctx.h"
 
 namespace {
@@ -139,8 +140,16 @@ int decompress_host(blsgpu_ctx* c, const uint8_t* in, size_t n, uint8_t* out, ui
 }  // namespace
 
 // ---------------------------------------------------------------- MSM -------
+// Which kernel family serves a sum, and every size, offset, window, chunk and grid of it, is msm_plan.h (host-only: tested without a
+// GPU); the functions here grow the two shared buffers to a plan's totals and launch what it says.
 namespace {
 constexpr int MSM_WAVES = 4;
+constexpr msm::Consts MSM_CONSTS = {blsgpu::SRT_LANES, blsgpu::SRT_SCW, blsgpu::SRT_BITADDS, blsgpu::SRT_MAXBITS, blsgpu::SRT_SLICE,
+                                    blsgpu::SMUL_T, blsgpu::PIP_W, blsgpu::PIP_NB, blsgpu::L28_AFF, blsgpu::L28_PJ, MSM_WAVES, BLSVM_HMSM2_NP,
+                                    {blsgpu::MsmCfg<1>::NP, blsgpu::MsmCfg<2>::NP}, {blsgpu::SrtG<1>::LP, blsgpu::SrtG<2>::LP},
+                                    {blsgpu::SrtG<1>::AFF, blsgpu::SrtG<2>::AFF}, {blsgpu::SrtG<1>::PJ, blsgpu::SrtG<2>::PJ}};
+static_assert(msm::same(MSM_CONSTS, msm::GFX950), "msm_plan.h: GFX950 (the host test's values) differs from the kernel files");
+static_assert(sizeof(msm::SortedPlan::bias) == sizeof(blsgpu::SrtBias), "msm_plan.h: SortedPlan::bias is not SRT_SCW words");
 
 // The wide machine's Horner (blsgpu_msmw.hip): list g of `lists` -> sum_i 2^(cbits i) in[g][i], one wavefront per list; AFFINE = 0
 // leaves projective sums for the next step, AFFINE = 1 writes the caller's affine point and its infinity flag.
@@ -149,96 +158,72 @@ static void horner_wide(hipStream_t st, size_t lists, const uint32_t* in, uint32
     hipLaunchKernelGGL((blsgpu::msmw::k_msm_horner_wide<DEG, AFFINE>), dim3((unsigned)lists), dim3(64), 0, st, in, npts, cbits, out, out_inf);
 }
 
+// the fold levels of a sorted or a plain sum in the workspace W
+template <int DEG>
+static int run_folds(hipStream_t st, uint32_t* W, const msm::Fold* fold, int nfolds) {
+    for (const msm::Fold* f = fold; f != fold + nfolds; f++) {
+        if (f->kernel == msm::F_HORNER_WIDE)
+            horner_wide<DEG, 0>(st, f->ftotal, W + f->src, f->npts, 0u, W + f->dst, nullptr);
+        else if (f->kernel == msm::F_SRT_FOLD)
+            hipLaunchKernelGGL(blsgpu::k_srt_fold<DEG>, dim3(f->grid), dim3(64), 0, st, W + f->src, (uint32_t)f->cur, 8u, (uint32_t)f->nfold,
+                               (uint32_t)f->ftotal, W + f->dst);
+        else
+            hipLaunchKernelGGL(blsgpu::k_msm_lane_fold<1>, dim3(f->grid), dim3(64), 0, st, W + f->src, (uint32_t)f->cur, 8u, (uint32_t)f->nfold,
+                               (uint32_t)f->ftotal, W + f->dst, f->last);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
 // One sum with scalars by sorted buckets (blsgpu_msm.hip, k_srt_*; G1 a unit per lane, G2 per lane pair): enqueues on `st` and
 // returns, like every _dev path (no synchronisation, usable under stream capture).  Returns 1 only when the key list would not fit
 // 32 bits; the caller then takes the fixed-window path.
 template <int DEG>
 static int msm_sorted(blsgpu_ctx* c, const void* d_pts, const void* d_scalars, size_t n, void* d_out, void* d_out_inf, hipStream_t st) {
-    typedef blsgpu::SrtG<DEG> G;
-    // Window bits: with 131 072 equal pieces a run covers 131072 / (keys per window x windows) pieces whatever n is, and a run of
-    // more than three pieces costs a whole wavefront in k_srt_fix_long.  With signed digits (2^(cb-1) keys per window) 13 bits are
-    // the best width at every size the sorted path serves (tools/c5_probe.py under BLSGPU_MSM_SORT_BITS, profiles/r05_c5_window_bits.txt:
-    // 2^20 points 5.71 / 5.42 / 5.46 ms for 12 / 13 / 14 bits, 16 384 points 1.88 / 1.52 / 1.68).
-    const size_t pinned = DEG == 1 ? c->sort_bits : c->sort2_bits;
-    if (pinned && (pinned < 5 || pinned > blsgpu::SRT_MAXBITS)) return fail(-EINVAL, "BLSGPU_MSM_SORT_BITS out of range");
-    const uint32_t cb = pinned ? (uint32_t)pinned : DEG == 1 ? (n < 512 ? 7u : 13u) : c->msm_sort2_bits(n);   // (a few points: 37 windows of 64 keys, 1.06 ms for one point against 1.24)
-    // signed digits (blsgpu_msm.hip): 2^(cb-1) keys per window; 258 <= cb x windows keeps the recoded scalar inside the windows
-    const uint32_t kb = cb - 1, nwin = (258 + cb - 1) / cb;
-    const size_t nkeys = (size_t)nwin << kb;
-    if ((size_t)nwin * n > 0xFFFFFFF0ull || n >= 0x80000000ull) return 1;
-    const size_t nch = ((size_t)1 << (cb - 2)) / blsgpu::SRT_BITADDS, nsum = (size_t)nwin * cb;
-    const size_t units = blsgpu::SRT_LANES / G::LP;
-    const bool wide = DEG == 2 || c->msm_wide_tail;           // (G2 has no tail on the wavefront VM)
-    // workspace: prep | recoded scalars | cnt | start (+1) | cursor | maxcnt, total | idx | bsum | headpart | headkey | bit sums (two buffers) | winsums
-    size_t off = 0;
-    auto take = [&](size_t words) { size_t o = off; off += (words + 3) & ~(size_t)3; return o; };
-    const size_t PJ = G::PJ;
-    const size_t o_prep = take(n * G::AFF), o_rec = take(n * blsgpu::SRT_SCW), o_cnt = take(nkeys), o_start = take(nkeys + 1), o_cur = take(nkeys),
-                 o_max = take(4), o_idx = take((size_t)nwin * n), o_bsum = take(nkeys * PJ), o_hp = take(units * PJ), o_hk = take(units),
-                 o_b0 = take(nsum * nch * PJ), o_b1 = take(nsum * ((nch + 7) / 8) * PJ + PJ), o_win = take((size_t)nwin * PJ), o_live = take((n + 3) / 4),
-                 o_wtot = take(2 * (size_t)nwin), o_long = take(nkeys + 4);
-    if (int rc_ = c->grow(B_BUCKETS, off * 4)) return rc_;
+    const msm::SortedPlan p = msm::plan_sorted(*c, MSM_CONSTS, DEG, n);
+    if (p.bad_bits) return fail(-EINVAL, "BLSGPU_MSM_SORT_BITS out of range");
+    if (p.not_me) return 1;
+    if (int rc_ = c->grow(B_BUCKETS, p.words * 4)) return rc_;
     uint32_t* W = c->at<uint32_t>(B_BUCKETS);
-    HIP_TRY(hipMemsetAsync(W + o_cnt, 0, nkeys * 4, st));
-    HIP_TRY(hipMemsetAsync(W + o_long, 0, 16, st));          // counter of the long runs (the key list follows it)
-    uint8_t* live = (uint8_t*)(W + o_live);
+    HIP_TRY(hipMemsetAsync(W + p.o_cnt, 0, p.nkeys * 4, st));
+    HIP_TRY(hipMemsetAsync(W + p.o_long, 0, 16, st));        // counter of the long runs (the key list follows it)
+    uint8_t* live = (uint8_t*)(W + p.o_live);
     blsgpu::SrtBias bias;
-    for (uint32_t j = 0; j < blsgpu::SRT_SCW; j++) bias.w[j] = 0;
-    for (uint32_t w = 0; w < nwin; w++) {
-        const uint32_t pos = cb * w + cb - 1;
-        bias.w[pos >> 5] |= 1u << (pos & 31);
-    }
-    hipLaunchKernelGGL(blsgpu::k_srt_prep<DEG>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_pts, (const uint32_t*)d_scalars, (uint32_t)n,
-                       bias, W + o_prep, live, W + o_rec);
+    memcpy(bias.w, p.bias, sizeof(bias.w));
+    const uint32_t cb = p.cb, kb = p.kb, nwin = p.nwin, nkeys = (uint32_t)p.nkeys, units = (uint32_t)p.units;
+    hipLaunchKernelGGL(blsgpu::k_srt_prep<DEG>, dim3(p.g_prep), dim3(256), 0, st, (const uint32_t*)d_pts, (const uint32_t*)d_scalars, (uint32_t)n,
+                       bias, W + p.o_prep, live, W + p.o_rec);
     HIP_TRY(hipGetLastError());
-    const uint32_t* sc = W + o_rec;
-    const dim3 sgrid((unsigned)((n + blsgpu::SRT_SLICE - 1) / blsgpu::SRT_SLICE), nwin);
-    hipLaunchKernelGGL(blsgpu::k_srt_count, sgrid, dim3(1024), 0, st, sc, live, (uint32_t)n, cb, W + o_cnt);
-    hipLaunchKernelGGL(blsgpu::k_srt_scan_window, dim3(nwin), dim3(1024), 0, st, W + o_cnt, kb, W + o_start, W + o_wtot, W + o_wtot + nwin);
-    hipLaunchKernelGGL(blsgpu::k_srt_scan_add, dim3(nwin), dim3(1024), 0, st, nwin, kb, W + o_wtot, W + o_wtot + nwin, W + o_start, W + o_cur,
-                       W + o_max);
+    const uint32_t* sc = W + p.o_rec;
+    const dim3 sgrid(p.g_slices, nwin);
+    hipLaunchKernelGGL(blsgpu::k_srt_count, sgrid, dim3(1024), 0, st, sc, live, (uint32_t)n, cb, W + p.o_cnt);
+    hipLaunchKernelGGL(blsgpu::k_srt_scan_window, dim3(nwin), dim3(1024), 0, st, W + p.o_cnt, kb, W + p.o_start, W + p.o_wtot, W + p.o_wtot + nwin);
+    hipLaunchKernelGGL(blsgpu::k_srt_scan_add, dim3(nwin), dim3(1024), 0, st, nwin, kb, W + p.o_wtot, W + p.o_wtot + nwin, W + p.o_start, W + p.o_cur,
+                       W + p.o_max);
     HIP_TRY(hipGetLastError());
     // No read-back, no host decision (round 3): whatever the digit distribution, a long run is finished by a wavefront of
     // k_srt_fix_long -- all-equal scalars cost ~100 additions per lane there (a millisecond), and only a batch whose scalars
     // leave all windows but one empty is slow (still correct, and still faster than the fixed windows it used to fall back to).
-    hipLaunchKernelGGL(blsgpu::k_srt_scatter, sgrid, dim3(1024), 0, st, sc, live, (uint32_t)n, cb, W + o_cur, W + o_idx);
-    const auto blocks = [&](size_t nunits) { return dim3((unsigned)((nunits * G::LP + 63) / 64)); };
-    hipLaunchKernelGGL(blsgpu::k_srt_accum<DEG>, blocks(units), dim3(64), 0, st, W + o_prep, W + o_idx, W + o_start, (uint32_t)nkeys, (uint32_t)units,
-                       W + o_bsum, W + o_hp, W + o_hk);
+    hipLaunchKernelGGL(blsgpu::k_srt_scatter, sgrid, dim3(1024), 0, st, sc, live, (uint32_t)n, cb, W + p.o_cur, W + p.o_idx);
+    hipLaunchKernelGGL(blsgpu::k_srt_accum<DEG>, dim3(p.g_accum), dim3(64), 0, st, W + p.o_prep, W + p.o_idx, W + p.o_start, nkeys, units,
+                       W + p.o_bsum, W + p.o_hp, W + p.o_hk);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(blsgpu::k_srt_fix<DEG>, blocks(nkeys), dim3(64), 0, st, W + o_start, (uint32_t)nkeys, (uint32_t)units, W + o_hp, W + o_hk, W + o_bsum,
-                       W + o_long, W + o_long + 4);
-    hipLaunchKernelGGL(blsgpu::k_srt_fix_long<DEG>, dim3(1024), dim3(64), 0, st, W + o_start, (uint32_t)nkeys, (uint32_t)units, W + o_hp, W + o_bsum, W + o_long,
-                       W + o_long + 4);
-    const size_t btotal = nsum * nch;
-    hipLaunchKernelGGL(blsgpu::k_srt_bits<DEG>, blocks(btotal), dim3(64), 0, st, W + o_bsum, nwin, cb, (uint32_t)btotal, W + o_b0);
+    hipLaunchKernelGGL(blsgpu::k_srt_fix<DEG>, dim3(p.g_fix), dim3(64), 0, st, W + p.o_start, nkeys, units, W + p.o_hp, W + p.o_hk, W + p.o_bsum,
+                       W + p.o_long, W + p.o_long + 4);
+    hipLaunchKernelGGL(blsgpu::k_srt_fix_long<DEG>, dim3(1024), dim3(64), 0, st, W + p.o_start, nkeys, units, W + p.o_hp, W + p.o_bsum, W + p.o_long,
+                       W + p.o_long + 4);
+    hipLaunchKernelGGL(blsgpu::k_srt_bits<DEG>, dim3(p.g_bits), dim3(64), 0, st, W + p.o_bsum, nwin, cb, (uint32_t)p.btotal, W + p.o_b0);
     HIP_TRY(hipGetLastError());
-    uint32_t *src = W + o_b0, *dst = W + o_b1;
-    if (nch == 1 && !wide) {                                  // (5-bit windows: nothing to fold, but the VM's tail reads its own form)
-        hipLaunchKernelGGL(blsgpu::k_msm_lane_fold<1>, dim3((unsigned)((nsum + 63) / 64)), dim3(64), 0, st, src, 1u, 1u, 1u, (uint32_t)nsum, dst, 1u);
-        src = dst;
-    }
-    for (size_t cur = nch; cur > 1;) {                        // runs of 8 partial sums per unit until one is left per (window, bit)
-        const size_t nfold = (cur + 7) / 8, ftotal = nsum * nfold;
-        if (wide && ftotal <= 4096 && (cur <= 8 || cur % 8 == 0))
-            // few runs left: one wavefront per run, an addition two steps of the wide machine (a lane's own addition is ~6000 instructions)
-            horner_wide<DEG, 0>(st, ftotal, src, (uint32_t)(cur < 8 ? cur : 8), 0u, dst, nullptr);
-        else if (wide)
-            hipLaunchKernelGGL(blsgpu::k_srt_fold<DEG>, blocks(ftotal), dim3(64), 0, st, src, (uint32_t)cur, 8u, (uint32_t)nfold, (uint32_t)ftotal, dst);
-        else
-            hipLaunchKernelGGL(blsgpu::k_msm_lane_fold<1>, dim3((unsigned)((ftotal + 63) / 64)), dim3(64), 0, st, src, (uint32_t)cur, 8u,
-                               (uint32_t)nfold, (uint32_t)ftotal, dst, nfold == 1 ? 1u : 0u);   // the last fold: the VM's form for the VM's tail
-        HIP_TRY(hipGetLastError());
-        uint32_t* t = src; src = dst; dst = t;
-        cur = nfold;
-    }
-    if (wide) {
+    if (p.pass5)                                              // (5-bit windows: nothing to fold, but the VM's tail reads its own form)
+        hipLaunchKernelGGL(blsgpu::k_msm_lane_fold<1>, dim3(p.g_pass5), dim3(64), 0, st, W + p.o_b0, 1u, 1u, 1u, (uint32_t)p.nsum, W + p.o_b1, 1u);
+    if (int rc_ = run_folds<DEG>(st, W, p.fold, p.nfolds)) return rc_;
+    if (p.wide) {
         // W_w = sum_b 2^b S_(w,b), one wavefront per window; then sum_w 2^(cb w) W_w on one wavefront
-        horner_wide<DEG, 0>(st, nwin, src, cb, 1u, W + o_win, nullptr);
-        horner_wide<DEG, 1>(st, 1, W + o_win, nwin, cb, (uint32_t*)d_out, (uint8_t*)d_out_inf);
+        horner_wide<DEG, 0>(st, nwin, W + p.src, cb, 1u, W + p.o_win, nullptr);
+        horner_wide<DEG, 1>(st, 1, W + p.o_win, nwin, cb, (uint32_t*)d_out, (uint8_t*)d_out_inf);
     } else {
-        hipLaunchKernelGGL(blsgpu::k_srt_windows, dim3(nwin), dim3(64), (size_t)blsgpu::TEAM_BYTES, st, c->tabs, src, cb, W + o_win);
-        hipLaunchKernelGGL(blsgpu::k_msm_pip_horner<1>, dim3(1), dim3(64), (size_t)blsgpu::TEAM_BYTES, st, c->tabs, W + o_win, nwin, cb,
+        hipLaunchKernelGGL(blsgpu::k_srt_windows, dim3(nwin), dim3(64), (size_t)blsgpu::TEAM_BYTES, st, c->tabs, W + p.src, cb, W + p.o_win);
+        hipLaunchKernelGGL(blsgpu::k_msm_pip_horner<1>, dim3(1), dim3(64), (size_t)blsgpu::TEAM_BYTES, st, c->tabs, W + p.o_win, nwin, cb,
                            (uint32_t*)d_out, (uint8_t*)d_out_inf);
     }
     HIP_TRY(hipGetLastError());
@@ -246,41 +231,20 @@ static int msm_sorted(blsgpu_ctx* c, const void* d_pts, const void* d_scalars, s
 }
 
 // One plain sum of n points (no scalars) -- BLS.aggregate_pub_keys / aggregate_sigs without exponents (bls.py:203-261): a chunk of
-// the list per unit (k_sum_chunks: complete mixed additions in registers), then runs of eight partial sums until eight are left
-// (k_srt_fold, or one wavefront per run on the wide machine once at most 4096 runs are left), then the last run with the affine
+// the list per unit (k_sum_chunks: complete mixed additions in registers), the fold levels, then the last run with the affine
 // conversion.  Enqueues on `st` and returns.
 template <int DEG>
 static int msm_plain(blsgpu_ctx* c, const void* d_pts, size_t n, void* d_out, void* d_out_inf, hipStream_t st) {
-    typedef blsgpu::SrtG<DEG> G;
-    const size_t units_max = blsgpu::SRT_LANES / G::LP;
-    size_t U = (n + 3) / 4;                                   // four points per unit while units are free (a small sum is a latency)
-    if (U > units_max) U = units_max;
-    const size_t chunk = (n + U - 1) / U;
-    U = (n + chunk - 1) / chunk;
-    size_t off = 0;
-    auto take = [&](size_t words) { size_t o = off; off += (words + 3) & ~(size_t)3; return o; };
-    const size_t PJ = G::PJ;
-    const size_t o_prep = take(n * blsgpu::L28_AFF * DEG), o_live = take((n + 3) / 4), o_b0 = take(U * PJ), o_b1 = take(((U + 7) / 8) * PJ + PJ);
-    if (int rc_ = c->grow(B_BUCKETS, off * 4)) return rc_;
+    const msm::PlainPlan p = msm::plan_plain(MSM_CONSTS, DEG, n);
+    if (int rc_ = c->grow(B_BUCKETS, p.words * 4)) return rc_;
     uint32_t* W = c->at<uint32_t>(B_BUCKETS);
-    uint8_t* live = (uint8_t*)(W + o_live);
-    hipLaunchKernelGGL(blsgpu::k_lane_prep<DEG>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_pts, (uint32_t)n, W + o_prep, live);
-    const auto blocks = [&](size_t nunits) { return dim3((unsigned)((nunits * G::LP + 63) / 64)); };
-    hipLaunchKernelGGL(blsgpu::k_sum_chunks<DEG>, blocks(U), dim3(64), 0, st, W + o_prep, live, (uint32_t)n, (uint32_t)chunk, (uint32_t)U, W + o_b0);
+    uint8_t* live = (uint8_t*)(W + p.o_live);
+    hipLaunchKernelGGL(blsgpu::k_lane_prep<DEG>, dim3(p.g_prep), dim3(256), 0, st, (const uint32_t*)d_pts, (uint32_t)n, W + p.o_prep, live);
+    hipLaunchKernelGGL(blsgpu::k_sum_chunks<DEG>, dim3(p.g_chunks), dim3(64), 0, st, W + p.o_prep, live, (uint32_t)n, (uint32_t)p.chunk, (uint32_t)p.U,
+                       W + p.o_b0);
     HIP_TRY(hipGetLastError());
-    uint32_t *src = W + o_b0, *dst = W + o_b1;
-    size_t cur = U;
-    while (cur > 8) {
-        const size_t nfold = (cur + 7) / 8;
-        if (nfold <= 4096 && cur % 8 == 0)
-            horner_wide<DEG, 0>(st, nfold, src, 8u, 0u, dst, nullptr);
-        else
-            hipLaunchKernelGGL(blsgpu::k_srt_fold<DEG>, blocks(nfold), dim3(64), 0, st, src, (uint32_t)cur, 8u, (uint32_t)nfold, (uint32_t)nfold, dst);
-        HIP_TRY(hipGetLastError());
-        uint32_t* t = src; src = dst; dst = t;
-        cur = nfold;
-    }
-    horner_wide<DEG, 1>(st, 1, src, (uint32_t)cur, 0u, (uint32_t*)d_out, (uint8_t*)d_out_inf);
+    if (int rc_ = run_folds<DEG>(st, W, p.fold, p.nfolds)) return rc_;
+    horner_wide<DEG, 1>(st, 1, W + p.src, p.last_n, 0u, (uint32_t*)d_out, (uint8_t*)d_out_inf);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -288,165 +252,127 @@ static int msm_plain(blsgpu_ctx* c, const void* d_pts, size_t n, void* d_out, vo
 // A batch of scalar multiplications / of small sums with scalars: one group per unit (k_smul).  Enqueues on `st` and returns.
 template <int DEG>
 static int msm_small_groups(blsgpu_ctx* c, const void* d_pts, const void* d_scalars, size_t k, size_t groups, void* d_out, void* d_out_inf, hipStream_t st) {
-    typedef blsgpu::SrtG<DEG> G;
-    // slices of groups whose tables (16 projective multiples per point) stay below 2 GB: 2^20 groups of eight G2 points would ask for 45 GB
-    const size_t upw = 64 / G::LP, per_group = k * blsgpu::SMUL_T * G::PJ * 4;
-    size_t slice = ((size_t)2 << 30) / per_group / upw * upw;
-    if (slice < upw) slice = upw;
-    slice = slice_len(c, slice, upw);
-    if (slice > groups) slice = groups;
-    const size_t units0 = (slice + upw - 1) / upw * upw, n0 = k * slice;
-    size_t off = 0;
-    auto take = [&](size_t words) { size_t o = off; off += (words + 3) & ~(size_t)3; return o; };
-    const size_t o_prep = take(n0 * blsgpu::L28_AFF * DEG), o_live = take((n0 + 3) / 4), o_tab = take(units0 * k * blsgpu::SMUL_T * G::PJ);
-    if (c->grow(B_BUCKETS, off * 4)) {
+    const msm::SmallPlan p = msm::plan_small_groups(*c, MSM_CONSTS, DEG, k, groups);
+    if (c->grow(B_BUCKETS, p.words * 4)) {
         (void)hipGetLastError();
         return 1;                                              // no room: the caller's other kernels
     }
     uint32_t* W = c->at<uint32_t>(B_BUCKETS);
-    uint8_t* live = (uint8_t*)(W + o_live);
-    for (size_t lo = 0; lo < groups; lo += slice) {
-        const size_t m = groups - lo < slice ? groups - lo : slice, n = k * m, units = (m + upw - 1) / upw * upw;
-        hipLaunchKernelGGL(blsgpu::k_lane_prep<DEG>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_pts + lo * k * 24 * DEG, (uint32_t)n,
-                           W + o_prep, live);
-        hipLaunchKernelGGL(blsgpu::k_smul<DEG>, dim3((unsigned)(units * G::LP / 64)), dim3(64), 0, st, W + o_prep, live, (const uint32_t*)d_scalars + lo * k * 8,
-                           (uint32_t)k, (uint32_t)m, W + o_tab, (uint32_t*)d_out + lo * 24 * DEG, d_out_inf ? (uint8_t*)d_out_inf + lo : nullptr);
+    uint8_t* live = (uint8_t*)(W + p.o_live);
+    for (size_t lo = 0; lo < groups; lo += p.slice) {
+        const msm::SmallSlice s = p.at(lo);
+        hipLaunchKernelGGL(blsgpu::k_lane_prep<DEG>, dim3(s.g_prep), dim3(256), 0, st, (const uint32_t*)d_pts + s.pts, (uint32_t)s.n, W + p.o_prep, live);
+        hipLaunchKernelGGL(blsgpu::k_smul<DEG>, dim3(s.g_smul), dim3(64), 0, st, W + p.o_prep, live, (const uint32_t*)d_scalars + s.scalars,
+                           (uint32_t)k, (uint32_t)s.m, W + p.o_tab, (uint32_t*)d_out + s.out, d_out_inf ? (uint8_t*)d_out_inf + lo : nullptr);
         HIP_TRY(hipGetLastError());
     }
+    return 0;
+}
+
+// The bucket method: one large sum is cut into chunks, a batch of sums uses one chunk per group; buckets in LDS (k_msm_pip) or one
+// (group, chunk, window) per lane with the buckets in HBM (k_msm_lane / k_msm_lane2x).
+template <int DEG>
+static int msm_bucket(blsgpu_ctx* c, const void* d_pts, const void* d_scalars, size_t k, size_t groups, void* d_out, void* d_out_inf, hipStream_t st) {
+    using P = blsgpu::PipCfg<DEG>;
+    const msm::BucketPlan p = msm::plan_bucket(*c, MSM_CONSTS, DEG, k, groups);
+    if (int rc_ = c->grow(B_MSM_PART, p.part_words * 4)) return rc_;
+    uint32_t* const d_part = c->at<uint32_t>(B_MSM_PART);
+    uint32_t *d_win = d_part + p.o_win, *d_prep = d_part + p.o_prep;
+    if (p.lane_path) {
+        uint8_t* d_live = (uint8_t*)(d_part + p.o_live);
+        hipLaunchKernelGGL(blsgpu::k_lane_prep<DEG>, dim3(p.g_prep), dim3(256), 0, st, (const uint32_t*)d_pts, (uint32_t)p.n, d_prep, d_live);
+        HIP_TRY(hipGetLastError());
+        if (int rc_ = c->grow(B_BUCKETS, p.bucket_words * 4)) return rc_;
+        uint32_t* const d_buckets = c->at<uint32_t>(B_BUCKETS);
+        if (p.pairs)
+            hipLaunchKernelGGL(blsgpu::k_msm_lane2x, dim3(p.g_lane), dim3(64), 0, st, d_prep, d_live, (const uint32_t*)d_scalars, (uint32_t)k,
+                               (uint32_t)p.chunk, (uint32_t)p.chunks, (uint32_t)p.lanes, d_buckets, d_part, p.lane_last);
+        else
+            hipLaunchKernelGGL(blsgpu::k_msm_lane<DEG>, dim3(p.g_lane), dim3(64), 0, st, d_prep, d_live, (const uint32_t*)d_scalars, (uint32_t)k,
+                               (uint32_t)p.chunk, (uint32_t)p.chunks, (uint32_t)p.lanes, d_buckets, d_part, p.lane_last);
+        HIP_TRY(hipGetLastError());
+        if (p.tail == msm::T_HORNER_QUADS) {
+            const WaveShape ws = wave_shape(c, p.quad_waves);
+            hipLaunchKernelGGL(blsgpu::k_msm_horner_quads, dim3(ws.blocks), dim3(ws.threads), 0, st, d_part,
+                               (uint32_t)blsgpu::PIP_W, (uint32_t)blsgpu::PIP_C, (uint32_t)groups, (uint32_t*)d_out, (uint8_t*)d_out_inf);
+            HIP_TRY(hipGetLastError());
+            return 0;
+        }
+        const uint32_t* winsrc = d_part;
+        if (p.fold_n) {                                      // many chunks: fold runs of 64 partials per lane first
+            uint32_t* d_fold = d_buckets + p.o_fold;
+            hipLaunchKernelGGL(blsgpu::k_msm_lane_fold<DEG>, dim3(p.g_fold), dim3(64), 0, st, d_part, (uint32_t)p.chunks, 64u, (uint32_t)p.fold_n,
+                               (uint32_t)p.ftotal, d_fold, 1u);
+            HIP_TRY(hipGetLastError());
+            winsrc = d_fold;
+        }
+        hipLaunchKernelGGL(blsgpu::k_msm_pip_windows<DEG>, dim3(blsgpu::PIP_W, (unsigned)groups), dim3(64), (size_t)blsgpu::TEAM_BYTES, st,
+                           c->tabs, winsrc, (uint32_t)p.wchunks, d_win);
+        HIP_TRY(hipGetLastError());
+    } else {
+        hipLaunchKernelGGL(blsgpu::k_msm_prep<DEG>, dim3(p.g_prep), dim3(MSM_WAVES * 64), (size_t)MSM_WAVES * blsgpu::TEAM_BYTES,
+                           st, c->tabs, (const uint32_t*)d_pts, (uint32_t)p.n, d_prep);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(blsgpu::k_msm_pip<DEG>, dim3((unsigned)p.chunks, blsgpu::PIP_W, (unsigned)groups), dim3(64), (size_t)P::SLOTS * 48,
+                           st, c->tabs, d_prep, (const uint32_t*)d_scalars, (uint32_t)k, (uint32_t)p.chunk, d_part);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(blsgpu::k_msm_pip_windows<DEG>, dim3(blsgpu::PIP_W, (unsigned)groups), dim3(64), (size_t)blsgpu::TEAM_BYTES, st,
+                           c->tabs, d_part, (uint32_t)p.chunks, d_win);
+        HIP_TRY(hipGetLastError());
+    }
+    if (p.tail == msm::T_HORNER_NP) {                        // a batch of G2 sums: BLSVM_HMSM2_NP sums per team
+        hipLaunchKernelGGL(blsgpu::k_msm_horner_np, dim3(p.g_np), dim3(64),
+                           (size_t)BLSVM_HMSM2_SLOTS * 48, st, c->tabs, d_win, (uint32_t)blsgpu::PIP_W, (uint32_t)blsgpu::PIP_C,
+                           (uint32_t)groups, (uint32_t*)d_out, (uint8_t*)d_out_inf);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    hipLaunchKernelGGL(blsgpu::k_msm_pip_horner<DEG>, dim3((unsigned)groups), dim3(64), (size_t)blsgpu::TEAM_BYTES, st, c->tabs, d_win,
+                       (uint32_t)blsgpu::PIP_W, (uint32_t)blsgpu::PIP_C, (uint32_t*)d_out, (uint8_t*)d_out_inf);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Double-and-add on the wavefront VM: every sum the other families do not serve.
+template <int DEG>
+static int msm_vm(blsgpu_ctx* c, const void* d_pts, const void* d_scalars, size_t k, size_t groups, void* d_out, void* d_out_inf, hipStream_t st) {
+    const msm::VmPlan p = msm::plan_vm(MSM_CONSTS, DEG, k, groups);
+    if (int rc_ = c->grow(B_MSM_PART, p.words * 4)) return rc_;
+    size_t lds = (size_t)MSM_WAVES * blsgpu::TEAM_BYTES;
+    hipLaunchKernelGGL(blsgpu::k_msm<DEG>, dim3((unsigned)p.blocks), dim3(MSM_WAVES * 64), lds, st, c->tabs,
+                       (const uint32_t*)d_pts, (const uint32_t*)d_scalars, (uint32_t)k, (uint32_t)p.chunk, (uint32_t)p.bpg,
+                       c->at<uint32_t>(B_MSM_PART));
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(blsgpu::k_msm_finish<DEG>, dim3((unsigned)p.fblocks), dim3(MSM_WAVES * 64), lds, st, c->tabs,
+                       c->at<uint32_t>(B_MSM_PART), (uint32_t)p.bpg, (uint32_t)groups, (uint32_t*)d_out, (uint8_t*)d_out_inf);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
 template <int DEG>
 int msm_dev(blsgpu_ctx* c, const void* d_pts, const void* d_scalars, size_t k, size_t groups, void* d_out,
             void* d_out_inf, hipStream_t st) {
-    using C = blsgpu::MsmCfg<DEG>;
     if (groups == 0) return 0;
     StreamGuard sg(c, st);
-    if (k == 0) {                                   // empty sums: infinity
-        HIP_TRY(hipMemsetAsync(d_out, 0, groups * 96 * DEG, st));
-        if (d_out_inf) HIP_TRY(hipMemsetAsync(d_out_inf, 1, groups, st));
-        return 0;
-    }
-    if (k > 0x7FFFFFFFull || groups > 0x7FFFFFFFull || k * groups > 0xFFFFFFF0ull) return fail(-EINVAL, "msm too large");
-    if (groups == 1 && !d_scalars && k >= c->msm_plain_threshold) return msm_plain<DEG>(c, d_pts, k, d_out, d_out_inf, st);
-    if (d_scalars && groups >= c->smul_min_groups && k <= c->smul_max_k) {
-        const int rc_ = msm_small_groups<DEG>(c, d_pts, d_scalars, k, groups, d_out, d_out_inf, st);
-        if (rc_ != 1) return rc_;
-    }
-    if (groups == 1 && d_scalars && k >= (DEG == 1 ? c->msm_sort_threshold : c->msm_sort2_threshold)) {
-        const int rc_ = msm_sorted<DEG>(c, d_pts, d_scalars, k, d_out, d_out_inf, st);
-        if (rc_ != 1) return rc_;
-    }
-    if ((groups == 1 && k >= c->pip_threshold) || (groups > 1 && groups <= 65535 && k >= c->pip_group_threshold)) {
-        // bucket method: one large sum is cut into about 256 chunks; a batch of sums uses one chunk per group
-        using P = blsgpu::PipCfg<DEG>;
-        size_t n = k * groups;
-        // enough points for one (group, chunk, window) per lane to fill the chip?  (3 waves per SIMD = 3072 chunks)
-        const bool lane_path = n >= c->msm_lane_threshold;
-        const size_t want = c->pip_chunks ? c->pip_chunks : (lane_path ? 3072 : 256);
-        size_t chunk = (groups > 1) ? k : (k + want - 1) / want;
-        if (!lane_path && chunk < 64 * (size_t)C::NP && groups == 1) chunk = 64 * (size_t)C::NP;
-        if (!lane_path) chunk = ((chunk + C::NP - 1) / C::NP) * C::NP;
-        if (chunk == 0) chunk = 1;
-        size_t chunks = (k + chunk - 1) / chunk;
-        const size_t fold_n = (lane_path && chunks > 96) ? (chunks + 63) / 64 : 0;
-        // partials: the VM's form (36 DEG dwords) except between the lane kernel and its fold (L28: 42 DEG); prep: the VM's
-        // projective triples (36 DEG) or the lane path's affine L28 points (28 DEG) + live flags
-        constexpr size_t PJ28 = blsgpu::L28_PJ * DEG;
-        size_t need = (chunks + 1) * groups * blsgpu::PIP_W * PJ28 + n * 36 * DEG + (n + 3) / 4 + 4;
-        if (int rc_ = c->grow(B_MSM_PART, need * 4)) return rc_;
-        uint32_t* const d_part = c->at<uint32_t>(B_MSM_PART);
-        uint32_t* d_win = d_part + chunks * groups * blsgpu::PIP_W * PJ28;
-        uint32_t* d_prep = d_win + groups * blsgpu::PIP_W * PJ28;
-        if (lane_path) {
-            // one (group, chunk, window) per lane, buckets in HBM
-            uint8_t* d_live = (uint8_t*)(d_prep + n * blsgpu::L28_AFF * DEG);
-            hipLaunchKernelGGL(blsgpu::k_lane_prep<DEG>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_pts, (uint32_t)n,
-                               d_prep, d_live);
-            HIP_TRY(hipGetLastError());
-            const size_t lanes = groups * chunks * blsgpu::PIP_W;
-            const size_t bneed = lanes * (blsgpu::PIP_NB - 1) * PJ28 + fold_n * groups * blsgpu::PIP_W * 36 * DEG;
-            if (int rc_ = c->grow(B_BUCKETS, bneed * 4)) return rc_;
-            uint32_t* const d_buckets = c->at<uint32_t>(B_BUCKETS);
-            // a batch of G2 sums (one chunk each): the window sums stay in the L28 form and the Horner runs one sum per lane quad
-            const bool horner_quads = DEG == 2 && c->msm_lane_pairs && chunks == 1 && groups >= c->horner_quads_threshold;
-            if (DEG == 2 && c->msm_lane_pairs)
-                hipLaunchKernelGGL(blsgpu::k_msm_lane2x, dim3((unsigned)((2 * lanes + 63) / 64)), dim3(64), 0, st, d_prep, d_live,
-                                   (const uint32_t*)d_scalars, (uint32_t)k, (uint32_t)chunk, (uint32_t)chunks, (uint32_t)lanes, d_buckets,
-                                   d_part, (fold_n || horner_quads) ? 0u : 1u);
-            else
-                hipLaunchKernelGGL(blsgpu::k_msm_lane<DEG>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, d_prep, d_live,
-                                   (const uint32_t*)d_scalars, (uint32_t)k, (uint32_t)chunk, (uint32_t)chunks, (uint32_t)lanes, d_buckets,
-                                   d_part, fold_n ? 0u : 1u);
-            HIP_TRY(hipGetLastError());
-            if (horner_quads) {
-                const WaveShape ws = wave_shape(c, (4 * groups + 63) / 64);
-                hipLaunchKernelGGL(blsgpu::k_msm_horner_quads, dim3(ws.blocks), dim3(ws.threads), 0, st, d_part,
-                                   (uint32_t)blsgpu::PIP_W, (uint32_t)blsgpu::PIP_C, (uint32_t)groups, (uint32_t*)d_out, (uint8_t*)d_out_inf);
-                HIP_TRY(hipGetLastError());
-                return 0;
-            }
-            const uint32_t* winsrc = d_part;
-            size_t wchunks = chunks;
-            if (fold_n) {                                    // many chunks: fold runs of 64 partials per lane first
-                uint32_t* d_fold = d_buckets + lanes * (blsgpu::PIP_NB - 1) * PJ28;
-                const size_t ftotal = groups * blsgpu::PIP_W * fold_n;
-                hipLaunchKernelGGL(blsgpu::k_msm_lane_fold<DEG>, dim3((unsigned)((ftotal + 63) / 64)), dim3(64), 0, st, d_part,
-                                   (uint32_t)chunks, 64u, (uint32_t)fold_n, (uint32_t)ftotal, d_fold, 1u);
-                HIP_TRY(hipGetLastError());
-                winsrc = d_fold;
-                wchunks = fold_n;
-            }
-            hipLaunchKernelGGL(blsgpu::k_msm_pip_windows<DEG>, dim3(blsgpu::PIP_W, (unsigned)groups), dim3(64), (size_t)blsgpu::TEAM_BYTES, st,
-                               c->tabs, winsrc, (uint32_t)wchunks, d_win);
-            HIP_TRY(hipGetLastError());
-        } else {
-            size_t pblocks = (n + (size_t)MSM_WAVES * C::NP - 1) / ((size_t)MSM_WAVES * C::NP);
-            hipLaunchKernelGGL(blsgpu::k_msm_prep<DEG>, dim3((unsigned)pblocks), dim3(MSM_WAVES * 64), (size_t)MSM_WAVES * blsgpu::TEAM_BYTES,
-                               st, c->tabs, (const uint32_t*)d_pts, (uint32_t)n, d_prep);
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(blsgpu::k_msm_pip<DEG>, dim3((unsigned)chunks, blsgpu::PIP_W, (unsigned)groups), dim3(64), (size_t)P::SLOTS * 48,
-                               st, c->tabs, d_prep, (const uint32_t*)d_scalars, (uint32_t)k, (uint32_t)chunk, d_part);
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(blsgpu::k_msm_pip_windows<DEG>, dim3(blsgpu::PIP_W, (unsigned)groups), dim3(64), (size_t)blsgpu::TEAM_BYTES, st,
-                               c->tabs, d_part, (uint32_t)chunks, d_win);
-            HIP_TRY(hipGetLastError());
-        }
-        if (DEG == 2 && groups >= c->horner_np_threshold) {  // a batch of G2 sums: BLSVM_HMSM2_NP sums per team
-            hipLaunchKernelGGL(blsgpu::k_msm_horner_np, dim3((unsigned)((groups + BLSVM_HMSM2_NP - 1) / BLSVM_HMSM2_NP)), dim3(64),
-                               (size_t)BLSVM_HMSM2_SLOTS * 48, st, c->tabs, d_win, (uint32_t)blsgpu::PIP_W, (uint32_t)blsgpu::PIP_C,
-                               (uint32_t)groups, (uint32_t*)d_out, (uint8_t*)d_out_inf);
-            HIP_TRY(hipGetLastError());
+    if (msm::too_large(k, groups)) return fail(-EINVAL, "msm too large");
+    // a route that answers 1 is not the one ("not me": msm_plan.h); the next one is asked
+    for (msm::Route r = msm::START; (r = msm::next_route(*c, DEG, k, groups, d_scalars != nullptr, r)) != msm::END;) {
+        int rc_ = 1;
+        switch (r) {
+        case msm::EMPTY:                            // empty sums: infinity
+            HIP_TRY(hipMemsetAsync(d_out, 0, groups * 96 * DEG, st));
+            if (d_out_inf) HIP_TRY(hipMemsetAsync(d_out_inf, 1, groups, st));
             return 0;
+        case msm::PLAIN: rc_ = msm_plain<DEG>(c, d_pts, k, d_out, d_out_inf, st); break;
+        case msm::SMALL_GROUPS: rc_ = msm_small_groups<DEG>(c, d_pts, d_scalars, k, groups, d_out, d_out_inf, st); break;
+        case msm::SORTED: rc_ = msm_sorted<DEG>(c, d_pts, d_scalars, k, d_out, d_out_inf, st); break;
+        case msm::BUCKET_VM:
+        case msm::BUCKET_LANE: rc_ = msm_bucket<DEG>(c, d_pts, d_scalars, k, groups, d_out, d_out_inf, st); break;
+        default: rc_ = msm_vm<DEG>(c, d_pts, d_scalars, k, groups, d_out, d_out_inf, st);
         }
-        hipLaunchKernelGGL(blsgpu::k_msm_pip_horner<DEG>, dim3((unsigned)groups), dim3(64), (size_t)blsgpu::TEAM_BYTES, st, c->tabs, d_win,
-                           (uint32_t)blsgpu::PIP_W, (uint32_t)blsgpu::PIP_C, (uint32_t*)d_out, (uint8_t*)d_out_inf);
-        HIP_TRY(hipGetLastError());
-        return 0;
+        if (rc_ != 1) return rc_;
     }
-    // points per block: whole group when small, else chunks that give >= ~2k blocks
-    size_t per_pass = (size_t)MSM_WAVES * C::NP;
-    size_t chunk = k;
-    if (groups < 1024 && k > 4 * per_pass) {
-        size_t want_blocks = 2048 / groups + 1;
-        chunk = (k + want_blocks - 1) / want_blocks;
-        chunk = ((chunk + per_pass - 1) / per_pass) * per_pass;
-        if (chunk > k) chunk = k;
-    }
-    size_t bpg = (k + chunk - 1) / chunk;
-    size_t blocks = bpg * groups;
-    size_t need = blocks * 36 * DEG;
-    if (int rc_ = c->grow(B_MSM_PART, need * 4)) return rc_;
-    size_t lds = (size_t)MSM_WAVES * blsgpu::TEAM_BYTES;
-    hipLaunchKernelGGL(blsgpu::k_msm<DEG>, dim3((unsigned)blocks), dim3(MSM_WAVES * 64), lds, st, c->tabs,
-                       (const uint32_t*)d_pts, (const uint32_t*)d_scalars, (uint32_t)k, (uint32_t)chunk, (uint32_t)bpg,
-                       c->at<uint32_t>(B_MSM_PART));
-    HIP_TRY(hipGetLastError());
-    size_t fblocks = (groups + MSM_WAVES - 1) / MSM_WAVES;
-    hipLaunchKernelGGL(blsgpu::k_msm_finish<DEG>, dim3((unsigned)fblocks), dim3(MSM_WAVES * 64), lds, st, c->tabs,
-                       c->at<uint32_t>(B_MSM_PART), (uint32_t)bpg, (uint32_t)groups, (uint32_t*)d_out, (uint8_t*)d_out_inf);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return fail(-EINVAL, "msm: no route");          // (not reached: VM serves every call)
 }
 
 template <int DEG>
@@ -1066,10 +992,9 @@ int smul64_launch(blsgpu_ctx* c, const void* d_pts, size_t n_pts, const void* d_
     typedef blsgpu::SrtG<DEG> G;
     const size_t upw = 64 / G::LP, S = slice_len(c, blsgpu::SRT_LANES / G::LP);
     const size_t m0 = n < S ? n : S, units0 = (m0 + upw - 1) / upw * upw, np0 = d_idx ? n_pts : m0;
-    size_t off = 0;
-    auto take = [&](size_t words) { size_t o = off; off += (words + 3) & ~(size_t)3; return o; };
-    const size_t o_prep = take(np0 * blsgpu::L28_AFF * DEG), o_live = take((np0 + 3) / 4), o_tab = take(units0 * blsgpu::SMUL_T * G::PJ);
-    if (int rc = c->grow(B_SM64_WS, off * 4)) return rc;
+    ws::Layout l{4, 0};                                       // (words)
+    const size_t o_prep = l.take(np0 * blsgpu::L28_AFF * DEG), o_live = l.take((np0 + 3) / 4), o_tab = l.take(units0 * blsgpu::SMUL_T * G::PJ);
+    if (int rc = c->grow(B_SM64_WS, l.off * 4)) return rc;
     uint32_t* W = c->at<uint32_t>(B_SM64_WS);
     uint8_t* live = (uint8_t*)(W + o_live);
     if (d_idx) {
@@ -1287,12 +1212,11 @@ template <int DEG> constexpr size_t pscan_slice() { return PSCAN_RECORD_BYTES / 
 template <int DEG>
 int pscan_ws(blsgpu_ctx* c, size_t pts, PscanWs& w) {
     const size_t PJ = blsgpu::L28_PJ * DEG, chunks = pts ? (pts + blsgpu::pscan::CHUNK - 1) / blsgpu::pscan::CHUNK : 1;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_prep = take(pts * blsgpu::L28_AFF * DEG * 4), o_live = take(pts), o_kind = take(pts), o_ct = take(chunks * PJ * 4),
-                 o_cb = take(chunks * 4), o_s = take((pts + 1) * PJ * 4), o_cnt = take((pts + 1) * 4), o_carry = take(PJ * 4), o_cc = take(4);
+    ws::Layout l{256, 0};                                     // (bytes)
+    const size_t o_prep = l.take(pts * blsgpu::L28_AFF * DEG * 4), o_live = l.take(pts), o_kind = l.take(pts), o_ct = l.take(chunks * PJ * 4),
+                 o_cb = l.take(chunks * 4), o_s = l.take((pts + 1) * PJ * 4), o_cnt = l.take((pts + 1) * 4), o_carry = l.take(PJ * 4), o_cc = l.take(4);
     const BufId id = DEG == 1 ? B_PSCAN_G1 : B_PSCAN_G2;
-    if (int rc = c->grow(id, off)) return rc;
+    if (int rc = c->grow(id, l.off)) return rc;
     char* const W = c->at<char>(id);
     w = {(uint32_t*)(W + o_prep), (uint32_t*)(W + o_ct), (uint32_t*)(W + o_cb), (uint32_t*)(W + o_s), (uint32_t*)(W + o_cnt),
          (uint32_t*)(W + o_carry), (uint32_t*)(W + o_cc), (uint8_t*)(W + o_live), (uint8_t*)(W + o_kind)};

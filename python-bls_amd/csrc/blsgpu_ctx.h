@@ -86,7 +86,8 @@ constexpr BufInfo BUF_INFO[B_COUNT] = {
 
 }  // namespace
 
-struct blsgpu_ctx {
+// (the knobs of the G1 / G2 sums are msm::Knobs, msm_plan.h)
+struct blsgpu_ctx : msm::Knobs {
     int device = 0;
     blsgpu::VmTables tabs{};
     void* d_tables = nullptr;          // one allocation holding every table
@@ -110,10 +111,7 @@ struct blsgpu_ctx {
     size_t miller_wide_max = 1536;     // calls of at most this many pairs run the wide Miller loop (blsgpu_mlw.hip: one pair per two-wavefront workgroup, a product per lane); 0: never
     size_t mp_threshold = 4096;        // pairs from which k_miller_mp is used
     size_t mp3_threshold = (size_t)-1; // ... with three pairs per wavefront from here on, two below; -1: the measured schedule
-    size_t pip_threshold = 4096;       // points from which a single sum uses the bucket method
-    size_t pip_group_threshold = 48;   // points per sum from which a batch of sums does
     size_t pow2_max = 32768;           // fixed-exponent powers (hash to G2, decompression): up to this many values per launch two wavefronts per 64 values (k_pow2: 0.32 ms against 0.47); 0: never
-    bool msm_wide_tail = true;         // the sorted-bucket G1 sum: window sums and the Horner over the windows on the wide machine (blsgpu_msmw.hip k_msm_horner_wide<1, .>: 0.9 ms against the wavefront VM's 1.45); false: k_srt_windows + k_msm_pip_horner<1>
     size_t h2c_wide_max = 2048;        // up to this many messages the cofactor clearing runs one message per WAVEFRONT with a product per lane (blsgpu_h2cw.hip: the latency form); 0: never
     size_t h2c_reg_threshold = 8192;   // messages from which cofactor clearing runs in registers (one message per lane PAIR; measured: DESIGN.md 2c)
     size_t h2c_lane_threshold = 2048;  // messages from which the three encoding stages run one encoding per lane (k_h2c_sw0/1/2)
@@ -121,22 +119,8 @@ struct blsgpu_ctx {
     size_t h2c_jacobi_threshold = 16384;   // ... from this many messages (below, five parallel powers finish sooner than three serial symbol loops)
     size_t h2c_quad_max = 16384;       // ... on lane QUADS up to this many messages (k_h2c_clear_quads: half the depth while the chip is not full)
     bool test_ls_nomem = false;        // test hook (BLSGPU_TEST_LS_NOMEM=1): the line-stream workspace "cannot be allocated"
-    size_t test_slice_cap = 0;         // test hook (BLSGPU_TEST_SLICE_CAP=items): the host loops cut their work into slices of at most this many items (slice_len), so a test crosses every slice boundary with a few items; 0: the natural slice lengths
-    size_t msm_sort_threshold = 1;      // points from which one G1 sum with scalars uses sorted buckets (k_srt_*): since the tail runs on the wide machine (round 5) they win at every size -- 1 point 1.24 ms against 1.63, 8192 points 1.45 against 2.59 (profiles/r05_c5_window_bits.txt)
-    size_t msm_sort2_threshold = 1;     // the same for ONE G2 sum with scalars (round 5: BLS.aggregate_sigs(secure) as a multi-scalar sum)
-    size_t msm_plain_threshold = 2;     // points from which ONE plain sum (no scalars) runs on the register kernels (k_sum_chunks + folds; round 5) instead of the wavefront VM's k_msm
-    size_t smul_min_groups = 4096;      // sums per call from which a batch of SMALL sums with scalars (scalar multiplications: groups x 1 point) runs one group per lane / lane pair (k_smul, round 5) instead of the wavefront VM's k_msm
-    size_t smul_max_k = 8;              // ... for sums of up to this many points
-    static uint32_t msm_sort2_bits(size_t n) { return n >= 16384 ? 13 : (n >= 512 ? 11 : 9); }   // window bits of the G2 path by size (tools/g2_single_sum_probe.py, profiles/r05_g2_single_sum.txt)
     bool sigdiv_plain = true;           // blsgpu_sig_divide*: a call whose accepted quotients are all 1 sums the negated divisors (blsgpu_g2_range_sums' passes) and multiplies nothing; false: every call takes the scalars through blsgpu_g2_msm_ranges' kernels (the tests hold the two against each other)
-    size_t horner_np_threshold = 1024; // G2 sums per call from which the window Horner runs several sums per team
-    size_t horner_quads_threshold = 2; // G2 sums per call (lane-pair bucket kernel) from which the window Horner runs one sum per lane quad
     size_t wg256_max_waves = 4096;     // register kernels: launches of up to this many wavefronts go out as 256-thread workgroups (blsgpu_tu.h)
-    size_t msm_lane_threshold = 65536; // points from which the bucket sums run one (group, chunk, window) per lane
-    bool msm_lane_pairs = true;        // G2: every (group, chunk, window) on a lane PAIR (k_msm_lane2x) instead of one lane
-    size_t sort_bits = 0;              // window bits of the sorted-bucket G1 sum (BLSGPU_MSM_SORT_BITS); 0: the measured schedule (msm_sorted)
-    size_t sort2_bits = 0;             // ... of the G2 sum (BLSGPU_MSM_SORT2_BITS); 0: msm_sort2_bits(n)
-    size_t pip_chunks = 0;             // chunks one large bucket-method sum is cut into (BLSGPU_PIP_CHUNKS); 0: 256, or 3072 on the lane path
     // line-stream multi-pairing (blsgpu_ml.hip): used from ls_threshold pairs per call when every group has at least
     // ls_min_group pairs
     size_t ls_threshold = 2304;        // measured crossover (tools/ls_wide_sweep.py, round 5 with the point chains sixteen lanes per pair): 2048 pairs 1.70 (VM) vs 1.70 ms, 3072 pairs 1.93 vs 1.79; 5120 in round 4, 16 384 in round 3
@@ -309,15 +293,8 @@ struct Staging {
     }
 };
 
-// The slice length of a host loop: `natural` -- unless the test hook caps it (blsgpu_ctx::test_slice_cap), then at most the cap
-// rounded up to a whole number of `unit`s and never less than one unit.  Every workspace size that follows from a slice length
-// is derived from this value, so loop and buffer cannot disagree.
-size_t slice_len(const blsgpu_ctx* c, size_t natural, size_t unit = 1) {
-    if (!c->test_slice_cap) return natural;
-    const size_t cap = (c->test_slice_cap + unit - 1) / unit * unit;
-    const size_t s = natural < cap ? natural : cap;
-    return s < unit ? unit : s;
-}
+// The slice length of a host loop (msm_plan.h: `natural`, unless the test hook caps it)
+size_t slice_len(const blsgpu_ctx* c, size_t natural, size_t unit = 1) { return msm::slice_len(*c, natural, unit); }
 
 // body(lo, m) over [0, n) in runs of at most `step` items
 template <class F>
