@@ -65,11 +65,12 @@ __device__ __forceinline__ void cyc_sqr(int32_t* __restrict__ fre, int32_t* __re
         a2i[j] = ev ? ys : x2i;
         b2i[j] = ev ? ys : (l1 ? yd : yr[j]);
     }
-    // column bound (units of 2^56, digits of f normalised): real 2 + 1 + 2, imaginary 2 + 4 + 2 = 8 on even lanes; 2 + 4 on lane 1
+    // column bound (units of 2^56, digits of f normalised), term by term: real 2 + 1 + 2, imaginary 2 + 4 + 2 = 8 on even lanes; 2 + 4 on
+    // lane 1 (the terms share operands: 4 is the most their sum reaches, tests/fx_vectors.py)
     int32_t tr[NL], ti[NL];
     bls28::fp28_dot3(tr, a1r, b1r, a2r, b2r, a3, yi);
     bls28::fp28_dot3(ti, x2r, b1i, a2i, b2i, a3, yi);
-    int32_t sr[NL], si[NL];                                    // 3 t -+ 2 f_k: a value in (-10 q, 14 q) ...
+    int32_t sr[NL], si[NL];                                    // 3 t -+ 2 f_k: a value in (-11 q, 14 q) ...
 #pragma unroll
     for (int j = 0; j < NL; j++) {
         const int32_t dr = fre[j] + fre[j], di = fim[j] + fim[j];
