@@ -5,13 +5,18 @@ Layout consumed by csrc/blsgpu_kernels.hip:
       sequence of rounds the kernel walks: {data_off (u16 units), meta},
       meta = kind (0 MUL, 1 LIN, 2 INV, 3 SGN; in the light multi-pair programs 2 SAVE, 3 RESTORE of
              the 12-slot window at slot K) | K << 8   (K = micro-ops per lane, LIN)
+             | levels << 16 (merge steps across adjacent lanes, 0 .. 2) | MN << 18 (the first MN micro-ops are the negative terms)
   BLSVM_SEG_FLAT: the same for single segments the kernels call directly
       (BLSVM_SEGF_<NAME>_OFF / _LEN index it)
   BLSVM_DATA[] u16, per round a record per lane:
      MUL / INV / SGN: {a, b, dst, 0}                (4 u16)
-     LIN      : {dst, uop_0 .. uop_{K-1}, pad..}    (roundup4(K + 1) u16)
+     LIN      : {dst, merge flags, uop_0 .. uop_{K-1}, pad..}    (kpad(K) = roundup4(K + 2) u16)
   slot reference  = slot_index * 3 (byte offset / 16 inside the team scratchpad)
-  micro-op        = neg << 15 | coef << 10 | slot_index:  acc += coef * (neg ? ~slot : slot)
+  micro-op        = coef << 10 | slot_index (bit 15 is 0: the kernel ignores it and tablesim asserts it): acc += coef * slot.
+                    No per-term complement: a round works in two phases split at MN -- micro-ops 0 .. MN-1 sum the negative terms
+                    as plain products, every lane flips the sign of its accumulators (acc <- BIAS - acc), micro-ops MN .. K-1 add
+                    the positive terms (plan_lin_round)
+  merge flags     = bit 14: add the odd neighbour at level 1, bit 15: add two lanes up at level 2
   padding = 0 (coef 0); inactive lane: dst = 0xFFFF
   BLSVM_CONSTS: Montgomery contents of the constant slots, 12 LE u32 limbs each
 """

@@ -537,6 +537,25 @@ def build_linear():
 C_FROM_VM, C_TO_VM, C_R2 = (1 << 400) % Q, (1 << 384) % Q, R * R % Q
 
 
+def vm_mul28(A, B):
+    """the word model of fp28.h vm_mul28 (the MUL round of the wavefront VM): two integers below 2^384 standing for 12 words each
+    -> the integer of the 12 result words, through the column arithmetic of model_dot on A shifted left by 8 bits"""
+    assert 0 <= A < 1 << 384 and 0 <= B < 1 << 384 and A * B < 9 * Q * Q
+    D = from_limbs(dot([(to_limbs(A << 8), to_limbs(B))]))
+    assert 0 <= D < 2 * Q and (D - A * B * pow(1 << 384, -1, Q)) % Q == 0
+    return D
+
+
+QNEG_R = (-pow(Q, -1, R)) % R
+
+
+def vm_mul28_closed(A, B):
+    """the same words without the columns: with non-negative digits model_dot's m is the one m < 2^392 that makes
+    (A 2^8 B + m q) divisible by 2^392 (tests/test_vm_vectors_model.py holds the two against each other)"""
+    t = (A << 8) * B
+    return (t + ((t * QNEG_R) % R) * Q) >> (W * L)
+
+
 def build_boundaries():
     rnd = _seed("boundaries")
     top384 = (1 << 384) - 1
@@ -588,12 +607,7 @@ def build_boundaries():
     mk_to("b_to_raw", 45, RINV)                        # x R -> x, canonical
 
     def vm_ref(w):
-        A, B = from_words(w[:12]), from_words(w[12:])
-        assert A * B < 9 * Q * Q
-        r = dot([(to_limbs(A << 8), to_limbs(B))])
-        D = from_limbs(r)
-        assert 0 <= D < 2 * Q and (D - A * B * pow(1 << 384, -1, Q)) % Q == 0
-        return words12(D)
+        return words12(vm_mul28(from_words(w[:12]), from_words(w[12:])))
 
     def vm_check(w, out):
         A, B, D = from_words(w[:12]), from_words(w[12:]), from_words(out)

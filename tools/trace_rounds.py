@@ -1,61 +1,55 @@
-"""Diagnostic (needs csrc/libblsgpu_stamps.so): run the first n rounds of a flat VM program
-on the GPU from a given scratchpad image and compare every slot with vmgen/tablesim.py,
-bisecting to the first round whose result differs.  Example: the G1 decompression program."""
-import ctypes, os, sys
+"""Diagnostic: run the first n rounds of any program of vmgen.emit.build_tables() on the GPU from a seeded scratchpad image, through
+the test-only library csrc/libblsgpu_vmcheck.so (the ordinary build: no stamps library needed), and compare every slot with
+vmgen/tablesim.py, bisecting to the first round whose result differs and printing that round's lane records.
+    python3 tools/trace_rounds.py            lists the programs
+    python3 tools/trace_rounds.py mscript    (or mpscript, mp2, fscript, slow, h2, or a directly called segment such as d1_a, g2_add)
+tests/test_gpu_vm.py asserts the same comparison at every segment boundary."""
+import os
+import sys
+
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "python-bls_amd"))
-os.environ["BLSGPU_LIBRARY"] = os.path.join(ROOT, "python-bls_amd", "csrc", "libblsgpu_stamps.so")
-from bls_py import _native, hostmath as H
-from vmgen import emit, tablesim, programs as P, h2c_programs as HP, sim
-Q = sim.Q
-e = _native.Engine(0)
-e.lib.blsgpu_debug_run.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint32)]
-tb = emit.build_tables()
-sr, data = tb["seg_rounds"], tb["data"]
-which = {"miller": (0, "mscript"), "mp": (1, "mpscript"), "fexp": (2, "fscript")}
-prog = sys.argv[1] if len(sys.argv) > 1 else "d1"
-if prog in ("d1", "d2", "h1", "h2"):
-    segs, lay, script = tb[prog]
-    wid = {"h1": 3, "h2": 4, "d1": 5, "d2": 6}[prog]
-else:
-    wid, key = which[prog]
-    script = tb[key]
-rounds = [r for n in script for r in sr[n]]
-consts = HP.h2c_scratch_consts()
-nslots = 900
-g1 = open(os.path.join(ROOT, "tests/golden/pairs_seed1_g1.bin"), "rb").read()
-img0 = [0] * nslots
-for i, c in enumerate(consts):
-    img0[i] = c
-if prog == "d1":
-    for k in range(lay.NE):
-        enc = H.g1_compress(H.g1_from_abi(g1[96 * k:96 * (k + 1)]))
-        img0[lay.X + k] = int.from_bytes(bytes([enc[0] & 0x1f]) + enc[1:], "big")
-        img0[lay.BIG + k] = sim.to_m(1) if enc[0] & 0x80 else 0
-else:
-    import random
-    rng = random.Random(1)
-    for s in range(len(consts), nslots):
-        img0[s] = rng.randrange(Q)
+sys.path[:0] = [os.path.join(ROOT, "python-bls_amd"), os.path.join(ROOT, "tests")]
+import checklib                                           # noqa: E402
+import vm_vectors as V                                    # noqa: E402
+from vmgen import emit                                    # noqa: E402
+
+progs, data, consts = V.production()
+by_name = {name: (op, rounds) for name, op, rounds, cuts in progs}
+if len(sys.argv) < 2 or sys.argv[1] not in by_name:
+    print("programs:", " ".join(by_name))
+    sys.exit(0 if len(sys.argv) < 2 else 2)
+prog = sys.argv[1]
+op, rounds = by_name[prog]
+img = V.production_image(prog, op, rounds, data, consts)
+nslots = len(img)
+lib = checklib.load("libblsgpu_vmcheck", "blsgpu_vm_check")
+t16 = np.array(list(data) + [0] * (len(data) & 1), dtype=np.uint32)
+table = t16[0::2] | (t16[1::2] << 16)
+image = np.frombuffer(b"".join(v.to_bytes(48, "little") for v in img), dtype=np.uint32)
+
 
 def gpu(n):
-    buf = (ctypes.c_uint32 * (nslots * 12))()
-    for s, v in enumerate(img0):
-        for j in range(12):
-            buf[s * 12 + j] = (v >> (32 * j)) & 0xFFFFFFFF
-    rc = e.lib.blsgpu_debug_run(e.h, wid, n, nslots, buf)
-    assert rc == 0, e.lib.blsgpu_last_error()
-    return [sum(buf[s * 12 + j] << (32 * j) for j in range(12)) % Q for s in range(nslots)]
+    if n == 0:
+        return [v % V.Q for v in img]
+    hdr = np.array([n, nslots, len(data), 0, 0, 1, 0, 0] + [x for r in rounds[:n] for x in r], dtype=np.uint32)
+    w, out = np.concatenate([hdr, table, image]), np.zeros(nslots * 12 + V.TRAILER, dtype=np.uint32)
+    rc = lib(V.OPS[op], w.ctypes.data, w.size, 1, out.ctypes.data, out.size)
+    assert rc == 0, "blsgpu_vm_check returned %d" % rc
+    b = out.tobytes()
+    return [int.from_bytes(b[48 * s:48 * s + 48], "little") % V.Q for s in range(nslots)]
+
 
 def cpu(n):
-    m = tablesim.TableMachine(consts, nslots, data, P.C_K1)
-    m.team = list(img0)
-    m.run(rounds[:n])
-    return [v % Q for v in m.team]
+    return V.tablesim_run(data, img, rounds[:n], op in V.LIGHT_OPS)[0]
+
 
 def same(n):
     return gpu(n) == cpu(n)
-print("program", prog, "rounds", len(rounds), "full run matches:", same(len(rounds)))
+
+
+print("program", prog, "under", op, "rounds", len(rounds), "slots", nslots, "full run matches:", same(len(rounds)))
 lo, hi = 0, len(rounds)
 if not same(hi):
     while hi - lo > 1:
@@ -67,7 +61,7 @@ if not same(hi):
     off, meta = rounds[hi - 1]
     a, b = gpu(hi), cpu(hi)
     bad = [s for s in range(nslots) if a[s] != b[s]]
-    print("first differing round: #%d kind %d K %d levels %d; slots %s" % (hi - 1, meta & 3, (meta >> 8) & 255, (meta >> 16) & 3, bad[:12]))
+    print("first differing round: #%d kind %d K %d levels %d MN %d; slots %s" % (hi - 1, meta & 3, (meta >> 8) & 255, (meta >> 16) & 3, (meta >> 18) & 255, bad[:12]))
     rl = emit.kpad((meta >> 8) & 255) if meta & 3 == 1 else 4
     for lane in range(64):
         rec = data[off + rl * lane: off + rl * (lane + 1)]
