@@ -1,5 +1,5 @@
 // check_runner.h -- TEST-ONLY: the host side the check libraries share (blsgpu_fp28_check.hip, blsgpu_fq32_check.hip,
-// blsgpu_wide_check.hip, blsgpu_ml_check.hip, blsgpu_fr_check.hip, blsgpu_curve_check.hip, blsgpu_fx_check.hip, blsgpu_vm_check.hip).  Not part of
+// blsgpu_wide_check.hip, blsgpu_ml_check.hip, blsgpu_fr_check.hip, blsgpu_curve_check.hip, blsgpu_fx_check.hip, blsgpu_vm_check.hip, blsgpu_h2c_check.hip).  Not part of
 // libblsgpu.so, not an ABI.
 //
 // Every library exports ONE function, int blsgpu_<layer>_check(op, in, words_in, n, out, words_out), over 32-bit words.
@@ -11,7 +11,8 @@
 //   -3    a guard record was written: the device output lies between two records of GUARD bytes of 0xAA, and a lane stored
 //         outside its own record
 //   -4    a record the library refuses before launching (an address outside the value file, a position outside 0 .. 5, a loop count
-//         or table index that is too large or differs between the items of a call, a VM program that vm_check_plan.h refuses)
+//         or table index that is too large or differs between the items of a call, a VM program that vm_check_plan.h refuses, an image slot
+//         outside the stage image)
 // and launches nothing unless it returns 0, -3 or a HIP error.
 //
 // Each library names its ops ONCE, in an X-macro LIB_OPS(X) of entries X(NAME, code); the enum, the exported switch and the

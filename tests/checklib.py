@@ -1,7 +1,7 @@
-"""The Python side the eight check-library GPU tests share (test_gpu_fp28, test_gpu_fq32, test_gpu_wide, test_gpu_ml_steps,
-test_gpu_fr, test_gpu_curve, test_gpu_fx, test_gpu_vm): loading a library, one call with its return-code message, the per-lane comparison loop of the
+"""The Python side the nine check-library GPU tests share (test_gpu_fp28, test_gpu_fq32, test_gpu_wide, test_gpu_ml_steps,
+test_gpu_fr, test_gpu_curve, test_gpu_fx, test_gpu_vm, test_gpu_h2c_check): loading a library, one call with its return-code message, the per-lane comparison loop of the
 lane-layout libraries and the per-set comparison loop of wide, ml, curve and fx (test_gpu_vm uploads whole programs and has its own
-loop over teams).  The return codes are csrc/check_runner.h's."""
+loop over teams, test_gpu_h2c_check its own loop over more sets than one call holds).  The return codes are csrc/check_runner.h's."""
 import ctypes
 import os
 
