@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -45,39 +46,35 @@
 #if BLSGPU_EMIT(BLSGPU_TU_HOST)
 #include "bisect_plan.h"
 #include "msm_plan.h"
+#include "pairing_plan.h"
 #include "blsgpu_ctx.h"
 
+// Which kernels a pairing call runs, its partials, chunks, levels, slices and buffer sizes are pairing_plan.h (host-only: tested
+// without a GPU); the pairing functions below grow the buffers to a plan's totals and launch what it says.
 namespace {
 constexpr int MILLER_WAVES = 4;        // teams (pairings) per workgroup in k_miller
 constexpr int REDUCE_WAVES = 8;        // teams per workgroup in k_reduce
 constexpr size_t BATCH_TREE_MIN_GROUP = 24;   // batches of groups at least this long use the per-group product tree
 constexpr int REDUCE_PER_BLOCK = 64;   // partials folded by one k_reduce block
-constexpr size_t LS_MAX_PAIRS = (size_t)1 << 20;       // pairs per line-stream launch sequence: 24 GB of line records
-
+constexpr size_t LS_MERGE_FAN = 8;     // partial products a merge level of the line-stream stage multiplies per output
+constexpr unsigned SLOW_GRID = 3072;   // k_miller_slow: three wavefronts per SIMD (166 VGPRs, 10 KB of LDS each)
+constexpr pairing::Consts PAIRING_CONSTS = {blsgpu::ml::LINES, blsgpu::ml::LINE_DW, blsgpu::ml::DENSE_DW, blsgpu::ml::TEAMS,
+                                            blsgpu::ml::sp::SLAB_BYTES_PER_LANE, BLSVM_MP_G, blsgpu::TEAM_BYTES, blsgpu::MP_TEAM_BYTES,
+                                            blsgpu::SLOW_TEAM_BYTES, BLS28_FEXP_NSLOTS, MILLER_WAVES, REDUCE_WAVES, REDUCE_PER_BLOCK,
+                                            BATCH_TREE_MIN_GROUP, LS_MERGE_FAN, SLOW_GRID};
+static_assert(pairing::same(PAIRING_CONSTS, pairing::GFX950), "pairing_plan.h: GFX950 (the host test's values) differs from the kernel files");
+static_assert(pairing::PARTIAL_BYTES == BLSGPU_FQ12_BYTES && BLSGPU_G1_BYTES == 96 && BLSGPU_G2_BYTES == 192, "pairing_plan.h: slice_offsets");
+// the slice lengths of the pairing path: groups per call of the grouped kernels (they ride on gridDim.y), pairs per line-stream
+// launch sequence (24 GB of line records), pairs per slice of blsgpu_miller_loop_batch (6 GB)
+pairing::Limits pairing_limits(const blsgpu_ctx* c) { return {slice_len(c, 32768), slice_len(c, (size_t)1 << 20), slice_len(c, 262144)}; }
+int refuse(pairing::Refusal r) { return fail(pairing::refusal_code(r), pairing::refusal_text(r)); }
 }  // namespace
 
-// Batches of at least mp_threshold pairs use the multi-pair program (k_miller_mp:
-// fewer instructions per pairing, longer per-batch latency); smaller ones the
-// one-pair-per-wavefront program (k_miller).  Default 4096; per context via
-// blsgpu_ctx_set_mp_threshold, or BLSGPU_MP_THRESHOLD in the environment.
-static bool use_mp(const blsgpu_ctx* c, size_t n) { return n >= c->mp_threshold; }
-// Two or three pairs per wavefront?  Three costs fewest instructions per pairing (large batches), two fills the
-// chip sooner: 4096 teams are one "round" of the chip, so teams of two win while the batch is a little under a
-// multiple of 8192 pairs and teams of three where it is a little under a multiple of 12288 -- measured crossovers
-// (tools/mp_threshold_sweep.py, profiles/r02_schedule_experiments.txt); from ~20 000 pairs on blocks flow
-// continuously and three wins by 8 %.
-static bool use_mp2(const blsgpu_ctx* c, size_t n) {
-    if (c->mp3_threshold != (size_t)-1) return n < c->mp3_threshold;
-    return n <= 8704 || (n > 9728 && n <= 11264) || (n > 14336 && n <= 18432);
-}
-// Partials a call of `pairs` pairs takes on the wavefront-VM kernels: one per Miller block -- at most a team of two pairs
-// (k_miller_mp<2>) -- plus the levels of the reduce chain.
-static size_t pairs_partials(size_t pairs) { return (pairs + 1) / 2 + (pairs + MILLER_WAVES - 1) / MILLER_WAVES + 1; }
 // Room for `partials` partials in each partial buffer, and one work-list entry per Miller block at most (+ the counter).
 static int ensure_partials(blsgpu_ctx* c, size_t partials) {
     for (BufId b : {B_PART0, B_PART1})
         if (int rc = c->grow(b, partials * BLSGPU_FQ12_BYTES)) return rc;
-    return c->grow(B_DEGEN, (c->part_cap() + 2) * sizeof(uint32_t));
+    return c->grow(B_DEGEN, pairing::degen_bytes(c->part_cap()));
 }
 
 // fixed-exponent powers on a stage image (blsgpu_h2c.hip)
@@ -1891,7 +1888,7 @@ BLSGPU_EXPORT int blsgpu_ctx_create(int device, blsgpu_ctx** out) {
     (void)hipFuncSetAttribute((const void*)blsgpu::k_msm<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * blsgpu::TEAM_BYTES);
     (void)hipFuncSetAttribute((const void*)blsgpu::k_msm_finish<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * blsgpu::TEAM_BYTES);
     (void)hipFuncSetAttribute((const void*)blsgpu::k_msm_finish<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * blsgpu::TEAM_BYTES);
-    int rc = ensure_partials(c, pairs_partials(4096));
+    int rc = ensure_partials(c, pairing::pairs_partials(PAIRING_CONSTS, 4096));
     if (!rc && hipEventCreateWithFlags(&c->last_event, hipEventDisableTiming) != hipSuccess) rc = fail(-EIO, "hipEventCreate failed");
     if (rc) {
         blsgpu_ctx_destroy(c);
@@ -2063,20 +2060,13 @@ BLSGPU_EXPORT int blsgpu_ctx_set_mp3_threshold(blsgpu_ctx* c, size_t pairs) {
 BLSGPU_EXPORT int blsgpu_ctx_reserve(blsgpu_ctx* c, size_t max_pairs) {
     if (!c) return fail(-EINVAL, "ctx is NULL");
     HIP_TRY(hipSetDevice(c->device));
-    if (int rc = ensure_partials(c, pairs_partials(max_pairs))) return rc;
-    if (max_pairs >= c->ls_threshold) {
-        // the line-stream stage's buffers as well (a call of that size takes them): line records of one slice, the
-        // flags and the work list, and dense partial products for the usual chunking (ls_teams accumulators plus 68 per
-        // group of at least ls_min_group pairs); a call that needs more grows them itself
-        const size_t n = max_pairs < LS_MAX_PAIRS ? max_pairs : LS_MAX_PAIRS;
-        const size_t teams = c->ls_teams + blsgpu::ml::LINES * (n / (c->ls_min_group ? c->ls_min_group : 1) + 1);
-        if (c->grow(B_LINES, n * blsgpu::ml::LINES * blsgpu::ml::LINE_DW * 4) ||
-            c->grow(B_BAD, n) || c->grow(B_DEGEN, (n + 2) * 4) ||
-            c->grow(B_LSP0, teams * blsgpu::ml::DENSE_DW * 4) ||
-            c->grow(B_LSP1, (teams / 8 + blsgpu::ml::LINES) * blsgpu::ml::DENSE_DW * 4)) {
-            (void)hipGetLastError();
-            return fail(-ENOMEM, "no memory for the line-stream workspace (calls of that size will use the wavefront-VM kernels)");
-        }
+    const pairing::ReservePlan p = pairing::plan_reserve(*c, PAIRING_CONSTS, pairing_limits(c), max_pairs);
+    if (int rc = ensure_partials(c, p.partials)) return rc;
+    // the line-stream stage's buffers as well (a call of that size takes them); a call that needs more grows them itself
+    if (p.ls && (c->grow(B_LINES, p.lines_bytes) || c->grow(B_BAD, p.bad_bytes) || c->grow(B_DEGEN, p.degen_bytes) ||
+                 c->grow(B_LSP0, p.lsp0_bytes) || c->grow(B_LSP1, p.lsp1_bytes))) {
+        (void)hipGetLastError();
+        return fail(-ENOMEM, "no memory for the line-stream workspace (calls of that size will use the wavefront-VM kernels)");
     }
     return 0;
 }
@@ -2106,132 +2096,97 @@ BLSGPU_EXPORT int blsgpu_ctx_trim(blsgpu_ctx* c) {
 }
 
 // `groups` results at once: product of the m partials of each group (partial i of group g at
-// d_in[(i * istride + g * gstride) * 144]) and its final exponentiation, six lanes per result (blsgpu_fexp.hip).
-static bool use_fexp_team(const blsgpu_ctx* c, size_t m, size_t groups) { return groups >= c->fexp_team_threshold && m <= 64; }
-static int launch_fexp_team(blsgpu_ctx* c, const uint32_t* d_in, size_t m, size_t istride, size_t gstride, size_t groups, void* d_out_bytes,
-                            hipStream_t st) {
+// d_in[(i * istride + g * gstride) * 144]) and its final exponentiation in registers, in the form pairing::fexp_form chose:
+// six lanes per result (blsgpu_fexp.hip), or -- fewer results than the team form wants -- one result per wavefront
+// (blsgpu_fexpw.hip), the latency form.
+static int launch_fexp(blsgpu_ctx* c, const pairing::FexpForm& f, const uint32_t* d_in, size_t m, size_t istride, size_t gstride, size_t groups,
+                       void* d_out_bytes, hipStream_t st) {
     using namespace blsgpu;
-    const WaveShape ws = wave_shape(c, (groups + ml::TEAMS - 1) / ml::TEAMS);
-    const size_t waves = (size_t)ws.blocks * (ws.threads / 64);                 // every launched wavefront owns rows of the workspace
-    if (int rc = c->grow(B_FEXP_WS, waves * (ml::TEAMS + 1) * BLS28_FEXP_NSLOTS * ml::DENSE_DW * 4)) return rc;
-    KernelTimer kt(c, st, 2);
-    hipLaunchKernelGGL(fx::k_fexp_team, dim3(ws.blocks), dim3(ws.threads), 0, st, d_in, (uint32_t)m, (uint32_t)istride, (uint32_t)gstride,
-                       (uint32_t)groups, c->at<int32_t>(B_FEXP_WS), (uint32_t*)d_out_bytes, (uint32_t*)c->d_fexp_dbg);
+    if (f.kind == pairing::FEXP_TEAM) {
+        const WaveShape ws = wave_shape(c, f.waves);
+        // every launched wavefront owns rows of the workspace
+        if (int rc = c->grow(B_FEXP_WS, (size_t)ws.blocks * (ws.threads / 64) * f.ws_bytes_per_wave)) return rc;
+        KernelTimer kt(c, st, 2);
+        hipLaunchKernelGGL(fx::k_fexp_team, dim3(ws.blocks), dim3(ws.threads), 0, st, d_in, (uint32_t)m, (uint32_t)istride, (uint32_t)gstride,
+                           (uint32_t)groups, c->at<int32_t>(B_FEXP_WS), (uint32_t*)d_out_bytes, (uint32_t*)c->d_fexp_dbg);
+    } else {
+        KernelTimer kt(c, st, 2);
+        hipLaunchKernelGGL(fxw::k_fexp_wide, dim3((unsigned)groups), dim3(64), 0, st, d_in, (uint32_t)m, (uint32_t)istride,
+                           (uint32_t)gstride, (uint32_t*)d_out_bytes, (unsigned long long*)c->d_fexpw_stamps);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+// ... in that form, or where there is none on the VM (k_final_groups: one wavefront per result, m partials side by side);
+// timed: the VM's launch is timed too
+static int launch_final(blsgpu_ctx* c, const pairing::FexpForm& f, const uint32_t* d_in, size_t m, size_t istride, size_t gstride, size_t groups,
+                        void* d_out_bytes, hipStream_t st, bool timed = true) {
+    if (f.kind != pairing::FEXP_NONE) return launch_fexp(c, f, d_in, m, istride, gstride, groups, d_out_bytes, st);
+    {
+        std::optional<KernelTimer> kt;
+        if (timed) kt.emplace(c, st, 2);
+        hipLaunchKernelGGL(blsgpu::k_final_groups, dim3(pairing::final_blocks(PAIRING_CONSTS, groups)), dim3(REDUCE_WAVES * 64),
+                           (size_t)REDUCE_WAVES * blsgpu::TEAM_BYTES, st, c->tabs, d_in, (uint32_t)m, (uint32_t)groups, (uint32_t*)d_out_bytes);
+    }
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-// Fewer results than the team form wants: one result per wavefront (blsgpu_fexpw.hip), the latency form.
-static bool use_fexp_wide(const blsgpu_ctx* c, size_t m, size_t groups) {
-    return c->fexp_wide && groups < c->fexp_team_threshold && m >= 1 && m <= c->fexp_wide_max_partials && groups <= 0x7FFFFFFFull;
-}
-static int launch_fexp_wide(blsgpu_ctx* c, const uint32_t* d_in, size_t m, size_t istride, size_t gstride, size_t groups, void* d_out_bytes,
-                            hipStream_t st) {
-    KernelTimer kt(c, st, 2);
-    hipLaunchKernelGGL(blsgpu::fxw::k_fexp_wide, dim3((unsigned)groups), dim3(64), 0, st, d_in, (uint32_t)m, (uint32_t)istride,
-                       (uint32_t)gstride, (uint32_t*)d_out_bytes, (unsigned long long*)c->d_fexpw_stamps);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-// the register forms of the final exponentiation: batches six lanes per result, a few results one wavefront each
-static bool use_fexp_reg(const blsgpu_ctx* c, size_t m, size_t groups) { return use_fexp_team(c, m, groups) || use_fexp_wide(c, m, groups); }
-static int launch_fexp_reg(blsgpu_ctx* c, const uint32_t* d_in, size_t m, size_t istride, size_t gstride, size_t groups, void* d_out_bytes,
-                           hipStream_t st) {
-    return use_fexp_team(c, m, groups) ? launch_fexp_team(c, d_in, m, istride, gstride, groups, d_out_bytes, st)
-                                       : launch_fexp_wide(c, d_in, m, istride, gstride, groups, d_out_bytes, st);
-}
-
-// For each of `groups` groups fold its m partials down to one; the last launch
+// For each of `groups` groups fold its m partials down to one (pairing::plan_reduce); the last launch
 // optionally applies the final exponentiation and writes 576 bytes per group to
 // d_out_bytes, otherwise one partial per group to d_out_partial.  Partial i of
 // group g is read from d_in[(i * istride + g * gstride) * 144].
 static int reduce_chain(blsgpu_ctx* c, const uint32_t* d_in, size_t m, size_t groups, size_t istride, size_t gstride,
                         bool do_final, uint32_t* d_out_partial, void* d_out_bytes, hipStream_t st) {
+    const pairing::ReducePlan p = pairing::plan_reduce(*c, PAIRING_CONSTS, m, groups, istride, gstride, do_final, d_in == c->part(0), c->part_cap());
+    if (p.refusal) return refuse(p.refusal);
+    const uint32_t* const bufs[] = {d_in, c->part(0), c->part(1), d_out_partial};
     const uint32_t* src = d_in;
-    int pp = (d_in == c->part(0)) ? 1 : 0;
-    size_t lds = (size_t)REDUCE_WAVES * blsgpu::TEAM_BYTES;
-    if (groups > 65535) return fail(-EINVAL, "too many groups");
-    while (true) {
-        // the final exponentiation in registers as soon as few enough partials per group are left
-        if (do_final && use_fexp_reg(c, m, groups)) return launch_fexp_reg(c, src, m, istride, gstride, groups, d_out_bytes, st);
-        size_t blocks = (m + REDUCE_PER_BLOCK - 1) / REDUCE_PER_BLOCK;
-        if (blocks == 0) blocks = 1;
-        bool last = blocks == 1;
-        // the level that leaves one partial per group hands it to the register forms (one more launch, but the VM's
-        // final exponentiation inside k_reduce is 1.25 ms of one wavefront)
-        const bool hand_over = last && do_final && use_fexp_reg(c, 1, groups) && groups <= c->part_cap();
-        uint32_t* dst = (last && !hand_over) ? d_out_partial : c->part(pp);
-        if (!last && blocks * groups > c->part_cap()) return fail(-ENOMEM, "workspace too small; call blsgpu_ctx_reserve");
+    for (const pairing::ReduceLevel* l = p.level; l != p.level + p.nlevels; l++) {
+        uint32_t* dst = (uint32_t*)bufs[l->dst];
         {
-            KernelTimer kt(c, st, (last && do_final && !hand_over) ? 2 : 1);
-            hipLaunchKernelGGL(blsgpu::k_reduce, dim3((unsigned)blocks, (unsigned)groups), dim3(REDUCE_WAVES * 64), lds, st, c->tabs,
-                               src, (uint32_t)m, (uint32_t)REDUCE_PER_BLOCK, (uint32_t)istride, (uint32_t)gstride, dst,
-                               (uint32_t)(last && do_final && !hand_over ? 1 : 0), (uint32_t*)d_out_bytes);
+            KernelTimer kt(c, st, l->timer);
+            hipLaunchKernelGGL(blsgpu::k_reduce, dim3((unsigned)l->blocks, (unsigned)groups), dim3(REDUCE_WAVES * 64), p.lds, st, c->tabs,
+                               src, (uint32_t)l->m, (uint32_t)REDUCE_PER_BLOCK, (uint32_t)l->istride, (uint32_t)l->gstride, dst,
+                               (uint32_t)l->final_flag, (uint32_t*)d_out_bytes);
         }
         HIP_TRY(hipGetLastError());
-        if (hand_over) return launch_fexp_reg(c, dst, 1, 1, 1, groups, d_out_bytes, st);
-        if (last) break;
         src = dst;
-        m = blocks;
-        istride = 1;
-        gstride = blocks;
-        pp ^= 1;
     }
-    return 0;
+    if (p.end == pairing::R_REDUCE) return 0;
+    return launch_fexp(c, p.fexp, bufs[p.fsrc], p.fm, p.fistride, p.fgstride, groups, d_out_bytes, st);
 }
 
-// Miller loops of `groups` runs of gsz pairs; returns the partials per group (bpg).
-// Then k_miller_slow: it rewrites the partials of the blocks that met a degenerate pair with the
-// reference-faithful program (normally none: every wavefront leaves at once).
-constexpr unsigned SLOW_GRID = 3072;           // three wavefronts per SIMD (166 VGPRs, 10 KB of LDS each)
-// Which Miller kernel runs `groups` runs of gsz pairs, hence how many partials come out per group (bpg).
-// team: 0 = choose by batch size; 2 / 3 = k_miller_mp with that many pairs per wavefront (groups of two or three pairs: one team
-// per group, the group's product comes out of the Miller kernel)
-struct MillerPlan { bool wide, mp, mp2; size_t per_block, bpg; };
-static MillerPlan miller_plan(const blsgpu_ctx* c, size_t gsz, size_t groups, bool one_per_block, int team = 0) {
-    MillerPlan p;
-    // a few pairs: one pair per two-wavefront workgroup with a product per lane (blsgpu_mlw.hip), every pair its own partial
-    // (where the one-pair-per-wavefront k_miller ran: calls below the throughput kernels' threshold)
-    p.wide = !team && gsz * groups <= c->miller_wide_max && !use_mp(c, gsz * groups);
-    p.mp = team ? true : (!p.wide && !one_per_block && use_mp(c, gsz * groups));
-    p.mp2 = team ? team == 2 : (p.mp && use_mp2(c, gsz * groups));   // a few thousand pairs: teams of two fill the chip
-    p.per_block = (one_per_block || p.wide) ? 1 : (p.mp ? (p.mp2 ? (size_t)2 : (size_t)BLSVM_MP_G) : (size_t)MILLER_WAVES);
-    p.bpg = (gsz + p.per_block - 1) / p.per_block;
-    return p;
-}
-// The caller has sized the workspace for miller_plan(...).bpg x groups partials (ensure_partials) BEFORE it took d_partials:
+// Miller loops of `groups` runs of gsz pairs on the kernel pairing::plan_miller chose; *bpg_out: the partials per group.
+// Then the blocks that met a degenerate pair once more with the reference-faithful program (normally none: every wavefront
+// leaves at once).
+// The caller has sized the workspace for plan_miller(...).bpg x groups partials (ensure_partials) BEFORE it took d_partials:
 // nothing grows here -- a grown buffer would leave that pointer on a retired one -- and a launch that does not fit fails.
 static int launch_miller(blsgpu_ctx* c, const void* d_g1, const void* d_g2, const void* d_inf, size_t gsz, size_t groups, bool one_per_block,
                          uint32_t* d_partials, hipStream_t st, size_t* bpg_out, int team = 0) {
-    const auto [wide, mp, mp2, per_block, bpg] = miller_plan(c, gsz, groups, one_per_block, team);
-    *bpg_out = bpg;
-    if (bpg * groups > 0x7FFFFFFFull) return fail(-EINVAL, "batch too large");
-    if ((d_partials == c->part(0) || d_partials == c->part(1)) && bpg * groups > c->part_cap())
-        return fail(-ENOMEM, "partial buffer too small for the Miller kernel's blocks");
-    if (bpg * groups + 2 > c->degen_cap()) return fail(-ENOMEM, "work list too small");
+    using namespace pairing;
+    const MillerPlan p = plan_miller(*c, PAIRING_CONSTS, gsz, groups, one_per_block, team, d_partials == c->part(0) || d_partials == c->part(1),
+                                     c->part_cap(), c->degen_cap());
+    *bpg_out = p.bpg;
+    if (p.refusal) return refuse(p.refusal);
+    const uint32_t *g1 = (const uint32_t*)d_g1, *g2 = (const uint32_t*)d_g2;
     blsgpu::DegenList dg{c->at<uint32_t>(B_DEGEN), c->at<uint32_t>(B_DEGEN) + 1, (const uint8_t*)d_inf};
     HIP_TRY(hipMemsetAsync(c->at<uint32_t>(B_DEGEN), 0, sizeof(uint32_t), st));
-    if (wide) {
+    {
         KernelTimer kt(c, st, 0);
-        if (gsz * groups <= c->miller_wide3_max)
-            hipLaunchKernelGGL(blsgpu::mlw::k_miller_wide<3>, dim3((unsigned)(bpg * groups)), dim3(192), 0, st, (const uint32_t*)d_g1,
-                               (const uint32_t*)d_g2, (uint32_t)(gsz * groups), d_partials, dg);
-        else
-            hipLaunchKernelGGL(blsgpu::mlw::k_miller_wide<2>, dim3((unsigned)((bpg * groups + 1) / 2)), dim3(256), 0, st, (const uint32_t*)d_g1,
-                               (const uint32_t*)d_g2, (uint32_t)(gsz * groups), d_partials, dg);
-    } else if (mp2) {
-        KernelTimer kt(c, st, 0);
-        hipLaunchKernelGGL(blsgpu::k_miller_mp<2>, dim3((unsigned)(bpg * groups)), dim3(64), (size_t)blsgpu::MP_TEAM_BYTES, st, c->tabs,
-                           (const uint32_t*)d_g1, (const uint32_t*)d_g2, (uint32_t)gsz, (uint32_t)bpg, d_partials, dg);
-    } else if (mp) {
-        KernelTimer kt(c, st, 0);
-        hipLaunchKernelGGL(blsgpu::k_miller_mp<BLSVM_MP_G>, dim3((unsigned)(bpg * groups)), dim3(64), (size_t)blsgpu::MP_TEAM_BYTES, st,
-                           c->tabs, (const uint32_t*)d_g1, (const uint32_t*)d_g2, (uint32_t)gsz, (uint32_t)bpg, d_partials, dg);
-    } else {
-        size_t lds = per_block * blsgpu::TEAM_BYTES;
-        KernelTimer kt(c, st, 0);
-        hipLaunchKernelGGL(blsgpu::k_miller, dim3((unsigned)(bpg * groups)), dim3((unsigned)per_block * 64), lds, st, c->tabs,
-                           (const uint32_t*)d_g1, (const uint32_t*)d_g2, (uint32_t)gsz, (uint32_t)bpg, d_partials, dg);
+        switch (p.kernel) {
+        case M_WIDE3: hipLaunchKernelGGL(blsgpu::mlw::k_miller_wide<3>, dim3(p.grid), dim3(p.threads), p.lds, st, g1, g2, (uint32_t)p.pairs, d_partials, dg); break;
+        case M_WIDE2: hipLaunchKernelGGL(blsgpu::mlw::k_miller_wide<2>, dim3(p.grid), dim3(p.threads), p.lds, st, g1, g2, (uint32_t)p.pairs, d_partials, dg); break;
+        case M_MP2:
+            hipLaunchKernelGGL(blsgpu::k_miller_mp<2>, dim3(p.grid), dim3(p.threads), p.lds, st, c->tabs, g1, g2, (uint32_t)gsz, (uint32_t)p.bpg, d_partials, dg);
+            break;
+        case M_MP3:
+            hipLaunchKernelGGL(blsgpu::k_miller_mp<BLSVM_MP_G>, dim3(p.grid), dim3(p.threads), p.lds, st, c->tabs, g1, g2, (uint32_t)gsz, (uint32_t)p.bpg, d_partials, dg);
+            break;
+        case M_VM:
+            hipLaunchKernelGGL(blsgpu::k_miller, dim3(p.grid), dim3(p.threads), p.lds, st, c->tabs, g1, g2, (uint32_t)gsz, (uint32_t)p.bpg, d_partials, dg);
+            break;
+        }
     }
     HIP_TRY(hipGetLastError());
     if (c->bulk_event) HIP_TRY(hipEventRecord(c->bulk_event, st));
@@ -2239,29 +2194,24 @@ static int launch_miller(blsgpu_ctx* c, const void* d_g1, const void* d_g2, cons
     // (k_ml_lines_exact, block mode) and one six-lane accumulator per block over them (k_ml_small, list mode) -- 1.5 ms
     // where the VM's slow program (k_miller_slow: one pair at a time per wavefront, 68 lane-serial inversions each)
     // takes 6 ms per PAIR.  Both kernels leave at once when the list is empty.
-    const size_t nv = bpg * groups * per_block;            // virtual pairs: every block could be listed
-    if (c->vm_exact_lanes && nv <= ((size_t)1 << 16) &&
-        !c->grow(B_LINES, nv * blsgpu::ml::LINES * blsgpu::ml::LINE_DW * 4) && !c->grow(B_BAD, nv)) {
+    if (p.exact_lanes && !c->grow(B_LINES, p.lines_bytes) && !c->grow(B_BAD, p.bad_bytes)) {
         KernelTimer kt(c, st, 3);
-        hipLaunchKernelGGL(blsgpu::ml::k_ml_lines_exact, dim3(1024), dim3(64), 0, st, (const uint32_t*)d_g1, (const uint32_t*)d_g2, (uint32_t)nv,
-                           c->at<int32_t>(B_LINES), c->at<uint8_t>(B_BAD), dg, (uint32_t)gsz, (uint32_t)bpg, (uint32_t)per_block);
-        hipLaunchKernelGGL(blsgpu::ml::k_ml_small, dim3((unsigned)((bpg * groups + blsgpu::ml::TEAMS - 1) / blsgpu::ml::TEAMS)), dim3(64), 0, st,
-                           c->at<int32_t>(B_LINES), c->at<uint8_t>(B_BAD), (uint32_t)nv, (uint32_t)per_block, (uint32_t)(bpg * groups),
+        hipLaunchKernelGGL(blsgpu::ml::k_ml_lines_exact, dim3(1024), dim3(64), 0, st, g1, g2, (uint32_t)p.nv,
+                           c->at<int32_t>(B_LINES), c->at<uint8_t>(B_BAD), dg, (uint32_t)gsz, (uint32_t)p.bpg, (uint32_t)p.per_block);
+        hipLaunchKernelGGL(blsgpu::ml::k_ml_small, dim3(p.small_grid), dim3(64), 0, st,
+                           c->at<int32_t>(B_LINES), c->at<uint8_t>(B_BAD), (uint32_t)p.nv, (uint32_t)p.per_block, (uint32_t)p.blocks,
                            d_partials, 144u, (const uint32_t*)dg.count, (const uint32_t*)dg.blocks);
     } else {
         (void)hipGetLastError();
         KernelTimer kt(c, st, 3);
         hipLaunchKernelGGL(blsgpu::k_miller_slow, dim3(SLOW_GRID), dim3(64), (size_t)blsgpu::SLOW_TEAM_BYTES, st, c->tabs,
-                           (const uint32_t*)d_g1, (const uint32_t*)d_g2, (uint32_t)gsz, (uint32_t)bpg, (uint32_t)per_block, d_partials, dg);
+                           g1, g2, (uint32_t)gsz, (uint32_t)p.bpg, (uint32_t)p.per_block, d_partials, dg);
     }
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-// The line-stream form of launch_miller (blsgpu_ml.hip): ONE partial per group comes out (bpg = 1).
-static bool use_ls(const blsgpu_ctx* c, size_t gsz, size_t groups) {
-    return gsz >= 1 && gsz * groups >= c->ls_threshold && gsz * groups <= 0x3FFFFFF0ull;
-}
+// The line-stream form of launch_miller (blsgpu_ml.hip, pairing::plan_ls): ONE partial per group comes out (bpg = 1).
 // d_fused_out (optional): the caller wants nothing but the final exponentiation of each group's product -- the kernel
 // that ends the stage (k_ml_horner_fexp) then goes on to it in place: no partial, no further launch; *fused tells.
 // one_per_group: one accumulator per group whatever ls_min_group says (blsgpu_miller_loop_batch_dev: a group is a pair).
@@ -2269,167 +2219,128 @@ static int launch_miller_ls(blsgpu_ctx* c, const void* d_g1, const void* d_g2, c
                             uint32_t* d_partials, hipStream_t st, void* d_fused_out = nullptr, bool* fused = nullptr,
                             bool one_per_group = false) {
     using namespace blsgpu;
-    const size_t n = gsz * groups;
-    // chunks: equal runs of a group's pairs, one accumulator each per line index, sized so that about ls_teams
-    // accumulators exist (a wavefront of ten then runs a few hundred products: many short wavefronts per SIMD, so the
-    // last round of the launch costs little) but never fewer than 16 pairs (the merge is a dense product per chunk)
-    // ... and fewer, longer chunks for mid-size calls (at least 128 pairs each while 40 960 accumulators -- two wavefronts per
-    // SIMD -- remain): the merge tree over the chunks is latency, 65 536 pairs 7.05 -> 6.8 ms (tools/c3_probe.py)
-    size_t aim = n * ml::LINES / 128;
-    if (aim < 40960) aim = 40960;
-    if (aim > c->ls_teams) aim = c->ls_teams;
-    size_t want = (n * ml::LINES + aim - 1) / aim;
-    if (want < 16) want = 16;
-    if (want > gsz) want = gsz;
-    size_t cpg = (gsz + want - 1) / want;
-    const size_t chunk = (gsz + cpg - 1) / cpg;
-    cpg = (gsz + chunk - 1) / chunk;
-    constexpr size_t FAN = 8;
-    const bool small = one_per_group || gsz < c->ls_min_group;   // one accumulator per group runs the whole loop (k_ml_small)
+    const pairing::LsPlan p = pairing::plan_ls(*c, PAIRING_CONSTS, gsz, groups, one_per_group, d_fused_out != nullptr);
     if (c->test_ls_nomem ||                                // tests/test_gpu_alternate_forms.py: the fallback below, without exhausting a GPU
-        c->grow(B_LINES, n * ml::LINES * ml::LINE_DW * 4) ||
-        (!small && c->grow(B_LSP0, groups * cpg * ml::LINES * ml::DENSE_DW * 4)) ||
-        (!small && c->grow(B_LSP1, groups * ((cpg + FAN - 1) / FAN) * ml::LINES * ml::DENSE_DW * 4)) ||
-        c->grow(B_BAD, n) ||
-        c->grow(B_DEGEN, (n + 2) * 4)) {
+        c->grow(B_LINES, p.lines_bytes) || c->grow(B_LSP0, p.lsp0_bytes) || c->grow(B_LSP1, p.lsp1_bytes) || c->grow(B_BAD, p.bad_bytes) ||
+        c->grow(B_DEGEN, p.degen_bytes)) {
         (void)hipGetLastError();
         return -ENOMEM;                                    // the caller falls back to the wavefront-VM kernels
     }
+    const uint32_t *g1 = (const uint32_t*)d_g1, *g2 = (const uint32_t*)d_g2, n = (uint32_t)p.n;
+    int32_t* const lines = c->at<int32_t>(B_LINES);
+    uint8_t* const bad = c->at<uint8_t>(B_BAD);
     DegenList dg{c->at<uint32_t>(B_DEGEN), c->at<uint32_t>(B_DEGEN) + 1, (const uint8_t*)d_inf};
     HIP_TRY(hipMemsetAsync(c->at<uint32_t>(B_DEGEN), 0, sizeof(uint32_t), st));
     {
         KernelTimer kt(c, st, 4);
-        if (n <= c->ls_wide_max) {                       // a few thousand pairs: sixteen lanes each, the values in LDS, a product per lane
-            hipLaunchKernelGGL(lsw::k_ml_lines_wide, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, st, (const uint32_t*)d_g1,
-                               (const uint32_t*)d_g2, (uint32_t)n, c->at<int32_t>(B_LINES), c->at<uint8_t>(B_BAD), dg);
-        } else if (n <= c->ls_quad_max) {                // few pairs: four lanes each, the tangent step's levels shared by the two pairs
-            const WaveShape ws = wave_shape(c, (4 * n + 63) / 64);
-            hipLaunchKernelGGL(ml::k_ml_lines4, dim3(ws.blocks), dim3(ws.threads), ws.threads * ml::sp::SLAB_BYTES_PER_LANE, st, (const uint32_t*)d_g1,
-                               (const uint32_t*)d_g2, (uint32_t)n, c->at<int32_t>(B_LINES), c->at<uint8_t>(B_BAD), dg);
-        } else {
-            const WaveShape ws = wave_shape(c, (2 * n + 63) / 64);
-            hipLaunchKernelGGL(ml::k_ml_lines2, dim3(ws.blocks), dim3(ws.threads), ws.threads * ml::sp::SLAB_BYTES_PER_LANE, st, (const uint32_t*)d_g1,
-                               (const uint32_t*)d_g2, (uint32_t)n, c->at<int32_t>(B_LINES), c->at<uint8_t>(B_BAD), dg);
+        if (p.chain == pairing::L_WIDE16) {              // a few thousand pairs: sixteen lanes each, the values in LDS, a product per lane
+            hipLaunchKernelGGL(lsw::k_ml_lines_wide, dim3(p.chain_grid), dim3(256), 0, st, g1, g2, n, lines, bad, dg);
+        } else {                                         // four lanes each (few pairs), or two
+            const WaveShape ws = wave_shape(c, p.chain_waves);
+            if (p.chain == pairing::L_QUAD)
+                hipLaunchKernelGGL(ml::k_ml_lines4, dim3(ws.blocks), dim3(ws.threads), ws.threads * ml::sp::SLAB_BYTES_PER_LANE, st, g1, g2, n, lines, bad, dg);
+            else
+                hipLaunchKernelGGL(ml::k_ml_lines2, dim3(ws.blocks), dim3(ws.threads), ws.threads * ml::sp::SLAB_BYTES_PER_LANE, st, g1, g2, n, lines, bad, dg);
         }
     }
     HIP_TRY(hipGetLastError());
     {   // the listed pairs once more with the reference's own formulas: their line records are rewritten (leaves at once
         // when the list is empty)
         KernelTimer kt(c, st, 3);
-        hipLaunchKernelGGL(ml::k_ml_lines_exact, dim3(2048), dim3(64), 0, st, (const uint32_t*)d_g1, (const uint32_t*)d_g2, (uint32_t)n,
-                           c->at<int32_t>(B_LINES), c->at<uint8_t>(B_BAD), dg, 0u, 0u, 0u);
+        hipLaunchKernelGGL(ml::k_ml_lines_exact, dim3(2048), dim3(64), 0, st, g1, g2, n, lines, bad, dg, 0u, 0u, 0u);
     }
     HIP_TRY(hipGetLastError());
-    if (small) {
+    if (p.small) {
         {
             KernelTimer kt(c, st, 5);
-            const WaveShape ws = wave_shape(c, (groups + ml::TEAMS - 1) / ml::TEAMS);
-            hipLaunchKernelGGL(ml::k_ml_small, dim3(ws.blocks), dim3(ws.threads), 0, st, c->at<int32_t>(B_LINES),
-                               c->at<uint8_t>(B_BAD), (uint32_t)n, (uint32_t)gsz, (uint32_t)groups, d_partials, 144u,
+            const WaveShape ws = wave_shape(c, p.small_waves);
+            hipLaunchKernelGGL(ml::k_ml_small, dim3(ws.blocks), dim3(ws.threads), 0, st, lines, bad, n, (uint32_t)gsz, (uint32_t)groups, d_partials, 144u,
                                (const uint32_t*)nullptr, (const uint32_t*)nullptr);
         }
         HIP_TRY(hipGetLastError());
         if (c->bulk_event) HIP_TRY(hipEventRecord(c->bulk_event, st));
         return 0;
     }
-    size_t teams = groups * cpg * ml::LINES;
     {
         KernelTimer kt(c, st, 5);
-        const WaveShape ws = wave_shape(c, (teams + ml::TEAMS - 1) / ml::TEAMS);
-        hipLaunchKernelGGL(ml::k_ml_accum, dim3(ws.blocks), dim3(ws.threads), 0, st, c->at<int32_t>(B_LINES),
-                           c->at<uint8_t>(B_BAD), (uint32_t)n, (uint32_t)gsz, (uint32_t)chunk, (uint32_t)cpg, (uint32_t)teams,
-                           c->lsp(0));
+        const WaveShape ws = wave_shape(c, p.accum_waves);
+        hipLaunchKernelGGL(ml::k_ml_accum, dim3(ws.blocks), dim3(ws.threads), 0, st, lines, bad, n, (uint32_t)gsz, (uint32_t)p.chunk, (uint32_t)p.cpg,
+                           (uint32_t)p.accum_teams, c->lsp(0));
     }
     HIP_TRY(hipGetLastError());
-    int cur = 0;
-    while (cpg > 1) {
-        const size_t cpo = (cpg + FAN - 1) / FAN;
-        teams = groups * cpo * ml::LINES;
+    for (const pairing::Merge* m = p.merge; m != p.merge + p.nmerges; m++) {
         KernelTimer kt(c, st, 6);
-        if (teams <= c->ls_merge_wide_max)                                 // few outputs: one wavefront each, a product per lane
-            hipLaunchKernelGGL(fxw::k_ml_merge_wide, dim3((unsigned)teams), dim3(64), 0, st, c->lsp(cur), (uint32_t)cpg,
-                               (uint32_t)FAN, (uint32_t)cpo, c->lsp(cur ^ 1));
+        if (m->wide)                                       // few outputs: one wavefront each, a product per lane
+            hipLaunchKernelGGL(fxw::k_ml_merge_wide, dim3((unsigned)m->teams), dim3(64), 0, st, c->lsp(m->src), (uint32_t)m->cpg,
+                               (uint32_t)LS_MERGE_FAN, (uint32_t)m->cpo, c->lsp(m->dst));
         else {
-            const WaveShape ws = wave_shape(c, (teams + ml::TEAMS - 1) / ml::TEAMS);
-            hipLaunchKernelGGL(ml::k_ml_merge, dim3(ws.blocks), dim3(ws.threads), 0, st,
-                               c->lsp(cur), (uint32_t)cpg, (uint32_t)FAN, (uint32_t)cpo, (uint32_t)teams,
-                               c->lsp(cur ^ 1));
+            const WaveShape ws = wave_shape(c, m->waves);
+            hipLaunchKernelGGL(ml::k_ml_merge, dim3(ws.blocks), dim3(ws.threads), 0, st, c->lsp(m->src), (uint32_t)m->cpg, (uint32_t)LS_MERGE_FAN,
+                               (uint32_t)m->cpo, (uint32_t)m->teams, c->lsp(m->dst));
         }
         HIP_TRY(hipGetLastError());
-        cpg = cpo;
-        cur ^= 1;
     }
     if (c->bulk_event) HIP_TRY(hipEventRecord(c->bulk_event, st));
     {
-        const bool fuse = d_fused_out != nullptr && use_fexp_wide(c, 1, groups);
-        KernelTimer kt(c, st, fuse ? 2 : 7);
-        hipLaunchKernelGGL(fxw::k_ml_horner_fexp, dim3((unsigned)groups), dim3(64), 0, st, c->lsp(cur), d_partials, 144u,
-                           (uint32_t*)(fuse ? d_fused_out : nullptr));
-        if (fused) *fused = fuse;
+        KernelTimer kt(c, st, p.fuse ? 2 : 7);
+        hipLaunchKernelGGL(fxw::k_ml_horner_fexp, dim3((unsigned)groups), dim3(64), 0, st, c->lsp(p.last), d_partials, 144u,
+                           (uint32_t*)(p.fuse ? d_fused_out : nullptr));
+        if (fused) *fused = p.fuse;
     }
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-// Miller loops + per-group product; final exponentiation iff d_out_bytes
+// A call's arrays from pair `lo` on -- the points and the flags (when given) -- and an array of 576-byte partials or results
+// (when given) from result `res` on
+struct PairArrays { const char *g1, *g2, *inf; };
+static PairArrays pairs_at(const void* d_g1, const void* d_g2, const void* d_inf, size_t lo) {
+    const pairing::SliceOffsets o = pairing::slice_offsets(lo, 0);
+    return {(const char*)d_g1 + o.g1, (const char*)d_g2 + o.g2, d_inf ? (const char*)d_inf + o.inf : nullptr};
+}
+static char* result_at(void* d, size_t res) { return d ? (char*)d + pairing::slice_offsets(0, res).res : nullptr; }
+
+// Miller loops + per-group product; final exponentiation iff d_out_bytes (pairing::plan_grouped)
 static int grouped_pairing(blsgpu_ctx* c, const void* d_g1, const void* d_g2, const void* d_inf, size_t gsz, size_t groups,
                            uint32_t* d_out_partial, void* d_out_bytes, hipStream_t st) {
-    constexpr size_t MAX_GROUPS = 32768;               // groups ride on gridDim.y: larger batches go in slices
-    if (groups > MAX_GROUPS) {
-        for (size_t g0 = 0; g0 < groups; g0 += MAX_GROUPS) {
-            const size_t gn = groups - g0 < MAX_GROUPS ? groups - g0 : MAX_GROUPS;
-            int rc = grouped_pairing(c, (const char*)d_g1 + g0 * gsz * BLSGPU_G1_BYTES, (const char*)d_g2 + g0 * gsz * BLSGPU_G2_BYTES,
-                                     d_inf ? (const char*)d_inf + g0 * gsz * 2 : nullptr, gsz,
-                                     gn, d_out_partial ? d_out_partial + g0 * 144 : nullptr,
-                                     d_out_bytes ? (char*)d_out_bytes + g0 * BLSGPU_FQ12_BYTES : nullptr, st);
-            if (rc) return rc;
-        }
-        return 0;
+    const pairing::GroupedPlan p = pairing::plan_grouped(*c, PAIRING_CONSTS, pairing_limits(c), gsz, groups, d_out_bytes != nullptr, d_out_partial != nullptr);
+    if (p.outer)                                           // groups ride on gridDim.y: larger batches go in slices
+        return for_slices(groups, p.outer, [&](size_t g0, size_t gn) {
+            const PairArrays a = pairs_at(d_g1, d_g2, d_inf, g0 * gsz);
+            return grouped_pairing(c, a.g1, a.g2, a.inf, gsz, gn, (uint32_t*)result_at(d_out_partial, g0), result_at(d_out_bytes, g0), st);
+        });
+    if (int rc = ensure_partials(c, p.partials)) return rc;
+    // the line-stream stage: a slice that finds no memory for its line records (-ENOMEM) leaves the call to the VM kernels
+    int rc = -ENOMEM;
+    switch (p.ls) {
+    case pairing::LS_OFF: case pairing::LS_VM_LONG_GROUPS: break;
+    case pairing::LS_WHOLE: {
+        bool fused = false;
+        uint32_t* target = p.direct ? d_out_partial : c->part(0);
+        rc = launch_miller_ls(c, d_g1, d_g2, d_inf, gsz, groups, target, st, d_out_bytes, &fused);
+        if (rc == 0 && (fused || p.direct)) return 0;      // (fused: the stage's last kernel ran the final exponentiations too)
+        break;
     }
-    // every group rounds its team count up; the wide Miller loop leaves one partial per pair
-    size_t partials = pairs_partials((gsz + 3) * groups);
-    const size_t vm_blocks = miller_plan(c, gsz, groups, false).bpg * groups;
-    if (int rc = ensure_partials(c, partials > vm_blocks ? partials : vm_blocks)) return rc;
-    size_t bpg = 0;
-    bool ls_done = false;
-    if (gsz > 0 && use_ls(c, gsz, groups)) {
-        // The line records are 22.8 KB per pair: a call is cut into slices of at most LS_MAX_PAIRS pairs -- whole groups,
-        // or, for ONE long group, runs of its pairs that each leave a partial for the product below.
-        int rc = 0;
-        if (gsz * groups <= LS_MAX_PAIRS) {
-            bool fused = false;
-            // one partial per group comes out of the stage: straight into the caller's buffer when that is all it wants
-            // (the sharded entries), no copying pass of k_reduce behind it
-            uint32_t* target = (d_out_partial && !d_out_bytes) ? d_out_partial : c->part(0);
-            rc = launch_miller_ls(c, d_g1, d_g2, d_inf, gsz, groups, target, st, d_out_bytes, &fused);
-            if (rc == 0 && (fused || target == d_out_partial)) return 0;   // (fused: the stage's last kernel ran the final exponentiations too)
-            bpg = 1;
-        } else if (gsz <= LS_MAX_PAIRS) {
-            const size_t per = LS_MAX_PAIRS / gsz;
-            for (size_t g0 = 0; g0 < groups && !rc; g0 += per) {
-                const size_t gn = groups - g0 < per ? groups - g0 : per;
-                rc = launch_miller_ls(c, (const char*)d_g1 + g0 * gsz * BLSGPU_G1_BYTES, (const char*)d_g2 + g0 * gsz * BLSGPU_G2_BYTES,
-                                      d_inf ? (const char*)d_inf + g0 * gsz * 2 : nullptr, gsz, gn, c->part(0) + g0 * 144, st);
-            }
-            bpg = 1;
-        } else if (groups == 1) {
-            size_t k = 0;
-            for (size_t p0 = 0; p0 < gsz && !rc; p0 += LS_MAX_PAIRS, k++) {
-                const size_t pn = gsz - p0 < LS_MAX_PAIRS ? gsz - p0 : LS_MAX_PAIRS;
-                rc = launch_miller_ls(c, (const char*)d_g1 + p0 * BLSGPU_G1_BYTES, (const char*)d_g2 + p0 * BLSGPU_G2_BYTES,
-                                      d_inf ? (const char*)d_inf + p0 * 2 : nullptr, pn, 1, c->part(0) + k * 144, st);
-            }
-            bpg = k;
-        } else {
-            rc = -ENOMEM;                                  // several groups of more than LS_MAX_PAIRS pairs: the VM kernels
-        }
-        if (rc == 0) ls_done = true;
-        else if (rc != -ENOMEM) return rc;                 // no memory for the line records: the wavefront-VM kernels instead
+    case pairing::LS_GROUP_SLICES:
+        rc = for_slices(groups, p.per, [&](size_t g0, size_t gn) {
+            const PairArrays a = pairs_at(d_g1, d_g2, d_inf, g0 * gsz);
+            return launch_miller_ls(c, a.g1, a.g2, a.inf, gsz, gn, (uint32_t*)result_at(c->part(0), g0), st);
+        });
+        break;
+    case pairing::LS_RUN_SLICES:
+        rc = for_slices(gsz, p.run_len, [&](size_t p0, size_t pn) {
+            const PairArrays a = pairs_at(d_g1, d_g2, d_inf, p0);
+            return launch_miller_ls(c, a.g1, a.g2, a.inf, pn, 1, (uint32_t*)result_at(c->part(0), p0 / p.run_len), st);
+        });
+        break;
     }
-    if (ls_done) {
-    } else if (gsz > 0) {
-        int rc = launch_miller(c, d_g1, d_g2, d_inf, gsz, groups, false, c->part(0), st, &bpg);
-        if (rc) return rc;
+    size_t bpg = p.ls_bpg;
+    if (rc == -ENOMEM) {
+        bpg = 0;
+        if (gsz > 0)
+            if (int rc2 = launch_miller(c, d_g1, d_g2, d_inf, gsz, groups, false, c->part(0), st, &bpg)) return rc2;
+    } else if (rc) {
+        return rc;
     }
     return reduce_chain(c, c->part(0), bpg, groups, 1, bpg, d_out_bytes != nullptr, d_out_partial, d_out_bytes, st);
 }
@@ -2463,8 +2374,7 @@ BLSGPU_EXPORT int blsgpu_final_exp_product_batch_dev(blsgpu_ctx* c, const void* 
     if (m > 0 && !d_partials) return fail(-EINVAL, "NULL partials");
     HIP_TRY(hipSetDevice(c->device));
     StreamGuard sg(c, (hipStream_t)stream);
-    // the first level of the reduce chain leaves a partial per 64 of a group's
-    if (int rc = ensure_partials(c, ((m + REDUCE_PER_BLOCK - 1) / REDUCE_PER_BLOCK) * groups + 1)) return rc;
+    if (int rc = ensure_partials(c, pairing::product_partials(PAIRING_CONSTS, m, groups))) return rc;
     return reduce_chain(c, (const uint32_t*)d_partials, m, groups, groups, 1, true, nullptr, d_out, (hipStream_t)stream);
 }
 
@@ -2501,57 +2411,54 @@ BLSGPU_EXPORT int blsgpu_miller_loop_batch_dev(blsgpu_ctx* c, const void* d_g1, 
     if (n > 0x7FFFFFF0ull) return fail(-EINVAL, "n too large");
     HIP_TRY(hipSetDevice(c->device));
     StreamGuard sg(c, (hipStream_t)stream);
+    using namespace blsgpu;
+    const hipStream_t st = (hipStream_t)stream;
+    const pairing::ExactPlan p = pairing::plan_exact(PAIRING_CONSTS, pairing_limits(c), n);
+    // slice [lo, lo + m) of the call: its points as words, its flags, its results
+    struct Slice { pairing::ExactSlice s; const uint32_t *p1, *p2; const uint8_t* inf; uint32_t* out; };
+    const auto slice = [&](size_t lo) {
+        const PairArrays a = pairs_at(d_g1, d_g2, d_inf, lo);
+        return Slice{p.at(lo), (const uint32_t*)a.g1, (const uint32_t*)a.g2, (const uint8_t*)a.inf, (uint32_t*)result_at(d_out, lo)};
+    };
     if (c->miller_exact_lanes) {
         // Round 5: the lane kernels instead of the VM's reference-faithful program (one pair per wavefront, 68 lane-serial inversions:
         // 7 ms for one pair, 158 k pairs/s): every pair on the work list, k_ml_lines_exact writes its 68 lines with the reference's
         // own formulas (a pair per lane pair), k_ml_small multiplies them up with one six-lane accumulator per pair, in slices that
         // keep the line records below 6 GB.
-        using namespace blsgpu;
-        const hipStream_t st = (hipStream_t)stream;
-        const size_t slice = 262144;
-        const size_t m0 = n < slice ? n : slice;
-        if (c->miller_exact_fast && c->grow(B_EXFLAGS, 2 * m0) == 0 && ensure_partials(c, m0 + (m0 + 1) / 2 + 1) == 0) {
+        if (c->miller_exact_fast && c->grow(B_EXFLAGS, p.exflags_bytes) == 0 && ensure_partials(c, p.partials) == 0) {
             // the ordinary line-stream kernels with one accumulator per pair, then one Fq2 factor per pair turns the fast value into the
             // reference's (k_ml_exact_fixup: 73 dependent inversions per pair become one); a pair the fast formulas are not valid for
             // -- or whose py is 0, which the factor divides by -- takes the reference's own lines inside the same launches
-            bool ok = true;
-            for (size_t lo = 0; lo < n && ok; lo += slice) {
-                const size_t m = n - lo < slice ? n - lo : slice;
-                const uint32_t* p1 = (const uint32_t*)d_g1 + lo * 24;
-                const uint32_t* p2 = (const uint32_t*)d_g2 + lo * 48;
-                hipLaunchKernelGGL(ml::k_ml_exact_flags, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, p1, d_inf ? (const uint8_t*)d_inf + 2 * lo : nullptr,
-                                   (uint32_t)m, c->at<uint8_t>(B_EXFLAGS));
-                const int rc_ = launch_miller_ls(c, p1, p2, c->at<uint8_t>(B_EXFLAGS), 1, m, c->part(0), st, nullptr, nullptr, true);
-                if (rc_ == -ENOMEM && lo == 0) { ok = false; break; }          // no room for the line records: the forms below
+            const int rc = for_slices(n, p.slice, [&](size_t lo, size_t m) {
+                const Slice s = slice(lo);
+                hipLaunchKernelGGL(ml::k_ml_exact_flags, dim3(s.s.g_flags), dim3(256), 0, st, s.p1, s.inf, (uint32_t)m, c->at<uint8_t>(B_EXFLAGS));
+                const int rc_ = launch_miller_ls(c, s.p1, s.p2, c->at<uint8_t>(B_EXFLAGS), 1, m, c->part(0), st, nullptr, nullptr, true);
+                if (rc_ == -ENOMEM && lo == 0) return 1;                   // no room for the line records: the forms below
                 if (rc_) return rc_;
-                hipLaunchKernelGGL(ml::k_ml_exact_fixup, dim3((unsigned)((2 * m + 255) / 256)), dim3(256), 0, st, p1, c->at<int32_t>(B_LINES),
-                                   c->at<uint8_t>(B_BAD), c->part(0), (uint32_t)m, (uint32_t*)d_out + lo * 144);
+                hipLaunchKernelGGL(ml::k_ml_exact_fixup, dim3(s.s.g_fixup), dim3(256), 0, st, s.p1, c->at<int32_t>(B_LINES),
+                                   c->at<uint8_t>(B_BAD), c->part(0), (uint32_t)m, s.out);
                 HIP_TRY(hipGetLastError());
-            }
-            if (ok) return 0;
+                return 0;
+            });
+            if (rc != 1) return rc;
         }
-        if (c->grow(B_LINES, m0 * ml::LINES * ml::LINE_DW * 4) == 0 && c->grow(B_BAD, m0) == 0 &&
-            c->grow(B_DEGEN, (m0 + 2) * 4) == 0 && ensure_partials(c, m0 + (m0 + 1) / 2 + 1) == 0) {
-            for (size_t lo = 0; lo < n; lo += slice) {
-                const size_t m = n - lo < slice ? n - lo : slice;
-                const uint32_t* p1 = (const uint32_t*)d_g1 + lo * 24;
-                const uint32_t* p2 = (const uint32_t*)d_g2 + lo * 48;
-                DegenList dg{c->at<uint32_t>(B_DEGEN), c->at<uint32_t>(B_DEGEN) + 1, d_inf ? (const uint8_t*)d_inf + 2 * lo : nullptr};
-                hipLaunchKernelGGL(ml::k_ml_list_all, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (uint32_t)m, c->at<uint32_t>(B_DEGEN), c->at<uint32_t>(B_DEGEN) + 1);
-                hipLaunchKernelGGL(ml::k_ml_lines_exact, dim3(2048), dim3(64), 0, st, p1, p2, (uint32_t)m, c->at<int32_t>(B_LINES), c->at<uint8_t>(B_BAD), dg, 0u, 0u, 0u);
-                const WaveShape ws = wave_shape(c, (m + ml::TEAMS - 1) / ml::TEAMS);
+        if (c->grow(B_LINES, p.lines_bytes) == 0 && c->grow(B_BAD, p.bad_bytes) == 0 && c->grow(B_DEGEN, p.degen_bytes) == 0 &&
+            ensure_partials(c, p.partials) == 0)
+            return for_slices(n, p.slice, [&](size_t lo, size_t m) {
+                const Slice s = slice(lo);
+                DegenList dg{c->at<uint32_t>(B_DEGEN), c->at<uint32_t>(B_DEGEN) + 1, s.inf};
+                hipLaunchKernelGGL(ml::k_ml_list_all, dim3(s.s.g_list), dim3(256), 0, st, (uint32_t)m, c->at<uint32_t>(B_DEGEN), c->at<uint32_t>(B_DEGEN) + 1);
+                hipLaunchKernelGGL(ml::k_ml_lines_exact, dim3(2048), dim3(64), 0, st, s.p1, s.p2, (uint32_t)m, c->at<int32_t>(B_LINES), c->at<uint8_t>(B_BAD), dg, 0u, 0u, 0u);
+                const WaveShape ws = wave_shape(c, s.s.small_waves);
                 hipLaunchKernelGGL(ml::k_ml_small, dim3(ws.blocks), dim3(ws.threads), 0, st, c->at<int32_t>(B_LINES), c->at<uint8_t>(B_BAD), (uint32_t)m, 1u,
                                    (uint32_t)m, c->part(0), 144u, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
-                hipLaunchKernelGGL(ml::k_ml_partials_to_bytes, dim3((unsigned)((m * 12 + 255) / 256)), dim3(256), 0, st, c->part(0), (uint32_t)(m * 12),
-                                   (uint32_t*)d_out + lo * 144);
+                hipLaunchKernelGGL(ml::k_ml_partials_to_bytes, dim3(s.s.g_bytes), dim3(256), 0, st, c->part(0), (uint32_t)(m * 12), s.out);
                 HIP_TRY(hipGetLastError());
-            }
-            return 0;
-        }
+                return 0;
+            });
         (void)hipGetLastError();                               // no room for the line records: the VM's program below
     }
-    const unsigned grid = (unsigned)(n < 16384 ? n : 16384);
-    hipLaunchKernelGGL(blsgpu::k_miller_exact, dim3(grid), dim3(64), (size_t)blsgpu::SLOW_TEAM_BYTES, (hipStream_t)stream, c->tabs,
+    hipLaunchKernelGGL(blsgpu::k_miller_exact, dim3(p.vm_grid), dim3(64), (size_t)blsgpu::SLOW_TEAM_BYTES, st, c->tabs,
                        (const uint32_t*)d_g1, (const uint32_t*)d_g2, (const uint8_t*)d_inf, (uint32_t)n, (uint32_t*)d_out);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -2633,21 +2540,13 @@ BLSGPU_EXPORT int blsgpu_final_exp_batch(blsgpu_ctx* c, const uint8_t* in, size_
     Staging s(c);
     const int din = s.in(in, m * 576), dout = s.out(out, m * 576);
     if (int rc = s.alloc()) return rc;
-    if (int rc = ensure_partials(c, 3 * m + 1)) return rc;    // (one per element is written)
+    if (int rc = ensure_partials(c, pairing::fexp_batch_partials(m))) return rc;
     StreamGuard sg(c, nullptr);
     if (int rc = s.up()) return rc;
-    size_t lds = (size_t)REDUCE_WAVES * blsgpu::TEAM_BYTES;
-    unsigned blocks = (unsigned)((m + REDUCE_WAVES - 1) / REDUCE_WAVES);
-    hipLaunchKernelGGL(blsgpu::k_bytes_to_partials, dim3(blocks), dim3(REDUCE_WAVES * 64), lds, 0, c->tabs,
-                       (const uint32_t*)s.at(din), (uint32_t)m, c->part(1));
+    hipLaunchKernelGGL(blsgpu::k_bytes_to_partials, dim3(pairing::final_blocks(PAIRING_CONSTS, m)), dim3(REDUCE_WAVES * 64),
+                       (size_t)REDUCE_WAVES * blsgpu::TEAM_BYTES, 0, c->tabs, (const uint32_t*)s.at(din), (uint32_t)m, c->part(1));
     HIP_TRY(hipGetLastError());
-    if (use_fexp_reg(c, 1, m)) {
-        if (int rc2 = launch_fexp_reg(c, c->part(1), 1, 1, 1, m, s.at(dout), 0)) return rc2;
-    } else {
-        hipLaunchKernelGGL(blsgpu::k_final_groups, dim3(blocks), dim3(REDUCE_WAVES * 64), lds, 0, c->tabs, c->part(1),
-                           1u, (uint32_t)m, (uint32_t*)s.at(dout));
-        HIP_TRY(hipGetLastError());
-    }
+    if (int rc = launch_final(c, pairing::fexp_form(*c, PAIRING_CONSTS, 1, m), c->part(1), 1, 1, 1, m, s.at(dout), 0, false)) return rc;
     return s.down();
 }
 
@@ -2668,45 +2567,27 @@ BLSGPU_EXPORT int blsgpu_pairing_multi_batch_dev(blsgpu_ctx* c, const void* d_g1
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     StreamGuard sg(c, st);
-    if (gsz >= BATCH_TREE_MIN_GROUP) return grouped_pairing(c, d_g1, d_g2, d_inf, gsz, groups, nullptr, d_out, st);
-    // every launch below leaves at most one partial per PAIR (miller_plan: bpg x groups <= n whichever kernel runs)
-    int rc = ensure_partials(c, 3 * (n + 1) + 1);
-    if (rc) return rc;
-    if (gsz >= 1 && use_ls(c, gsz, groups) && n <= LS_MAX_PAIRS) {
+    const pairing::BatchPlan p = pairing::plan_batch(*c, PAIRING_CONSTS, pairing_limits(c), gsz, groups);
+    if (p.route == pairing::B_TREE) return grouped_pairing(c, d_g1, d_g2, d_inf, gsz, groups, nullptr, d_out, st);
+    // every launch below leaves at most one partial per PAIR (plan_miller: bpg x groups <= n whichever kernel runs)
+    if (int rc = ensure_partials(c, p.partials)) return rc;
+    bool ls = p.route == pairing::B_LS_SMALL;
+    if (ls) {
         // a large batch of small groups: point chains on lane pairs, then one accumulator per group (blsgpu_ml.hip)
-        rc = launch_miller_ls(c, d_g1, d_g2, d_inf, gsz, groups, c->part(0), st);
-        if (rc == 0) {
-            if (use_fexp_reg(c, 1, groups)) return launch_fexp_reg(c, c->part(0), 1, 1, 1, groups, d_out, st);
-            size_t lds = (size_t)REDUCE_WAVES * blsgpu::TEAM_BYTES;
-            unsigned blocks = (unsigned)((groups + REDUCE_WAVES - 1) / REDUCE_WAVES);
-            KernelTimer kt(c, st, 2);
-            hipLaunchKernelGGL(blsgpu::k_final_groups, dim3(blocks), dim3(REDUCE_WAVES * 64), lds, st, c->tabs, c->part(0), 1u,
-                               (uint32_t)groups, (uint32_t*)d_out);
-            HIP_TRY(hipGetLastError());
-            return 0;
-        }
-        if (rc != -ENOMEM) return rc;
+        const int rc = launch_miller_ls(c, d_g1, d_g2, d_inf, gsz, groups, c->part(0), st);
+        if (rc && rc != -ENOMEM) return rc;
+        ls = rc == 0;                                      // no memory for the line records: the fallback route
     }
-    // groups of two or three pairs in a batch large enough for the team kernels: the group IS the team (one
-    // accumulator, its squarings shared), one partial per group; otherwise one partial per pair
-    const bool team_groups = (gsz == 2 || gsz == (size_t)BLSVM_MP_G) && use_mp(c, n) && groups <= 0x7FFFFFFFull;
-    if (n) {
+    const pairing::BatchFinal& fin = ls ? p.fin : p.fallback_fin;
+    if (n && !ls) {
+        // groups of two or three pairs in a batch large enough for the team kernels: the group IS the team (one
+        // accumulator, its squarings shared), one partial per group; otherwise one partial per pair
         size_t bpg = 0;
-        rc = team_groups ? launch_miller(c, d_g1, d_g2, d_inf, gsz, groups, false, c->part(0), st, &bpg, (int)gsz)
-                         : launch_miller(c, d_g1, d_g2, d_inf, n, 1, true, c->part(0), st, &bpg);
+        const int rc = p.fallback == pairing::B_TEAM_GROUPS ? launch_miller(c, d_g1, d_g2, d_inf, gsz, groups, false, c->part(0), st, &bpg, (int)gsz)
+                                                            : launch_miller(c, d_g1, d_g2, d_inf, n, 1, true, c->part(0), st, &bpg);
         if (rc) return rc;
     }
-    if (use_fexp_reg(c, team_groups ? 1 : gsz, groups))
-        return launch_fexp_reg(c, c->part(0), team_groups ? 1 : gsz, 1, team_groups ? 1 : gsz, groups, d_out, st);
-    size_t lds = (size_t)REDUCE_WAVES * blsgpu::TEAM_BYTES;
-    unsigned blocks = (unsigned)((groups + REDUCE_WAVES - 1) / REDUCE_WAVES);
-    {
-        KernelTimer kt(c, st, 2);
-        hipLaunchKernelGGL(blsgpu::k_final_groups, dim3(blocks), dim3(REDUCE_WAVES * 64), lds, st, c->tabs, c->part(0),
-                           (uint32_t)(team_groups ? 1 : gsz), (uint32_t)groups, (uint32_t*)d_out);
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch_final(c, fin.fexp, c->part(0), fin.m, fin.istride, fin.gstride, groups, d_out, st);
 }
 
 BLSGPU_EXPORT int blsgpu_pairing_multi_batch(blsgpu_ctx* c, const uint8_t* g1, const uint8_t* g2, const uint8_t* inf, size_t gsz,
@@ -2871,7 +2752,7 @@ BLSGPU_EXPORT int blsgpu_verify_pipeline(blsgpu_ctx* c, const uint8_t neg_g1[96]
               dkp = s.in(sums ? key_pts : nullptr, n * k * BLSGPU_G1_BYTES), dks = s.in(sums ? key_scalars : nullptr, n * k * 32), dout = s.out(out, 576);
     if (int rc = s.alloc()) return rc;
     // the VM kernels round their team counts up: reserve as a call of n + 1 pairs does
-    if (int rc = ensure_partials(c, 3 * (n + 4) + 1)) return rc;
+    if (int rc = ensure_partials(c, pairing::batch_partials(n + 3))) return rc;
     {
         StreamGuard sg(c, nullptr);
         HIP_TRY(hipMemcpyAsync(s.at(d1), neg_g1, BLSGPU_G1_BYTES, hipMemcpyHostToDevice, nullptr));

@@ -86,8 +86,8 @@ constexpr BufInfo BUF_INFO[B_COUNT] = {
 
 }  // namespace
 
-// (the knobs of the G1 / G2 sums are msm::Knobs, msm_plan.h)
-struct blsgpu_ctx : msm::Knobs {
+// (the knobs of the G1 / G2 sums are msm::Knobs, msm_plan.h; those of the pairing path pairing::Knobs, pairing_plan.h)
+struct blsgpu_ctx : msm::Knobs, pairing::Knobs {
     int device = 0;
     blsgpu::VmTables tabs{};
     void* d_tables = nullptr;          // one allocation holding every table
@@ -107,10 +107,6 @@ struct blsgpu_ctx : msm::Knobs {
 
     // ---- tuning knobs: the defaults are the measured ones; KNOBS below names the environment variable of each, read once
     // by blsgpu_ctx_create
-    size_t miller_wide3_max = 256;     // ... with the accumulator split over two wavefronts (three per pair) up to this many pairs: three SIMDs per pair are free
-    size_t miller_wide_max = 1536;     // calls of at most this many pairs run the wide Miller loop (blsgpu_mlw.hip: one pair per two-wavefront workgroup, a product per lane); 0: never
-    size_t mp_threshold = 4096;        // pairs from which k_miller_mp is used
-    size_t mp3_threshold = (size_t)-1; // ... with three pairs per wavefront from here on, two below; -1: the measured schedule
     size_t pow2_max = 32768;           // fixed-exponent powers (hash to G2, decompression): up to this many values per launch two wavefronts per 64 values (k_pow2: 0.32 ms against 0.47); 0: never
     size_t h2c_wide_max = 2048;        // up to this many messages the cofactor clearing runs one message per WAVEFRONT with a product per lane (blsgpu_h2cw.hip: the latency form); 0: never
     size_t h2c_reg_threshold = 8192;   // messages from which cofactor clearing runs in registers (one message per lane PAIR; measured: DESIGN.md 2c)
@@ -118,23 +114,8 @@ struct blsgpu_ctx : msm::Knobs {
     bool h2c_jacobi = true;            // ... with the quadratic characters decided by a Jacobi-symbol routine: two powers per encoding, not five
     size_t h2c_jacobi_threshold = 16384;   // ... from this many messages (below, five parallel powers finish sooner than three serial symbol loops)
     size_t h2c_quad_max = 16384;       // ... on lane QUADS up to this many messages (k_h2c_clear_quads: half the depth while the chip is not full)
-    bool test_ls_nomem = false;        // test hook (BLSGPU_TEST_LS_NOMEM=1): the line-stream workspace "cannot be allocated"
     bool sigdiv_plain = true;           // blsgpu_sig_divide*: a call whose accepted quotients are all 1 sums the negated divisors (blsgpu_g2_range_sums' passes) and multiplies nothing; false: every call takes the scalars through blsgpu_g2_msm_ranges' kernels (the tests hold the two against each other)
     size_t wg256_max_waves = 4096;     // register kernels: launches of up to this many wavefronts go out as 256-thread workgroups (blsgpu_tu.h)
-    // line-stream multi-pairing (blsgpu_ml.hip): used from ls_threshold pairs per call when every group has at least
-    // ls_min_group pairs
-    size_t ls_threshold = 2304;        // measured crossover (tools/ls_wide_sweep.py, round 5 with the point chains sixteen lanes per pair): 2048 pairs 1.70 (VM) vs 1.70 ms, 3072 pairs 1.93 vs 1.79; 5120 in round 4, 16 384 in round 3
-    size_t ls_min_group = 64;
-    size_t ls_teams = 163840;          // accumulators k_ml_accum aims at (10 per wavefront: 8 wavefronts per place at two per SIMD)
-    bool vm_exact_lanes = true;        // degenerate blocks of the VM kernels through the lane kernels (k_ml_lines_exact / k_ml_small) instead of k_miller_slow
-    bool miller_exact_lanes = true;    // blsgpu_miller_loop_batch (one exact Fq12 per pair) on the lane kernels (k_ml_lines_exact + k_ml_small, round 5) instead of the VM's k_miller_exact
-    bool miller_exact_fast = true;     // ... from the FAST lines: the line-stream kernels + one Fq2 factor per pair (k_ml_exact_fixup) instead of the reference's 73 affine slopes per pair; false: k_ml_lines_exact for every pair
-    size_t ls_merge_wide_max = 16384;  // merge levels with at most this many outputs run one wavefront per output
-    size_t ls_wide_max = 5120;         // calls of at most this many pairs run the point chains sixteen lanes per pair with the values in LDS (k_ml_lines_wide, blsgpu_lsw.hip); 0: never
-    size_t ls_quad_max = 20480;        // calls of at most this many pairs run the point chains on lane QUADS (k_ml_lines4: 0.6 of the depth while lane pairs leave SIMDs empty)
-    size_t fexp_team_threshold = 5120; // results per call from which the final exponentiations run six lanes each (blsgpu_fexp.hip); below: one result per wavefront (measured crossover, tools/fexp_latency.py)
-    bool fexp_wide = true;             // fewer results than that: one result per wavefront, a product per lane (blsgpu_fexpw.hip); false: the VM program
-    size_t fexp_wide_max_partials = 8; // ... which also multiplies up to this many partials per result itself (a dense product is ~2.5 us)
 
     void* d_fexp_dbg = nullptr;        // tools/fexp_trace.py: the accumulator of result 0 after every operation of the script (k_fexp_team)
     void* d_fexpw_stamps = nullptr;    // tools/fexpw_stamps.py: cycle counter of result 0 around every operation of the script (k_fexp_wide)

@@ -628,3 +628,103 @@ def test_share_check_dev_and_sums_of_secrets_across_slices(engine, capped):
     d_y, d_out, d_pka, d_pks = up(be32(ys)), blank(32 * groups), blank(96 * groups), blank(48 * groups)
     eng.fr_sum_secret_dev(d_y.data_ptr(), k, groups, d_out.data_ptr(), d_pka.data_ptr(), d_pks.data_ptr(), 0)
     assert (down(d_out), down(d_pka), down(d_pks)) == (wsum,) + tuple(wpk)
+
+
+# ------------------------------------------------------------------------------------------------ pairings --
+# The pairing path's slices (csrc/pairing_plan.h Limits: groups per call of the grouped kernels, pairs per line-stream launch
+# sequence, pairs per slice of blsgpu_miller_loop_batch) all hold CAP items here.  Expected values are the CPU oracle's and the
+# reference's own Miller values of tests/golden/pairing.json.
+LS_RUNS = {"BLSGPU_LS_THRESHOLD": 1, "BLSGPU_LS_MIN_GROUP": 2}      # every call asks for the line-stream kernels, chunked from two pairs on
+LS_SMALL = {"BLSGPU_LS_THRESHOLD": 1}                               # ... one accumulator per group below 64 pairs
+
+
+def slice_edges(n, cap=CAP):
+    """the pairs that get a degenerate: the last of the first slice, the first of the second, the last of the second, the last"""
+    return sorted({p for p in (cap - 1, cap, 2 * cap - 1, n - 1) if 0 <= p < n})
+
+
+@pytest.fixture(scope="module")
+def pair_world(golden, seeded_pairs):
+    """world(n, at, py_zero) -> g1, g2, inf, miller: the first n seeded pairs with the reference's infinity vectors (flag on P, on
+    Q, on both) and, if asked for, a pair with py = 0 planted at the places `at`, in turn; miller[i] is the reference's Miller value of pair i where a
+    vector gives it, else None"""
+    g1, g2 = seeded_pairs
+    edge = golden("pairing.json")["edge"]
+    flagged = [edge[k] for k in ("p_inf", "q_inf", "both_inf")]
+
+    def world(n, at, py_zero=False):
+        kinds = [None] * py_zero + flagged                   # (py = 0 only where the call is blsgpu_miller_loop_batch)
+        a, b, inf, miller = bytearray(g1[:96 * n]), bytearray(g2[:192 * n]), bytearray(2 * n), [None] * n
+        for j, i in enumerate(at):
+            v = kinds[j % len(kinds)]
+            if v is None:
+                a[96 * i + 48:96 * (i + 1)] = bytes(48)      # py = 0: not a point of G1, but the loops are total functions
+            else:
+                a[96 * i:96 * (i + 1)], b[192 * i:192 * (i + 1)] = bytes.fromhex(v["g1"][0]), bytes.fromhex(v["g2"][0])
+                inf[2 * i:2 * i + 2] = bytes(int(x) for x in v["inf"][0])
+                miller[i] = bytes.fromhex(v["miller"][0])
+        return bytes(a), bytes(b), bytes(inf), miller
+    return world
+
+
+def want_groups(oracle, a, b, inf, gsz, groups):
+    return b"".join(oracle.pairing_multi(a[96 * gsz * g:96 * gsz * (g + 1)], b[192 * gsz * g:192 * gsz * (g + 1)], gsz, threads=8,
+                                         inf=inf[2 * gsz * g:2 * gsz * (g + 1)]) for g in range(groups))
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_one_long_group_in_runs(engine, capped, pair_world, oracle, n):
+    """blsgpu_pairing_multi_dev: runs of one long group, each leaves a partial for the reduce chain (five, four, two, one)"""
+    a, b, inf, _ = pair_world(n, slice_edges(n))
+    want = oracle.pairing_multi(a, b, n, threads=8, inf=inf)
+    got = []
+    for eng in (capped(CAP, **LS_RUNS), engine):
+        d_a, d_b, d_i, d_o = up(a), up(b), up(inf), blank(576)
+        eng.pairing_multi_dev(d_a.data_ptr(), d_b.data_ptr(), n, d_o.data_ptr(), 0, d_i.data_ptr())
+        got.append(down(d_o))
+    assert got[0] == want
+    assert got[1] == want
+
+
+def product_then_final(eng, a, b, inf, gsz, groups):
+    d_a, d_b, d_i, d_p, d_o = up(a), up(b), up(inf), blank(576 * groups), blank(576 * groups)
+    eng.miller_product_batch_dev(d_a.data_ptr(), d_b.data_ptr(), gsz, groups, d_p.data_ptr(), 0, d_i.data_ptr())
+    eng.final_exp_product_batch_dev(d_p.data_ptr(), 1, groups, d_o.data_ptr(), 0)
+    return down(d_o)
+
+
+@pytest.mark.parametrize("gsz,groups,knobs", [(2, 7, LS_RUNS), (1, 23, LS_SMALL), (7, 3, LS_RUNS)])
+def test_groups_in_slices(engine, capped, pair_world, oracle, gsz, groups, knobs):
+    """blsgpu_miller_product_batch_dev, then blsgpu_final_exp_product_batch_dev: 7 groups of 2 pairs are two slices of at most
+    five groups, the first of them three line-stream slices of whole groups; 23 groups of one pair five slices of groups; of 3
+    groups of 7 pairs every one is longer than a slice, so the VM kernels take them"""
+    n = gsz * groups
+    at = sorted(set(slice_edges(n) + slice_edges(n, CAP * gsz) + slice_edges(n, CAP // gsz * gsz or gsz)))
+    a, b, inf, _ = pair_world(n, at)
+    want = want_groups(oracle, a, b, inf, gsz, groups)
+    assert product_then_final(capped(CAP, **knobs), a, b, inf, gsz, groups) == want
+    assert product_then_final(engine, a, b, inf, gsz, groups) == want
+
+
+def test_batch_tree_under_the_cap(engine, capped, pair_world, oracle):
+    """blsgpu_pairing_multi_batch_dev with groups of 24 pairs: the per-group product tree"""
+    gsz, groups = 24, 2
+    n = gsz * groups
+    a, b, inf, _ = pair_world(n, sorted(set(slice_edges(n) + [gsz - 1, gsz, n - 1])))
+    want = want_groups(oracle, a, b, inf, gsz, groups)
+    for eng in (capped(CAP, **LS_RUNS), engine):
+        d_a, d_b, d_i, d_o = up(a), up(b), up(inf), blank(576 * groups)
+        eng.pairing_multi_batch_dev(d_a.data_ptr(), d_b.data_ptr(), gsz, groups, d_o.data_ptr(), 0, d_i.data_ptr())
+        assert down(d_o) == want
+
+
+@pytest.mark.parametrize("fast", [1, 0])
+@pytest.mark.parametrize("n", SIZES)
+def test_miller_loop_batch_in_slices(engine, capped, pair_world, oracle, n, fast):
+    """blsgpu_miller_loop_batch_dev on the fast form and on the reference's lines for every pair"""
+    a, b, inf, miller = pair_world(n, slice_edges(n), py_zero=True)
+    want = b"".join(miller[i] or oracle.miller_loop(a[96 * i:96 * (i + 1)], b[192 * i:192 * (i + 1)]) for i in range(n))
+    for eng in (capped(CAP, BLSGPU_MILLER_EXACT_FAST=fast), engine):
+        d_a, d_b, d_i, d_o = up(a), up(b), up(inf), blank(576 * n)
+        eng.miller_loop_batch_dev(d_a.data_ptr(), d_b.data_ptr(), n, d_o.data_ptr(), 0, d_i.data_ptr())
+        assert down(d_o) == want
