@@ -10,6 +10,19 @@ def hash256(m):
     return hashlib.sha256(_b(m)).digest()
 
 
+def hash256_batch(messages):
+    """[hash256(m) for m in messages]; messages: bytes, bytearray, memoryview or str each.  A provider that offers a hash256
+    extension (the list of bytes-like messages -> n x 32 digest bytes) gets the whole list in one call; without one -- the HIP
+    provider has none yet, and the host provider of the CPU tests never will -- this is exactly that loop."""
+    from . import backend
+    ms = [m.encode("utf-8") if isinstance(m, str) else m for m in messages]
+    fn = backend.extension("hash256") if ms else None
+    if fn is None:
+        return [hashlib.sha256(m).digest() for m in ms]
+    out = fn(ms)
+    return [out[32 * i:32 * (i + 1)] for i in range(len(ms))]
+
+
 def hash512(m):
     m = bytes(_b(m))
     return hash256(m + b"\x00") + hash256(m + b"\x01")
