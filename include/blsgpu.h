@@ -225,6 +225,33 @@ int blsgpu_pairing_multi_batch(blsgpu_ctx *ctx, const uint8_t *g1, const uint8_t
 int blsgpu_pairing_multi_batch_dev(blsgpu_ctx *ctx, const void *d_g1, const void *d_g2, const void *d_inf,
                                    size_t gsz, size_t groups, void *d_out, void *stream);
 
+/* RAGGED multi-pairing (csrc/blsgpu_mlr.hip; csrc/pairing_ranges_plan.h is its schedule):
+ * out[j] = fq_ate_pairing_multi of the pairs [begin_j, end_j) of ONE list of n pairs, for m ranges of ANY lengths, in one launch
+ * sequence and with nothing padded -- where blsgpu_pairing_multi_batch takes runs of one and the same gsz.  g1, g2, inf: the n
+ * pairs and their flag bytes, laid out as in blsgpu_pairing_multi_batch (inf may be NULL).  ranges: m x 2 uint32 (begin, end),
+ * begin <= end <= n; ranges may overlap, repeat or be empty, and each pays for its own chunks.  An empty range gives Fq12 one,
+ * as blsgpu_pairing_multi does for n == 0.  out: m x 576 bytes.  Every input the reference accepts (infinity, off-curve, zero
+ * and flagged points) gives the reference's bytes, as in every other pairing call.
+ * Every range is cut into chunks of at most 16 consecutive pairs (BLSGPU_PAIR_RANGES_CHUNK at context creation); the point
+ * chains of the line-stream stage run once per PAIR of the list (whether or not a range holds it: hand in the pairs the ranges
+ * use), one six-lane accumulator runs the Miller loop of one chunk, the chunks' partials of a range are multiplied in levels of
+ * 8, and one final exponentiation per range ends the call.  The pair list is processed in slices of 2^20 pairs (the line
+ * records cost 22.8 KB per pair); a range may span slices.
+ * The range table is a HOST pointer in BOTH forms: the whole schedule -- validation, chunks, fold levels, buffer sizes -- is
+ * host arithmetic on it, nothing is read back from the device and the _dev form does not synchronise.  The table may be
+ * released or changed as soon as the call returns.  The workspace (partials and tables) counts in BLSGPU_WS_TOTAL, the line
+ * records in BLSGPU_WS_LINES.
+ * -EINVAL before anything is written: a NULL required buffer (g1 or g2 with n > 0; ranges or out with m > 0), a range with
+ * begin > end or end > n, n > 0x3FFFFFF0, 2^31 chunks or more in all.  -ENOMEM when the line records cannot be allocated (this
+ * call has no other form to fall back to); every buffer is sized before the first launch.  m == 0 writes nothing and
+ * returns 0.  All of this is PUBLIC data: not constant-time. */
+int blsgpu_pairing_multi_ranges(blsgpu_ctx *ctx, const uint8_t *g1, const uint8_t *g2, const uint8_t *inf, size_t n,
+                                const uint32_t *ranges, size_t m, uint8_t *out);
+/* The same with the pairs, the flags and the results in device memory (points 16-byte aligned), on `stream`; `ranges` stays
+ * HOST memory. */
+int blsgpu_pairing_multi_ranges_dev(blsgpu_ctx *ctx, const void *d_g1, const void *d_g2, const void *d_inf, size_t n,
+                                    const uint32_t *ranges, size_t m, void *d_out, void *stream);
+
 /* Sharded form of the batch: every rank holds gsz pairs of each of the `groups`
  * multi-pairings.  Step 1 writes one partial per group (groups x
  * BLSGPU_PARTIAL_WORDS uint32).  Step 2 takes the all-gathered buffer of m ranks

@@ -122,6 +122,8 @@ PROTOTYPES = {
     "blsgpu_g2_msm_ranges": (vp, cp, cp, sz, vp, sz, vp, vp),
     "blsgpu_g1_msm_ranges_dev": (vp, vp, vp, sz, vp, sz, vp, vp, vp),
     "blsgpu_g2_msm_ranges_dev": (vp, vp, vp, sz, vp, sz, vp, vp, vp),
+    "blsgpu_pairing_multi_ranges": (vp, cp, cp, cp, sz, vp, sz, vp),
+    "blsgpu_pairing_multi_ranges_dev": (vp, vp, vp, vp, sz, vp, sz, vp, vp),
     "blsgpu_sig_divide": (vp, cp, sz, vp, sz, vp, cp, cp, sz, vp, vp, vp, vp, vp),
     "blsgpu_sig_divide_dev": (vp, vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp),
     "blsgpu_verify_find_folded": (vp, cp, cp, sz, vp, cp, sz, vp, cp, sz, vp, vp),

@@ -105,6 +105,9 @@ def use(provider):
     ent_dividend, ent_divisor) -> (m x 192 affine bytes, m flag bytes, n_pts status bytes, n_pts x 32 scalar bytes, (path, divisors
     with a quotient other than 1)) for m dividends whose points [pt_off[j], pt_off[j + 1]) are the dividend's own signature and
     then its divisors, and whose entries [ent_off[p], ent_off[p + 1]) carry the exponents of divisor p's tree.
+    Optional extension (without it BLS.verify_batch(ragged=True) raises; the default verify_batch does not use it):
+    pairing_multi_ranges(g1, g2, ranges, inf=None) -> m x 576 bytes, fq_ate_pairing_multi of the pairs [begin, end) of one
+    list of pairs for m ranges (begin, end) of any lengths.
     Extensions are looked up by extension(name), not by hasattr: a stand-in offers one as an attribute of that name, the
     HipProvider's come from EXTENSIONS.  Optional (without it PrivateKey.from_seed_batch and
     ExtendedPrivateKey.from_seed_batch run the per-seed host calls): keys_from_seeds(seeds, seed_len, n, hd) -> (key bytes,
@@ -128,18 +131,20 @@ MSM_RANGE_EXTENSIONS = {"g1_msm_ranges": "_native_msmr", "g2_msm_ranges": "_nati
 H2G1_EXTENSIONS = {"map_to_g1": "_native_h2g1", "hash_to_g1": "_native_h2g1"}
 # ... and the batched Signature.divide_by (Signature.divide_by_batch).
 SIGDIV_EXTENSIONS = {"sig_divide": "_native_sigdiv"}
+# ... and the multi-pairings over ranges of any lengths (BLS.verify_batch(ragged=True)).
+PAIR_RANGE_EXTENSIONS = {"pairing_multi_ranges": "_native_pairranges"}
 
 
 def extension(name):
     """The installed provider's extension `name`: the provider's own attribute of that name if it has one (stand-ins), for
-    a HipProvider the function of EXTENSIONS (or FIND_EXTENSIONS, RANGE_EXTENSIONS, MSM_RANGE_EXTENSIONS, H2G1_EXTENSIONS, SIGDIV_EXTENSIONS) bound to its
+    a HipProvider the function of EXTENSIONS (or FIND_EXTENSIONS, RANGE_EXTENSIONS, MSM_RANGE_EXTENSIONS, H2G1_EXTENSIONS, SIGDIV_EXTENSIONS, PAIR_RANGE_EXTENSIONS) bound to its
     engine, otherwise None."""
     prov = get()
     fn = getattr(prov, name, None)
     if fn is not None:
         return fn
     where = (EXTENSIONS.get(name) or FIND_EXTENSIONS.get(name) or RANGE_EXTENSIONS.get(name) or MSM_RANGE_EXTENSIONS.get(name)
-             or H2G1_EXTENSIONS.get(name) or SIGDIV_EXTENSIONS.get(name))
+             or H2G1_EXTENSIONS.get(name) or SIGDIV_EXTENSIONS.get(name) or PAIR_RANGE_EXTENSIONS.get(name))
     if isinstance(prov, HipProvider) and where:
         import functools
         import importlib

@@ -163,13 +163,22 @@ class BLS:
         return out == Fq12.one(default_ec.q).serialize()
 
     @staticmethod
-    def verify_batch(signatures):
+    def verify_batch(signatures, ragged=False):
         """[BLS.verify(s) for s in signatures] with every GPU step batched across the
         signatures: one hash-to-G2 call for all distinct (signature, message) pairs, one call
         for all per-message key sums, and blsgpu_pairing_multi_batch per distinct pair count
-        (independent multi-pairings side by side).  Same results as verify, one by one."""
+        (independent multi-pairings side by side).  Same results as verify, one by one.
+        ragged=True: ONE pair list with one range per aggregate and one call of the pairing_multi_ranges
+        extension (blsgpu_pairing_multi_ranges) in place of the call per distinct pair count; a provider
+        without the extension raises.  Not the default: which is faster is measured by
+        tools/pair_ranges_probe.py, and routing is a later decision."""
         from . import backend
         prov = backend.get()
+        ranges_fn = None
+        if ragged:
+            ranges_fn = backend.extension("pairing_multi_ranges")
+            if ranges_fn is None:
+                raise NotImplementedError("verify_batch(ragged=True) needs a provider with the pairing_multi_ranges extension")
         ONE = Fq12.one(default_ec.q).serialize()
         results = [None] * len(signatures)
         plans = []                                        # (index, message hashes, key groups, exponent groups)
@@ -194,6 +203,21 @@ class BLS:
         Qs = hash_to_points_prehashed_Fq2(all_hashes)
         Ps = _g1_sums([g for _, _, kg, _ in plans for g in kg], [e for _, _, _, eg in plans for e in eg])
         neg_g1 = H.g1_affine_bytes((generator_Fq() * (GROUP_ORDER - 1))._aff())
+        if ragged:
+            # -G1 / sig first, then the per-message keys and hashes, aggregate after aggregate: one range each
+            g1s, g2s, ranges, pos = [], [], [], 0
+            for i, mhs, _, _ in plans:
+                k = len(mhs)
+                g1s.append(neg_g1 + b"".join(H.g1_affine_bytes(p.to_affine()._aff()) for p in Ps[pos:pos + k]))
+                g2s.append(H.g2_affine_bytes(signatures[i].value.to_affine()._aff()) +
+                           b"".join(H.g2_affine_bytes(q._aff()) for q in Qs[pos:pos + k]))
+                lo = ranges[-1][1] if ranges else 0
+                ranges.append((lo, lo + k + 1))
+                pos += k
+            out = ranges_fn(b"".join(g1s), b"".join(g2s), ranges)
+            for j, (i, _, _, _) in enumerate(plans):
+                results[i] = out[576 * j:576 * (j + 1)] == ONE
+            return results
         by_size, pos = {}, 0
         for i, mhs, _, _ in plans:
             k = len(mhs)

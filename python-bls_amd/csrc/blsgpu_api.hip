@@ -18,6 +18,7 @@
 #include "blsgpu_kernels.hip"
 #include "fp28.h"
 #include "blsgpu_ml.hip"
+#include "blsgpu_mlr.hip"
 #include "blsgpu_fexp.hip"
 #include "blsgpu_fexpw.hip"
 #include "blsgpu_mlw.hip"
@@ -47,6 +48,7 @@
 #include "bisect_plan.h"
 #include "msm_plan.h"
 #include "pairing_plan.h"
+#include "pairing_ranges_plan.h"
 #include "blsgpu_ctx.h"
 
 // Which kernels a pairing call runs, its partials, chunks, levels, slices and buffer sizes are pairing_plan.h (host-only: tested
@@ -1909,6 +1911,8 @@ BLSGPU_EXPORT void blsgpu_ctx_destroy(blsgpu_ctx* c) {
         if (b.p) (void)hipFree(b.p);
     for (void* q : c->retired) (void)hipFree(q);
     if (c->last_event) (void)hipEventDestroy(c->last_event);
+    if (c->pin_event) (void)hipEventDestroy(c->pin_event);
+    if (c->pin) (void)hipHostFree(c->pin);
     if (c->ev0) {
         for (int i = 0; i < blsgpu_ctx::TIMING_SLOTS; i++) { (void)hipEventDestroy(c->ev0[i]); (void)hipEventDestroy(c->ev1[i]); }
         delete[] c->ev0; delete[] c->ev1; delete[] c->ev_kind;
@@ -2211,20 +2215,16 @@ static int launch_miller(blsgpu_ctx* c, const void* d_g1, const void* d_g2, cons
     return 0;
 }
 
-// The line-stream form of launch_miller (blsgpu_ml.hip, pairing::plan_ls): ONE partial per group comes out (bpg = 1).
-// d_fused_out (optional): the caller wants nothing but the final exponentiation of each group's product -- the kernel
-// that ends the stage (k_ml_horner_fexp) then goes on to it in place: no partial, no further launch; *fused tells.
-// one_per_group: one accumulator per group whatever ls_min_group says (blsgpu_miller_loop_batch_dev: a group is a pair).
-static int launch_miller_ls(blsgpu_ctx* c, const void* d_g1, const void* d_g2, const void* d_inf, size_t gsz, size_t groups,
-                            uint32_t* d_partials, hipStream_t st, void* d_fused_out = nullptr, bool* fused = nullptr,
-                            bool one_per_group = false) {
+// The chain part of the line-stream stage, shared by launch_miller_ls and the ragged multi-pairing: room for the line records,
+// the flags and the work list of p.n pairs, the work list reset, the point chains on the kernel plan_ls chose and the listed
+// pairs once more with the reference's own formulas.  Leaves 68 line records and a `bad` flag per pair in B_LINES / B_BAD.
+// -ENOMEM (nothing enqueued): the buffers cannot be had.
+static int launch_ls_chains(blsgpu_ctx* c, const pairing::LsPlan& p, const void* d_g1, const void* d_g2, const void* d_inf, hipStream_t st) {
     using namespace blsgpu;
-    const pairing::LsPlan p = pairing::plan_ls(*c, PAIRING_CONSTS, gsz, groups, one_per_group, d_fused_out != nullptr);
-    if (c->test_ls_nomem ||                                // tests/test_gpu_alternate_forms.py: the fallback below, without exhausting a GPU
-        c->grow(B_LINES, p.lines_bytes) || c->grow(B_LSP0, p.lsp0_bytes) || c->grow(B_LSP1, p.lsp1_bytes) || c->grow(B_BAD, p.bad_bytes) ||
-        c->grow(B_DEGEN, p.degen_bytes)) {
+    if (c->test_ls_nomem ||                                // tests/test_gpu_alternate_forms.py: the callers' -ENOMEM paths, without exhausting a GPU
+        c->grow(B_LINES, p.lines_bytes) || c->grow(B_BAD, p.bad_bytes) || c->grow(B_DEGEN, p.degen_bytes)) {
         (void)hipGetLastError();
-        return -ENOMEM;                                    // the caller falls back to the wavefront-VM kernels
+        return -ENOMEM;
     }
     const uint32_t *g1 = (const uint32_t*)d_g1, *g2 = (const uint32_t*)d_g2, n = (uint32_t)p.n;
     int32_t* const lines = c->at<int32_t>(B_LINES);
@@ -2250,6 +2250,26 @@ static int launch_miller_ls(blsgpu_ctx* c, const void* d_g1, const void* d_g2, c
         hipLaunchKernelGGL(ml::k_ml_lines_exact, dim3(2048), dim3(64), 0, st, g1, g2, n, lines, bad, dg, 0u, 0u, 0u);
     }
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The line-stream form of launch_miller (blsgpu_ml.hip, pairing::plan_ls): ONE partial per group comes out (bpg = 1).
+// d_fused_out (optional): the caller wants nothing but the final exponentiation of each group's product -- the kernel
+// that ends the stage (k_ml_horner_fexp) then goes on to it in place: no partial, no further launch; *fused tells.
+// one_per_group: one accumulator per group whatever ls_min_group says (blsgpu_miller_loop_batch_dev: a group is a pair).
+static int launch_miller_ls(blsgpu_ctx* c, const void* d_g1, const void* d_g2, const void* d_inf, size_t gsz, size_t groups,
+                            uint32_t* d_partials, hipStream_t st, void* d_fused_out = nullptr, bool* fused = nullptr,
+                            bool one_per_group = false) {
+    using namespace blsgpu;
+    const pairing::LsPlan p = pairing::plan_ls(*c, PAIRING_CONSTS, gsz, groups, one_per_group, d_fused_out != nullptr);
+    if (!c->test_ls_nomem && (c->grow(B_LSP0, p.lsp0_bytes) || c->grow(B_LSP1, p.lsp1_bytes))) {
+        (void)hipGetLastError();
+        return -ENOMEM;                                    // the caller falls back to the wavefront-VM kernels
+    }
+    if (int rc = launch_ls_chains(c, p, d_g1, d_g2, d_inf, st)) return rc;   // (-ENOMEM likewise)
+    const uint32_t n = (uint32_t)p.n;
+    int32_t* const lines = c->at<int32_t>(B_LINES);
+    uint8_t* const bad = c->at<uint8_t>(B_BAD);
     if (p.small) {
         {
             KernelTimer kt(c, st, 5);
@@ -2602,6 +2622,101 @@ BLSGPU_EXPORT int blsgpu_pairing_multi_batch(blsgpu_ctx* c, const uint8_t* g1, c
     if (int rc = s.alloc()) return rc;
     if (int rc = s.up()) return rc;
     if (int rc = blsgpu_pairing_multi_batch_dev(c, s.at(d1), s.at(d2), s.opt(di), gsz, groups, s.at(dout), nullptr)) return rc;
+    return s.down();
+}
+
+// The RAGGED multi-pairing: out[j] = fq_ate_pairing_multi of the pairs [begin_j, end_j) of one list, for m ranges of any lengths
+// in one launch sequence (pairing_ranges_plan.h is the whole schedule, host arithmetic on the caller's HOST range table; nothing
+// is read back).  Per slice of the pair list the point chains and k_ml_ranges -- one six-lane team per chunk of at most
+// pair_ranges_chunk pairs --, after the last slice the fold levels, then the final exponentiation of one partial per range.
+namespace {
+// the argument checks, before anything is written; 1: nothing to do
+int pairing_ranges_args(const blsgpu_ctx* c, const void* g1, const void* g2, size_t n, const uint32_t* ranges, size_t m, const void* out) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (m == 0) return 1;
+    if (!ranges || !out) return fail(-EINVAL, "NULL argument");
+    if (n && (!g1 || !g2)) return fail(-EINVAL, "NULL point buffer");
+    return 0;
+}
+int pairing_ranges_refuse(const pairing_ranges::Plan& p) { return fail(pairing_ranges::refusal_code(p.refusal), pairing_ranges::refusal_text(p.refusal)); }
+
+int pairing_ranges_launch(blsgpu_ctx* c, const pairing_ranges::Plan& p, const void* d_g1, const void* d_g2, const void* d_inf, void* d_out,
+                          hipStream_t st) {
+    using namespace blsgpu;
+    // every buffer of every slice before the first launch: a later slice cannot fail after an earlier one wrote.  No memory for
+    // the line records is this call's error -- it has no wavefront-VM form to fall back to.
+    if (p.lines_bytes && (c->test_ls_nomem || c->grow(B_LINES, p.lines_bytes) || c->grow(B_BAD, p.bad_bytes) || c->grow(B_DEGEN, p.degen_bytes))) {
+        (void)hipGetLastError();
+        return fail(-ENOMEM, "no memory for the line records");
+    }
+    if (int rc = c->grow(B_PAIRR_WS, p.ws_bytes)) return rc;
+    const pairing::FexpForm form = pairing::fexp_form(*c, PAIRING_CONSTS, 1, p.m < p.final_step ? p.m : p.final_step);
+    if (form.kind == pairing::FEXP_TEAM) {                   // (launch_fexp grows it again: nothing to do then)
+        const WaveShape ws = wave_shape(c, form.waves);
+        if (int rc = c->grow(B_FEXP_WS, (size_t)ws.blocks * (ws.threads / 64) * form.ws_bytes_per_wave)) return rc;
+    }
+    char* const W = c->at<char>(B_PAIRR_WS);
+    uint32_t* const partials = (uint32_t*)(W + p.o_partials);
+    {   // the tables: written to pinned memory that outlives the enqueue, one asynchronous upload
+        PinnedTables pin(c);
+        void* image = nullptr;
+        if (int rc = pin.take(p.ws_bytes - p.o_tables, &image)) return rc;
+        p.fill_tables(image);
+        if (int rc = pin.upload(W + p.o_tables, p.ws_bytes - p.o_tables, st)) return rc;
+    }
+    for (const pairing_ranges::Slice& s : p.slices) {
+        if (!s.nchunks) continue;
+        if (s.chains) {
+            const PairArrays a = pairs_at(d_g1, d_g2, d_inf, s.lo);
+            if (int rc = launch_ls_chains(c, s.ls, a.g1, a.g2, a.inf, st)) return rc == -ENOMEM ? fail(rc, "no memory for the line records") : rc;
+        }
+        {
+            KernelTimer kt(c, st, 5);
+            const WaveShape ws = wave_shape(c, s.waves);
+            hipLaunchKernelGGL(ml::k_ml_ranges, dim3(ws.blocks), dim3(ws.threads), 0, st, c->at<int32_t>(B_LINES), c->at<uint8_t>(B_BAD),
+                               (uint32_t)(s.chains ? s.pairs : 0), (const uint32_t*)(W + s.tab_off), (uint32_t)s.nchunks, partials);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    if (c->bulk_event) HIP_TRY(hipEventRecord(c->bulk_event, st));
+    for (const pairing_ranges::Level& l : p.levels) {
+        KernelTimer kt(c, st, 6);
+        const WaveShape ws = wave_shape(c, l.waves);
+        hipLaunchKernelGGL(ml::k_ml_fold_ranges, dim3(ws.blocks), dim3(ws.threads), 0, st, partials, (const uint32_t*)(W + l.tab_off), (uint32_t)l.nfolds);
+        HIP_TRY(hipGetLastError());
+    }
+    // one partial per result; more results than one launch takes go in slices (as the groups of blsgpu_pairing_multi_batch)
+    return for_slices(p.m, p.final_step, [&](size_t lo, size_t mm) {
+        return launch_final(c, pairing::fexp_form(*c, PAIRING_CONSTS, 1, mm), (const uint32_t*)result_at(partials, lo), 1, 1, 1, mm, result_at(d_out, lo), st);
+    });
+}
+}  // namespace
+
+BLSGPU_EXPORT int blsgpu_pairing_multi_ranges_dev(blsgpu_ctx* c, const void* d_g1, const void* d_g2, const void* d_inf, size_t n,
+                                                  const uint32_t* ranges, size_t m, void* d_out, void* stream) {
+    if (int rc = pairing_ranges_args(c, d_g1, d_g2, n, ranges, m, d_out)) return rc < 0 ? rc : 0;
+    const pairing_ranges::Plan p = pairing_ranges::plan(n, ranges, m, *c, *c, PAIRING_CONSTS, pairing_limits(c));
+    if (p.refusal) return pairing_ranges_refuse(p);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    StreamGuard sg(c, st);
+    return pairing_ranges_launch(c, p, d_g1, d_g2, d_inf, d_out, st);
+}
+
+BLSGPU_EXPORT int blsgpu_pairing_multi_ranges(blsgpu_ctx* c, const uint8_t* g1, const uint8_t* g2, const uint8_t* inf, size_t n,
+                                              const uint32_t* ranges, size_t m, uint8_t* out) {
+    if (int rc = pairing_ranges_args(c, g1, g2, n, ranges, m, out)) return rc < 0 ? rc : 0;
+    const pairing_ranges::Plan p = pairing_ranges::plan(n, ranges, m, *c, *c, PAIRING_CONSTS, pairing_limits(c));
+    if (p.refusal) return pairing_ranges_refuse(p);
+    HIP_TRY(hipSetDevice(c->device));
+    Staging s(c);
+    const int d1 = s.in(g1, n * BLSGPU_G1_BYTES), d2 = s.in(g2, n * BLSGPU_G2_BYTES), di = s.in(inf, n * 2), dout = s.out(out, m * 576);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    {
+        StreamGuard sg(c, nullptr);
+        if (int rc = pairing_ranges_launch(c, p, s.at(d1), s.at(d2), s.opt(di), s.at(dout), nullptr)) return rc;
+    }
     return s.down();
 }
 

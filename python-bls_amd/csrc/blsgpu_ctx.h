@@ -73,6 +73,7 @@ enum BufId {
     B_PSCAN_G2,          // ... the same for blsgpu_g2_range_sums* and SA
     B_PSCAN_RANGE,       // blsgpu_g?_range_sums*: a flag word and, when the points take several slices, the record and count at every range's begin
     B_SIGDIV_WS,         // blsgpu_sig_divide*: the head words, the mismatch / zero / non-unit / status bytes per point, the refused byte and the range per dividend, the scalars and the working copy of the points
+    B_PAIRR_WS,          // blsgpu_pairing_multi_ranges*: the partials (a slot per range, then the slots of the folds), every slice's chunk table and every fold level's table (pairing_ranges_plan.h)
     B_COUNT
 };
 // (unit: what the buffer is counted in -- whole partials, whole u32 entries, bytes)
@@ -82,12 +83,13 @@ constexpr BufInfo BUF_INFO[B_COUNT] = {
     {BLSGPU_WS_LINE_PRODUCTS, 1}, {BLSGPU_WS_LINE_PRODUCTS, 1}, {BLSGPU_WS_FLAGS_AND_LISTS, 1}, {BLSGPU_WS_FLAGS_AND_LISTS, 4},
     {BLSGPU_WS_FLAGS_AND_LISTS, 1}, {BLSGPU_WS_GROUP_SUMS, 4}, {BLSGPU_WS_GROUP_SUMS, 4}, {BLSGPU_WS_SLOTS, 1}, {BLSGPU_WS_SLOTS, 1},
     {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1},
-    {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}};   // no field of their own: they count in the total only
+    {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}};   // no field of their own: they count in the total only
 
 }  // namespace
 
-// (the knobs of the G1 / G2 sums are msm::Knobs, msm_plan.h; those of the pairing path pairing::Knobs, pairing_plan.h)
-struct blsgpu_ctx : msm::Knobs, pairing::Knobs {
+// (the knobs of the G1 / G2 sums are msm::Knobs, msm_plan.h; those of the pairing path pairing::Knobs, pairing_plan.h, and
+// pairing_ranges::Knobs, pairing_ranges_plan.h)
+struct blsgpu_ctx : msm::Knobs, pairing::Knobs, pairing_ranges::Knobs {
     int device = 0;
     blsgpu::VmTables tabs{};
     void* d_tables = nullptr;          // one allocation holding every table
@@ -133,6 +135,12 @@ struct blsgpu_ctx : msm::Knobs, pairing::Knobs {
     hipStream_t last_stream = nullptr;
     hipEvent_t last_event = nullptr;
     bool used = false;
+    // Pinned host memory for tables a call computes on the host and uploads with hipMemcpyAsync (PinnedTables): it outlives
+    // the enqueue, and pin_event -- recorded behind the copy -- is waited for before the next call writes it again.
+    void* pin = nullptr;
+    size_t pin_cap = 0;
+    hipEvent_t pin_event = nullptr;
+    bool pin_busy = false;
 };
 
 namespace {
@@ -189,6 +197,7 @@ const Knob KNOBS[] = {
     {"BLSGPU_MSM_LANE_THRESHOLD", &blsgpu_ctx::msm_lane_threshold},
     {"BLSGPU_MSM_LANE_PAIRS", &blsgpu_ctx::msm_lane_pairs},
     {"BLSGPU_SIGDIV_PLAIN", &blsgpu_ctx::sigdiv_plain},
+    {"BLSGPU_PAIR_RANGES_CHUNK", &blsgpu_ctx::pair_ranges_chunk},
 };
 void read_knobs(blsgpu_ctx* c) {
     for (const Knob& k : KNOBS)
@@ -270,6 +279,32 @@ struct Staging {
             const size_t bytes = m ? m * r[i].item : (r[i].item ? 0 : r[i].bytes);
             if (r[i].dst && bytes) HIP_TRY(hipMemcpy(r[i].dst + lo * r[i].item, at(i), bytes, hipMemcpyDeviceToHost));
         }
+        return 0;
+    }
+};
+
+// Tables written by the host for an asynchronous upload: take(bytes) waits for the previous upload from the context's pinned
+// block, grows it if need be and hands it out; upload() copies it to the device on `st` and records the event the next take()
+// waits for.  The block is freed by blsgpu_ctx_destroy alone, so it outlives everything enqueued from it.
+struct PinnedTables {
+    blsgpu_ctx* c;
+    explicit PinnedTables(blsgpu_ctx* c_) : c(c_) {}
+    int take(size_t bytes, void** out) {
+        if (c->pin_busy) { HIP_TRY(hipEventSynchronize(c->pin_event)); c->pin_busy = false; }
+        if (bytes > c->pin_cap) {
+            void* n = nullptr;
+            HIP_TRY(hipHostMalloc(&n, bytes + bytes / 4, hipHostMallocDefault));
+            if (c->pin) (void)hipHostFree(c->pin);
+            c->pin = n, c->pin_cap = bytes + bytes / 4;
+        }
+        if (!c->pin_event) HIP_TRY(hipEventCreateWithFlags(&c->pin_event, hipEventDisableTiming));
+        *out = c->pin;
+        return 0;
+    }
+    int upload(void* d_dst, size_t bytes, hipStream_t st) {
+        HIP_TRY(hipMemcpyAsync(d_dst, c->pin, bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(c->pin_event, st));
+        c->pin_busy = true;
         return 0;
     }
 };

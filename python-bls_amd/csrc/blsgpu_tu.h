@@ -18,6 +18,7 @@
                             // membership, Lagrange coefficients, the scalar-field work on secrets (dealing, recovery, threshold
                             // signing), the exponents of secure aggregation, the glue of the signature-share check and of the
                             // batch verification that names the forgeries, the quotient scalars of Signature.divide_by
+#define BLSGPU_TU_MLR 9     // blsgpu_mlr.hip: the accumulate and fold stages of the ragged multi-pairing
 #ifndef BLSGPU_TU
 #define BLSGPU_TU 0
 #endif
