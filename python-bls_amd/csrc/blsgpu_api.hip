@@ -49,6 +49,7 @@
 #include "msm_plan.h"
 #include "pairing_plan.h"
 #include "pairing_ranges_plan.h"
+#include "ragged_plan.h"
 #include "blsgpu_ctx.h"
 
 // Which kernels a pairing call runs, its partials, chunks, levels, slices and buffer sizes are pairing_plan.h (host-only: tested
@@ -149,6 +150,9 @@ constexpr msm::Consts MSM_CONSTS = {blsgpu::SRT_LANES, blsgpu::SRT_SCW, blsgpu::
                                     {blsgpu::SrtG<1>::AFF, blsgpu::SrtG<2>::AFF}, {blsgpu::SrtG<1>::PJ, blsgpu::SrtG<2>::PJ}};
 static_assert(msm::same(MSM_CONSTS, msm::GFX950), "msm_plan.h: GFX950 (the host test's values) differs from the kernel files");
 static_assert(sizeof(msm::SortedPlan::bias) == sizeof(blsgpu::SrtBias), "msm_plan.h: SortedPlan::bias is not SRT_SCW words");
+// ... and ragged_plan.h (the range sums, the ragged sums, the short scalars and the signature division below)
+constexpr ragged::Consts RAGGED_CONSTS = {blsgpu::pscan::CHUNK, blsgpu::pscan::MID_THREADS, blsgpu::msmr::CHUNK, blsgpu::msmr::SCAN_THREADS};
+static_assert(ragged::same(RAGGED_CONSTS, ragged::GFX950), "ragged_plan.h: GFX950 (the host test's values) differs from the kernel files");
 
 // The wide machine's Horner (blsgpu_msmw.hip): list g of `lists` -> sum_i 2^(cbits i) in[g][i], one wavefront per list; AFFINE = 0
 // leaves projective sums for the next step, AFFINE = 1 writes the caller's affine point and its infinity flag.
@@ -988,27 +992,21 @@ int sig_shares_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_t
 template <int DEG>
 int smul64_launch(blsgpu_ctx* c, const void* d_pts, size_t n_pts, const void* d_idx, const void* d_w, size_t n, void* d_out, void* d_out_inf,
                   hipStream_t st) {
-    typedef blsgpu::SrtG<DEG> G;
-    const size_t upw = 64 / G::LP, S = slice_len(c, blsgpu::SRT_LANES / G::LP);
-    const size_t m0 = n < S ? n : S, units0 = (m0 + upw - 1) / upw * upw, np0 = d_idx ? n_pts : m0;
-    ws::Layout l{4, 0};                                       // (words)
-    const size_t o_prep = l.take(np0 * blsgpu::L28_AFF * DEG), o_live = l.take((np0 + 3) / 4), o_tab = l.take(units0 * blsgpu::SMUL_T * G::PJ);
-    if (int rc = c->grow(B_SM64_WS, l.off * 4)) return rc;
+    const ragged::Smul64Plan p = ragged::plan_smul64(*c, MSM_CONSTS, DEG, n_pts, n, d_idx != nullptr);
+    if (int rc = c->grow(B_SM64_WS, p.words * 4)) return rc;
     uint32_t* W = c->at<uint32_t>(B_SM64_WS);
-    uint8_t* live = (uint8_t*)(W + o_live);
+    uint8_t* live = (uint8_t*)(W + p.o_live);
     if (d_idx) {
-        hipLaunchKernelGGL(blsgpu::k_lane_prep<DEG>, dim3((unsigned)((n_pts + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_pts, (uint32_t)n_pts,
-                           W + o_prep, live);
+        hipLaunchKernelGGL(blsgpu::k_lane_prep<DEG>, dim3(p.g_prep_all), dim3(256), 0, st, (const uint32_t*)d_pts, (uint32_t)n_pts, W + p.o_prep, live);
         HIP_TRY(hipGetLastError());
     }
-    return for_slices(n, S, [&](size_t lo, size_t m) {
+    return for_slices(n, p.S, [&](size_t lo, size_t) {
+        const ragged::Smul64Slice s = p.at(lo);
         if (!d_idx)
-            hipLaunchKernelGGL(blsgpu::k_lane_prep<DEG>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_pts + lo * 24 * DEG,
-                               (uint32_t)m, W + o_prep, live);
-        const size_t units = (m + upw - 1) / upw * upw;
-        hipLaunchKernelGGL(blsgpu::k_smul64<DEG>, dim3((unsigned)(units * G::LP / 64)), dim3(64), 0, st, W + o_prep, live,
-                           d_idx ? (const uint32_t*)d_idx + lo : nullptr, (const uint8_t*)d_w + lo * 8, (uint32_t)m, W + o_tab,
-                           (uint32_t*)d_out + lo * 24 * DEG, d_out_inf ? (uint8_t*)d_out_inf + lo : nullptr);
+            hipLaunchKernelGGL(blsgpu::k_lane_prep<DEG>, dim3(s.g_prep), dim3(256), 0, st, (const uint32_t*)d_pts + s.pts, (uint32_t)s.m, W + p.o_prep, live);
+        hipLaunchKernelGGL(blsgpu::k_smul64<DEG>, dim3(s.g_smul), dim3(64), 0, st, W + p.o_prep, live,
+                           d_idx ? (const uint32_t*)d_idx + lo : nullptr, (const uint8_t*)d_w + s.w, (uint32_t)s.m, W + p.o_tab,
+                           (uint32_t*)d_out + s.out, d_out_inf ? (uint8_t*)d_out_inf + lo : nullptr);
         HIP_TRY(hipGetLastError());
         return 0;
     });
@@ -1206,19 +1204,14 @@ int verify_find_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_
 // One scan's workspace (B_PSCAN_G1 / B_PSCAN_G2): the prepared points of a slice, their live and kind bytes, the chunk totals
 // and counts, the n + 1 prefix records and counts, and the carry into the next slice.
 struct PscanWs { uint32_t *prep, *ct, *cb, *s, *cnt, *carry, *carryc; uint8_t *live, *kind; };
-constexpr size_t PSCAN_RECORD_BYTES = ((size_t)2 << 30) - ((size_t)1 << 20);    // what the prefix records of one slice may take
-template <int DEG> constexpr size_t pscan_slice() { return PSCAN_RECORD_BYTES / (blsgpu::L28_PJ * DEG * 4) - 1; }   // points
 template <int DEG>
 int pscan_ws(blsgpu_ctx* c, size_t pts, PscanWs& w) {
-    const size_t PJ = blsgpu::L28_PJ * DEG, chunks = pts ? (pts + blsgpu::pscan::CHUNK - 1) / blsgpu::pscan::CHUNK : 1;
-    ws::Layout l{256, 0};                                     // (bytes)
-    const size_t o_prep = l.take(pts * blsgpu::L28_AFF * DEG * 4), o_live = l.take(pts), o_kind = l.take(pts), o_ct = l.take(chunks * PJ * 4),
-                 o_cb = l.take(chunks * 4), o_s = l.take((pts + 1) * PJ * 4), o_cnt = l.take((pts + 1) * 4), o_carry = l.take(PJ * 4), o_cc = l.take(4);
+    const ragged::ScanWs o = ragged::scan_ws(MSM_CONSTS, RAGGED_CONSTS, DEG, pts);
     const BufId id = DEG == 1 ? B_PSCAN_G1 : B_PSCAN_G2;
-    if (int rc = c->grow(id, l.off)) return rc;
+    if (int rc = c->grow(id, o.bytes)) return rc;
     char* const W = c->at<char>(id);
-    w = {(uint32_t*)(W + o_prep), (uint32_t*)(W + o_ct), (uint32_t*)(W + o_cb), (uint32_t*)(W + o_s), (uint32_t*)(W + o_cnt),
-         (uint32_t*)(W + o_carry), (uint32_t*)(W + o_cc), (uint8_t*)(W + o_live), (uint8_t*)(W + o_kind)};
+    w = {(uint32_t*)(W + o.o_prep), (uint32_t*)(W + o.o_ct), (uint32_t*)(W + o.o_cb), (uint32_t*)(W + o.o_s), (uint32_t*)(W + o.o_cnt),
+         (uint32_t*)(W + o.o_carry), (uint32_t*)(W + o.o_cc), (uint8_t*)(W + o.o_live), (uint8_t*)(W + o.o_kind)};
     return 0;
 }
 // enqueues the prefix records of the m points at d_pts (one slice) into w; `first`: no carry comes in; `more`: the last record
@@ -1226,12 +1219,13 @@ int pscan_ws(blsgpu_ctx* c, size_t pts, PscanWs& w) {
 template <int DEG>
 int pscan_launch(const PscanWs& w, const void* d_pts, size_t m, bool first, bool more, hipStream_t st) {
     namespace ps = blsgpu::pscan;
-    const size_t PJ = blsgpu::L28_PJ * DEG, chunks = m ? (m + ps::CHUNK - 1) / ps::CHUNK : 1;
-    if (m) hipLaunchKernelGGL(blsgpu::k_lane_prep<DEG>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_pts, (uint32_t)m, w.prep, w.live);
-    hipLaunchKernelGGL(ps::k_pscan_totals<DEG>, dim3((unsigned)((chunks + 63) / 64)), dim3(64), 0, st, w.prep, w.live, (uint32_t)m, w.kind, w.ct, w.cb);
-    hipLaunchKernelGGL(ps::k_pscan_mid<DEG>, dim3(1), dim3(ps::MID_THREADS), 0, st, w.ct, w.cb, (uint32_t)chunks, first ? nullptr : w.carry,
+    const size_t PJ = blsgpu::L28_PJ * DEG;
+    const ragged::ScanGrids g = ragged::scan_grids(RAGGED_CONSTS, m);
+    if (m) hipLaunchKernelGGL(blsgpu::k_lane_prep<DEG>, dim3(g.g_prep), dim3(256), 0, st, (const uint32_t*)d_pts, (uint32_t)m, w.prep, w.live);
+    hipLaunchKernelGGL(ps::k_pscan_totals<DEG>, dim3(g.g_chunks), dim3(64), 0, st, w.prep, w.live, (uint32_t)m, w.kind, w.ct, w.cb);
+    hipLaunchKernelGGL(ps::k_pscan_mid<DEG>, dim3(1), dim3(ps::MID_THREADS), 0, st, w.ct, w.cb, (uint32_t)g.chunks, first ? nullptr : w.carry,
                        first ? nullptr : w.carryc);
-    hipLaunchKernelGGL(ps::k_pscan_replay<DEG>, dim3((unsigned)((chunks + 63) / 64)), dim3(64), 0, st, w.prep, w.kind, (uint32_t)m, w.ct, w.cb, w.s, w.cnt);
+    hipLaunchKernelGGL(ps::k_pscan_replay<DEG>, dim3(g.g_chunks), dim3(64), 0, st, w.prep, w.kind, (uint32_t)m, w.ct, w.cb, w.s, w.cnt);
     HIP_TRY(hipGetLastError());
     if (more) {
         HIP_TRY(hipMemcpyAsync(w.carry, w.s + m * PJ, PJ * 4, hipMemcpyDeviceToDevice, st));
@@ -1244,8 +1238,7 @@ int pscan_launch(const PscanWs& w, const void* d_pts, size_t m, bool first, bool
 template <int DEG>
 int pscan_ranges_launch(const PscanWs& w, size_t lo, size_t hi, bool last, const void* d_ranges, size_t m, const uint32_t* base,
                         const uint32_t* basec, void* d_out, void* d_flag, hipStream_t st) {
-    const size_t lanes = m * blsgpu::SrtG<DEG>::LP;
-    hipLaunchKernelGGL(blsgpu::pscan::k_pscan_range<DEG>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, w.s, w.cnt, (uint32_t)lo, (uint32_t)hi,
+    hipLaunchKernelGGL(blsgpu::pscan::k_pscan_range<DEG>, dim3(ragged::range_blocks(MSM_CONSTS, DEG, m)), dim3(64), 0, st, w.s, w.cnt, (uint32_t)lo, (uint32_t)hi,
                        last ? 1u : 0u, (const uint32_t*)d_ranges, (uint32_t)m, base, basec, (uint32_t*)d_out, (uint8_t*)d_flag);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1254,10 +1247,10 @@ int pscan_ranges_launch(const PscanWs& w, size_t lo, size_t hi, bool last, const
 int range_sums_args(const blsgpu_ctx* c, const void* pts, size_t n, const void* ranges, size_t m, const void* out, const void* flag) {
     if (!c) return fail(-EINVAL, "ctx is NULL");
     if ((n && !pts) || (m && (!ranges || !out || !flag))) return fail(-EINVAL, "NULL argument");
-    if (n > 0xFFFFFFF0ull || m > 0x7FFFFFF0ull / blsgpu::SrtG<2>::LP) return fail(-EINVAL, "batch too large");
+    if (ragged::too_large(MSM_CONSTS, n, m)) return fail(-EINVAL, "batch too large");
     return m == 0 ? 1 : 0;
 }
-// Points in slices of pscan_slice<DEG>() whose records carry on from the slice before; a range is finished in the slice that
+// Points in slices (ragged::plan_scan) whose records carry on from the slice before; a range is finished in the slice that
 // holds its end.  With more than one slice the record at a range's begin is copied beside the range (B_PSCAN_RANGE) while its
 // slice is there.  `scan`: the _dev form's device scan of the ranges first -- one synchronisation, before anything is written.
 template <int DEG>
@@ -1273,44 +1266,37 @@ template <int DEG>
 int range_sums_run(blsgpu_ctx* c, const void* d_pts, size_t n, const void* d_ranges, size_t m, void* d_out, void* d_flag, bool scan,
                    hipStream_t st) {
     namespace ps = blsgpu::pscan;
-    const size_t PJ = blsgpu::L28_PJ * DEG, SL = slice_len(c, pscan_slice<DEG>()), S = n < SL ? n : SL;
-    const bool single = n <= SL;
-    const size_t o_base = 256, o_basec = o_base + ((single ? 0 : m * PJ * 4 + 255) & ~(size_t)255);
-    if (int rc = c->grow(B_PSCAN_RANGE, o_basec + (single ? 0 : m * 4))) return rc;
+    const ragged::ScanPlan p = ragged::plan_scan(*c, MSM_CONSTS, RAGGED_CONSTS, DEG, n, m);
+    if (int rc = c->grow(B_PSCAN_RANGE, p.range_bytes)) return rc;
     char* const R = c->at<char>(B_PSCAN_RANGE);
     if (scan) {
         uint32_t bad = 0;
         if (int rc = scan_flag(R, st, bad, [&](uint32_t* flag) {
-                hipLaunchKernelGGL(ps::k_pscan_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_ranges, (uint32_t)m,
-                                   (uint32_t)n, flag);
+                hipLaunchKernelGGL(ps::k_pscan_check, dim3(p.g_check), dim3(256), 0, st, (const uint32_t*)d_ranges, (uint32_t)m, (uint32_t)n, flag);
             }))
             return rc;
         if (bad) return fail(-EINVAL, "range out of order or past the points");
     }
     PscanWs w;
-    if (int rc = pscan_ws<DEG>(c, S, w)) return rc;
-    uint32_t* const base = single ? nullptr : (uint32_t*)(R + o_base);
-    uint32_t* const basec = single ? nullptr : (uint32_t*)(R + o_basec);
+    if (int rc = pscan_ws<DEG>(c, p.S, w)) return rc;
+    uint32_t* const base = p.single ? nullptr : (uint32_t*)(R + p.o_base);
+    uint32_t* const basec = p.single ? nullptr : (uint32_t*)(R + p.o_basec);
     size_t lo = 0;
     do {
-        const size_t len = n - lo < SL ? n - lo : SL, hi = lo + len;
-        const bool last = hi == n;
-        if (int rc = pscan_launch<DEG>(w, (const char*)d_pts + lo * 96 * DEG, len, lo == 0, !last, st)) return rc;
-        if (!single) {
-            const size_t total = m * PJ;
-            hipLaunchKernelGGL(ps::k_pscan_begin<DEG>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w.s, w.cnt, (uint32_t)lo, (uint32_t)hi,
-                               last ? 1u : 0u, (const uint32_t*)d_ranges, total, base, basec);
-        }
-        if (int rc = pscan_ranges_launch<DEG>(w, lo, hi, last, d_ranges, m, base, basec, d_out, d_flag, st)) return rc;
-        lo = hi;
+        const ragged::ScanSlice s = p.at(lo);
+        if (int rc = pscan_launch<DEG>(w, (const char*)d_pts + s.lo * 96 * DEG, s.len, s.first, s.more, st)) return rc;
+        if (!p.single)
+            hipLaunchKernelGGL(ps::k_pscan_begin<DEG>, dim3(p.g_begin), dim3(256), 0, st, w.s, w.cnt, (uint32_t)s.lo, (uint32_t)s.hi, s.last ? 1u : 0u,
+                               (const uint32_t*)d_ranges, p.begin_total, base, basec);
+        if (int rc = pscan_ranges_launch<DEG>(w, s.lo, s.hi, s.last, d_ranges, m, base, basec, d_out, d_flag, st)) return rc;
+        lo = s.hi;
     } while (lo < n);
     return 0;
 }
 template <int DEG>
 int range_sums_host(blsgpu_ctx* c, const uint8_t* pts, size_t n, const uint32_t* ranges, size_t m, uint8_t* out, uint8_t* flag) {
     if (int rc = range_sums_args(c, pts, n, ranges, m, out, flag)) return rc < 0 ? rc : 0;
-    for (size_t i = 0; i < m; i++)
-        if (ranges[2 * i] > ranges[2 * i + 1] || ranges[2 * i + 1] > n) return fail(-EINVAL, "range out of order or past the points");
+    if (ragged::first_bad_range(ranges, m, n) != ragged::NONE) return fail(-EINVAL, "range out of order or past the points");
     HIP_TRY(hipSetDevice(c->device));
     Staging s(c);
     const int dp = s.in(n ? pts : nullptr, n * 96 * DEG), dr = s.in(ranges, m * 8), dout = s.out(out, m * 96 * DEG), df = s.out(flag, m);
@@ -1326,7 +1312,7 @@ int msm_ranges_args(const blsgpu_ctx* c, const void* pts, const void* scalars, s
                     const void* flag) {
     if (!c) return fail(-EINVAL, "ctx is NULL");
     if ((n && (!pts || !scalars)) || (m && (!ranges || !out || !flag))) return fail(-EINVAL, "NULL argument");
-    if (n > 0xFFFFFFF0ull || m > 0x7FFFFFF0ull / blsgpu::SrtG<2>::LP) return fail(-EINVAL, "batch too large");
+    if (ragged::too_large(MSM_CONSTS, n, m)) return fail(-EINVAL, "batch too large");
     return m == 0 ? 1 : 0;
 }
 // The ranges are checked and cut into chunks of at most eight points on the device (k_msmr_count, k_msmr_scan, k_msmr_fill); ONE
@@ -1342,57 +1328,44 @@ template <int DEG>
 int msm_ranges_dev(blsgpu_ctx* c, const void* d_pts, const void* d_scalars, size_t n, const void* d_ranges, size_t m, void* d_out,
                    void* d_flag, hipStream_t st) {
     namespace mr = blsgpu::msmr;
-    typedef blsgpu::SrtG<DEG> G;
     StreamGuard sg(c, st);
-    auto words = [](size_t w) { return (w + 63) & ~(size_t)63; };                 // every region on a 256-byte boundary
-    const size_t h_cnt = 64, h_first = h_cnt + words(m), h_cr = h_first + words(m + 1), h_end = h_cr + words(2 * m);
-    if (int rc = c->grow(B_MSM_PART, h_end * 4)) return rc;
+    const ragged::MsmrHeads h = ragged::plan_msmr_heads(m);
+    if (int rc = c->grow(B_MSM_PART, h.words * 4)) return rc;
     uint32_t* const Hd = c->at<uint32_t>(B_MSM_PART);
     HIP_TRY(hipMemsetAsync(Hd, 0, 16, st));
-    hipLaunchKernelGGL(mr::k_msmr_count, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_ranges, (uint32_t)m, (uint32_t)n, Hd,
-                       Hd + h_cnt);
-    hipLaunchKernelGGL(mr::k_msmr_scan, dim3(1), dim3(mr::SCAN_THREADS), 0, st, Hd + h_cnt, (uint32_t)m, Hd + h_first);
+    hipLaunchKernelGGL(mr::k_msmr_count, dim3(h.g_count), dim3(256), 0, st, (const uint32_t*)d_ranges, (uint32_t)m, (uint32_t)n, Hd, Hd + h.h_cnt);
+    hipLaunchKernelGGL(mr::k_msmr_scan, dim3(1), dim3(mr::SCAN_THREADS), 0, st, Hd + h.h_cnt, (uint32_t)m, Hd + h.h_first);
     HIP_TRY(hipGetLastError());
     uint32_t head[4] = {0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(head, Hd, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (head[0]) return fail(-EINVAL, "range out of order or past the points");
-    const uint64_t total64 = (uint64_t)head[2] | ((uint64_t)head[3] << 32);
-    if (total64 >= ((uint64_t)1 << 31)) return fail(-EINVAL, "too many chunks");
-    const size_t total = (size_t)total64;
-    // slices of chunks: tables below 2 GB, a launch of at most SRT_LANES / LP units
-    const size_t upw = 64 / G::LP, per_unit = (size_t)mr::CHUNK * blsgpu::SMUL_T * G::PJ * 4;
-    size_t slice = ((size_t)2 << 30) / per_unit / upw * upw;
-    if (slice > blsgpu::SRT_LANES / G::LP) slice = blsgpu::SRT_LANES / G::LP;
-    slice = slice_len(c, slice, upw);
-    const size_t units0 = ((total < slice ? total : slice) + upw - 1) / upw * upw;
-    const size_t o_prep = 0, o_live = o_prep + words(n * blsgpu::L28_AFF * DEG), o_tab = o_live + words((n + 3) / 4), o_part = o_tab + words(2 * total),
-                 o_bad = o_part + words(total * 24 * DEG), o_bpre = o_bad + words(total), o_table = o_bpre + words(total + 1),
-                 o_end = o_table + units0 * mr::CHUNK * blsgpu::SMUL_T * G::PJ;
-    if (int rc = c->grow(B_BUCKETS, o_end * 4)) return rc;
+    const ragged::MsmrBody p = ragged::plan_msmr_body(*c, MSM_CONSTS, RAGGED_CONSTS, DEG, n, m, (uint64_t)head[2] | ((uint64_t)head[3] << 32));
+    if (p.too_many) return fail(-EINVAL, "too many chunks");
+    const size_t total = p.total;
+    if (int rc = c->grow(B_BUCKETS, p.words * 4)) return rc;
     uint32_t* const W = c->at<uint32_t>(B_BUCKETS);
-    uint8_t* const live = (uint8_t*)(W + o_live);
-    const size_t fill = total > m ? total : m;
-    hipLaunchKernelGGL(mr::k_msmr_fill, dim3((unsigned)((fill + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_ranges, Hd + h_first, (uint32_t)m,
-                       (uint32_t)total, W + o_tab, Hd + h_cr);
+    uint8_t* const live = (uint8_t*)(W + p.o_live);
+    hipLaunchKernelGGL(mr::k_msmr_fill, dim3(p.g_fill), dim3(256), 0, st, (const uint32_t*)d_ranges, Hd + h.h_first, (uint32_t)m, (uint32_t)total,
+                       W + p.o_tab, Hd + h.h_cr);
     HIP_TRY(hipGetLastError());
     if (total) {
-        hipLaunchKernelGGL(blsgpu::k_lane_prep<DEG>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_pts, (uint32_t)n, W + o_prep, live);
+        hipLaunchKernelGGL(blsgpu::k_lane_prep<DEG>, dim3(p.g_prep), dim3(256), 0, st, (const uint32_t*)d_pts, (uint32_t)n, W + p.o_prep, live);
         HIP_TRY(hipGetLastError());
-        if (int rc = for_slices(total, slice, [&](size_t lo, size_t k) {
-                const size_t units = (k + upw - 1) / upw * upw;
-                hipLaunchKernelGGL(mr::k_smul_seg<DEG>, dim3((unsigned)(units * G::LP / 64)), dim3(64), 0, st, W + o_prep, live, (const uint32_t*)d_scalars,
-                                   W + o_tab + 2 * lo, (uint32_t)k, W + o_table, W + o_part + lo * 24 * DEG, W + o_bad + lo);
+        if (int rc = for_slices(total, p.slice, [&](size_t lo, size_t) {
+                const ragged::MsmrSlice s = p.at(lo);
+                hipLaunchKernelGGL(mr::k_smul_seg<DEG>, dim3(s.g_smul), dim3(64), 0, st, W + p.o_prep, live, (const uint32_t*)d_scalars, W + s.tab,
+                                   (uint32_t)s.k, W + p.o_table, W + s.part, W + s.bad);
                 HIP_TRY(hipGetLastError());
                 return 0;
             }))
             return rc;
-        hipLaunchKernelGGL(mr::k_msmr_scan, dim3(1), dim3(mr::SCAN_THREADS), 0, st, W + o_bad, (uint32_t)total, W + o_bpre);
+        hipLaunchKernelGGL(mr::k_msmr_scan, dim3(1), dim3(mr::SCAN_THREADS), 0, st, W + p.o_bad, (uint32_t)total, W + p.o_bpre);
         HIP_TRY(hipGetLastError());
     }
-    if (int rc = range_sums_run<DEG>(c, W + o_part, total, Hd + h_cr, m, d_out, d_flag, false, st)) return rc;
+    if (int rc = range_sums_run<DEG>(c, W + p.o_part, total, Hd + h.h_cr, m, d_out, d_flag, false, st)) return rc;
     if (total) {
-        hipLaunchKernelGGL(mr::k_msmr_offcurve<DEG>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, W + o_bpre, Hd + h_first, (uint32_t)m,
+        hipLaunchKernelGGL(mr::k_msmr_offcurve<DEG>, dim3(p.g_offcurve), dim3(256), 0, st, W + p.o_bpre, Hd + h.h_first, (uint32_t)m,
                            (uint32_t*)d_out, (uint8_t*)d_flag);
         HIP_TRY(hipGetLastError());
     }
@@ -1402,8 +1375,7 @@ template <int DEG>
 int msm_ranges_host(blsgpu_ctx* c, const uint8_t* pts, const uint8_t* scalars, size_t n, const uint32_t* ranges, size_t m, uint8_t* out,
                     uint8_t* flag) {
     if (int rc = msm_ranges_args(c, pts, scalars, n, ranges, m, out, flag)) return rc < 0 ? rc : 0;
-    for (size_t i = 0; i < m; i++)
-        if (ranges[2 * i] > ranges[2 * i + 1] || ranges[2 * i + 1] > n) return fail(-EINVAL, "range out of order or past the points");
+    if (ragged::first_bad_range(ranges, m, n) != ragged::NONE) return fail(-EINVAL, "range out of order or past the points");
     HIP_TRY(hipSetDevice(c->device));
     Staging s(c);
     const int dp = s.in(n ? pts : nullptr, n * 96 * DEG), dsc = s.in(n ? scalars : nullptr, n * 32), dr = s.in(ranges, m * 8),
@@ -1421,7 +1393,7 @@ int sig_divide_args(const blsgpu_ctx* c, const void* pts, size_t n_pts, const vo
     if (!c) return fail(-EINVAL, "ctx is NULL");
     if (m == 0) return 1;
     if (!pts || !pt_off || !ent_off || !out || !flag || !status || (n_ent && (!ea || !eb))) return fail(-EINVAL, "NULL argument");
-    if (n_pts > 0xFFFFFFF0ull || n_ent > 0xFFFFFFF0ull || m > 0x7FFFFFF0ull / blsgpu::SrtG<2>::LP) return fail(-EINVAL, "batch too large");
+    if (ragged::too_large(MSM_CONSTS, n_pts, m, n_ent)) return fail(-EINVAL, "batch too large");
     if (n_pts < m) return fail(-EINVAL, "a dividend without a point");
     return 0;
 }
@@ -1434,25 +1406,21 @@ int sig_divide_dev(blsgpu_ctx* c, const void* d_pts, size_t n_pts, const void* d
                    const void* d_eb, size_t n_ent, void* d_out, void* d_flag, void* d_status, void* d_scalars, uint32_t* stats, hipStream_t st) {
     namespace sd = blsgpu::sigdiv;
     StreamGuard sg(c, st);
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_mism = 256, o_zero = o_mism + al(n_pts), o_nonunit = o_zero + al(n_pts), o_status = o_nonunit + al(n_pts),
-                 o_refused = o_status + al(n_pts), o_ranges = o_refused + al(m), o_scalars = o_ranges + al(8 * m), o_work = o_scalars + al(32 * n_pts),
-                 o_end = o_work + al(192 * n_pts);
-    if (int rc = c->grow(B_SIGDIV_WS, o_end)) return rc;
+    const ragged::SigdivPlan p = ragged::plan_sigdiv(n_pts, m, n_ent);
+    if (int rc = c->grow(B_SIGDIV_WS, p.bytes)) return rc;
     char* const W = c->at<char>(B_SIGDIV_WS);
     uint32_t* const head = (uint32_t*)W;
-    HIP_TRY(hipMemsetAsync(W, 0, o_nonunit, st));                              // the head words, mism and zero
-    const size_t idx = (m > n_pts ? m : n_pts) + 1;
-    hipLaunchKernelGGL(sd::k_sigdiv_check, dim3((unsigned)((idx + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_pt_off, (uint32_t)m,
-                       (const uint32_t*)d_ent_off, (uint32_t)n_pts, (uint32_t)n_ent, head);
+    HIP_TRY(hipMemsetAsync(W, 0, p.memset_bytes, st));                         // the head words, mism and zero
+    hipLaunchKernelGGL(sd::k_sigdiv_check, dim3(p.g_check), dim3(256), 0, st, (const uint32_t*)d_pt_off, (uint32_t)m, (const uint32_t*)d_ent_off,
+                       (uint32_t)n_pts, (uint32_t)n_ent, head);
     if (n_ent)
-        hipLaunchKernelGGL(sd::k_sigdiv_cross, dim3((unsigned)((n_ent + 255) / 256)), dim3(256), 0, st, head, (const uint32_t*)d_ent_off, (uint32_t)n_pts,
-                           (const uint8_t*)d_ea, (const uint8_t*)d_eb, (uint32_t)n_ent, (uint8_t*)(W + o_mism), (uint8_t*)(W + o_zero));
-    hipLaunchKernelGGL(sd::k_sigdiv_quot, dim3((unsigned)((n_pts + 255) / 256)), dim3(256), 0, st, head, (const uint32_t*)d_ent_off, (uint32_t)n_pts,
-                       (const uint8_t*)d_ea, (const uint8_t*)d_eb, (const uint8_t*)(W + o_mism), (const uint8_t*)(W + o_zero), (const uint32_t*)d_pts,
-                       (uint8_t*)(W + o_status), (uint8_t*)(W + o_scalars), (uint8_t*)(W + o_nonunit), (uint32_t*)(W + o_work));
-    hipLaunchKernelGGL(sd::k_sigdiv_fold, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, head, (const uint32_t*)d_pt_off, (uint32_t)m,
-                       (const uint8_t*)(W + o_status), (uint8_t*)(W + o_refused), (uint32_t*)(W + o_ranges));
+        hipLaunchKernelGGL(sd::k_sigdiv_cross, dim3(p.g_cross), dim3(256), 0, st, head, (const uint32_t*)d_ent_off, (uint32_t)n_pts,
+                           (const uint8_t*)d_ea, (const uint8_t*)d_eb, (uint32_t)n_ent, (uint8_t*)(W + p.o_mism), (uint8_t*)(W + p.o_zero));
+    hipLaunchKernelGGL(sd::k_sigdiv_quot, dim3(p.g_quot), dim3(256), 0, st, head, (const uint32_t*)d_ent_off, (uint32_t)n_pts, (const uint8_t*)d_ea,
+                       (const uint8_t*)d_eb, (const uint8_t*)(W + p.o_mism), (const uint8_t*)(W + p.o_zero), (const uint32_t*)d_pts,
+                       (uint8_t*)(W + p.o_status), (uint8_t*)(W + p.o_scalars), (uint8_t*)(W + p.o_nonunit), (uint32_t*)(W + p.o_work));
+    hipLaunchKernelGGL(sd::k_sigdiv_fold, dim3(p.g_fold), dim3(256), 0, st, head, (const uint32_t*)d_pt_off, (uint32_t)m,
+                       (const uint8_t*)(W + p.o_status), (uint8_t*)(W + p.o_refused), (uint32_t*)(W + p.o_ranges));
     HIP_TRY(hipGetLastError());
     uint32_t h[4] = {0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(h, head, 16, hipMemcpyDeviceToHost, st));
@@ -1464,15 +1432,15 @@ int sig_divide_dev(blsgpu_ctx* c, const void* d_pts, size_t n_pts, const void* d
         stats[0] = plain ? 0u : 1u;
         stats[1] = h[2];
     }
-    HIP_TRY(hipMemcpyAsync(d_status, W + o_status, n_pts, hipMemcpyDeviceToDevice, st));
-    if (d_scalars) HIP_TRY(hipMemcpyAsync(d_scalars, W + o_scalars, 32 * n_pts, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_status, W + p.o_status, n_pts, hipMemcpyDeviceToDevice, st));
+    if (d_scalars) HIP_TRY(hipMemcpyAsync(d_scalars, W + p.o_scalars, 32 * n_pts, hipMemcpyDeviceToDevice, st));
     if (plain) {
-        if (int rc = range_sums_run<2>(c, W + o_work, n_pts, W + o_ranges, m, d_out, d_flag, false, st)) return rc;
+        if (int rc = range_sums_run<2>(c, W + p.o_work, n_pts, W + p.o_ranges, m, d_out, d_flag, false, st)) return rc;
     } else {
-        if (int rc = msm_ranges_dev<2>(c, d_pts, W + o_scalars, n_pts, W + o_ranges, m, d_out, d_flag, st)) return rc;
+        if (int rc = msm_ranges_dev<2>(c, d_pts, W + p.o_scalars, n_pts, W + p.o_ranges, m, d_out, d_flag, st)) return rc;
     }
-    hipLaunchKernelGGL(sd::k_sigdiv_refuse, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint8_t*)(W + o_refused), (uint32_t)m,
-                       (uint32_t*)d_out, (uint8_t*)d_flag);
+    hipLaunchKernelGGL(sd::k_sigdiv_refuse, dim3(p.g_refuse), dim3(256), 0, st, (const uint8_t*)(W + p.o_refused), (uint32_t)m, (uint32_t*)d_out,
+                       (uint8_t*)d_flag);
     HIP_TRY(hipGetLastError());
     return 0;
 }

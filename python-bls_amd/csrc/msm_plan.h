@@ -204,6 +204,17 @@ inline PlainPlan plan_plain(const Consts& K, int DEG, size_t n) {
 
 // ---- a batch of scalar multiplications / of small sums with scalars: one group per unit (k_smul), in slices of groups whose
 // tables (16 projective multiples per point) stay below 2 GB: 2^20 groups of eight G2 points would ask for 45 GB
+// The slice rule of the kernels that run one item per unit on a table of SMUL_T projective multiples per point (k_smul here,
+// k_smul_seg and k_smul64 in ragged_plan.h): whole wavefronts of units whose tables stay below 2 GB, at least one wavefront.
+// `ceiling`: units one launch may take (0: none -- k_smul's grid is not bound to SRT_LANES); `cap_unit`: what the test cap is
+// rounded up to (a wavefront of units, or 1 where the cap counts single items).
+inline size_t unit_slice(const Knobs& c, const Consts& K, int DEG, size_t pts_per_unit, size_t ceiling, size_t cap_unit) {
+    const size_t upw = 64 / K.lp[DEG - 1], per_unit = pts_per_unit * K.smul_t * K.pj[DEG - 1] * 4;
+    size_t slice = ((size_t)2 << 30) / per_unit / upw * upw;
+    if (slice < upw) slice = upw;
+    if (ceiling && slice > ceiling) slice = ceiling;
+    return slice_len(c, slice, cap_unit);
+}
 struct SmallSlice { size_t m, n, units, pts, scalars, out; unsigned g_prep, g_smul; };   // pts, scalars, out: words into the caller's arrays
 struct SmallPlan {
     size_t upw, slice, units0, o_prep, o_live, o_tab, words;
@@ -216,11 +227,9 @@ struct SmallPlan {
 inline SmallPlan plan_small_groups(const Knobs& c, const Consts& K, int DEG, size_t k, size_t groups) {
     SmallPlan p{};
     const size_t LP = K.lp[DEG - 1], PJ = K.pj[DEG - 1];
-    const size_t upw = p.upw = 64 / LP, per_group = k * K.smul_t * PJ * 4;
-    size_t slice = ((size_t)2 << 30) / per_group / upw * upw;
-    if (slice < upw) slice = upw;
-    slice = slice_len(c, slice, upw);
-    if (slice > groups) slice = groups;
+    const size_t upw = p.upw = 64 / LP;
+    size_t slice = unit_slice(c, K, DEG, k, 0, upw);
+    if (slice > groups) slice = groups;                       // (the ragged plans keep their slice and clamp the units instead)
     p.slice = slice, p.k = k, p.groups = groups, p.LP = LP, p.DEG = (size_t)DEG;
     p.units0 = (slice + upw - 1) / upw * upw;
     const size_t n0 = k * slice;

@@ -9,22 +9,27 @@ import pytest
 
 import test_gpu_hd_keys as THD
 import test_gpu_hd_paths as TPATH
+import test_gpu_msm_ranges as TMR
 import test_gpu_mul_short as TSHORT
 import test_gpu_seeds as TSEED
+import test_gpu_sigdiv as TDIV
 import test_gpu_sign as TSIGN
 import test_gpu_subgroup as TSUB
 from bls_py import _native_find as F
 from bls_py import _native_ranges as R
+from bls_py import _native_sigdiv as S
 from bls_py import hostmath as H
 from conftest import engine_with_env
 from sigshares_vectors import Session, msg_hash, truth_bytes
 from sigshares_vectors import pack as pack_sessions
 from test_gpu_batch_find import KINDS, objects
 from test_gpu_hd_paths import fx as paths_fx  # noqa: F401  (fixtures of the tests called below, under names of their own)
+from test_gpu_msm_ranges import worlds as msmr_worlds  # noqa: F401
 from test_gpu_mul_short import pool as short_pool  # noqa: F401
 from test_gpu_range_sums import expect, ranges_for, worlds  # noqa: F401
 from test_gpu_seeds import drawn as seeds_drawn  # noqa: F401
 from test_gpu_seeds import fx as seeds_fx  # noqa: F401
+from test_gpu_sigdiv import pool as sigdiv_pool  # noqa: F401
 from test_gpu_sign import cases as sign_cases  # noqa: F401
 from test_gpu_sign import fixture as sign_fixture  # noqa: F401
 from test_gpu_subgroup import sub as subgroup_sub  # noqa: F401
@@ -181,6 +186,93 @@ def test_range_sums_workspace_holds_one_slice_of_records(worlds, deg):
         assert (CAP + 1) * 168 * deg <= grown < (n + 1) * 168 * deg
     finally:
         fresh.close()
+
+
+# ------------------------------------------------------------------------------------------------ ragged multi-scalar sums --
+# BLSGPU_TEST_SLICE_CAP rounds a chunk slice up to a wavefront of units (64 chunks in G1, 32 in G2: csrc/ragged_plan.h) and cuts
+# the range sums over the chunk partials into slices of `cap` partials.  Expected values: the single multiplications of
+# test_gpu_msm_ranges.py on the default engine.
+@pytest.mark.parametrize("deg", [1, 2])
+@pytest.mark.parametrize("cap", [5, 16])
+@pytest.mark.parametrize("n", [65, 520])
+def test_msm_ranges_across_slices(engine, capped, msmr_worlds, deg, cap, n):
+    g, t, s, pts = msmr_worlds[deg]
+    eng, ranges = capped(cap), TMR.ranges_for(n)
+    chunks = sum(-(-(e - b) // 8) for b, e in ranges)
+    assert chunks > (2 if n == 520 else 1) * 64 // deg and chunks > 2 * cap         # several chunk slices, many slices of partials
+    TMR.test_sizes_and_ranges(eng, msmr_worlds, deg, n)                             # the expectation and the planted cases
+    buf, sc = b"".join(pts[:n]), b"".join(v.to_bytes(32, "big") for v in s[:n])
+    want = TMR.expect(g, t[:n], s[:n], ranges)
+    host = g.sums(eng, buf, sc, ranges)
+    assert host == want
+    assert g.sums(engine, buf, sc, ranges) == host
+    m = len(ranges)
+    d_p, d_s, d_r, d_o, d_f = up(buf), up(sc), words([v for r in ranges for v in r]), blank(m * g.size), blank(m)
+    g.sums_dev(eng, d_p.data_ptr(), d_s.data_ptr(), n, d_r.data_ptr(), m, d_o.data_ptr(), d_f.data_ptr(), 0)
+    assert (down(d_o), down(d_f)) == host
+
+
+@pytest.mark.parametrize("deg", [1, 2])
+def test_msm_ranges_off_curve_point_across_slices(capped, msmr_worlds, deg):
+    """flag 2 from a chunk of an earlier slice of partials (and, in G2, of an earlier chunk slice)"""
+    TMR.test_off_curve_point_and_infinity_inputs(capped(CAP), msmr_worlds, deg)
+    TMR.test_chunk_counts_around_a_wavefront_of_units(capped(CAP), msmr_worlds, deg, 57)
+
+
+@pytest.mark.parametrize("deg", [1, 2])
+def test_msm_ranges_workspace_holds_one_chunk_slice_of_tables(msmr_worlds, deg):
+    import ragged_plan_model as RM
+    g, t, s, pts = msmr_worlds[deg]
+    n, ranges = 520, TMR.ranges_for(520)
+    m, chunks = len(ranges), sum(-(-(e - b) // 8) for b, e in ranges)
+    fresh = engine_with_env({"BLSGPU_TEST_SLICE_CAP": str(CAP)})
+    try:
+        before = fresh.workspace_bytes()["group_sums"]
+        assert g.sums(fresh, b"".join(pts[:n]), s[:n], ranges) == TMR.expect(g, t[:n], s[:n], ranges)
+        grown = fresh.workspace_bytes()["group_sums"] - before
+    finally:
+        fresh.close()
+    one, every = (RM.msmr_body(RM.knobs(test_slice_cap=cap), deg, n, m, chunks) for cap in (CAP, 0))
+    assert one["units0"] == 64 // deg < chunks <= every["units0"]
+    # B_MSM_PART holds the head words and B_BUCKETS one chunk slice's tables, each through the headroom rule (bytes + bytes / 4)
+    assert before == 0 and grown == RM.grown_bytes(RM.msmr_heads(m)["words"]) + RM.grown_bytes(one["words"])
+    assert grown < RM.grown_bytes(every["words"])
+
+
+# ------------------------------------------------------------------------------------------------ signature division --
+@pytest.mark.parametrize("plain", [1, 0])
+def test_sig_divide_across_slices(engine, capped, sigdiv_pool, plain):
+    """forty dividends over 100 points in slices of five: the plain path's range sums over the working copy, the scalar path's
+    chunk slices and range sums over the partials; unit and seeded quotients, a refused divisor, a point off the twist and a
+    (0,0) divisor.  Expected: the Python scalars and blsgpu_g2_msm_ranges on the DEFAULT engine (test_gpu_sigdiv.expect)"""
+    eng = capped(CAP, BLSGPU_SIGDIV_PLAIN=plain)
+    rng = random.Random("slices sigdiv")
+    for q in (1, None):
+        dividends = [[TDIV.divisor(rng, 1 + (i + j) % 5, q) for i in range(j % 4)] for j in range(40)]
+        pts, pt_off, ent_off, ea, eb = TDIV.layout(sigdiv_pool, dividends)
+        assert len(pts) == 100 and len(dividends) > 2 * CAP
+        for spoil in (False, True):
+            if spoil:
+                ea = list(ea)
+                ea[ent_off[7]] = (ea[ent_off[7]] + 1) % N                        # point 7, a divisor of dividend 3: refused
+                off = bytearray(pts[26])
+                off[-1] ^= 1                                                     # off the twist
+                pts[26], pts[51] = bytes(off), bytes(192)
+            wout, wflag, wstatus, wsc, nonunit = TDIV.expect(engine, pts, pt_off, ent_off, ea, eb)
+            got = S.sig_divide(eng, b"".join(pts), pt_off, ent_off, ea, eb)
+            assert got[:4] == (wout, wflag, wstatus, wsc)
+            assert got[4] == (0 if plain and not nonunit else 1, nonunit)
+            assert S.sig_divide(engine, b"".join(pts), pt_off, ent_off, ea, eb)[:4] == got[:4]
+            if spoil:
+                assert 3 in wflag and 2 in wflag and wstatus[7] == 1
+
+
+@pytest.mark.parametrize("plain", [1, 0])
+def test_divide_by_batch_through_the_capped_engine(capped, golden, plain):
+    """the cases of tests/golden/sigdiv.json, as test_gpu_sigdiv.py runs them"""
+    from bls_py import backend
+    with provider(capped(CAP, BLSGPU_SIGDIV_PLAIN=plain)):
+        TDIV.test_divide_by_batch_on_the_device_equals_the_loop(golden, backend)
 
 
 # ------------------------------------------------------------------------------------------------ verify_find --
