@@ -162,6 +162,49 @@ int blsgpu_verify_pipeline(blsgpu_ctx *ctx, const uint8_t neg_g1[BLSGPU_G1_BYTES
 int blsgpu_verify_pipeline_dev(blsgpu_ctx *ctx, void *d_g1, void *d_g2, const void *d_msg_hashes, size_t n,
                                const void *d_key_pts, const void *d_key_scalars, size_t k, void *d_out, void *stream);
 
+/* BLS.verify of m aggregates of ANY shapes in ONE call (csrc/blsgpu_veragg.hip; csrc/verify_agg_plan.h is its schedule): the
+ * bytes and three tables go up once, nothing returns to the host between the stages, m status bytes come back.
+ *   sigs        m x 192 bytes, the aggregates' signatures, affine G2
+ *   msg_hashes  n_msgs x 32 bytes; each is hashed to G2 ONCE per call, however many groups name it (an entry no group names
+ *               is hashed too)
+ *   keys, exps  n_keys x 96 bytes affine G1 and n_keys x 32 bytes big-endian exponents, or exps == NULL: every exponent is 1
+ *   grp_off     n_grp + 1 offsets into keys: group g sums the keys [grp_off[g], grp_off[g + 1])
+ *   grp_msg     n_grp indices into msg_hashes
+ *   agg_off     m + 1 offsets into the groups: aggregate j owns the groups [agg_off[j], agg_off[j + 1])
+ * For aggregate j the value computed is fq_ate_pairing_multi of the pairs (-G1, sig_j), (sum_i e_i pk_i over group g,
+ * H(msg_hashes[grp_msg[g]])) for g in j's groups in order -- the pair order of bls.py:197-199; -G1 is the library's own.
+ * status[j]: 1 the value is Fq12 one, 0 it is not, 2 NOT DECIDED here (the caller runs its exact path): the signature is (0,0)
+ * -- an infinity signature carries the one flag the reference's Miller loop reads --, or one of j's groups holds a key that is
+ * neither (0,0) nor on the curve (flag 2 of the sums).  A key sum at infinity is NOT status 2: its (0,0) goes into the pair
+ * list with no flag, exactly as blsgpu_verify_pipeline_dev hands it on.  An aggregate with no groups is the one-pair product.
+ * out_gt: m x 576 bytes, the value of every aggregate (unspecified where status is 2), or NULL.
+ * Stages: the key sums of all groups -- blsgpu_g1_msm_ranges' implementation with exps, blsgpu_g1_range_sums' without (the same
+ * bytes for unit exponents) --, the hash to G2 of all n_msgs hashes, then per slice of whole aggregates (pair lists of at most
+ * 2^20 pairs; a longer aggregate is a slice of its own) k_va_pairs gathers the pair list in 16-byte moves, the ragged
+ * multi-pairing (blsgpu_pairing_multi_ranges' implementation) runs a range per aggregate, and k_va_status writes the bytes.
+ * The call inherits what its stages cost: the serial chain of the ragged sums on a long group and the ragged multi-pairing's
+ * loss on one long range (README).  Measured (profiles/verify_aggregates_probe.txt, one run, host buffers, medians of 3): 32 768
+ * single-key signatures over distinct messages 28.9 ms, 1000 aggregates of 2 .. 201 messages 33.9 ms, one message with 1024 keys
+ * plus 1024 messages with one key 21.4 ms.  The _dev form alone: NOT MEASURED.
+ * The three tables are HOST memory in BOTH forms: validation and the whole schedule are host arithmetic on them, the derived
+ * tables go up in one copy, and they may be released or changed as soon as the call returns.  The workspace counts in
+ * BLSGPU_WS_TOTAL, the line records in BLSGPU_WS_LINES; every buffer of every slice is sized before the first launch.
+ * -EINVAL before anything is written: a NULL required buffer (sigs, status, agg_off, grp_off with m > 0; grp_msg with
+ * n_grp > 0; keys with n_keys > 0; msg_hashes with n_msgs > 0), a table that steps down, grp_off[n_grp] != n_keys,
+ * agg_off[m] != n_grp, grp_msg[g] >= n_msgs (blsgpu_last_error names the first offending entry), m + n_grp > 0x3FFFFFF0,
+ * n_msgs > 0x03FFFFF0, n_keys > 0xFFFFFFF0.  -ENOMEM when the line records cannot be allocated.  m == 0 writes nothing and
+ * returns 0.  All of this is PUBLIC data: not constant-time. */
+int blsgpu_verify_aggregates(blsgpu_ctx *ctx, const uint8_t *sigs, const uint8_t *msg_hashes, size_t n_msgs, const uint8_t *keys,
+                             const uint8_t *exps, size_t n_keys, const uint32_t *grp_off, const uint32_t *grp_msg, size_t n_grp,
+                             const uint32_t *agg_off, size_t m, uint8_t *status, uint8_t *out_gt);
+/* The same with the points, hashes, exponents, status and out_gt in device memory (points and out_gt 16-byte aligned), on
+ * `stream`; the three tables stay HOST memory.  With exps the call inherits the ONE synchronisation of that stream by which the
+ * ragged multi-scalar sums read their chunk count (before anything is written to status or out_gt); with exps == NULL it
+ * does not synchronise. */
+int blsgpu_verify_aggregates_dev(blsgpu_ctx *ctx, const void *d_sigs, const void *d_msg_hashes, size_t n_msgs, const void *d_keys,
+                                 const void *d_exps, size_t n_keys, const uint32_t *grp_off, const uint32_t *grp_msg, size_t n_grp,
+                                 const uint32_t *agg_off, size_t m, void *d_status, void *d_out_gt, void *stream);
+
 /* fq_ate_pairing_multi(Ps, Qs) -- fields_t.py:1114-1121 / fields_t_c.pyx:2333-2391.
  * Host buffers in, 576 result bytes out; synchronous.  n == 0 returns one. */
 int blsgpu_pairing_multi(blsgpu_ctx *ctx, const uint8_t *g1, const uint8_t *g2, const uint8_t *inf,

@@ -51,6 +51,8 @@ PROTOTYPES = {
     "blsgpu_debug_read_lines": (vp, vp, sz),
     "blsgpu_verify_pipeline": (vp, cp, cp, cp, sz, cp, cp, cp, sz, cp),
     "blsgpu_verify_pipeline_dev": (vp, vp, vp, vp, sz, vp, vp, sz, vp, vp),
+    "blsgpu_verify_aggregates": (vp, cp, cp, sz, cp, cp, sz, vp, vp, sz, vp, sz, vp, vp),
+    "blsgpu_verify_aggregates_dev": (vp, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp),
     "blsgpu_pairing_multi": (vp, cp, cp, cp, sz, cp),
     "blsgpu_pairing_multi_dev": (vp, vp, vp, vp, sz, vp, vp),
     "blsgpu_miller_loop_batch": (vp, cp, cp, cp, sz, cp),

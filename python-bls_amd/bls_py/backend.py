@@ -108,6 +108,10 @@ def use(provider):
     Optional extension (without it BLS.verify_batch(ragged=True) raises; the default verify_batch does not use it):
     pairing_multi_ranges(g1, g2, ranges, inf=None) -> m x 576 bytes, fq_ate_pairing_multi of the pairs [begin, end) of one
     list of pairs for m ranges (begin, end) of any lengths.
+    Optional extension (without it BLS.verify_batch(fused=True) raises; the default verify_batch does not use it):
+    verify_aggregates(sigs, msg_hashes, keys, exps|None, grp_off, grp_msg, agg_off, gt=False) -> (m status bytes: 1 valid, 0
+    not, 2 not decided; m x 576 bytes|None) -- BLS.verify of m aggregates, group g summing the keys [grp_off[g], grp_off[g + 1])
+    for message grp_msg[g], aggregate j owning the groups [agg_off[j], agg_off[j + 1]).
     Extensions are looked up by extension(name), not by hasattr: a stand-in offers one as an attribute of that name, the
     HipProvider's come from EXTENSIONS.  Optional (without it PrivateKey.from_seed_batch and
     ExtendedPrivateKey.from_seed_batch run the per-seed host calls): keys_from_seeds(seeds, seed_len, n, hd) -> (key bytes,
@@ -133,18 +137,21 @@ H2G1_EXTENSIONS = {"map_to_g1": "_native_h2g1", "hash_to_g1": "_native_h2g1"}
 SIGDIV_EXTENSIONS = {"sig_divide": "_native_sigdiv"}
 # ... and the multi-pairings over ranges of any lengths (BLS.verify_batch(ragged=True)).
 PAIR_RANGE_EXTENSIONS = {"pairing_multi_ranges": "_native_pairranges"}
+# ... and the verification of many aggregates of any shapes in one device call (BLS.verify_batch(fused=True)).
+VERIFY_AGG_EXTENSIONS = {"verify_aggregates": "_native_veragg"}
 
 
 def extension(name):
     """The installed provider's extension `name`: the provider's own attribute of that name if it has one (stand-ins), for
-    a HipProvider the function of EXTENSIONS (or FIND_EXTENSIONS, RANGE_EXTENSIONS, MSM_RANGE_EXTENSIONS, H2G1_EXTENSIONS, SIGDIV_EXTENSIONS, PAIR_RANGE_EXTENSIONS) bound to its
+    a HipProvider the function of EXTENSIONS (or FIND_EXTENSIONS, RANGE_EXTENSIONS, MSM_RANGE_EXTENSIONS, H2G1_EXTENSIONS, SIGDIV_EXTENSIONS, PAIR_RANGE_EXTENSIONS, VERIFY_AGG_EXTENSIONS) bound to its
     engine, otherwise None."""
     prov = get()
     fn = getattr(prov, name, None)
     if fn is not None:
         return fn
     where = (EXTENSIONS.get(name) or FIND_EXTENSIONS.get(name) or RANGE_EXTENSIONS.get(name) or MSM_RANGE_EXTENSIONS.get(name)
-             or H2G1_EXTENSIONS.get(name) or SIGDIV_EXTENSIONS.get(name) or PAIR_RANGE_EXTENSIONS.get(name))
+             or H2G1_EXTENSIONS.get(name) or SIGDIV_EXTENSIONS.get(name) or PAIR_RANGE_EXTENSIONS.get(name)
+             or VERIFY_AGG_EXTENSIONS.get(name))
     if isinstance(prov, HipProvider) and where:
         import functools
         import importlib

@@ -163,7 +163,7 @@ class BLS:
         return out == Fq12.one(default_ec.q).serialize()
 
     @staticmethod
-    def verify_batch(signatures, ragged=False):
+    def verify_batch(signatures, ragged=False, fused=False):
         """[BLS.verify(s) for s in signatures] with every GPU step batched across the
         signatures: one hash-to-G2 call for all distinct (signature, message) pairs, one call
         for all per-message key sums, and blsgpu_pairing_multi_batch per distinct pair count
@@ -171,9 +171,21 @@ class BLS:
         ragged=True: ONE pair list with one range per aggregate and one call of the pairing_multi_ranges
         extension (blsgpu_pairing_multi_ranges) in place of the call per distinct pair count; a provider
         without the extension raises.  Not the default: which is faster is measured by
-        tools/pair_ranges_probe.py, and routing is a later decision."""
+        tools/pair_ranges_probe.py, and routing is a later decision.
+        fused=True: after the dictionary work per signature, ONE call of the verify_aggregates extension
+        (blsgpu_verify_aggregates) for all signatures whose tree holds their keys: the distinct message hashes
+        of the whole batch, every key as affine bytes, the exponents (None when every one is 1 mod n) and the
+        three tables go up once; hash to G2, the key sums, the multi-pairings and the comparison with one stay
+        on the device.  A signature that comes back undecided (status 2: an infinity signature, a key off the
+        curve) and one with a message hash that is not 32 bytes are decided by BLS.verify.  A provider without
+        the extension raises.  Not the default either: tools/verify_aggregates_probe.py measures it."""
         from . import backend
         prov = backend.get()
+        fused_fn = None
+        if fused:
+            fused_fn = backend.extension("verify_aggregates")
+            if fused_fn is None:
+                raise NotImplementedError("verify_batch(fused=True) needs a provider with the verify_aggregates extension")
         ranges_fn = None
         if ragged:
             ranges_fn = backend.extension("pairing_multi_ranges")
@@ -199,6 +211,8 @@ class BLS:
             plans.append((i, list(by_message), kg, eg))
         if not plans:
             return results
+        if fused:
+            return BLS._verify_batch_fused(fused_fn, signatures, plans, results)
         all_hashes = [mh for _, mhs, _, _ in plans for mh in mhs]
         Qs = hash_to_points_prehashed_Fq2(all_hashes)
         Ps = _g1_sums([g for _, _, kg, _ in plans for g in kg], [e for _, _, _, eg in plans for e in eg])
@@ -230,6 +244,31 @@ class BLS:
             out = prov.pairing_multi_batch(b"".join(x[1] for x in items), b"".join(x[2] for x in items), size, len(items))
             for j, (i, _, _) in enumerate(items):
                 results[i] = out[576 * j:576 * (j + 1)] == ONE
+        return results
+
+    @staticmethod
+    def _verify_batch_fused(fused_fn, signatures, plans, results):
+        """verify_batch(fused=True) behind the dictionary work: the tables of ONE verify_aggregates call, its status bytes"""
+        from ._native_veragg import tables
+        msgs, keys, exps, shapes, sigs, sent = {}, [], [], [], [], []
+        for i, mhs, kg, eg in plans:
+            if not all(len(mh) == 32 for mh in mhs):
+                continue
+            shapes.append([(msgs.setdefault(mh, len(msgs)), len(g)) for mh, g in zip(mhs, kg)])
+            for g, e in zip(kg, eg):
+                keys += [_jac_g1_bytes(p) for p in g]
+                exps += [int(x) % GROUP_ORDER for x in e]
+            sigs.append(H.g2_affine_bytes(signatures[i].value.to_affine()._aff()))
+            sent.append(i)
+        if sent:
+            status, _ = fused_fn(b"".join(sigs), b"".join(msgs), b"".join(keys), None if all(x == 1 for x in exps) else exps,
+                                 *tables(shapes))
+            for i, st in zip(sent, status):
+                if st != 2:
+                    results[i] = st == 1
+        for i, _, _, _ in plans:
+            if results[i] is None:
+                results[i] = BLS.verify(signatures[i])
         return results
 
     @staticmethod

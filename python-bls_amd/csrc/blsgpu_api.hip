@@ -19,6 +19,7 @@
 #include "fp28.h"
 #include "blsgpu_ml.hip"
 #include "blsgpu_mlr.hip"
+#include "blsgpu_veragg.hip"
 #include "blsgpu_fexp.hip"
 #include "blsgpu_fexpw.hip"
 #include "blsgpu_mlw.hip"
@@ -50,6 +51,7 @@
 #include "pairing_plan.h"
 #include "pairing_ranges_plan.h"
 #include "ragged_plan.h"
+#include "verify_agg_plan.h"
 #include "blsgpu_ctx.h"
 
 // Which kernels a pairing call runs, its partials, chunks, levels, slices and buffer sizes are pairing_plan.h (host-only: tested
@@ -2608,11 +2610,9 @@ int pairing_ranges_args(const blsgpu_ctx* c, const void* g1, const void* g2, siz
 }
 int pairing_ranges_refuse(const pairing_ranges::Plan& p) { return fail(pairing_ranges::refusal_code(p.refusal), pairing_ranges::refusal_text(p.refusal)); }
 
-int pairing_ranges_launch(blsgpu_ctx* c, const pairing_ranges::Plan& p, const void* d_g1, const void* d_g2, const void* d_inf, void* d_out,
-                          hipStream_t st) {
-    using namespace blsgpu;
-    // every buffer of every slice before the first launch: a later slice cannot fail after an earlier one wrote.  No memory for
-    // the line records is this call's error -- it has no wavefront-VM form to fall back to.
+// every buffer of every slice before the first launch: a later slice cannot fail after an earlier one wrote.  No memory for
+// the line records is this call's error -- it has no wavefront-VM form to fall back to.
+int pairing_ranges_reserve(blsgpu_ctx* c, const pairing_ranges::Plan& p) {
     if (p.lines_bytes && (c->test_ls_nomem || c->grow(B_LINES, p.lines_bytes) || c->grow(B_BAD, p.bad_bytes) || c->grow(B_DEGEN, p.degen_bytes))) {
         (void)hipGetLastError();
         return fail(-ENOMEM, "no memory for the line records");
@@ -2623,9 +2623,20 @@ int pairing_ranges_launch(blsgpu_ctx* c, const pairing_ranges::Plan& p, const vo
         const WaveShape ws = wave_shape(c, form.waves);
         if (int rc = c->grow(B_FEXP_WS, (size_t)ws.blocks * (ws.threads / 64) * form.ws_bytes_per_wave)) return rc;
     }
+    return 0;
+}
+
+// d_tables: the image of the plan's tables already in device memory (blsgpu_verify_aggregates uploads those of all its slices
+// in one copy), or NULL: written here to pinned memory and uploaded
+int pairing_ranges_launch(blsgpu_ctx* c, const pairing_ranges::Plan& p, const void* d_g1, const void* d_g2, const void* d_inf, void* d_out,
+                          hipStream_t st, const void* d_tables = nullptr) {
+    using namespace blsgpu;
+    if (int rc = pairing_ranges_reserve(c, p)) return rc;
     char* const W = c->at<char>(B_PAIRR_WS);
     uint32_t* const partials = (uint32_t*)(W + p.o_partials);
-    {   // the tables: written to pinned memory that outlives the enqueue, one asynchronous upload
+    if (d_tables) {
+        HIP_TRY(hipMemcpyAsync(W + p.o_tables, d_tables, p.ws_bytes - p.o_tables, hipMemcpyDeviceToDevice, st));
+    } else {   // the tables: written to pinned memory that outlives the enqueue, one asynchronous upload
         PinnedTables pin(c);
         void* image = nullptr;
         if (int rc = pin.take(p.ws_bytes - p.o_tables, &image)) return rc;
@@ -2844,6 +2855,104 @@ BLSGPU_EXPORT int blsgpu_verify_pipeline(blsgpu_ctx* c, const uint8_t neg_g1[96]
         if (n && !sums) HIP_TRY(hipMemcpyAsync(s.at(d1) + BLSGPU_G1_BYTES, keys_affine, n * BLSGPU_G1_BYTES, hipMemcpyHostToDevice, nullptr));
     }
     if (int rc = blsgpu_verify_pipeline_dev(c, s.at(d1), s.at(d2), s.at(dh), n, s.opt(dkp), s.opt(dks), sums ? k : 0, s.at(dout), nullptr)) return rc;
+    return s.down();
+}
+
+// ---- m aggregates of any shapes in one call (blsgpu_veragg.hip; verify_agg_plan.h is the whole schedule) -----------------
+// Once per call: the tables (one upload), the key sums of ALL groups -- msm_ranges_dev with exponents, which synchronises the
+// stream once to read its chunk count, range_sums_dev (no scan: the plan checked the ranges) without --, and the hash of all
+// n_msgs message hashes.  Then per slice of whole aggregates: k_va_pairs, the ragged multi-pairing with a range per aggregate,
+// k_va_status.  Nothing of the caller's is written before the first slice's k_va_status, and every buffer the slices take is
+// sized before the first launch.
+namespace {
+// the argument checks, before anything is written; 1: nothing to do
+int veragg_args(const blsgpu_ctx* c, const void* sigs, const void* msg_hashes, size_t n_msgs, const void* keys, size_t n_keys,
+                const uint32_t* grp_off, const uint32_t* grp_msg, size_t n_grp, const uint32_t* agg_off, size_t m, const void* status) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (m == 0) return 1;
+    if (!sigs || !status || !agg_off || !grp_off || (n_grp && !grp_msg) || (n_keys && !keys) || (n_msgs && !msg_hashes))
+        return fail(-EINVAL, "NULL argument");
+    return 0;
+}
+verify_agg::Plan veragg_plan(const blsgpu_ctx* c, const uint32_t* grp_off, const uint32_t* grp_msg, size_t n_grp, const uint32_t* agg_off,
+                             size_t m, size_t n_keys, size_t n_msgs) {
+    return verify_agg::plan(grp_off, grp_msg, n_grp, agg_off, m, n_keys, n_msgs, *c, *c, PAIRING_CONSTS, pairing_limits(c), MSM_CONSTS);
+}
+int veragg_refuse(const verify_agg::Plan& p) {
+    return fail(verify_agg::refusal_code(p.refusal), std::string(verify_agg::refusal_text(p.refusal)) + " (entry " + std::to_string(p.bad) + ")");
+}
+
+int veragg_launch(blsgpu_ctx* c, const verify_agg::Plan& p, const void* d_sigs, const void* d_hashes, const void* d_keys, const void* d_exps,
+                  void* d_status, void* d_out_gt, hipStream_t st) {
+    namespace va = blsgpu::veragg;
+    static_assert(va::PER == verify_agg::PIECES && va::THREADS == verify_agg::THREADS && va::SRC_SIG == verify_agg::SIG &&
+                      verify_agg::GT_BYTES == BLSGPU_FQ12_BYTES,
+                  "verify_agg_plan.h differs from blsgpu_veragg.hip");
+    static const uint32_t neg_g1[24] = SIGSH_NEG_G1_WORDS;
+    for (const verify_agg::Slice& s : p.slices)
+        if (int rc = pairing_ranges_reserve(c, s.pr)) return rc;
+    if (int rc = c->grow(B_VERAGG_WS, p.ws_bytes)) return rc;
+    char* const W = c->at<char>(B_VERAGG_WS);
+    {
+        PinnedTables pin(c);
+        void* image = nullptr;
+        if (int rc = pin.take(p.ws_bytes - p.o_tables, &image)) return rc;
+        p.fill_tables(image, neg_g1);
+        if (int rc = pin.upload(W + p.o_tables, p.ws_bytes - p.o_tables, st)) return rc;
+    }
+    HIP_TRY(hipMemsetAsync(W + p.o_und, 0, (p.m + 3) & ~(size_t)3, st));
+    if (p.n_grp) {
+        if (d_exps) {
+            if (int rc = msm_ranges_dev<1>(c, d_keys, d_exps, p.n_keys, W + p.o_kr, p.n_grp, W + p.o_sum, W + p.o_flag, st)) return rc;
+        } else if (int rc = range_sums_dev<1>(c, d_keys, p.n_keys, W + p.o_kr, p.n_grp, W + p.o_sum, W + p.o_flag, false, st)) {
+            return rc;
+        }
+    }
+    if (int rc = map_to_g2_impl(c, d_hashes, p.n_msgs, W + p.o_h, st, true)) return rc;
+    for (const verify_agg::Slice& s : p.slices) {
+        char* const gt = d_out_gt ? (char*)d_out_gt + s.agg0 * BLSGPU_FQ12_BYTES : W + p.o_gt;
+        hipLaunchKernelGGL(va::k_va_pairs, dim3(s.g_pairs), dim3(va::THREADS), 0, st, (const uint32_t*)(W + s.src_off), s.pairs * va::PER,
+                           (const uint4*)d_sigs, (const uint4*)(W + p.o_neg), (const uint4*)(W + p.o_sum), (const uint8_t*)(W + p.o_flag),
+                           (const uint4*)(W + p.o_h), (uint4*)(W + p.o_g1), (uint4*)(W + p.o_g2), (uint32_t*)(W + p.o_und));
+        HIP_TRY(hipGetLastError());
+        if (int rc = pairing_ranges_launch(c, s.pr, W + p.o_g1, W + p.o_g2, nullptr, gt, st, W + s.prtab_off)) return rc;
+        hipLaunchKernelGGL(va::k_va_status, dim3(s.g_status), dim3(va::THREADS), 0, st, (const uint4*)gt, (const uint8_t*)(W + p.o_und + s.agg0),
+                           (uint32_t)s.aggs, (uint8_t*)d_status + s.agg0);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+}  // namespace
+
+BLSGPU_EXPORT int blsgpu_verify_aggregates_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_msg_hashes, size_t n_msgs, const void* d_keys,
+                                               const void* d_exps, size_t n_keys, const uint32_t* grp_off, const uint32_t* grp_msg, size_t n_grp,
+                                               const uint32_t* agg_off, size_t m, void* d_status, void* d_out_gt, void* stream) {
+    if (int rc = veragg_args(c, d_sigs, d_msg_hashes, n_msgs, d_keys, n_keys, grp_off, grp_msg, n_grp, agg_off, m, d_status)) return rc < 0 ? rc : 0;
+    const verify_agg::Plan p = veragg_plan(c, grp_off, grp_msg, n_grp, agg_off, m, n_keys, n_msgs);
+    if (p.refusal) return veragg_refuse(p);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    StreamGuard sg(c, st);
+    return veragg_launch(c, p, d_sigs, d_msg_hashes, d_keys, d_exps, d_status, d_out_gt, st);
+}
+
+BLSGPU_EXPORT int blsgpu_verify_aggregates(blsgpu_ctx* c, const uint8_t* sigs, const uint8_t* msg_hashes, size_t n_msgs, const uint8_t* keys,
+                                           const uint8_t* exps, size_t n_keys, const uint32_t* grp_off, const uint32_t* grp_msg, size_t n_grp,
+                                           const uint32_t* agg_off, size_t m, uint8_t* status, uint8_t* out_gt) {
+    if (int rc = veragg_args(c, sigs, msg_hashes, n_msgs, keys, n_keys, grp_off, grp_msg, n_grp, agg_off, m, status)) return rc < 0 ? rc : 0;
+    const verify_agg::Plan p = veragg_plan(c, grp_off, grp_msg, n_grp, agg_off, m, n_keys, n_msgs);
+    if (p.refusal) return veragg_refuse(p);
+    HIP_TRY(hipSetDevice(c->device));
+    Staging s(c);
+    const int ds = s.in(sigs, m * BLSGPU_G2_BYTES), dh = s.in(n_msgs ? msg_hashes : nullptr, n_msgs * 32),
+              dk = s.in(n_keys ? keys : nullptr, n_keys * BLSGPU_G1_BYTES), de = s.in(n_keys ? exps : nullptr, n_keys * 32),
+              dst = s.out(status, m), dgt = s.out(out_gt, m * BLSGPU_FQ12_BYTES);
+    if (int rc = s.alloc()) return rc;
+    if (int rc = s.up()) return rc;
+    {
+        StreamGuard sg(c, nullptr);
+        if (int rc = veragg_launch(c, p, s.at(ds), s.opt(dh), s.opt(dk), s.opt(de), s.at(dst), s.opt(dgt), nullptr)) return rc;
+    }
     return s.down();
 }
 

@@ -74,6 +74,7 @@ enum BufId {
     B_PSCAN_RANGE,       // blsgpu_g?_range_sums*: a flag word and, when the points take several slices, the record and count at every range's begin
     B_SIGDIV_WS,         // blsgpu_sig_divide*: the head words, the mismatch / zero / non-unit / status bytes per point, the refused byte and the range per dividend, the scalars and the working copy of the points
     B_PAIRR_WS,          // blsgpu_pairing_multi_ranges*: the partials (a slot per range, then the slots of the folds), every slice's chunk table and every fold level's table (pairing_ranges_plan.h)
+    B_VERAGG_WS,         // blsgpu_verify_aggregates*: the key sums and their flags, the hashed points, the undecided bytes, one slice's pair list and results, and every table of the call (verify_agg_plan.h)
     B_COUNT
 };
 // (unit: what the buffer is counted in -- whole partials, whole u32 entries, bytes)
@@ -83,12 +84,12 @@ constexpr BufInfo BUF_INFO[B_COUNT] = {
     {BLSGPU_WS_LINE_PRODUCTS, 1}, {BLSGPU_WS_LINE_PRODUCTS, 1}, {BLSGPU_WS_FLAGS_AND_LISTS, 1}, {BLSGPU_WS_FLAGS_AND_LISTS, 4},
     {BLSGPU_WS_FLAGS_AND_LISTS, 1}, {BLSGPU_WS_GROUP_SUMS, 4}, {BLSGPU_WS_GROUP_SUMS, 4}, {BLSGPU_WS_SLOTS, 1}, {BLSGPU_WS_SLOTS, 1},
     {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1},
-    {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}};   // no field of their own: they count in the total only
+    {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}, {BLSGPU_WS_TOTAL, 1}};   // no field of their own: they count in the total only
 
 }  // namespace
 
 // (the knobs of the G1 / G2 sums are msm::Knobs, msm_plan.h; those of the pairing path pairing::Knobs, pairing_plan.h, and
-// pairing_ranges::Knobs, pairing_ranges_plan.h)
+// pairing_ranges::Knobs, pairing_ranges_plan.h; verify_agg_plan.h has none of its own)
 struct blsgpu_ctx : msm::Knobs, pairing::Knobs, pairing_ranges::Knobs {
     int device = 0;
     blsgpu::VmTables tabs{};
