@@ -47,6 +47,7 @@
 
 #if BLSGPU_EMIT(BLSGPU_TU_HOST)
 #include "bisect_plan.h"
+#include "find_plan.h"
 #include "msm_plan.h"
 #include "pairing_plan.h"
 #include "pairing_ranges_plan.h"
@@ -155,6 +156,12 @@ static_assert(sizeof(msm::SortedPlan::bias) == sizeof(blsgpu::SrtBias), "msm_pla
 // ... and ragged_plan.h (the range sums, the ragged sums, the short scalars and the signature division below)
 constexpr ragged::Consts RAGGED_CONSTS = {blsgpu::pscan::CHUNK, blsgpu::pscan::MID_THREADS, blsgpu::msmr::CHUNK, blsgpu::msmr::SCAN_THREADS};
 static_assert(ragged::same(RAGGED_CONSTS, ragged::GFX950), "ragged_plan.h: GFX950 (the host test's values) differs from the kernel files");
+// ... and find_plan.h (the three forgery finders below)
+static_assert(find::G1 == BLSGPU_G1_BYTES && find::G2 == BLSGPU_G2_BYTES && find::FQ12 == BLSGPU_FQ12_BYTES &&
+                  find::NODE_BYTES == sizeof(blsgpu::sigsh::Node) && find::THREADS == blsgpu::sigsh::THREADS &&
+                  find::THREADS == blsgpu::bfind::THREADS && find::THREADS == blsgpu::pscan::THREADS && find::G1_Q == blsgpu::bfind::G1_Q &&
+                  find::G2_Q == blsgpu::bfind::G2_Q && find::G1_Q == blsgpu::sigsh::G1_Q && find::G2_Q == blsgpu::sigsh::G2_Q,
+              "find_plan.h: its constants (the host test's values) differ from blsgpu.h or the kernel files");
 
 // The wide machine's Horner (blsgpu_msmw.hip): list g of `lists` -> sum_i 2^(cbits i) in[g][i], one wavefront per list; AFFINE = 0
 // leaves projective sums for the next step, AFFINE = 1 writes the caller's affine point and its infinity flag.
@@ -894,10 +901,11 @@ int sig_shares_args(const blsgpu_ctx* c, size_t k, size_t groups, size_t n_keys,
     if (groups == 0) return 1;
     if (n_keys == 0) return fail(-EINVAL, "key index out of range");
     if (null_buffer) return fail(-EINVAL, "NULL argument");
-    if (groups > 0x7FFFFFFFull || n_keys > 0x7FFFFFFFull || k * groups > 0xFFFFFFF0ull) return fail(-EINVAL, "batch too large");
+    if (find::shares_too_large(k, groups, n_keys)) return fail(-EINVAL, "batch too large");
     return 0;
 }
-// Sessions in slices; per slice the once-per-call stages into B_SHR_WS, then the rounds (bisect_rounds): the nodes of a round
+// Sessions in slices (find::plan_shares: the slice and B_SHR_WS; find::shares_round: B_SHR_ROUND and the grids of a round); per
+// slice the once-per-call stages into B_SHR_WS, then the rounds (bisect_rounds): the nodes of a round
 // (all of one length) go up and their verdict bytes come back.  A node's second half that lies past the session's k shares holds
 // nothing and is not tested.  `scan`: the _dev form's device scan of the key indices first.  stats (host, may be NULL): rounds,
 // node tests.
@@ -905,81 +913,64 @@ int sig_shares_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_t
                    const void* d_hashes, const void* d_weights, int scaled, size_t k, size_t groups, void* d_status, void* d_sess,
                    uint64_t* stats, bool scan, hipStream_t st) {
     using namespace blsgpu::sigsh;
-    const size_t K = bisect::ceil_pow2(k);
-    // slices of sessions whose kept arrays, and whose largest possible round (every leaf a node), stay below 2 GB each
-    const size_t keep_per = k * (2 + 3 * 32 + 2 * BLSGPU_G1_BYTES + BLSGPU_G2_BYTES) + BLSGPU_G2_BYTES + 1;
-    const size_t round_per = K * (sizeof(Node) + 3 * BLSGPU_G1_BYTES + 4 * BLSGPU_G2_BYTES + BLSGPU_FQ12_BYTES + 3);
-    size_t slice = ((size_t)2 << 30) / (keep_per > round_per ? keep_per : round_per);
-    if (slice < 1) slice = 1;
-    slice = slice_len(c, slice);
-    if (slice > groups) slice = groups;
-    const size_t n0 = slice * k;
-    bisect::Layout w{256, 256};                                              // [0, 4): the flag word of the index scan
-    const size_t o_keyst = w.take(n_keys), o_sigst = w.take(n0), o_h = w.take(slice * BLSGPU_G2_BYTES), o_hinf = w.take(slice),
-                 o_lam = w.take(scaled ? n0 * 32 : 0), o_r = w.take(n0 * 32), o_w = w.take(n0 * 32), o_pk = w.take(n0 * BLSGPU_G1_BYTES),
-                 o_elig = w.take(n0), o_a = w.take(n0 * BLSGPU_G2_BYTES), o_b = w.take(n0 * BLSGPU_G1_BYTES);
+    const find::SharesPlan p = find::plan_shares(*c, k, groups, n_keys, scaled != 0);
+    const find::SharesWs& w = p.w;
+    const size_t slice = p.slice, K = p.K;
     StreamGuard sg(c, st);
-    if (int rc = c->grow(B_SHR_WS, w.off)) return rc;
+    if (int rc = c->grow(B_SHR_WS, w.bytes)) return rc;
     char* const W = c->at<char>(B_SHR_WS);
     if (scan) {
         uint32_t bad = 0;
         if (int rc = scan_indices(c, W, d_key_idx, n_keys, nullptr, 0, groups * k, false, bad, st)) return rc;
         if (bad) return fail(-EINVAL, "key index out of range");
     }
-    if (int rc = subgroup_dev(c, 1, d_keys, n_keys, W + o_keyst, st)) return rc;
+    if (int rc = subgroup_dev(c, 1, d_keys, n_keys, W + w.o_keyst, st)) return rc;
     if (!scaled) HIP_TRY(hipMemsetAsync(d_sess, 1, groups, st));
     bisect::State<Node> bis;
     int rc = for_slices(groups, slice, [&](size_t lo, size_t m) {
-        const size_t n = m * k;
+        const size_t n = p.at(m).n;
         const char* sigs = (const char*)d_sigs + lo * k * BLSGPU_G2_BYTES;
         uint8_t* status = (uint8_t*)d_status + lo * k;
-        if (int rc = subgroup_dev(c, 2, sigs, n, W + o_sigst, st)) return rc;
-        if (int rc = blsgpu_hash_to_g2_dev(c, (const char*)d_hashes + lo * 32, m, W + o_h, st)) return rc;
+        if (int rc = subgroup_dev(c, 2, sigs, n, W + w.o_sigst, st)) return rc;
+        if (int rc = blsgpu_hash_to_g2_dev(c, (const char*)d_hashes + lo * 32, m, W + w.o_h, st)) return rc;
         if (scaled) {
-            if (int rc = lagrange_launch(c, (const char*)d_x + lo * k * 32, k, m, W + o_lam, (uint8_t*)d_sess + lo, st)) return rc;
+            if (int rc = lagrange_launch(c, (const char*)d_x + lo * k * 32, k, m, W + w.o_lam, (uint8_t*)d_sess + lo, st)) return rc;
         }
-        hipLaunchKernelGGL(k_share_weights, dim3((unsigned)((n + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, (const uint32_t*)sigs,
-                           (const uint8_t*)(W + o_sigst), (const uint32_t*)d_keys, (const uint8_t*)(W + o_keyst),
-                           (const uint32_t*)d_key_idx + lo * k, scaled ? (const uint8_t*)(W + o_lam) : nullptr,
+        hipLaunchKernelGGL(k_share_weights, dim3(p.at(m).g_weights), dim3(THREADS), 0, st, (const uint32_t*)sigs,
+                           (const uint8_t*)(W + w.o_sigst), (const uint32_t*)d_keys, (const uint8_t*)(W + w.o_keyst),
+                           (const uint32_t*)d_key_idx + lo * k, scaled ? (const uint8_t*)(W + w.o_lam) : nullptr,
                            scaled ? (const uint8_t*)d_sess + lo : nullptr, (const uint8_t*)d_weights + lo * k * 8,
-                           (const uint32_t*)(W + o_h), (uint32_t)k, (uint32_t)n, (uint8_t*)(W + o_r), (uint8_t*)(W + o_w),
-                           (uint32_t*)(W + o_pk), (uint8_t*)(W + o_elig), (uint8_t*)(W + o_hinf), status);
+                           (const uint32_t*)(W + w.o_h), (uint32_t)k, (uint32_t)n, (uint8_t*)(W + w.o_r), (uint8_t*)(W + w.o_w),
+                           (uint32_t*)(W + w.o_pk), (uint8_t*)(W + w.o_elig), (uint8_t*)(W + w.o_hinf), status);
         HIP_TRY(hipGetLastError());
         // the leaves: scalar multiplications as sums of one point with device scalars
-        if (int rc = msm_dev<2>(c, sigs, W + o_r, 1, n, W + o_a, nullptr, st)) return rc;
-        if (int rc = msm_dev<1>(c, W + o_pk, W + o_w, 1, n, W + o_b, nullptr, st)) return rc;
+        if (int rc = msm_dev<2>(c, sigs, W + w.o_r, 1, n, W + w.o_a, nullptr, st)) return rc;
+        if (int rc = msm_dev<1>(c, W + w.o_pk, W + w.o_w, 1, n, W + w.o_b, nullptr, st)) return rc;
         bis.nodes.resize(m);
         for (size_t s = 0; s < m; s++) bis.nodes[s] = {(uint32_t)s, 0u};
         return bisect_rounds(bis, K, k, st, [&](std::vector<Node>& cur, size_t len, const void*& d_verdict) {
-            const size_t nn = cur.size(), slots = nn * len;
-            const uint32_t lg = (uint32_t)__builtin_ctzll(len);
-            bisect::Layout r{256, 0};
-            const size_t r_nodes = r.take(nn * sizeof(Node)), r_ga = r.take(slots * BLSGPU_G2_BYTES), r_gb = r.take(slots * BLSGPU_G1_BYTES),
-                         r_s = r.take(nn * BLSGPU_G2_BYTES), r_p = r.take(nn * BLSGPU_G1_BYTES), r_sinf = r.take(nn), r_pinf = r.take(nn),
-                         r_g1 = r.take(nn * 2 * BLSGPU_G1_BYTES), r_g2 = r.take(nn * 2 * BLSGPU_G2_BYTES),
-                         r_e = r.take(nn * BLSGPU_FQ12_BYTES), r_v = r.take(nn);
-            if (int rc = c->grow(B_SHR_ROUND, r.off)) return rc;
+            const size_t nn = cur.size();
+            const find::SharesRound r = find::shares_round(nn, len, k);
+            if (int rc = c->grow(B_SHR_ROUND, r.w.bytes)) return rc;
             char* const R = c->at<char>(B_SHR_ROUND);
-            const Node* d_nodes = (const Node*)(R + r_nodes);
-            HIP_TRY(hipMemcpyAsync(R + r_nodes, cur.data(), nn * sizeof(Node), hipMemcpyHostToDevice, st));
-            const size_t gtotal = slots * (G1_Q + G2_Q);
-            hipLaunchKernelGGL(k_share_gather, dim3((unsigned)((gtotal + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, d_nodes, lg, gtotal,
-                               (uint32_t)k, (const uint4*)(W + o_a), (const uint4*)(W + o_b), (const uint8_t*)(W + o_elig),
-                               (uint4*)(R + r_ga), (uint4*)(R + r_gb));
+            const Node* d_nodes = (const Node*)(R + r.w.o_nodes);
+            HIP_TRY(hipMemcpyAsync(R + r.w.o_nodes, cur.data(), nn * sizeof(Node), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_share_gather, dim3(r.g_gather), dim3(THREADS), 0, st, d_nodes, r.lg, r.gtotal,
+                               (uint32_t)k, (const uint4*)(W + w.o_a), (const uint4*)(W + w.o_b), (const uint8_t*)(W + w.o_elig),
+                               (uint4*)(R + r.w.o_ga), (uint4*)(R + r.w.o_gb));
             HIP_TRY(hipGetLastError());
-            if (int rc = msm_dev<2>(c, R + r_ga, nullptr, len, nn, R + r_s, R + r_sinf, st)) return rc;
-            if (int rc = msm_dev<1>(c, R + r_gb, nullptr, len, nn, R + r_p, R + r_pinf, st)) return rc;
-            const size_t ptotal = nn * (2 * G1_Q + 2 * G2_Q);
-            hipLaunchKernelGGL(k_share_pairs, dim3((unsigned)((ptotal + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, d_nodes, ptotal,
-                               (const uint4*)(R + r_s), (const uint8_t*)(R + r_sinf), (const uint4*)(R + r_p), (const uint8_t*)(R + r_pinf),
-                               (const uint4*)(W + o_h), (const uint8_t*)(W + o_hinf), (uint4*)(R + r_g1), (uint4*)(R + r_g2));
+            if (int rc = msm_dev<2>(c, R + r.w.o_ga, nullptr, len, nn, R + r.w.o_s, R + r.w.o_sinf, st)) return rc;
+            if (int rc = msm_dev<1>(c, R + r.w.o_gb, nullptr, len, nn, R + r.w.o_p, R + r.w.o_pinf, st)) return rc;
+            hipLaunchKernelGGL(k_share_pairs, dim3(r.g_pairs), dim3(THREADS), 0, st, d_nodes, r.ptotal,
+                               (const uint4*)(R + r.w.o_s), (const uint8_t*)(R + r.w.o_sinf), (const uint4*)(R + r.w.o_p), (const uint8_t*)(R + r.w.o_pinf),
+                               (const uint4*)(W + w.o_h), (const uint8_t*)(W + w.o_hinf), (uint4*)(R + r.w.o_g1), (uint4*)(R + r.w.o_g2));
             HIP_TRY(hipGetLastError());
-            if (int rc = blsgpu_pairing_multi_batch_dev(c, R + r_g1, R + r_g2, nullptr, 2, nn, R + r_e, st)) return rc;
-            hipLaunchKernelGGL(k_share_verdict, dim3((unsigned)((nn + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, d_nodes, (uint32_t)nn,
-                               (const uint4*)(R + r_e), (const uint8_t*)(R + r_sinf), (const uint8_t*)(R + r_pinf),
-                               (const uint8_t*)(W + o_hinf), len == 1 ? 1u : 0u, (uint32_t)k, (uint8_t*)(R + r_v), status);
+            if (int rc = blsgpu_pairing_multi_batch_dev(c, R + r.w.o_g1, R + r.w.o_g2, nullptr, 2, nn, R + r.w.o_e, st)) return rc;
+            hipLaunchKernelGGL(k_share_verdict, dim3(r.g_verdict), dim3(THREADS), 0, st, d_nodes, (uint32_t)nn,
+                               (const uint4*)(R + r.w.o_e), (const uint8_t*)(R + r.w.o_sinf), (const uint8_t*)(R + r.w.o_pinf),
+                               (const uint8_t*)(W + w.o_hinf), len == 1 ? 1u : 0u, (uint32_t)k, (uint8_t*)(R + r.w.o_v), status);
             HIP_TRY(hipGetLastError());
-            d_verdict = R + r_v;
+            d_verdict = R + r.w.o_v;
             return 0;
         });
     });
@@ -1055,7 +1046,7 @@ int verify_find_args(const blsgpu_ctx* c, size_t n, size_t n_keys, size_t n_msgs
     if (null_buffer) return fail(-EINVAL, "NULL argument");
     if (n_keys == 0) return fail(-EINVAL, "key index out of range");
     if (n_msgs == 0) return fail(-EINVAL, "message index out of range");
-    if (n > 0x7FFFFFF0ull || n_keys > 0x7FFFFFFFull || n_msgs > ((size_t)2 << 30) / BLSGPU_G2_BYTES) return fail(-EINVAL, "batch too large");
+    if (find::find_too_large(n, n_keys, n_msgs)) return fail(-EINVAL, "batch too large");
     return 0;
 }
 // e(-G1, G2) in B_FIND_UNIT (+512), from the pairing itself, once per context: what k_find_verdict compares a node with S = O with
@@ -1070,25 +1061,9 @@ int find_unit(blsgpu_ctx* c, hipStream_t st) {
     c->find_unit_ready = true;
     return 0;
 }
-// What the two verify_find forms share.  The slice: items whose kept arrays (`keep_per` bytes an item), and whose largest
-// possible round (`round_per`), stay below 2 GB each
-size_t find_slice(const blsgpu_ctx* c, size_t n, size_t keep_per, size_t round_per) {
-    const size_t slice = slice_len(c, (((size_t)2 << 30) - ((size_t)1 << 20)) / (keep_per > round_per ? keep_per : round_per));
-    return slice < n ? slice : n;
-}
-// B_FIND_WS: [0, 4) the flag word of the index scan, [4, 8) n_e, [8, 12) the number of runs, then the arrays of the call (key
-// flags, hashes) and of a slice; with `rcap` (the folded form: entries of the run table) its dense leaves and run table as well
-struct FindWs { size_t o_keyst, o_h, o_sigst, o_r, o_elig, o_dense, o_a, o_b, o_ad, o_bd, o_rb, o_rmsg, bytes; };
-FindWs find_ws(size_t n_keys, size_t n_msgs, size_t slice, size_t rcap) {
-    bisect::Layout l{256, 256};
-    FindWs w = {};
-    w.o_keyst = l.take(n_keys), w.o_h = l.take(n_msgs * BLSGPU_G2_BYTES), w.o_sigst = l.take(slice), w.o_r = l.take(slice * 8);
-    w.o_elig = l.take(slice), w.o_dense = l.take(slice * 4), w.o_a = l.take(slice * BLSGPU_G2_BYTES), w.o_b = l.take(slice * BLSGPU_G1_BYTES);
-    if (rcap)
-        w.o_ad = l.take(slice * BLSGPU_G2_BYTES), w.o_bd = l.take(slice * BLSGPU_G1_BYTES), w.o_rb = l.take(rcap * 4), w.o_rmsg = l.take(rcap * 4);
-    w.bytes = l.off;
-    return w;
-}
+// What the two verify_find forms share: find::plan_find gives the slice and B_FIND_WS, find::plain_round / find::folded_round
+// B_FIND_ROUND and the grids of a round (find_plan.h).
+using find::FindWs;
 // once per call: the workspace, the _dev form's device scan of the indices (`scan`; `mono`: the folded form's precondition too),
 // e(-G1, G2), the key subgroup flags and the distinct hashes, once each
 int find_call_stages(blsgpu_ctx* c, const FindWs& w, const void* d_keys, size_t n_keys, const void* d_key_idx, const void* d_hashes,
@@ -1108,16 +1083,17 @@ int find_call_stages(blsgpu_ctx* c, const FindWs& w, const void* d_keys, size_t 
 // once per slice of m items from `lo`: the signature subgroup flags, the weights, eligibility and status bytes (k_find_settle),
 // the dense order and n_e (k_find_dense), what `after_dense` enqueues, and the leaves A_i = r_i sig_i, B_i = r_i keys[key_idx[i]]
 // by item (those of items that are not eligible are never read)
-struct FindSlice { const char* sigs; const uint32_t *kidx, *midx, *dense; uint8_t* status; };
+struct FindSlice { const char* sigs; const uint32_t *kidx, *midx, *dense; uint8_t* status; find::FindSlice at; };
 template <class F>
-int find_slice_stages(blsgpu_ctx* c, const FindWs& w, char* W, const void* d_sigs, const void* d_keys, size_t n_keys, const void* d_key_idx,
-                      const void* d_msg_idx, const void* d_weights, void* d_status, size_t lo, size_t m, hipStream_t st, FindSlice& s,
-                      F after_dense) {
+int find_slice_stages(blsgpu_ctx* c, const find::FindPlan& p, char* W, const void* d_sigs, const void* d_keys, size_t n_keys,
+                      const void* d_key_idx, const void* d_msg_idx, const void* d_weights, void* d_status, size_t lo, size_t m, hipStream_t st,
+                      FindSlice& s, F after_dense) {
     using namespace blsgpu::bfind;
+    const FindWs& w = p.w;
     s = {(const char*)d_sigs + lo * BLSGPU_G2_BYTES, (const uint32_t*)d_key_idx + lo, (const uint32_t*)d_msg_idx + lo,
-         (const uint32_t*)(W + w.o_dense), (uint8_t*)d_status + lo};
+         (const uint32_t*)(W + w.o_dense), (uint8_t*)d_status + lo, p.at(m)};
     if (int rc = subgroup_dev(c, 2, s.sigs, m, W + w.o_sigst, st)) return rc;
-    hipLaunchKernelGGL(k_find_settle, dim3((unsigned)((m + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, (const uint32_t*)s.sigs,
+    hipLaunchKernelGGL(k_find_settle, dim3(s.at.g_settle), dim3(THREADS), 0, st, (const uint32_t*)s.sigs,
                        (const uint8_t*)(W + w.o_sigst), (const uint32_t*)d_keys, (const uint8_t*)(W + w.o_keyst), s.kidx,
                        (const uint32_t*)(W + w.o_h), s.midx, (const uint8_t*)d_weights + lo * 8, (uint32_t)m, (uint8_t*)(W + w.o_r),
                        (uint8_t*)(W + w.o_elig), s.status);
@@ -1138,18 +1114,16 @@ int verify_find_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_
                     size_t n_msgs, const void* d_msg_idx, const void* d_weights, size_t n, void* d_status, uint64_t* stats, bool scan,
                     hipStream_t st) {
     using namespace blsgpu::bfind;
-    const size_t keep_per = 1 + 8 + 1 + 4 + BLSGPU_G2_BYTES + BLSGPU_G1_BYTES;
-    const size_t round_per = 4 + 2 * BLSGPU_G2_BYTES + 1 + 2 * BLSGPU_G1_BYTES + 2 * BLSGPU_G2_BYTES + BLSGPU_FQ12_BYTES + 1;   // every leaf a node
-    const size_t slice = find_slice(c, n, keep_per, round_per);
-    const FindWs w = find_ws(n_keys, n_msgs, slice, 0);
+    const find::FindPlan plan = find::plan_find(*c, n, n_keys, n_msgs, false);
+    const FindWs& w = plan.w;
     StreamGuard sg(c, st);
     if (int rc = find_call_stages(c, w, d_keys, n_keys, d_key_idx, d_hashes, n_msgs, d_msg_idx, n, scan, false, st)) return rc;
     char* const W = c->at<char>(B_FIND_WS);
     const uint4* d_unit = (const uint4*)(c->at<char>(B_FIND_UNIT) + 512);
     bisect::State<uint32_t> bis;
-    int rc = for_slices(n, slice, [&](size_t lo, size_t m) {
+    int rc = for_slices(n, plan.slice, [&](size_t lo, size_t m) {
         FindSlice s;
-        if (int rc = find_slice_stages(c, w, W, d_sigs, d_keys, n_keys, d_key_idx, d_msg_idx, d_weights, d_status, lo, m, st, s, [] {})) return rc;
+        if (int rc = find_slice_stages(c, plan, W, d_sigs, d_keys, n_keys, d_key_idx, d_msg_idx, d_weights, d_status, lo, m, st, s, [] {})) return rc;
         uint32_t n_e = 0;
         HIP_TRY(hipMemcpyAsync(&n_e, W + 4, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -1158,43 +1132,29 @@ int verify_find_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys, size_
         return bisect_rounds(bis, bisect::ceil_pow2(n_e), n_e, st, [&](std::vector<uint32_t>& order, size_t L, const void*& d_verdict) {
             bisect::Part shape[2];
             bisect::plain_round(order, L, n_e, shape);
-            const size_t nn = order.size();
-            struct { size_t nodes, len, ga, s, sinf, g1, g2, e; } part[2] = {{shape[0].nodes, shape[0].len}, {shape[1].nodes, shape[1].len}};
-            bisect::Layout r{256, 0};
-            const size_t r_off = r.take(nn * 4), r_v = r.take(nn);
-            for (auto& p : part) {
-                p.ga = r.take(p.nodes * p.len * BLSGPU_G2_BYTES);
-                p.s = r.take(p.nodes * BLSGPU_G2_BYTES);
-                p.sinf = r.take(p.nodes);
-                p.g1 = r.take(p.nodes * (p.len + 1) * BLSGPU_G1_BYTES);
-                p.g2 = r.take(p.nodes * (p.len + 1) * BLSGPU_G2_BYTES);
-                p.e = r.take(p.nodes * BLSGPU_FQ12_BYTES);
-            }
-            if (int rc = c->grow(B_FIND_ROUND, r.off)) return rc;
+            const find::PlainRound r = find::plain_round(shape);
+            if (int rc = c->grow(B_FIND_ROUND, r.bytes)) return rc;
             char* const R = c->at<char>(B_FIND_ROUND);
-            HIP_TRY(hipMemcpyAsync(R + r_off, order.data(), nn * 4, hipMemcpyHostToDevice, st));
-            size_t first = 0;
-            for (const auto& p : part) {
+            HIP_TRY(hipMemcpyAsync(R + r.head.o_off, order.data(), r.nn * 4, hipMemcpyHostToDevice, st));
+            for (const find::PlainPart& p : r.part) {
                 if (p.nodes == 0) continue;
-                const uint32_t* d_off = (const uint32_t*)(R + r_off) + first;
-                const size_t gtotal = p.nodes * p.len * G2_Q, ptotal = p.nodes * (p.len + 1) * (G1_Q + G2_Q);
-                hipLaunchKernelGGL(k_find_gather, dim3((unsigned)((gtotal + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, d_off,
-                                   (uint32_t)p.len, gtotal, s.dense, (const uint4*)(W + w.o_a), (uint4*)(R + p.ga));
+                const uint32_t* d_off = (const uint32_t*)(R + r.head.o_off) + p.first;
+                hipLaunchKernelGGL(k_find_gather, dim3(p.g_gather), dim3(THREADS), 0, st, d_off, (uint32_t)p.len, p.gtotal, s.dense,
+                                   (const uint4*)(W + w.o_a), (uint4*)(R + p.w.o_ga));
                 HIP_TRY(hipGetLastError());
-                if (int rc = msm_dev<2>(c, R + p.ga, nullptr, p.len, p.nodes, R + p.s, R + p.sinf, st)) return rc;
-                hipLaunchKernelGGL(k_find_pairs, dim3((unsigned)((ptotal + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, d_off,
-                                   (uint32_t)p.len, ptotal, s.dense, (const uint4*)(R + p.s), (const uint8_t*)(R + p.sinf),
-                                   (const uint4*)(W + w.o_b), (const uint4*)(W + w.o_h), s.midx, (uint4*)(R + p.g1), (uint4*)(R + p.g2));
+                if (int rc = msm_dev<2>(c, R + p.w.o_ga, nullptr, p.len, p.nodes, R + p.w.o_s, R + p.w.o_sinf, st)) return rc;
+                hipLaunchKernelGGL(k_find_pairs, dim3(p.g_pairs), dim3(THREADS), 0, st, d_off, (uint32_t)p.len, p.ptotal, s.dense,
+                                   (const uint4*)(R + p.w.o_s), (const uint8_t*)(R + p.w.o_sinf), (const uint4*)(W + w.o_b),
+                                   (const uint4*)(W + w.o_h), s.midx, (uint4*)(R + p.w.o_g1), (uint4*)(R + p.w.o_g2));
                 HIP_TRY(hipGetLastError());
-                if (int rc = blsgpu_pairing_multi_batch_dev(c, R + p.g1, R + p.g2, nullptr, p.len + 1, p.nodes, R + p.e, st)) return rc;
-                hipLaunchKernelGGL(k_find_verdict, dim3((unsigned)((p.nodes + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, d_off,
-                                   (uint32_t)p.nodes, (const uint4*)(R + p.e), (const uint8_t*)(R + p.sinf), d_unit, L == 1 ? 1u : 0u, s.dense,
-                                   (uint8_t*)(R + r_v) + first, s.status);
+                if (int rc = blsgpu_pairing_multi_batch_dev(c, R + p.w.o_g1, R + p.w.o_g2, nullptr, p.gsz, p.nodes, R + p.w.o_e, st)) return rc;
+                hipLaunchKernelGGL(k_find_verdict, dim3(p.g_verdict), dim3(THREADS), 0, st, d_off, (uint32_t)p.nodes, (const uint4*)(R + p.w.o_e),
+                                   (const uint8_t*)(R + p.w.o_sinf), d_unit, L == 1 ? 1u : 0u, s.dense, (uint8_t*)(R + r.head.o_v) + p.first,
+                                   s.status);
                 HIP_TRY(hipGetLastError());
-                first += p.nodes;
-                bis.pairs += p.nodes * (p.len + 1);
+                bis.pairs += p.pairs;
             }
-            d_verdict = R + r_v;
+            d_verdict = R + r.head.o_v;
             return 0;
         });
     });
@@ -1484,35 +1444,28 @@ int verify_find_folded_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys
                            hipStream_t st) {
     using namespace blsgpu::bfind;
     namespace ps = blsgpu::pscan;
-    // a round has at most one node per item and at most 2 nodes + runs <= 3 items slots
-    const size_t keep_per = 1 + 8 + 1 + 4 + 2 * (BLSGPU_G2_BYTES + BLSGPU_G1_BYTES) + 8;
-    const size_t slot_per = 8 + 4 + 4 + 1 + 1 + 2 * BLSGPU_G1_BYTES + BLSGPU_G2_BYTES;
-    const size_t round_per = 3 * slot_per + 4 + 8 + 4 + BLSGPU_G2_BYTES + 3 + BLSGPU_FQ12_BYTES;
-    const size_t slice = find_slice(c, n, keep_per, round_per);
-    const size_t rcap = (slice < n_msgs ? slice : n_msgs) + 1;                 // entries of the run table
-    const FindWs w = find_ws(n_keys, n_msgs, slice, rcap);
+    const find::FindPlan fp = find::plan_find(*c, n, n_keys, n_msgs, true);
+    const FindWs& w = fp.w;
     StreamGuard sg(c, st);
     if (int rc = find_call_stages(c, w, d_keys, n_keys, d_key_idx, d_hashes, n_msgs, d_msg_idx, n, scan, true, st)) return rc;
     char* const W = c->at<char>(B_FIND_WS);
     const uint4* d_unit = (const uint4*)(c->at<char>(B_FIND_UNIT) + 512);
     bisect::State<uint32_t> bis;
     bisect::FoldPlan plan;                                                   // plan.tab goes up in every round: written by the round alone
-    std::vector<uint32_t> rb(rcap), rmsg(rcap);
-    int rc = for_slices(n, slice, [&](size_t lo, size_t m) {
+    std::vector<uint32_t> rb(fp.rcap), rmsg(fp.rcap);
+    int rc = for_slices(n, fp.slice, [&](size_t lo, size_t m) {
         FindSlice s;
-        if (int rc = find_slice_stages(c, w, W, d_sigs, d_keys, n_keys, d_key_idx, d_msg_idx, d_weights, d_status, lo, m, st, s, [&] {
+        if (int rc = find_slice_stages(c, fp, W, d_sigs, d_keys, n_keys, d_key_idx, d_msg_idx, d_weights, d_status, lo, m, st, s, [&] {
                 hipLaunchKernelGGL(ps::k_fold_runs, dim3(1), dim3(ps::RUN_THREADS), 0, st, s.dense, (const uint32_t*)(W + 4), s.midx,
                                    (uint32_t*)(W + w.o_rb), (uint32_t*)(W + w.o_rmsg), (uint32_t*)(W + 8));
             }))
             return rc;
         // the leaves of the eligible items in the dense order
-        const size_t ltotal = m * 18;
-        hipLaunchKernelGGL(ps::k_fold_leaves, dim3((unsigned)((ltotal + ps::THREADS - 1) / ps::THREADS)), dim3(ps::THREADS), 0, st, s.dense,
-                           (const uint32_t*)(W + 4), ltotal, (const uint4*)(W + w.o_a), (const uint4*)(W + w.o_b), (uint4*)(W + w.o_ad),
-                           (uint4*)(W + w.o_bd));
+        hipLaunchKernelGGL(ps::k_fold_leaves, dim3(s.at.g_leaves), dim3(ps::THREADS), 0, st, s.dense, (const uint32_t*)(W + 4), s.at.ltotal,
+                           (const uint4*)(W + w.o_a), (const uint4*)(W + w.o_b), (uint4*)(W + w.o_ad), (uint4*)(W + w.o_bd));
         HIP_TRY(hipGetLastError());
         uint32_t head[2] = {0, 0};                                           // n_e, the number of runs
-        const size_t rn = (m < n_msgs ? m : n_msgs) + 1;
+        const size_t rn = s.at.rn;
         HIP_TRY(hipMemcpyAsync(head, W + 4, 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(rb.data(), W + w.o_rb, rn * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(rmsg.data(), W + w.o_rmsg, rn * 4, hipMemcpyDeviceToHost, st));
@@ -1529,40 +1482,34 @@ int verify_find_folded_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys
         return bisect_rounds(bis, bisect::ceil_pow2(n_e), n_e, st, [&](std::vector<uint32_t>& nodes, size_t L, const void*& d_verdict) {
             bisect::fold_round(nodes, L, n_e, rb.data(), rmsg.data(), n_runs, plan);
             const bisect::FoldPlan& t = plan;
-            const size_t nn = nodes.size(), slots = t.slots, nb = t.nb;
-            bisect::Layout r{256, 0};
-            const size_t r_tab = r.take(t.tab.size() * 4), r_code = r.take(slots), r_bflag = r.take(nb), r_b = r.take(nb * BLSGPU_G1_BYTES),
-                         r_sflag = r.take(nn), r_odd = r.take(nn), r_v = r.take(nn), r_s = r.take(nn * BLSGPU_G2_BYTES),
-                         r_g1 = r.take(slots * BLSGPU_G1_BYTES), r_g2 = r.take(slots * BLSGPU_G2_BYTES), r_e = r.take(nn * BLSGPU_FQ12_BYTES);
-            if (int rc = c->grow(B_FIND_ROUND, r.off)) return rc;
+            const find::FoldRound r = find::folded_round(t);
+            const size_t nn = r.nn;
+            if (int rc = c->grow(B_FIND_ROUND, r.w.bytes)) return rc;
             char* const R = c->at<char>(B_FIND_ROUND);
-            const uint32_t* const T = (const uint32_t*)(R + r_tab);
-            HIP_TRY(hipMemcpyAsync(R + r_tab, t.tab.data(), t.tab.size() * 4, hipMemcpyHostToDevice, st));
-            if (int rc = pscan_ranges_launch<1>(wb, 0, n_e, true, T + t.t_rng1, nb, nullptr, nullptr, R + r_b, R + r_bflag, st)) return rc;
-            if (int rc = pscan_ranges_launch<2>(wa, 0, n_e, true, T + t.t_rng2, nn, nullptr, nullptr, R + r_s, R + r_sflag, st)) return rc;
-            hipLaunchKernelGGL(ps::k_fold_codes, dim3((unsigned)((nn + ps::THREADS - 1) / ps::THREADS)), dim3(ps::THREADS), 0, st, T + t.t_first,
-                               (uint32_t)nn, (const uint8_t*)(R + r_bflag), (const uint8_t*)(R + r_sflag), (uint8_t*)(R + r_code),
-                               (uint8_t*)(R + r_odd));
-            const size_t ftotal = slots * 18;
-            hipLaunchKernelGGL(ps::k_fold_fill, dim3((unsigned)((ftotal + ps::THREADS - 1) / ps::THREADS)), dim3(ps::THREADS), 0, st, T + t.t_node,
-                               T + t.t_first, T + t.t_msg, ftotal, (const uint8_t*)(R + r_code), (const uint4*)(R + r_b), (const uint4*)(R + r_s),
-                               (const uint4*)(W + w.o_h), (uint4*)(R + r_g1), (uint4*)(R + r_g2));
+            const uint32_t* const T = (const uint32_t*)(R + r.w.o_tab);
+            HIP_TRY(hipMemcpyAsync(R + r.w.o_tab, t.tab.data(), t.tab.size() * 4, hipMemcpyHostToDevice, st));
+            if (int rc = pscan_ranges_launch<1>(wb, 0, n_e, true, T + t.t_rng1, r.nb, nullptr, nullptr, R + r.w.o_b, R + r.w.o_bflag, st)) return rc;
+            if (int rc = pscan_ranges_launch<2>(wa, 0, n_e, true, T + t.t_rng2, nn, nullptr, nullptr, R + r.w.o_s, R + r.w.o_sflag, st)) return rc;
+            hipLaunchKernelGGL(ps::k_fold_codes, dim3(r.g_codes), dim3(ps::THREADS), 0, st, T + t.t_first, (uint32_t)nn,
+                               (const uint8_t*)(R + r.w.o_bflag), (const uint8_t*)(R + r.w.o_sflag), (uint8_t*)(R + r.w.o_code),
+                               (uint8_t*)(R + r.w.o_odd));
+            hipLaunchKernelGGL(ps::k_fold_fill, dim3(r.g_fill), dim3(ps::THREADS), 0, st, T + t.t_node, T + t.t_first, T + t.t_msg, r.ftotal,
+                               (const uint8_t*)(R + r.w.o_code), (const uint4*)(R + r.w.o_b), (const uint4*)(R + r.w.o_s),
+                               (const uint4*)(W + w.o_h), (uint4*)(R + r.w.o_g1), (uint4*)(R + r.w.o_g2));
             HIP_TRY(hipGetLastError());
             for (size_t i = 0; i < nn;) {                                    // the nodes of one pair count: one multi-pairing batch
                 size_t j = i;
                 while (j < nn && t.order[j].cnt == t.order[i].cnt) j++;
                 const size_t s0 = t.tab[t.t_first + i];
-                if (int rc = blsgpu_pairing_multi_batch_dev(c, R + r_g1 + s0 * BLSGPU_G1_BYTES, R + r_g2 + s0 * BLSGPU_G2_BYTES, nullptr,
-                                                            t.order[i].cnt, j - i, R + r_e + i * BLSGPU_FQ12_BYTES, st))
+                if (int rc = blsgpu_pairing_multi_batch_dev(c, R + r.g1_at(s0), R + r.g2_at(s0), nullptr, t.order[i].cnt, j - i, R + r.e_at(i), st))
                     return rc;
                 i = j;
             }
-            hipLaunchKernelGGL(k_find_verdict, dim3((unsigned)((nn + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, T + t.t_off, (uint32_t)nn,
-                               (const uint4*)(R + r_e), (const uint8_t*)(R + r_odd), d_unit, L == 1 ? 1u : 0u, s.dense, (uint8_t*)(R + r_v),
-                               s.status);
+            hipLaunchKernelGGL(k_find_verdict, dim3(r.g_verdict), dim3(THREADS), 0, st, T + t.t_off, (uint32_t)nn, (const uint4*)(R + r.w.o_e),
+                               (const uint8_t*)(R + r.w.o_odd), d_unit, L == 1 ? 1u : 0u, s.dense, (uint8_t*)(R + r.w.o_v), s.status);
             HIP_TRY(hipGetLastError());
-            bis.pairs += slots;
-            d_verdict = R + r_v;
+            bis.pairs += r.slots;
+            d_verdict = R + r.w.o_v;
             return 0;
         });
     });

@@ -62,12 +62,12 @@ enum BufId {
     B_SMUL_WS,           // blsgpu_g2_mul_secret* / blsgpu_sign*: one slice of H(m) points (sign) and of tables 1P .. 8P (k_g2_smul)
     B_FRS_WS,            // blsgpu_sign_threshold*: the scalars lambda_i sk_i of a call and, with a message per session, one slice of H(m) copies
     B_HPK_WS,            // blsgpu_hash_pks* / blsgpu_aggregate_*_secure*: groups digests (32 bytes each), then groups x m exponents (32 bytes each)
-    B_SHR_WS,            // blsgpu_sig_shares_check*: what one slice of sessions keeps over its rounds -- a flag word, the subgroup flags, H(m), the scalars r and w, the key copies and the leaves A, B
-    B_SHR_ROUND,         // ... and what one round of it takes: the node table, the gathered leaves, the node sums, the pairs, the pairing results and the verdict bytes
+    B_SHR_WS,            // blsgpu_sig_shares_check*: what one slice of sessions keeps over its rounds -- a flag word, the subgroup flags, H(m), the scalars r and w, the key copies and the leaves A, B (every array, its writer and readers: find_plan.h, FIND_SHR_KEEP)
+    B_SHR_ROUND,         // ... and what one round of it takes: the node table, the gathered leaves, the node sums, the pairs, the pairing results and the verdict bytes (find_plan.h, FIND_SHR_ROUND)
     B_SEED_WS,           // blsgpu_keys_from_seeds*: one slice of the keys (32 bytes each) and of their affine public keys (96) where the caller does not ask for them
     B_SM64_WS,           // blsgpu_g1_mul_short* / blsgpu_g2_mul_short* and the leaves of blsgpu_verify_find*: the prepared points, their live flags and one launch's tables 0 .. 15 P (k_smul64)
-    B_FIND_WS,           // blsgpu_verify_find* / blsgpu_verify_find_folded* (which adds the leaves in the dense order and the run table): what one slice of items keeps over its rounds -- a flag word, n_e, the subgroup flags, H(h), the weights, the dense order and the leaves A, B
-    B_FIND_ROUND,        // ... and what one round of it takes: the node offsets, the gathered leaves, the node sums, the pairs, the pairing results and the verdict bytes
+    B_FIND_WS,           // blsgpu_verify_find* / blsgpu_verify_find_folded* (which adds the leaves in the dense order and the run table): what one slice of items keeps over its rounds -- a flag word, n_e, the subgroup flags, H(h), the weights, the dense order and the leaves A, B (find_plan.h, FIND_KEEP)
+    B_FIND_ROUND,        // ... and what one round of it takes: the node offsets, the gathered leaves, the node sums, the pairs, the pairing results and the verdict bytes (find_plan.h: FIND_PLAIN_HEAD and FIND_PLAIN_PART, or FIND_FOLD_ROUND)
     B_FIND_UNIT,         // ... and e(-G1, G2) with the pair it comes from, computed once per context (find_unit_ready)
     B_PSCAN_G1,          // blsgpu_g1_range_sums* and SB of blsgpu_verify_find_folded*: one slice of prepared points, their live and kind bytes, the chunk totals and counts, the prefix records and counts, the carry (blsgpu_pscan.hip)
     B_PSCAN_G2,          // ... the same for blsgpu_g2_range_sums* and SA

@@ -346,6 +346,21 @@ def test_verify_find_forgeries_across_slices(engine, capped, find_world, pos):
         assert got[2][1] == (len(sl), len(sl), sum(len({msg_idx[i] for i in r}) + 1 for r in sl)) == (5, 5, 12)
 
 
+@pytest.mark.parametrize("m", [2, 7])
+def test_folded_run_table_below_and_above_a_slice(engine, capped, fold_keys, m):
+    """the folded form's run table has min(slice, n_msgs) + 1 entries, of which a slice of k items reads min(k, n_msgs) + 1
+    (find::plan_find, csrc/find_plan.h): 12 items in slices of five over 2 messages (fewer than a slice) and over 7 (more), one
+    forgery in the last slice of two items"""
+    w = build(engine, fold_keys, 12, m)
+    assert len(set(w["msg"])) == m and (m < CAP) == (m == 2)
+    args, want = pack_items(w, {10: "wrong_key"})
+    weights = [random.Random(13 + m).getrandbits(64) or 1 for _ in range(12)]
+    got = find_calls(capped(CAP), args, weights)
+    assert [g[0] for g in got] == [want] * 4 and want[10] == 0
+    assert got[0][1] == got[1][1] and got[2][1] == got[3][1]
+    assert F.verify_find(engine, *args, weights)[0] == want == R.verify_find_folded(engine, *args, weights)[0]
+
+
 def test_verify_find_ineligible_slices(engine, capped, find_world, golden):
     eng = capped(CAP)
     sub = golden("subgroup.json")
