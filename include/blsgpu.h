@@ -954,6 +954,65 @@ int blsgpu_aggregate_priv_keys_secure_dev(blsgpu_ctx *ctx, const void *d_sks, co
                                           size_t k, size_t groups, void *d_out, void *d_out_pk_aff, void *d_out_pk_ser,
                                           void *stream);
 
+/* RAGGED secure aggregation: groups of ANY sizes in one call (csrc/blsgpu_hashpks.hip's *_ranges kernels on csrc/hash_pks.h; host
+ * plan csrc/secure_ranges_plan.h).  The three entries above take one k per call, so a caller with groups of many sizes --
+ * committees, colliding-message sets, signer subsets -- pays a call, a host assembly and a synchronisation per distinct size;
+ * these take them all at once.  Group g hashes the keys [pk_off[g], pk_off[g + 1]) of ONE list of n_keys serialised keys
+ * (pks_ser: n_keys x 48 bytes in the order to be hashed, 16-byte aligned) and owns the exponents [exp_off[g], exp_off[g + 1]) of
+ * one list: exponent i of group g is t_gi = SHA256(be32(i) || SHA256(the group's keys)) mod n (util.py:36-50), i counted
+ * from the group's own begin.  Either table holds groups + 1 uint32 offsets: the first is 0, they never step down, and the last
+ * is at most its list's count (keys or points past it belong to no group).  A group may be empty on either side: no keys
+ * hashes nothing (SHA256 of the empty string), no exponents gives none -- and, in the aggregates, infinity with flag 1.  The
+ * two tables are separate because BLS.aggregate_sigs hashes a different number of keys than it has signatures (bls.py:58-151), the
+ * reason the uniform call has k and k_pks and blsgpu_hash_pks' m is independent of k.
+ * pk_hash_in (may be NULL): groups x 32 bytes, the inner SHA-256 of every group computed by the caller; then the digest
+ * kernel is not launched and pks_ser / pk_off are not read (they may be NULL) -- the advice on few groups and very long groups
+ * above holds here as well, and a wavefront of k_hash_pks_digest_ranges runs as long as its longest group (the groups are
+ * taken in the caller's order).
+ * k_secr_check checks both tables on the device (the host-buffer forms have checked them on the host already) and writes the
+ * (begin, end) range table of the sums; the kernels behind it return on its flag, so a bad table is neither followed nor
+ * written for.  -EINVAL with a blsgpu_last_error text BEFORE ANYTHING IS WRITTEN to an output: a NULL context, a NULL required
+ * buffer with groups > 0, a bad offset table, n_keys or the number of exponents 2^31 or more, 2^30 groups or more.
+ * groups == 0 writes nothing and returns 0.  The host-buffer forms stage their groups in slices of at most 2^18 keys,
+ * exponents and groups (cut on group boundaries; a longer group is a slice of its own), each a call of its own.  The
+ * workspace counts in BLSGPU_WS_TOTAL.  All of this is PUBLIC data: not constant-time.
+ *
+ * blsgpu_hash_pks_ranges (util.py:36-50 per group): out_ts[32 j ..] for j in [exp_off[g], exp_off[g + 1]) = t_g,j-exp_off[g] --
+ * exp_off[groups] exponents in all, 32 bytes big-endian each, below n: the layout blsgpu_g?_msm_ranges take as scalars.
+ * out_pk_hash (may be NULL): groups x 32 bytes, the inner digests (computed or copied from pk_hash_in).  The _dev form takes
+ * n_exp, the exponents d_out_ts has room for (exp_off[groups] <= n_exp is checked), and synchronises `stream` ONCE to read
+ * the verdict on the tables. */
+int blsgpu_hash_pks_ranges(blsgpu_ctx *ctx, const uint8_t *pks_ser, size_t n_keys, const uint32_t *pk_off, const uint32_t *exp_off,
+                           size_t groups, const uint8_t *pk_hash_in, uint8_t *out_ts, uint8_t *out_pk_hash);
+int blsgpu_hash_pks_ranges_dev(blsgpu_ctx *ctx, const void *d_pks_ser, size_t n_keys, const void *d_pk_off, const void *d_exp_off,
+                               size_t n_exp, size_t groups, const void *d_pk_hash_in, void *d_out_ts, void *d_out_pk_hash,
+                               void *stream);
+/* BLS.aggregate_pub_keys(keys, secure=True) (bls.py:203-223) per group: out[g] = sum_i t_gi P_i over the group's own keys,
+ * exp_off = pk_off.  pts_aff: n_keys x 96 bytes, the affine points of the keys of pks_ser in the same order (the reference
+ * sorts a group's keys first: the order is the caller's).  pk_off is required with pk_hash_in too: it counts the exponents.
+ * The exponents and the range table go to the workspace, then the sums are blsgpu_g1_msm_ranges_dev's: out_aff (groups x 96,
+ * (0,0) for infinity) and out_flag (groups bytes, required: 0 finite, 1 infinity, 2 the group holds a point that is neither
+ * (0,0) nor on the curve and its output is (0,0); such a point enters as infinity, the other groups are not disturbed).
+ * Equal-length groups give the bytes of blsgpu_aggregate_pub_keys_secure, out_inf == (flag == 1).  The _dev form makes no
+ * synchronisation beyond the ONE of blsgpu_g1_msm_ranges_dev, whose check also refuses a bad offset table. */
+int blsgpu_aggregate_pub_keys_secure_ranges(blsgpu_ctx *ctx, const uint8_t *pts_aff, const uint8_t *pks_ser, size_t n_keys,
+                                            const uint32_t *pk_off, size_t groups, const uint8_t *pk_hash_in, uint8_t *out_aff,
+                                            uint8_t *out_flag);
+int blsgpu_aggregate_pub_keys_secure_ranges_dev(blsgpu_ctx *ctx, const void *d_pts_aff, const void *d_pks_ser, size_t n_keys,
+                                                const void *d_pk_off, size_t groups, const void *d_pk_hash_in, void *d_out_aff,
+                                                void *d_out_flag, void *stream);
+/* BLS.aggregate_sigs_secure (bls.py:28-56; the colliding part of BLS.aggregate_sigs, bls.py:58-151) per group: out[g] =
+ * sum_i t_gi S_i over the signatures [sig_off[g], sig_off[g + 1]) of sigs_aff (n_sigs x 192 bytes affine, in the order the
+ * exponents multiply them: the reference sorts them by (message hash, key, signature)), the exponents counted by sig_off and
+ * hashed over the keys [pk_off[g], pk_off[g + 1]).  The sums are blsgpu_g2_msm_ranges_dev's: out_aff (groups x 192), out_flag
+ * as above.  Equal-length groups give the bytes of blsgpu_aggregate_sigs_secure. */
+int blsgpu_aggregate_sigs_secure_ranges(blsgpu_ctx *ctx, const uint8_t *sigs_aff, size_t n_sigs, const uint32_t *sig_off,
+                                        const uint8_t *pks_ser, size_t n_keys, const uint32_t *pk_off, size_t groups,
+                                        const uint8_t *pk_hash_in, uint8_t *out_aff, uint8_t *out_flag);
+int blsgpu_aggregate_sigs_secure_ranges_dev(blsgpu_ctx *ctx, const void *d_sigs_aff, size_t n_sigs, const void *d_sig_off,
+                                            const void *d_pks_ser, size_t n_keys, const void *d_pk_off, size_t groups,
+                                            const void *d_pk_hash_in, void *d_out_aff, void *d_out_flag, void *stream);
+
 /* Measurement aid (bench.py): when enabled, HIP events are recorded on the
  * launch stream around every kernel this context launches (up to 1024 launches
  * between reads).  blsgpu_timing_read waits for them and returns, per launch,
@@ -969,7 +1028,8 @@ int blsgpu_aggregate_priv_keys_secure_dev(blsgpu_ctx *ctx, const void *d_sks, co
  * blsgpu_sign_threshold_dev, blsgpu_fr_sum_secret_dev, blsgpu_aggregate_priv_keys_secure_dev; the G1 / G2 halves of those
  * calls keep their kinds 9 and 8),
  * 11 = k_hash_pks_digest and 12 = k_hash_pks_exp (one record each per blsgpu_hash_pks_dev / blsgpu_aggregate_*_secure_dev
- * call; no record of kind 11 when the caller hands in the digests),
+ * call; no record of kind 11 when the caller hands in the digests; the *_ranges forms record their digest and exponent kernels
+ * under the same kinds),
  * 13 = k_seed_keys (one record per slice of 2^20 seeds of blsgpu_keys_from_seeds_dev / per staged slice of the host form; the
  * multiplication behind it keeps kind 9, the copy into the parent records has no record).
  * Reading resets the ring. */

@@ -152,6 +152,12 @@ PROTOTYPES = {
     "blsgpu_aggregate_sigs_secure_dev": (vp, vp, sz, vp, sz, vp, sz, vp, vp, vp),
     "blsgpu_aggregate_priv_keys_secure": (vp, cp, cp, cp, sz, sz, vp, vp, vp),
     "blsgpu_aggregate_priv_keys_secure_dev": (vp, vp, vp, vp, sz, sz, vp, vp, vp, vp),
+    "blsgpu_hash_pks_ranges": (vp, cp, sz, vp, vp, sz, cp, vp, vp),
+    "blsgpu_hash_pks_ranges_dev": (vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp),
+    "blsgpu_aggregate_pub_keys_secure_ranges": (vp, cp, cp, sz, vp, sz, cp, vp, vp),
+    "blsgpu_aggregate_pub_keys_secure_ranges_dev": (vp, vp, vp, sz, vp, sz, vp, vp, vp, vp),
+    "blsgpu_aggregate_sigs_secure_ranges": (vp, cp, sz, vp, cp, sz, vp, sz, cp, vp, vp),
+    "blsgpu_aggregate_sigs_secure_ranges_dev": (vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp),
     "blsgpu_timing_enable": (vp, ci),
     "blsgpu_timing_read": (vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci), sz, ctypes.POINTER(sz)),
 }

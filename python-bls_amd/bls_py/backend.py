@@ -112,6 +112,11 @@ def use(provider):
     verify_aggregates(sigs, msg_hashes, keys, exps|None, grp_off, grp_msg, agg_off, gt=False) -> (m status bytes: 1 valid, 0
     not, 2 not decided; m x 576 bytes|None) -- BLS.verify of m aggregates, group g summing the keys [grp_off[g], grp_off[g + 1])
     for message grp_msg[g], aggregate j owning the groups [agg_off[j], agg_off[j + 1]).
+    Optional extensions (without them the ragged=True forms of util.hash_pks_batch, BLS.aggregate_pub_keys_batch and
+    BLS.aggregate_sigs_secure_batch raise; the defaults do not use them): hash_pks_ranges(pks_ser, pk_off, exp_off) -> exponent
+    bytes, aggregate_pub_keys_secure_ranges(pts_aff, pks_ser, pk_off) -> (affine bytes, flag bytes: 0 finite, 1 infinity, 2 a
+    point off the curve in the group), aggregate_sigs_secure_ranges(sigs_aff, sig_off, pks_ser, pk_off) -> likewise -- group g
+    hashing the keys [pk_off[g], pk_off[g + 1]) of one list and owning the exponents (signatures) [exp_off[g], exp_off[g + 1]).
     Extensions are looked up by extension(name), not by hasattr: a stand-in offers one as an attribute of that name, the
     HipProvider's come from EXTENSIONS.  Optional (without it PrivateKey.from_seed_batch and
     ExtendedPrivateKey.from_seed_batch run the per-seed host calls): keys_from_seeds(seeds, seed_len, n, hd) -> (key bytes,
@@ -139,11 +144,15 @@ SIGDIV_EXTENSIONS = {"sig_divide": "_native_sigdiv"}
 PAIR_RANGE_EXTENSIONS = {"pairing_multi_ranges": "_native_pairranges"}
 # ... and the verification of many aggregates of any shapes in one device call (BLS.verify_batch(fused=True)).
 VERIFY_AGG_EXTENSIONS = {"verify_aggregates": "_native_veragg"}
+# ... and secure aggregation for groups of any sizes in one device call (the ragged=True forms of util.hash_pks_batch,
+# BLS.aggregate_pub_keys_batch and BLS.aggregate_sigs_secure_batch).
+SECURE_RANGE_EXTENSIONS = {"hash_pks_ranges": "_native_secranges", "aggregate_pub_keys_secure_ranges": "_native_secranges",
+                           "aggregate_sigs_secure_ranges": "_native_secranges"}
 
 
 def extension(name):
     """The installed provider's extension `name`: the provider's own attribute of that name if it has one (stand-ins), for
-    a HipProvider the function of EXTENSIONS (or FIND_EXTENSIONS, RANGE_EXTENSIONS, MSM_RANGE_EXTENSIONS, H2G1_EXTENSIONS, SIGDIV_EXTENSIONS, PAIR_RANGE_EXTENSIONS, VERIFY_AGG_EXTENSIONS) bound to its
+    a HipProvider the function of EXTENSIONS (or FIND_EXTENSIONS, RANGE_EXTENSIONS, MSM_RANGE_EXTENSIONS, H2G1_EXTENSIONS, SIGDIV_EXTENSIONS, PAIR_RANGE_EXTENSIONS, VERIFY_AGG_EXTENSIONS, SECURE_RANGE_EXTENSIONS) bound to its
     engine, otherwise None."""
     prov = get()
     fn = getattr(prov, name, None)
@@ -151,7 +160,7 @@ def extension(name):
         return fn
     where = (EXTENSIONS.get(name) or FIND_EXTENSIONS.get(name) or RANGE_EXTENSIONS.get(name) or MSM_RANGE_EXTENSIONS.get(name)
              or H2G1_EXTENSIONS.get(name) or SIGDIV_EXTENSIONS.get(name) or PAIR_RANGE_EXTENSIONS.get(name)
-             or VERIFY_AGG_EXTENSIONS.get(name))
+             or VERIFY_AGG_EXTENSIONS.get(name) or SECURE_RANGE_EXTENSIONS.get(name))
     if isinstance(prov, HipProvider) and where:
         import functools
         import importlib

@@ -492,14 +492,32 @@ class BLS:
         return PrivateKey.from_bytes(total.to_bytes(32, "big"))
 
     @staticmethod
-    def aggregate_pub_keys_batch(groups, secure):
+    def aggregate_pub_keys_batch(groups, secure, ragged=False):
         """[BLS.aggregate_pub_keys(list(g), secure) for g in groups] without sorting the caller's lists: one device call per
         distinct group length.  secure=True: blsgpu_aggregate_pub_keys_secure -- the hash_pks exponents of every group
         (both SHA-256 steps and the reduction mod n) and the G1 sums behind them in one call, the exponents never on the
-        host; a provider without the entry runs the loop above.  secure=False: one grouped plain sum (g1_msm)."""
+        host; a provider without the entry runs the loop above.  secure=False: one grouped plain sum (g1_msm).
+        ragged=True (with secure=True; without it the keyword changes nothing): ALL groups in ONE call of the provider's
+        aggregate_pub_keys_secure_ranges extension (blsgpu_aggregate_pub_keys_secure_ranges) whatever their lengths;
+        NotImplementedError when the provider has none."""
         groups = [sorted(g) for g in groups]                 # copies: the reference sorts in place (bls.py:210)
         if any(not g for g in groups):
             raise Exception("Invalid number of keys")
+        if ragged and secure:
+            fn = backend.extension("aggregate_pub_keys_secure_ranges")
+            if fn is None:
+                raise NotImplementedError("the provider has no aggregate_pub_keys_secure_ranges extension")
+            if not groups:
+                return []
+            pk_off = [0]
+            for g in groups:
+                pk_off.append(pk_off[-1] + len(g))
+            res, flag = fn(b"".join(_jac_g1_bytes(pk.value) for g in groups for pk in g), b"".join(pk.serialize() for g in groups for pk in g),
+                           pk_off)
+            if 2 in bytes(flag):
+                raise ValueError("a public key that is not on the curve")
+            return [PublicKey.from_g1(JacobianPoint._from(H.F1, None if flag[q] else H.aff_to_jac(H.F1, H.g1_from_abi(res[96 * q:96 * (q + 1)]))))
+                    for q in range(len(groups))]
         prov = backend.get()
         fn = getattr(prov, "aggregate_pub_keys_secure", None) if secure else prov.g1_msm
         if fn is None:
@@ -519,15 +537,35 @@ class BLS:
         return out
 
     @staticmethod
-    def aggregate_sigs_secure_batch(sig_groups, pk_groups, mh_groups):
+    def aggregate_sigs_secure_batch(sig_groups, pk_groups, mh_groups, ragged=False):
         """[BLS.aggregate_sigs_secure(s, p, m) for s, p, m in zip(sig_groups, pk_groups, mh_groups)]: one
         blsgpu_aggregate_sigs_secure call per distinct group length.  As in bls.py:39-45 the signatures are ordered by
         (message hash, public key, signature) and the exponents hashed over the public keys in the CALLER's order.  A
-        provider without the entry runs that loop."""
+        provider without the entry runs that loop.
+        ragged=True: ALL groups, empty ones included, in ONE call of the provider's aggregate_sigs_secure_ranges extension
+        (blsgpu_aggregate_sigs_secure_ranges) whatever their lengths; NotImplementedError when the provider has none."""
         trip = [(list(s), list(p), list(m)) for s, p, m in zip(sig_groups, pk_groups, mh_groups)]
         for s, p, m in trip:
             if not (len(s) == len(p) == len(m)):
                 raise Exception("Invalid number of keys")
+        if ragged:
+            fn = backend.extension("aggregate_sigs_secure_ranges")
+            if fn is None:
+                raise NotImplementedError("the provider has no aggregate_sigs_secure_ranges extension")
+            if not trip:
+                return []
+            sigs, sers, off = bytearray(), bytearray(), [0]
+            for s, p, m in trip:
+                for _, _, sig in sorted(zip(m, p, s)):
+                    sigs += H.g2_affine_bytes(sig.value.to_affine()._aff())
+                for pk in p:
+                    sers += pk.serialize()
+                off.append(off[-1] + len(s))
+            res, flag = fn(bytes(sigs), off, bytes(sers), off)
+            if 2 in bytes(flag):
+                raise ValueError("a signature that is not on the curve")
+            return [Signature.from_g2(JacobianPoint._from(H.F2, None if flag[q] else H.aff_to_jac(H.F2, H.g2_from_abi(res[192 * q:192 * (q + 1)]))))
+                    for q in range(len(trip))]
         fn = getattr(backend.get(), "aggregate_sigs_secure", None)
         if fn is None:
             return [BLS.aggregate_sigs_secure(s, p, m) for s, p, m in trip]

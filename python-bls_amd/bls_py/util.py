@@ -45,12 +45,26 @@ def hash_pks(num_outputs, public_keys):
     return [int.from_bytes(hash256(i.to_bytes(4, "big") + digest), "big") % n for i in range(num_outputs)]
 
 
-def hash_pks_batch(num_outputs, key_groups):
+def hash_pks_batch(num_outputs, key_groups, ragged=False):
     """[hash_pks(num_outputs, g) for g in key_groups] with ONE device call per distinct group length (blsgpu_hash_pks: both
     SHA-256 steps and the reduction mod n on the GPU) when the provider has hash_pks; otherwise that loop.  Empty groups and
-    num_outputs = 0 never reach the device."""
+    num_outputs = 0 never reach the device.
+    ragged=True: the same list from ONE call of the provider's hash_pks_ranges extension (blsgpu_hash_pks_ranges) whatever
+    the lengths, empty groups included; NotImplementedError when the provider has none."""
     from . import backend
     key_groups = [list(g) for g in key_groups]
+    if ragged:
+        fn = backend.extension("hash_pks_ranges")
+        if fn is None:
+            raise NotImplementedError("the provider has no hash_pks_ranges extension")
+        if not key_groups or num_outputs <= 0:
+            return [[] for _ in key_groups]
+        pk_off = [0]
+        for g in key_groups:
+            pk_off.append(pk_off[-1] + len(g))
+        ts = fn(b"".join(pk.serialize() for g in key_groups for pk in g), pk_off, [num_outputs * j for j in range(len(key_groups) + 1)])
+        return [[int.from_bytes(ts[32 * (j * num_outputs + i):32 * (j * num_outputs + i + 1)], "big") for i in range(num_outputs)]
+                for j in range(len(key_groups))]
     fn = getattr(backend.get(), "hash_pks", None) if key_groups and num_outputs > 0 else None
     if fn is None:
         return [hash_pks(num_outputs, g) for g in key_groups]

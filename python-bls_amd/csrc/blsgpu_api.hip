@@ -52,6 +52,7 @@
 #include "pairing_plan.h"
 #include "pairing_ranges_plan.h"
 #include "ragged_plan.h"
+#include "secure_ranges_plan.h"
 #include "verify_agg_plan.h"
 #include "blsgpu_ctx.h"
 
@@ -1657,6 +1658,153 @@ int aggregate_priv_args(const blsgpu_ctx* c, size_t k, size_t groups, bool null_
     if (c && k > blsgpu::lagr::MAX_K) return fail(-EINVAL, "k must be 1 .. BLSGPU_LAGRANGE_MAX_K");
     if (int rc = hash_pks_args(c, k, k, groups, null_buffer)) return rc;
     if (k * groups > 0xFFFFFFF0ull) return fail(-EINVAL, "batch too large");
+    return 0;
+}
+
+// ------------------------------------------------------------ ragged secure aggregation (blsgpu_hashpks.hip, secure_ranges_plan.h) --
+static_assert(secure_ranges::CHECK_THREADS == blsgpu::hashpks::CHECK_THREADS && secure_ranges::DIGEST_THREADS == blsgpu::hashpks::DIGEST_THREADS &&
+                  secure_ranges::EXP_THREADS == blsgpu::hashpks::EXP_THREADS,
+              "secure_ranges_plan.h: the grids differ from the kernels of blsgpu_hashpks.hip");
+// the argument checks of blsgpu_hash_pks_ranges* and blsgpu_aggregate_*_secure_ranges* (before anything is written); 1: nothing to do
+int secr_args(const blsgpu_ctx* c, size_t n_keys, size_t n_exp, size_t groups, bool null_buffer) {
+    if (!c) return fail(-EINVAL, "ctx is NULL");
+    if (groups == 0) return 1;
+    if (null_buffer) return fail(-EINVAL, "NULL argument");
+    if (secure_ranges::too_large(n_keys, n_exp, groups)) return fail(-EINVAL, "batch too large");
+    return 0;
+}
+// the host tables of a host-buffer form, before anything is staged (pk_off NULL: the caller hands in the digests)
+int secr_validate(const uint32_t* pk_off, size_t n_keys, const uint32_t* exp_off, size_t n_exp, size_t groups) {
+    namespace sr = secure_ranges;
+    if (pk_off)
+        if (const sr::Verdict v = sr::validate(pk_off, groups, n_keys)) return fail(-EINVAL, std::string("pk_off: ") + sr::verdict_text(v));
+    if (const sr::Verdict v = sr::validate(exp_off, groups, n_exp)) return fail(-EINVAL, std::string("exponent offsets: ") + sr::verdict_text(v));
+    return 0;
+}
+constexpr const char* SECR_BAD_TABLE = "offsets decrease, do not begin at 0 or end past their buffer";
+// Enqueues the check of both tables (k_secr_check, which also writes the pair table of the sums when W.pairs is wanted), the
+// digests of the groups' own key ranges (k_hash_pks_digest_ranges, timing kind 11; skipped when the caller has them) and the
+// exponents (k_hash_pks_exp_ranges, kind 12) on `st` (caller: StreamGuard, arguments checked by secr_args).  Both kernels
+// return on the check's flag, W.head word 0.  d_digest_ws / d_ts: where the digests and the exponents go.
+int secr_launch(blsgpu_ctx* c, const void* d_pks_ser, size_t n_keys, const void* d_pk_off, const void* d_exp_off, size_t n_exp, size_t groups,
+                const void* d_pk_hash_in, uint32_t* d_flag, void* d_digest_ws, void* d_ts, uint32_t* d_pairs, hipStream_t st) {
+    using namespace blsgpu::hashpks;
+    const secure_ranges::Grids g = secure_ranges::grids(groups, n_exp);
+    HIP_TRY(hipMemsetAsync(d_flag, 0, 16, st));
+    hipLaunchKernelGGL(k_secr_check, dim3(g.check), dim3(CHECK_THREADS), 0, st, d_pk_hash_in ? nullptr : (const uint32_t*)d_pk_off, (uint32_t)n_keys,
+                       (const uint32_t*)d_exp_off, (uint32_t)n_exp, (uint32_t)groups, d_flag, d_pairs);
+    HIP_TRY(hipGetLastError());
+    const void* d_digest = d_pk_hash_in;
+    if (!d_digest) {
+        KernelTimer kt(c, st, 11);
+        hipLaunchKernelGGL(k_hash_pks_digest_ranges, dim3(g.digest), dim3(DIGEST_THREADS), 0, st, (const uint32_t*)d_pks_ser, (const uint32_t*)d_pk_off,
+                           (uint32_t)groups, (const uint32_t*)d_flag, (uint32_t*)d_digest_ws);
+        HIP_TRY(hipGetLastError());
+        d_digest = d_digest_ws;
+    }
+    if (n_exp) {
+        KernelTimer kt(c, st, 12);
+        hipLaunchKernelGGL(k_hash_pks_exp_ranges, dim3(g.exp), dim3(EXP_THREADS), 0, st, (const uint32_t*)d_digest, (const uint32_t*)d_exp_off,
+                           (uint32_t)groups, (uint32_t)n_exp, (const uint32_t*)d_flag, (uint32_t*)d_ts);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+// blsgpu_hash_pks_ranges_dev: the exponents into the caller's buffer, the digests into the caller's if it asks for them.  This
+// call has no sums behind it whose synchronisation it could share: it reads the check's flag itself -- ONE synchronisation,
+// before anything is written to an output (the kernels are enqueued first and return on the flag; the copy of the caller's
+// digests waits for the verdict).
+int hash_pks_ranges_dev(blsgpu_ctx* c, const void* d_pks_ser, size_t n_keys, const void* d_pk_off, const void* d_exp_off, size_t n_exp, size_t groups,
+                        const void* d_pk_hash_in, void* d_out_ts, void* d_out_pk_hash, hipStream_t st) {
+    StreamGuard sg(c, st);
+    const secure_ranges::Workspace w = secure_ranges::workspace(groups, n_exp, !d_pk_hash_in && !d_out_pk_hash, false, false);
+    if (int rc = c->grow(B_HPK_WS, w.total)) return rc;
+    char* const W = c->at<char>(B_HPK_WS);
+    uint32_t* const d_flag = (uint32_t*)(W + w.head);
+    if (int rc = secr_launch(c, d_pks_ser, n_keys, d_pk_off, d_exp_off, n_exp, groups, d_pk_hash_in, d_flag, d_out_pk_hash ? d_out_pk_hash : W + w.digests,
+                             d_out_ts, nullptr, st))
+        return rc;
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, d_flag, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (bad) return fail(-EINVAL, SECR_BAD_TABLE);
+    if (d_pk_hash_in && d_out_pk_hash && d_pk_hash_in != d_out_pk_hash)
+        HIP_TRY(hipMemcpyAsync(d_out_pk_hash, d_pk_hash_in, groups * 32, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+// The exponents of all groups into the workspace, then the sums of msm_ranges_dev<DEG> over the n_exp points with them as its
+// device scalars and the pair table k_secr_check wrote as its ranges.  No synchronisation of its own: a bad table poisons
+// the pair table, so msm_ranges_dev's one read-back refuses the call before anything is written to the outputs; only then --
+// on the failure path -- is the flag read, to tell whose refusal it was.
+template <int DEG>
+int aggregate_secure_ranges_dev(blsgpu_ctx* c, const void* d_pts, size_t n_exp, const void* d_exp_off, const void* d_pks_ser, size_t n_keys,
+                                const void* d_pk_off, size_t groups, const void* d_pk_hash_in, void* d_out, void* d_flag_out, hipStream_t st) {
+    const secure_ranges::Workspace w = secure_ranges::workspace(groups, n_exp, !d_pk_hash_in, true, true);
+    char* W;
+    {
+        StreamGuard sg(c, st);
+        if (int rc = c->grow(B_HPK_WS, w.total)) return rc;
+        W = c->at<char>(B_HPK_WS);
+        if (int rc = secr_launch(c, d_pks_ser, n_keys, d_pk_off, d_exp_off, n_exp, groups, d_pk_hash_in, (uint32_t*)(W + w.head), W + w.digests, W + w.exps,
+                                 (uint32_t*)(W + w.pairs), st))
+            return rc;
+    }
+    const int rc = msm_ranges_dev<DEG>(c, d_pts, W + w.exps, n_exp, W + w.pairs, groups, d_out, d_flag_out, st);
+    if (rc == -EINVAL) {
+        const std::string theirs = g_err;
+        uint32_t bad = 0;
+        HIP_TRY(hipMemcpyAsync(&bad, W + w.head, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return fail(-EINVAL, bad ? SECR_BAD_TABLE : theirs);
+    }
+    return rc;
+}
+// The host-buffer forms: the tables are validated on the host, the groups cut into slices (secure_ranges::cut, the test hook
+// BLSGPU_TEST_SLICE_CAP shortening them) and every slice staged, run as a call of its own on tables that begin at 0, and
+// read back.  DEG 0: blsgpu_hash_pks_ranges (out: the exponents; out2: the digests, may be NULL); DEG 1 / 2: the aggregates
+// (pts: the n_exp points; out: the sums; out2: the flags).
+template <int DEG>
+int secure_ranges_host(blsgpu_ctx* c, const uint8_t* pts, size_t n_exp, const uint32_t* exp_off, const uint8_t* pks_ser, size_t n_keys,
+                       const uint32_t* pk_off, size_t groups, const uint8_t* pk_hash_in, uint8_t* out, uint8_t* out2) {
+    namespace sr = secure_ranges;
+    if (pk_hash_in) pk_off = nullptr, pks_ser = nullptr;     // (with the digests given the keys are not read: they stay on the host)
+    if (int rc = secr_validate(pk_off, n_keys, exp_off, n_exp, groups)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<sr::Slice> slices;
+    sr::cut(pk_off, exp_off, groups, sr::slice_cap(*c), slices);
+    const sr::Extent e = sr::extent(pk_off, exp_off, slices);
+    constexpr size_t PT = DEG ? 96 * DEG : 0, OUT = DEG ? 96 * DEG : 0;
+    Staging s(c);
+    const int dpts = s.scratch(e.exps * PT), dpk = s.scratch(e.keys * 48), dko = s.scratch(pk_off ? (e.groups + 1) * 4 : 0),
+              deo = s.scratch((e.groups + 1) * 4), dh = s.scratch(pk_hash_in ? e.groups * 32 : 0),
+              dout = s.scratch(DEG ? e.groups * OUT : e.exps * 32), dout2 = s.scratch(DEG ? e.groups : (out2 ? e.groups * 32 : 0));
+    if (int rc = s.alloc()) return rc;
+    std::vector<uint32_t> ko, eo;
+    for (const sr::Slice& sl : slices) {
+        const size_t m = sl.hi - sl.lo, e0 = exp_off[sl.lo], ne = exp_off[sl.hi] - e0, k0 = pk_off ? pk_off[sl.lo] : 0, nk = pk_off ? pk_off[sl.hi] - k0 : 0;
+        sr::rebase(exp_off, sl, eo);
+        HIP_TRY(hipMemcpyAsync(s.at(deo), eo.data(), (m + 1) * 4, hipMemcpyHostToDevice, 0));
+        if (pk_off) {
+            sr::rebase(pk_off, sl, ko);
+            HIP_TRY(hipMemcpyAsync(s.at(dko), ko.data(), (m + 1) * 4, hipMemcpyHostToDevice, 0));
+            if (nk) HIP_TRY(hipMemcpyAsync(s.at(dpk), pks_ser + k0 * 48, nk * 48, hipMemcpyHostToDevice, 0));
+        }
+        if (pk_hash_in) HIP_TRY(hipMemcpyAsync(s.at(dh), pk_hash_in + sl.lo * 32, m * 32, hipMemcpyHostToDevice, 0));
+        if (DEG && ne) HIP_TRY(hipMemcpyAsync(s.at(dpts), pts + e0 * PT, ne * PT, hipMemcpyHostToDevice, 0));
+        const void* d_ko = pk_off ? s.at(dko) : nullptr;
+        const void* d_pk = pk_off ? s.at(dpk) : nullptr;
+        const void* d_h = pk_hash_in ? s.at(dh) : nullptr;
+        if constexpr (DEG == 0) {
+            if (int rc = hash_pks_ranges_dev(c, d_pk, nk, d_ko, s.at(deo), ne, m, d_h, s.at(dout), out2 ? s.at(dout2) : nullptr, nullptr)) return rc;
+            if (ne) HIP_TRY(hipMemcpy(out + e0 * 32, s.at(dout), ne * 32, hipMemcpyDeviceToHost));
+            if (out2) HIP_TRY(hipMemcpy(out2 + sl.lo * 32, s.at(dout2), m * 32, hipMemcpyDeviceToHost));
+        } else {
+            if (int rc = aggregate_secure_ranges_dev<DEG>(c, s.at(dpts), ne, s.at(deo), d_pk, nk, d_ko, m, d_h, s.at(dout), s.at(dout2), nullptr))
+                return rc;
+            HIP_TRY(hipMemcpy(out + sl.lo * OUT, s.at(dout), m * OUT, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(out2 + sl.lo, s.at(dout2), m, hipMemcpyDeviceToHost));
+        }
+    }
     return 0;
 }
 
@@ -3757,6 +3905,60 @@ BLSGPU_EXPORT int blsgpu_aggregate_priv_keys_secure(blsgpu_ctx* c, const uint8_t
     if (int rc = aggregate_priv_keys_secure_dev(c, s.at(dsk), s.opt(dpk), s.opt(dh), k, groups, s.at(dout), s.opt(daff), s.opt(dser), nullptr))
         return rc;
     return s.down();
+}
+
+// ------------------------------------------------------------ ragged secure aggregation: groups of any sizes in one call --
+BLSGPU_EXPORT int blsgpu_hash_pks_ranges_dev(blsgpu_ctx* c, const void* d_pks_ser, size_t n_keys, const void* d_pk_off, const void* d_exp_off,
+                                             size_t n_exp, size_t groups, const void* d_pk_hash_in, void* d_out_ts, void* d_out_pk_hash, void* stream) {
+    if (int rc = secr_args(c, d_pk_hash_in ? 0 : n_keys, n_exp, groups, (!d_pk_hash_in && (!d_pks_ser || !d_pk_off)) || !d_exp_off || !d_out_ts))
+        return rc < 0 ? rc : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return hash_pks_ranges_dev(c, d_pks_ser, n_keys, d_pk_off, d_exp_off, n_exp, groups, d_pk_hash_in, d_out_ts, d_out_pk_hash, (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_hash_pks_ranges(blsgpu_ctx* c, const uint8_t* pks_ser, size_t n_keys, const uint32_t* pk_off, const uint32_t* exp_off,
+                                         size_t groups, const uint8_t* pk_hash_in, uint8_t* out_ts, uint8_t* out_pk_hash) {
+    const bool null_buffer = (!pk_hash_in && (!pks_ser || !pk_off)) || !exp_off || !out_ts;
+    const size_t n_exp = groups && c && !null_buffer ? exp_off[groups] : 0;
+    if (int rc = secr_args(c, pk_hash_in ? 0 : n_keys, n_exp, groups, null_buffer)) return rc < 0 ? rc : 0;
+    return secure_ranges_host<0>(c, nullptr, n_exp, exp_off, pks_ser, n_keys, pk_off, groups, pk_hash_in, out_ts, out_pk_hash);
+}
+// (the sums' own limits on top of secr_args': msm_ranges_args)
+BLSGPU_EXPORT int blsgpu_aggregate_pub_keys_secure_ranges_dev(blsgpu_ctx* c, const void* d_pts_aff, const void* d_pks_ser, size_t n_keys,
+                                                              const void* d_pk_off, size_t groups, const void* d_pk_hash_in, void* d_out_aff,
+                                                              void* d_out_flag, void* stream) {
+    if (int rc = secr_args(c, n_keys, n_keys, groups, !d_pts_aff || !d_pk_off || (!d_pks_ser && !d_pk_hash_in) || !d_out_aff || !d_out_flag))
+        return rc < 0 ? rc : 0;
+    if (ragged::too_large(MSM_CONSTS, n_keys, groups)) return fail(-EINVAL, "batch too large");
+    HIP_TRY(hipSetDevice(c->device));
+    return aggregate_secure_ranges_dev<1>(c, d_pts_aff, n_keys, d_pk_off, d_pks_ser, n_keys, d_pk_off, groups, d_pk_hash_in, d_out_aff, d_out_flag,
+                                          (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_aggregate_pub_keys_secure_ranges(blsgpu_ctx* c, const uint8_t* pts_aff, const uint8_t* pks_ser, size_t n_keys,
+                                                          const uint32_t* pk_off, size_t groups, const uint8_t* pk_hash_in, uint8_t* out_aff,
+                                                          uint8_t* out_flag) {
+    if (int rc = secr_args(c, n_keys, n_keys, groups, !pts_aff || !pk_off || (!pks_ser && !pk_hash_in) || !out_aff || !out_flag)) return rc < 0 ? rc : 0;
+    if (ragged::too_large(MSM_CONSTS, n_keys, groups)) return fail(-EINVAL, "batch too large");
+    return secure_ranges_host<1>(c, pts_aff, n_keys, pk_off, pks_ser, n_keys, pk_off, groups, pk_hash_in, out_aff, out_flag);
+}
+BLSGPU_EXPORT int blsgpu_aggregate_sigs_secure_ranges_dev(blsgpu_ctx* c, const void* d_sigs_aff, size_t n_sigs, const void* d_sig_off,
+                                                          const void* d_pks_ser, size_t n_keys, const void* d_pk_off, size_t groups,
+                                                          const void* d_pk_hash_in, void* d_out_aff, void* d_out_flag, void* stream) {
+    if (int rc = secr_args(c, d_pk_hash_in ? 0 : n_keys, n_sigs, groups,
+                           !d_sigs_aff || !d_sig_off || (!d_pk_hash_in && (!d_pks_ser || !d_pk_off)) || !d_out_aff || !d_out_flag))
+        return rc < 0 ? rc : 0;
+    if (ragged::too_large(MSM_CONSTS, n_sigs, groups)) return fail(-EINVAL, "batch too large");
+    HIP_TRY(hipSetDevice(c->device));
+    return aggregate_secure_ranges_dev<2>(c, d_sigs_aff, n_sigs, d_sig_off, d_pks_ser, n_keys, d_pk_off, groups, d_pk_hash_in, d_out_aff, d_out_flag,
+                                          (hipStream_t)stream);
+}
+BLSGPU_EXPORT int blsgpu_aggregate_sigs_secure_ranges(blsgpu_ctx* c, const uint8_t* sigs_aff, size_t n_sigs, const uint32_t* sig_off,
+                                                      const uint8_t* pks_ser, size_t n_keys, const uint32_t* pk_off, size_t groups,
+                                                      const uint8_t* pk_hash_in, uint8_t* out_aff, uint8_t* out_flag) {
+    if (int rc = secr_args(c, pk_hash_in ? 0 : n_keys, n_sigs, groups,
+                           !sigs_aff || !sig_off || (!pk_hash_in && (!pks_ser || !pk_off)) || !out_aff || !out_flag))
+        return rc < 0 ? rc : 0;
+    if (ragged::too_large(MSM_CONSTS, n_sigs, groups)) return fail(-EINVAL, "batch too large");
+    return secure_ranges_host<2>(c, sigs_aff, n_sigs, sig_off, pks_ser, n_keys, pk_off, groups, pk_hash_in, out_aff, out_flag);
 }
 
 #ifdef BLSGPU_STAMPS

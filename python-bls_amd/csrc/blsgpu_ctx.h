@@ -61,7 +61,7 @@ enum BufId {
     B_HDP_WS,            // blsgpu_hd_paths*: a flag word and one slice of per-path state (chain code, key / i_left, two affine keys)
     B_SMUL_WS,           // blsgpu_g2_mul_secret* / blsgpu_sign*: one slice of H(m) points (sign) and of tables 1P .. 8P (k_g2_smul)
     B_FRS_WS,            // blsgpu_sign_threshold*: the scalars lambda_i sk_i of a call and, with a message per session, one slice of H(m) copies
-    B_HPK_WS,            // blsgpu_hash_pks* / blsgpu_aggregate_*_secure*: groups digests (32 bytes each), then groups x m exponents (32 bytes each)
+    B_HPK_WS,            // blsgpu_hash_pks* / blsgpu_aggregate_*_secure*: groups digests (32 bytes each), then groups x m exponents (32 bytes each); the *_ranges forms: the head words, the digests, the exponents and the range table of the sums (secure_ranges_plan.h)
     B_SHR_WS,            // blsgpu_sig_shares_check*: what one slice of sessions keeps over its rounds -- a flag word, the subgroup flags, H(m), the scalars r and w, the key copies and the leaves A, B (every array, its writer and readers: find_plan.h, FIND_SHR_KEEP)
     B_SHR_ROUND,         // ... and what one round of it takes: the node table, the gathered leaves, the node sums, the pairs, the pairing results and the verdict bytes (find_plan.h, FIND_SHR_ROUND)
     B_SEED_WS,           // blsgpu_keys_from_seeds*: one slice of the keys (32 bytes each) and of their affine public keys (96) where the caller does not ask for them
