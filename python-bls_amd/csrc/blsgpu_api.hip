@@ -48,6 +48,7 @@
 #if BLSGPU_EMIT(BLSGPU_TU_HOST)
 #include "bisect_plan.h"
 #include "find_plan.h"
+#include "keys_plan.h"
 #include "msm_plan.h"
 #include "pairing_plan.h"
 #include "pairing_ranges_plan.h"
@@ -403,9 +404,16 @@ int msm_host(blsgpu_ctx* c, const uint8_t* pts, const uint8_t* scalars, size_t k
     return s.down();
 }
 
-// ------------------------------------------------------------ fixed-base G1, HD derivation (blsgpu_g1fix.hip) --
-constexpr size_t FIX_SLICE = (size_t)1 << 22;          // items per launch of the _dev forms
-constexpr size_t FIX_HOST_SLICE = (size_t)1 << 18;     // items per staged slice of the host-buffer forms (<= 76 MB of staging)
+// ------------------------------------------------------------ fixed-base G1, HD derivation (blsgpu_g1fix.hip, keys_plan.h) --
+using keys::FIX_SLICE;
+using keys::FIX_HOST_SLICE;
+constexpr keys::Consts KEYS_CONSTS = {blsgpu::g2smul::SLICE, blsgpu::g2smul::PAIRS, blsgpu::g2smul::TABLE_DW, blsgpu::frsec::SUM_THREADS,
+                                      blsgpu::frsec::EVAL_THREADS, blsgpu::g1poly::ENTRY_DW, blsgpu::seeds::PARENT_DW, blsgpu::lagr::MAX_K,
+                                      BLSGPU_HD_PARENT_BYTES};
+static_assert(keys::same(KEYS_CONSTS, keys::GFX950), "keys_plan.h: GFX950 (the host test's values) differs from the kernel files");
+static_assert(keys::G1 == BLSGPU_G1_BYTES && keys::G2 == BLSGPU_G2_BYTES, "keys_plan.h: the point sizes");
+// blsgpu_keys_from_seeds' staged slice is never zero: the longest seed and its outputs fit the staging target many times
+static_assert(keys::STAGE_TARGET / keys::seeds_item_bytes(BLSGPU_SEED_MAX_BYTES) >= 1, "keys_plan.h: staged_fit of the seeds form");
 
 // G1, ec.py:394-396 (little-endian words)
 blsgpu::g1fix::Gen g1_generator() {
@@ -442,15 +450,20 @@ int check_n_add(size_t n, size_t n_add, const void* add) {
     return 0;
 }
 
+// an optional array of the caller at a plan's offset: NULL stays NULL
+uint32_t* at_words(void* d, size_t words) { return d ? (uint32_t*)d + words : nullptr; }
+char* at_bytes(void* d, size_t bytes) { return d ? (char*)d + bytes : nullptr; }
+
 // enqueues out_i = s_i G1 (+ A) on `st` (caller: StreamGuard, table built)
 int fix_mul_launch(blsgpu_ctx* c, const void* d_scalars, size_t n, const void* d_add, size_t n_add, void* d_out_aff, void* d_out_ser,
                    hipStream_t st) {
     const bool per = n_add == n && n_add > 1;
-    return for_slices(n, slice_len(c, FIX_SLICE), [&](size_t lo, size_t m) {
-        hipLaunchKernelGGL(blsgpu::g1fix::k_fix_mul, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint32_t*)c->d_fix_table,
-                           (const uint32_t*)d_scalars + lo * 8, (uint32_t)m,
-                           n_add ? (const uint32_t*)d_add + (per ? lo * 24 : 0) : nullptr, per ? 1u : 0u,
-                           d_out_aff ? (uint32_t*)d_out_aff + lo * 24 : nullptr, d_out_ser ? (uint32_t*)d_out_ser + lo * 12 : nullptr);
+    const size_t step = keys::fix_step(*c);
+    return for_slices(n, step, [&](size_t lo, size_t) {
+        const keys::FixAt a = keys::fix_at(n, step, lo);
+        hipLaunchKernelGGL(blsgpu::g1fix::k_fix_mul, dim3(a.grid), dim3(256), 0, st, (const uint32_t*)c->d_fix_table,
+                           (const uint32_t*)d_scalars + a.scalars, (uint32_t)a.m, n_add ? (const uint32_t*)d_add + (per ? a.add : 0) : nullptr,
+                           per ? 1u : 0u, at_words(d_out_aff, a.aff), at_words(d_out_ser, a.ser));
         HIP_TRY(hipGetLastError());
         return 0;
     });
@@ -459,10 +472,11 @@ int fix_mul_launch(blsgpu_ctx* c, const void* d_scalars, size_t n, const void* d
 // enqueues out_i = s_i G1 on the scalar-independent schedule on `st` (caller: StreamGuard, fix_table(secret))
 int fix_mul_secret_launch(blsgpu_ctx* c, const void* d_scalars, size_t n, void* d_out_aff, void* d_out_ser, hipStream_t st) {
     KernelTimer kt(c, st, 9);
-    return for_slices(n, slice_len(c, FIX_SLICE), [&](size_t lo, size_t m) {
-        hipLaunchKernelGGL(blsgpu::g1fix::k_fix_mul_secret, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
-                           (const uint32_t*)c->d_fix_table_secret, (const uint32_t*)d_scalars + lo * 8, (uint32_t)m,
-                           d_out_aff ? (uint32_t*)d_out_aff + lo * 24 : nullptr, d_out_ser ? (uint32_t*)d_out_ser + lo * 12 : nullptr);
+    const size_t step = keys::fix_step(*c);
+    return for_slices(n, step, [&](size_t lo, size_t) {
+        const keys::FixAt a = keys::fix_at(n, step, lo);
+        hipLaunchKernelGGL(blsgpu::g1fix::k_fix_mul_secret, dim3(a.grid), dim3(256), 0, st, (const uint32_t*)c->d_fix_table_secret,
+                           (const uint32_t*)d_scalars + a.scalars, (uint32_t)a.m, at_words(d_out_aff, a.aff), at_words(d_out_ser, a.ser));
         HIP_TRY(hipGetLastError());
         return 0;
     });
@@ -541,18 +555,18 @@ int bisect_rounds(bisect::State<N>& b, size_t top, size_t limit, hipStream_t st,
 // over n entries in launches of FIX_SLICE; `mono`: that msg_idx does not decrease as well (another bit)
 int scan_indices(blsgpu_ctx* c, void* d_flag, const void* d_key_idx, size_t n_keys, const void* d_msg_idx, size_t n_msgs, size_t n, bool mono,
                  uint32_t& bad, hipStream_t st) {
-    const size_t FS = slice_len(c, FIX_SLICE);
+    const size_t FS = keys::fix_step(*c);
     return scan_flag(d_flag, st, bad, [&](uint32_t* flag) {
         for (size_t lo = 0; lo < n; lo += FS) {
-            const size_t m = n - lo < FS ? n - lo : FS;
-            hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
-                               (const uint32_t*)d_key_idx + lo, (uint32_t)m, (uint32_t)n_keys, flag);
+            const size_t m = keys::run_len(n, FS, lo);
+            const dim3 grid(keys::blocks(m));
+            hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, grid, dim3(256), 0, st, (const uint32_t*)d_key_idx + lo, (uint32_t)m,
+                               (uint32_t)n_keys, flag);
             if (d_msg_idx)
-                hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
-                                   (const uint32_t*)d_msg_idx + lo, (uint32_t)m, (uint32_t)n_msgs, flag);
+                hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, grid, dim3(256), 0, st, (const uint32_t*)d_msg_idx + lo, (uint32_t)m,
+                                   (uint32_t)n_msgs, flag);
             if (mono)
-                hipLaunchKernelGGL(blsgpu::pscan::k_fold_mono, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_msg_idx,
-                                   (uint32_t)lo, (uint32_t)m, flag);
+                hipLaunchKernelGGL(blsgpu::pscan::k_fold_mono, grid, dim3(256), 0, st, (const uint32_t*)d_msg_idx, (uint32_t)lo, (uint32_t)m, flag);
         }
     });
 }
@@ -564,19 +578,17 @@ int hd_children_dev(blsgpu_ctx* c, const uint8_t chain_code[32], const uint8_t p
     if (n == 0) return 0;
     if (!chain_code || !parent_pk_aff || !d_idx || !d_chain) return fail(-EINVAL, "NULL argument");
     if (parent_sk && !d_sk) return fail(-EINVAL, "private derivation needs out_sk");
-    if (n > 0xFFFFFFFFull) return fail(-EINVAL, "batch too large");
+    if (keys::too_many_lanes(n)) return fail(-EINVAL, "batch too large");
     const blsgpu::g1fix::HdParent P = hd_parent(chain_code, parent_pk_aff, parent_sk);
     StreamGuard sg(c, st);
     const bool pub = parent_sk == nullptr;
-    const size_t host_slice = slice_len(c, FIX_HOST_SLICE);
-    const size_t slice = pub ? (n < host_slice ? n : host_slice) : 0;
-    if (int rc = c->grow(B_FIX_WS, 256 + slice * 32)) return rc;
-    char* ws = c->at<char>(B_FIX_WS);                                  // [0, 96) parent key, [128, 132) flag, [256, ..) i_left
+    const keys::ChildrenPlan p = keys::plan_children(*c, n, pub);
+    if (int rc = c->grow(B_FIX_WS, p.bytes)) return rc;
+    char* ws = c->at<char>(B_FIX_WS);
     if (pub && check) {
         uint32_t flag;
-        if (int rc = scan_flag(ws + 128, st, flag, [&](uint32_t* d_flag) {
-                hipLaunchKernelGGL(blsgpu::g1fix::k_hd_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_idx,
-                                   (uint32_t)n, d_flag);
+        if (int rc = scan_flag(ws + p.o_flag, st, flag, [&](uint32_t* d_flag) {
+                hipLaunchKernelGGL(blsgpu::g1fix::k_hd_check, dim3(keys::blocks(n)), dim3(256), 0, st, (const uint32_t*)d_idx, (uint32_t)n, d_flag);
             }))
             return rc;
         if (flag) return fail(-EINVAL, "Cannot derive hardened children from public key");
@@ -585,15 +597,15 @@ int hd_children_dev(blsgpu_ctx* c, const uint8_t chain_code[32], const uint8_t p
     if (pk_out) {
         if (int rc = fix_table(c, st)) return rc;
     }
-    if (pub) HIP_TRY(hipMemcpyAsync(ws, parent_pk_aff, 96, hipMemcpyHostToDevice, st));
-    return for_slices(n, pub ? slice : slice_len(c, FIX_SLICE), [&](size_t lo, size_t m) {
-        uint32_t* scal = pub ? (uint32_t*)(ws + 256) : (uint32_t*)d_sk + lo * 8;
-        hipLaunchKernelGGL(blsgpu::g1fix::k_hd_hmac, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, P, (const uint32_t*)d_idx + lo,
-                           (uint32_t)m, (uint32_t*)d_chain + lo * 8, scal);
+    if (pub) HIP_TRY(hipMemcpyAsync(ws + p.o_parent, parent_pk_aff, 96, hipMemcpyHostToDevice, st));
+    return for_slices(n, p.step, [&](size_t lo, size_t) {
+        const keys::ChildrenAt a = p.at(lo);
+        uint32_t* scal = pub ? (uint32_t*)(ws + p.o_ileft) : (uint32_t*)d_sk + a.sk;
+        hipLaunchKernelGGL(blsgpu::g1fix::k_hd_hmac, dim3(a.grid), dim3(256), 0, st, P, (const uint32_t*)d_idx + a.idx, (uint32_t)a.m,
+                           (uint32_t*)d_chain + a.chain, scal);
         HIP_TRY(hipGetLastError());
         if (!pk_out) return 0;
-        return fix_mul_launch(c, scal, m, pub ? ws : nullptr, pub ? 1 : 0, d_pk_aff ? (char*)d_pk_aff + lo * 96 : nullptr,
-                              d_pk_ser ? (char*)d_pk_ser + lo * 48 : nullptr, st);
+        return fix_mul_launch(c, scal, a.m, pub ? ws + p.o_parent : nullptr, pub ? 1 : 0, at_bytes(d_pk_aff, a.aff), at_bytes(d_pk_ser, a.ser), st);
     });
 }
 // blsgpu_hd_paths*: the arguments every form checks before anything is written (after n == 0)
@@ -604,13 +616,12 @@ int hd_paths_args(const void* parents, size_t n_parents, int priv, const void* i
     if (!parents || !indices || !chain) return fail(-EINVAL, "NULL argument");
     if (priv && !sk) return fail(-EINVAL, "private derivation needs out_sk");
     if (!aff && !ser) return fail(-EINVAL, "ask for out_pk_aff or out_pk_ser");
-    if (n > 0xFFFFFFFFull || n_parents > 0xFFFFFFFFull) return fail(-EINVAL, "batch too large");
+    if (keys::hd_paths_too_large(n, n_parents)) return fail(-EINVAL, "batch too large");
     return 0;
 }
 
 // n paths of `depth` levels on `st`, every buffer in device memory: per slice and level k_hd_path_hmac, then k_fix_mul, over
-// state in B_HDP_WS -- [0, 4) the flag of the scan, [256, ..) per path 32 bytes chain code, 32 bytes key (private) or i_left
-// (public), 96 bytes affine key, and in public mode 96 more (k_fix_mul reads the parent key while it writes the child's).
+// the state of one slice in B_HDP_WS (keys::PathsPlan).
 // `check`: the device scan of parent_of and (public mode) the indices and one synchronising read of its flag first.
 // `secret` (private mode only, blsgpu_hd_paths_secret): k_hd_path_hmac_secret and k_fix_mul_secret in their places.
 int hd_paths_dev(blsgpu_ctx* c, const void* d_parents, size_t n_parents, int priv, const void* d_parent_of, const void* d_idx, size_t depth,
@@ -620,40 +631,40 @@ int hd_paths_dev(blsgpu_ctx* c, const void* d_parents, size_t n_parents, int pri
     if (n == 0) return 0;
     if (int rc = hd_paths_args(d_parents, n_parents, priv, d_idx, depth, n, d_chain, d_sk, d_pk_aff, d_pk_ser)) return rc;
     StreamGuard sg(c, st);
-    const size_t HS = slice_len(c, FIX_HOST_SLICE), S = n < HS ? n : HS;
-    if (int rc = c->grow(B_HDP_WS, 256 + S * (priv ? 160 : 256))) return rc;
+    const keys::PathsPlan p = keys::plan_paths(*c, n, depth, priv != 0);
+    if (int rc = c->grow(B_HDP_WS, p.bytes)) return rc;
     char* ws = c->at<char>(B_HDP_WS);
     if (check && (d_parent_of || !priv)) {
         uint32_t flag;
-        if (int rc = scan_flag(ws, st, flag, [&](uint32_t* d_flag) {
-                hipLaunchKernelGGL(k_hd_path_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_parent_of,
-                                   (uint32_t)n_parents, (const uint32_t*)d_idx, (uint32_t)depth, priv ? 0u : 1u, (uint32_t)n, d_flag);
+        if (int rc = scan_flag(ws + p.o_flag, st, flag, [&](uint32_t* d_flag) {
+                hipLaunchKernelGGL(k_hd_path_check, dim3(keys::blocks(n)), dim3(256), 0, st, (const uint32_t*)d_parent_of, (uint32_t)n_parents,
+                                   (const uint32_t*)d_idx, (uint32_t)depth, priv ? 0u : 1u, (uint32_t)n, d_flag);
             }))
             return rc;
         if (flag & 2u) return fail(-EINVAL, "parent index out of range");
         if (flag & 1u) return fail(-EINVAL, "Cannot derive hardened children from public key");
     }
     if (int rc = fix_table(c, st, secret)) return rc;
-    uint32_t* ws_chain = (uint32_t*)(ws + 256);
-    uint32_t* ws_scal = ws_chain + S * 8;
-    uint32_t* ws_aff[2] = {ws_scal + S * 8, ws_scal + S * 8 + S * 24};
+    uint32_t* ws_chain = (uint32_t*)(ws + p.o_chain);
+    uint32_t* ws_scal = (uint32_t*)(ws + p.o_scal);
+    uint32_t* ws_aff[2] = {(uint32_t*)(ws + p.o_aff[0]), (uint32_t*)(ws + p.o_aff[1])};
     const uint32_t* par = (const uint32_t*)d_parents;
-    return for_slices(n, S, [&](size_t lo, size_t m) {
+    return for_slices(n, p.S, [&](size_t lo, size_t m) {
+        const keys::PathsAt a = p.at(lo);
         int cur = 0;                                                       // ws_aff[cur]: the keys the next level derives from
         for (size_t l = 0; l < depth; l++) {
             const bool first = l == 0, last = l + 1 == depth;
-            uint32_t* chain_out = last ? (uint32_t*)d_chain + lo * 8 : ws_chain;
-            uint32_t* scal_out = last && priv ? (uint32_t*)d_sk + lo * 8 : ws_scal;
-            hipLaunchKernelGGL(secret ? k_hd_path_hmac_secret : k_hd_path_hmac, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
-                               first ? par : ws_chain,
+            uint32_t* chain_out = last ? (uint32_t*)d_chain + a.chain : ws_chain;
+            uint32_t* scal_out = last && priv ? (uint32_t*)d_sk + a.sk : ws_scal;
+            hipLaunchKernelGGL(secret ? k_hd_path_hmac_secret : k_hd_path_hmac, dim3(a.grid), dim3(256), 0, st, first ? par : ws_chain,
                                first ? par + 32 : ws_scal, first ? par + 8 : ws_aff[cur], first ? 40u : 0u,
-                               d_parent_of ? (const uint32_t*)d_parent_of + lo : nullptr, first ? 1u : 0u,
-                               (const uint32_t*)d_idx + lo * depth + l, (uint32_t)depth, (uint32_t)m, priv ? 1u : 0u, chain_out, scal_out,
-                               first && !priv ? ws_aff[0] : nullptr, last && d_fp ? (uint32_t*)d_fp + lo : nullptr);
+                               d_parent_of ? (const uint32_t*)d_parent_of + a.parent_of : nullptr, first ? 1u : 0u,
+                               (const uint32_t*)d_idx + a.idx + l, (uint32_t)depth, (uint32_t)m, priv ? 1u : 0u, chain_out, scal_out,
+                               first && !priv ? ws_aff[0] : nullptr, last ? at_words(d_fp, a.fp) : nullptr);
             HIP_TRY(hipGetLastError());
             const int next = priv ? 0 : cur ^ 1;
-            void* aff_out = last ? (d_pk_aff ? (char*)d_pk_aff + lo * 96 : nullptr) : (char*)ws_aff[next];
-            void* ser_out = last && d_pk_ser ? (char*)d_pk_ser + lo * 48 : nullptr;
+            void* aff_out = last ? at_bytes(d_pk_aff, a.aff) : (char*)ws_aff[next];
+            void* ser_out = last ? at_bytes(d_pk_ser, a.ser) : nullptr;
             if (int rc = secret ? fix_mul_secret_launch(c, scal_out, m, aff_out, ser_out, st)
                                 : fix_mul_launch(c, scal_out, m, priv ? nullptr : ws_aff[cur], priv ? 0 : m, aff_out, ser_out, st))
                 return rc;
@@ -663,8 +674,6 @@ int hd_paths_dev(blsgpu_ctx* c, const void* d_parents, size_t n_parents, int pri
     });
 }
 // ------------------------------------------------------------ keys from seeds (blsgpu_seeds.hip) --
-constexpr size_t SEED_SLICE = (size_t)1 << 20;         // seeds per launch of the _dev form (<= 128 MB of workspace)
-
 // the midstates of the two fixed keys (public constants), computed once: [0] "BLS private key seed", [1] "BLS HD seed"
 const hdk::HmacKey& seed_key(int hd) {
     static const struct Keys {
@@ -687,43 +696,39 @@ int seeds_args(const blsgpu_ctx* c, const void* seeds, size_t seed_len, size_t n
     if (n == 0) return 1;
     if (!seeds && seed_len) return fail(-EINVAL, "NULL seed buffer");
     if (!sk && !chain && !aff && !ser && !parents) return fail(-EINVAL, "ask for at least one output");
-    if (n > 0xFFFFFFFFull) return fail(-EINVAL, "batch too large");
+    if (keys::too_many_lanes(n)) return fail(-EINVAL, "batch too large");
     return 0;
 }
 
 // n keys from n seeds of seed_len bytes on `st`, every buffer in device memory (caller: seeds_args): per slice k_seed_keys
 // (timing kind 13), then -- when a public key is asked for -- k_fix_mul_secret on the keys where k_seed_keys left them (the
-// caller's out_sk or B_SEED_WS) and k_seed_pack_aff for the records.  B_SEED_WS: [0, S x 32) the keys when out_sk is NULL,
-// then S x 96 the affine keys when the records need them and out_pk_aff is NULL.
+// caller's out_sk or B_SEED_WS, keys::SeedsPlan) and k_seed_pack_aff for the records.
 int keys_from_seeds_dev(blsgpu_ctx* c, const void* d_seeds, size_t seed_len, size_t n, int hd, void* d_sk, void* d_chain, void* d_pk_aff,
                         void* d_pk_ser, void* d_parents, hipStream_t st) {
     using namespace blsgpu::seeds;
     StreamGuard sg(c, st);
     const bool pk = d_pk_aff || d_pk_ser || d_parents;
-    const size_t SS = slice_len(c, SEED_SLICE), S = n < SS ? n : SS;
-    const size_t ws_sk = d_sk ? 0 : S * 32, ws_aff = d_parents && !d_pk_aff ? S * 96 : 0;
-    if (ws_sk + ws_aff) {
-        if (int rc = c->grow(B_SEED_WS, ws_sk + ws_aff)) return rc;
-    }
+    const keys::SeedsPlan p = keys::plan_seeds(*c, KEYS_CONSTS, seed_len, n, d_sk != nullptr, d_pk_aff != nullptr, d_parents != nullptr);
+    if (int rc = c->grow(B_SEED_WS, p.bytes)) return rc;                   // (nothing to hold: nothing grows)
     if (pk) {
         if (int rc = fix_table(c, st, true)) return rc;
     }
     char* ws = c->at<char>(B_SEED_WS);
-    return for_slices(n, S, [&](size_t lo, size_t m) {
-        uint32_t* sk = d_sk ? (uint32_t*)d_sk + lo * 8 : (uint32_t*)ws;
-        uint32_t* par = d_parents ? (uint32_t*)d_parents + lo * PARENT_DW : nullptr;
+    return for_slices(n, p.S, [&](size_t lo, size_t) {
+        const keys::SeedsAt a = p.at(lo);
+        uint32_t* sk = d_sk ? (uint32_t*)d_sk + a.sk : (uint32_t*)(ws + p.o_sk);
+        uint32_t* par = at_words(d_parents, a.par);
         {
             KernelTimer kt(c, st, 13);
-            hipLaunchKernelGGL(k_seed_keys, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, seed_key(hd),
-                               (const uint8_t*)d_seeds + lo * seed_len, (uint32_t)seed_len, (uint32_t)m, (uint32_t)hd, sk,
-                               d_chain ? (uint32_t*)d_chain + lo * 8 : nullptr, par);
+            hipLaunchKernelGGL(k_seed_keys, dim3(a.grid), dim3(256), 0, st, seed_key(hd), (const uint8_t*)d_seeds + a.seeds, (uint32_t)seed_len,
+                               (uint32_t)a.m, (uint32_t)hd, sk, at_words(d_chain, a.chain), par);
             HIP_TRY(hipGetLastError());
         }
         if (!pk) return 0;
-        uint32_t* aff = d_pk_aff ? (uint32_t*)d_pk_aff + lo * 24 : (par ? (uint32_t*)(ws + ws_sk) : nullptr);
-        if (int rc = fix_mul_secret_launch(c, sk, m, aff, d_pk_ser ? (char*)d_pk_ser + lo * 48 : nullptr, st)) return rc;
+        uint32_t* aff = d_pk_aff ? (uint32_t*)d_pk_aff + a.aff : (par ? (uint32_t*)(ws + p.o_aff) : nullptr);
+        if (int rc = fix_mul_secret_launch(c, sk, a.m, aff, at_bytes(d_pk_ser, a.ser), st)) return rc;
         if (par) {
-            hipLaunchKernelGGL(k_seed_pack_aff, dim3((unsigned)((m * 24 + 255) / 256)), dim3(256), 0, st, (const uint32_t*)aff, (uint32_t)m, par);
+            hipLaunchKernelGGL(k_seed_pack_aff, dim3(a.g_pack), dim3(256), 0, st, (const uint32_t*)aff, (uint32_t)a.m, par);
             HIP_TRY(hipGetLastError());
         }
         return 0;
@@ -738,15 +743,12 @@ int poly_args(size_t n_polys, size_t t, const void* commit, const void* poly, co
     if (!s != !status) return fail(-EINVAL, "s and status must be NULL together");
     if (!status && !out_aff) return fail(-EINVAL, "ask for status or out_aff");
     if (n_polys == 0) return fail(-EINVAL, "polynomial index out of range");
-    if (n_polys > 0x7FFFFFFFull / t) return fail(-EINVAL, "too many commitments");
+    if (keys::poly_too_many(n_polys, t)) return fail(-EINVAL, "too many commitments");
     return 0;
 }
 
-// workspace: [0, 4) index-check flag, [256, o_l28) subgroup flags (one word per polynomial), [o_l28, ..) the L28 commitments
-size_t poly_ws_l28(size_t n_polys) { return 256 + (n_polys * 4 + 255) / 256 * 256; }
-int poly_ws(blsgpu_ctx* c, size_t n_polys, size_t t) {
-    return c->grow(B_POLY_WS, poly_ws_l28(n_polys) + n_polys * t * blsgpu::g1poly::ENTRY_DW * 4);
-}
+// B_POLY_WS of the call (keys::PolyPlan)
+int poly_ws(blsgpu_ctx* c, size_t n_polys, size_t t) { return c->grow(B_POLY_WS, keys::plan_poly(KEYS_CONSTS, n_polys, t).bytes); }
 
 // the commitments of the call, once: L28 entries, then the subgroup flags (caller: StreamGuard, poly_ws); `table`: the
 // left-hand sides need the fixed-base table -- `secret`: the signed 4-bit one of k_poly_eval_secret
@@ -756,15 +758,14 @@ int poly_prep(blsgpu_ctx* c, const void* d_commit, size_t n_polys, size_t t, boo
         if (int rc = fix_table(c, st, secret)) return rc;
     }
     char* ws = c->at<char>(B_POLY_WS);
-    const size_t m = n_polys * t;
-    uint32_t* l28 = (uint32_t*)(ws + poly_ws_l28(n_polys));
-    HIP_TRY(hipMemsetAsync(ws + 256, 0, n_polys * 4, st));
-    hipLaunchKernelGGL(k_poly_prep, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_commit, (uint32_t)m, l28);
+    const keys::PolyPlan p = keys::plan_poly(KEYS_CONSTS, n_polys, t);
+    uint32_t* l28 = (uint32_t*)(ws + p.o_l28);
+    HIP_TRY(hipMemsetAsync(ws + p.o_sub, 0, p.sub_bytes, st));
+    hipLaunchKernelGGL(k_poly_prep, dim3(p.g_prep), dim3(256), 0, st, (const uint32_t*)d_commit, (uint32_t)p.m, l28);
     HIP_TRY(hipGetLastError());
     if (t > 1) {
-        const size_t mk = n_polys * (t - 1);
-        hipLaunchKernelGGL(k_poly_subgroup, dim3((unsigned)((mk + 255) / 256)), dim3(256), 0, st, (const uint32_t*)l28, (uint32_t)n_polys,
-                           (uint32_t)t, (uint32_t*)(ws + 256));
+        hipLaunchKernelGGL(k_poly_subgroup, dim3(p.g_sub), dim3(256), 0, st, (const uint32_t*)l28, (uint32_t)n_polys, (uint32_t)t,
+                           (uint32_t*)(ws + p.o_sub));
         HIP_TRY(hipGetLastError());
     }
     return 0;
@@ -775,14 +776,16 @@ int poly_prep(blsgpu_ctx* c, const void* d_commit, size_t n_polys, size_t t, boo
 int poly_eval_launch(blsgpu_ctx* c, size_t n_polys, size_t t, const void* d_poly, const void* d_x, const void* d_s, size_t n, void* d_status,
                      void* d_out_aff, hipStream_t st, bool secret = false) {
     char* ws = c->at<char>(B_POLY_WS);
+    const keys::PolyPlan p = keys::plan_poly(KEYS_CONSTS, n_polys, t);
+    const size_t step = keys::fix_step(*c);
     auto launches = [&]() {
-        return for_slices(n, slice_len(c, FIX_SLICE), [&](size_t lo, size_t m) {
-            hipLaunchKernelGGL(secret ? blsgpu::g1poly::k_poly_eval_secret : blsgpu::g1poly::k_poly_eval, dim3((unsigned)((m + 255) / 256)),
-                               dim3(256), 0, st, (const uint32_t*)(secret ? c->d_fix_table_secret : c->d_fix_table),
-                               (const uint32_t*)(ws + poly_ws_l28(n_polys)), (const uint32_t*)(ws + 256), (uint32_t)n_polys, (uint32_t)t,
-                               (const uint32_t*)d_poly + lo, (const uint32_t*)d_x + lo * 8, d_s ? (const uint32_t*)d_s + lo * 8 : nullptr,
-                               (uint32_t)m, d_status ? (uint8_t*)d_status + lo : nullptr,
-                               d_out_aff ? (uint32_t*)d_out_aff + lo * 24 : nullptr);
+        return for_slices(n, step, [&](size_t lo, size_t) {
+            const keys::FixAt a = keys::fix_at(n, step, lo);                // (x and s: scalars; the polynomial index and the status: an entry an item)
+            hipLaunchKernelGGL(secret ? blsgpu::g1poly::k_poly_eval_secret : blsgpu::g1poly::k_poly_eval, dim3(a.grid), dim3(256), 0, st,
+                               (const uint32_t*)(secret ? c->d_fix_table_secret : c->d_fix_table), (const uint32_t*)(ws + p.o_l28),
+                               (const uint32_t*)(ws + p.o_sub), (uint32_t)n_polys, (uint32_t)t, (const uint32_t*)d_poly + lo,
+                               (const uint32_t*)d_x + a.scalars, d_s ? (const uint32_t*)d_s + a.scalars : nullptr, (uint32_t)a.m,
+                               (uint8_t*)at_bytes(d_status, lo), at_words(d_out_aff, a.aff));
             HIP_TRY(hipGetLastError());
             return 0;
         });
@@ -802,18 +805,9 @@ int poly_check_dev(blsgpu_ctx* c, const void* d_commit, size_t n_polys, size_t t
     if (int rc = poly_args(n_polys, t, d_commit, d_poly, d_x, d_s, d_status, d_out_aff)) return rc;
     StreamGuard sg(c, st);
     if (int rc = poly_ws(c, n_polys, t)) return rc;
-    uint32_t* flag = c->at<uint32_t>(B_POLY_WS);
-    HIP_TRY(hipMemsetAsync(flag, 0, 4, st));
-    const size_t FS = slice_len(c, FIX_SLICE);
-    for (size_t lo = 0; lo < n; lo += FS) {
-        const size_t m = n - lo < FS ? n - lo : FS;
-        hipLaunchKernelGGL(blsgpu::g1poly::k_poly_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_poly + lo,
-                           (uint32_t)m, (uint32_t)n_polys, flag);
-        HIP_TRY(hipGetLastError());
-    }
-    uint32_t bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    uint32_t bad;
+    if (int rc = scan_indices(c, c->at<char>(B_POLY_WS) + keys::plan_poly(KEYS_CONSTS, n_polys, t).o_flag, d_poly, n_polys, nullptr, 0, n, false, bad, st))
+        return rc;
     if (bad) return fail(-EINVAL, "polynomial index out of range");
     if (int rc = poly_prep(c, d_commit, n_polys, t, d_status != nullptr, st, secret)) return rc;
     return poly_eval_launch(c, n_polys, t, d_poly, d_x, d_s, n, d_status, d_out_aff, st, secret);
@@ -858,26 +852,34 @@ int subgroup_host(blsgpu_ctx* c, int g, const uint8_t* pts, size_t n, uint8_t* s
 // the argument checks the three entry-point pairs share (before anything is written); 1: nothing to do
 int lagrange_args(const blsgpu_ctx* c, size_t k, size_t groups, bool null_buffer) {
     if (!c) return fail(-EINVAL, "ctx is NULL");
-    if (k == 0 || k > blsgpu::lagr::MAX_K) return fail(-EINVAL, "k must be 1 .. BLSGPU_LAGRANGE_MAX_K");
+    if (keys::bad_k(KEYS_CONSTS, k)) return fail(-EINVAL, "k must be 1 .. BLSGPU_LAGRANGE_MAX_K");
     if (groups == 0) return 1;
     if (null_buffer) return fail(-EINVAL, "NULL argument");
-    if (groups > 0x7FFFFFFFull || k * groups > 0xFFFFFFF0ull) return fail(-EINVAL, "batch too large");
+    if (keys::lagrange_too_large(k, groups)) return fail(-EINVAL, "batch too large");
     return 0;
 }
 // coefficients and status of `groups` groups of k points (checked by lagrange_args), all on the device
 int lagrange_launch(blsgpu_ctx* c, const void* d_x, size_t k, size_t groups, void* d_coeffs, void* d_status, hipStream_t st) {
-    const blsgpu::lagr::Shape sh = blsgpu::lagr::shape((uint32_t)k);
-    hipLaunchKernelGGL(blsgpu::lagr::k_lagrange, dim3((unsigned)((groups + sh.gpb - 1) / sh.gpb)), dim3(sh.threads), sh.lds, st,
-                       (const uint8_t*)d_x, (uint32_t)k, (uint32_t)groups, sh.gpb, (uint8_t*)d_coeffs, (uint8_t*)d_status);
+    const keys::LagrShape sh = keys::lagrange_shape((uint32_t)k);
+    hipLaunchKernelGGL(blsgpu::lagr::k_lagrange, dim3(sh.grid(groups)), dim3(sh.threads), sh.lds, st, (const uint8_t*)d_x, (uint32_t)k,
+                       (uint32_t)groups, sh.gpb, (uint8_t*)d_coeffs, (uint8_t*)d_status);
     HIP_TRY(hipGetLastError());
     return 0;
 }
-int fr_interpolate_dev(blsgpu_ctx* c, const void* d_x, const void* d_y, size_t k, size_t groups, void* d_out, void* d_status, hipStream_t st) {
+// ... into B_LAGR_WS (caller: StreamGuard)
+int lagrange_to_ws(blsgpu_ctx* c, const void* d_x, size_t k, size_t groups, void* d_status, hipStream_t st) {
+    if (int rc = c->grow(B_LAGR_WS, keys::coeff_bytes(k, groups))) return rc;
+    return lagrange_launch(c, d_x, k, groups, c->at<void>(B_LAGR_WS), d_status, st);
+}
+// out[g] = sum_j L_j y_j with the coefficients of B_LAGR_WS: k_fr_dot, or `secret`: k_fr_dot_secret's masked sums (timing kind 10)
+int fr_interpolate_dev(blsgpu_ctx* c, const void* d_x, const void* d_y, size_t k, size_t groups, void* d_out, void* d_status, hipStream_t st,
+                       bool secret = false) {
     StreamGuard sg(c, st);
-    if (int rc = c->grow(B_LAGR_WS, groups * k * 32)) return rc;
-    if (int rc = lagrange_launch(c, d_x, k, groups, c->at<void>(B_LAGR_WS), d_status, st)) return rc;
-    const blsgpu::lagr::Shape sh = blsgpu::lagr::shape((uint32_t)k);
-    hipLaunchKernelGGL(blsgpu::lagr::k_fr_dot, dim3((unsigned)((groups + sh.gpb - 1) / sh.gpb)), dim3(sh.threads), sh.lds, st,
+    if (int rc = lagrange_to_ws(c, d_x, k, groups, d_status, st)) return rc;
+    const keys::LagrShape sh = keys::lagrange_shape((uint32_t)k);
+    std::optional<KernelTimer> kt;
+    if (secret) kt.emplace(c, st, 10);
+    hipLaunchKernelGGL(secret ? blsgpu::frsec::k_fr_dot_secret : blsgpu::lagr::k_fr_dot, dim3(sh.grid(groups)), dim3(sh.threads), sh.lds, st,
                        c->at<uint8_t>(B_LAGR_WS), (const uint8_t*)d_y, (uint32_t)k, (uint32_t)groups, sh.gpb, (uint8_t*)d_out);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -888,8 +890,7 @@ int threshold_combine_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_x, si
                           void* d_status, hipStream_t st) {
     {
         StreamGuard sg(c, st);
-        if (int rc = c->grow(B_LAGR_WS, groups * k * 32)) return rc;
-        if (int rc = lagrange_launch(c, d_x, k, groups, c->at<void>(B_LAGR_WS), d_status, st)) return rc;
+        if (int rc = lagrange_to_ws(c, d_x, k, groups, d_status, st)) return rc;
     }
     return msm_dev<2>(c, d_sigs, c->at<void>(B_LAGR_WS), k, groups, d_out, d_out_inf, st);
 }
@@ -1519,27 +1520,14 @@ int verify_find_folded_dev(blsgpu_ctx* c, const void* d_sigs, const void* d_keys
 }
 
 // ------------------------------------------------------------ scalar-field work on secrets (blsgpu_frsecret.hip) --
-// blsgpu_fr_interpolate_at_zero_secret: fr_interpolate_dev with the masked sums (timing kind 10)
-int fr_interpolate_secret_dev(blsgpu_ctx* c, const void* d_x, const void* d_y, size_t k, size_t groups, void* d_out, void* d_status,
-                              hipStream_t st) {
-    StreamGuard sg(c, st);
-    if (int rc = c->grow(B_LAGR_WS, groups * k * 32)) return rc;
-    if (int rc = lagrange_launch(c, d_x, k, groups, c->at<void>(B_LAGR_WS), d_status, st)) return rc;
-    const blsgpu::lagr::Shape sh = blsgpu::lagr::shape((uint32_t)k);
-    KernelTimer kt(c, st, 10);
-    hipLaunchKernelGGL(blsgpu::frsec::k_fr_dot_secret, dim3((unsigned)((groups + sh.gpb - 1) / sh.gpb)), dim3(sh.threads), sh.lds, st,
-                       c->at<uint8_t>(B_LAGR_WS), (const uint8_t*)d_y, (uint32_t)k, (uint32_t)groups, sh.gpb, (uint8_t*)d_out);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
+// (blsgpu_fr_interpolate_at_zero_secret: fr_interpolate_dev with `secret`)
 // the argument checks of blsgpu_fr_sum_secret* (before anything is written); 1: nothing to do
 int fr_sum_args(const blsgpu_ctx* c, const void* y, size_t k, size_t groups, const void* out) {
     if (!c) return fail(-EINVAL, "ctx is NULL");
     if (k == 0) return fail(-EINVAL, "k must be at least 1");
     if (groups == 0) return 1;
     if (!y || !out) return fail(-EINVAL, "NULL argument");
-    if (groups > 0x7FFFFFFFull || k > (~(size_t)0 >> 6) / groups) return fail(-EINVAL, "batch too large");
+    if (keys::fr_sum_too_large(k, groups)) return fail(-EINVAL, "batch too large");
     return 0;
 }
 // out[g] = sum_j y[g k + j] mod n (k_fr_sum_secret, timing kind 10), then the public key of every sum from k_fix_mul_secret
@@ -1552,11 +1540,11 @@ int fr_sum_secret_dev(blsgpu_ctx* c, const void* d_y, size_t k, size_t groups, v
     if (pk) {
         if (int rc = fix_table(c, st, true)) return rc;
     }
-    const uint32_t per = k <= SUM_THREADS ? (uint32_t)k : SUM_THREADS, gpb = SUM_THREADS / per;
+    const keys::SumShape sh = keys::sum_shape(KEYS_CONSTS, k);
     {
         KernelTimer kt(c, st, 10);
-        hipLaunchKernelGGL(k_fr_sum_secret, dim3((unsigned)((groups + gpb - 1) / gpb)), dim3(SUM_THREADS), 0, st, (const uint8_t*)d_y, k,
-                           (uint32_t)groups, gpb, per, (uint8_t*)d_out);
+        hipLaunchKernelGGL(k_fr_sum_secret, dim3(sh.grid(groups)), dim3(SUM_THREADS), 0, st, (const uint8_t*)d_y, k, (uint32_t)groups, sh.gpb,
+                           sh.per, (uint8_t*)d_out);
         HIP_TRY(hipGetLastError());
     }
     return pk ? fix_mul_secret_launch(c, d_out, groups, d_out_pk_aff, d_out_pk_ser, st) : 0;
@@ -1570,17 +1558,16 @@ int hash_pks_args(const blsgpu_ctx* c, size_t k, size_t m, size_t groups, bool n
     if (k == 0 || m == 0) return fail(-EINVAL, "k and m must be at least 1");
     if (groups == 0) return 1;
     if (null_buffer) return fail(-EINVAL, "NULL argument");
-    if (groups > 0x7FFFFFFFull || m > 0xFFFFFFFFull || m * groups > 0xFFFFFFF0ull || k > (~(size_t)0 >> 6) / groups)
-        return fail(-EINVAL, "batch too large");
+    if (secure_ranges::fixed_too_large(k, m, groups)) return fail(-EINVAL, "batch too large");
     return 0;
 }
-// the workspace of a call: the digests, then the exponents (when they are not the caller's buffers)
+// the workspace of a call: the digests, then the exponents (when they are not the caller's buffers; secure_ranges::FixedWorkspace)
 struct HashPksWs { uint32_t* digest; uint32_t* ts; };
 int hash_pks_ws(blsgpu_ctx* c, size_t m, size_t groups, HashPksWs& w) {
-    const size_t dg_bytes = (groups * 32 + 255) & ~(size_t)255;
-    if (int rc = c->grow(B_HPK_WS, dg_bytes + groups * m * 32)) return rc;
-    w.digest = c->at<uint32_t>(B_HPK_WS);
-    w.ts = (uint32_t*)(c->at<char>(B_HPK_WS) + dg_bytes);
+    const secure_ranges::FixedWorkspace p = secure_ranges::fixed_workspace(m, groups);
+    if (int rc = c->grow(B_HPK_WS, p.total)) return rc;
+    w.digest = (uint32_t*)(c->at<char>(B_HPK_WS) + p.digests);
+    w.ts = (uint32_t*)(c->at<char>(B_HPK_WS) + p.exps);
     return 0;
 }
 // enqueues the digests of `groups` groups of k keys (k_hash_pks_digest, timing kind 11; skipped when the caller has them:
@@ -1590,17 +1577,17 @@ int hash_pks_launch(blsgpu_ctx* c, const void* d_pks_ser, size_t k, size_t group
                     void* d_digest_ws, hipStream_t st) {
     using namespace blsgpu::hashpks;
     const void* d_digest = d_pk_hash_in;
+    const size_t total = groups * m;
+    const secure_ranges::Grids g = secure_ranges::grids(groups, total);
     if (!d_digest) {
         KernelTimer kt(c, st, 11);
-        hipLaunchKernelGGL(k_hash_pks_digest, dim3((unsigned)((groups + DIGEST_THREADS - 1) / DIGEST_THREADS)), dim3(DIGEST_THREADS), 0, st,
-                           (const uint32_t*)d_pks_ser, k, (uint32_t)groups, (uint32_t*)d_digest_ws);
+        hipLaunchKernelGGL(k_hash_pks_digest, dim3(g.digest), dim3(DIGEST_THREADS), 0, st, (const uint32_t*)d_pks_ser, k, (uint32_t)groups,
+                           (uint32_t*)d_digest_ws);
         HIP_TRY(hipGetLastError());
         d_digest = d_digest_ws;
     }
-    const size_t total = groups * m;
     KernelTimer kt(c, st, 12);
-    hipLaunchKernelGGL(k_hash_pks_exp, dim3((unsigned)((total + EXP_THREADS - 1) / EXP_THREADS)), dim3(EXP_THREADS), 0, st,
-                       (const uint32_t*)d_digest, (uint32_t)m, total, (uint32_t*)d_ts);
+    hipLaunchKernelGGL(k_hash_pks_exp, dim3(g.exp), dim3(EXP_THREADS), 0, st, (const uint32_t*)d_digest, (uint32_t)m, total, (uint32_t*)d_ts);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1644,11 +1631,11 @@ int aggregate_priv_keys_secure_dev(blsgpu_ctx* c, const void* d_sks, const void*
     HashPksWs w;
     if (int rc = hash_pks_ws(c, k, groups, w)) return rc;
     if (int rc = hash_pks_launch(c, d_pks_ser, k, groups, d_pk_hash_in, k, w.ts, w.digest, st)) return rc;
-    const blsgpu::lagr::Shape sh = blsgpu::lagr::shape((uint32_t)k);
+    const keys::LagrShape sh = keys::lagrange_shape((uint32_t)k);
     {
         KernelTimer kt(c, st, 10);
-        hipLaunchKernelGGL(blsgpu::frsec::k_fr_dot_secret, dim3((unsigned)((groups + sh.gpb - 1) / sh.gpb)), dim3(sh.threads), sh.lds, st,
-                           (const uint8_t*)w.ts, (const uint8_t*)d_sks, (uint32_t)k, (uint32_t)groups, sh.gpb, (uint8_t*)d_out);
+        hipLaunchKernelGGL(blsgpu::frsec::k_fr_dot_secret, dim3(sh.grid(groups)), dim3(sh.threads), sh.lds, st, (const uint8_t*)w.ts,
+                           (const uint8_t*)d_sks, (uint32_t)k, (uint32_t)groups, sh.gpb, (uint8_t*)d_out);
         HIP_TRY(hipGetLastError());
     }
     return pk ? fix_mul_secret_launch(c, d_out, groups, d_out_pk_aff, d_out_pk_ser, st) : 0;
@@ -1657,7 +1644,7 @@ int aggregate_priv_keys_secure_dev(blsgpu_ctx* c, const void* d_sks, const void*
 int aggregate_priv_args(const blsgpu_ctx* c, size_t k, size_t groups, bool null_buffer) {
     if (c && k > blsgpu::lagr::MAX_K) return fail(-EINVAL, "k must be 1 .. BLSGPU_LAGRANGE_MAX_K");
     if (int rc = hash_pks_args(c, k, k, groups, null_buffer)) return rc;
-    if (k * groups > 0xFFFFFFF0ull) return fail(-EINVAL, "batch too large");
+    if (secure_ranges::fixed_priv_too_large(k, groups)) return fail(-EINVAL, "batch too large");
     return 0;
 }
 
@@ -1812,14 +1799,12 @@ int secure_ranges_host(blsgpu_ctx* c, const uint8_t* pts, size_t n_exp, const ui
 int deal_args(const blsgpu_ctx* c, const void* coeffs, size_t n_polys, size_t t, const void* x, size_t n_x, const void* out_commit,
               const void* out_frag) {
     if (!c) return fail(-EINVAL, "ctx is NULL");
-    if (t == 0 || t > blsgpu::lagr::MAX_K) return fail(-EINVAL, "t must be 1 .. BLSGPU_LAGRANGE_MAX_K");
+    if (keys::bad_k(KEYS_CONSTS, t)) return fail(-EINVAL, "t must be 1 .. BLSGPU_LAGRANGE_MAX_K");
     if (n_polys == 0) return 1;
     if (!coeffs) return fail(-EINVAL, "NULL argument");
     if (!out_commit && !out_frag) return fail(-EINVAL, "out_commit_aff and out_frag are both NULL");
     if (out_frag && (n_x == 0 || !x)) return fail(-EINVAL, "fragments need at least one point");
-    const size_t bpp = (n_x + blsgpu::frsec::EVAL_THREADS - 1) / blsgpu::frsec::EVAL_THREADS;
-    if (n_polys > 0x7FFFFFFFull || n_x > 0xFFFFFF00ull || (out_frag && n_polys * bpp > 0x7FFFFFFFull) || n_polys * t > 0xFFFFFFF0ull)
-        return fail(-EINVAL, "batch too large");
+    if (keys::deal_too_large(KEYS_CONSTS, n_polys, t, n_x, out_frag != nullptr)) return fail(-EINVAL, "batch too large");
     return 0;
 }
 // commitments c_k G1 (k_fix_mul_secret) and fragments P(x_j) (k_fr_poly_eval_secret) of n_polys polynomials, all on the device
@@ -1831,10 +1816,10 @@ int deal_secret_dev(blsgpu_ctx* c, const void* d_coeffs, size_t n_polys, size_t 
         if (int rc = fix_mul_secret_launch(c, d_coeffs, n_polys * t, d_out_commit, nullptr, st)) return rc;
     }
     if (d_out_frag) {
-        const size_t bpp = (n_x + blsgpu::frsec::EVAL_THREADS - 1) / blsgpu::frsec::EVAL_THREADS;
         KernelTimer kt(c, st, 10);
-        hipLaunchKernelGGL(blsgpu::frsec::k_fr_poly_eval_secret, dim3((unsigned)(n_polys * bpp)), dim3(blsgpu::frsec::EVAL_THREADS), t * 32, st,
-                           (const uint8_t*)d_coeffs, (uint32_t)t, (const uint8_t*)d_x, (uint32_t)n_x, (uint32_t)bpp, (uint8_t*)d_out_frag);
+        hipLaunchKernelGGL(blsgpu::frsec::k_fr_poly_eval_secret, dim3(keys::eval_blocks(KEYS_CONSTS, n_polys, n_x)), dim3(blsgpu::frsec::EVAL_THREADS),
+                           t * keys::FR, st, (const uint8_t*)d_coeffs, (uint32_t)t, (const uint8_t*)d_x, (uint32_t)n_x,
+                           (uint32_t)keys::eval_bpp(KEYS_CONSTS, n_x), (uint8_t*)d_out_frag);
         HIP_TRY(hipGetLastError());
     }
     return 0;
@@ -3147,25 +3132,23 @@ static int g2_smul_launch(blsgpu_ctx* c, const void* d_pts, size_t n_pts, const 
         hipLaunchKernelGGL(k_g2_smul_table, dim3(1), dim3(256), 0, st, (const uint32_t*)d_pts, 1u, table);
         HIP_TRY(hipGetLastError());
     }
-    return for_slices(n, slice_len(c, SLICE), [&](size_t lo, size_t m) {
-        const unsigned blocks = (unsigned)((m + PAIRS - 1) / PAIRS);
-        if (!shared) hipLaunchKernelGGL(k_g2_smul_table, dim3(blocks), dim3(256), 0, st, (const uint32_t*)d_pts + lo * 48, (uint32_t)m, table);
-        hipLaunchKernelGGL(k_g2_smul, dim3(blocks), dim3(256), 0, st, (const uint32_t*)table, shared ? 2u : (uint32_t)(2 * m), shared ? 1u : 0u,
-                           (const uint32_t*)d_scalars + lo * 8, (uint32_t)m, d_out_aff ? (uint32_t*)d_out_aff + lo * 48 : nullptr,
-                           d_out_ser ? (uint32_t*)d_out_ser + lo * 24 : nullptr, d_out_inf ? (uint8_t*)d_out_inf + lo : nullptr);
+    const size_t step = keys::smul_step(*c, KEYS_CONSTS);
+    return for_slices(n, step, [&](size_t lo, size_t) {
+        const keys::SmulAt a = keys::smul_at(KEYS_CONSTS, n, step, lo);
+        const uint32_t m = (uint32_t)a.m;
+        if (!shared) hipLaunchKernelGGL(k_g2_smul_table, dim3(a.grid), dim3(256), 0, st, (const uint32_t*)d_pts + a.pts, m, table);
+        hipLaunchKernelGGL(k_g2_smul, dim3(a.grid), dim3(256), 0, st, (const uint32_t*)table, shared ? 2u : 2 * m, shared ? 1u : 0u,
+                           (const uint32_t*)d_scalars + a.scalars, m, at_words(d_out_aff, a.aff), at_words(d_out_ser, a.ser),
+                           (uint8_t*)at_bytes(d_out_inf, a.inf));
         HIP_TRY(hipGetLastError());
         return 0;
     });
-}
-static size_t g2_smul_tables(const blsgpu_ctx* c, size_t n_pts, size_t n) {   // points whose tables are held at a time
-    const size_t S = slice_len(c, blsgpu::g2smul::SLICE);
-    return n_pts == 1 ? 1 : (n < S ? n : S);
 }
 static int g2_smul_args(size_t n_sel, size_t n, const void* a, const void* b, const void* out_aff, const void* out_ser, const char* what) {
     if (n_sel != 1 && n_sel != n) return fail(-EINVAL, std::string(what) + " must be 1 or n");
     if (!a || !b) return fail(-EINVAL, "NULL argument");
     if (!out_aff && !out_ser) return fail(-EINVAL, "out_aff and out_ser are both NULL");
-    if (n > 0xFFFFFFF0ull) return fail(-EINVAL, "batch too large");
+    if (keys::g2_smul_too_large(n)) return fail(-EINVAL, "batch too large");
     return 0;
 }
 
@@ -3176,7 +3159,7 @@ BLSGPU_EXPORT int blsgpu_g2_mul_secret_dev(blsgpu_ctx* c, const void* d_pts, siz
     if (int rc = g2_smul_args(n_pts, n, d_pts, d_scalars, d_out_aff, d_out_ser, "n_pts")) return rc;
     HIP_TRY(hipSetDevice(c->device));
     StreamGuard sg(c, (hipStream_t)stream);
-    if (int rc = c->grow(B_SMUL_WS, g2_smul_tables(c, n_pts, n) * blsgpu::g2smul::TABLE_DW * 4)) return rc;
+    if (int rc = c->grow(B_SMUL_WS, keys::smul_table_bytes(KEYS_CONSTS, keys::smul_held(*c, KEYS_CONSTS, n_pts == 1, n)))) return rc;
     return g2_smul_launch(c, d_pts, n_pts, d_scalars, n, d_out_aff, d_out_ser, d_out_inf, c->at<uint32_t>(B_SMUL_WS), (hipStream_t)stream);
 }
 BLSGPU_EXPORT int blsgpu_g2_mul_secret(blsgpu_ctx* c, const uint8_t* pts, size_t n_pts, const uint8_t* scalars, size_t n, uint8_t* out_aff,
@@ -3185,7 +3168,7 @@ BLSGPU_EXPORT int blsgpu_g2_mul_secret(blsgpu_ctx* c, const uint8_t* pts, size_t
     if (n == 0) return 0;
     if (int rc = g2_smul_args(n_pts, n, pts, scalars, out_aff, out_ser, "n_pts")) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t GS = slice_len(c, blsgpu::g2smul::SLICE), S = n < GS ? n : GS;
+    const size_t S = keys::staged_slice(*c, n, KEYS_CONSTS.smul_slice);
     const bool per = n_pts != 1;
     Staging s(c);
     const int dp = per ? s.in(pts, S, 192) : s.in(pts, 192), dsc = s.in(scalars, S, 32), daff = s.out(out_aff, S, 192),
@@ -3208,16 +3191,16 @@ BLSGPU_EXPORT int blsgpu_sign_dev(blsgpu_ctx* c, const void* d_sks, const void* 
     if (int rc = g2_smul_args(n_msg, n, d_sks, d_msg_hashes, d_out_aff, d_out_ser, "n_msg")) return rc;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
-    const size_t held = g2_smul_tables(c, n_msg, n), pts_bytes = (held * BLSGPU_G2_BYTES + 255) & ~(size_t)255;
-    if (int rc = c->grow(B_SMUL_WS, pts_bytes + held * blsgpu::g2smul::TABLE_DW * 4)) return rc;
-    char* d_hm = c->at<char>(B_SMUL_WS);
-    uint32_t* table = (uint32_t*)(d_hm + pts_bytes);
-    return for_slices(n, n_msg == 1 ? n : held, [&](size_t lo, size_t m) {
-        const size_t msgs = n_msg == 1 ? 1 : m;
-        if (int rc = map_to_g2_impl(c, (const char*)d_msg_hashes + (n_msg == 1 ? 0 : lo * 32), msgs, d_hm, st, true)) return rc;
+    const keys::SignPlan p = keys::plan_sign(*c, KEYS_CONSTS, n_msg, n);
+    if (int rc = c->grow(B_SMUL_WS, p.bytes)) return rc;
+    char* d_hm = c->at<char>(B_SMUL_WS) + p.o_pts;
+    uint32_t* table = (uint32_t*)(c->at<char>(B_SMUL_WS) + p.o_table);
+    return for_slices(n, p.step, [&](size_t lo, size_t) {
+        const keys::SignAt a = p.at(lo);
+        if (int rc = map_to_g2_impl(c, (const char*)d_msg_hashes + a.hashes, a.msgs, d_hm, st, true)) return rc;
         StreamGuard sg(c, st);
-        return g2_smul_launch(c, d_hm, msgs, (const char*)d_sks + lo * 32, m, d_out_aff ? (char*)d_out_aff + lo * BLSGPU_G2_BYTES : nullptr,
-                              d_out_ser ? (char*)d_out_ser + lo * 96 : nullptr, nullptr, table, st);
+        return g2_smul_launch(c, d_hm, a.msgs, (const char*)d_sks + a.sks, a.m, at_bytes(d_out_aff, a.aff), at_bytes(d_out_ser, a.ser), nullptr,
+                              table, st);
     });
 }
 BLSGPU_EXPORT int blsgpu_sign(blsgpu_ctx* c, const uint8_t* sks, const uint8_t* msg_hashes, size_t n_msg, size_t n, uint8_t* out_aff,
@@ -3226,7 +3209,7 @@ BLSGPU_EXPORT int blsgpu_sign(blsgpu_ctx* c, const uint8_t* sks, const uint8_t* 
     if (n == 0) return 0;
     if (int rc = g2_smul_args(n_msg, n, sks, msg_hashes, out_aff, out_ser, "n_msg")) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t GS = slice_len(c, blsgpu::g2smul::SLICE), S = n < GS ? n : GS;
+    const size_t S = keys::staged_slice(*c, n, KEYS_CONSTS.smul_slice);
     const bool per = n_msg != 1;
     Staging s(c);
     const int dsk = s.in(sks, S, 32), dh = per ? s.in(msg_hashes, S, 32) : s.in(msg_hashes, 32), daff = s.out(out_aff, S, 192),
@@ -3268,7 +3251,7 @@ static int g1_mul_gen_host(blsgpu_ctx* c, const uint8_t* scalars, size_t n, cons
     if (!secret)
         if (int rc = check_n_add(n, n_add, add)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t HS = slice_len(c, FIX_HOST_SLICE), S = n < HS ? n : HS;
+    const size_t S = keys::staged_slice(*c, n, FIX_HOST_SLICE);
     const bool per = n_add == n && n_add > 1;
     Staging s(c);
     const int dsc = s.in(scalars, S, 32), dadd = per ? s.in(add, S, 96) : s.in(n_add ? add : nullptr, 96), daff = s.out(out_aff, S, 96),
@@ -3315,7 +3298,7 @@ BLSGPU_EXPORT int blsgpu_hd_children(blsgpu_ctx* c, const uint8_t chain_code[32]
         for (size_t i = 0; i < n; i++)
             if (indices[i] >> 31) return fail(-EINVAL, "Cannot derive hardened children from public key");
     HIP_TRY(hipSetDevice(c->device));
-    const size_t HS = slice_len(c, FIX_HOST_SLICE), S = n < HS ? n : HS;
+    const size_t S = keys::staged_slice(*c, n, FIX_HOST_SLICE);
     Staging s(c);
     const int didx = s.in(indices, S, 4), dchain = s.out(out_chain, S, 32), dsk = s.out(parent_sk ? out_sk : nullptr, S, 32),
               daff = s.out(out_pk_aff, S, 96), dser = s.out(out_pk_ser, S, 48);
@@ -3350,7 +3333,7 @@ static int hd_paths_host(blsgpu_ctx* c, const uint8_t* parents, size_t n_parents
         for (size_t i = 0; i < n * depth; i++)
             if (indices[i] >> 31) return fail(-EINVAL, "Cannot derive hardened children from public key");
     HIP_TRY(hipSetDevice(c->device));
-    const size_t HS = slice_len(c, FIX_HOST_SLICE), S = n < HS ? n : HS;
+    const size_t S = keys::staged_slice(*c, n, FIX_HOST_SLICE);
     Staging s(c);
     const int dpar = s.in(parents, n_parents * BLSGPU_HD_PARENT_BYTES), dof = s.in(parent_of, S, 4), didx = s.in(indices, S, depth * 4),
               dchain = s.out(out_chain, S, 32), dsk = s.out(priv ? out_sk : nullptr, S, 32), daff = s.out(out_pk_aff, S, 96),
@@ -3407,9 +3390,7 @@ BLSGPU_EXPORT int blsgpu_keys_from_seeds(blsgpu_ctx* c, const uint8_t* seeds, si
                                          uint8_t* out_chain, uint8_t* out_pk_aff, uint8_t* out_pk_ser, uint8_t* out_parents) {
     if (int rc = seeds_args(c, seeds, seed_len, n, hd, out_sk, out_chain, out_pk_aff, out_pk_ser, out_parents)) return rc < 0 ? rc : 0;
     HIP_TRY(hipSetDevice(c->device));
-    // about 64 MB of staging per slice
-    const size_t fit = slice_len(c, ((size_t)1 << 26) / (seed_len + 368));
-    const size_t S = n < fit ? n : fit;
+    const size_t S = keys::staged_fit(*c, n, keys::seeds_item_bytes(seed_len));
     Staging s(c);
     const int dseed = s.in(seed_len ? seeds : nullptr, S, seed_len), dsk = s.out(out_sk, S, 32), dchain = s.out(out_chain, S, 32),
               daff = s.out(out_pk_aff, S, 96), dser = s.out(out_pk_ser, S, 48), dpar = s.out(out_parents, S, BLSGPU_HD_PARENT_BYTES);
@@ -3434,7 +3415,7 @@ static int poly_check_host(blsgpu_ctx* c, const uint8_t* commit, size_t n_polys,
     for (size_t i = 0; i < n; i++)
         if (poly[i] >= n_polys) return fail(-EINVAL, "polynomial index out of range");
     HIP_TRY(hipSetDevice(c->device));
-    const size_t HS = slice_len(c, FIX_HOST_SLICE), S = n < HS ? n : HS;
+    const size_t S = keys::staged_slice(*c, n, FIX_HOST_SLICE);
     Staging st(c);
     const int dcommit = st.in(commit, n_polys * t * 96), dpoly = st.in(poly, S, 4), dx = st.in(x, S, 32), ds = st.in(s, S, 32),
               dstatus = st.out(status, S, 1), daff = st.out(out_aff, S, 96);
@@ -3721,9 +3702,7 @@ BLSGPU_EXPORT int blsgpu_threshold_deal_secret(blsgpu_ctx* c, const uint8_t* coe
                                                uint8_t* out_commit_aff, uint8_t* out_frag) {
     if (int rc = deal_args(c, coeffs, n_polys, t, x, n_x, out_commit_aff, out_frag)) return rc < 0 ? rc : 0;
     HIP_TRY(hipSetDevice(c->device));
-    // whole polynomials per staged slice: about 64 MB of staging
-    const size_t per_poly = t * (32 + 96) + (out_frag ? n_x * 32 : 0), fit = slice_len(c, ((size_t)1 << 26) / per_poly);
-    const size_t S = n_polys < fit ? n_polys : (fit ? fit : 1);
+    const size_t S = keys::staged_fit(*c, n_polys, keys::deal_item_bytes(t, n_x, out_frag != nullptr));   // whole polynomials per staged slice
     Staging s(c);
     const int dco = s.in(coeffs, S, t * 32), dx = s.in(out_frag ? x : nullptr, n_x * 32), dcm = s.out(out_commit_aff, S, t * 96),
               dfr = s.out(out_frag, S, n_x * 32);
@@ -3740,7 +3719,7 @@ BLSGPU_EXPORT int blsgpu_fr_interpolate_at_zero_secret_dev(blsgpu_ctx* c, const 
                                                            void* d_status, void* stream) {
     if (int rc = lagrange_args(c, k, groups, !d_x || !d_y || !d_out || !d_status)) return rc < 0 ? rc : 0;
     HIP_TRY(hipSetDevice(c->device));
-    return fr_interpolate_secret_dev(c, d_x, d_y, k, groups, d_out, d_status, (hipStream_t)stream);
+    return fr_interpolate_dev(c, d_x, d_y, k, groups, d_out, d_status, (hipStream_t)stream, true);
 }
 BLSGPU_EXPORT int blsgpu_fr_interpolate_at_zero_secret(blsgpu_ctx* c, const uint8_t* x, const uint8_t* y, size_t k, size_t groups, uint8_t* out,
                                                        uint8_t* status) {
@@ -3750,7 +3729,7 @@ BLSGPU_EXPORT int blsgpu_fr_interpolate_at_zero_secret(blsgpu_ctx* c, const uint
     const int dx = s.in(x, groups * k * 32), dy = s.in(y, groups * k * 32), dout = s.out(out, groups * 32), dst = s.out(status, groups);
     if (int rc = s.alloc()) return rc;
     if (int rc = s.up()) return rc;
-    if (int rc = fr_interpolate_secret_dev(c, s.at(dx), s.at(dy), k, groups, s.at(dout), s.at(dst), nullptr)) return rc;
+    if (int rc = fr_interpolate_dev(c, s.at(dx), s.at(dy), k, groups, s.at(dout), s.at(dst), nullptr, true)) return rc;
     return s.down();
 }
 
@@ -3764,9 +3743,7 @@ BLSGPU_EXPORT int blsgpu_fr_sum_secret(blsgpu_ctx* c, const uint8_t* y, size_t k
                                        uint8_t* out_pk_ser) {
     if (int rc = fr_sum_args(c, y, k, groups, out)) return rc < 0 ? rc : 0;
     HIP_TRY(hipSetDevice(c->device));
-    // whole groups per staged slice: about 64 MB of staging
-    const size_t fit = slice_len(c, ((size_t)1 << 26) / (k * 32 + 176));
-    const size_t S = groups < fit ? groups : (fit ? fit : 1);
+    const size_t S = keys::staged_fit(*c, groups, keys::fr_sum_item_bytes(k));                           // whole groups per staged slice
     Staging s(c);
     const int dy = s.in(y, S, k * 32), dout = s.out(out, S, 32), daff = s.out(out_pk_aff, S, 96), dser = s.out(out_pk_ser, S, 48);
     if (int rc = s.alloc()) return rc;
@@ -3784,36 +3761,33 @@ BLSGPU_EXPORT int blsgpu_sign_threshold_dev(blsgpu_ctx* c, const void* d_sks, co
                                             size_t n_msg, void* d_out_aff, void* d_out_ser, void* d_out_inf, void* d_status, void* stream) {
     if (int rc = sign_threshold_args(c, k, groups, n_msg, !d_sks || !d_x || !d_msg_hashes || !d_status, d_out_aff, d_out_ser)) return rc < 0 ? rc : 0;
     HIP_TRY(hipSetDevice(c->device));
-    using namespace blsgpu::g2smul;
     hipStream_t st = (hipStream_t)stream;
-    const size_t n = k * groups;
-    const bool shared = n_msg == 1;
-    const size_t held = g2_smul_tables(c, shared ? 1 : n, n);
-    const size_t sc_bytes = (n * 32 + 255) & ~(size_t)255, hm_bytes = (n_msg * BLSGPU_G2_BYTES + 255) & ~(size_t)255;
-    if (int rc = c->grow(B_LAGR_WS, n * 32)) return rc;
-    if (int rc = c->grow(B_FRS_WS, sc_bytes + (shared ? 0 : held * BLSGPU_G2_BYTES))) return rc;
-    if (int rc = c->grow(B_SMUL_WS, hm_bytes + held * TABLE_DW * 4)) return rc;
-    char* d_sc = c->at<char>(B_FRS_WS);
-    char* d_rep = d_sc + sc_bytes;
-    char* d_hm = c->at<char>(B_SMUL_WS);
-    uint32_t* table = (uint32_t*)(d_hm + hm_bytes);
+    const keys::ThresholdPlan p = keys::plan_threshold(*c, KEYS_CONSTS, k, groups, n_msg);
+    if (int rc = c->grow(B_LAGR_WS, p.lagr_bytes)) return rc;
+    if (int rc = c->grow(B_FRS_WS, p.frs_bytes)) return rc;
+    if (int rc = c->grow(B_SMUL_WS, p.smul_bytes)) return rc;
+    char* d_sc = c->at<char>(B_FRS_WS) + p.o_sc;
+    char* d_rep = c->at<char>(B_FRS_WS) + p.o_rep;
+    char* d_hm = c->at<char>(B_SMUL_WS) + p.o_hm;
+    uint32_t* table = (uint32_t*)(c->at<char>(B_SMUL_WS) + p.o_table);
     {
         StreamGuard sg(c, st);
         if (int rc = lagrange_launch(c, d_x, k, groups, c->at<void>(B_LAGR_WS), d_status, st)) return rc;
         KernelTimer kt(c, st, 10);
-        hipLaunchKernelGGL(blsgpu::frsec::k_fr_scale_secret, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c->at<uint8_t>(B_LAGR_WS),
-                           (const uint8_t*)d_sks, (uint32_t)n, (uint8_t*)d_sc);
+        hipLaunchKernelGGL(blsgpu::frsec::k_fr_scale_secret, dim3(p.g_scale), dim3(256), 0, st, c->at<uint8_t>(B_LAGR_WS), (const uint8_t*)d_sks,
+                           (uint32_t)p.n, (uint8_t*)d_sc);
         HIP_TRY(hipGetLastError());
     }
     if (int rc = map_to_g2_impl(c, d_msg_hashes, n_msg, d_hm, st, true)) return rc;
     StreamGuard sg(c, st);
-    if (shared) return g2_smul_launch(c, d_hm, 1, d_sc, n, d_out_aff, d_out_ser, d_out_inf, table, st);
-    return for_slices(n, held, [&](size_t lo, size_t m) {
-        hipLaunchKernelGGL(blsgpu::frsec::k_g2_spread, dim3((unsigned)((m * 48 + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_hm, (uint32_t)k,
-                           lo, (uint32_t)m, (uint32_t*)d_rep);
+    if (p.shared) return g2_smul_launch(c, d_hm, 1, d_sc, p.n, d_out_aff, d_out_ser, d_out_inf, table, st);
+    return for_slices(p.n, p.held, [&](size_t lo, size_t) {
+        const keys::ThresholdAt a = p.at(lo);
+        hipLaunchKernelGGL(blsgpu::frsec::k_g2_spread, dim3(a.g_spread), dim3(256), 0, st, (const uint32_t*)d_hm, (uint32_t)k, lo, (uint32_t)a.m,
+                           (uint32_t*)d_rep);
         HIP_TRY(hipGetLastError());
-        return g2_smul_launch(c, d_rep, m, d_sc + lo * 32, m, d_out_aff ? (char*)d_out_aff + lo * BLSGPU_G2_BYTES : nullptr,
-                              d_out_ser ? (char*)d_out_ser + lo * 96 : nullptr, d_out_inf ? (char*)d_out_inf + lo : nullptr, table, st);
+        return g2_smul_launch(c, d_rep, a.m, d_sc + a.sc, a.m, at_bytes(d_out_aff, a.aff), at_bytes(d_out_ser, a.ser), at_bytes(d_out_inf, a.inf),
+                              table, st);
     });
 }
 BLSGPU_EXPORT int blsgpu_sign_threshold(blsgpu_ctx* c, const uint8_t* sks, const uint8_t* x, size_t k, size_t groups, const uint8_t* msg_hashes,

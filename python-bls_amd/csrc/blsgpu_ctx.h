@@ -55,16 +55,16 @@ enum BufId {
     B_BUCKETS,           // the bucket sums' buckets (HBM); the workspace of the sorted, plain and small-group sums; blsgpu_g?_msm_ranges*: the prepared points, the chunk table, the partials, the off-curve counts and one slice's tables (k_smul_seg)
     B_FEXP_WS,           // the slots of k_fexp_team
     B_H2C_WS,            // the lane-private point slots of k_h2c_clear_pairs
-    B_FIX_WS,            // blsgpu_hd_children*: the parent key, a flag word and one slice of HMAC outputs
-    B_POLY_WS,           // blsgpu_g1_poly_check*: a flag word, the subgroup flags and the commitments in L28 form
-    B_LAGR_WS,           // blsgpu_threshold_combine* / blsgpu_fr_interpolate_at_zero*: groups x k coefficients (32 bytes each)
-    B_HDP_WS,            // blsgpu_hd_paths*: a flag word and one slice of per-path state (chain code, key / i_left, two affine keys)
-    B_SMUL_WS,           // blsgpu_g2_mul_secret* / blsgpu_sign*: one slice of H(m) points (sign) and of tables 1P .. 8P (k_g2_smul)
-    B_FRS_WS,            // blsgpu_sign_threshold*: the scalars lambda_i sk_i of a call and, with a message per session, one slice of H(m) copies
-    B_HPK_WS,            // blsgpu_hash_pks* / blsgpu_aggregate_*_secure*: groups digests (32 bytes each), then groups x m exponents (32 bytes each); the *_ranges forms: the head words, the digests, the exponents and the range table of the sums (secure_ranges_plan.h)
+    B_FIX_WS,            // blsgpu_hd_children*: the parent key, a flag word and one slice of HMAC outputs (keys_plan.h, ChildrenPlan)
+    B_POLY_WS,           // blsgpu_g1_poly_check*: a flag word, the subgroup flags and the commitments in L28 form (keys_plan.h, PolyPlan)
+    B_LAGR_WS,           // blsgpu_threshold_combine* / blsgpu_fr_interpolate_at_zero* / blsgpu_sign_threshold*: the coefficients of a call (keys_plan.h, coeff_bytes)
+    B_HDP_WS,            // blsgpu_hd_paths*: a flag word and one slice of per-path state (keys_plan.h, PathsPlan)
+    B_SMUL_WS,           // blsgpu_g2_mul_secret* / blsgpu_sign* / blsgpu_sign_threshold*: H(m) points and one slice of tables 1P .. 8P of k_g2_smul (keys_plan.h: smul_table_bytes, SignPlan, ThresholdPlan)
+    B_FRS_WS,            // blsgpu_sign_threshold*: the scalars lambda_i sk_i of a call and, with a message per session, one slice of H(m) copies (keys_plan.h, ThresholdPlan)
+    B_HPK_WS,            // blsgpu_hash_pks* / blsgpu_aggregate_*_secure*: the digests, then the exponents (secure_ranges_plan.h, FixedWorkspace); the *_ranges forms: the head words, the digests, the exponents and the range table of the sums (secure_ranges_plan.h, Workspace)
     B_SHR_WS,            // blsgpu_sig_shares_check*: what one slice of sessions keeps over its rounds -- a flag word, the subgroup flags, H(m), the scalars r and w, the key copies and the leaves A, B (every array, its writer and readers: find_plan.h, FIND_SHR_KEEP)
     B_SHR_ROUND,         // ... and what one round of it takes: the node table, the gathered leaves, the node sums, the pairs, the pairing results and the verdict bytes (find_plan.h, FIND_SHR_ROUND)
-    B_SEED_WS,           // blsgpu_keys_from_seeds*: one slice of the keys (32 bytes each) and of their affine public keys (96) where the caller does not ask for them
+    B_SEED_WS,           // blsgpu_keys_from_seeds*: one slice of the keys and of their affine public keys where the caller does not ask for them (keys_plan.h, SeedsPlan)
     B_SM64_WS,           // blsgpu_g1_mul_short* / blsgpu_g2_mul_short* and the leaves of blsgpu_verify_find*: the prepared points, their live flags and one launch's tables 0 .. 15 P (k_smul64)
     B_FIND_WS,           // blsgpu_verify_find* / blsgpu_verify_find_folded* (which adds the leaves in the dense order and the run table): what one slice of items keeps over its rounds -- a flag word, n_e, the subgroup flags, H(h), the weights, the dense order and the leaves A, B (find_plan.h, FIND_KEEP)
     B_FIND_ROUND,        // ... and what one round of it takes: the node offsets, the gathered leaves, the node sums, the pairs, the pairing results and the verdict bytes (find_plan.h: FIND_PLAIN_HEAD and FIND_PLAIN_PART, or FIND_FOLD_ROUND)

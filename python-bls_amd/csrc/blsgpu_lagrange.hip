@@ -27,15 +27,7 @@ namespace lagr {
 constexpr uint32_t MAX_K = BLSGPU_LAGRANGE_MAX_K;
 static_assert(MAX_K == 1024, "a group is one workgroup: at most 1024 threads");
 
-// the launch shape for groups of k points (1 <= k <= MAX_K)
-struct Shape { uint32_t threads, gpb; size_t lds; };
-inline Shape shape(uint32_t k) {
-    Shape s;
-    s.threads = k <= 256 ? 256u : (k + 63u) / 64u * 64u;
-    s.gpb = k <= 256 ? 256u / k : 1u;                                         // groups per workgroup
-    s.lds = ((size_t)s.gpb * k + s.gpb) * 32 + (size_t)s.gpb * 4;            // points / shifts, one den and one flag per group
-    return s;
-}
+// (the launch shape for groups of k points, 1 <= k <= MAX_K: keys::lagrange_shape, keys_plan.h)
 
 __global__ void __launch_bounds__(1024) k_lagrange(const uint8_t* __restrict__ x, uint32_t k, uint32_t groups, uint32_t gpb,
                                                    uint8_t* __restrict__ out, uint8_t* __restrict__ status)

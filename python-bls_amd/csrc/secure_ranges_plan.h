@@ -76,6 +76,26 @@ inline Workspace workspace(size_t groups, size_t n_exp, bool own_digests, bool o
     return w;
 }
 
+// ---- the fixed-shape forms (blsgpu_hash_pks*, blsgpu_aggregate_*_secure*): every group hashes k keys and owns m exponents.  Their
+// launches are grids(groups, groups * m)'s digest and exp.
+// "batch too large"; groups >= 1
+inline bool fixed_too_large(size_t k, size_t m, size_t groups) {
+    return groups > 0x7FFFFFFFull || m > 0xFFFFFFFFull || m * groups > 0xFFFFFFF0ull || k > (~(size_t)0 >> 6) / groups;
+}
+// ... and on top of it for blsgpu_aggregate_priv_keys_secure*, whose keys are k_fr_dot_secret's lanes
+inline bool fixed_priv_too_large(size_t k, size_t groups) { return k * groups > 0xFFFFFFF0ull; }
+// B_HPK_WS of a fixed-shape call (bytes): the digests | the exponents (m == 0: the caller's buffer takes them)
+struct FixedWorkspace { size_t digests, exps, total; };
+inline FixedWorkspace fixed_workspace(size_t m, size_t groups) {
+    ws::Layout l{256, 0};
+    FixedWorkspace w;
+    w.digests = l.take(groups * 32);
+    l.unit = 32;
+    w.exps = l.take(groups * m * 32);
+    w.total = l.off;
+    return w;
+}
+
 // ---- the host-buffer forms: staged slices on GROUP boundaries
 // items per slice: SLICE_ITEMS, or what the test hook BLSGPU_TEST_SLICE_CAP sets
 inline size_t slice_cap(const msm::Knobs& c) { return msm::slice_len(c, SLICE_ITEMS); }

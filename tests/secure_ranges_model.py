@@ -53,6 +53,21 @@ def workspace(groups, n_exp, own_digests, own_exps, pair_table):
     return head, digests, exps, pairs, pairs + up(8 * groups if pair_table else 0)
 
 
+def fixed_too_large(k, m, groups):
+    """the fixed-shape forms: every group hashes k keys and owns m exponents (groups >= 1)"""
+    return groups > 0x7FFFFFFF or m > 0xFFFFFFFF or m * groups > 0xFFFFFFF0 or k > (((1 << 64) - 1) >> 6) // groups
+
+
+def fixed_priv_too_large(k, groups):
+    return k * groups > 0xFFFFFFF0
+
+
+def fixed_workspace(m, groups):
+    """-> (digests, exps, total): the digests rounded up to 256 bytes, then groups x m exponents"""
+    dg_bytes = (groups * 32 + 255) // 256 * 256
+    return 0, dg_bytes, dg_bytes + groups * m * 32
+
+
 def cut(pk_off, exp_off, cap):
     """[(lo, hi)]: the rule in words -- walk the groups; a group joins the current slice when the slice's groups, keys and
     exponents all stay within the cap with it, and otherwise starts the next; a slice's first group is taken whatever its

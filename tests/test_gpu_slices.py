@@ -556,6 +556,37 @@ def test_hd_paths_public_private_and_secret_across_slices(engine, capped, paths_
     check_digest(sers, rec["esk"])
 
 
+def grown_by(fresh, call):
+    """what `call` adds to the workspace of `fresh` beside the staging of the host-buffer form"""
+    before = fresh.workspace_bytes()
+    got = call()
+    after = fresh.workspace_bytes()
+    return got, (after["total"] - before["total"]) - (after["staging"] - before["staging"])
+
+
+def test_hd_paths_workspace_holds_one_slice_of_path_state(engine):
+    """23 public paths of depth 3 in slices of five: B_HDP_WS holds the state of one slice (256 bytes a path), not of the call.
+    The fixed-base table counts in the total and is allocated apart: one multiplication warms the engine first.  The outputs: the
+    default engine's, which test_hd_paths_public_private_and_secret_across_slices holds against the host's on these inputs."""
+    import keys_plan_model as KP
+    from bls_py.keys import ExtendedPrivateKey
+    n, depth = 23, 3
+    rnd = random.Random("slices paths")
+    parents = b"".join(TPATH._record(ExtendedPrivateKey.from_seed(b"slices parent %d" % j)) for j in range(4))
+    parent_of = [rnd.randrange(4) for _ in range(n)]
+    paths = [[rnd.randrange(2**31) for _ in range(depth)] for _ in range(n)]
+    one, whole = KP.plan_paths(CAP, n, depth, False), KP.plan_paths(0, n, depth, False)
+    assert one["S"] == CAP and whole["S"] == n
+    fresh = engine_with_env({"BLSGPU_TEST_SLICE_CAP": str(CAP)})
+    try:
+        fresh.g1_mul_gen([1])
+        got, grown = grown_by(fresh, lambda: fresh.hd_paths(parents, False, parent_of, paths))
+        assert got == engine.hd_paths(parents, False, parent_of, paths)
+        assert CAP * 256 == one["bytes"] - one["o_chain"] <= grown < whole["bytes"] - whole["o_chain"] == n * 256
+    finally:
+        fresh.close()
+
+
 @pytest.mark.parametrize("mode", ["plain", "hd"])
 def test_keys_from_seeds_across_slices(capped, seeds_fx, seeds_drawn, mode):
     eng = capped(CAP)
@@ -642,6 +673,26 @@ def test_g2_mul_secret_and_sign_across_slices(engine, capped, sign_cases, sign_f
     d_sk, d_h = up(cat(same, "sk")), up(bytes.fromhex(same[0]["hash"]))
     eng.sign_dev(d_sk.data_ptr(), d_h.data_ptr(), 1, 23, d_aff.data_ptr(), d_ser.data_ptr(), 0)
     assert (down(d_aff), down(d_ser)) == (cat(same, "aff"), cat(same, "sig"))
+
+
+def test_sign_workspace_holds_one_slice_of_tables(sign_fixture):
+    """23 keys on 23 messages in slices of five: B_SMUL_WS holds the H(m) points and the tables of one slice -- at least five
+    tables, less than 23 slices' worth.  The hash to G2 has workspaces of its own: hashing one slice of messages warms the engine
+    first."""
+    import keys_plan_model as KP
+    recs = sign_fixture["cases"]
+    rep = [recs[i % len(recs)] for i in range(23)]
+    cat = lambda rs, k: b"".join(bytes.fromhex(r[k]) for r in rs)
+    one = KP.plan_sign(CAP, CAP, CAP)                                       # what a staged slice asks of blsgpu_sign_dev
+    assert one["held"] == CAP and KP.staged_slice(CAP, 23, KP.SMUL_SLICE) == CAP
+    fresh = engine_with_env({"BLSGPU_TEST_SLICE_CAP": str(CAP)})
+    try:
+        fresh.hash_to_g2(cat(rep[:CAP], "hash"))
+        got, grown = grown_by(fresh, lambda: fresh.sign(cat(rep, "sk"), cat(rep, "hash")))
+        assert got == (cat(rep, "aff"), cat(rep, "sig"))
+        assert CAP * KP.TABLE_DW * 4 == KP.smul_table_bytes(one["held"]) <= grown < 23 * KP.smul_table_bytes(one["held"])
+    finally:
+        fresh.close()
 
 
 @pytest.mark.parametrize("deg", [1, 2])

@@ -17,6 +17,7 @@ CSRC = os.path.join(ROOT, "python-bls_amd", "csrc")
 #   large n_keys n_exp groups                          -> 0 | 1
 #   grids groups n_exp                                 -> check digest exp
 #   ws groups n_exp own_digests own_exps pair_table    -> head digests exps pairs total
+#   fixed k m groups                                   -> too large, too large for the private keys, digests exps total
 #   cap test_slice_cap                                 -> items per slice
 #   validate count groups off[groups + 1]              -> verdict where
 #   cut test_slice_cap has_pk groups [pk_off[groups + 1]] exp_off[groups + 1]
@@ -46,6 +47,11 @@ int main() {
             in >> groups >> n_exp >> a >> b >> c;
             const sr::Workspace w = sr::workspace(groups, n_exp, a != 0, b != 0, c != 0);
             printf("%zu %zu %zu %zu %zu\n", w.head, w.digests, w.exps, w.pairs, w.total);
+        } else if (op == "fixed") {
+            size_t k, m, groups;
+            in >> k >> m >> groups;
+            const sr::FixedWorkspace w = sr::fixed_workspace(m, groups);
+            printf("%d %d %zu %zu %zu\n", sr::fixed_too_large(k, m, groups) ? 1 : 0, sr::fixed_priv_too_large(k, groups) ? 1 : 0, w.digests, w.exps, w.total);
         } else if (op == "cap") {
             msm::Knobs k;
             in >> k.test_slice_cap;
@@ -95,6 +101,12 @@ LARGE = [(0, 0, 0), (B31 - 1, B31 - 1, B30 - 1), (B31, 0, 1), (0, B31, 1), (B31 
 GRIDS = [(0, 0), (1, 0), (1, 1), (64, 256), (65, 257), (255, 511), (256, 512), (257, 513), (70, 1000)]
 WS = [(g, x, a, b, c) for g, x in ((1, 0), (8, 8), (9, 7), (65, 400), (70, 0)) for a, b, c in ((0, 0, 0), (1, 0, 0), (1, 1, 1), (0, 1, 1))]
 CAPS = [0, 1, 3, 64, 1 << 18, 1 << 19]
+# the fixed-shape forms (k keys, m exponents a group): layouts with 7, 8 and 9 digests (256 bytes are eight) and without
+# exponents of its own (m = 0: blsgpu_hash_pks_dev), and on every term of the bound the last value taken and the first refused
+K58 = ((1 << 64) - 1) >> 6
+FIXED = [(1, 0, 1), (3, 3, 7), (3, 3, 8), (67, 67, 9), (2, 5, 1000), (1, 1, B31 - 1), (1, 1, B31), (1, (1 << 32) - 1, 1), (1, 1 << 32, 1),
+         (1, 2, 0x7FFFFFF8), (1, 2, 0x7FFFFFF9), (K58 // 3, 1, 3), (K58 // 3 + 1, 1, 3), (1024, 1024, 4194303), (1024, 1024, 4194304),
+         (2, 1, 0x7FFFFFF8), (2, 1, 0x7FFFFFF9)]
 
 # (offsets, count) the header takes ...
 GOOD = [([0, 0], 0), ([0, 5], 5), ([0, 5], 9), ([0, 0, 0, 0], 0), ([0, 1, 1, 70, 200], 200), ([0, B31 - 1], B31 - 1), ([0, 3, 3, 3, 10], 11)]
@@ -155,7 +167,7 @@ CUTS = cut_cases()
 def case_lines():
     j = lambda v: " ".join(map(str, v))
     lines = ["large %d %d %d" % v for v in LARGE] + ["grids %d %d" % v for v in GRIDS] + ["ws %d %d %d %d %d" % w for w in WS]
-    lines += ["cap %d" % c for c in CAPS]
+    lines += ["fixed %d %d %d" % v for v in FIXED] + ["cap %d" % c for c in CAPS]
     lines += ["validate %d %d %s" % (count, len(off) - 1, j(off)) for off, count in VALIDATE] + ["validate 9 0"]
     lines += ["cut %d %d %d %s %s" % (cap, pk is not None, len(ex) - 1, j(pk or []), j(ex)) for cap, pk, ex in CUTS]
     return "\n".join(lines) + "\n"
@@ -185,6 +197,8 @@ def test_against_the_model(out):
         assert tuple(ints(next(out))) == M.grids(*v)
     for g, x, a, b, c in WS:
         assert tuple(ints(next(out))) == M.workspace(g, x, bool(a), bool(b), bool(c))
+    for k, m, g in FIXED:
+        assert tuple(ints(next(out))) == (int(M.fixed_too_large(k, m, g)), int(M.fixed_priv_too_large(k, g))) + M.fixed_workspace(m, g), (k, m, g)
     for c in CAPS:
         assert int(next(out)) == M.slice_len(c, M.SLICE_ITEMS)
     for off, count in VALIDATE:
@@ -231,6 +245,12 @@ def test_the_model_alone():
     assert len(M.cut(M.offsets(lens), M.offsets(lens), 1)) == 70                          # cap 1: a group a slice, the empty ones too
     assert M.cut(M.offsets([2, 1, 0, 3]), M.offsets([2, 1, 0, 3]), 3) == [(0, 3), (3, 4)]
     assert M.workspace(65, 400, True, True, True) == (0, 256, 256 + 2304, 256 + 2304 + 12800, 256 + 2304 + 12800 + 768)
+    # (the bound on m alone never decides: m x groups passes 0xFFFFFFF0 first -- both values around 2^32 are refused)
+    assert [M.fixed_too_large(*v) for v in FIXED] == [False] * 6 + [True, True, True, False, True, False, True, False, True, False, False]
+    assert [M.fixed_priv_too_large(k, g) for k, _, g in FIXED[-4:]] == [False, True, False, True]
+    assert M.fixed_workspace(3, 7) == (0, 256, 256 + 672) and M.fixed_workspace(67, 9) == (0, 512, 512 + 9 * 67 * 32) and M.fixed_workspace(0, 1) == (0, 256, 256)
+    # the fixed-shape launches are the ragged grids over groups x m exponents
+    assert M.grids(9, 9 * 67) == (1, 1, 3)
     import hashlib
     dg, ts = M.hash_pks_ranges(b"", [0, 0], [0, 1])
     assert dg == hashlib.sha256(b"").digest() and int.from_bytes(ts, "big") == int.from_bytes(hashlib.sha256(bytes(4) + dg).digest(), "big") % M.N

@@ -25,4 +25,4 @@ for entry in re.split(r"\n\s*- (?=\.)", filt):
     if sys.argv[1:] and not any(k in n for k in sys.argv[1:]):
         continue
     g = lambda k: (re.search(k + r":\s+(\d+)", b) or [0, "-"])[1]
-    print("%-90s vgpr %4s agpr %3s scratch %5s spills %4s lds %6s" % (n[:90], g(r"\.vgpr_count"), g(r"\.agpr_count"), g(r"\.private_segment_fixed_size"), g(r"\.vgpr_spill_count"), g(r"\.group_segment_fixed_size")))
+    print("%-90s vgpr %4s agpr %3s sgpr %3s scratch %5s spills %4s lds %6s" % (n[:90], g(r"\.vgpr_count"), g(r"\.agpr_count"), g(r"\.sgpr_count"), g(r"\.private_segment_fixed_size"), g(r"\.vgpr_spill_count"), g(r"\.group_segment_fixed_size")))
